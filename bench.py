@@ -4,6 +4,8 @@
 One "step" = one tahoe_forest_predict over one resident batch (BASELINE.json config 3, "K3": synthetic
 forest of 1000 trees of depth 12 over 256 features, 1M rows, float32).  Inputs and the forest are
 resident in HBM before the timed region (as in the reference, BaseTahoeTest.h:563-573).
+--dump-outputs DIR writes the predictions of the last timed step (float32 .npy); the inputs are seeded, so two builds run
+with the same arguments can be compared output for output.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
@@ -43,6 +45,22 @@ HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md, chip-leve
 MISSING = -999.0
 PROFILE_ROUND = "r04"
 PROFILE_DIR = os.path.join(ROOT, "profiles", PROFILE_ROUND)
+MAX_PROFILED_LAUNCHES = 4096  # what tahoe_forest_set_profiling accepts
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs writes at most this much
+
+
+def dump_outputs(out_dir, name, values, limit_bytes):
+    """--dump-outputs: `values` as out_dir/<name>.npy in float32.  Past `limit_bytes` (with the index) an evenly spaced sample
+    of the entries is written instead, their positions beside it as <name>_index.npy (float64), so that two runs with the same
+    arguments compare entry for entry."""
+    os.makedirs(out_dir, exist_ok=True)
+    values = np.ascontiguousarray(values, dtype=np.float32).ravel()
+    if values.nbytes > limit_bytes:
+        keep = limit_bytes // (values.itemsize + 8)
+        index = np.arange(keep, dtype=np.int64) * values.size // keep
+        np.save(os.path.join(out_dir, name + "_index.npy"), index.astype(np.float64))
+        values = values[index]
+    np.save(os.path.join(out_dir, name + ".npy"), values)
 
 
 def algorithmic_bytes_per_sample(T, depth, cols, bits_bytes):
@@ -361,7 +379,11 @@ def main():
                     help="N > 1: also time the chained (bit-exact, point-to-point) tree shards of K4; off by default because a stuck "
                          "send/recv would take the process group -- and the primary line -- down with it")
     ap.add_argument("--k4-sample", type=int, default=2048, help="rows of the K4 legs checked against the float64 CPU sum")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the predictions of the last one as DIR/<name>.npy (float32, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
 
@@ -515,7 +537,8 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    forest.set_profiling(args.steps if not (tree_sharded and args.tree_mode == "chain") else 0)
+    # kernel events cover the first MAX_PROFILED_LAUNCHES steps; the wall time covers all of them
+    forest.set_profiling(min(args.steps, MAX_PROFILED_LAUNCHES) if not (tree_sharded and args.tree_mode == "chain") else 0)
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -532,6 +555,12 @@ def main():
     kernel_ms = forest.kernel_times_ms()
     prepass_ms = forest.prepass_times_ms()
     forest.set_profiling(0)
+    if args.dump_outputs:
+        # what a caller of the timed path receives: this rank's rows, or a tree-sharded result once, from a rank that holds it
+        if not tree_sharded:
+            dump_outputs(args.dump_outputs, "preds" if world == 1 else f"preds_rank{rank}", preds.cpu().numpy(), DUMP_LIMIT_BYTES // world)
+        elif rank == (world - 1 if args.tree_mode == "chain" else 0):
+            dump_outputs(args.dump_outputs, "preds", preds.cpu().numpy(), DUMP_LIMIT_BYTES)
 
     ms_per_step = dt / args.steps * 1e3
     total_rows = R * world if weak else R

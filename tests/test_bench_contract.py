@@ -102,7 +102,7 @@ def test_committed_pmc_profile_belongs_to_these_kernel_sources():
     assert phys["quantise"]["hbm_frac_compulsory"] < 0.5  # the kernel furthest from its HBM roofline, said so
 
 
-def test_walk_ceiling_and_config_roofline_arithmetic():
+def test_walk_ceiling_and_config_roofline_arithmetic(built):
     """bench.py's host-side arithmetic without a GPU: the <= 1 fraction (here the live micro-benchmark cannot run, so the committed
     figure serves and says so), the per-configuration byte model on a hand example, and the workloads of the `configs` legs."""
     import sys
@@ -146,3 +146,26 @@ def test_every_stamped_profile_of_the_round_belongs_to_these_sources():
     assert line["roofline"]["kernel_source_hash"] == want
     for k in ("K1", "K2", "K5", "KR3"):
         assert line["configs"][k]["roofline"]["counters"]["src_hash"] == want, k
+
+
+def test_dump_outputs_keeps_to_its_limit(tmp_path):
+    """bench.dump_outputs (--dump-outputs): float32 as is below the limit; above it an evenly spaced sample of the entries with
+    their positions (float64) beside it, the same on every run."""
+    import sys
+
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    values = np.arange(1000, dtype=np.float64) * 0.5
+    bench.dump_outputs(str(tmp_path / "all"), "preds", values, 4000)
+    got = np.load(tmp_path / "all" / "preds.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, values.astype(np.float32))
+    assert sorted(os.listdir(tmp_path / "all")) == ["preds.npy"]
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), "preds", values, 1200)
+    a, ia = np.load(tmp_path / "a" / "preds.npy"), np.load(tmp_path / "a" / "preds_index.npy")
+    assert a.dtype == np.float32 and ia.dtype == np.float64 and a.size == ia.size == 100 and a.nbytes + ia.nbytes <= 1200
+    assert np.array_equal(a, values[ia.astype(np.int64)].astype(np.float32)) and ia[0] == 0 and ia[-1] == 990
+    assert np.array_equal(a, np.load(tmp_path / "b" / "preds.npy")) and np.array_equal(ia, np.load(tmp_path / "b" / "preds_index.npy"))

@@ -96,6 +96,36 @@ def test_two_ranks_tree_shards_chained_bit_exact():
     assert ch["bit_identical_to_cpu_f32"] is True and "error" not in ch
 
 
+def test_dump_outputs_of_the_last_timed_step(built, tmp_path):
+    """--dump-outputs DIR: the float32 predictions of the last timed step, bit-exact against the CPU oracle on the seeded inputs;
+    the two row shards of a two-rank run put back together are the one-rank dump.  --steps above the 4096 launches the kernel
+    events can hold still sets the number of timed steps."""
+    import numpy as np
+
+    import tahoe_amd as ta
+    from oracle import oracle
+
+    one = tmp_path / "one"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--trees", "100", "--rows", "40000", "--steps", "4100",
+                        "--warmup", "1", "--no-cpu", "--no-host", "--no-k4", "--dump-outputs", str(one)],
+                       capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 4100 and line["ms_per_step"] > 0
+    assert sorted(os.listdir(one)) == ["preds.npy"]
+    preds = np.load(one / "preds.npy")
+    assert preds.dtype == np.float32 and preds.shape == (40000,)
+    n = 2048
+    want, _ = oracle.predict(ta.synth_forest(100, 12, 256, seed=42), 100, 12, ta.synth_data(n, 256, seed=43), -999.0, threads=1)
+    assert np.array_equal(preds[:n].view(np.uint32), want.view(np.uint32))
+
+    two = tmp_path / "two"
+    run_bench(["--trees", "100", "--dump-outputs", str(two)])
+    assert sorted(os.listdir(two)) == ["preds_rank0.npy", "preds_rank1.npy"]
+    both = np.concatenate([np.load(two / "preds_rank0.npy"), np.load(two / "preds_rank1.npy")])
+    assert np.array_equal(both.view(np.uint32), preds.view(np.uint32))
+
+
 def test_one_rank_line_carries_the_same_scaling_label():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rows", "40000", "--steps", "2", "--warmup", "1", "--no-cpu",
                         "--no-host", "--no-k4"], capture_output=True, text=True, timeout=300, cwd=ROOT)
