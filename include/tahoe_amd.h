@@ -88,6 +88,9 @@ enum { TAHOE_ALGO_NAIVE = 0, TAHOE_ALGO_TREE_REORG = 1, TAHOE_ALGO_BATCH_TREE_RE
 enum { TAHOE_FIL_SHARED_DATA = 0, TAHOE_FIL_SHARED_FOREST = 1, TAHOE_FIL_SPLIT_FOREST = 2,
        TAHOE_FIL_SPLIT_FOREST_SHARED_DATA = 3 };
 enum { TAHOE_OUT_RAW = 0x0, TAHOE_OUT_AVG = 0x1, TAHOE_OUT_SIGMOID = 0x10, TAHOE_OUT_THRESHOLD = 0x100 };
+/* Row-wise softmax over the classes of a multi-class handle (tahoe_forest_create_multiclass); no counterpart in the
+ * reference.  tahoe_forest_create / _create_ex reject it. */
+#define TAHOE_OUT_SOFTMAX 0x1000
 
 /* forest_params_t, Struct.h:166-189 (same fields, same order). */
 typedef struct {
@@ -176,6 +179,28 @@ tahoe_status tahoe_forest_create_ex(tahoe_forest **out, const tahoe_dense_node *
                                     const tahoe_forest_params *params, unsigned flags);
 void tahoe_forest_destroy(tahoe_forest *f);
 
+/* Multi-class forests (XGBoost multi:softprob / multi:softmax, LightGBM multiclass: one tree per class per boosting round).
+ * Tree t of the num_trees trees belongs to class t % num_classes; num_trees must be a multiple of num_classes, each class then
+ * has Tc = num_trees / num_classes trees.  A predict writes rows x num_classes values, row-major: margin[row][c] = the float32
+ * sum of class c's leaf values added from 0.0f in increasing tree order -- bit for bit what predict_on_cpu gives on the
+ * sub-forest of trees c, c + C, c + 2C, ...  Output bits, applied per element in this order: AVG divides by (float)Tc,
+ * global_bias is added to every class (XGBoost's base_score), SIGMOID per element (LightGBM multiclassova), then
+ * TAHOE_OUT_SOFTMAX: m = max_c z_c, e_c = expf(z_c - m), p_c = e_c / sum_c e_c (sum in class order).  THRESHOLD with
+ * num_classes > 1, SOFTMAX with SIGMOID and SOFTMAX with num_classes == 1 are TAHOE_ERR_INVALID_ARG.  num_classes must be in
+ * [1, 1024]; every argument is checked before a device is touched.  `flags` as for tahoe_forest_create_ex.
+ * num_classes == 1 gives a handle that behaves exactly like tahoe_forest_create_ex.
+ * The trees are stored class-major (class c's trees contiguous, in their relative order), so one walk over all trees
+ * serves every class and QRING's quantise pass runs once per predict.  On a multi-class handle:
+ *   - tahoe_forest_predict, _predict_raw and the sums of _predict_leaf_idx write rows x num_classes values; leaf indices
+ *     stay leaf_dev[row * num_trees + tree] in the caller's tree numbering and the original heap numbering;
+ *   - reserve (and HIP graph capture after it), set/get_strategy, get_kernel_form, get_info, profiling and check work
+ *     unchanged.  Strategies served: AUTO, DIRECT, ROWTILE, QRING; TILEBLOCK and TILERING are TAHOE_ERR_UNSUPPORTED;
+ *   - tahoe_forest_predict_accumulate and tahoe_forest_predict_host return TAHOE_ERR_UNSUPPORTED and launch nothing. */
+tahoe_status tahoe_forest_create_multiclass(tahoe_forest **out, const tahoe_dense_node *nodes,
+                                            const tahoe_forest_params *params, int num_classes, unsigned flags);
+/* Classes of the handle: num_classes of tahoe_forest_create_multiclass, 1 for every other handle (sparse included), 0 for NULL. */
+int tahoe_forest_num_classes(const tahoe_forest *f);
+
 /* ---- sparse (irregular) forests: sparse_node_t Struct.h:50-54, sparse_storage Struct.h:343-354,
  * init_sparse / sparse_forest::init (BaseTahoeTest.h:766-772, Struct.h:2329-2343) ---- */
 typedef struct {
@@ -202,7 +227,8 @@ tahoe_status tahoe_synth_sparse_forest(tahoe_sparse_node *nodes, int32_t *trees,
                                        int num_cols, int min_depth, int max_depth, float leaf_prob,
                                        int max_tree_nodes, uint64_t seed);
 
-/* preds_dev[rows] <- per-row float32 sum of leaf values in tree order 0..T-1 (the order of
+/* (Multi-class handles: rows x num_classes values, see tahoe_forest_create_multiclass.)
+ * preds_dev[rows] <- per-row float32 sum of leaf values in tree order 0..T-1 (the order of
  * predict_on_cpu, BaseTahoeTest.h:462-466), then AVG / bias / sigmoid / threshold as
  * forest::predict + transform_k do (Struct.h:196-209, :263-268).  data_dev is row-major
  * rows x num_cols float32 (data_d of generate_data_from_file, BaseTahoeTest.h:378-392). */
@@ -217,12 +243,14 @@ tahoe_status tahoe_forest_predict_raw(tahoe_forest *f, float *sums_dev, const fl
  * that come BEFORE this forest's trees in the whole ensemble; on return, those sums continued through this forest's
  * trees in tree order.  Shard k called on shard k-1's output therefore reproduces the single sequential float32 sum of
  * predict_on_cpu (BaseTahoeTest.h:462-466) bit for bit, which an all-reduce of per-shard totals cannot.  Every
- * strategy supports it (the kernels start their per-row accumulator from sums_dev[row] instead of 0.0f). */
+ * strategy supports it (the kernels start their per-row accumulator from sums_dev[row] instead of 0.0f).
+ * TAHOE_ERR_UNSUPPORTED on a multi-class handle. */
 tahoe_status tahoe_forest_predict_accumulate(tahoe_forest *f, float *sums_dev, const float *data_dev, size_t rows,
                                              void *stream);
 
 /* leaf_dev[row * num_trees + tree] <- index of the leaf the row ends in, in the tree's original heap
- * numbering (final `curr` of infer_one_tree, BaseTahoeTest.h:441-455).  sums_dev may be NULL. */
+ * numbering (final `curr` of infer_one_tree, BaseTahoeTest.h:441-455).  sums_dev may be NULL (else rows x num_classes
+ * raw sums on a multi-class handle). */
 tahoe_status tahoe_forest_predict_leaf_idx(tahoe_forest *f, uint32_t *leaf_dev, float *sums_dev,
                                            const float *data_dev, size_t rows, void *stream);
 
@@ -244,7 +272,7 @@ tahoe_status tahoe_forest_check(tahoe_forest *f, void *stream);
 tahoe_status tahoe_forest_reserve(tahoe_forest *f, size_t rows);
 
 /* Host-resident batch (the reference uploads the data file once, BaseTahoeTest.h:378-389, and
- * has no per-batch host path).  Rows are uploaded in chunks of `chunk_rows` rows (0 = about 32 MiB of rows)
+ * has no per-batch host path; TAHOE_ERR_UNSUPPORTED on a multi-class handle).  Rows are uploaded in chunks of `chunk_rows` rows (0 = about 32 MiB of rows)
  * through two device buffers; the upload of chunk i+1 overlaps the traversal of chunk i and the download of
  * chunk i-1's predictions.  A pinned source (hipHostMalloc / hipHostRegister) is copied from directly,
  * pageable memory is staged through pinned buffers by a few host threads.  Synchronous: preds_host is

@@ -26,6 +26,7 @@ from .capi import (  # noqa: F401
     OUT_AVG,
     OUT_SIGMOID,
     OUT_THRESHOLD,
+    OUT_SOFTMAX,
     STRATEGY_AUTO,
     STRATEGY_DIRECT,
     STRATEGY_ROWTILE,

@@ -32,6 +32,7 @@ lib = C.CDLL(LIB_PATH)
 
 # ---- constants mirrored from the header ----
 OUT_RAW, OUT_AVG, OUT_SIGMOID, OUT_THRESHOLD = 0x0, 0x1, 0x10, 0x100
+OUT_SOFTMAX = 0x1000  # multi-class handles only (tahoe_forest_create_multiclass)
 STRATEGY_AUTO, STRATEGY_DIRECT, STRATEGY_ROWTILE, STRATEGY_TILEBLOCK, STRATEGY_TILERING, STRATEGY_QRING = range(6)
 CREATE_PROB_RELAYOUT = 0x1
 STRATEGY_NAMES = {1: "direct", 2: "rowtile", 3: "tileblock", 4: "tilering", 5: "qring"}
@@ -118,6 +119,8 @@ _PROTOS = {
     "tahoe_forest_create": (_i, [C.POINTER(_vp), _vp, C.POINTER(ForestParams)]),
     "tahoe_forest_create_ex": (_i, [C.POINTER(_vp), _vp, C.POINTER(ForestParams), C.c_uint]),
     "tahoe_forest_destroy": (None, [_vp]),
+    "tahoe_forest_create_multiclass": (_i, [C.POINTER(_vp), _vp, C.POINTER(ForestParams), _i, C.c_uint]),
+    "tahoe_forest_num_classes": (_i, [_vp]),
     "tahoe_sparse_forest_create": (_i, [C.POINTER(_vp), _vp, _vp, C.POINTER(ForestParams)]),
     "tahoe_dense_to_sparse": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz)]),
     "tahoe_synth_sparse_forest": (_i, [_vp, _vp, C.POINTER(_sz), _i, _i, _i, _i, _f, _i, C.c_uint64]),
@@ -364,24 +367,35 @@ class Forest:
     """Handle on a device forest: tahoe_forest_create / predict / destroy.
 
     Mirrors the reference's init_dense* + predict_dense* pair (BaseTahoeTest.h:519-547, :599-611).
-    Tensors are torch CUDA tensors (float32 data [rows, cols] contiguous, float32 preds [rows])."""
+    Tensors are torch CUDA tensors (float32 data [rows, cols] contiguous, float32 preds [rows]).
+    num_classes > 1 (tahoe_forest_create_multiclass): tree t belongs to class t % num_classes, predict / predict_raw
+    return [rows, num_classes] and predict_leaf_idx [rows, num_trees] leaves with [rows, num_classes] sums."""
 
     def __init__(self, nodes: np.ndarray, num_trees: int, depth: int, num_cols: int, missing: float = 0.0,
                  output: int = OUT_RAW, threshold: float = 0.0, global_bias: float = 0.0, algo: int = 0,
-                 strategy: int = 0, relayout: bool = False):
+                 strategy: int = 0, relayout: bool = False, num_classes: int = 1):
         nodes = np.ascontiguousarray(nodes, dtype=NODE_DTYPE)
         if nodes.size != num_trees * tree_num_nodes(depth):
             raise ValueError("nodes.size != num_trees * tree_num_nodes(depth)")
         self.params = ForestParams(0, depth, num_trees, num_cols, algo, output, threshold, global_bias, strategy,
                                    missing)
         self._h = _vp()
-        if relayout:  # TAHOE_CREATE_PROB_RELAYOUT: subtrees ordered by dense_node_t.weight (Struct.h:1775-1825)
+        if num_classes != 1:
+            _check(lib.tahoe_forest_create_multiclass(C.byref(self._h), nodes.ctypes.data if nodes.size else None,
+                                                      C.byref(self.params), num_classes,
+                                                      CREATE_PROB_RELAYOUT if relayout else 0),
+                   "tahoe_forest_create_multiclass")
+        elif relayout:  # TAHOE_CREATE_PROB_RELAYOUT: subtrees ordered by dense_node_t.weight (Struct.h:1775-1825)
             _check(lib.tahoe_forest_create_ex(C.byref(self._h), nodes.ctypes.data if nodes.size else None,
                                               C.byref(self.params), CREATE_PROB_RELAYOUT), "tahoe_forest_create_ex")
         else:
             _check(lib.tahoe_forest_create(C.byref(self._h), nodes.ctypes.data if nodes.size else None,
                                            C.byref(self.params)), "tahoe_forest_create")
         self.num_trees, self.depth, self.num_cols = num_trees, depth, num_cols
+        self.num_classes = lib.tahoe_forest_num_classes(self._h)
+
+    def _out_shape(self, rows: int):
+        return (rows, self.num_classes) if self.num_classes > 1 else (rows,)
 
     def close(self) -> None:
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -400,7 +414,7 @@ class Forest:
         self._check_data(data)
         rows = data.shape[0]
         if preds is None:
-            preds = torch.empty(rows, dtype=torch.float32, device=data.device)
+            preds = torch.empty(self._out_shape(rows), dtype=torch.float32, device=data.device)
         _check(lib.tahoe_forest_predict(self._h, _ptr(preds), _ptr(data), rows, _stream(stream)),
                "tahoe_forest_predict")
         return preds
@@ -411,7 +425,7 @@ class Forest:
         self._check_data(data)
         rows = data.shape[0]
         if sums is None:
-            sums = torch.empty(rows, dtype=torch.float32, device=data.device)
+            sums = torch.empty(self._out_shape(rows), dtype=torch.float32, device=data.device)
         _check(lib.tahoe_forest_predict_raw(self._h, _ptr(sums), _ptr(data), rows, _stream(stream)),
                "tahoe_forest_predict_raw")
         return sums
@@ -432,7 +446,7 @@ class Forest:
         self._check_data(data)
         rows = data.shape[0]
         leaf = torch.empty((rows, self.num_trees), dtype=torch.int32, device=data.device)
-        sums = torch.empty(rows, dtype=torch.float32, device=data.device) if want_sums else None
+        sums = torch.empty(self._out_shape(rows), dtype=torch.float32, device=data.device) if want_sums else None
         _check(lib.tahoe_forest_predict_leaf_idx(self._h, _ptr(leaf), _ptr(sums) if want_sums else None,
                                                  _ptr(data), rows, _stream(stream)),
                "tahoe_forest_predict_leaf_idx")
@@ -540,6 +554,7 @@ class SparseForest(Forest):
                                               nodes.ctypes.data if nodes.size else None, C.byref(self.params)),
                "tahoe_sparse_forest_create")
         self.num_trees, self.depth, self.num_cols = int(trees.size), 0, num_cols
+        self.num_classes = 1
 
 
 def transform_preds(preds, output: int, num_trees_total: int, threshold: float, global_bias: float, stream=None):

@@ -48,13 +48,15 @@ __device__ __forceinline__ uint32_t step(uint32_t idx, float thr, uint32_t meta,
 // ------------------------------------------------------------------------------------------------
 // DIRECT: lane = row; nodes and features come straight from global memory.  Works for any shape.
 // Analogue of infer_adaptive_reorg_* (Struct.h:1196-1240).
-template <bool WRITE_LEAF>
+// MC (multi-class handle, trees class-major): the sum is stored to sums[row * num_classes + c] at the end of class c's
+// trees and restarts from 0.0f; leaf indices go to the original tree's column.
+template <bool WRITE_LEAF, bool MC = false>
 __global__ void __launch_bounds__(kBlock) direct_kernel(const InnerNode *__restrict__ inner,
                                                         const float *__restrict__ leaf_val,
                                                         const uint32_t *__restrict__ leaf_orig,
                                                         const float *__restrict__ data, float *sums,
                                                         uint32_t *__restrict__ leaf_out, const float *sums_in, size_t rows, int cols,
-                                                        int num_trees, int depth, float missing)
+                                                        int num_trees, int depth, float missing, int num_classes)
 {
     const size_t row = (size_t)blockIdx.x * kBlock + threadIdx.x;
     if (row >= rows) return;
@@ -62,6 +64,8 @@ __global__ void __launch_bounds__(kBlock) direct_kernel(const InnerNode *__restr
     const size_t n_inner = ((size_t)1 << depth) - 1;
     const size_t n_leaf = (size_t)1 << depth;
     float sum = sums_in ? sums_in[row] : 0.0f;  // continues a running sum (tree shards chained in order)
+    const int ctrees = MC ? num_trees / num_classes : 0;
+    int cls = 0, cend = ctrees;  // MC: class of tree t and the end of its trees
     for (int t = 0; t < num_trees; ++t) {
         const InnerNode *tree = inner + (size_t)t * n_inner;
         uint32_t idx = 0;
@@ -71,9 +75,15 @@ __global__ void __launch_bounds__(kBlock) direct_kernel(const InnerNode *__restr
         }
         const size_t b = (size_t)t * n_leaf + (idx - (uint32_t)n_inner);
         sum += leaf_val[b];
-        if (WRITE_LEAF) leaf_out[row * (size_t)num_trees + t] = leaf_orig[b];
+        if (WRITE_LEAF) leaf_out[MC ? row * (size_t)num_trees + (t - cls * ctrees) * num_classes + cls : row * (size_t)num_trees + t] = leaf_orig[b];
+        if (MC && t + 1 == cend) {
+            if (sums) sums[row * (size_t)num_classes + cls] = sum;
+            sum = 0.0f;
+            ++cls;
+            cend += ctrees;
+        }
     }
-    if (sums) sums[row] = sum;
+    if (!MC && sums) sums[row] = sum;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -85,14 +95,15 @@ __global__ void __launch_bounds__(kBlock) direct_kernel(const InnerNode *__restr
 // added by the row's owner lane in tree order.  Any num_cols whose 64-row tile fits LDS.
 //
 // Dynamic LDS: [cols][64] float | kWaves slots of slot_nodes InnerNode | [2][kWaves][64] float.
-template <bool WRITE_LEAF>
+// MC: the owner lane stores its sum at the end of every class (direct_kernel).
+template <bool WRITE_LEAF, bool MC = false>
 __global__ void __launch_bounds__(kBlock) rowtile_kernel(const InnerNode *__restrict__ inner,
                                                          const float *__restrict__ leaf_val,
                                                          const uint32_t *__restrict__ leaf_orig,
                                                          const float *__restrict__ data, float *sums,
                                                          uint32_t *__restrict__ leaf_out, const float *sums_in, size_t rows, int cols,
                                                          int num_trees, int depth, int lds_levels, float missing,
-                                                         int vec4_ok)
+                                                         int vec4_ok, int num_classes)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
@@ -154,6 +165,8 @@ __global__ void __launch_bounds__(kBlock) rowtile_kernel(const InnerNode *__rest
 
     float sum = 0.0f;  // meaningful in lanes 0..15: row 16*wave + lane of the tile
     if (sums_in && lane < 16 && row0 + 16 * wave + lane < rows) sum = sums_in[row0 + 16 * wave + lane];
+    const int ctrees = MC ? num_trees / num_classes : 0;
+    int cls = 0, cend = ctrees;  // MC: class being summed and the end of its trees
     const int rounds = (num_trees + kWaves - 1) / kWaves;
     for (int r = 0; r < rounds; ++r) {
         const int t = r * kWaves + wave;
@@ -176,7 +189,8 @@ __global__ void __launch_bounds__(kBlock) rowtile_kernel(const InnerNode *__rest
             const size_t b = (size_t)t * n_leaf + (idx - (uint32_t)n_inner);
             v = leaf_val[b];
             if (WRITE_LEAF) {
-                if (row_ok) leaf_out[row * (size_t)num_trees + t] = leaf_orig[b];
+                if (row_ok)
+                    leaf_out[MC ? row * (size_t)num_trees + mc_orig_tree(t, num_classes, num_trees / num_classes) : row * (size_t)num_trees + t] = leaf_orig[b];
             }
             if (more) commit_top();  // this wave's reads of the slot are done (in-order LDS)
         }
@@ -186,10 +200,23 @@ __global__ void __launch_bounds__(kBlock) rowtile_kernel(const InnerNode *__rest
         if (lane < 16) {
             const int rr = 16 * wave + lane;
             const int nt = min(kWaves, num_trees - r * kWaves);
-            for (int j = 0; j < nt; ++j) sum += vb[j * kTileRows + rr];  // tree order
+            if (MC) {
+                const size_t orow = row0 + rr;
+                for (int j = 0; j < nt; ++j) {
+                    sum += vb[j * kTileRows + rr];  // tree order
+                    if (r * kWaves + j + 1 == cend) {
+                        if (sums && orow < rows) sums[orow * (size_t)num_classes + cls] = sum;
+                        sum = 0.0f;
+                        ++cls;
+                        cend += ctrees;
+                    }
+                }
+            } else {
+                for (int j = 0; j < nt; ++j) sum += vb[j * kTileRows + rr];  // tree order
+            }
         }
     }
-    if (sums && lane < 16) {
+    if (!MC && sums && lane < 16) {
         const size_t orow = row0 + 16 * wave + lane;
         if (orow < rows) sums[orow] = sum;
     }
@@ -648,6 +675,33 @@ __global__ void transform_kernel(float *preds, size_t n, int output, int num_tre
     preds[i] = r;
 }
 
+// Epilogue of a multi-class handle, one thread per row of preds[rows][num_classes]: per element AVG (by the trees of a
+// class), bias and sigmoid with transform_kernel's arithmetic, then the row-wise softmax m = max z, e = expf(z - m),
+// p = e / sum(e) with the sum taken in class order.
+__global__ void transform_mc_kernel(float *preds, size_t rows, int num_classes, int output, int class_trees, float global_bias)
+{
+    const size_t row = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= rows) return;
+    float *p = preds + row * (size_t)num_classes;
+    float m = -INFINITY;
+    for (int c = 0; c < num_classes; ++c) {
+        float r = p[c];
+        if ((output & TAHOE_OUT_AVG) != 0) r = r / (float)class_trees;
+        r += global_bias;
+        if ((output & TAHOE_OUT_SIGMOID) != 0) r = 1.0f / (1.0f + expf(-r));
+        p[c] = r;
+        m = fmaxf(m, r);
+    }
+    if ((output & TAHOE_OUT_SOFTMAX) == 0) return;
+    float s = 0.0f;
+    for (int c = 0; c < num_classes; ++c) {
+        const float e = expf(p[c] - m);
+        p[c] = e;
+        s += e;
+    }
+    for (int c = 0; c < num_classes; ++c) p[c] = p[c] / s;
+}
+
 // ------------------------------------------------------------------------------------------------
 static int rowtile_lds_bytes(int cols, int lds_levels)
 {
@@ -713,7 +767,7 @@ static int resolve_strategy(const tahoe_forest *f, size_t rows)
         if (sparse_top_waves(f) > 0) return TAHOE_STRATEGY_TILEBLOCK;
         return sparse_tile_fits(f) ? TAHOE_STRATEGY_ROWTILE : TAHOE_STRATEGY_DIRECT;
     }
-    if (f->strategy != TAHOE_STRATEGY_AUTO) return f->strategy;
+    if (f->strategy != TAHOE_STRATEGY_AUTO) return f->strategy;  // (a multi-class handle refuses the float32 tile forms)
     // QRING pays a quantise pass over rows x cols to make every (row, tree, level) step ~3x cheaper.  Fitted on the
     // enumeration of tools/selector_check.py (profiles/r01/selector_vs_enumeration.json): it loses to ROWTILE on
     // very shallow trees (the whole tree sits in ROWTILE's LDS top, no pre-pass) and to the float32 tile kernels
@@ -723,6 +777,11 @@ static int resolve_strategy(const tahoe_forest *f, size_t rows)
     // overtook ROWTILE on large shallow forests: 2000 trees x depth 3 x 32 features 0.85 against 0.99 ms, 800 x 4 x 100 0.38 against 0.58,
     // while 100 x 4 x 16 and 30 x 3 x 8 stay with ROWTILE, profiles/r04/selector_*.json)
     const bool shallow = f->depth <= 4 && rowtile_fits(f) && (long long)f->p.num_trees * f->depth <= 1024;
+    if (f->num_classes > 1) {  // the same rule over the forms that serve a multi-class handle
+        if (shallow) return TAHOE_STRATEGY_ROWTILE;
+        if (qring_walkers(f) > 0) return TAHOE_STRATEGY_QRING;
+        return rowtile_fits(f) ? TAHOE_STRATEGY_ROWTILE : TAHOE_STRATEGY_DIRECT;
+    }
     // (wide rows whose quantised form walks three trees per lane: that form is ~1.25 x faster, the float32 form pays off later)
     const long long per_col = qwide_chains(f) == 3 ? 10 : 13;
     const bool little_work = 2LL * f->p.num_trees * f->depth < per_col * f->p.num_cols &&
@@ -809,7 +868,9 @@ static tahoe_status launch_traversal(tahoe_forest *f, float *sums, uint32_t *lea
         if (sums && sums_in && sums != sums_in)
             TAHOE_HIP_TRY(hipMemcpyAsync(sums, sums_in, rows * sizeof(float), hipMemcpyDeviceToDevice, stream));
         else if (sums && !sums_in)
-            TAHOE_HIP_TRY(hipMemsetAsync(sums, 0, rows * sizeof(float), stream));
+            TAHOE_HIP_TRY(hipMemsetAsync(sums, 0, rows * (size_t)f->num_classes * sizeof(float), stream));
+    } else if (f->num_classes > 1 && (strategy == TAHOE_STRATEGY_TILERING || strategy == TAHOE_STRATEGY_TILEBLOCK)) {
+        return fail(TAHOE_ERR_UNSUPPORTED, "the float32 tile forms (TILEBLOCK, TILERING) do not serve multi-class handles");
     } else if (f->sp) {
         const tahoe_status ss = sparse_launch(f, sums, leaf_out, data, rows, stream, strategy, sums_in);
         if (ss != TAHOE_OK) return ss;
@@ -846,25 +907,43 @@ static tahoe_status launch_traversal(tahoe_forest *f, float *sums, uint32_t *lea
                         rowtile_lds_bytes(f->p.num_cols, f->lds_levels), f->p.num_cols, f->lds_limit);
         const size_t grid = (rows + kTileRows - 1) / kTileRows;
         const int lds = rowtile_lds_bytes(f->p.num_cols, f->lds_levels);
-        if (leaf_out)
+        const int nc = f->num_classes;
+        if (leaf_out && nc > 1)
+            hipLaunchKernelGGL((rowtile_kernel<true, true>), dim3((unsigned)grid), dim3(kBlock), lds, stream, f->inner,
+                               f->leaf_val, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
+                               f->p.num_trees, f->depth, f->lds_levels, f->p.missing, vec4_ok, nc);
+        else if (nc > 1)
+            hipLaunchKernelGGL((rowtile_kernel<false, true>), dim3((unsigned)grid), dim3(kBlock), lds, stream, f->inner,
+                               f->leaf_val, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
+                               f->p.num_trees, f->depth, f->lds_levels, f->p.missing, vec4_ok, nc);
+        else if (leaf_out)
             hipLaunchKernelGGL(rowtile_kernel<true>, dim3((unsigned)grid), dim3(kBlock), lds, stream, f->inner,
                                f->leaf_val, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
-                               f->p.num_trees, f->depth, f->lds_levels, f->p.missing, vec4_ok);
+                               f->p.num_trees, f->depth, f->lds_levels, f->p.missing, vec4_ok, nc);
         else
             hipLaunchKernelGGL(rowtile_kernel<false>, dim3((unsigned)grid), dim3(kBlock), lds, stream, f->inner,
                                f->leaf_val, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
-                               f->p.num_trees, f->depth, f->lds_levels, f->p.missing, vec4_ok);
+                               f->p.num_trees, f->depth, f->lds_levels, f->p.missing, vec4_ok, nc);
         TAHOE_HIP_TRY(hipGetLastError());
     } else if (strategy == TAHOE_STRATEGY_DIRECT) {
         const size_t grid = (rows + kBlock - 1) / kBlock;
-        if (leaf_out)
+        const int nc = f->num_classes;
+        if (leaf_out && nc > 1)
+            hipLaunchKernelGGL((direct_kernel<true, true>), dim3((unsigned)grid), dim3(kBlock), 0, stream, f->inner,
+                               f->leaf_val, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
+                               f->p.num_trees, f->depth, f->p.missing, nc);
+        else if (nc > 1)
+            hipLaunchKernelGGL((direct_kernel<false, true>), dim3((unsigned)grid), dim3(kBlock), 0, stream, f->inner,
+                               f->leaf_val, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
+                               f->p.num_trees, f->depth, f->p.missing, nc);
+        else if (leaf_out)
             hipLaunchKernelGGL(direct_kernel<true>, dim3((unsigned)grid), dim3(kBlock), 0, stream, f->inner,
                                f->leaf_val, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
-                               f->p.num_trees, f->depth, f->p.missing);
+                               f->p.num_trees, f->depth, f->p.missing, nc);
         else
             hipLaunchKernelGGL(direct_kernel<false>, dim3((unsigned)grid), dim3(kBlock), 0, stream, f->inner,
                                f->leaf_val, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
-                               f->p.num_trees, f->depth, f->p.missing);
+                               f->p.num_trees, f->depth, f->p.missing, nc);
         TAHOE_HIP_TRY(hipGetLastError());
     } else {
         return fail(TAHOE_ERR_INVALID_ARG, "unknown strategy %d", strategy);
@@ -885,6 +964,16 @@ static tahoe_status launch_transform(float *preds, size_t rows, int output, int 
     const size_t grid = (rows + kBlock - 1) / kBlock;
     hipLaunchKernelGGL(transform_kernel, dim3((unsigned)grid), dim3(kBlock), 0, stream, preds, rows, output,
                        num_trees, threshold, global_bias);
+    TAHOE_HIP_TRY(hipGetLastError());
+    return TAHOE_OK;
+}
+
+static tahoe_status launch_transform_mc(const tahoe_forest *f, float *preds, size_t rows, hipStream_t stream)
+{
+    if (rows == 0 || (f->p.output == TAHOE_OUT_RAW && f->p.global_bias == 0.0f)) return TAHOE_OK;
+    const size_t grid = (rows + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(transform_mc_kernel, dim3((unsigned)grid), dim3(kBlock), 0, stream, preds, rows, f->num_classes, f->p.output,
+                       f->class_trees, f->p.global_bias);
     TAHOE_HIP_TRY(hipGetLastError());
     return TAHOE_OK;
 }
@@ -922,7 +1011,9 @@ tahoe_status tahoe_forest_create(tahoe_forest **out, const tahoe_dense_node *nod
     return tahoe_forest_create_ex(out, nodes, p, flags);
 }
 
-tahoe_status tahoe_forest_create_ex(tahoe_forest **out, const tahoe_dense_node *nodes, const tahoe_forest_params *p, unsigned flags)
+// num_classes > 1: tahoe_forest_create_multiclass, whose own checks have run; the trees are laid out class-major.
+static tahoe_status create_dense(tahoe_forest **out, const tahoe_dense_node *nodes, const tahoe_forest_params *p, unsigned flags,
+                                 int num_classes)
 {
     if (!out || !p) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_create: null argument");
     if ((flags & ~(unsigned)TAHOE_CREATE_PROB_RELAYOUT) != 0) return fail(TAHOE_ERR_INVALID_ARG, "unknown create flags 0x%x", flags);
@@ -933,7 +1024,7 @@ tahoe_status tahoe_forest_create_ex(tahoe_forest **out, const tahoe_dense_node *
     if (p->num_cols < 0) return fail(TAHOE_ERR_INVALID_ARG, "num_cols must be non-negative");
     if (p->algo < TAHOE_ALGO_NAIVE || p->algo > TAHOE_ALGO_BATCH_TREE_REORG)
         return fail(TAHOE_ERR_INVALID_ARG, "algo should be NAIVE, TREE_REORG or BATCH_TREE_REORG");
-    if ((p->output & ~(TAHOE_OUT_AVG | TAHOE_OUT_SIGMOID | TAHOE_OUT_THRESHOLD)) != 0)
+    if ((p->output & ~(TAHOE_OUT_AVG | TAHOE_OUT_SIGMOID | TAHOE_OUT_THRESHOLD | (num_classes > 1 ? TAHOE_OUT_SOFTMAX : 0))) != 0)
         return fail(TAHOE_ERR_INVALID_ARG, "output should be a combination of RAW, AVG, SIGMOID and THRESHOLD");
     if (p->num_trees > 0 && !nodes) return fail(TAHOE_ERR_INVALID_ARG, "nodes is null");
 
@@ -950,6 +1041,8 @@ tahoe_status tahoe_forest_create_ex(tahoe_forest **out, const tahoe_dense_node *
     const int D = p->depth;             // depth of the trees as given
     const int De = std::max(D, 2);      // depth of the normalised trees
     f->p = *p;
+    f->num_classes = num_classes;
+    f->class_trees = p->num_trees / num_classes;
     f->depth = De;
     f->n_inner = ((size_t)1 << De) - 1;
     f->n_leaf = (size_t)1 << De;
@@ -972,6 +1065,9 @@ tahoe_status tahoe_forest_create_ex(tahoe_forest **out, const tahoe_dense_node *
     // ---- normalise: heap records of the perfect depth-De tree ----
     const size_t T = (size_t)p->num_trees;
     const size_t src_nodes = (size_t)tahoe_tree_num_nodes(D);
+    // internal tree t is the caller's tree src_tree(t): the identity, or the class-major order of a multi-class handle
+    const size_t n_cls = (size_t)num_classes, c_trees = (size_t)f->class_trees;
+    auto src_tree = [n_cls, c_trees](size_t t) { return n_cls > 1 ? (t % c_trees) * n_cls + t / c_trees : t; };
     const size_t all_nodes = f->n_inner + f->n_leaf;
     std::vector<InnerNode> h_inner(T * f->n_inner);
     std::vector<float> h_leaf(T * f->n_leaf);
@@ -992,7 +1088,7 @@ tahoe_status tahoe_forest_create_ex(tahoe_forest **out, const tahoe_dense_node *
         Bad bad;
         int max_fid_local = 0;
         for (size_t t = t_lo; t < t_hi && bad.kind == 0; ++t) {
-            const tahoe_dense_node *tree = nodes + t * src_nodes;
+            const tahoe_dense_node *tree = nodes + src_tree(t) * src_nodes;
             for (size_t i = 0; i < all_nodes; ++i) {
                 const int64_t up = i ? inherit[(i - 1) / 2] : -1;
                 int fid = 0, def_left = 0, is_leaf = 0;
@@ -1057,7 +1153,7 @@ tahoe_status tahoe_forest_create_ex(tahoe_forest **out, const tahoe_dense_node *
             std::vector<float> w(all_nodes);
             size_t swaps = 0;
             for (size_t t = t_lo; t < t_hi; ++t) {
-                const tahoe_dense_node *tree = nodes + t * src_nodes;
+                const tahoe_dense_node *tree = nodes + src_tree(t) * src_nodes;
                 for (size_t i = 0; i < all_nodes; ++i) w[i] = i < src_nodes ? tree[i].weight : 0.0f;
                 InnerNode *in = &h_inner[t * n_inner];
                 unsigned char *re = &h_real[t * n_inner];
@@ -1150,6 +1246,10 @@ tahoe_status tahoe_forest_create_ex(tahoe_forest **out, const tahoe_dense_node *
     if (rowtile_fits(f)) {
         if ((e = allow_max_lds(reinterpret_cast<const void *>(&rowtile_kernel<false>), f->lds_limit)) != hipSuccess) return bail(e, "hipFuncSetAttribute(rowtile)");
         if ((e = allow_max_lds(reinterpret_cast<const void *>(&rowtile_kernel<true>), f->lds_limit)) != hipSuccess) return bail(e, "hipFuncSetAttribute(rowtile)");
+        if (num_classes > 1) {
+            if ((e = allow_max_lds(reinterpret_cast<const void *>(&rowtile_kernel<false, true>), f->lds_limit)) != hipSuccess) return bail(e, "hipFuncSetAttribute(rowtile)");
+            if ((e = allow_max_lds(reinterpret_cast<const void *>(&rowtile_kernel<true, true>), f->lds_limit)) != hipSuccess) return bail(e, "hipFuncSetAttribute(rowtile)");
+        }
     }
     if (f->has_blocks && tileblock_lds_bytes(f, 128) <= f->lds_limit) {
         if ((e = allow_max_lds(reinterpret_cast<const void *>(&tileblock_kernel<128, false>), f->lds_limit)) != hipSuccess) return bail(e, "hipFuncSetAttribute(tileblock)");
@@ -1188,6 +1288,31 @@ tahoe_status tahoe_forest_create_ex(tahoe_forest **out, const tahoe_dense_node *
     return TAHOE_OK;
 }
 
+tahoe_status tahoe_forest_create_ex(tahoe_forest **out, const tahoe_dense_node *nodes, const tahoe_forest_params *p, unsigned flags)
+{
+    return create_dense(out, nodes, p, flags, 1);
+}
+
+tahoe_status tahoe_forest_create_multiclass(tahoe_forest **out, const tahoe_dense_node *nodes, const tahoe_forest_params *p,
+                                            int num_classes, unsigned flags)
+{
+    // every check here runs before a device is touched
+    if (!out || !p) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_create_multiclass: null argument");
+    *out = nullptr;
+    if (num_classes < 1 || num_classes > 1024) return fail(TAHOE_ERR_INVALID_ARG, "num_classes must be in [1,1024], got %d", num_classes);
+    if (p->num_trees < 0 || p->num_trees % num_classes != 0)
+        return fail(TAHOE_ERR_INVALID_ARG, "num_trees (%d) must be a non-negative multiple of num_classes (%d)", p->num_trees, num_classes);
+    if ((p->output & TAHOE_OUT_SOFTMAX) != 0 && num_classes == 1)
+        return fail(TAHOE_ERR_INVALID_ARG, "SOFTMAX needs num_classes > 1");
+    if ((p->output & TAHOE_OUT_SOFTMAX) != 0 && (p->output & TAHOE_OUT_SIGMOID) != 0)
+        return fail(TAHOE_ERR_INVALID_ARG, "SOFTMAX and SIGMOID exclude each other");
+    if ((p->output & TAHOE_OUT_THRESHOLD) != 0 && num_classes > 1)
+        return fail(TAHOE_ERR_INVALID_ARG, "THRESHOLD needs num_classes == 1");
+    return create_dense(out, nodes, p, flags, num_classes);
+}
+
+int tahoe_forest_num_classes(const tahoe_forest *f) { return f ? f->num_classes : 0; }
+
 void tahoe_forest_destroy(tahoe_forest *f)
 {
     if (!f) return;
@@ -1220,6 +1345,7 @@ tahoe_status tahoe_forest_predict_accumulate(tahoe_forest *f, float *sums_dev, c
 {
     if (!f || (rows && (!sums_dev || !data_dev)))
         return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_accumulate: null argument");
+    if (f->num_classes > 1) return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_accumulate: not served on a multi-class handle");
     return launch_traversal(f, sums_dev, nullptr, data_dev, rows, (hipStream_t)stream, sums_dev);
 }
 
@@ -1231,6 +1357,7 @@ tahoe_status tahoe_forest_predict(tahoe_forest *f, float *preds_dev, const float
     DeviceGuard on_device(f->device);
     tahoe_status s = launch_traversal(f, preds_dev, nullptr, data_dev, rows, (hipStream_t)stream);
     if (s != TAHOE_OK) return s;
+    if (f->num_classes > 1) return launch_transform_mc(f, preds_dev, rows, (hipStream_t)stream);
     return launch_transform(preds_dev, rows, f->p.output, f->p.num_trees, f->p.threshold, f->p.global_bias,
                             (hipStream_t)stream);
 }
@@ -1266,6 +1393,8 @@ tahoe_status tahoe_forest_set_strategy(tahoe_forest *f, int strategy)
         f->strategy = strategy;
         return TAHOE_OK;
     }
+    if (f->num_classes > 1 && (strategy == TAHOE_STRATEGY_TILEBLOCK || strategy == TAHOE_STRATEGY_TILERING))
+        return fail(TAHOE_ERR_UNSUPPORTED, "a multi-class handle runs AUTO, DIRECT, ROWTILE or QRING (no float32 tile forms)");
     if (strategy == TAHOE_STRATEGY_ROWTILE && !rowtile_fits(f))
         return fail(TAHOE_ERR_UNSUPPORTED, "ROWTILE needs %d B of LDS for %d columns; device offers %d",
                     rowtile_lds_bytes(f->p.num_cols, f->lds_levels), f->p.num_cols, f->lds_limit);

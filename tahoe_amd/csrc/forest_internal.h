@@ -71,6 +71,11 @@ struct tahoe_forest {
     tahoe_pstate *pipe = nullptr;  // tahoe_forest_predict_host: chunk buffers, streams, events (created on first use)
     tahoe_wstate *wf = nullptr;    // non-null: TILERING runs the wide-row float32 form (widef.hip)
     size_t device_bytes = 0;
+    // Multi-class handle (tahoe_forest_create_multiclass): the trees are stored class-major -- internal tree p belongs to class
+    // p / class_trees and is original tree (p % class_trees) * num_classes + p / class_trees -- and every consumer writes
+    // sums[row * num_classes + class].  1 / num_trees on every other handle.
+    int num_classes = 1;
+    int class_trees = 0;
     // Tuning knobs for experiments, read from the environment ONCE, in tahoe_forest_create (never on the predict path):
     // TAHOE_TILE_ROWS (64 / 128: rows per TILEBLOCK / TILERING tile), TAHOE_QRING_WALKERS (15 / 12 / 8 / 4).  0 = unset.
     // Probability-guided re-layout (TAHOE_CREATE_PROB_RELAYOUT; Struct.h:1775-1825): subtrees swapped so that the likelier
@@ -134,6 +139,14 @@ __device__ __forceinline__ uint32_t go_right(float x, float thr, bool def_left, 
 __device__ __forceinline__ uint32_t go_right_meta(float x, float thr, uint32_t meta, float missing)
 {
     return go_right(x, thr, (meta >> 31) != 0, missing) ^ ((meta >> 30) & 1u);
+}
+
+// Multi-class handles store the trees class-major: internal tree p (class p / class_trees) is original tree
+// (p % class_trees) * num_classes + p / class_trees.  Leaf indices are written in the original numbering.
+__device__ __forceinline__ int mc_orig_tree(int p, int num_classes, int class_trees)
+{
+    const int c = p / class_trees;
+    return (p - c * class_trees) * num_classes + c;
 }
 
 // QRING entry points (qring.hip).  h_real[i] != 0 marks heap records that exist in the original tree

@@ -74,16 +74,19 @@ namespace tahoe {
 // REGB = LDS stride of a region: 32 KiB (num_cols <= 256), or 16 KiB for forests of <= 128 features (a region is cols x 128 bytes;
 // fid < 128 leaves bit 14 of the v_bfi field clear) -- six 64-row regions of u16 codes then fit where three did (384-row tiles for
 // narrow forests with any number of thresholds), and six chains of u8 codes leave room for 15 walkers and a ring of 24.
+// MC (multi-class handle, trees class-major): the consumer stores its K sums to sums[row * num_classes + c] at the end of class
+// c's trees and restarts from 0.0f; a group that starts inside a class continues that class's sum from sums_in, one that ends
+// inside a class leaves the partial sum there.  Leaf indices go to the original tree's column.
 template <int NWALK, bool WRITE_LEAF, bool LDSX, bool NARROW = false, bool EXCH = false, int K = 2, bool REG = false, int RING = kQRing,
           bool SPLIT = false, int BATCH = (RING >= 2 * kQBatch ? kQBatch : RING / 2), bool CODE8 = false, bool DEP = false,
-          int REGB = kRegBytes>
+          int REGB = kRegBytes, bool MC = false>
 __global__ void __launch_bounds__((NWALK + 1) * 64)
     qring_kernel(const uint16_t *__restrict__ xq, const uint32_t *__restrict__ top, const uint4 *__restrict__ blocks,
                  const uint32_t *__restrict__ qinner, const uint32_t *__restrict__ leaf_orig, float *sums,
                  uint32_t *__restrict__ leaf_out, size_t rows, int cols, int num_trees, int depth, int top_levels,
                  int top_stride, const uint32_t *__restrict__ chunk_flags, int *__restrict__ error_flag,
                  const float *sums_in, int tree_base, int total_trees, int cshift, float *__restrict__ leafbuf, size_t leaf_stride,
-                 int slices, size_t row_begin)
+                 int slices, size_t row_begin, int num_classes)
 {
     // `rows` is the END of the rows this launch walks and row_begin (region form only; a multiple of 384) their start: a batch
     // may be walked as whole waves of 192-row tiles followed by a remainder of 128-row tiles (qring_launch).
@@ -148,11 +151,28 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
         __syncthreads();
         if (SPLIT) return;  // the leaf values go to leafbuf; ordered_sum_kernel adds them
         float sum[K];  // continues the running sums of the previous tree group (sums_in may alias sums)
+        // MC: class cls of the group's first tree; its trees end after local tree cend - 1
+        const int ctrees = MC ? total_trees / num_classes : 0;
+        int cls = MC ? tree_base / ctrees : 0;
+        int cend = MC ? (cls + 1) * ctrees - tree_base : 0;
+        const bool mid_class = MC && cls * ctrees != tree_base;
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             const size_t irow = row0 + k * 64 + lane;
-            sum[k] = (sums_in && irow < rows) ? sums_in[irow] : 0.0f;
+            if (MC)
+                sum[k] = (mid_class && sums_in && irow < rows) ? sums_in[irow * (size_t)num_classes + cls] : 0.0f;
+            else
+                sum[k] = (sums_in && irow < rows) ? sums_in[irow] : 0.0f;
         }
+        auto flush = [&]() {  // MC: class cls's sums (complete, or the partial sum the next group continues)
+            if (sums) {
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    const size_t orow = row0 + k * 64 + lane;
+                    if (orow < rows) sums[orow * (size_t)num_classes + cls] = sum[k];
+                }
+            }
+        };
         bool dead = false;
         for (int t0 = 0; t0 < num_trees && !dead; t0 += BATCH) {
             const int nb = min(BATCH, num_trees - t0);
@@ -172,12 +192,21 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
                 const int e = (t0 + j) % RING;
 #pragma unroll
                 for (int k = 0; k < K; ++k) sum[k] += ring_vals[e * TR + k * 64 + lane];  // tree order
+                if (MC && t0 + j + 1 == cend) {
+                    flush();
+#pragma unroll
+                    for (int k = 0; k < K; ++k) sum[k] = 0.0f;
+                    ++cls;
+                    cend += ctrees;
+                }
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             if (lane == 0) lds_flag_store(consumed, (uint32_t)(t0 + nb));
         }
         if (dead && lane == 0) atomicOr(error_flag, 1);
-        if (sums) {
+        if (MC) {
+            if (num_trees > cend - ctrees) flush();  // the group ends inside class cls
+        } else if (sums) {
 #pragma unroll
             for (int k = 0; k < K; ++k) {
                 const size_t orow = row0 + k * 64 + lane;
@@ -246,7 +275,8 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
                 if (WRITE_LEAF) {
                     const size_t row = row0 + k * 64 + lane;
                     if (row < rows)
-                        leaf_out[row * (size_t)total_trees + tree_base + t] =
+                        leaf_out[MC ? row * (size_t)total_trees + mc_orig_tree(tree_base + t, num_classes, total_trees / num_classes)
+                                    : row * (size_t)total_trees + tree_base + t] =
                             leaf_orig[(size_t)t * ((size_t)n_blocks * 4) + (size_t)bs[k] * 4 + 2 * (c0 ? 1 : 0) + (c1 ? 1 : 0)];
                 }
             }
@@ -399,13 +429,14 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
 // independent dependent-read chains per wave instead of one, with a ring of 16 KiB for the larger number of trees in flight.
 constexpr int kWideRingBytes = 8192;
 constexpr int kWideRingBytesK = 16384;  // ring of the KG = 3 form
-template <int RT, bool WRITE_LEAF, int KG = 1, int RB = kWideRingBytes>
+// MC: the per-class flush of qring_kernel's consumer.
+template <int RT, bool WRITE_LEAF, int KG = 1, int RB = kWideRingBytes, bool MC = false>
 __global__ void __launch_bounds__(16 * 64)
     qwide_kernel(const uint16_t *__restrict__ xq, const uint32_t *__restrict__ top, const uint4 *__restrict__ blocks,
                  const uint32_t *__restrict__ qinner, const uint32_t *__restrict__ leaf_orig, float *sums,
                  uint32_t *__restrict__ leaf_out, size_t rows, int cols, int num_trees, int depth, int top_levels,
                  int top_stride, const uint32_t *__restrict__ chunk_flags, int *__restrict__ error_flag,
-                 const float *sums_in, int tree_base, int total_trees, int slot_bytes, int lw, int cshift)
+                 const float *sums_in, int tree_base, int total_trees, int slot_bytes, int lw, int cshift, int num_classes)
 {
     constexpr int NWALK = 15;
     constexpr int NT = (NWALK + 1) * 64;
@@ -441,7 +472,20 @@ __global__ void __launch_bounds__(16 * 64)
         // ================= consumer: ordered accumulation, lane = row =================
         __syncthreads();
         const size_t irow = row0 + lane;
+        const int ctrees = MC ? total_trees / num_classes : 0;  // MC: as in qring_kernel's consumer
+        int cls = MC ? tree_base / ctrees : 0;
+        int cend = MC ? (cls + 1) * ctrees - tree_base : 0;
         float sum = (sums_in && lane < RT && irow < rows) ? sums_in[irow] : 0.0f;
+        if (MC) sum = (cls * ctrees != tree_base && sums_in && lane < RT && irow < rows) ? sums_in[irow * (size_t)num_classes + cls] : 0.0f;
+        auto add = [&](float v, int t) {  // MC: tree t's leaf value, the sum stored at the end of a class
+            sum += v;
+            if (t + 1 == cend) {
+                if (sums && irow < rows) sums[irow * (size_t)num_classes + cls] = sum;
+                sum = 0.0f;
+                ++cls;
+                cend += ctrees;
+            }
+        };
         bool dead = false;
         for (int t0 = 0; t0 < num_trees && !dead; t0 += NBATCH) {
             const int nb = min(NBATCH, num_trees - t0);
@@ -464,16 +508,28 @@ __global__ void __launch_bounds__(16 * 64)
                     float v[8];
 #pragma unroll
                     for (int u = 0; u < 8; ++u) v[u] = ring_vals[((t0 + jj + u) % RE) * RT + lane];
+                    if (MC) {
 #pragma unroll
-                    for (int u = 0; u < 8; ++u) sum += v[u];
+                        for (int u = 0; u < 8; ++u) add(v[u], t0 + jj + u);
+                    } else {
+#pragma unroll
+                        for (int u = 0; u < 8; ++u) sum += v[u];
+                    }
                 }
-                for (; jj < nb; ++jj) sum += ring_vals[((t0 + jj) % RE) * RT + lane];
+                if (MC)
+                    for (; jj < nb; ++jj) add(ring_vals[((t0 + jj) % RE) * RT + lane], t0 + jj);
+                else
+                    for (; jj < nb; ++jj) sum += ring_vals[((t0 + jj) % RE) * RT + lane];
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             if (lane == 0) lds_flag_store(consumed, (uint32_t)(t0 + nb));
         }
         if (dead && lane == 0) atomicOr(error_flag, 1);
-        if (sums && lane < RT && irow < rows) sums[irow] = sum;
+        if (MC) {
+            if (sums && lane < RT && irow < rows && num_trees > cend - ctrees) sums[irow * (size_t)num_classes + cls] = sum;  // ends inside a class
+        } else if (sums && lane < RT && irow < rows) {
+            sums[irow] = sum;
+        }
         return;
     }
 
@@ -533,7 +589,8 @@ __global__ void __launch_bounds__(16 * 64)
                 v[k] = __uint_as_float(c1 ? hi : lo);
                 if (WRITE_LEAF) {
                     if (t < num_trees && row < rows)
-                        leaf_out[row * (size_t)total_trees + tree_base + t] =
+                        leaf_out[MC ? row * (size_t)total_trees + mc_orig_tree(tree_base + t, num_classes, total_trees / num_classes)
+                                    : row * (size_t)total_trees + tree_base + t] =
                             leaf_orig[(size_t)t * ((size_t)n_blocks * 4) + (size_t)bs[k] * 4 + 2 * (c0 ? 1 : 0) + (c1 ? 1 : 0)];
                 }
             }
@@ -662,6 +719,33 @@ __global__ void __launch_bounds__(kOrderedSumThreads) ordered_sum_kernel(const f
     }
     for (; t < num_trees; ++t) sum += leafbuf[(size_t)t * leaf_stride + r];
     sums[row] = sum;
+}
+
+// ... on a multi-class handle: thread = (row, class blockIdx.y of the classes the group [tree_base, tree_base + num_trees)
+// overlaps).  Each class's trees of the group in tree order; a class that began in an earlier group continues from sums_in.
+__global__ void __launch_bounds__(kOrderedSumThreads) ordered_sum_mc_kernel(const float *__restrict__ leafbuf, size_t leaf_stride,
+                                                                            int num_trees, const float *sums_in, float *sums, size_t rows,
+                                                                            size_t row_begin, int tree_base, int total_trees,
+                                                                            int num_classes)
+{
+    const size_t r = (size_t)blockIdx.x * kOrderedSumThreads + threadIdx.x;
+    const size_t row = row_begin + r;
+    if (row >= rows) return;
+    const int ctrees = total_trees / num_classes;
+    const int cls = tree_base / ctrees + (int)blockIdx.y;
+    const int lo = max(cls * ctrees, tree_base) - tree_base, hi = min((cls + 1) * ctrees, tree_base + num_trees) - tree_base;
+    const size_t out = row * (size_t)num_classes + cls;
+    float sum = (sums_in && cls * ctrees < tree_base) ? sums_in[out] : 0.0f;
+    int t = lo;
+    for (; t + 8 <= hi; t += 8) {  // 8 loads in flight, 8 adds in tree order
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = leafbuf[(size_t)(t + j) * leaf_stride + r];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) sum += v[j];
+    }
+    for (; t < hi; ++t) sum += leafbuf[(size_t)t * leaf_stride + r];
+    sums[out] = sum;
 }
 
 static long long qring_lds_for(const tahoe_forest *f, int nwalk, bool lds_tile = true)
@@ -1092,19 +1176,37 @@ static void q_launch(tahoe_forest *f, const tahoe_qgroup &g, float *sums, const 
     const size_t leaf_stride = SPLIT ? q->leaf_stride : 0;
     const int lds = REG ? (int)qreg_lds_for(K, NWALK, RING, CODE8, REGB) : (int)qring_lds_for(f, NWALK, LDSX);
     const uint32_t *leaf_orig = f->leaf_orig + (size_t)g.tree_lo * f->n_leaf;
-    if (leaf_out)
-        hipLaunchKernelGGL((qring_kernel<NWALK, true, LDSX, NARROW, EXCH, K, REG, RING, SPLIT, BATCH, CODE8, DEP, REGB>), dim3(grid), dim3((NWALK + 1) * 64), lds, stream, q->xq, g.top,
-                           g.blocks, g.qinner, leaf_orig, sums, leaf_out, rows, f->p.num_cols, g.num_trees, f->depth,
-                           q->top_levels, q->top_stride, q->chunk_flags, f->error_flag, sums_in, g.tree_lo, f->p.num_trees, cshift, leafbuf, leaf_stride,
-                           slices, row_begin);
-    else
-        hipLaunchKernelGGL((qring_kernel<NWALK, false, LDSX, NARROW, EXCH, K, REG, RING, SPLIT, BATCH, CODE8, DEP, REGB>), dim3(grid), dim3((NWALK + 1) * 64), lds, stream, q->xq, g.top,
-                           g.blocks, g.qinner, leaf_orig, sums, leaf_out, rows, f->p.num_cols, g.num_trees, f->depth,
-                           q->top_levels, q->top_stride, q->chunk_flags, f->error_flag, sums_in, g.tree_lo, f->p.num_trees, cshift, leafbuf, leaf_stride,
-                           slices, row_begin);
-    if (SPLIT && sums)
-        hipLaunchKernelGGL(ordered_sum_kernel, dim3((unsigned)((rows - row_begin + kOrderedSumThreads - 1) / kOrderedSumThreads)), dim3(kOrderedSumThreads), 0, stream,
+    const int nc = f->num_classes;
+#define TAHOE_Q_LAUNCH(WL, MCF)                                                                                                        \
+    hipLaunchKernelGGL((qring_kernel<NWALK, WL, LDSX, NARROW, EXCH, K, REG, RING, SPLIT, BATCH, CODE8, DEP, REGB, MCF>), dim3(grid),   \
+                       dim3((NWALK + 1) * 64), lds, stream, q->xq, g.top, g.blocks, g.qinner, leaf_orig, sums, leaf_out, rows,        \
+                       f->p.num_cols, g.num_trees, f->depth, q->top_levels, q->top_stride, q->chunk_flags, f->error_flag, sums_in,    \
+                       g.tree_lo, f->p.num_trees, cshift, leafbuf, leaf_stride, slices, row_begin, nc)
+    if (nc > 1) {
+        // multi-class instantiations: their LDS limit is raised on first use (process-wide, like allow_max_lds at create)
+        static const bool allowed = allow_max_lds(reinterpret_cast<const void *>(&qring_kernel<NWALK, false, LDSX, NARROW, EXCH, K, REG, RING, SPLIT, BATCH, CODE8, DEP, REGB, true>), f->lds_limit) == hipSuccess &&
+                                    allow_max_lds(reinterpret_cast<const void *>(&qring_kernel<NWALK, true, LDSX, NARROW, EXCH, K, REG, RING, SPLIT, BATCH, CODE8, DEP, REGB, true>), f->lds_limit) == hipSuccess;
+        (void)allowed;  // a failure shows as the launch error
+        if (leaf_out)
+            TAHOE_Q_LAUNCH(true, true);
+        else
+            TAHOE_Q_LAUNCH(false, true);
+    } else if (leaf_out) {
+        TAHOE_Q_LAUNCH(true, false);
+    } else {
+        TAHOE_Q_LAUNCH(false, false);
+    }
+#undef TAHOE_Q_LAUNCH
+    const unsigned sum_blocks = (unsigned)((rows - row_begin + kOrderedSumThreads - 1) / kOrderedSumThreads);
+    if (SPLIT && sums && nc > 1) {
+        const int ctrees = f->p.num_trees / nc;
+        const unsigned classes = (unsigned)((g.tree_lo + g.num_trees - 1) / ctrees - g.tree_lo / ctrees + 1);  // classes the group overlaps
+        hipLaunchKernelGGL(ordered_sum_mc_kernel, dim3(sum_blocks, classes), dim3(kOrderedSumThreads), 0, stream, leafbuf, leaf_stride, g.num_trees,
+                           sums_in, sums, rows, row_begin, g.tree_lo, f->p.num_trees, nc);
+    } else if (SPLIT && sums) {
+        hipLaunchKernelGGL(ordered_sum_kernel, dim3(sum_blocks), dim3(kOrderedSumThreads), 0, stream,
                            leafbuf, leaf_stride, g.num_trees, sums_in, sums, rows, row_begin);
+    }
 }
 
 template <int RT, int KG, int RB>
@@ -1116,14 +1218,25 @@ static void qwide_launch_form(tahoe_forest *f, const tahoe_qgroup &g, float *sum
     const int lds = (int)qwide_lds_for(f, RT, q->wide_lw, KG);
     const int slot_bytes = KG * (int)qwide_slot_bytes(q->wide_lw, RT);
     const uint32_t *leaf_orig = f->leaf_orig + (size_t)g.tree_lo * f->n_leaf;
-    if (leaf_out)
-        hipLaunchKernelGGL((qwide_kernel<RT, true, KG, RB>), dim3(grid), dim3(16 * 64), lds, stream, q->xq, g.top, g.blocks, g.qinner,
-                           leaf_orig, sums, leaf_out, rows, f->p.num_cols, g.num_trees, f->depth, q->top_levels, q->top_stride,
-                           q->chunk_flags, f->error_flag, sums_in, g.tree_lo, f->p.num_trees, slot_bytes, q->wide_lw, cshift);
-    else
-        hipLaunchKernelGGL((qwide_kernel<RT, false, KG, RB>), dim3(grid), dim3(16 * 64), lds, stream, q->xq, g.top, g.blocks, g.qinner,
-                           leaf_orig, sums, leaf_out, rows, f->p.num_cols, g.num_trees, f->depth, q->top_levels, q->top_stride,
-                           q->chunk_flags, f->error_flag, sums_in, g.tree_lo, f->p.num_trees, slot_bytes, q->wide_lw, cshift);
+    const int nc = f->num_classes;
+#define TAHOE_QW_LAUNCH(WL, MCF)                                                                                                      \
+    hipLaunchKernelGGL((qwide_kernel<RT, WL, KG, RB, MCF>), dim3(grid), dim3(16 * 64), lds, stream, q->xq, g.top, g.blocks, g.qinner, \
+                       leaf_orig, sums, leaf_out, rows, f->p.num_cols, g.num_trees, f->depth, q->top_levels, q->top_stride,          \
+                       q->chunk_flags, f->error_flag, sums_in, g.tree_lo, f->p.num_trees, slot_bytes, q->wide_lw, cshift, nc)
+    if (nc > 1) {
+        static const bool allowed = allow_max_lds(reinterpret_cast<const void *>(&qwide_kernel<RT, false, KG, RB, true>), f->lds_limit) == hipSuccess &&
+                                    allow_max_lds(reinterpret_cast<const void *>(&qwide_kernel<RT, true, KG, RB, true>), f->lds_limit) == hipSuccess;
+        (void)allowed;  // (as in q_launch)
+        if (leaf_out)
+            TAHOE_QW_LAUNCH(true, true);
+        else
+            TAHOE_QW_LAUNCH(false, true);
+    } else if (leaf_out) {
+        TAHOE_QW_LAUNCH(true, false);
+    } else {
+        TAHOE_QW_LAUNCH(false, false);
+    }
+#undef TAHOE_QW_LAUNCH
 }
 
 template <int RT>

@@ -1,0 +1,91 @@
+"""Compares the gfx950 instruction streams of two builds of the kernels, kernel by kernel: did a change leave the
+pre-existing template instantiations as they were?
+
+Build each tree's translation units with --save-temps (the Makefile's flags), e.g. for forest.hip and qring.hip:
+    hipcc --offload-arch=gfx950 -std=c++17 -O3 -fPIC -fvisibility=hidden -fvisibility-inlines-hidden -I<tree>/include \
+          -ffp-contract=off --save-temps -c forest.hip -o forest.o
+then   python tools/isa_diff.py <old_dir> <new_dir> [forest qring ...] [-v]
+(dirs = where the *-hip-amdgcn-amd-amdhsa-gfx950.s files are).  Local branch labels are renumbered and the kernel descriptor's
+name, section and kernarg_size lines are left out of the comparison (a kernel argument appended at the end changes only those).
+A template flag appended with a default (`bool MC = false`) is matched by dropping a trailing `, false` template argument; new
+instantiations with `, true` there are counted, not compared."""
+import difflib
+import re
+import subprocess
+import sys
+
+FLAGGED = ("direct_kernel", "rowtile_kernel", "qring_kernel", "qwide_kernel")  # kernels that carry the appended flag
+
+
+def functions(path):
+    out, cur, body = {}, None, []
+    for line in open(path):
+        m = re.match(r"^(_Z\S+):\s*(;.*)?$", line)
+        if m:
+            cur, body = m.group(1), []
+            continue
+        if cur and line.startswith(".Lfunc_end"):
+            out[cur] = body
+            cur = None
+            continue
+        if cur:
+            text = line.split(";")[0].rstrip()
+            text = re.sub(r"\.LBB\d+_", ".LBB_", text)
+            text = re.sub(r"\.Ltmp\d+", ".Ltmp", text)
+            if any(x in text for x in (".amdhsa_kernel ", ".section", ".amdhsa_kernarg_size")):
+                continue
+            if text.strip():
+                body.append(text)
+    return out
+
+
+def demangle(names):
+    res = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
+    return dict(zip(names, res))
+
+
+def key(name, new):
+    base = name.split("(")[0]
+    if new and any(k in base for k in FLAGGED):
+        if base.endswith(", false>"):
+            return base[: -len(", false>")] + ">"
+        if base.endswith(", true>"):
+            return None
+    return base
+
+
+def main(argv):
+    verbose = "-v" in argv
+    args = [a for a in argv if a != "-v"]
+    old_dir, new_dir, units = args[0], args[1], args[2:] or ["forest", "qring"]
+    changed = 0
+    for unit in units:
+        old = functions(f"{old_dir}/{unit}-hip-amdgcn-amd-amdhsa-gfx950.s")
+        new = functions(f"{new_dir}/{unit}-hip-amdgcn-amd-amdhsa-gfx950.s")
+        od, nd = demangle(list(old)), demangle(list(new))
+        old_by = {key(od[k], False): k for k in old}
+        new_by = {}
+        for k in new:
+            kk = key(nd[k], True)
+            if kk is not None:
+                new_by[kk] = k
+        same = 0
+        for name, k in old_by.items():
+            if name not in new_by:
+                print(f"{unit}: gone: {name}")
+                changed += 1
+            elif old[k] == new[new_by[name]]:
+                same += 1
+            else:
+                changed += 1
+                print(f"{unit}: CHANGED: {name}")
+                if verbose:
+                    print("\n".join(list(difflib.unified_diff(old[k], new[new_by[name]], lineterm=""))[:60]))
+        added = [n for n in new_by if n not in old_by]
+        flagged = sum(1 for k in new if key(nd[k], True) is None)
+        print(f"{unit}: {same} of {len(old_by)} pre-existing functions identical; new: {added}; new flagged instantiations: {flagged}")
+    return 1 if changed else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1:]))
