@@ -201,6 +201,27 @@ tahoe_status tahoe_forest_create_multiclass(tahoe_forest **out, const tahoe_dens
 /* Classes of the handle: num_classes of tahoe_forest_create_multiclass, 1 for every other handle (sparse included), 0 for NULL. */
 int tahoe_forest_num_classes(const tahoe_forest *f);
 
+/* Per-feature contributions (path-dependent TreeSHAP: XGBoost pred_contribs, LightGBM pred_contrib).  A create flag for
+ * tahoe_forest_create_ex and tahoe_forest_create_multiclass; it combines with TAHOE_CREATE_PROB_RELAYOUT.  dense_node_t.weight
+ * is the cover of a node (a reach probability, a hessian sum, any positive scale): at every reachable internal node the
+ * children's weights wl, wr must be finite and >= 0 with wl + wr > 0, else create returns TAHOE_ERR_INVALID_FOREST naming the
+ * tree and node (checked before a device is touched; weights below a leaf are ignored).  The handle then also holds one path per
+ * reachable leaf (repeated features merged), built from the caller's nodes, in 64-lane bins; num_cols must be <= the device's
+ * LDS bytes / 20 (8192 on an MI355X), else TAHOE_ERR_UNSUPPORTED.  Without the flag `weight` is ignored and nothing is built. */
+#define TAHOE_CREATE_CONTRIBS 0x4u
+/* phi_dev[rows][num_classes][num_cols + 1] <- exact Shapley values of v(S) = E[f(x) | x_S], the path-dependent expectation: at a
+ * node whose feature is in S the row's branch (the rule of tahoe_forest_predict: missing sentinel -> default branch, else right
+ * iff x >= thr), at any other node the mix of the two children by their cover ratios wl / (wl + wr), wr / (wl + wr).  Class c
+ * is explained by its trees c, c + C, ... .  Contributions explain the margin before SIGMOID / THRESHOLD / SOFTMAX; with
+ * TAHOE_OUT_AVG every column is divided by (float)Tc (trees of the class).  Column num_cols (the bias) is
+ * sum_t E_t / (AVG ? Tc : 1) + global_bias, computed on the host in float64 at create and rounded once; sum_i phi_i is the
+ * margin up to rounding.  Deterministic: the same bits on every call, for a row in any batch, under every strategy (the
+ * strategy is not used), with or without TAHOE_CREATE_PROB_RELAYOUT; class c of a multi-class handle gives the bits of a
+ * handle created from class c's sub-forest.  Asynchronous on `stream`; allocates nothing (graph-capturable).  rows == 0:
+ * TAHOE_OK, nothing launched; NULL phi_dev / data_dev with rows > 0: TAHOE_ERR_INVALID_ARG; a handle created without
+ * TAHOE_CREATE_CONTRIBS, or a sparse handle: TAHOE_ERR_UNSUPPORTED, nothing launched. */
+tahoe_status tahoe_forest_predict_contribs(tahoe_forest *f, float *phi_dev, const float *data_dev, size_t rows, void *stream);
+
 /* ---- sparse (irregular) forests: sparse_node_t Struct.h:50-54, sparse_storage Struct.h:343-354,
  * init_sparse / sparse_forest::init (BaseTahoeTest.h:766-772, Struct.h:2329-2343) ---- */
 typedef struct {

@@ -27,6 +27,8 @@ from .capi import (  # noqa: F401
     OUT_SIGMOID,
     OUT_THRESHOLD,
     OUT_SOFTMAX,
+    CREATE_CONTRIBS,
+    CREATE_PROB_RELAYOUT,
     STRATEGY_AUTO,
     STRATEGY_DIRECT,
     STRATEGY_ROWTILE,

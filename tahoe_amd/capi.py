@@ -35,6 +35,7 @@ OUT_RAW, OUT_AVG, OUT_SIGMOID, OUT_THRESHOLD = 0x0, 0x1, 0x10, 0x100
 OUT_SOFTMAX = 0x1000  # multi-class handles only (tahoe_forest_create_multiclass)
 STRATEGY_AUTO, STRATEGY_DIRECT, STRATEGY_ROWTILE, STRATEGY_TILEBLOCK, STRATEGY_TILERING, STRATEGY_QRING = range(6)
 CREATE_PROB_RELAYOUT = 0x1
+CREATE_CONTRIBS = 0x4  # per-feature contributions (tahoe_forest_predict_contribs); node weights are covers
 STRATEGY_NAMES = {1: "direct", 2: "rowtile", 3: "tileblock", 4: "tilering", 5: "qring"}
 STATUS_NAMES = {
     0: "TAHOE_OK",
@@ -121,6 +122,7 @@ _PROTOS = {
     "tahoe_forest_destroy": (None, [_vp]),
     "tahoe_forest_create_multiclass": (_i, [C.POINTER(_vp), _vp, C.POINTER(ForestParams), _i, C.c_uint]),
     "tahoe_forest_num_classes": (_i, [_vp]),
+    "tahoe_forest_predict_contribs": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "tahoe_sparse_forest_create": (_i, [C.POINTER(_vp), _vp, _vp, C.POINTER(ForestParams)]),
     "tahoe_dense_to_sparse": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz)]),
     "tahoe_synth_sparse_forest": (_i, [_vp, _vp, C.POINTER(_sz), _i, _i, _i, _i, _f, _i, C.c_uint64]),
@@ -373,21 +375,21 @@ class Forest:
 
     def __init__(self, nodes: np.ndarray, num_trees: int, depth: int, num_cols: int, missing: float = 0.0,
                  output: int = OUT_RAW, threshold: float = 0.0, global_bias: float = 0.0, algo: int = 0,
-                 strategy: int = 0, relayout: bool = False, num_classes: int = 1):
+                 strategy: int = 0, relayout: bool = False, num_classes: int = 1, contribs: bool = False):
         nodes = np.ascontiguousarray(nodes, dtype=NODE_DTYPE)
         if nodes.size != num_trees * tree_num_nodes(depth):
             raise ValueError("nodes.size != num_trees * tree_num_nodes(depth)")
         self.params = ForestParams(0, depth, num_trees, num_cols, algo, output, threshold, global_bias, strategy,
                                    missing)
         self._h = _vp()
+        flags = (CREATE_PROB_RELAYOUT if relayout else 0) | (CREATE_CONTRIBS if contribs else 0)
         if num_classes != 1:
             _check(lib.tahoe_forest_create_multiclass(C.byref(self._h), nodes.ctypes.data if nodes.size else None,
-                                                      C.byref(self.params), num_classes,
-                                                      CREATE_PROB_RELAYOUT if relayout else 0),
+                                                      C.byref(self.params), num_classes, flags),
                    "tahoe_forest_create_multiclass")
-        elif relayout:  # TAHOE_CREATE_PROB_RELAYOUT: subtrees ordered by dense_node_t.weight (Struct.h:1775-1825)
+        elif flags:  # re-layout by dense_node_t.weight (Struct.h:1775-1825) and / or the contribution tables
             _check(lib.tahoe_forest_create_ex(C.byref(self._h), nodes.ctypes.data if nodes.size else None,
-                                              C.byref(self.params), CREATE_PROB_RELAYOUT), "tahoe_forest_create_ex")
+                                              C.byref(self.params), flags), "tahoe_forest_create_ex")
         else:
             _check(lib.tahoe_forest_create(C.byref(self._h), nodes.ctypes.data if nodes.size else None,
                                            C.byref(self.params)), "tahoe_forest_create")
@@ -451,6 +453,21 @@ class Forest:
                                                  _ptr(data), rows, _stream(stream)),
                "tahoe_forest_predict_leaf_idx")
         return leaf, sums
+
+    def predict_contribs(self, data, out=None, stream=None):
+        """Per-feature contributions (path-dependent TreeSHAP, tahoe_forest_predict_contribs): [rows, num_cols + 1] float32,
+        or [rows, num_classes, num_cols + 1] on a multi-class handle; the bias is the last column.  Needs contribs=True."""
+        import torch
+
+        self._check_data(data)
+        rows = data.shape[0]
+        shape = (rows, self.num_classes, self.num_cols + 1) if self.num_classes > 1 else (rows, self.num_cols + 1)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=data.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == shape
+        _check(lib.tahoe_forest_predict_contribs(self._h, _ptr(out), _ptr(data), rows, _stream(stream)),
+               "tahoe_forest_predict_contribs")
+        return out
 
     def set_strategy(self, strategy: int) -> None:
         _check(lib.tahoe_forest_set_strategy(self._h, strategy), "tahoe_forest_set_strategy")

@@ -1,0 +1,428 @@
+// Per-feature contributions: path-dependent TreeSHAP (Lundberg et al. 2018, Algorithm 2) in the lane-per-path-element form of
+// GPUTreeShap (Mitchell et al. 2022).  Create (TAHOE_CREATE_CONTRIBS) turns every reachable leaf into a path -- its ancestors'
+// features, repeated ones merged into one element -- and packs the paths into 64-lane bins; the kernel evaluates, for each row,
+// every bin with one lane per path element: one-fraction by the library's branch rule, the extend recursion across the lanes of
+// a path, one unwound-path sum per lane, and the lane's term added into its row's phi[feature] in a fixed order.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <mutex>
+#include <new>
+#include <vector>
+
+#include "forest_internal.h"
+
+struct tahoe_cstate {
+    uint4 *elems = nullptr;         // [bins][64] path elements, class-major (bin ranges class_bins[c] .. class_bins[c + 1])
+    float *one_minus_z = nullptr;   // [bins][64] 1 - zero fraction, from float64 (1 - (float)z loses it when z is near 1)
+    uint32_t *bin_info = nullptr;   // [bins] longest path of the bin (elements, root included) | rounds of ordered adds << 8
+    int *class_bins = nullptr;      // [num_classes + 1]
+    float *bias = nullptr;          // [num_classes] the bias column, float64 on the host, rounded once
+    float *class_div = nullptr;     // [num_classes] (float)Tc with TAHOE_OUT_AVG, else 1.0f
+    size_t bins = 0;
+    size_t paths = 0;
+    size_t path_elems = 0;          // elements of all paths, root elements included
+    int rows_per_tile = 0;          // rows of a workgroup's LDS tile (fixed per handle)
+    size_t lds_bytes = 0;
+};
+
+namespace tahoe {
+
+// Element word (.w): fid (15 bits) | rank in its path << 15 | (path length - 1) << 20 | round << 25 | missing_ok << 30 |
+// nan_ok << 31.  .x / .y / .z: the lower bound (x >= lower for every right edge), the upper bound (!(x >= upper) for every left
+// edge; NaN = none), the zero fraction (product of the edges' cover ratios).  A path's rank-0 lane is its root element (z = o
+// = 1) and carries the leaf value in .x.  Padding lanes are rank-0 paths of length 1.
+constexpr int kContribWaves = 4;      // waves per workgroup; bin b of a class goes to wave (b - first bin of the class) % 4
+constexpr int kContribMaxCols = 32767;
+constexpr uint32_t kElemFidMask = 0x7fffu;
+
+static inline uint32_t elem_word(int fid, int rank, int len, int round, bool missing_ok, bool nan_ok)
+{
+    return (uint32_t)fid | (uint32_t)rank << 15 | (uint32_t)(len - 1) << 20 | (uint32_t)round << 25 | (missing_ok ? 1u << 30 : 0u) |
+           (nan_ok ? 1u << 31 : 0u);
+}
+
+// 1 / k, correctly rounded (constant folding), for the uniform factors of the recursions
+__constant__ float c_inv[34] = {0.0f,        1.0f,        1.0f / 2.0f,  1.0f / 3.0f,  1.0f / 4.0f,  1.0f / 5.0f,  1.0f / 6.0f,
+                                1.0f / 7.0f,  1.0f / 8.0f,  1.0f / 9.0f,  1.0f / 10.0f, 1.0f / 11.0f, 1.0f / 12.0f, 1.0f / 13.0f,
+                                1.0f / 14.0f, 1.0f / 15.0f, 1.0f / 16.0f, 1.0f / 17.0f, 1.0f / 18.0f, 1.0f / 19.0f, 1.0f / 20.0f,
+                                1.0f / 21.0f, 1.0f / 22.0f, 1.0f / 23.0f, 1.0f / 24.0f, 1.0f / 25.0f, 1.0f / 26.0f, 1.0f / 27.0f,
+                                1.0f / 28.0f, 1.0f / 29.0f, 1.0f / 30.0f, 1.0f / 31.0f, 1.0f / 32.0f, 1.0f / 33.0f};
+
+__device__ __forceinline__ float lane_read(float v, int src_lane)
+{
+    return __int_as_float(__builtin_amdgcn_ds_bpermute(src_lane << 2, __float_as_int(v)));
+}
+__device__ __forceinline__ uint32_t lane_read_u(uint32_t v, int src_lane)
+{
+    return (uint32_t)__builtin_amdgcn_ds_bpermute(src_lane << 2, (int)v);
+}
+// value of lane - 1 (0 in lane 0): DPP wave_shr:1
+__device__ __forceinline__ float from_left_lane(float v)
+{
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138, 0xf, 0xf, false));
+}
+
+// One workgroup = a tile of R rows (staged in LDS) x all bins; wave w evaluates bins w, w + 4, ... of each class into its own
+// slab [R][F] of LDS; the four slabs are then summed in wave order and written out.  Every row sees the same operations in the
+// same order whatever its batch, tile or position: results are bitwise reproducible.
+__global__ __launch_bounds__(256) void contribs_kernel(float *__restrict__ phi, const float *__restrict__ data, size_t rows, int F,
+                                                       int C, int R, const uint4 *__restrict__ elems,
+                                                       const float *__restrict__ one_minus_z,
+                                                       const uint32_t *__restrict__ bin_info, const int *__restrict__ class_bins,
+                                                       const float *__restrict__ bias, const float *__restrict__ class_div,
+                                                       float missing)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const size_t row0 = (size_t)blockIdx.x * R;
+    const int nr = (int)min((size_t)R, rows - row0);
+    const int tile_n = nr * F;
+    const size_t slab_n = (size_t)R * F;
+    float *tile = smem;
+    float *slab = smem + slab_n * (1 + wave);
+    const float *s0 = smem + slab_n, *s1 = s0 + slab_n, *s2 = s1 + slab_n, *s3 = s2 + slab_n;
+    const float *src = data + row0 * F;
+    for (int i = tid; i < tile_n; i += 256) tile[i] = src[i];
+    const size_t out_row = (size_t)C * (F + 1);
+
+    for (int c = 0; c < C; ++c) {
+        for (int i = lane; i < tile_n; i += 64) slab[i] = 0.0f;
+        __syncthreads();
+        const int b_end = class_bins[c + 1];
+        for (int b = class_bins[c] + wave; b < b_end; b += kContribWaves) {
+            const uint4 e = elems[(size_t)b * 64 + lane];
+            const float om = one_minus_z[(size_t)b * 64 + lane];
+            const uint32_t info = bin_info[b];
+            const int steps = (int)(info & 0xffu), rounds = (int)(info >> 8);
+            const float lower = __uint_as_float(e.x), upper = __uint_as_float(e.y), z = __uint_as_float(e.z);
+            const int fid = (int)(e.w & kElemFidMask), rank = (int)((e.w >> 15) & 31u), ud = (int)((e.w >> 20) & 31u);
+            const int round = (int)((e.w >> 25) & 31u);
+            const bool missing_ok = (e.w >> 30) & 1u, nan_ok = (e.w >> 31) != 0;
+            const int gs = lane - rank;  // lane of the path's root element
+            const float leaf = lane_read(lower, gs);
+            const float zdiv = z / (float)(ud + 1);
+            const float udp1 = (float)(ud + 1);
+            for (int r = 0; r < nr; ++r) {
+                // one-fraction: does the row follow every edge of this feature on the path?  (go_right's rule)
+                const float x = tile[r * F + fid];
+                const bool is_missing = fabsf(x - missing) <= kMissingEps;
+                const bool o = is_missing ? missing_ok : (x != x ? nan_ok : (x >= lower && !(x >= upper)));
+                const uint32_t zo = e.z | (o ? 0x80000000u : 0u);
+                // extend: after step d, lanes of rank <= d hold the permutation weights of the first d + 1 elements
+                float pw = rank == 0 ? 1.0f : 0.0f;
+                for (int d = 1; d < steps; ++d) {
+                    const uint32_t s = lane_read_u(zo, min(gs + d, 63));
+                    const float zd = __uint_as_float(s & 0x7fffffffu), od = (s >> 31) ? 1.0f : 0.0f;
+                    const float left = from_left_lane(pw);
+                    const float inv = c_inv[d + 1];
+                    const float a = (float)max(d - rank, 0) * inv, bb = (float)rank * inv;
+                    const float np = pw * zd * a + od * left * bb;
+                    pw = d <= ud ? np : pw;
+                }
+                // unwound-path sum of this lane's element
+                float next = lane_read(pw, gs + ud);
+                float total = 0.0f;
+                for (int i = steps - 2; i >= 0; --i) {
+                    const float pwi = lane_read(pw, min(gs + i, 63));
+                    const float pre = (float)(ud - i) * zdiv;
+                    const float tmp = next * udp1 * c_inv[i + 1];
+                    const float t_one = total + tmp, n_one = pwi - tmp * pre;
+                    const float t_zero = pre > 0.0f ? total + pwi * __builtin_amdgcn_rcpf(pre) : total;
+                    if (i < ud) {
+                        total = o ? t_one : t_zero;
+                        next = o ? n_one : next;
+                    }
+                }
+                const float term = total * (o ? om : -z) * leaf;  // (one - zero) x leaf
+                // two lanes of a bin on one feature add in lane order (round = earlier lanes of the bin on that feature)
+                for (int k = 0; k < rounds; ++k)
+                    if (rank != 0 && round == k) slab[r * F + fid] += term;
+            }
+        }
+        __syncthreads();
+        const float div = class_div[c];
+        for (int i = tid; i < tile_n; i += 256) {
+            const int r = i / F, col = i - r * F;
+            const float v = ((s0[i] + s1[i]) + s2[i]) + s3[i];
+            phi[(row0 + r) * out_row + (size_t)c * (F + 1) + col] = v / div;
+        }
+        for (int r = tid; r < nr; r += 256) phi[(row0 + r) * out_row + (size_t)c * (F + 1) + F] = bias[c];
+        __syncthreads();
+    }
+}
+
+tahoe_status contribs_validate(const tahoe_dense_node *nodes, const tahoe_forest_params *p)
+{
+    const size_t per = (size_t)tahoe_tree_num_nodes(p->depth);
+    for (int t = 0; t < p->num_trees; ++t) {
+        const tahoe_dense_node *tree = nodes + (size_t)t * per;
+        std::vector<size_t> stack{0};
+        while (!stack.empty()) {
+            const size_t i = stack.back();
+            stack.pop_back();
+            if ((tree[i].bits >> 31) & 1) continue;  // leaf
+            const size_t l = 2 * i + 1, r = 2 * i + 2;
+            if (r >= per) continue;  // a non-leaf on the bottom level: create's structural check reports it
+            const float wl = tree[l].weight, wr = tree[r].weight;
+            if (!std::isfinite(wl) || !std::isfinite(wr) || !(wl >= 0.0f) || !(wr >= 0.0f) || !((double)wl + (double)wr > 0.0))
+                return fail(TAHOE_ERR_INVALID_FOREST,
+                            "tree %d node %zu: child weights %g and %g (TAHOE_CREATE_CONTRIBS needs finite covers >= 0 with a "
+                            "positive sum at every reachable internal node)",
+                            t, i, (double)wl, (double)wr);
+            stack.push_back(r);
+            stack.push_back(l);
+        }
+    }
+    return TAHOE_OK;
+}
+
+namespace {
+
+struct TreePaths {
+    std::vector<uint4> elems;       // paths one after the other, root element first, rank / length / round not yet set
+    std::vector<float> om;          // 1 - zero fraction of each element
+    std::vector<unsigned char> len;  // elements per path
+    double expect = 0.0;             // E_t = sum over leaves of leaf x product of cover ratios
+};
+
+struct Elem {
+    int fid;
+    float lower, upper;
+    bool missing_ok, nan_ok;
+    double rho;
+};
+
+void tree_paths(const tahoe_dense_node *tree, size_t per, TreePaths &out)
+{
+    struct Edge {
+        size_t node;
+        bool right;
+    };
+    Edge edges[32];
+    // iterative pre-order walk (left before right): leaves in heap order left to right
+    struct Frame {
+        size_t node;
+        int depth;
+        bool right;
+    };
+    std::vector<Frame> stack{{0, 0, false}};
+    while (!stack.empty()) {
+        const Frame fr = stack.back();
+        stack.pop_back();
+        if (fr.depth > 0) edges[fr.depth - 1] = {(fr.node - 1) / 2, fr.right};
+        const tahoe_dense_node &n = tree[fr.node];
+        if (!((n.bits >> 31) & 1)) {
+            stack.push_back({2 * fr.node + 2, fr.depth + 1, true});
+            stack.push_back({2 * fr.node + 1, fr.depth + 1, false});
+            continue;
+        }
+        Elem el[32];
+        int ne = 0;
+        double prod = 1.0;
+        for (int k = 0; k < fr.depth; ++k) {
+            const tahoe_dense_node &a = tree[edges[k].node];
+            const int fid = a.bits & 0x3fffffff;
+            const bool def_left = (a.bits >> 30) & 1;
+            const float thr = a.val;
+            const double wl = tree[2 * edges[k].node + 1].weight, wr = tree[2 * edges[k].node + 2].weight;
+            const double rho = (edges[k].right ? wr : wl) / (wl + wr);
+            prod *= rho;
+            int j = 0;
+            while (j < ne && el[j].fid != fid) ++j;
+            if (j == ne) el[ne++] = {fid, -INFINITY, NAN, true, true, 1.0};
+            Elem &m = el[j];
+            m.rho *= rho;
+            if (edges[k].right) {  // x >= thr; NaN never satisfies it, missing does iff the default is right
+                m.lower = (std::isnan(thr) || std::isnan(m.lower)) ? NAN : std::max(m.lower, thr);
+                m.nan_ok = false;
+                m.missing_ok = m.missing_ok && !def_left;
+            } else {  // !(x >= thr); a NaN threshold sends every non-missing row left
+                if (!std::isnan(thr)) m.upper = std::isnan(m.upper) ? thr : std::min(m.upper, thr);
+                m.missing_ok = m.missing_ok && def_left;
+            }
+        }
+        out.expect += (double)n.val * prod;
+        if (ne == 0) continue;  // a root leaf: all of it is bias
+        uint4 root;
+        memcpy(&root.x, &n.val, 4);
+        root.y = 0u;
+        const float one = 1.0f;
+        memcpy(&root.z, &one, 4);
+        root.w = 0u;
+        out.elems.push_back(root);
+        out.om.push_back(0.0f);
+        for (int j = 0; j < ne; ++j) {
+            uint4 u;
+            const float zf = (float)el[j].rho;
+            memcpy(&u.x, &el[j].lower, 4);
+            memcpy(&u.y, &el[j].upper, 4);
+            memcpy(&u.z, &zf, 4);
+            u.w = elem_word(el[j].fid, 0, 1, 0, el[j].missing_ok, el[j].nan_ok);
+            out.elems.push_back(u);
+            out.om.push_back((float)(1.0 - el[j].rho));
+        }
+        out.len.push_back((unsigned char)(ne + 1));
+    }
+}
+
+}  // namespace
+
+tahoe_status contribs_build(tahoe_forest *f, const tahoe_dense_node *nodes)
+{
+    const int F = f->p.num_cols;
+    // LDS: the row tile and four slabs, R rows each; R is the largest power of two <= 64 that fits 80 KiB (two workgroups
+    // per CU), else the whole LDS
+    size_t R = 64;
+    const size_t per_row = 5 * (size_t)F * sizeof(float);
+    while (R > 1 && R * per_row > 80 * 1024) R /= 2;
+    if (F > kContribMaxCols || per_row > (size_t)f->lds_limit)
+        return fail(TAHOE_ERR_UNSUPPORTED, "TAHOE_CREATE_CONTRIBS needs 20 B of LDS per column (num_cols %d; device offers %d B)", F,
+                    f->lds_limit);
+
+    const int C = f->num_classes;
+    const size_t T = (size_t)f->p.num_trees, Tc = (size_t)f->class_trees;
+    const size_t per = (size_t)tahoe_tree_num_nodes(f->p.depth);
+    std::vector<TreePaths> trees(T);  // in the caller's tree numbering
+    parallel_for(T, 4, [&](size_t lo, size_t hi) {
+        for (size_t t = lo; t < hi; ++t) tree_paths(nodes + t * per, per, trees[t]);
+    });
+
+    std::vector<uint4> h_elems;
+    std::vector<float> h_om;
+    std::vector<uint32_t> h_info;
+    std::vector<int> h_class_bins(C + 1, 0);
+    std::vector<float> h_bias(C), h_div(C);
+    size_t n_paths = 0, n_elems = 0;
+    uint4 pad;
+    {
+        const float one = 1.0f;
+        pad.x = pad.y = 0u;
+        memcpy(&pad.z, &one, 4);
+        pad.w = 0u;
+    }
+    // next-fit packing of each class's paths, in tree order then leaf order
+    for (int c = 0; c < C; ++c) {
+        h_class_bins[c] = (int)(h_elems.size() / 64);
+        size_t start = h_elems.size();
+        int fill = 0, steps = 0;
+        auto flush = [&]() {
+            if (fill == 0) return;
+            h_elems.resize(start + 64, pad);
+            h_om.resize(start + 64, 0.0f);
+            int rounds = 0;
+            for (int l = 0; l < 64; ++l) {
+                uint4 &u = h_elems[start + l];
+                if (((u.w >> 15) & 31u) == 0) continue;
+                int round = 0;
+                for (int k = 0; k < l; ++k) {
+                    const uint4 &v = h_elems[start + k];
+                    if (((v.w >> 15) & 31u) != 0 && (v.w & kElemFidMask) == (u.w & kElemFidMask)) ++round;
+                }
+                u.w |= (uint32_t)round << 25;
+                rounds = std::max(rounds, round + 1);
+            }
+            h_info.push_back((uint32_t)steps | (uint32_t)rounds << 8);
+            start = h_elems.size();
+            fill = 0;
+            steps = 0;
+        };
+        double expect = 0.0;
+        for (size_t k = 0; k < Tc; ++k) {
+            const size_t t = k * (size_t)C + (size_t)c;
+            TreePaths &tp = trees[t];
+            expect += tp.expect;
+            size_t off = 0;
+            for (unsigned char len : tp.len) {
+                if (fill + len > 64) flush();
+                for (int j = 0; j < len; ++j) {
+                    uint4 u = tp.elems[off + j];
+                    u.w = (u.w & ~(0x3ffu << 15)) | (uint32_t)j << 15 | (uint32_t)(len - 1) << 20;
+                    h_elems.push_back(u);
+                    h_om.push_back(tp.om[off + j]);
+                }
+                fill += len;
+                steps = std::max(steps, (int)len);
+                off += len;
+                ++n_paths;
+                n_elems += len;
+            }
+            std::vector<uint4>().swap(tp.elems);
+            std::vector<float>().swap(tp.om);
+        }
+        flush();
+        const bool avg = (f->p.output & TAHOE_OUT_AVG) != 0 && Tc > 0;
+        h_bias[c] = (float)((avg ? expect / (double)Tc : expect) + (double)f->p.global_bias);
+        h_div[c] = avg ? (float)Tc : 1.0f;
+    }
+    h_class_bins[C] = (int)(h_elems.size() / 64);
+
+    tahoe_cstate *cs = new (std::nothrow) tahoe_cstate();
+    if (!cs) return fail(TAHOE_ERR_NO_MEMORY, "contribs_build");
+    f->cs = cs;
+    cs->bins = h_info.size();
+    cs->paths = n_paths;
+    cs->path_elems = n_elems;
+    cs->rows_per_tile = (int)R;
+    cs->lds_bytes = R * per_row;
+    auto up = [f](auto **dst, const auto &v) -> hipError_t {
+        const size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(v[0]);
+        hipError_t e = hipMalloc(reinterpret_cast<void **>(dst), bytes);
+        if (e != hipSuccess) return e;
+        f->device_bytes += bytes;
+        return v.empty() ? hipSuccess : hipMemcpy(*dst, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice);
+    };
+    hipError_t e;
+    if ((e = up(&cs->elems, h_elems)) != hipSuccess || (e = up(&cs->one_minus_z, h_om)) != hipSuccess ||
+        (e = up(&cs->bin_info, h_info)) != hipSuccess ||
+        (e = up(&cs->class_bins, h_class_bins)) != hipSuccess || (e = up(&cs->bias, h_bias)) != hipSuccess ||
+        (e = up(&cs->class_div, h_div)) != hipSuccess)
+        return fail(TAHOE_ERR_HIP, "contribs_build: upload failed: %s", hipGetErrorString(e));
+    if ((e = allow_max_lds(reinterpret_cast<const void *>(&contribs_kernel), f->lds_limit)) != hipSuccess)
+        return fail(TAHOE_ERR_HIP, "hipFuncSetAttribute(contribs) failed: %s", hipGetErrorString(e));
+    return TAHOE_OK;
+}
+
+void contribs_destroy(tahoe_forest *f)
+{
+    tahoe_cstate *cs = f->cs;
+    if (!cs) return;
+    if (cs->elems) (void)hipFree(cs->elems);
+    if (cs->one_minus_z) (void)hipFree(cs->one_minus_z);
+    if (cs->bin_info) (void)hipFree(cs->bin_info);
+    if (cs->class_bins) (void)hipFree(cs->class_bins);
+    if (cs->bias) (void)hipFree(cs->bias);
+    if (cs->class_div) (void)hipFree(cs->class_div);
+    delete cs;
+    f->cs = nullptr;
+}
+
+}  // namespace tahoe
+
+using namespace tahoe;
+
+extern "C" tahoe_status tahoe_forest_predict_contribs(tahoe_forest *f, float *phi_dev, const float *data_dev, size_t rows,
+                                                      void *stream)
+{
+    if (!f) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_contribs: null forest");
+    if (f->sp)
+        return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_contribs: a sparse handle has no node covers (weights); "
+                                           "contributions need a dense handle created with TAHOE_CREATE_CONTRIBS");
+    if (!f->cs)
+        return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_contribs: the handle was created without TAHOE_CREATE_CONTRIBS "
+                                           "and has no path tables");
+    if (rows == 0) return TAHOE_OK;
+    if (!phi_dev || !data_dev) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_contribs: null argument");
+    const tahoe_cstate *cs = f->cs;
+    DeviceGuard on_device(f->device);
+    const size_t R = (size_t)cs->rows_per_tile;
+    const size_t grid = (rows + R - 1) / R;
+    hipLaunchKernelGGL(contribs_kernel, dim3((unsigned)grid), dim3(256), cs->lds_bytes, (hipStream_t)stream, phi_dev, data_dev, rows,
+                       f->p.num_cols, f->num_classes, (int)R, cs->elems, cs->one_minus_z, cs->bin_info, cs->class_bins, cs->bias, cs->class_div,
+                       f->p.missing);
+    TAHOE_HIP_TRY(hipGetLastError());
+    return TAHOE_OK;
+}

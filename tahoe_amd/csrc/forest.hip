@@ -827,23 +827,6 @@ static void launch_tilering(tahoe_forest *f, float *sums, uint32_t *leaf_out, co
                            f->p.num_trees, f->depth, f->top_levels, stride, f->p.missing, vec4_ok, f->error_flag);
 }
 
-// A process that drives several GPUs (one handle per device) calls predict with any device current: the launches
-// must be issued with the handle's device current.  Restores the caller's device on scope exit.
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int want)
-    {
-        int cur = -1;
-        if (hipGetDevice(&cur) == hipSuccess && cur != want && hipSetDevice(want) == hipSuccess) prev = cur;
-    }
-    ~DeviceGuard()
-    {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-    DeviceGuard(const DeviceGuard &) = delete;
-    DeviceGuard &operator=(const DeviceGuard &) = delete;
-};
-
 // sums_in (optional, may be `sums` itself): running float32 sums of the trees BEFORE this forest -- every kernel then
 // continues that sum in tree order instead of starting from 0.0f (tahoe_forest_predict_accumulate).
 static tahoe_status launch_traversal(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data,
@@ -1016,7 +999,8 @@ static tahoe_status create_dense(tahoe_forest **out, const tahoe_dense_node *nod
                                  int num_classes)
 {
     if (!out || !p) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_create: null argument");
-    if ((flags & ~(unsigned)TAHOE_CREATE_PROB_RELAYOUT) != 0) return fail(TAHOE_ERR_INVALID_ARG, "unknown create flags 0x%x", flags);
+    if ((flags & ~(unsigned)(TAHOE_CREATE_PROB_RELAYOUT | TAHOE_CREATE_CONTRIBS)) != 0)
+        return fail(TAHOE_ERR_INVALID_ARG, "unknown create flags 0x%x", flags);
     *out = nullptr;
     // check_params, BaseTahoeTest.h:490-516
     if (p->depth < 0 || p->depth > 30) return fail(TAHOE_ERR_INVALID_ARG, "depth must be in [0,30], got %d", p->depth);
@@ -1027,6 +1011,10 @@ static tahoe_status create_dense(tahoe_forest **out, const tahoe_dense_node *nod
     if ((p->output & ~(TAHOE_OUT_AVG | TAHOE_OUT_SIGMOID | TAHOE_OUT_THRESHOLD | (num_classes > 1 ? TAHOE_OUT_SOFTMAX : 0))) != 0)
         return fail(TAHOE_ERR_INVALID_ARG, "output should be a combination of RAW, AVG, SIGMOID and THRESHOLD");
     if (p->num_trees > 0 && !nodes) return fail(TAHOE_ERR_INVALID_ARG, "nodes is null");
+    if (flags & TAHOE_CREATE_CONTRIBS) {  // the cover weights, on the caller's nodes, before a device is touched
+        const tahoe_status cs = contribs_validate(nodes, p);
+        if (cs != TAHOE_OK) return cs;
+    }
 
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
@@ -1284,6 +1272,13 @@ static tahoe_status create_dense(tahoe_forest **out, const tahoe_dense_node *nod
         if ((e = allow_max_lds(reinterpret_cast<const void *>(&tileblock_kernel<64, false>), f->lds_limit)) != hipSuccess) return bail(e, "hipFuncSetAttribute(tileblock)");
         if ((e = allow_max_lds(reinterpret_cast<const void *>(&tileblock_kernel<64, true>), f->lds_limit)) != hipSuccess) return bail(e, "hipFuncSetAttribute(tileblock)");
     }
+    if (flags & TAHOE_CREATE_CONTRIBS) {
+        const tahoe_status cs = contribs_build(f, nodes);
+        if (cs != TAHOE_OK) {
+            tahoe_forest_destroy(f);
+            return cs;
+        }
+    }
     *out = f;
     return TAHOE_OK;
 }
@@ -1326,6 +1321,7 @@ void tahoe_forest_destroy(tahoe_forest *f)
     qring_destroy(f);
     sparse_destroy(f);
     widef_destroy(f);
+    contribs_destroy(f);
     for (hipEvent_t e : f->ev_start) (void)hipEventDestroy(e);
     for (hipEvent_t e : f->ev_mid) (void)hipEventDestroy(e);
     for (hipEvent_t e : f->ev_stop) (void)hipEventDestroy(e);

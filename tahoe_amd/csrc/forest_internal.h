@@ -12,6 +12,7 @@ struct tahoe_qstate;  // quantised views + workspace, owned by qring.hip
 struct tahoe_sstate;  // sparse (irregular) forest, owned by sparse.hip
 struct tahoe_pstate;  // host-batch upload pipeline, owned by pipeline.hip
 struct tahoe_wstate;  // float32 walk for wide rows, owned by widef.hip
+struct tahoe_cstate;  // TreeSHAP path tables (TAHOE_CREATE_CONTRIBS), owned by contribs.hip
 
 namespace tahoe {
 
@@ -70,6 +71,7 @@ struct tahoe_forest {
     tahoe_sstate *sp = nullptr;    // non-null: this handle is a sparse forest (sparse.hip); the dense views are unused
     tahoe_pstate *pipe = nullptr;  // tahoe_forest_predict_host: chunk buffers, streams, events (created on first use)
     tahoe_wstate *wf = nullptr;    // non-null: TILERING runs the wide-row float32 form (widef.hip)
+    tahoe_cstate *cs = nullptr;    // non-null: created with TAHOE_CREATE_CONTRIBS (contribs.hip)
     size_t device_bytes = 0;
     // Multi-class handle (tahoe_forest_create_multiclass): the trees are stored class-major -- internal tree p belongs to class
     // p / class_trees and is original tree (p % class_trees) * num_classes + p / class_trees -- and every consumer writes
@@ -127,6 +129,23 @@ inline hipError_t allow_max_lds(const void *fn, int limit)
     if (e != hipSuccess) return e;
     return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, limit - (int)a.sharedSizeBytes);
 }
+
+// A process that drives several GPUs (one handle per device) calls predict with any device current: the launches
+// must be issued with the handle's device current.  Restores the caller's device on scope exit.
+struct DeviceGuard {
+    int prev = -1;
+    explicit DeviceGuard(int want)
+    {
+        int cur = -1;
+        if (hipGetDevice(&cur) == hipSuccess && cur != want && hipSetDevice(want) == hipSuccess) prev = cur;
+    }
+    ~DeviceGuard()
+    {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+    DeviceGuard(const DeviceGuard &) = delete;
+    DeviceGuard &operator=(const DeviceGuard &) = delete;
+};
 
 // The branch rule of infer_one_tree, BaseTahoeTest.h:450-453: 1 = right child.
 __device__ __forceinline__ uint32_t go_right(float x, float thr, bool def_left, float missing)
@@ -189,5 +208,11 @@ tahoe_status widef_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, cons
                           const float *sums_in);
 void widef_destroy(tahoe_forest *f);
 tahoe_status widef_reserve(tahoe_forest *f, size_t rows);
+
+// per-feature contributions (contribs.hip).  contribs_validate runs on the caller's nodes before any device is touched;
+// contribs_build builds the path tables of a validated forest from the caller's nodes (not the re-laid-out ones).
+tahoe_status contribs_validate(const tahoe_dense_node *nodes, const tahoe_forest_params *p);
+tahoe_status contribs_build(tahoe_forest *f, const tahoe_dense_node *nodes);
+void contribs_destroy(tahoe_forest *f);
 
 }  // namespace tahoe

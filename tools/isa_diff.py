@@ -8,7 +8,8 @@ then   python tools/isa_diff.py <old_dir> <new_dir> [forest qring ...] [-v]
 (dirs = where the *-hip-amdgcn-amd-amdhsa-gfx950.s files are).  Local branch labels are renumbered and the kernel descriptor's
 name, section and kernarg_size lines are left out of the comparison (a kernel argument appended at the end changes only those).
 A template flag appended with a default (`bool MC = false`) is matched by dropping a trailing `, false` template argument; new
-instantiations with `, true` there are counted, not compared."""
+instantiations with `, true` there are counted, not compared.  --exact: both builds have the same template parameters (no appended
+flag): functions are matched by their full names.  A translation unit that exists only in <new_dir> is listed as new."""
 import difflib
 import re
 import subprocess
@@ -56,17 +57,21 @@ def key(name, new):
 
 def main(argv):
     verbose = "-v" in argv
-    args = [a for a in argv if a != "-v"]
+    exact = "--exact" in argv
+    args = [a for a in argv if a not in ("-v", "--exact")]
     old_dir, new_dir, units = args[0], args[1], args[2:] or ["forest", "qring"]
     changed = 0
     for unit in units:
-        old = functions(f"{old_dir}/{unit}-hip-amdgcn-amd-amdhsa-gfx950.s")
+        try:
+            old = functions(f"{old_dir}/{unit}-hip-amdgcn-amd-amdhsa-gfx950.s")
+        except FileNotFoundError:
+            old = {}
         new = functions(f"{new_dir}/{unit}-hip-amdgcn-amd-amdhsa-gfx950.s")
         od, nd = demangle(list(old)), demangle(list(new))
         old_by = {key(od[k], False): k for k in old}
         new_by = {}
         for k in new:
-            kk = key(nd[k], True)
+            kk = key(nd[k], not exact)
             if kk is not None:
                 new_by[kk] = k
         same = 0
@@ -82,7 +87,7 @@ def main(argv):
                 if verbose:
                     print("\n".join(list(difflib.unified_diff(old[k], new[new_by[name]], lineterm=""))[:60]))
         added = [n for n in new_by if n not in old_by]
-        flagged = sum(1 for k in new if key(nd[k], True) is None)
+        flagged = 0 if exact else sum(1 for k in new if key(nd[k], True) is None)
         print(f"{unit}: {same} of {len(old_by)} pre-existing functions identical; new: {added}; new flagged instantiations: {flagged}")
     return 1 if changed else 0
 
