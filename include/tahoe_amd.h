@@ -222,6 +222,23 @@ int tahoe_forest_num_classes(const tahoe_forest *f);
  * TAHOE_CREATE_CONTRIBS, or a sparse handle: TAHOE_ERR_UNSUPPORTED, nothing launched. */
 tahoe_status tahoe_forest_predict_contribs(tahoe_forest *f, float *phi_dev, const float *data_dev, size_t rows, void *stream);
 
+/* SHAP interaction values (XGBoost pred_interactions, SHAP's TreeExplainer.shap_interaction_values) of the game that
+ * tahoe_forest_predict_contribs explains: same v(S), branch rule, cover ratios and class trees c, c + C, ...; the margin before
+ * SIGMOID / THRESHOLD / SOFTMAX.  out_dev[((row * C + c) * (F + 1) + i) * (F + 1) + j], F = num_cols, C = num_classes:
+ *  - i != j, both < F: the Shapley interaction index sum_{S in N \ {i,j}} |S|! (M - |S| - 2)! / (2 (M - 1)!) (v(S + {i,j}) -
+ *    v(S + {i}) - v(S + {j}) + v(S)) summed over trees; per path leaf (o_i - z_i)(o_j - z_j) U_j(P \ {i}) / 2, U_j(P \ {i}) the
+ *    unwound-path sum of j on the path without i (XGBoost's conditioned TreeSHAP); with TAHOE_OUT_AVG divided by (float)Tc.
+ *    out[i][j] and out[j][i] carry the same bits; a pair that shares no path is +0.0f.
+ *  - i < F: out[i][i] = phi_i - S_i in float32, phi_i bit for bit the value of tahoe_forest_predict_contribs, S_i the sum of
+ *    out[i][j] over j < F, j != i, added in increasing j from 0.0f: each row sums to phi_i up to that rounding.
+ *  - out[F][F] is the bias column of tahoe_forest_predict_contribs, bit for bit; out[i][F] and out[F][i] (i < F) are +0.0f.
+ * Deterministic as tahoe_forest_predict_contribs (any batch, strategy, re-layout; class c = class c's sub-forest).  The
+ * off-diagonal sums run in LDS for num_cols <= 71 and in place in out_dev above that (no other limit than the create flag's).
+ * Asynchronous on `stream`; allocates nothing (graph-capturable).  rows == 0: TAHOE_OK, nothing launched; NULL out_dev /
+ * data_dev with rows > 0, or rows * C * (F + 1)^2 * 4 overflowing size_t: TAHOE_ERR_INVALID_ARG; a handle created without
+ * TAHOE_CREATE_CONTRIBS, or a sparse handle: TAHOE_ERR_UNSUPPORTED; nothing launched on any refusal. */
+tahoe_status tahoe_forest_predict_interactions(tahoe_forest *f, float *out_dev, const float *data_dev, size_t rows, void *stream);
+
 /* ---- sparse (irregular) forests: sparse_node_t Struct.h:50-54, sparse_storage Struct.h:343-354,
  * init_sparse / sparse_forest::init (BaseTahoeTest.h:766-772, Struct.h:2329-2343) ---- */
 typedef struct {

@@ -123,6 +123,7 @@ _PROTOS = {
     "tahoe_forest_create_multiclass": (_i, [C.POINTER(_vp), _vp, C.POINTER(ForestParams), _i, C.c_uint]),
     "tahoe_forest_num_classes": (_i, [_vp]),
     "tahoe_forest_predict_contribs": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "tahoe_forest_predict_interactions": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "tahoe_sparse_forest_create": (_i, [C.POINTER(_vp), _vp, _vp, C.POINTER(ForestParams)]),
     "tahoe_dense_to_sparse": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz)]),
     "tahoe_synth_sparse_forest": (_i, [_vp, _vp, C.POINTER(_sz), _i, _i, _i, _i, _f, _i, C.c_uint64]),
@@ -467,6 +468,22 @@ class Forest:
         assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == shape
         _check(lib.tahoe_forest_predict_contribs(self._h, _ptr(out), _ptr(data), rows, _stream(stream)),
                "tahoe_forest_predict_contribs")
+        return out
+
+    def predict_interactions(self, data, out=None, stream=None):
+        """SHAP interaction values (tahoe_forest_predict_interactions): [rows, num_cols + 1, num_cols + 1] float32, or
+        [rows, num_classes, num_cols + 1, num_cols + 1] on a multi-class handle; index num_cols is the bias.  Needs
+        contribs=True."""
+        import torch
+
+        self._check_data(data)
+        rows, F1 = data.shape[0], self.num_cols + 1
+        shape = (rows, self.num_classes, F1, F1) if self.num_classes > 1 else (rows, F1, F1)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=data.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == shape
+        _check(lib.tahoe_forest_predict_interactions(self._h, _ptr(out), _ptr(data), rows, _stream(stream)),
+               "tahoe_forest_predict_interactions")
         return out
 
     def set_strategy(self, strategy: int) -> None:

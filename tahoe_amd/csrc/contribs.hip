@@ -26,6 +26,11 @@ struct tahoe_cstate {
     size_t path_elems = 0;          // elements of all paths, root elements included
     int rows_per_tile = 0;          // rows of a workgroup's LDS tile (fixed per handle)
     size_t lds_bytes = 0;
+    // tahoe_forest_predict_interactions: the form (LDS slabs or in place), its rows per workgroup (slabs) or per wave (in
+    // place), and its LDS bytes per workgroup; fixed per handle by num_cols
+    bool inter_slabs = false;
+    int inter_rows = 0;
+    size_t inter_lds_bytes = 0;
 };
 
 namespace tahoe {
@@ -68,14 +73,16 @@ __device__ __forceinline__ float from_left_lane(float v)
 // One workgroup = a tile of R rows (staged in LDS) x all bins; wave w evaluates bins w, w + 4, ... of each class into its own
 // slab [R][F] of LDS; the four slabs are then summed in wave order and written out.  Every row sees the same operations in the
 // same order whatever its batch, tile or position: results are bitwise reproducible.
-__global__ __launch_bounds__(256) void contribs_kernel(float *__restrict__ phi, const float *__restrict__ data, size_t rows, int F,
-                                                       int C, int R, const uint4 *__restrict__ elems,
-                                                       const float *__restrict__ one_minus_z,
-                                                       const uint32_t *__restrict__ bin_info, const int *__restrict__ class_bins,
-                                                       const float *__restrict__ bias, const float *__restrict__ class_div,
-                                                       float missing)
+// SPARE = false: phi[rows][C][F + 1] (contribs_kernel).  SPARE = true: the same values into row F of each (row, class) matrix of
+// out[rows][C][F + 1][F + 1] (tahoe_forest_predict_interactions, contribs_spare_kernel).
+template <bool SPARE>
+__device__ __forceinline__ void contribs_tile(float *__restrict__ phi, const float *__restrict__ data, size_t rows, int F, int C,
+                                              int R, const uint4 *__restrict__ elems, const float *__restrict__ one_minus_z,
+                                              const uint32_t *__restrict__ bin_info, const int *__restrict__ class_bins,
+                                              const float *__restrict__ bias, const float *__restrict__ class_div, float missing)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
+    if (SPARE) phi += (size_t)F * (F + 1);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const size_t row0 = (size_t)blockIdx.x * R;
@@ -87,7 +94,8 @@ __global__ __launch_bounds__(256) void contribs_kernel(float *__restrict__ phi, 
     const float *s0 = smem + slab_n, *s1 = s0 + slab_n, *s2 = s1 + slab_n, *s3 = s2 + slab_n;
     const float *src = data + row0 * F;
     for (int i = tid; i < tile_n; i += 256) tile[i] = src[i];
-    const size_t out_row = (size_t)C * (F + 1);
+    const size_t mat = (size_t)(F + 1) * (F + 1);
+    const size_t out_row = SPARE ? (size_t)C * mat : (size_t)C * (F + 1);
 
     for (int c = 0; c < C; ++c) {
         for (int i = lane; i < tile_n; i += 64) slab[i] = 0.0f;
@@ -148,12 +156,239 @@ __global__ __launch_bounds__(256) void contribs_kernel(float *__restrict__ phi, 
         for (int i = tid; i < tile_n; i += 256) {
             const int r = i / F, col = i - r * F;
             const float v = ((s0[i] + s1[i]) + s2[i]) + s3[i];
-            phi[(row0 + r) * out_row + (size_t)c * (F + 1) + col] = v / div;
+            phi[(row0 + r) * out_row + (size_t)c * (SPARE ? mat : (F + 1)) + col] = v / div;
         }
-        for (int r = tid; r < nr; r += 256) phi[(row0 + r) * out_row + (size_t)c * (F + 1) + F] = bias[c];
+        for (int r = tid; r < nr; r += 256) phi[(row0 + r) * out_row + (size_t)c * (SPARE ? mat : (F + 1)) + F] = bias[c];
         __syncthreads();
     }
 }
+
+__global__ __launch_bounds__(256) void contribs_kernel(float *__restrict__ phi, const float *__restrict__ data, size_t rows, int F,
+                                                       int C, int R, const uint4 *__restrict__ elems,
+                                                       const float *__restrict__ one_minus_z,
+                                                       const uint32_t *__restrict__ bin_info, const int *__restrict__ class_bins,
+                                                       const float *__restrict__ bias, const float *__restrict__ class_div,
+                                                       float missing)
+{
+    contribs_tile<false>(phi, data, rows, F, C, R, elems, one_minus_z, bin_info, class_bins, bias, class_div, missing);
+}
+
+// ---- SHAP interaction values (tahoe_forest_predict_interactions) ----
+// Output: out[row][c] is an (F + 1) x (F + 1) matrix M.  contribs_spare_kernel first writes phi, with contribs_kernel's exact
+// bits, into its row F (a row that ends up all zero but the bias corner, so it serves as scratch); interactions_kernel then
+// writes the rest.  Off-diagonal: for every path, every conditioning element k (rank 1 .. L - 2) and every element j of rank > k,
+// the term leaf (o_j - z_j)(o_k - z_k) U_j(P \ {k}) / 2 goes into both M[fid_k][fid_j] and M[fid_j][fid_k], where U_j(P \ {k})
+// is j's unwound-path sum on the path with k removed (XGBoost's PredictInteractionContributions, GPUTreeShap's conditioned
+// TreeSHAP).  Lanes of one bin that hit the same feature pair at the same k add in lane order (one round per earlier lane on
+// that pair); both entries of a pair see the same adds in the same order, so M is exactly symmetric.  Diagonal: M[i][i] =
+// phi_i - sum_{j != i} M[i][j] (ascending j from 0.0f), with phi_i read back from row F.
+//
+// Two forms, fixed per handle at create by F alone:
+//   SLABS (4 (F^2 + F / 4) floats per row fit 80 KiB, F <= 71): a workgroup of R rows; wave w evaluates bins w, w + 4, ... of a
+//     class into its own LDS slab [R][F][F]; the slabs are summed in wave order, as contribs_kernel does.
+//   in place (wider rows): wave w of a workgroup owns row 4 blockIdx + w and evaluates every bin of a class in order, adding
+//     straight into that row's matrix in the output; dependent read-modify-writes of one wave are separated by an explicit
+//     s_waitcnt vmcnt(0).
+constexpr int kInterSlabMaxBytes = 80 * 1024;
+constexpr int kInterMaxRows = 32;  // rows of a tile: one bit each in the per-lane one-fraction mask
+
+__global__ __launch_bounds__(256) void contribs_spare_kernel(float *__restrict__ out, const float *__restrict__ data, size_t rows,
+                                                             int F, int C, int R, const uint4 *__restrict__ elems,
+                                                             const float *__restrict__ one_minus_z,
+                                                             const uint32_t *__restrict__ bin_info,
+                                                             const int *__restrict__ class_bins, const float *__restrict__ bias,
+                                                             const float *__restrict__ class_div, float missing)
+{
+    contribs_tile<true>(out, data, rows, F, C, R, elems, one_minus_z, bin_info, class_bins, bias, class_div, missing);
+}
+
+__device__ __forceinline__ void vm_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+
+// The off-diagonal terms of bins b_first, b_first + b_step, ... < b_end for the nr rows of `tile` (row r at tile + r F), added
+// into acc + r acc_row + a ld + b for the pair (a, b).
+template <bool SLABS>
+__device__ __forceinline__ void interaction_bins(float *acc, size_t acc_row, int ld, const float *tile, int nr, int F, int b_first,
+                                                 int b_end, int b_step, const uint4 *__restrict__ elems,
+                                                 const float *__restrict__ one_minus_z, const uint32_t *__restrict__ bin_info,
+                                                 float missing)
+{
+    const int lane = threadIdx.x & 63;
+    if (nr == 0) return;  // a wave past the last row (in place)
+    for (int b = b_first; b < b_end; b += b_step) {
+        const int steps = (int)(bin_info[b] & 0xffu);
+        if (steps < 3) continue;  // no path with two features
+        const uint4 e = elems[(size_t)b * 64 + lane];
+        const float om = one_minus_z[(size_t)b * 64 + lane];
+        const float lower = __uint_as_float(e.x), upper = __uint_as_float(e.y), z = __uint_as_float(e.z);
+        const int fid = (int)(e.w & kElemFidMask), rank = (int)((e.w >> 15) & 31u), ud = (int)((e.w >> 20) & 31u);
+        const bool missing_ok = (e.w >> 30) & 1u, nan_ok = (e.w >> 31) != 0;
+        const int gs = lane - rank;  // lane of the path's root element
+        const float leaf = lane_read(lower, gs);
+        // one-fractions of this lane's element, bit r for row r (go_right's rule, as in contribs_tile)
+        uint32_t omask = 0;
+        for (int r = 0; r < nr; ++r) {
+            const float x = tile[r * F + fid];
+            const bool is_missing = fabsf(x - missing) <= kMissingEps;
+            const bool o = is_missing ? missing_ok : (x != x ? nan_ok : (x >= lower && !(x >= upper)));
+            omask |= (o ? 1u : 0u) << r;
+        }
+        // on the path without element k, element j (rank > k) has unique depth ud - 1
+        const int udk = ud - 1;
+        const float zdiv = z / (float)max(ud, 1);
+        const float udkp1 = (float)ud;
+        for (int k = 1; k <= steps - 2; ++k) {
+            const int lk = min(gs + k, 63);
+            const int fk = (int)lane_read_u((uint32_t)fid, lk);
+            const float om_k = lane_read(om, lk), z_k = lane_read(z, lk);
+            const uint32_t omask_k = lane_read_u(omask, lk);
+            const bool pair = rank > k;
+            const uint64_t pairs = __ballot(pair);
+            if (pairs == 0) continue;
+            // order of the adds: earlier lanes of the bin on the same unordered pair {fid, fk} (row-independent)
+            const uint32_t key = pair ? (uint32_t)min(fid, fk) << 15 | (uint32_t)max(fid, fk) : 0xffffffffu;
+            int round = 0;
+            for (uint64_t m = pairs; m; m &= m - 1) {
+                const int l = __builtin_ctzll(m);
+                round += ((uint32_t)__builtin_amdgcn_readlane((int)key, l) == key && l < lane) ? 1 : 0;
+            }
+            int rounds = 0;
+            while (__ballot(pair && round >= rounds)) ++rounds;
+            const int nrk = rank > k ? rank - 1 : rank;  // position on the path without element k
+            const bool skip_left = rank == k + 1;        // the left neighbour on that path is two lanes down
+            for (int r = 0; r < nr; ++r) {
+                const bool o = (omask >> r) & 1u, ok = (omask_k >> r) & 1u;
+                const uint32_t zo = e.z | (o ? 0x80000000u : 0u);
+                // extend over the path without element k: after step d, positions <= d hold the permutation weights
+                float pw = rank == 0 ? 1.0f : 0.0f;
+                for (int d = 1; d < steps - 1; ++d) {
+                    const uint32_t s = lane_read_u(zo, min(gs + (d < k ? d : d + 1), 63));
+                    const float zd = __uint_as_float(s & 0x7fffffffu), od = (s >> 31) ? 1.0f : 0.0f;
+                    const float left1 = from_left_lane(pw);
+                    const float left2 = from_left_lane(left1);
+                    const float left = skip_left ? left2 : left1;
+                    const float inv = c_inv[d + 1];
+                    const float a = (float)max(d - nrk, 0) * inv, bb = (float)nrk * inv;
+                    const float np = pw * zd * a + od * left * bb;
+                    pw = d <= udk ? np : pw;
+                }
+                // unwound-path sum of this lane's element on that path
+                float next = lane_read(pw, min(gs + ud, 63));
+                float total = 0.0f;
+                for (int i = steps - 3; i >= 0; --i) {
+                    const float pwi = lane_read(pw, min(gs + (i < k ? i : i + 1), 63));
+                    const float pre = (float)(udk - i) * zdiv;
+                    const float tmp = next * udkp1 * c_inv[i + 1];
+                    const float t_one = total + tmp, n_one = pwi - tmp * pre;
+                    const float t_zero = pre > 0.0f ? total + pwi * __builtin_amdgcn_rcpf(pre) : total;
+                    if (i < udk) {
+                        total = o ? t_one : t_zero;
+                        next = o ? n_one : next;
+                    }
+                }
+                const float term = total * (o ? om : -z) * leaf * ((ok ? om_k : -z_k) * 0.5f);
+                float *pa = acc + r * acc_row + (size_t)fk * ld + fid, *pb = acc + r * acc_row + (size_t)fid * ld + fk;
+                for (int q = 0; q < rounds; ++q) {
+                    if (pair && round == q) {
+                        *pa += term;
+                        *pb += term;
+                    }
+                    if (!SLABS) vm_drain();
+                }
+            }
+        }
+    }
+}
+
+template <bool SLABS>
+__global__ __launch_bounds__(256) void interactions_kernel(float *out, const float *__restrict__ data, size_t rows, int F, int C,
+                                                           int R, const uint4 *__restrict__ elems,
+                                                           const float *__restrict__ one_minus_z,
+                                                           const uint32_t *__restrict__ bin_info,
+                                                           const int *__restrict__ class_bins, const float *__restrict__ bias,
+                                                           const float *__restrict__ class_div, float missing)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int F1 = F + 1;
+    const size_t mat = (size_t)F1 * F1;
+    const size_t tile_rows = SLABS ? (size_t)R : (size_t)R * kContribWaves;
+    const size_t row0 = (size_t)blockIdx.x * tile_rows;
+    const int nt = (int)min(tile_rows, rows - row0);
+    float *tile = smem;
+    const float *src = data + row0 * F;
+    for (int i = tid; i < nt * F; i += 256) tile[i] = src[i];
+    __syncthreads();
+
+    if (SLABS) {
+        const int FF = F * F;
+        const size_t slab_n = (size_t)R * FF;
+        float *s0 = smem + (size_t)R * F, *s1 = s0 + slab_n, *s2 = s1 + slab_n, *s3 = s2 + slab_n;
+        float *slab = s0 + slab_n * wave;
+        for (int c = 0; c < C; ++c) {
+            for (int i = lane; i < nt * FF; i += 64) slab[i] = 0.0f;
+            __syncthreads();
+            interaction_bins<true>(slab, (size_t)FF, F, tile, nt, F, class_bins[c] + wave, class_bins[c + 1], kContribWaves, elems,
+                                   one_minus_z, bin_info, missing);
+            __syncthreads();
+            const float div = class_div[c];
+            for (int i = tid; i < nt * FF; i += 256) s0[i] = (((s0[i] + s1[i]) + s2[i]) + s3[i]) / div;
+            __syncthreads();
+            // diagonal: phi_i (row F of the output) - the row's off-diagonal sum in ascending j
+            for (int t = tid; t < nt * F; t += 256) {
+                const int r = t / F, i = t - r * F;
+                float *m = s0 + (size_t)r * FF + (size_t)i * F;
+                float sum = 0.0f;
+                for (int j = 0; j < F; ++j)
+                    if (j != i) sum += m[j];
+                m[i] = out[((row0 + r) * C + c) * mat + (size_t)F * F1 + i] - sum;
+            }
+            __syncthreads();
+            for (int r = 0; r < nt; ++r)
+                for (int p = tid; p < F1 * F1; p += 256) {
+                    const int a = p / F1, b = p - a * F1;
+                    out[((row0 + r) * C + c) * mat + p] = a < F && b < F ? s0[r * FF + a * F + b] : (a == F && b == F ? bias[c] : 0.0f);
+                }
+            __syncthreads();
+        }
+    } else {
+        const int rw0 = wave * R;
+        const int nr = max(0, min(R, nt - rw0));
+        const float *wtile = tile + (size_t)rw0 * F;
+        const size_t row_stride = (size_t)C * mat;
+        for (int c = 0; c < C; ++c) {
+            float *acc = out + ((row0 + rw0) * C + c) * mat;
+            for (int r = 0; r < nr; ++r)
+                for (size_t i = lane; i < (size_t)F * F1; i += 64) acc[r * row_stride + i] = 0.0f;
+            vm_drain();
+            interaction_bins<false>(acc, row_stride, F1, wtile, nr, F, class_bins[c], class_bins[c + 1], 1, elems, one_minus_z,
+                                    bin_info, missing);
+            const float div = class_div[c];
+            for (int r = 0; r < nr; ++r) {
+                float *m = acc + r * row_stride;
+                if (div != 1.0f) {  // x / 1.0f is x: skipping the pass changes no bit
+                    for (size_t i = lane; i < (size_t)F * F1; i += 64) m[i] = m[i] / div;
+                    vm_drain();
+                }
+                for (int i = lane; i < F; i += 64) {
+                    const float *mi = m + (size_t)i * F1;
+                    float sum = 0.0f;
+                    for (int j = 0; j < F; ++j)
+                        if (j != i) sum += mi[j];
+                    m[(size_t)i * F1 + i] = m[(size_t)F * F1 + i] - sum;
+                    m[(size_t)i * F1 + F] = 0.0f;
+                }
+                vm_drain();
+                for (int i = lane; i < F; i += 64) m[(size_t)F * F1 + i] = 0.0f;
+            }
+        }
+    }
+}
+
+template __global__ void interactions_kernel<true>(float *, const float *, size_t, int, int, int, const uint4 *, const float *,
+                                                   const uint32_t *, const int *, const float *, const float *, float);
+template __global__ void interactions_kernel<false>(float *, const float *, size_t, int, int, int, const uint4 *, const float *,
+                                                    const uint32_t *, const int *, const float *, const float *, float);
 
 tahoe_status contribs_validate(const tahoe_dense_node *nodes, const tahoe_forest_params *p)
 {
@@ -368,6 +603,15 @@ tahoe_status contribs_build(tahoe_forest *f, const tahoe_dense_node *nodes)
     cs->path_elems = n_elems;
     cs->rows_per_tile = (int)R;
     cs->lds_bytes = R * per_row;
+    // interactions: four LDS slabs of F x F floats and the row per tile row where that fits 80 KiB, else in place in the output,
+    // one row per wave (rows are then the only parallelism: a wave walks every bin of its row)
+    const size_t inter_row = ((size_t)F + 4 * (size_t)F * F) * sizeof(float);
+    cs->inter_slabs = inter_row <= (size_t)kInterSlabMaxBytes && inter_row <= (size_t)f->lds_limit;
+    size_t RI = 1;
+    if (cs->inter_slabs)
+        for (RI = kInterMaxRows; RI > 1 && RI * inter_row > (size_t)kInterSlabMaxBytes;) RI /= 2;
+    cs->inter_rows = (int)RI;
+    cs->inter_lds_bytes = cs->inter_slabs ? RI * inter_row : kContribWaves * (size_t)F * sizeof(float);
     auto up = [f](auto **dst, const auto &v) -> hipError_t {
         const size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(v[0]);
         hipError_t e = hipMalloc(reinterpret_cast<void **>(dst), bytes);
@@ -383,6 +627,10 @@ tahoe_status contribs_build(tahoe_forest *f, const tahoe_dense_node *nodes)
         return fail(TAHOE_ERR_HIP, "contribs_build: upload failed: %s", hipGetErrorString(e));
     if ((e = allow_max_lds(reinterpret_cast<const void *>(&contribs_kernel), f->lds_limit)) != hipSuccess)
         return fail(TAHOE_ERR_HIP, "hipFuncSetAttribute(contribs) failed: %s", hipGetErrorString(e));
+    if ((e = allow_max_lds(reinterpret_cast<const void *>(&contribs_spare_kernel), f->lds_limit)) != hipSuccess ||
+        (e = allow_max_lds(reinterpret_cast<const void *>(&interactions_kernel<true>), f->lds_limit)) != hipSuccess ||
+        (e = allow_max_lds(reinterpret_cast<const void *>(&interactions_kernel<false>), f->lds_limit)) != hipSuccess)
+        return fail(TAHOE_ERR_HIP, "hipFuncSetAttribute(interactions) failed: %s", hipGetErrorString(e));
     return TAHOE_OK;
 }
 
@@ -423,6 +671,44 @@ extern "C" tahoe_status tahoe_forest_predict_contribs(tahoe_forest *f, float *ph
     hipLaunchKernelGGL(contribs_kernel, dim3((unsigned)grid), dim3(256), cs->lds_bytes, (hipStream_t)stream, phi_dev, data_dev, rows,
                        f->p.num_cols, f->num_classes, (int)R, cs->elems, cs->one_minus_z, cs->bin_info, cs->class_bins, cs->bias, cs->class_div,
                        f->p.missing);
+    TAHOE_HIP_TRY(hipGetLastError());
+    return TAHOE_OK;
+}
+
+
+extern "C" tahoe_status tahoe_forest_predict_interactions(tahoe_forest *f, float *out_dev, const float *data_dev, size_t rows,
+                                                          void *stream)
+{
+    if (!f) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_interactions: null forest");
+    if (f->sp)
+        return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_interactions: a sparse handle has no node covers (weights); "
+                                           "interactions need a dense handle created with TAHOE_CREATE_CONTRIBS");
+    if (!f->cs)
+        return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_interactions: the handle was created without "
+                                           "TAHOE_CREATE_CONTRIBS and has no path tables");
+    if (rows == 0) return TAHOE_OK;
+    if (!out_dev || !data_dev) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_interactions: null argument");
+    const int F = f->p.num_cols, C = f->num_classes;
+    const size_t F1 = (size_t)F + 1, limit = SIZE_MAX / sizeof(float);
+    if (F1 > limit / F1 || (size_t)C > limit / (F1 * F1) || rows > limit / ((size_t)C * F1 * F1))
+        return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_interactions: rows x classes x (num_cols + 1)^2 floats overflow "
+                                           "size_t (rows %zu)", rows);
+    const tahoe_cstate *cs = f->cs;
+    DeviceGuard on_device(f->device);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t R = (size_t)cs->rows_per_tile;
+    hipLaunchKernelGGL(contribs_spare_kernel, dim3((unsigned)((rows + R - 1) / R)), dim3(256), cs->lds_bytes, s, out_dev, data_dev,
+                       rows, F, C, (int)R, cs->elems, cs->one_minus_z, cs->bin_info, cs->class_bins, cs->bias, cs->class_div,
+                       f->p.missing);
+    TAHOE_HIP_TRY(hipGetLastError());
+    const size_t RI = (size_t)cs->inter_rows, per_block = cs->inter_slabs ? RI : RI * kContribWaves;
+    const dim3 grid((unsigned)((rows + per_block - 1) / per_block));
+    if (cs->inter_slabs)
+        hipLaunchKernelGGL(interactions_kernel<true>, grid, dim3(256), cs->inter_lds_bytes, s, out_dev, data_dev, rows, F, C, (int)RI,
+                           cs->elems, cs->one_minus_z, cs->bin_info, cs->class_bins, cs->bias, cs->class_div, f->p.missing);
+    else
+        hipLaunchKernelGGL(interactions_kernel<false>, grid, dim3(256), cs->inter_lds_bytes, s, out_dev, data_dev, rows, F, C,
+                           (int)RI, cs->elems, cs->one_minus_z, cs->bin_info, cs->class_bins, cs->bias, cs->class_div, f->p.missing);
     TAHOE_HIP_TRY(hipGetLastError());
     return TAHOE_OK;
 }
