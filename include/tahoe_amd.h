@@ -239,6 +239,40 @@ tahoe_status tahoe_forest_predict_contribs(tahoe_forest *f, float *phi_dev, cons
  * TAHOE_CREATE_CONTRIBS, or a sparse handle: TAHOE_ERR_UNSUPPORTED; nothing launched on any refusal. */
 tahoe_status tahoe_forest_predict_interactions(tahoe_forest *f, float *out_dev, const float *data_dev, size_t rows, void *stream);
 
+/* Interventional TreeSHAP (SHAP's TreeExplainer(model, data=bg), feature_perturbation="interventional"; Lundberg et al. 2020):
+ * the game v_r(S) = f(x_S, r_{N \ S}) against each row r of a background data set, averaged over the background.  Served on
+ * dense and multi-class handles created with TAHOE_CREATE_CONTRIBS; it reads the path bins that flag builds.  The covers are
+ * checked at create as for tahoe_forest_predict_contribs but this game does not use them.
+ *
+ * tahoe_forest_set_background: bg_dev is row-major bg_rows x num_cols float32 on the handle's device; the handle keeps what it
+ * needs (per path bin and background row, the 64-bit ballot of the bin's lanes whose element the row follows: bins x bg_rows x
+ * 8 bytes, counted in tahoe_forest_info.device_bytes), so the caller may free bg_dev on return.  Synchronous on `stream`, and
+ * it allocates: not graph-capturable.  A second call replaces the background; (NULL, 0) clears it.  It also computes the bias
+ * column of each class c, bias_c = (float)((sum_r (double)raw_c(r)) / bg_rows / div_c + (double)global_bias): raw_c(r) the bits
+ * of tahoe_forest_predict_raw for background row r, div_c = Tc with TAHOE_OUT_AVG, else 1, the sum in background order in
+ * float64 on the host, rounded once.  The handle's strategy setting is left as it was.  Refusals: NULL handle, NULL bg_dev with
+ * bg_rows > 0, bg_rows x num_cols x 4 overflowing size_t or bg_rows >= 2^31: TAHOE_ERR_INVALID_ARG; a sparse handle or one
+ * created without TAHOE_CREATE_CONTRIBS: TAHOE_ERR_UNSUPPORTED; an allocation that fails: TAHOE_ERR_NO_MEMORY.  On any refusal
+ * the previous background is kept. */
+tahoe_status tahoe_forest_set_background(tahoe_forest *f, const float *bg_dev, size_t bg_rows, void *stream);
+/* phi_dev[rows][num_classes][num_cols + 1] <- phi_i(x) = (1 / B) sum_r phi_i(x, r), B = background rows, phi_i(x, r) the exact
+ * Shapley value of v_r(S) = f(x_S, r_{N \ S}) summed over class c's trees c, c + C, ... and divided by (float)Tc with
+ * TAHOE_OUT_AVG.  Every node applies the rule of tahoe_forest_predict to the value it gets, background values included
+ * (missing sentinel -> default branch, NaN left, else right iff x >= thr).  Per leaf path, with A = the path's features that
+ * only x follows and B' = those that only r follows (one that neither follows kills the path): i in A gets
+ * +leaf (|A| - 1)! |B'|! / (|A| + |B'|)!, j in B' gets -leaf |A|! (|B'| - 1)! / (|A| + |B'|)!.  In float32: per (path element,
+ * row) the weights are summed over the background rows in order, times +-leaf, the paths' terms summed in a fixed order, the sum
+ * divided by (float)B, then by (float)Tc with AVG.  Column num_cols is the bias column of tahoe_forest_set_background, bit for
+ * bit; sum_i phi_i + bias is the margin before SIGMOID / THRESHOLD / SOFTMAX up to rounding.  Deterministic: the same bits on
+ * every call, for a row in any batch, under every strategy, with or without TAHOE_CREATE_PROB_RELAYOUT, and after the same
+ * background is set again; class c of a multi-class handle gives the bits of a handle created from class c's sub-forest with
+ * the same background.  No atomics.  Asynchronous on `stream`; allocates nothing (graph-capturable after set_background).
+ * Refusals, nothing launched: a sparse handle, one created without TAHOE_CREATE_CONTRIBS, or one with no background:
+ * TAHOE_ERR_UNSUPPORTED (tahoe_last_error says which); then rows == 0: TAHOE_OK; NULL phi_dev / data_dev with rows > 0, or
+ * rows x C x (num_cols + 1) x 4 overflowing size_t: TAHOE_ERR_INVALID_ARG. */
+tahoe_status tahoe_forest_predict_contribs_interventional(tahoe_forest *f, float *phi_dev, const float *data_dev, size_t rows,
+                                                          void *stream);
+
 /* ---- sparse (irregular) forests: sparse_node_t Struct.h:50-54, sparse_storage Struct.h:343-354,
  * init_sparse / sparse_forest::init (BaseTahoeTest.h:766-772, Struct.h:2329-2343) ---- */
 typedef struct {

@@ -124,6 +124,8 @@ _PROTOS = {
     "tahoe_forest_num_classes": (_i, [_vp]),
     "tahoe_forest_predict_contribs": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "tahoe_forest_predict_interactions": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "tahoe_forest_set_background": (_i, [_vp, _vp, _sz, _vp]),
+    "tahoe_forest_predict_contribs_interventional": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "tahoe_sparse_forest_create": (_i, [C.POINTER(_vp), _vp, _vp, C.POINTER(ForestParams)]),
     "tahoe_dense_to_sparse": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz)]),
     "tahoe_synth_sparse_forest": (_i, [_vp, _vp, C.POINTER(_sz), _i, _i, _i, _i, _f, _i, C.c_uint64]),
@@ -484,6 +486,31 @@ class Forest:
         assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == shape
         _check(lib.tahoe_forest_predict_interactions(self._h, _ptr(out), _ptr(data), rows, _stream(stream)),
                "tahoe_forest_predict_interactions")
+        return out
+
+    def set_background(self, bg, stream=None) -> None:
+        """Background data set of interventional TreeSHAP (tahoe_forest_set_background): float32 [B, num_cols], contiguous, on
+        the handle's device; None clears it.  Synchronous; the handle keeps what it needs, so `bg` may be freed afterwards."""
+        if bg is None:
+            _check(lib.tahoe_forest_set_background(self._h, None, 0, None), "tahoe_forest_set_background")
+            return
+        self._check_data(bg)
+        _check(lib.tahoe_forest_set_background(self._h, _ptr(bg), bg.shape[0], _stream(stream)), "tahoe_forest_set_background")
+
+    def predict_contribs_interventional(self, data, out=None, stream=None):
+        """Interventional TreeSHAP against the background of set_background (tahoe_forest_predict_contribs_interventional):
+        [rows, num_cols + 1] float32, or [rows, num_classes, num_cols + 1] on a multi-class handle; the bias is the last
+        column.  Needs contribs=True and a background."""
+        import torch
+
+        self._check_data(data)
+        rows = data.shape[0]
+        shape = (rows, self.num_classes, self.num_cols + 1) if self.num_classes > 1 else (rows, self.num_cols + 1)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=data.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == shape
+        _check(lib.tahoe_forest_predict_contribs_interventional(self._h, _ptr(out), _ptr(data), rows, _stream(stream)),
+               "tahoe_forest_predict_contribs_interventional")
         return out
 
     def set_strategy(self, strategy: int) -> None:

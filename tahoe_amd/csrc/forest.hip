@@ -1321,6 +1321,7 @@ void tahoe_forest_destroy(tahoe_forest *f)
     qring_destroy(f);
     sparse_destroy(f);
     widef_destroy(f);
+    interventional_destroy(f);
     contribs_destroy(f);
     for (hipEvent_t e : f->ev_start) (void)hipEventDestroy(e);
     for (hipEvent_t e : f->ev_mid) (void)hipEventDestroy(e);

@@ -13,6 +13,7 @@ struct tahoe_sstate;  // sparse (irregular) forest, owned by sparse.hip
 struct tahoe_pstate;  // host-batch upload pipeline, owned by pipeline.hip
 struct tahoe_wstate;  // float32 walk for wide rows, owned by widef.hip
 struct tahoe_cstate;  // TreeSHAP path tables (TAHOE_CREATE_CONTRIBS), owned by contribs.hip
+struct tahoe_istate;  // background of interventional TreeSHAP (tahoe_forest_set_background), owned by interventional.hip
 
 namespace tahoe {
 
@@ -72,6 +73,7 @@ struct tahoe_forest {
     tahoe_pstate *pipe = nullptr;  // tahoe_forest_predict_host: chunk buffers, streams, events (created on first use)
     tahoe_wstate *wf = nullptr;    // non-null: TILERING runs the wide-row float32 form (widef.hip)
     tahoe_cstate *cs = nullptr;    // non-null: created with TAHOE_CREATE_CONTRIBS (contribs.hip)
+    tahoe_istate *iv = nullptr;    // non-null: a background is set (interventional.hip)
     size_t device_bytes = 0;
     // Multi-class handle (tahoe_forest_create_multiclass): the trees are stored class-major -- internal tree p belongs to class
     // p / class_trees and is original tree (p % class_trees) * num_classes + p / class_trees -- and every consumer writes
@@ -214,5 +216,7 @@ tahoe_status widef_reserve(tahoe_forest *f, size_t rows);
 tahoe_status contribs_validate(const tahoe_dense_node *nodes, const tahoe_forest_params *p);
 tahoe_status contribs_build(tahoe_forest *f, const tahoe_dense_node *nodes);
 void contribs_destroy(tahoe_forest *f);
+// interventional TreeSHAP (interventional.hip): frees the background, if any
+void interventional_destroy(tahoe_forest *f);
 
 }  // namespace tahoe
