@@ -206,7 +206,10 @@ int tahoe_forest_num_classes(const tahoe_forest *f);
  * is the cover of a node (a reach probability, a hessian sum, any positive scale): at every reachable internal node the
  * children's weights wl, wr must be finite and >= 0 with wl + wr > 0, else create returns TAHOE_ERR_INVALID_FOREST naming the
  * tree and node (checked before a device is touched; weights below a leaf are ignored).  The handle then also holds one path per
- * reachable leaf (repeated features merged), built from the caller's nodes, in 64-lane bins; num_cols must be <= the device's
+ * reachable leaf (repeated features merged), built from the caller's nodes, in 64-lane bins.  A path element whose product of
+ * cover ratios (float64) is below 2^-121 is stored with a zero fraction of 0 (its 1 - z is kept from float64), so the float32
+ * recursions never take the reciprocal of a subnormal: results stay finite for any valid covers, and a path term moves by
+ * less than 2^-121 |leaf| per element cut from the exact value.  num_cols must be <= the device's
  * LDS bytes / 20 (8192 on an MI355X), else TAHOE_ERR_UNSUPPORTED.  Without the flag `weight` is ignored and nothing is built. */
 #define TAHOE_CREATE_CONTRIBS 0x4u
 /* phi_dev[rows][num_classes][num_cols + 1] <- exact Shapley values of v(S) = E[f(x) | x_S], the path-dependent expectation: at a

@@ -466,7 +466,10 @@ void tree_paths(const tahoe_dense_node *tree, size_t per, TreePaths &out)
         out.om.push_back(0.0f);
         for (int j = 0; j < ne; ++j) {
             uint4 u;
-            const float zf = (float)el[j].rho;
+            // below kContribMinZ the zero fraction is stored as 0 (1 - z still from float64): the kernels' pre = (ud - i) z /
+            // (ud + 1) is then 0 or >= 2^-126, never subnormal, so rcp(pre) stays finite.  Exact Shapley values are multilinear
+            // in z with slopes <= |leaf|, so a path term changes by less than 2^-121 |leaf| per element cut.
+            const float zf = el[j].rho < kContribMinZ ? 0.0f : (float)el[j].rho;
             memcpy(&u.x, &el[j].lower, 4);
             memcpy(&u.y, &el[j].upper, 4);
             memcpy(&u.z, &zf, 4);

@@ -35,5 +35,7 @@ namespace tahoe {
 constexpr int kContribWaves = 4;      // waves per workgroup; bin b of a class goes to wave (b - first bin of the class) % 4
 constexpr int kContribMaxCols = 32767;
 constexpr uint32_t kElemFidMask = 0x7fffu;
+// Smallest nonzero zero fraction a path element stores: 32 x 2^-126, so that z / (ud + 1) >= 2^-126 (normal) for ud <= 31
+constexpr double kContribMinZ = 0x1p-121;
 
 }  // namespace tahoe

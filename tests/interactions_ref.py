@@ -80,8 +80,10 @@ def _extend(Z, O):
     return W
 
 
-def _unwound_sum(W, zk, ok):
-    """Algorithm 2's UNWOUND-SUM of the element (zk [P, 1], ok [P, rows]) on the path of weights W [L, P, rows]."""
+def _unwound_sum(W, zk, ok, absolute=False):
+    """Algorithm 2's UNWOUND-SUM of the element (zk [P, 1], ok [P, rows]) on the path of weights W [L, P, rows].  absolute:
+    the same recursion with its one subtraction (the unwound weight of a followed element) made an addition -- every
+    intermediate then bounds the absolute value of the exact one's terms, the magnitude a float32 run of the recursion rounds."""
     ud = W.shape[0] - 1
     nxt = W[ud].copy()
     t_one = np.zeros_like(nxt)
@@ -89,21 +91,23 @@ def _unwound_sum(W, zk, ok):
     for i in range(ud - 1, -1, -1):
         tmp = nxt * (ud + 1) / (i + 1)
         t_one += tmp
-        nxt = W[i] - tmp * zk * (ud - i) / (ud + 1)
+        nxt = (W[i] + tmp * zk * (ud - i) / (ud + 1)) if absolute else (W[i] - tmp * zk * (ud - i) / (ud + 1))
         pre = zk * (ud - i) / (ud + 1)
         with np.errstate(divide="ignore", invalid="ignore"):
             t_zero += np.where(pre > 0, W[i] / np.where(pre > 0, pre, 1.0), 0.0)
     return np.where(ok > 0, t_one, t_zero)
 
 
-def poly(nodes, T, D, F, data, missing, num_classes=1, avg=False, global_bias=0.0, chunk=2048):
+def poly(nodes, T, D, F, data, missing, num_classes=1, avg=False, global_bias=0.0, chunk=2048, cond=False):
     """-> (Phi [rows, C, F + 1, F + 1], A [rows, C, F + 1, F + 1], N [C, F + 1, F + 1]) in float64; A and N cover the
-    off-diagonal entries (zero elsewhere)."""
+    off-diagonal entries (zero elsewhere).  cond: also returns Aabs [rows, C, F + 1, F + 1], A with each term's unwound sum
+    taken by _unwound_sum(absolute=True) (>= A; equal where no followed element's weight is unwound)."""
     data = np.ascontiguousarray(data, np.float32)
     rows = data.shape[0]
     per = nodes.size // max(T, 1)
     offT = np.zeros((num_classes, F * F, rows))
     AT = np.zeros((num_classes, F * F, rows))
+    AbsT = np.zeros((num_classes, F * F, rows)) if cond else None
     NF = np.zeros((num_classes, F * F))
     for t in range(T):
         c = t % num_classes
@@ -114,7 +118,8 @@ def poly(nodes, T, D, F, data, missing, num_classes=1, avg=False, global_bias=0.
             if L < 3:
                 continue
             for lo in range(0, len(paths), chunk):
-                _poly_chunk(paths[lo:lo + chunk], L, F, data, missing, offT[c], AT[c], NF[c])
+                _poly_chunk(paths[lo:lo + chunk], L, F, data, missing, offT[c], AT[c], NF[c],
+                            AbsT[c] if cond else None)
     # the upper triangle holds each pair's sum; [j][i] is the same number as [i][j]
     off = offT.transpose(2, 0, 1).reshape(rows, num_classes, F, F)
     off = off + off.swapaxes(-1, -2)
@@ -131,10 +136,18 @@ def poly(nodes, T, D, F, data, missing, num_classes=1, avg=False, global_bias=0.
     A[:, :, :F, :F] = A_off
     N = np.zeros((num_classes, F + 1, F + 1))
     N[:, :F, :F] = NF
-    return out, A, N
+    if not cond:
+        return out, A, N
+    Abs = AbsT.transpose(2, 0, 1).reshape(rows, num_classes, F, F)
+    Abs = Abs + Abs.swapaxes(-1, -2)
+    if avg and Tc > 0:
+        Abs = Abs / Tc
+    Aabs = np.zeros_like(out)
+    Aabs[:, :, :F, :F] = Abs
+    return out, A, N, Aabs
 
 
-def _poly_chunk(paths, L, F, data, missing, offT, AT, N):
+def _poly_chunk(paths, L, F, data, missing, offT, AT, N, AbsT=None):
     P, rows = len(paths), data.shape[0]
     Z = np.ones((P, L))
     O = np.ones((P, L, rows))
@@ -158,3 +171,6 @@ def _poly_chunk(paths, L, F, data, missing, offT, AT, N):
             np.add.at(offT, dst, term)
             np.add.at(AT, dst, np.abs(term))
             np.add.at(N, dst, 1)
+            if AbsT is not None:
+                Ua = _unwound_sum(W, Z[:, j][:, None], O[:, j], absolute=True)
+                np.add.at(AbsT, dst, np.abs(cond * (O[:, j] - Z[:, j][:, None])) * Ua)
