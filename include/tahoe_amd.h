@@ -179,7 +179,8 @@ tahoe_status tahoe_forest_create_ex(tahoe_forest **out, const tahoe_dense_node *
                                     const tahoe_forest_params *params, unsigned flags);
 void tahoe_forest_destroy(tahoe_forest *f);
 
-/* Multi-class forests (XGBoost multi:softprob / multi:softmax, LightGBM multiclass: one tree per class per boosting round).
+/* Multi-class forests (XGBoost multi:softprob / multi:softmax, LightGBM multiclass: one tree per class per boosting round);
+ * sparse forests take the same contract through tahoe_sparse_forest_create_ex.
  * Tree t of the num_trees trees belongs to class t % num_classes; num_trees must be a multiple of num_classes, each class then
  * has Tc = num_trees / num_classes trees.  A predict writes rows x num_classes values, row-major: margin[row][c] = the float32
  * sum of class c's leaf values added from 0.0f in increasing tree order -- bit for bit what predict_on_cpu gives on the
@@ -195,10 +196,13 @@ void tahoe_forest_destroy(tahoe_forest *f);
  *     stay leaf_dev[row * num_trees + tree] in the caller's tree numbering and the original heap numbering;
  *   - reserve (and HIP graph capture after it), set/get_strategy, get_kernel_form, get_info, profiling and check work
  *     unchanged.  Strategies served: AUTO, DIRECT, ROWTILE, QRING; TILEBLOCK and TILERING are TAHOE_ERR_UNSUPPORTED;
- *   - tahoe_forest_predict_accumulate and tahoe_forest_predict_host return TAHOE_ERR_UNSUPPORTED and launch nothing. */
+ *   - tahoe_forest_predict_accumulate and tahoe_forest_predict_host return TAHOE_ERR_UNSUPPORTED and launch nothing.
+ * (A multi-class sparse handle serves every strategy of a sparse handle -- AUTO, DIRECT, ROWTILE, TILEBLOCK, QRING -- with
+ * the same outputs; see tahoe_sparse_forest_create_ex.) */
 tahoe_status tahoe_forest_create_multiclass(tahoe_forest **out, const tahoe_dense_node *nodes,
                                             const tahoe_forest_params *params, int num_classes, unsigned flags);
-/* Classes of the handle: num_classes of tahoe_forest_create_multiclass, 1 for every other handle (sparse included), 0 for NULL. */
+/* Classes of the handle: num_classes of tahoe_forest_create_multiclass or tahoe_sparse_forest_create_ex, 1 for every other
+ * handle (tahoe_sparse_forest_create included), 0 for NULL. */
 int tahoe_forest_num_classes(const tahoe_forest *f);
 
 /* Per-feature contributions (path-dependent TreeSHAP: XGBoost pred_contribs, LightGBM pred_contrib).  A create flag for
@@ -221,8 +225,10 @@ int tahoe_forest_num_classes(const tahoe_forest *f);
  * margin up to rounding.  Deterministic: the same bits on every call, for a row in any batch, under every strategy (the
  * strategy is not used), with or without TAHOE_CREATE_PROB_RELAYOUT; class c of a multi-class handle gives the bits of a
  * handle created from class c's sub-forest.  Asynchronous on `stream`; allocates nothing (graph-capturable).  rows == 0:
- * TAHOE_OK, nothing launched; NULL phi_dev / data_dev with rows > 0: TAHOE_ERR_INVALID_ARG; a handle created without
- * TAHOE_CREATE_CONTRIBS, or a sparse handle: TAHOE_ERR_UNSUPPORTED, nothing launched. */
+ * TAHOE_OK, nothing launched; NULL phi_dev / data_dev with rows > 0: TAHOE_ERR_INVALID_ARG; a handle (dense or sparse) created
+ * without TAHOE_CREATE_CONTRIBS: TAHOE_ERR_UNSUPPORTED, nothing launched.  A sparse handle created with the flag
+ * (tahoe_sparse_forest_create_ex, covers given per node) is served the same way: its paths are walked pre-order, left child
+ * first, so a forest converted with tahoe_dense_to_sparse_ex holds the dense handle's path bins and gives its bits. */
 tahoe_status tahoe_forest_predict_contribs(tahoe_forest *f, float *phi_dev, const float *data_dev, size_t rows, void *stream);
 
 /* SHAP interaction values (XGBoost pred_interactions, SHAP's TreeExplainer.shap_interaction_values) of the game that
@@ -238,13 +244,14 @@ tahoe_status tahoe_forest_predict_contribs(tahoe_forest *f, float *phi_dev, cons
  * Deterministic as tahoe_forest_predict_contribs (any batch, strategy, re-layout; class c = class c's sub-forest).  The
  * off-diagonal sums run in LDS for num_cols <= 71 and in place in out_dev above that (no other limit than the create flag's).
  * Asynchronous on `stream`; allocates nothing (graph-capturable).  rows == 0: TAHOE_OK, nothing launched; NULL out_dev /
- * data_dev with rows > 0, or rows * C * (F + 1)^2 * 4 overflowing size_t: TAHOE_ERR_INVALID_ARG; a handle created without
- * TAHOE_CREATE_CONTRIBS, or a sparse handle: TAHOE_ERR_UNSUPPORTED; nothing launched on any refusal. */
+ * data_dev with rows > 0, or rows * C * (F + 1)^2 * 4 overflowing size_t: TAHOE_ERR_INVALID_ARG; a handle (dense or sparse)
+ * created without TAHOE_CREATE_CONTRIBS: TAHOE_ERR_UNSUPPORTED; nothing launched on any refusal.  Sparse handles created with
+ * the flag are served as by tahoe_forest_predict_contribs. */
 tahoe_status tahoe_forest_predict_interactions(tahoe_forest *f, float *out_dev, const float *data_dev, size_t rows, void *stream);
 
 /* Interventional TreeSHAP (SHAP's TreeExplainer(model, data=bg), feature_perturbation="interventional"; Lundberg et al. 2020):
  * the game v_r(S) = f(x_S, r_{N \ S}) against each row r of a background data set, averaged over the background.  Served on
- * dense and multi-class handles created with TAHOE_CREATE_CONTRIBS; it reads the path bins that flag builds.  The covers are
+ * dense, sparse and multi-class handles created with TAHOE_CREATE_CONTRIBS; it reads the path bins that flag builds.  The covers are
  * checked at create as for tahoe_forest_predict_contribs but this game does not use them.
  *
  * tahoe_forest_set_background: bg_dev is row-major bg_rows x num_cols float32 on the handle's device; the handle keeps what it
@@ -254,7 +261,7 @@ tahoe_status tahoe_forest_predict_interactions(tahoe_forest *f, float *out_dev, 
  * column of each class c, bias_c = (float)((sum_r (double)raw_c(r)) / bg_rows / div_c + (double)global_bias): raw_c(r) the bits
  * of tahoe_forest_predict_raw for background row r, div_c = Tc with TAHOE_OUT_AVG, else 1, the sum in background order in
  * float64 on the host, rounded once.  The handle's strategy setting is left as it was.  Refusals: NULL handle, NULL bg_dev with
- * bg_rows > 0, bg_rows x num_cols x 4 overflowing size_t or bg_rows >= 2^31: TAHOE_ERR_INVALID_ARG; a sparse handle or one
+ * bg_rows > 0, bg_rows x num_cols x 4 overflowing size_t or bg_rows >= 2^31: TAHOE_ERR_INVALID_ARG; a handle (dense or sparse)
  * created without TAHOE_CREATE_CONTRIBS: TAHOE_ERR_UNSUPPORTED; an allocation that fails: TAHOE_ERR_NO_MEMORY.  On any refusal
  * the previous background is kept. */
 tahoe_status tahoe_forest_set_background(tahoe_forest *f, const float *bg_dev, size_t bg_rows, void *stream);
@@ -270,7 +277,7 @@ tahoe_status tahoe_forest_set_background(tahoe_forest *f, const float *bg_dev, s
  * every call, for a row in any batch, under every strategy, with or without TAHOE_CREATE_PROB_RELAYOUT, and after the same
  * background is set again; class c of a multi-class handle gives the bits of a handle created from class c's sub-forest with
  * the same background.  No atomics.  Asynchronous on `stream`; allocates nothing (graph-capturable after set_background).
- * Refusals, nothing launched: a sparse handle, one created without TAHOE_CREATE_CONTRIBS, or one with no background:
+ * Refusals, nothing launched: a handle (dense or sparse) created without TAHOE_CREATE_CONTRIBS, or one with no background:
  * TAHOE_ERR_UNSUPPORTED (tahoe_last_error says which); then rows == 0: TAHOE_OK; NULL phi_dev / data_dev with rows > 0, or
  * rows x C x (num_cols + 1) x 4 overflowing size_t: TAHOE_ERR_INVALID_ARG. */
 tahoe_status tahoe_forest_predict_contribs_interventional(tahoe_forest *f, float *phi_dev, const float *data_dev, size_t rows,
@@ -289,12 +296,33 @@ typedef struct {
  * relative to the tree's root.  The walk is infer_one_tree_sparse (Struct.h:2217-2250) with the branch rule of
  * the live dense path (BaseTahoeTest.h:452), so a forest converted with tahoe_dense_to_sparse predicts exactly
  * what the dense forest predicts.  Rejects (TAHOE_ERR_INVALID_FOREST) child links that leave the tree or point
- * backwards, and fid >= num_cols. */
+ * backwards, and fid >= num_cols.  One output, no covers: tahoe_sparse_forest_create_ex adds classes and TreeSHAP. */
 tahoe_status tahoe_sparse_forest_create(tahoe_forest **out, const int32_t *trees, const tahoe_sparse_node *nodes,
                                         const tahoe_forest_params *params);
+/* The same with classes and covers.  Every check runs before a device is touched.
+ *  - num_classes: the contract of tahoe_forest_create_multiclass (tree t belongs to class t % C, num_trees % C == 0, C in
+ *    [1, 1024], SOFTMAX only with C > 1, THRESHOLD only with C == 1, not SOFTMAX with SIGMOID).  The trees are stored
+ *    class-major; every strategy of a sparse handle (AUTO, DIRECT, ROWTILE, TILEBLOCK, QRING) adds each class's leaf values
+ *    from 0.0f in increasing tree order, and predict / predict_raw / the sums of predict_leaf_idx write rows x C values, bit
+ *    for bit the single-class sparse handle of trees c, c + C, ...; leaf indices stay in the caller's tree numbering.
+ *    tahoe_forest_predict_accumulate and tahoe_forest_predict_host return TAHOE_ERR_UNSUPPORTED when C > 1.
+ *  - flags: TAHOE_CREATE_CONTRIBS only (any other bit, TAHOE_CREATE_PROB_RELAYOUT included: TAHOE_ERR_INVALID_ARG).  With it,
+ *    covers[i] is the cover of nodes[i] (params->num_nodes floats; NULL: TAHOE_ERR_INVALID_ARG); at every reachable internal
+ *    node the covers of nodes left_idx and left_idx + 1 must be finite and >= 0 with a positive sum (TAHOE_ERR_INVALID_FOREST
+ *    naming the tree and node), and no reachable leaf's path may have more than 31 distinct features (TAHOE_ERR_UNSUPPORTED
+ *    naming the tree; a deep path that repeats features is fine).  The handle then serves the four TreeSHAP calls.  Without
+ *    the flag covers is ignored and may be NULL.
+ * num_classes == 1 with flags == 0 gives a handle that behaves exactly like tahoe_sparse_forest_create. */
+tahoe_status tahoe_sparse_forest_create_ex(tahoe_forest **out, const int32_t *trees, const tahoe_sparse_node *nodes,
+                                           const float *covers, const tahoe_forest_params *params, int num_classes,
+                                           unsigned flags);
 /* dense2sparse (BaseTahoeTest.h:728-764).  *nodes_out / *trees_out: tahoe_free_host. */
 tahoe_status tahoe_dense_to_sparse(const tahoe_dense_node *dense, int num_trees, int depth,
                                    tahoe_sparse_node **nodes_out, int32_t **trees_out, size_t *num_nodes_out);
+/* The same nodes and trees, and *covers_out[i] = the weight of the dense node that sparse node i came from (tahoe_free_host):
+ * the covers tahoe_sparse_forest_create_ex takes. */
+tahoe_status tahoe_dense_to_sparse_ex(const tahoe_dense_node *dense, int num_trees, int depth, tahoe_sparse_node **nodes_out,
+                                      int32_t **trees_out, float **covers_out, size_t *num_nodes_out);
 /* Deterministic irregular forest (BASELINE config 5): per tree a depth limit in [min_depth, max_depth]; nodes
  * below min_depth become leaves with probability leaf_prob; at most max_tree_nodes per tree.  With nodes == NULL
  * only *num_nodes is computed (call twice). */
@@ -375,7 +403,7 @@ typedef struct {
     int qring_walkers;       /* walker waves of the QRING kernel; 0 = strategy unavailable */
     int qring_lds_bytes;     /* dynamic LDS of the QRING kernel */
     int qring_groups;        /* tree groups quantised separately (forests with > 32767 thresholds per feature) */
-    int is_sparse;           /* 1: handle made by tahoe_sparse_forest_create (only the generic fields are set) */
+    int is_sparse;           /* 1: handle made by tahoe_sparse_forest_create(_ex) (only the generic fields are set) */
     int ring_rows;           /* rows per TILERING tile: 64 or 128; 32 / 16 / 8 for the wide-row float32 form (num_cols > 512);
                               * 0 = strategy unavailable */
     int tilering_lds_bytes;  /* dynamic LDS of the TILERING kernel the launch takes (of the wide-row form where that runs) */

@@ -127,7 +127,9 @@ _PROTOS = {
     "tahoe_forest_set_background": (_i, [_vp, _vp, _sz, _vp]),
     "tahoe_forest_predict_contribs_interventional": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "tahoe_sparse_forest_create": (_i, [C.POINTER(_vp), _vp, _vp, C.POINTER(ForestParams)]),
+    "tahoe_sparse_forest_create_ex": (_i, [C.POINTER(_vp), _vp, _vp, _vp, C.POINTER(ForestParams), _i, C.c_uint]),
     "tahoe_dense_to_sparse": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz)]),
+    "tahoe_dense_to_sparse_ex": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz)]),
     "tahoe_synth_sparse_forest": (_i, [_vp, _vp, C.POINTER(_sz), _i, _i, _i, _i, _f, _i, C.c_uint64]),
     "tahoe_forest_predict": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "tahoe_forest_predict_raw": (_i, [_vp, _vp, _vp, _sz, _vp]),
@@ -572,20 +574,29 @@ class Forest:
 SPARSE_NODE_DTYPE = np.dtype([("val", "<f4"), ("bits", "<i4"), ("left_idx", "<i4")])  # sparse_node_t, Struct.h:50-54
 
 
-def dense_to_sparse(nodes: np.ndarray, num_trees: int, depth: int):
-    """dense2sparse (BaseTahoeTest.h:728-764) -> (sparse nodes, root offsets int32[num_trees])."""
+def dense_to_sparse(nodes: np.ndarray, num_trees: int, depth: int, covers: bool = False):
+    """dense2sparse (BaseTahoeTest.h:728-764) -> (sparse nodes, root offsets int32[num_trees]); with covers=True also the
+    float32 covers[num_nodes] (the dense weights, tahoe_dense_to_sparse_ex) as a third element."""
     nodes = np.ascontiguousarray(nodes, dtype=NODE_DTYPE)
-    pn, pt, n = _vp(), _vp(), _sz()
-    _check(lib.tahoe_dense_to_sparse(nodes.ctypes.data, num_trees, depth, C.byref(pn), C.byref(pt), C.byref(n)),
-           "tahoe_dense_to_sparse")
+    pn, pt, pc, n = _vp(), _vp(), _vp(), _sz()
+    if covers:
+        _check(lib.tahoe_dense_to_sparse_ex(nodes.ctypes.data, num_trees, depth, C.byref(pn), C.byref(pt), C.byref(pc),
+                                            C.byref(n)), "tahoe_dense_to_sparse_ex")
+    else:
+        _check(lib.tahoe_dense_to_sparse(nodes.ctypes.data, num_trees, depth, C.byref(pn), C.byref(pt), C.byref(n)),
+               "tahoe_dense_to_sparse")
     try:
         sn = np.frombuffer((C.c_char * (n.value * 12)).from_address(pn.value), dtype=SPARSE_NODE_DTYPE, count=n.value).copy()
         tr = np.frombuffer((C.c_char * (num_trees * 4)).from_address(pt.value), dtype=np.int32, count=num_trees).copy() \
             if num_trees else np.empty(0, np.int32)
+        cv = np.frombuffer((C.c_char * (n.value * 4)).from_address(pc.value), dtype=np.float32, count=n.value).copy() \
+            if covers else None
     finally:
         lib.tahoe_free_host(pn)
         lib.tahoe_free_host(pt)
-    return sn, tr
+        if covers:
+            lib.tahoe_free_host(pc)
+    return (sn, tr, cv) if covers else (sn, tr)
 
 
 def synth_sparse_forest(num_trees: int, num_cols: int, min_depth: int = 4, max_depth: int = 24, leaf_prob: float = 0.32,
@@ -602,20 +613,33 @@ def synth_sparse_forest(num_trees: int, num_cols: int, min_depth: int = 4, max_d
 
 
 class SparseForest(Forest):
-    """tahoe_sparse_forest_create: nodes[SPARSE_NODE_DTYPE] + root offsets; predict* as Forest."""
+    """tahoe_sparse_forest_create: nodes[SPARSE_NODE_DTYPE] + root offsets; predict* as Forest.  covers (float32, one per
+    node), num_classes and contribs go through tahoe_sparse_forest_create_ex: tree t belongs to class t % num_classes, and
+    contribs=True builds the TreeSHAP path tables from the covers."""
 
     def __init__(self, nodes: np.ndarray, trees: np.ndarray, num_cols: int, missing: float = 0.0, output: int = OUT_RAW,
-                 threshold: float = 0.0, global_bias: float = 0.0):
+                 threshold: float = 0.0, global_bias: float = 0.0, covers=None, num_classes: int = 1,
+                 contribs: bool = False):
         nodes = np.ascontiguousarray(nodes, dtype=SPARSE_NODE_DTYPE)
         trees = np.ascontiguousarray(trees, dtype=np.int32)
         self.params = ForestParams(int(nodes.size), 0, int(trees.size), num_cols, 0, output, threshold, global_bias, 0,
                                    missing)
         self._h = _vp()
-        _check(lib.tahoe_sparse_forest_create(C.byref(self._h), trees.ctypes.data if trees.size else None,
-                                              nodes.ctypes.data if nodes.size else None, C.byref(self.params)),
-               "tahoe_sparse_forest_create")
+        if covers is not None or num_classes != 1 or contribs:
+            cv = None if covers is None else np.ascontiguousarray(covers, dtype=np.float32)
+            if cv is not None and cv.size != nodes.size:
+                raise ValueError("covers.size != nodes.size")
+            _check(lib.tahoe_sparse_forest_create_ex(C.byref(self._h), trees.ctypes.data if trees.size else None,
+                                                     nodes.ctypes.data if nodes.size else None,
+                                                     cv.ctypes.data if cv is not None else None,
+                                                     C.byref(self.params), num_classes, CREATE_CONTRIBS if contribs else 0),
+                   "tahoe_sparse_forest_create_ex")
+        else:
+            _check(lib.tahoe_sparse_forest_create(C.byref(self._h), trees.ctypes.data if trees.size else None,
+                                                  nodes.ctypes.data if nodes.size else None, C.byref(self.params)),
+                   "tahoe_sparse_forest_create")
         self.num_trees, self.depth, self.num_cols = int(trees.size), 0, num_cols
-        self.num_classes = 1
+        self.num_classes = lib.tahoe_forest_num_classes(self._h)
 
 
 def transform_preds(preds, output: int, num_trees_total: int, threshold: float, global_bias: float, stream=None):

@@ -405,44 +405,67 @@ struct Elem {
     double rho;
 };
 
-void tree_paths(const tahoe_dense_node *tree, size_t per, TreePaths &out)
+// The two node formats as one tree for tree_paths: val, bits (fid[0:29] | def_left << 30 | is_leaf << 31 in both), the left
+// child (the right one follows it) and a node's cover.
+struct DenseTree {
+    const tahoe_dense_node *n;
+    float val(size_t i) const { return n[i].val; }
+    int32_t bits(size_t i) const { return n[i].bits; }
+    size_t left(size_t i) const { return 2 * i + 1; }
+    double cover(size_t i) const { return n[i].weight; }
+};
+struct SparseTree {
+    const tahoe_sparse_node *n;
+    const float *covers;  // parallel to n
+    float val(size_t i) const { return n[i].val; }
+    int32_t bits(size_t i) const { return n[i].bits; }
+    size_t left(size_t i) const { return (size_t)n[i].left_idx; }
+    double cover(size_t i) const { return covers[i]; }
+};
+
+template <typename Tree>
+void tree_paths(const Tree &tree, TreePaths &out)
 {
     struct Edge {
         size_t node;
         bool right;
     };
-    Edge edges[32];
+    std::vector<Edge> edges;  // the path from the root: as long as the deepest leaf (sparse trees are not bounded by 32 levels)
     // iterative pre-order walk (left before right): leaves in heap order left to right
     struct Frame {
-        size_t node;
+        size_t node, parent;
         int depth;
         bool right;
     };
-    std::vector<Frame> stack{{0, 0, false}};
+    std::vector<Frame> stack{{0, 0, 0, false}};
+    std::vector<Elem> el;
     while (!stack.empty()) {
         const Frame fr = stack.back();
         stack.pop_back();
-        if (fr.depth > 0) edges[fr.depth - 1] = {(fr.node - 1) / 2, fr.right};
-        const tahoe_dense_node &n = tree[fr.node];
-        if (!((n.bits >> 31) & 1)) {
-            stack.push_back({2 * fr.node + 2, fr.depth + 1, true});
-            stack.push_back({2 * fr.node + 1, fr.depth + 1, false});
+        if (fr.depth > 0) {
+            if (edges.size() < (size_t)fr.depth) edges.resize((size_t)fr.depth);
+            edges[fr.depth - 1] = {fr.parent, fr.right};
+        }
+        if (!((tree.bits(fr.node) >> 31) & 1)) {
+            const size_t l = tree.left(fr.node);
+            stack.push_back({l + 1, fr.node, fr.depth + 1, true});
+            stack.push_back({l, fr.node, fr.depth + 1, false});
             continue;
         }
-        Elem el[32];
-        int ne = 0;
+        // repeated features are merged into their first element: at most 31 distinct ones (checked at create)
+        el.clear();
         double prod = 1.0;
         for (int k = 0; k < fr.depth; ++k) {
-            const tahoe_dense_node &a = tree[edges[k].node];
-            const int fid = a.bits & 0x3fffffff;
-            const bool def_left = (a.bits >> 30) & 1;
-            const float thr = a.val;
-            const double wl = tree[2 * edges[k].node + 1].weight, wr = tree[2 * edges[k].node + 2].weight;
+            const size_t a = edges[k].node;
+            const int fid = tree.bits(a) & 0x3fffffff;
+            const bool def_left = (tree.bits(a) >> 30) & 1;
+            const float thr = tree.val(a);
+            const double wl = tree.cover(tree.left(a)), wr = tree.cover(tree.left(a) + 1);
             const double rho = (edges[k].right ? wr : wl) / (wl + wr);
             prod *= rho;
-            int j = 0;
-            while (j < ne && el[j].fid != fid) ++j;
-            if (j == ne) el[ne++] = {fid, -INFINITY, NAN, true, true, 1.0};
+            size_t j = 0;
+            while (j < el.size() && el[j].fid != fid) ++j;
+            if (j == el.size()) el.push_back({fid, -INFINITY, NAN, true, true, 1.0});
             Elem &m = el[j];
             m.rho *= rho;
             if (edges[k].right) {  // x >= thr; NaN never satisfies it, missing does iff the default is right
@@ -454,10 +477,12 @@ void tree_paths(const tahoe_dense_node *tree, size_t per, TreePaths &out)
                 m.missing_ok = m.missing_ok && def_left;
             }
         }
-        out.expect += (double)n.val * prod;
+        const float leaf = tree.val(fr.node);
+        const int ne = (int)el.size();
+        out.expect += (double)leaf * prod;
         if (ne == 0) continue;  // a root leaf: all of it is bias
         uint4 root;
-        memcpy(&root.x, &n.val, 4);
+        memcpy(&root.x, &leaf, 4);
         root.y = 0u;
         const float one = 1.0f;
         memcpy(&root.z, &one, 4);
@@ -483,7 +508,8 @@ void tree_paths(const tahoe_dense_node *tree, size_t per, TreePaths &out)
 
 }  // namespace
 
-tahoe_status contribs_build(tahoe_forest *f, const tahoe_dense_node *nodes)
+// The path tables from the paths of every tree (caller's tree numbering): packing, bias and LDS shapes.
+static tahoe_status build_tables(tahoe_forest *f, std::vector<TreePaths> &trees)
 {
     const int F = f->p.num_cols;
     // LDS: the row tile and four slabs, R rows each; R is the largest power of two <= 64 that fits 80 KiB (two workgroups
@@ -496,12 +522,7 @@ tahoe_status contribs_build(tahoe_forest *f, const tahoe_dense_node *nodes)
                     f->lds_limit);
 
     const int C = f->num_classes;
-    const size_t T = (size_t)f->p.num_trees, Tc = (size_t)f->class_trees;
-    const size_t per = (size_t)tahoe_tree_num_nodes(f->p.depth);
-    std::vector<TreePaths> trees(T);  // in the caller's tree numbering
-    parallel_for(T, 4, [&](size_t lo, size_t hi) {
-        for (size_t t = lo; t < hi; ++t) tree_paths(nodes + t * per, per, trees[t]);
-    });
+    const size_t Tc = (size_t)f->class_trees;
 
     std::vector<uint4> h_elems;
     std::vector<float> h_om;
@@ -611,6 +632,77 @@ tahoe_status contribs_build(tahoe_forest *f, const tahoe_dense_node *nodes)
     return TAHOE_OK;
 }
 
+tahoe_status contribs_build(tahoe_forest *f, const tahoe_dense_node *nodes)
+{
+    const size_t T = (size_t)f->p.num_trees;
+    const size_t per = (size_t)tahoe_tree_num_nodes(f->p.depth);
+    std::vector<TreePaths> trees(T);  // in the caller's tree numbering
+    parallel_for(T, 4, [&](size_t lo, size_t hi) {
+        for (size_t t = lo; t < hi; ++t) tree_paths(DenseTree{nodes + t * per}, trees[t]);
+    });
+    return build_tables(f, trees);
+}
+
+tahoe_status contribs_validate_sparse(const int32_t *trees, const tahoe_sparse_node *nodes, const float *covers,
+                                      const tahoe_forest_params *p)
+{
+    // per reachable internal node, the covers of its two children; per reachable leaf, the distinct features of its path (the
+    // element word's 5-bit rank and length fields, and interventional.hip's 32 x 32 weight table, hold at most 31)
+    std::vector<int> count((size_t)std::max(p->num_cols, 1), 0);  // uses of each feature on the current path
+    std::vector<int> path;                                        // features of the current path, root first
+    struct Frame {
+        int32_t node;
+        int depth;
+    };
+    std::vector<Frame> stack;
+    for (int t = 0; t < p->num_trees; ++t) {
+        const tahoe_sparse_node *tn = nodes + trees[t];
+        const float *tc = covers + trees[t];
+        int distinct = 0;
+        path.clear();
+        stack.assign(1, Frame{0, 0});
+        while (!stack.empty()) {
+            const Frame fr = stack.back();
+            stack.pop_back();
+            while ((int)path.size() > fr.depth) {  // back up to this node's parent
+                if (--count[(size_t)path.back()] == 0) --distinct;
+                path.pop_back();
+            }
+            const tahoe_sparse_node &n = tn[fr.node];
+            if (n.bits & (int32_t)(1u << 31)) {
+                if (distinct > 31)
+                    return fail(TAHOE_ERR_UNSUPPORTED,
+                                "tree %d: a leaf's path has %d distinct features (TAHOE_CREATE_CONTRIBS supports at most 31)", t,
+                                distinct);
+                continue;
+            }
+            const int fid = n.bits & 0x3fffffff;
+            if (count[(size_t)fid]++ == 0) ++distinct;
+            path.push_back(fid);
+            const float wl = tc[n.left_idx], wr = tc[n.left_idx + 1];
+            if (!std::isfinite(wl) || !std::isfinite(wr) || !(wl >= 0.0f) || !(wr >= 0.0f) || !((double)wl + (double)wr > 0.0))
+                return fail(TAHOE_ERR_INVALID_FOREST,
+                            "tree %d node %d: child covers %g and %g (TAHOE_CREATE_CONTRIBS needs finite covers >= 0 with a "
+                            "positive sum at every reachable internal node)",
+                            t, fr.node, (double)wl, (double)wr);
+            stack.push_back(Frame{n.left_idx + 1, fr.depth + 1});
+            stack.push_back(Frame{n.left_idx, fr.depth + 1});
+        }
+        for (int fid : path) count[(size_t)fid] = 0;
+    }
+    return TAHOE_OK;
+}
+
+tahoe_status contribs_build_sparse(tahoe_forest *f, const int32_t *tree_roots, const tahoe_sparse_node *nodes, const float *covers)
+{
+    const size_t T = (size_t)f->p.num_trees;
+    std::vector<TreePaths> trees(T);  // in the caller's tree numbering
+    parallel_for(T, 4, [&](size_t lo, size_t hi) {
+        for (size_t t = lo; t < hi; ++t) tree_paths(SparseTree{nodes + tree_roots[t], covers + tree_roots[t]}, trees[t]);
+    });
+    return build_tables(f, trees);
+}
+
 void contribs_destroy(tahoe_forest *f)
 {
     tahoe_cstate *cs = f->cs;
@@ -633,9 +725,9 @@ extern "C" tahoe_status tahoe_forest_predict_contribs(tahoe_forest *f, float *ph
                                                       void *stream)
 {
     if (!f) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_contribs: null forest");
-    if (f->sp)
-        return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_contribs: a sparse handle has no node covers (weights); "
-                                           "contributions need a dense handle created with TAHOE_CREATE_CONTRIBS");
+    if (f->sp && !f->cs)
+        return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_contribs: a sparse handle created without TAHOE_CREATE_CONTRIBS "
+                                           "has no node covers and no path tables (tahoe_sparse_forest_create_ex)");
     if (!f->cs)
         return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_contribs: the handle was created without TAHOE_CREATE_CONTRIBS "
                                            "and has no path tables");
@@ -657,9 +749,9 @@ extern "C" tahoe_status tahoe_forest_predict_interactions(tahoe_forest *f, float
                                                           void *stream)
 {
     if (!f) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_interactions: null forest");
-    if (f->sp)
-        return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_interactions: a sparse handle has no node covers (weights); "
-                                           "interactions need a dense handle created with TAHOE_CREATE_CONTRIBS");
+    if (f->sp && !f->cs)
+        return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_interactions: a sparse handle created without "
+                                           "TAHOE_CREATE_CONTRIBS has no node covers and no path tables (tahoe_sparse_forest_create_ex)");
     if (!f->cs)
         return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_interactions: the handle was created without "
                                            "TAHOE_CREATE_CONTRIBS and has no path tables");

@@ -852,7 +852,7 @@ static tahoe_status launch_traversal(tahoe_forest *f, float *sums, uint32_t *lea
             TAHOE_HIP_TRY(hipMemcpyAsync(sums, sums_in, rows * sizeof(float), hipMemcpyDeviceToDevice, stream));
         else if (sums && !sums_in)
             TAHOE_HIP_TRY(hipMemsetAsync(sums, 0, rows * (size_t)f->num_classes * sizeof(float), stream));
-    } else if (f->num_classes > 1 && (strategy == TAHOE_STRATEGY_TILERING || strategy == TAHOE_STRATEGY_TILEBLOCK)) {
+    } else if (!f->sp && f->num_classes > 1 && (strategy == TAHOE_STRATEGY_TILERING || strategy == TAHOE_STRATEGY_TILEBLOCK)) {
         return fail(TAHOE_ERR_UNSUPPORTED, "the float32 tile forms (TILEBLOCK, TILERING) do not serve multi-class handles");
     } else if (f->sp) {
         const tahoe_status ss = sparse_launch(f, sums, leaf_out, data, rows, stream, strategy, sums_in);

@@ -215,6 +215,11 @@ tahoe_status widef_reserve(tahoe_forest *f, size_t rows);
 // contribs_build builds the path tables of a validated forest from the caller's nodes (not the re-laid-out ones).
 tahoe_status contribs_validate(const tahoe_dense_node *nodes, const tahoe_forest_params *p);
 tahoe_status contribs_build(tahoe_forest *f, const tahoe_dense_node *nodes);
+// ... the same for a sparse forest whose structure check has passed: covers[i] is the cover of nodes[i]; the validation also
+// refuses (TAHOE_ERR_UNSUPPORTED) a leaf whose path has more than 31 distinct features
+tahoe_status contribs_validate_sparse(const int32_t *trees, const tahoe_sparse_node *nodes, const float *covers,
+                                      const tahoe_forest_params *p);
+tahoe_status contribs_build_sparse(tahoe_forest *f, const int32_t *trees, const tahoe_sparse_node *nodes, const float *covers);
 void contribs_destroy(tahoe_forest *f);
 // interventional TreeSHAP (interventional.hip): frees the background, if any
 void interventional_destroy(tahoe_forest *f);

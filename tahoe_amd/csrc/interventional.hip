@@ -211,9 +211,9 @@ using namespace tahoe;
 extern "C" tahoe_status tahoe_forest_set_background(tahoe_forest *f, const float *bg_dev, size_t bg_rows, void *stream)
 {
     if (!f) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_set_background: null forest");
-    if (f->sp)
-        return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_set_background: a sparse handle has no path tables; interventional "
-                                           "contributions need a dense handle created with TAHOE_CREATE_CONTRIBS");
+    if (f->sp && !f->cs)
+        return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_set_background: a sparse handle created without TAHOE_CREATE_CONTRIBS "
+                                           "has no path tables (tahoe_sparse_forest_create_ex)");
     if (!f->cs)
         return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_set_background: the handle was created without TAHOE_CREATE_CONTRIBS "
                                            "and has no path tables");
@@ -268,7 +268,7 @@ extern "C" tahoe_status tahoe_forest_set_background(tahoe_forest *f, const float
             return bail(fail(TAHOE_ERR_HIP, "tahoe_forest_set_background: mask kernel: %s", hipGetErrorString(e)));
     }
     // raw_c(r): tahoe_forest_predict_raw's bits (the same under every strategy); DIRECT serves every dense shape and allocates
-    // nothing.  The caller's strategy setting is restored.
+    // nothing (on a sparse handle it is sparse_kernel).  The caller's strategy setting is restored.
     const int saved = f->strategy;
     f->strategy = TAHOE_STRATEGY_DIRECT;
     const tahoe_status st = tahoe_forest_predict_raw(f, sums, bg_dev, bg_rows, stream);
@@ -305,9 +305,9 @@ extern "C" tahoe_status tahoe_forest_predict_contribs_interventional(tahoe_fores
                                                                      size_t rows, void *stream)
 {
     if (!f) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_contribs_interventional: null forest");
-    if (f->sp)
-        return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_contribs_interventional: a sparse handle has no path tables; "
-                                           "interventional contributions need a dense handle created with TAHOE_CREATE_CONTRIBS");
+    if (f->sp && !f->cs)
+        return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_contribs_interventional: a sparse handle created without "
+                                           "TAHOE_CREATE_CONTRIBS has no path tables (tahoe_sparse_forest_create_ex)");
     if (!f->cs)
         return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_contribs_interventional: the handle was created without "
                                            "TAHOE_CREATE_CONTRIBS and has no path tables");

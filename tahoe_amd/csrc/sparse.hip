@@ -62,12 +62,14 @@ constexpr int32_t kSFidMask = (int32_t)((1u << 30) - 1u);
 constexpr int32_t kSDefLeft = (int32_t)(1u << 30);
 constexpr int32_t kSIsLeaf = (int32_t)(1u << 31);
 
-template <bool TILE, bool WRITE_LEAF>
+// MC (multi-class handle, trees class-major): the owner lanes store the sum to sums[row * num_classes + c] at the last tree of
+// class c and restart from 0.0f (sums_in is not read); leaf indices go to the caller's tree numbering.
+template <bool TILE, bool WRITE_LEAF, bool MC = false>
 __global__ void __launch_bounds__(kBlock) sparse_kernel(const tahoe_sparse_node *__restrict__ nodes,
                                                         const int32_t *__restrict__ trees, const float *__restrict__ data,
                                                         float *sums, uint32_t *__restrict__ leaf_out,
                                                         const float *sums_in, size_t rows, int cols, int num_trees, float missing,
-                                                        int vec4_ok)
+                                                        int vec4_ok, int num_classes)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
@@ -94,7 +96,9 @@ __global__ void __launch_bounds__(kBlock) sparse_kernel(const tahoe_sparse_node 
         __syncthreads();
     }
     float sum = 0.0f;  // lanes 0..15: row 16*wave + lane of the tile
-    if (sums_in && lane < 16 && row0 + 16 * wave + lane < rows) sum = sums_in[row0 + 16 * wave + lane];
+    if (!MC && sums_in && lane < 16 && row0 + 16 * wave + lane < rows) sum = sums_in[row0 + 16 * wave + lane];
+    const int class_trees = MC ? num_trees / num_classes : 0;
+    int cls = 0, cend = class_trees;  // MC: the class being summed, and the tree after its last
     const int rounds = (num_trees + kWaves - 1) / kWaves;
     for (int r = 0; r < rounds; ++r) {
         const int t = r * kWaves + wave;
@@ -113,7 +117,7 @@ __global__ void __launch_bounds__(kBlock) sparse_kernel(const tahoe_sparse_node 
                 curr = (uint32_t)n.left_idx + go_right(x, n.val, (n.bits & kSDefLeft) != 0, missing);
             }
             if (WRITE_LEAF) {
-                if (row_ok) leaf_out[row * (size_t)num_trees + t] = curr;
+                if (row_ok) leaf_out[row * (size_t)num_trees + (MC ? mc_orig_tree(t, num_classes, class_trees) : t)] = curr;
             }
         }
         float *vb = vals + (size_t)(r & 1) * kWaves * kTileRows;
@@ -122,10 +126,18 @@ __global__ void __launch_bounds__(kBlock) sparse_kernel(const tahoe_sparse_node 
         if (lane < 16) {
             const int rr = 16 * wave + lane;
             const int nt = min(kWaves, num_trees - r * kWaves);
-            for (int j = 0; j < nt; ++j) sum += vb[j * kTileRows + rr];  // tree order
+            for (int j = 0; j < nt; ++j) {
+                sum += vb[j * kTileRows + rr];  // tree order
+                if (MC && r * kWaves + j + 1 == cend) {
+                    if (sums && row0 + rr < rows) sums[(row0 + rr) * (size_t)num_classes + cls] = sum;
+                    sum = 0.0f;
+                    ++cls;
+                    cend += class_trees;
+                }
+            }
         }
     }
-    if (sums && lane < 16) {
+    if (!MC && sums && lane < 16) {
         const size_t orow = row0 + 16 * wave + lane;
         if (orow < rows) sums[orow] = sum;
     }
@@ -149,12 +161,13 @@ constexpr int kSRing = 32;    // ring entries (trees)
 #endif
 constexpr int kSBatch = TAHOE_SPARSE_BATCH;   // trees the consumer takes per poll
 constexpr int kSSpinLimit = 1 << 22;
-template <int NW, bool WRITE_LEAF>
+// MC: as sparse_kernel's, in the consumer wave.
+template <int NW, bool WRITE_LEAF, bool MC = false>
 __global__ void __launch_bounds__(NW * 64) sparse_top_kernel(const uint2 *__restrict__ cnodes, const int32_t *__restrict__ ctrees,
                                                              const uint32_t *__restrict__ corig, const float *__restrict__ data,
                                                              float *sums, uint32_t *__restrict__ leaf_out,
                                                              const float *sums_in, size_t rows, int cols, int num_trees, float missing,
-                                                             int vec4_ok, int *__restrict__ error_flag)
+                                                             int vec4_ok, int *__restrict__ error_flag, int num_classes)
 {
     constexpr int NWALK = NW - 1;
     static_assert(kSRing >= 2 * kSBatch && kSRing > NWALK, "ring too small");
@@ -188,7 +201,9 @@ __global__ void __launch_bounds__(NW * 64) sparse_top_kernel(const uint2 *__rest
     if (wave == NWALK) {
         // ================= consumer: lane = row, trees in order =================
         __syncthreads();
-        float sum = (sums_in && row_ok) ? sums_in[row] : 0.0f;
+        float sum = (!MC && sums_in && row_ok) ? sums_in[row] : 0.0f;
+        const int class_trees = MC ? num_trees / num_classes : 0;
+        int cls = 0, cend = class_trees;  // MC: the class being summed, and the tree after its last
         bool dead = false;
         for (int t0 = 0; t0 < num_trees && !dead; t0 += kSBatch) {
             const int nb = min(kSBatch, num_trees - t0);
@@ -204,12 +219,20 @@ __global__ void __launch_bounds__(NW * 64) sparse_top_kernel(const uint2 *__rest
             }
             if (dead) break;
             TAHOE_LDS_ACQUIRE();  // the values are read after the flags
-            for (int j = 0; j < nb; ++j) sum += ring_vals[((t0 + j) % kSRing) * kTileRows + lane];  // tree order
+            for (int j = 0; j < nb; ++j) {
+                sum += ring_vals[((t0 + j) % kSRing) * kTileRows + lane];  // tree order
+                if (MC && t0 + j + 1 == cend) {
+                    if (sums && row_ok) sums[row * (size_t)num_classes + cls] = sum;
+                    sum = 0.0f;
+                    ++cls;
+                    cend += class_trees;
+                }
+            }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             if (lane == 0) lds_flag_store(consumed, (uint32_t)(t0 + nb));
         }
         if (dead && lane == 0) atomicOr(error_flag, 1);
-        if (sums && row_ok) sums[row] = sum;
+        if (!MC && sums && row_ok) sums[row] = sum;
         return;
     }
 
@@ -262,7 +285,9 @@ __global__ void __launch_bounds__(NW * 64) sparse_top_kernel(const uint2 *__rest
             curr = left + r;
         }
         if (WRITE_LEAF) {
-            if (row_ok) leaf_out[row * (size_t)num_trees + t] = corig[ctrees[t] + curr];
+            if (row_ok)
+                leaf_out[row * (size_t)num_trees + (MC ? mc_orig_tree(t, num_classes, num_trees / num_classes) : t)] =
+                    corig[ctrees[t] + curr];
         }
         if (t >= kSRing) {  // ring entry still in use by tree t - kSRing?
             int spins = 0;
@@ -304,14 +329,16 @@ constexpr int kSQLevels = 9;
 #define TAHOE_SQ_DEP 0  // 1: the top walk reads only the chosen child (make SQDEP=1; K5 measured in profiles/r04/tune_dep.txt)
 #endif
 constexpr bool kSparseQDep = TAHOE_SQ_DEP != 0;
-template <int NWALK, bool WRITE_LEAF, int K, int RING>
+// MC: the consumer of qring_kernel's MC form -- a group that starts inside class c continues its partial sum from
+// sums_in[row * num_classes + c], one that ends inside a class leaves its partial sum in sums.
+template <int NWALK, bool WRITE_LEAF, int K, int RING, bool MC = false>
 __global__ void __launch_bounds__((NWALK + 1) * 64)
     sparse_q_kernel(const uint16_t *__restrict__ xq, const uint32_t *__restrict__ qtop, const uint4 *__restrict__ qblocks,
                     const int32_t *__restrict__ qblkoff, const uint32_t *__restrict__ qbotpos, const uint32_t *__restrict__ qblkpos,
                     const int32_t *__restrict__ ctrees, const uint32_t *__restrict__ corig,
                     float *sums, uint32_t *__restrict__ leaf_out, size_t rows, int cols, int tree_lo, int num_trees,
                     int total_trees, const uint32_t *__restrict__ chunk_flags, int *__restrict__ error_flag, const float *sums_in,
-                    int cshift, size_t row_begin)
+                    int cshift, size_t row_begin, int num_classes)
 {
     // `rows` is the END of the rows this launch walks, row_begin (a multiple of 384) their start (see qreg_plan)
     constexpr int TR = 64 * K;
@@ -348,11 +375,28 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
         // ================= consumer: ordered accumulation =================
         __syncthreads();
         float sum[K];  // continues the running sums of the previous tree group (sums_in may alias sums)
+        // MC: class cls of the group's first tree; its trees end after local tree cend - 1
+        const int class_trees = MC ? total_trees / num_classes : 0;
+        int cls = MC ? tree_lo / class_trees : 0;
+        int cend = MC ? (cls + 1) * class_trees - tree_lo : 0;
+        const bool mid_class = MC && cls * class_trees != tree_lo;
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             const size_t irow = row0 + k * 64 + lane;
-            sum[k] = (sums_in && irow < rows) ? sums_in[irow] : 0.0f;
+            if (MC)
+                sum[k] = (mid_class && sums_in && irow < rows) ? sums_in[irow * (size_t)num_classes + cls] : 0.0f;
+            else
+                sum[k] = (sums_in && irow < rows) ? sums_in[irow] : 0.0f;
         }
+        auto flush = [&]() {  // MC: class cls's sums (complete, or the partial sum the next group continues)
+            if (sums) {
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    const size_t orow = row0 + k * 64 + lane;
+                    if (orow < rows) sums[orow * (size_t)num_classes + cls] = sum[k];
+                }
+            }
+        };
         bool dead = false;
         for (int t0 = 0; t0 < num_trees && !dead; t0 += BATCH) {
             const int nb = min(BATCH, num_trees - t0);
@@ -372,12 +416,21 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
                 const int e = (t0 + j) % RING;
 #pragma unroll
                 for (int k = 0; k < K; ++k) sum[k] += ring_vals[e * TR + k * 64 + lane];  // tree order
+                if (MC && t0 + j + 1 == cend) {
+                    flush();
+#pragma unroll
+                    for (int k = 0; k < K; ++k) sum[k] = 0.0f;
+                    ++cls;
+                    cend += class_trees;
+                }
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             if (lane == 0) lds_flag_store(consumed, (uint32_t)(t0 + nb));
         }
         if (dead && lane == 0) atomicOr(error_flag, 1);
-        if (sums) {
+        if (MC) {
+            if (num_trees > cend - class_trees) flush();  // the group ends inside class cls
+        } else if (sums) {
 #pragma unroll
             for (int k = 0; k < K; ++k) {
                 const size_t orow = row0 + k * 64 + lane;
@@ -460,7 +513,9 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
 #pragma unroll
                 for (int k = 0; k < K; ++k) {
                     const size_t row = row0 + k * 64 + lane;
-                    if (row < rows) leaf_out[row * (size_t)total_trees + tree_lo + t] = corig[ctrees[tree_lo + t] + cpos_p[k]];
+                    if (row < rows)
+                        leaf_out[MC ? row * (size_t)total_trees + mc_orig_tree(tree_lo + t, num_classes, total_trees / num_classes)
+                                    : row * (size_t)total_trees + tree_lo + t] = corig[ctrees[tree_lo + t] + cpos_p[k]];
                 }
             }
             if (t >= RING) {  // ring entry still in use by tree t - RING?
@@ -591,14 +646,24 @@ static void sparse_q_launch_form(tahoe_forest *f, const tahoe_qgroup &g, float *
     const unsigned grid = (unsigned)((rows_end - row_begin + 64 * K - 1) / (64 * K));
     if (grid == 0) return;
     const int lds = (int)qreg_lds_for(K, NWALK, RING);
-    if (leaf_out)
-        hipLaunchKernelGGL((sparse_q_kernel<NWALK, true, K, RING>), dim3(grid), dim3((NWALK + 1) * 64), lds, stream, f->q->xq, sp->qtop, sp->qblocks,
-                           sp->qblkoff, sp->qbotpos, sp->qblkpos, sp->ctrees, sp->corig, sums, leaf_out, rows_end, f->p.num_cols, g.tree_lo, g.num_trees, f->p.num_trees,
-                           f->q->chunk_flags, f->error_flag, sums_in, cshift, row_begin);
-    else
-        hipLaunchKernelGGL((sparse_q_kernel<NWALK, false, K, RING>), dim3(grid), dim3((NWALK + 1) * 64), lds, stream, f->q->xq, sp->qtop, sp->qblocks,
-                           sp->qblkoff, sp->qbotpos, sp->qblkpos, sp->ctrees, sp->corig, sums, leaf_out, rows_end, f->p.num_cols, g.tree_lo, g.num_trees, f->p.num_trees,
-                           f->q->chunk_flags, f->error_flag, sums_in, cshift, row_begin);
+    const int nc = f->num_classes;
+#define TAHOE_SPARSE_Q(LEAF_, MC_)                                                                                                  \
+    hipLaunchKernelGGL((sparse_q_kernel<NWALK, LEAF_, K, RING, MC_>), dim3(grid), dim3((NWALK + 1) * 64), lds, stream, f->q->xq,  \
+                       sp->qtop, sp->qblocks, sp->qblkoff, sp->qbotpos, sp->qblkpos, sp->ctrees, sp->corig, sums, leaf_out,       \
+                       rows_end, f->p.num_cols, g.tree_lo, g.num_trees, f->p.num_trees, f->q->chunk_flags, f->error_flag, sums_in, \
+                       cshift, row_begin, nc)
+    if (nc > 1) {
+        if (leaf_out)
+            TAHOE_SPARSE_Q(true, true);
+        else
+            TAHOE_SPARSE_Q(false, true);
+    } else {
+        if (leaf_out)
+            TAHOE_SPARSE_Q(true, false);
+        else
+            TAHOE_SPARSE_Q(false, false);
+    }
+#undef TAHOE_SPARSE_Q
 }
 
 // quantise + walk per tree group, in stream order; the tile plan of the dense region form (qreg_plan)
@@ -665,19 +730,32 @@ tahoe_status sparse_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, con
         const int nw = sparse_top_waves(f);
         if (nw == 0) return fail(TAHOE_ERR_UNSUPPORTED, "sparse TILEBLOCK: the compact form or its LDS tile is unavailable");
         const int lds = (int)sparse_top_lds(f, nw);
-#define TAHOE_SPARSE_TOP(NW_, LEAF_)                                                                                     \
-    hipLaunchKernelGGL((sparse_top_kernel<NW_, LEAF_>), dim3(grid), dim3(NW_ * 64), lds, stream, sp->cnodes, sp->ctrees, \
-                       sp->corig, data, sums, leaf_out, sums_in, rows, f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, f->error_flag)
-        if (nw == 16) {
+        const int nc = f->num_classes;
+#define TAHOE_SPARSE_TOP(NW_, LEAF_, MC_)                                                                                     \
+    hipLaunchKernelGGL((sparse_top_kernel<NW_, LEAF_, MC_>), dim3(grid), dim3(NW_ * 64), lds, stream, sp->cnodes, sp->ctrees, \
+                       sp->corig, data, sums, leaf_out, sums_in, rows, f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, f->error_flag, nc)
+        if (nc > 1) {
+            if (nw == 16) {
+                if (leaf_out)
+                    TAHOE_SPARSE_TOP(16, true, true);
+                else
+                    TAHOE_SPARSE_TOP(16, false, true);
+            } else {
+                if (leaf_out)
+                    TAHOE_SPARSE_TOP(8, true, true);
+                else
+                    TAHOE_SPARSE_TOP(8, false, true);
+            }
+        } else if (nw == 16) {
             if (leaf_out)
-                TAHOE_SPARSE_TOP(16, true);
+                TAHOE_SPARSE_TOP(16, true, false);
             else
-                TAHOE_SPARSE_TOP(16, false);
+                TAHOE_SPARSE_TOP(16, false, false);
         } else {
             if (leaf_out)
-                TAHOE_SPARSE_TOP(8, true);
+                TAHOE_SPARSE_TOP(8, true, false);
             else
-                TAHOE_SPARSE_TOP(8, false);
+                TAHOE_SPARSE_TOP(8, false, false);
         }
 #undef TAHOE_SPARSE_TOP
         TAHOE_HIP_TRY(hipGetLastError());
@@ -685,19 +763,32 @@ tahoe_status sparse_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, con
     }
     const bool tile = strategy == TAHOE_STRATEGY_ROWTILE;
     const int lds = (int)sparse_lds(f, tile);
-#define TAHOE_SPARSE_LAUNCH(TILE_, LEAF_)                                                                            \
-    hipLaunchKernelGGL((sparse_kernel<TILE_, LEAF_>), dim3(grid), dim3(kBlock), lds, stream, sp->nodes, sp->trees, data, \
-                       sums, leaf_out, sums_in, rows, f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok)
-    if (tile) {
+    const int nc = f->num_classes;
+#define TAHOE_SPARSE_LAUNCH(TILE_, LEAF_, MC_)                                                                            \
+    hipLaunchKernelGGL((sparse_kernel<TILE_, LEAF_, MC_>), dim3(grid), dim3(kBlock), lds, stream, sp->nodes, sp->trees, data, \
+                       sums, leaf_out, sums_in, rows, f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, nc)
+    if (nc > 1) {
+        if (tile) {
+            if (leaf_out)
+                TAHOE_SPARSE_LAUNCH(true, true, true);
+            else
+                TAHOE_SPARSE_LAUNCH(true, false, true);
+        } else {
+            if (leaf_out)
+                TAHOE_SPARSE_LAUNCH(false, true, true);
+            else
+                TAHOE_SPARSE_LAUNCH(false, false, true);
+        }
+    } else if (tile) {
         if (leaf_out)
-            TAHOE_SPARSE_LAUNCH(true, true);
+            TAHOE_SPARSE_LAUNCH(true, true, false);
         else
-            TAHOE_SPARSE_LAUNCH(true, false);
+            TAHOE_SPARSE_LAUNCH(true, false, false);
     } else {
         if (leaf_out)
-            TAHOE_SPARSE_LAUNCH(false, true);
+            TAHOE_SPARSE_LAUNCH(false, true, false);
         else
-            TAHOE_SPARSE_LAUNCH(false, false);
+            TAHOE_SPARSE_LAUNCH(false, false, false);
     }
 #undef TAHOE_SPARSE_LAUNCH
     TAHOE_HIP_TRY(hipGetLastError());
@@ -932,7 +1023,10 @@ static tahoe_status sparse_q_build(tahoe_forest *f, const std::vector<uint2> &cn
     if ((e = q_upload(&sp->qblkpos, h_blkpos.data(), h_blkpos.size(), &f->device_bytes)) != hipSuccess) return bad("qblkpos");
     if ((e = q_upload(&sp->qblkoff, h_blkoff.data(), h_blkoff.size(), &f->device_bytes)) != hipSuccess) return bad("qblkoff");
     for (const void *k : {(const void *)&sparse_q_kernel<kReg3Walkers, false, 3, kReg3Ring>, (const void *)&sparse_q_kernel<kReg3Walkers, true, 3, kReg3Ring>,
-                          (const void *)&sparse_q_kernel<15, false, 2, kQRing>, (const void *)&sparse_q_kernel<15, true, 2, kQRing>})
+                          (const void *)&sparse_q_kernel<15, false, 2, kQRing>, (const void *)&sparse_q_kernel<15, true, 2, kQRing>,
+                          (const void *)&sparse_q_kernel<kReg3Walkers, false, 3, kReg3Ring, true>,
+                          (const void *)&sparse_q_kernel<kReg3Walkers, true, 3, kReg3Ring, true>,
+                          (const void *)&sparse_q_kernel<15, false, 2, kQRing, true>, (const void *)&sparse_q_kernel<15, true, 2, kQRing, true>})
         if ((e = allow_max_lds(k, f->lds_limit)) != hipSuccess)
             return fail(TAHOE_ERR_HIP, "sparse_q_build: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
     if ((e = quantize_allow_lds(f)) != hipSuccess)
@@ -940,14 +1034,10 @@ static tahoe_status sparse_q_build(tahoe_forest *f, const std::vector<uint2> &cn
     return TAHOE_OK;
 }
 
-}  // namespace tahoe
-
-using namespace tahoe;
-
-extern "C" {
-
-tahoe_status tahoe_sparse_forest_create(tahoe_forest **out, const int32_t *trees, const tahoe_sparse_node *nodes,
-                                        const tahoe_forest_params *p)
+// num_classes > 1 / covers: tahoe_sparse_forest_create_ex, whose own checks have run.  A multi-class forest is stored
+// class-major (internal tree p = the caller's tree (p % Tc) C + p / Tc); every builder below then runs on that order unchanged.
+static tahoe_status create_sparse(tahoe_forest **out, const int32_t *trees, const tahoe_sparse_node *nodes, const float *covers,
+                                  const tahoe_forest_params *p, int num_classes, unsigned flags)
 {
     if (!out || !p) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_sparse_forest_create: null argument");
     *out = nullptr;
@@ -956,7 +1046,7 @@ tahoe_status tahoe_sparse_forest_create(tahoe_forest **out, const int32_t *trees
     if (p->algo != TAHOE_ALGO_NAIVE) return fail(TAHOE_ERR_INVALID_ARG, "only NAIVE algorithm is supported for sparse forests");
     if (p->num_trees < 0) return fail(TAHOE_ERR_INVALID_ARG, "num_trees must be non-negative");
     if (p->num_cols < 0) return fail(TAHOE_ERR_INVALID_ARG, "num_cols must be non-negative");
-    if ((p->output & ~(TAHOE_OUT_AVG | TAHOE_OUT_SIGMOID | TAHOE_OUT_THRESHOLD)) != 0)
+    if ((p->output & ~(TAHOE_OUT_AVG | TAHOE_OUT_SIGMOID | TAHOE_OUT_THRESHOLD | (num_classes > 1 ? TAHOE_OUT_SOFTMAX : 0))) != 0)
         return fail(TAHOE_ERR_INVALID_ARG, "output should be a combination of RAW, AVG, SIGMOID and THRESHOLD");
     if (p->num_trees > 0 && (!trees || !nodes)) return fail(TAHOE_ERR_INVALID_ARG, "trees / nodes is null");
     // Structure check (the reference trusts its input): roots ascending, every child pair inside its tree
@@ -978,6 +1068,10 @@ tahoe_status tahoe_sparse_forest_create(tahoe_forest **out, const int32_t *trees
                             p->num_cols);
         }
     }
+    if (flags & TAHOE_CREATE_CONTRIBS) {  // the covers and the path lengths, on the caller's nodes, before a device is touched
+        const tahoe_status cs = contribs_validate_sparse(trees, nodes, covers, p);
+        if (cs != TAHOE_OK) return cs;
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail(TAHOE_ERR_NO_DEVICE, "no HIP device is visible; libtahoe_amd has no CPU path");
@@ -994,6 +1088,8 @@ tahoe_status tahoe_sparse_forest_create(tahoe_forest **out, const int32_t *trees
     }
     f->sp = sp;
     f->p = *p;
+    f->num_classes = num_classes;
+    f->class_trees = p->num_trees / num_classes;
     f->depth = 0;  // a placeholder value, as in sparse_forest::init (Struct.h:2332)
     f->device = dev;
     f->num_cus = prop.multiProcessorCount;
@@ -1002,6 +1098,24 @@ tahoe_status tahoe_sparse_forest_create(tahoe_forest **out, const int32_t *trees
     f->bits_bytes = 4;
     sp->num_nodes = (size_t)p->num_nodes;
     sp->max_tree_nodes = max_tree_nodes;
+    const int32_t *const caller_trees = trees;
+    const tahoe_sparse_node *const caller_nodes = nodes;
+    std::vector<int32_t> mc_trees;
+    std::vector<tahoe_sparse_node> mc_nodes;
+    if (num_classes > 1) {  // class-major copy: each tree's node range moves as a block (child links are root-relative)
+        const int T = p->num_trees, Tc = T / num_classes;
+        mc_trees.resize((size_t)T);
+        mc_nodes.reserve(sp->num_nodes);
+        for (int q = 0; q < T; ++q) {
+            const int t = (q % Tc) * num_classes + q / Tc;
+            const long long lo = trees[t], hi = (t + 1 < T) ? trees[t + 1] : p->num_nodes;
+            mc_trees[(size_t)q] = (int32_t)mc_nodes.size();
+            mc_nodes.insert(mc_nodes.end(), nodes + lo, nodes + hi);
+        }
+        sp->num_nodes = mc_nodes.size();  // (nodes before the first root are not copied)
+        trees = mc_trees.data();
+        nodes = mc_nodes.data();
+    }
     auto bail = [&](hipError_t e, const char *what) {
         tahoe_forest_destroy(f);
         return fail(TAHOE_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
@@ -1023,6 +1137,10 @@ tahoe_status tahoe_sparse_forest_create(tahoe_forest **out, const int32_t *trees
             return bail(e, "hipFuncSetAttribute(sparse)");
         if ((e = allow_max_lds(reinterpret_cast<const void *>(&sparse_kernel<true, true>), f->lds_limit)) != hipSuccess)
             return bail(e, "hipFuncSetAttribute(sparse)");
+        if (num_classes > 1 &&
+            ((e = allow_max_lds(reinterpret_cast<const void *>(&sparse_kernel<true, false, true>), f->lds_limit)) != hipSuccess ||
+             (e = allow_max_lds(reinterpret_cast<const void *>(&sparse_kernel<true, true, true>), f->lds_limit)) != hipSuccess))
+            return bail(e, "hipFuncSetAttribute(sparse)");
     }
     // ---- compact breadth-first copy (sparse_top_kernel) ----
     if (p->num_cols <= 32767 && p->num_trees > 0) {
@@ -1032,7 +1150,7 @@ tahoe_status tahoe_sparse_forest_create(tahoe_forest **out, const int32_t *trees
         std::vector<uint32_t> order, newpos;
         bool ok = true;
         for (int t = 0; t < p->num_trees && ok; ++t) {
-            const long long lo = trees[t], hi = (t + 1 < p->num_trees) ? trees[t + 1] : p->num_nodes;
+            const long long lo = trees[t], hi = (t + 1 < p->num_trees) ? trees[t + 1] : (long long)sp->num_nodes;
             const tahoe_sparse_node *tn = nodes + lo;
             // breadth-first order of the reachable nodes; a child pair stays adjacent
             order.assign(1, 0u);
@@ -1082,6 +1200,10 @@ tahoe_status tahoe_sparse_forest_create(tahoe_forest **out, const int32_t *trees
             for (const void *k : {(const void *)&sparse_top_kernel<16, false>, (const void *)&sparse_top_kernel<16, true>,
                                   (const void *)&sparse_top_kernel<8, false>, (const void *)&sparse_top_kernel<8, true>})
                 if ((e = allow_max_lds(k, f->lds_limit)) != hipSuccess) return bail(e, "hipFuncSetAttribute(sparse_top)");
+            if (num_classes > 1)
+                for (const void *k : {(const void *)&sparse_top_kernel<16, false, true>, (const void *)&sparse_top_kernel<16, true, true>,
+                                      (const void *)&sparse_top_kernel<8, false, true>, (const void *)&sparse_top_kernel<8, true, true>})
+                    if ((e = allow_max_lds(k, f->lds_limit)) != hipSuccess) return bail(e, "hipFuncSetAttribute(sparse_top)");
             const tahoe_status qs = sparse_q_build(f, cn, ct);
             if (qs != TAHOE_OK) {
                 tahoe_forest_destroy(f);
@@ -1089,18 +1211,61 @@ tahoe_status tahoe_sparse_forest_create(tahoe_forest **out, const int32_t *trees
             }
         }
     }
+    if (flags & TAHOE_CREATE_CONTRIBS) {  // from the caller's trees, in the caller's numbering (contribs_build's order)
+        const tahoe_status cs = contribs_build_sparse(f, caller_trees, caller_nodes, covers);
+        if (cs != TAHOE_OK) {
+            tahoe_forest_destroy(f);
+            return cs;
+        }
+    }
     *out = f;
     return TAHOE_OK;
 }
 
+}  // namespace tahoe
+
+using namespace tahoe;
+
+extern "C" {
+
+tahoe_status tahoe_sparse_forest_create(tahoe_forest **out, const int32_t *trees, const tahoe_sparse_node *nodes,
+                                        const tahoe_forest_params *p)
+{
+    return create_sparse(out, trees, nodes, nullptr, p, 1, 0u);
+}
+
+tahoe_status tahoe_sparse_forest_create_ex(tahoe_forest **out, const int32_t *trees, const tahoe_sparse_node *nodes,
+                                           const float *covers, const tahoe_forest_params *p, int num_classes, unsigned flags)
+{
+    // every check here (and in create_sparse) runs before a device is touched
+    if (!out || !p) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_sparse_forest_create_ex: null argument");
+    *out = nullptr;
+    if (num_classes < 1 || num_classes > 1024) return fail(TAHOE_ERR_INVALID_ARG, "num_classes must be in [1,1024], got %d", num_classes);
+    if (p->num_trees < 0 || p->num_trees % num_classes != 0)
+        return fail(TAHOE_ERR_INVALID_ARG, "num_trees (%d) must be a non-negative multiple of num_classes (%d)", p->num_trees, num_classes);
+    if ((p->output & TAHOE_OUT_SOFTMAX) != 0 && num_classes == 1)
+        return fail(TAHOE_ERR_INVALID_ARG, "SOFTMAX needs num_classes > 1");
+    if ((p->output & TAHOE_OUT_SOFTMAX) != 0 && (p->output & TAHOE_OUT_SIGMOID) != 0)
+        return fail(TAHOE_ERR_INVALID_ARG, "SOFTMAX and SIGMOID exclude each other");
+    if ((p->output & TAHOE_OUT_THRESHOLD) != 0 && num_classes > 1)
+        return fail(TAHOE_ERR_INVALID_ARG, "THRESHOLD needs num_classes == 1");
+    if ((flags & ~(unsigned)TAHOE_CREATE_CONTRIBS) != 0)
+        return fail(TAHOE_ERR_INVALID_ARG, "unknown create flags 0x%x (a sparse handle takes TAHOE_CREATE_CONTRIBS only)", flags);
+    if ((flags & TAHOE_CREATE_CONTRIBS) && !covers)
+        return fail(TAHOE_ERR_INVALID_ARG, "TAHOE_CREATE_CONTRIBS needs covers (one per node)");
+    return create_sparse(out, trees, nodes, covers, p, num_classes, flags);
+}
+
 // dense2sparse, BaseTahoeTest.h:728-764: per tree a root, then for every inner node its two children are
 // appended together (left_idx is relative to the tree's root) and converted depth-first, left first.
-tahoe_status tahoe_dense_to_sparse(const tahoe_dense_node *dense, int num_trees, int depth, tahoe_sparse_node **nodes_out,
-                                   int32_t **trees_out, size_t *num_nodes_out)
+// covers_out (optional): the weight of the dense node each sparse node came from.
+static tahoe_status dense_to_sparse(const tahoe_dense_node *dense, int num_trees, int depth, tahoe_sparse_node **nodes_out,
+                                    int32_t **trees_out, float **covers_out, size_t *num_nodes_out)
 {
     if (!dense || !nodes_out || !trees_out || !num_nodes_out || num_trees < 0 || depth < 0 || depth > 30)
         return fail(TAHOE_ERR_INVALID_ARG, "tahoe_dense_to_sparse: bad argument");
     std::vector<tahoe_sparse_node> out;
+    std::vector<float> cov;  // parallel to out
     std::vector<int32_t> roots((size_t)num_trees);
     const size_t per_tree = (size_t)tahoe_tree_num_nodes(depth);
     struct Item {
@@ -1111,6 +1276,7 @@ tahoe_status tahoe_dense_to_sparse(const tahoe_dense_node *dense, int num_trees,
         const tahoe_dense_node *root = dense + (size_t)t * per_tree;
         const size_t i_root = out.size();
         out.push_back(tahoe_sparse_node{0.f, 0, 0});
+        cov.push_back(0.f);
         roots[(size_t)t] = (int32_t)i_root;
         stack.assign(1, Item{0, i_root});
         while (!stack.empty()) {
@@ -1118,8 +1284,8 @@ tahoe_status tahoe_dense_to_sparse(const tahoe_dense_node *dense, int num_trees,
             stack.pop_back();
             if (it.i_dense >= per_tree) return fail(TAHOE_ERR_INVALID_FOREST, "tree %d: a bottom-level node is not a leaf", t);
             int fid, def_left, is_leaf;
-            float value;
-            tahoe_decode_node(&root[it.i_dense], &value, nullptr, &fid, &def_left, &is_leaf);
+            float value, weight;
+            tahoe_decode_node(&root[it.i_dense], &value, &weight, &fid, &def_left, &is_leaf);
             tahoe_sparse_node n;
             n.val = value;
             n.bits = (fid & kSFidMask) | (def_left ? kSDefLeft : 0) | (is_leaf ? kSIsLeaf : 0);
@@ -1128,27 +1294,46 @@ tahoe_status tahoe_dense_to_sparse(const tahoe_dense_node *dense, int num_trees,
                 const size_t left = out.size();
                 out.push_back(tahoe_sparse_node{0.f, 0, 0});
                 out.push_back(tahoe_sparse_node{0.f, 0, 0});
+                cov.resize(out.size(), 0.f);
                 n.left_idx = (int32_t)(left - i_root);
                 // depth-first, left subtree first: push right, then left
                 stack.push_back(Item{2 * it.i_dense + 2, left + 1});
                 stack.push_back(Item{2 * it.i_dense + 1, left});
             }
             out[it.i_sparse] = n;
+            cov[it.i_sparse] = weight;
         }
     }
     tahoe_sparse_node *nodes = (tahoe_sparse_node *)malloc(std::max<size_t>(out.size(), 1) * sizeof(tahoe_sparse_node));
     int32_t *trees = (int32_t *)malloc(std::max<size_t>(roots.size(), 1) * sizeof(int32_t));
-    if (!nodes || !trees) {
+    float *covers = covers_out ? (float *)malloc(std::max<size_t>(cov.size(), 1) * sizeof(float)) : nullptr;
+    if (!nodes || !trees || (covers_out && !covers)) {
         free(nodes);
         free(trees);
+        free(covers);
         return fail(TAHOE_ERR_NO_MEMORY, "tahoe_dense_to_sparse");
     }
     if (!out.empty()) memcpy(nodes, out.data(), out.size() * sizeof(tahoe_sparse_node));
     if (!roots.empty()) memcpy(trees, roots.data(), roots.size() * sizeof(int32_t));
+    if (covers && !cov.empty()) memcpy(covers, cov.data(), cov.size() * sizeof(float));
     *nodes_out = nodes;
     *trees_out = trees;
+    if (covers_out) *covers_out = covers;
     *num_nodes_out = out.size();
     return TAHOE_OK;
+}
+
+tahoe_status tahoe_dense_to_sparse(const tahoe_dense_node *dense, int num_trees, int depth, tahoe_sparse_node **nodes_out,
+                                   int32_t **trees_out, size_t *num_nodes_out)
+{
+    return dense_to_sparse(dense, num_trees, depth, nodes_out, trees_out, nullptr, num_nodes_out);
+}
+
+tahoe_status tahoe_dense_to_sparse_ex(const tahoe_dense_node *dense, int num_trees, int depth, tahoe_sparse_node **nodes_out,
+                                      int32_t **trees_out, float **covers_out, size_t *num_nodes_out)
+{
+    if (!covers_out) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_dense_to_sparse_ex: bad argument");
+    return dense_to_sparse(dense, num_trees, depth, nodes_out, trees_out, covers_out, num_nodes_out);
 }
 
 // Synthetic irregular forest: tree t may grow to depth d_t = min_depth + (x mod (max_depth -

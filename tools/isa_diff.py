@@ -15,7 +15,8 @@ import re
 import subprocess
 import sys
 
-FLAGGED = ("direct_kernel", "rowtile_kernel", "qring_kernel", "qwide_kernel")  # kernels that carry the appended flag
+FLAGGED = ("direct_kernel", "rowtile_kernel", "qring_kernel", "qwide_kernel",  # kernels that carry the appended flag
+           "sparse_kernel", "sparse_top_kernel", "sparse_q_kernel")
 
 
 def functions(path):
