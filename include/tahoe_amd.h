@@ -283,6 +283,34 @@ tahoe_status tahoe_forest_set_background(tahoe_forest *f, const float *bg_dev, s
 tahoe_status tahoe_forest_predict_contribs_interventional(tahoe_forest *f, float *phi_dev, const float *data_dev, size_t rows,
                                                           void *stream);
 
+/* Saabas contributions (XGBoost predict(..., pred_contribs=True, approx_contribs=True)): one root-to-leaf walk per (row, tree)
+ * instead of exact TreeSHAP.  A create flag for tahoe_forest_create_ex, tahoe_forest_create_multiclass and
+ * tahoe_sparse_forest_create_ex; it combines with TAHOE_CREATE_CONTRIBS and, on dense handles, with TAHOE_CREATE_PROB_RELAYOUT.
+ * dense_node_t.weight (dense) or covers[] (sparse) are checked exactly as TAHOE_CREATE_CONTRIBS checks them, before a device is
+ * touched, with the same codes and messages; on a sparse handle NULL covers with the flag is TAHOE_ERR_INVALID_ARG.  The flag
+ * alone builds no path bins and brings neither the num_cols <= LDS / 20 limit nor the 31-distinct-features-per-path limit of
+ * TAHOE_CREATE_CONTRIBS: any num_cols (below 2^29) and any depth.  It builds one 16-byte record per normalised heap node of a
+ * dense tree, or one 8-byte pair of child deltas per sparse node, counted in tahoe_forest_info.device_bytes.
+ *
+ * Node means, on the host in float64 from the caller's trees: E(leaf) = (double)val; at an internal node
+ * E(n) = (wl * E(l) + wr * E(r)) / (wl + wr), in that order, wl / wr the children's covers as double.  Each child of a reachable
+ * internal node carries d(child) = (float)(E(child) - E(n)), rounded once.  Per row and tree the row follows the path of
+ * tahoe_forest_predict (missing sentinel -> default branch, NaN left, else right iff x >= thr) and every internal node n on it
+ * adds d(child taken) to phi[c][fid(n)]; the padding below a shallow leaf of a dense tree adds nothing, and a tree whose root
+ * is a leaf adds nothing.  phi[row][c][i], i < F, is a float32 sum from +0.0f over class c's trees c, c + C, ... in increasing
+ * order, root to leaf within a tree; with TAHOE_OUT_AVG the finished sum is divided by (float)Tc.  A feature the row never
+ * splits on is +0.0f.  Column F is the bias column of tahoe_forest_predict_contribs, bit for bit.  sum_i phi_i + bias is the
+ * margin before SIGMOID / THRESHOLD / SOFTMAX up to rounding (the deltas of a path telescope to leaf - E(root)). */
+#define TAHOE_CREATE_APPROX_CONTRIBS 0x10u
+/* phi_dev[rows][num_classes][num_cols + 1] <- the Saabas contributions above; the layout of tahoe_forest_predict_contribs.
+ * Deterministic: the same bits on every call, for a row in any batch, under every strategy (the strategy is not used), with or
+ * without TAHOE_CREATE_PROB_RELAYOUT; class c of a multi-class handle gives the bits of a handle created from class c's
+ * sub-forest; a sparse handle converted with tahoe_dense_to_sparse_ex gives the dense handle's bits.  No atomics.  Asynchronous
+ * on `stream`; allocates nothing (graph-capturable).  Refusals, nothing launched, in this order: NULL handle:
+ * TAHOE_ERR_INVALID_ARG; a handle created without TAHOE_CREATE_APPROX_CONTRIBS: TAHOE_ERR_UNSUPPORTED; then rows == 0: TAHOE_OK;
+ * NULL phi_dev / data_dev with rows > 0, or rows x C x (num_cols + 1) x 4 overflowing size_t: TAHOE_ERR_INVALID_ARG. */
+tahoe_status tahoe_forest_predict_contribs_approx(tahoe_forest *f, float *phi_dev, const float *data_dev, size_t rows, void *stream);
+
 /* ---- sparse (irregular) forests: sparse_node_t Struct.h:50-54, sparse_storage Struct.h:343-354,
  * init_sparse / sparse_forest::init (BaseTahoeTest.h:766-772, Struct.h:2329-2343) ---- */
 typedef struct {
@@ -306,7 +334,8 @@ tahoe_status tahoe_sparse_forest_create(tahoe_forest **out, const int32_t *trees
  *    from 0.0f in increasing tree order, and predict / predict_raw / the sums of predict_leaf_idx write rows x C values, bit
  *    for bit the single-class sparse handle of trees c, c + C, ...; leaf indices stay in the caller's tree numbering.
  *    tahoe_forest_predict_accumulate and tahoe_forest_predict_host return TAHOE_ERR_UNSUPPORTED when C > 1.
- *  - flags: TAHOE_CREATE_CONTRIBS only (any other bit, TAHOE_CREATE_PROB_RELAYOUT included: TAHOE_ERR_INVALID_ARG).  With it,
+ *  - flags: TAHOE_CREATE_CONTRIBS and / or TAHOE_CREATE_APPROX_CONTRIBS (any other bit, TAHOE_CREATE_PROB_RELAYOUT included:
+ *    TAHOE_ERR_INVALID_ARG; the covers of TAHOE_CREATE_APPROX_CONTRIBS are checked as below, its path lengths are not).  With it,
  *    covers[i] is the cover of nodes[i] (params->num_nodes floats; NULL: TAHOE_ERR_INVALID_ARG); at every reachable internal
  *    node the covers of nodes left_idx and left_idx + 1 must be finite and >= 0 with a positive sum (TAHOE_ERR_INVALID_FOREST
  *    naming the tree and node), and no reachable leaf's path may have more than 31 distinct features (TAHOE_ERR_UNSUPPORTED

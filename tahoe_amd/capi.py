@@ -36,6 +36,7 @@ OUT_SOFTMAX = 0x1000  # multi-class handles only (tahoe_forest_create_multiclass
 STRATEGY_AUTO, STRATEGY_DIRECT, STRATEGY_ROWTILE, STRATEGY_TILEBLOCK, STRATEGY_TILERING, STRATEGY_QRING = range(6)
 CREATE_PROB_RELAYOUT = 0x1
 CREATE_CONTRIBS = 0x4  # per-feature contributions (tahoe_forest_predict_contribs); node weights are covers
+CREATE_APPROX_CONTRIBS = 0x10  # Saabas contributions (tahoe_forest_predict_contribs_approx); node weights are covers
 STRATEGY_NAMES = {1: "direct", 2: "rowtile", 3: "tileblock", 4: "tilering", 5: "qring"}
 STATUS_NAMES = {
     0: "TAHOE_OK",
@@ -126,6 +127,7 @@ _PROTOS = {
     "tahoe_forest_predict_interactions": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "tahoe_forest_set_background": (_i, [_vp, _vp, _sz, _vp]),
     "tahoe_forest_predict_contribs_interventional": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "tahoe_forest_predict_contribs_approx": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "tahoe_sparse_forest_create": (_i, [C.POINTER(_vp), _vp, _vp, C.POINTER(ForestParams)]),
     "tahoe_sparse_forest_create_ex": (_i, [C.POINTER(_vp), _vp, _vp, _vp, C.POINTER(ForestParams), _i, C.c_uint]),
     "tahoe_dense_to_sparse": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz)]),
@@ -380,19 +382,21 @@ class Forest:
 
     def __init__(self, nodes: np.ndarray, num_trees: int, depth: int, num_cols: int, missing: float = 0.0,
                  output: int = OUT_RAW, threshold: float = 0.0, global_bias: float = 0.0, algo: int = 0,
-                 strategy: int = 0, relayout: bool = False, num_classes: int = 1, contribs: bool = False):
+                 strategy: int = 0, relayout: bool = False, num_classes: int = 1, contribs: bool = False,
+                 approx_contribs: bool = False):
         nodes = np.ascontiguousarray(nodes, dtype=NODE_DTYPE)
         if nodes.size != num_trees * tree_num_nodes(depth):
             raise ValueError("nodes.size != num_trees * tree_num_nodes(depth)")
         self.params = ForestParams(0, depth, num_trees, num_cols, algo, output, threshold, global_bias, strategy,
                                    missing)
         self._h = _vp()
-        flags = (CREATE_PROB_RELAYOUT if relayout else 0) | (CREATE_CONTRIBS if contribs else 0)
+        flags = ((CREATE_PROB_RELAYOUT if relayout else 0) | (CREATE_CONTRIBS if contribs else 0)
+                 | (CREATE_APPROX_CONTRIBS if approx_contribs else 0))
         if num_classes != 1:
             _check(lib.tahoe_forest_create_multiclass(C.byref(self._h), nodes.ctypes.data if nodes.size else None,
                                                       C.byref(self.params), num_classes, flags),
                    "tahoe_forest_create_multiclass")
-        elif flags:  # re-layout by dense_node_t.weight (Struct.h:1775-1825) and / or the contribution tables
+        elif flags:  # re-layout by dense_node_t.weight (Struct.h:1775-1825) and / or the contribution tables / node deltas
             _check(lib.tahoe_forest_create_ex(C.byref(self._h), nodes.ctypes.data if nodes.size else None,
                                               C.byref(self.params), flags), "tahoe_forest_create_ex")
         else:
@@ -488,6 +492,21 @@ class Forest:
         assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == shape
         _check(lib.tahoe_forest_predict_interactions(self._h, _ptr(out), _ptr(data), rows, _stream(stream)),
                "tahoe_forest_predict_interactions")
+        return out
+
+    def predict_contribs_approx(self, data, out=None, stream=None):
+        """Saabas contributions (XGBoost approx_contribs, tahoe_forest_predict_contribs_approx): [rows, num_cols + 1] float32, or
+        [rows, num_classes, num_cols + 1] on a multi-class handle; the bias is the last column.  Needs approx_contribs=True."""
+        import torch
+
+        self._check_data(data)
+        rows = data.shape[0]
+        shape = (rows, self.num_classes, self.num_cols + 1) if self.num_classes > 1 else (rows, self.num_cols + 1)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=data.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == shape
+        _check(lib.tahoe_forest_predict_contribs_approx(self._h, _ptr(out), _ptr(data), rows, _stream(stream)),
+               "tahoe_forest_predict_contribs_approx")
         return out
 
     def set_background(self, bg, stream=None) -> None:
@@ -614,25 +633,27 @@ def synth_sparse_forest(num_trees: int, num_cols: int, min_depth: int = 4, max_d
 
 class SparseForest(Forest):
     """tahoe_sparse_forest_create: nodes[SPARSE_NODE_DTYPE] + root offsets; predict* as Forest.  covers (float32, one per
-    node), num_classes and contribs go through tahoe_sparse_forest_create_ex: tree t belongs to class t % num_classes, and
-    contribs=True builds the TreeSHAP path tables from the covers."""
+    node), num_classes, contribs and approx_contribs go through tahoe_sparse_forest_create_ex: tree t belongs to class
+    t % num_classes, contribs=True builds the TreeSHAP path tables from the covers and approx_contribs=True the Saabas node
+    deltas."""
 
     def __init__(self, nodes: np.ndarray, trees: np.ndarray, num_cols: int, missing: float = 0.0, output: int = OUT_RAW,
                  threshold: float = 0.0, global_bias: float = 0.0, covers=None, num_classes: int = 1,
-                 contribs: bool = False):
+                 contribs: bool = False, approx_contribs: bool = False):
         nodes = np.ascontiguousarray(nodes, dtype=SPARSE_NODE_DTYPE)
         trees = np.ascontiguousarray(trees, dtype=np.int32)
         self.params = ForestParams(int(nodes.size), 0, int(trees.size), num_cols, 0, output, threshold, global_bias, 0,
                                    missing)
         self._h = _vp()
-        if covers is not None or num_classes != 1 or contribs:
+        flags = (CREATE_CONTRIBS if contribs else 0) | (CREATE_APPROX_CONTRIBS if approx_contribs else 0)
+        if covers is not None or num_classes != 1 or flags:
             cv = None if covers is None else np.ascontiguousarray(covers, dtype=np.float32)
             if cv is not None and cv.size != nodes.size:
                 raise ValueError("covers.size != nodes.size")
             _check(lib.tahoe_sparse_forest_create_ex(C.byref(self._h), trees.ctypes.data if trees.size else None,
                                                      nodes.ctypes.data if nodes.size else None,
                                                      cv.ctypes.data if cv is not None else None,
-                                                     C.byref(self.params), num_classes, CREATE_CONTRIBS if contribs else 0),
+                                                     C.byref(self.params), num_classes, flags),
                    "tahoe_sparse_forest_create_ex")
         else:
             _check(lib.tahoe_sparse_forest_create(C.byref(self._h), trees.ctypes.data if trees.size else None,

@@ -395,7 +395,7 @@ struct TreePaths {
     std::vector<uint4> elems;       // paths one after the other, root element first, rank / length / round not yet set
     std::vector<float> om;          // 1 - zero fraction of each element
     std::vector<unsigned char> len;  // elements per path
-    double expect = 0.0;             // E_t = sum over leaves of leaf x product of cover ratios
+    double expect = 0.0;             // E_t (tree_expect)
 };
 
 struct Elem {
@@ -422,6 +422,32 @@ struct SparseTree {
     size_t left(size_t i) const { return (size_t)n[i].left_idx; }
     double cover(size_t i) const { return covers[i]; }
 };
+
+// E_t: the sum over reachable leaves, pre-order (left before right), of leaf x the product of the cover ratios of its edges,
+// multiplied root first (float64).  The bias column of every TreeSHAP form and of the Saabas form (approx.hip).
+template <typename Tree>
+double tree_expect(const Tree &tree)
+{
+    struct Frame {
+        size_t node;
+        double prod;
+    };
+    std::vector<Frame> stack{{0, 1.0}};
+    double expect = 0.0;
+    while (!stack.empty()) {
+        const Frame fr = stack.back();
+        stack.pop_back();
+        if ((tree.bits(fr.node) >> 31) & 1) {
+            expect += (double)tree.val(fr.node) * fr.prod;
+            continue;
+        }
+        const size_t l = tree.left(fr.node);
+        const double wl = tree.cover(l), wr = tree.cover(l + 1);
+        stack.push_back({l + 1, fr.prod * (wr / (wl + wr))});
+        stack.push_back({l, fr.prod * (wl / (wl + wr))});
+    }
+    return expect;
+}
 
 template <typename Tree>
 void tree_paths(const Tree &tree, TreePaths &out)
@@ -454,7 +480,6 @@ void tree_paths(const Tree &tree, TreePaths &out)
         }
         // repeated features are merged into their first element: at most 31 distinct ones (checked at create)
         el.clear();
-        double prod = 1.0;
         for (int k = 0; k < fr.depth; ++k) {
             const size_t a = edges[k].node;
             const int fid = tree.bits(a) & 0x3fffffff;
@@ -462,7 +487,6 @@ void tree_paths(const Tree &tree, TreePaths &out)
             const float thr = tree.val(a);
             const double wl = tree.cover(tree.left(a)), wr = tree.cover(tree.left(a) + 1);
             const double rho = (edges[k].right ? wr : wl) / (wl + wr);
-            prod *= rho;
             size_t j = 0;
             while (j < el.size() && el[j].fid != fid) ++j;
             if (j == el.size()) el.push_back({fid, -INFINITY, NAN, true, true, 1.0});
@@ -479,7 +503,6 @@ void tree_paths(const Tree &tree, TreePaths &out)
         }
         const float leaf = tree.val(fr.node);
         const int ne = (int)el.size();
-        out.expect += (double)leaf * prod;
         if (ne == 0) continue;  // a root leaf: all of it is bias
         uint4 root;
         memcpy(&root.x, &leaf, 4);
@@ -508,6 +531,44 @@ void tree_paths(const Tree &tree, TreePaths &out)
 
 }  // namespace
 
+// The bias column of every class from E_t of the caller's trees: sum_t E_t over class c's trees c, c + C, ... in order, / Tc with
+// TAHOE_OUT_AVG, + global_bias, in float64, rounded once; div[c] = (float)Tc with AVG, else 1.0f.
+static void class_bias(const tahoe_forest *f, const std::vector<double> &expect, std::vector<float> &bias, std::vector<float> &div)
+{
+    const int C = f->num_classes;
+    const size_t Tc = (size_t)f->class_trees;
+    const bool avg = (f->p.output & TAHOE_OUT_AVG) != 0 && Tc > 0;
+    bias.assign((size_t)C, 0.0f);
+    div.assign((size_t)C, 1.0f);
+    for (int c = 0; c < C; ++c) {
+        double sum = 0.0;
+        for (size_t k = 0; k < Tc; ++k) sum += expect[k * (size_t)C + (size_t)c];
+        bias[(size_t)c] = (float)((avg ? sum / (double)Tc : sum) + (double)f->p.global_bias);
+        div[(size_t)c] = avg ? (float)Tc : 1.0f;
+    }
+}
+
+void contribs_bias(const tahoe_forest *f, const tahoe_dense_node *nodes, std::vector<float> &bias, std::vector<float> &div)
+{
+    const size_t T = (size_t)f->p.num_trees, per = (size_t)tahoe_tree_num_nodes(f->p.depth);
+    std::vector<double> expect(T);
+    parallel_for(T, 16, [&](size_t lo, size_t hi) {
+        for (size_t t = lo; t < hi; ++t) expect[t] = tree_expect(DenseTree{nodes + t * per});
+    });
+    class_bias(f, expect, bias, div);
+}
+
+void contribs_bias_sparse(const tahoe_forest *f, const int32_t *trees, const tahoe_sparse_node *nodes, const float *covers,
+                          std::vector<float> &bias, std::vector<float> &div)
+{
+    const size_t T = (size_t)f->p.num_trees;
+    std::vector<double> expect(T);
+    parallel_for(T, 16, [&](size_t lo, size_t hi) {
+        for (size_t t = lo; t < hi; ++t) expect[t] = tree_expect(SparseTree{nodes + trees[t], covers + trees[t]});
+    });
+    class_bias(f, expect, bias, div);
+}
+
 // The path tables from the paths of every tree (caller's tree numbering): packing, bias and LDS shapes.
 static tahoe_status build_tables(tahoe_forest *f, std::vector<TreePaths> &trees)
 {
@@ -528,7 +589,12 @@ static tahoe_status build_tables(tahoe_forest *f, std::vector<TreePaths> &trees)
     std::vector<float> h_om;
     std::vector<uint32_t> h_info;
     std::vector<int> h_class_bins(C + 1, 0);
-    std::vector<float> h_bias(C), h_div(C);
+    std::vector<float> h_bias, h_div;
+    {
+        std::vector<double> expect(trees.size());
+        for (size_t t = 0; t < trees.size(); ++t) expect[t] = trees[t].expect;
+        class_bias(f, expect, h_bias, h_div);
+    }
     size_t n_paths = 0, n_elems = 0;
     uint4 pad;
     {
@@ -563,11 +629,9 @@ static tahoe_status build_tables(tahoe_forest *f, std::vector<TreePaths> &trees)
             fill = 0;
             steps = 0;
         };
-        double expect = 0.0;
         for (size_t k = 0; k < Tc; ++k) {
             const size_t t = k * (size_t)C + (size_t)c;
             TreePaths &tp = trees[t];
-            expect += tp.expect;
             size_t off = 0;
             for (unsigned char len : tp.len) {
                 if (fill + len > 64) flush();
@@ -587,9 +651,6 @@ static tahoe_status build_tables(tahoe_forest *f, std::vector<TreePaths> &trees)
             std::vector<float>().swap(tp.om);
         }
         flush();
-        const bool avg = (f->p.output & TAHOE_OUT_AVG) != 0 && Tc > 0;
-        h_bias[c] = (float)((avg ? expect / (double)Tc : expect) + (double)f->p.global_bias);
-        h_div[c] = avg ? (float)Tc : 1.0f;
     }
     h_class_bins[C] = (int)(h_elems.size() / 64);
 
@@ -638,13 +699,16 @@ tahoe_status contribs_build(tahoe_forest *f, const tahoe_dense_node *nodes)
     const size_t per = (size_t)tahoe_tree_num_nodes(f->p.depth);
     std::vector<TreePaths> trees(T);  // in the caller's tree numbering
     parallel_for(T, 4, [&](size_t lo, size_t hi) {
-        for (size_t t = lo; t < hi; ++t) tree_paths(DenseTree{nodes + t * per}, trees[t]);
+        for (size_t t = lo; t < hi; ++t) {
+            tree_paths(DenseTree{nodes + t * per}, trees[t]);
+            trees[t].expect = tree_expect(DenseTree{nodes + t * per});
+        }
     });
     return build_tables(f, trees);
 }
 
 tahoe_status contribs_validate_sparse(const int32_t *trees, const tahoe_sparse_node *nodes, const float *covers,
-                                      const tahoe_forest_params *p)
+                                      const tahoe_forest_params *p, bool path_limit)
 {
     // per reachable internal node, the covers of its two children; per reachable leaf, the distinct features of its path (the
     // element word's 5-bit rank and length fields, and interventional.hip's 32 x 32 weight table, hold at most 31)
@@ -670,7 +734,7 @@ tahoe_status contribs_validate_sparse(const int32_t *trees, const tahoe_sparse_n
             }
             const tahoe_sparse_node &n = tn[fr.node];
             if (n.bits & (int32_t)(1u << 31)) {
-                if (distinct > 31)
+                if (path_limit && distinct > 31)
                     return fail(TAHOE_ERR_UNSUPPORTED,
                                 "tree %d: a leaf's path has %d distinct features (TAHOE_CREATE_CONTRIBS supports at most 31)", t,
                                 distinct);
@@ -698,7 +762,10 @@ tahoe_status contribs_build_sparse(tahoe_forest *f, const int32_t *tree_roots, c
     const size_t T = (size_t)f->p.num_trees;
     std::vector<TreePaths> trees(T);  // in the caller's tree numbering
     parallel_for(T, 4, [&](size_t lo, size_t hi) {
-        for (size_t t = lo; t < hi; ++t) tree_paths(SparseTree{nodes + tree_roots[t], covers + tree_roots[t]}, trees[t]);
+        for (size_t t = lo; t < hi; ++t) {
+            tree_paths(SparseTree{nodes + tree_roots[t], covers + tree_roots[t]}, trees[t]);
+            trees[t].expect = tree_expect(SparseTree{nodes + tree_roots[t], covers + tree_roots[t]});
+        }
     });
     return build_tables(f, trees);
 }

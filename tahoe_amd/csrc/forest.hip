@@ -999,7 +999,7 @@ static tahoe_status create_dense(tahoe_forest **out, const tahoe_dense_node *nod
                                  int num_classes)
 {
     if (!out || !p) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_create: null argument");
-    if ((flags & ~(unsigned)(TAHOE_CREATE_PROB_RELAYOUT | TAHOE_CREATE_CONTRIBS)) != 0)
+    if ((flags & ~(unsigned)(TAHOE_CREATE_PROB_RELAYOUT | TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS)) != 0)
         return fail(TAHOE_ERR_INVALID_ARG, "unknown create flags 0x%x", flags);
     *out = nullptr;
     // check_params, BaseTahoeTest.h:490-516
@@ -1011,7 +1011,7 @@ static tahoe_status create_dense(tahoe_forest **out, const tahoe_dense_node *nod
     if ((p->output & ~(TAHOE_OUT_AVG | TAHOE_OUT_SIGMOID | TAHOE_OUT_THRESHOLD | (num_classes > 1 ? TAHOE_OUT_SOFTMAX : 0))) != 0)
         return fail(TAHOE_ERR_INVALID_ARG, "output should be a combination of RAW, AVG, SIGMOID and THRESHOLD");
     if (p->num_trees > 0 && !nodes) return fail(TAHOE_ERR_INVALID_ARG, "nodes is null");
-    if (flags & TAHOE_CREATE_CONTRIBS) {  // the cover weights, on the caller's nodes, before a device is touched
+    if (flags & (TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS)) {  // the cover weights, on the caller's nodes, before a device is touched
         const tahoe_status cs = contribs_validate(nodes, p);
         if (cs != TAHOE_OK) return cs;
     }
@@ -1279,6 +1279,13 @@ static tahoe_status create_dense(tahoe_forest **out, const tahoe_dense_node *nod
             return cs;
         }
     }
+    if (flags & TAHOE_CREATE_APPROX_CONTRIBS) {  // the Saabas records of the final (class-major, re-laid-out) layout
+        const tahoe_status as = approx_build(f, nodes, h_inner, h_real);
+        if (as != TAHOE_OK) {
+            tahoe_forest_destroy(f);
+            return as;
+        }
+    }
     *out = f;
     return TAHOE_OK;
 }
@@ -1323,6 +1330,7 @@ void tahoe_forest_destroy(tahoe_forest *f)
     widef_destroy(f);
     interventional_destroy(f);
     contribs_destroy(f);
+    approx_destroy(f);
     for (hipEvent_t e : f->ev_start) (void)hipEventDestroy(e);
     for (hipEvent_t e : f->ev_mid) (void)hipEventDestroy(e);
     for (hipEvent_t e : f->ev_stop) (void)hipEventDestroy(e);

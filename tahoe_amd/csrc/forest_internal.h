@@ -14,6 +14,7 @@ struct tahoe_pstate;  // host-batch upload pipeline, owned by pipeline.hip
 struct tahoe_wstate;  // float32 walk for wide rows, owned by widef.hip
 struct tahoe_cstate;  // TreeSHAP path tables (TAHOE_CREATE_CONTRIBS), owned by contribs.hip
 struct tahoe_istate;  // background of interventional TreeSHAP (tahoe_forest_set_background), owned by interventional.hip
+struct tahoe_astate;  // Saabas node deltas (TAHOE_CREATE_APPROX_CONTRIBS), owned by approx.hip
 
 namespace tahoe {
 
@@ -74,6 +75,7 @@ struct tahoe_forest {
     tahoe_wstate *wf = nullptr;    // non-null: TILERING runs the wide-row float32 form (widef.hip)
     tahoe_cstate *cs = nullptr;    // non-null: created with TAHOE_CREATE_CONTRIBS (contribs.hip)
     tahoe_istate *iv = nullptr;    // non-null: a background is set (interventional.hip)
+    tahoe_astate *ap = nullptr;    // non-null: created with TAHOE_CREATE_APPROX_CONTRIBS (approx.hip)
     size_t device_bytes = 0;
     // Multi-class handle (tahoe_forest_create_multiclass): the trees are stored class-major -- internal tree p belongs to class
     // p / class_trees and is original tree (p % class_trees) * num_classes + p / class_trees -- and every consumer writes
@@ -197,6 +199,7 @@ tahoe_status sparse_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, con
 int sparse_top_waves(const tahoe_forest *f);
 bool sparse_q_available(const tahoe_forest *f);  // the walk on quantised codes (strategy QRING on a sparse handle)
 void sparse_destroy(tahoe_forest *f);
+void sparse_device_views(const tahoe_forest *f, const tahoe_sparse_node **nodes, const int32_t **trees);  // the stored nodes and roots
 void pipeline_destroy(tahoe_forest *f);
 // TILERING for rows too wide for a 64-row float32 tile (widef.hip)
 tahoe_status widef_build(tahoe_forest *f, const std::vector<InnerNode> &h_inner, const std::vector<unsigned char> &h_real,
@@ -215,13 +218,24 @@ tahoe_status widef_reserve(tahoe_forest *f, size_t rows);
 // contribs_build builds the path tables of a validated forest from the caller's nodes (not the re-laid-out ones).
 tahoe_status contribs_validate(const tahoe_dense_node *nodes, const tahoe_forest_params *p);
 tahoe_status contribs_build(tahoe_forest *f, const tahoe_dense_node *nodes);
-// ... the same for a sparse forest whose structure check has passed: covers[i] is the cover of nodes[i]; the validation also
-// refuses (TAHOE_ERR_UNSUPPORTED) a leaf whose path has more than 31 distinct features
+// ... the same for a sparse forest whose structure check has passed: covers[i] is the cover of nodes[i]; with path_limit the
+// validation also refuses (TAHOE_ERR_UNSUPPORTED) a leaf whose path has more than 31 distinct features
 tahoe_status contribs_validate_sparse(const int32_t *trees, const tahoe_sparse_node *nodes, const float *covers,
-                                      const tahoe_forest_params *p);
+                                      const tahoe_forest_params *p, bool path_limit);
+// The bias column of tahoe_forest_predict_contribs (bias[c], float64 on the host, rounded once) and the AVG divisor (div[c]) of
+// every class, from the caller's validated trees; f->p, num_classes and class_trees must be set
+void contribs_bias(const tahoe_forest *f, const tahoe_dense_node *nodes, std::vector<float> &bias, std::vector<float> &div);
+void contribs_bias_sparse(const tahoe_forest *f, const int32_t *trees, const tahoe_sparse_node *nodes, const float *covers,
+                          std::vector<float> &bias, std::vector<float> &div);
 tahoe_status contribs_build_sparse(tahoe_forest *f, const int32_t *trees, const tahoe_sparse_node *nodes, const float *covers);
 void contribs_destroy(tahoe_forest *f);
 // interventional TreeSHAP (interventional.hip): frees the background, if any
 void interventional_destroy(tahoe_forest *f);
+// Saabas contributions (approx.hip).  approx_build runs on a dense handle's final layout (h_inner / h_real after re-layout,
+// internal tree order) and the caller's validated nodes; approx_build_sparse on the caller's validated sparse trees.
+tahoe_status approx_build(tahoe_forest *f, const tahoe_dense_node *nodes, const std::vector<InnerNode> &h_inner,
+                          const std::vector<unsigned char> &h_real);
+tahoe_status approx_build_sparse(tahoe_forest *f, const int32_t *trees, const tahoe_sparse_node *nodes, const float *covers);
+void approx_destroy(tahoe_forest *f);
 
 }  // namespace tahoe

@@ -1034,6 +1034,12 @@ static tahoe_status sparse_q_build(tahoe_forest *f, const std::vector<uint2> &cn
     return TAHOE_OK;
 }
 
+void sparse_device_views(const tahoe_forest *f, const tahoe_sparse_node **nodes, const int32_t **trees)
+{
+    *nodes = f->sp->nodes;
+    *trees = f->sp->trees;
+}
+
 // num_classes > 1 / covers: tahoe_sparse_forest_create_ex, whose own checks have run.  A multi-class forest is stored
 // class-major (internal tree p = the caller's tree (p % Tc) C + p / Tc); every builder below then runs on that order unchanged.
 static tahoe_status create_sparse(tahoe_forest **out, const int32_t *trees, const tahoe_sparse_node *nodes, const float *covers,
@@ -1068,8 +1074,9 @@ static tahoe_status create_sparse(tahoe_forest **out, const int32_t *trees, cons
                             p->num_cols);
         }
     }
-    if (flags & TAHOE_CREATE_CONTRIBS) {  // the covers and the path lengths, on the caller's nodes, before a device is touched
-        const tahoe_status cs = contribs_validate_sparse(trees, nodes, covers, p);
+    if (flags & (TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS)) {
+        // the covers (and, for the path bins, the path lengths), on the caller's nodes, before a device is touched
+        const tahoe_status cs = contribs_validate_sparse(trees, nodes, covers, p, (flags & TAHOE_CREATE_CONTRIBS) != 0);
         if (cs != TAHOE_OK) return cs;
     }
     int ndev = 0;
@@ -1218,6 +1225,13 @@ static tahoe_status create_sparse(tahoe_forest **out, const int32_t *trees, cons
             return cs;
         }
     }
+    if (flags & TAHOE_CREATE_APPROX_CONTRIBS) {  // per-node child deltas in the stored (class-major) order
+        const tahoe_status as = approx_build_sparse(f, caller_trees, caller_nodes, covers);
+        if (as != TAHOE_OK) {
+            tahoe_forest_destroy(f);
+            return as;
+        }
+    }
     *out = f;
     return TAHOE_OK;
 }
@@ -1249,10 +1263,13 @@ tahoe_status tahoe_sparse_forest_create_ex(tahoe_forest **out, const int32_t *tr
         return fail(TAHOE_ERR_INVALID_ARG, "SOFTMAX and SIGMOID exclude each other");
     if ((p->output & TAHOE_OUT_THRESHOLD) != 0 && num_classes > 1)
         return fail(TAHOE_ERR_INVALID_ARG, "THRESHOLD needs num_classes == 1");
-    if ((flags & ~(unsigned)TAHOE_CREATE_CONTRIBS) != 0)
-        return fail(TAHOE_ERR_INVALID_ARG, "unknown create flags 0x%x (a sparse handle takes TAHOE_CREATE_CONTRIBS only)", flags);
+    if ((flags & ~(unsigned)(TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS)) != 0)
+        return fail(TAHOE_ERR_INVALID_ARG, "unknown create flags 0x%x (a sparse handle takes TAHOE_CREATE_CONTRIBS and "
+                                           "TAHOE_CREATE_APPROX_CONTRIBS only)", flags);
     if ((flags & TAHOE_CREATE_CONTRIBS) && !covers)
         return fail(TAHOE_ERR_INVALID_ARG, "TAHOE_CREATE_CONTRIBS needs covers (one per node)");
+    if ((flags & TAHOE_CREATE_APPROX_CONTRIBS) && !covers)
+        return fail(TAHOE_ERR_INVALID_ARG, "TAHOE_CREATE_APPROX_CONTRIBS needs covers (one per node)");
     return create_sparse(out, trees, nodes, covers, p, num_classes, flags);
 }
 
