@@ -463,51 +463,35 @@ class Forest:
                "tahoe_forest_predict_leaf_idx")
         return leaf, sums
 
-    def predict_contribs(self, data, out=None, stream=None):
-        """Per-feature contributions (path-dependent TreeSHAP, tahoe_forest_predict_contribs): [rows, num_cols + 1] float32,
-        or [rows, num_classes, num_cols + 1] on a multi-class handle; the bias is the last column.  Needs contribs=True."""
+    def _shap_out(self, name, data, k, out, stream):
+        """The SHAP predict_* methods: runs the C function `name` into `out` (allocated if None), float32 [rows, num_cols + 1
+        (k times)], or [rows, num_classes, ...] on a multi-class handle."""
         import torch
 
         self._check_data(data)
         rows = data.shape[0]
-        shape = (rows, self.num_classes, self.num_cols + 1) if self.num_classes > 1 else (rows, self.num_cols + 1)
+        shape = (rows,) + ((self.num_classes,) if self.num_classes > 1 else ()) + (self.num_cols + 1,) * k
         if out is None:
             out = torch.empty(shape, dtype=torch.float32, device=data.device)
         assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == shape
-        _check(lib.tahoe_forest_predict_contribs(self._h, _ptr(out), _ptr(data), rows, _stream(stream)),
-               "tahoe_forest_predict_contribs")
+        _check(getattr(lib, name)(self._h, _ptr(out), _ptr(data), rows, _stream(stream)), name)
         return out
+
+    def predict_contribs(self, data, out=None, stream=None):
+        """Per-feature contributions (path-dependent TreeSHAP, tahoe_forest_predict_contribs): [rows, num_cols + 1] float32,
+        or [rows, num_classes, num_cols + 1] on a multi-class handle; the bias is the last column.  Needs contribs=True."""
+        return self._shap_out("tahoe_forest_predict_contribs", data, 1, out, stream)
 
     def predict_interactions(self, data, out=None, stream=None):
         """SHAP interaction values (tahoe_forest_predict_interactions): [rows, num_cols + 1, num_cols + 1] float32, or
         [rows, num_classes, num_cols + 1, num_cols + 1] on a multi-class handle; index num_cols is the bias.  Needs
         contribs=True."""
-        import torch
-
-        self._check_data(data)
-        rows, F1 = data.shape[0], self.num_cols + 1
-        shape = (rows, self.num_classes, F1, F1) if self.num_classes > 1 else (rows, F1, F1)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=data.device)
-        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == shape
-        _check(lib.tahoe_forest_predict_interactions(self._h, _ptr(out), _ptr(data), rows, _stream(stream)),
-               "tahoe_forest_predict_interactions")
-        return out
+        return self._shap_out("tahoe_forest_predict_interactions", data, 2, out, stream)
 
     def predict_contribs_approx(self, data, out=None, stream=None):
         """Saabas contributions (XGBoost approx_contribs, tahoe_forest_predict_contribs_approx): [rows, num_cols + 1] float32, or
         [rows, num_classes, num_cols + 1] on a multi-class handle; the bias is the last column.  Needs approx_contribs=True."""
-        import torch
-
-        self._check_data(data)
-        rows = data.shape[0]
-        shape = (rows, self.num_classes, self.num_cols + 1) if self.num_classes > 1 else (rows, self.num_cols + 1)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=data.device)
-        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == shape
-        _check(lib.tahoe_forest_predict_contribs_approx(self._h, _ptr(out), _ptr(data), rows, _stream(stream)),
-               "tahoe_forest_predict_contribs_approx")
-        return out
+        return self._shap_out("tahoe_forest_predict_contribs_approx", data, 1, out, stream)
 
     def set_background(self, bg, stream=None) -> None:
         """Background data set of interventional TreeSHAP (tahoe_forest_set_background): float32 [B, num_cols], contiguous, on
@@ -522,17 +506,7 @@ class Forest:
         """Interventional TreeSHAP against the background of set_background (tahoe_forest_predict_contribs_interventional):
         [rows, num_cols + 1] float32, or [rows, num_classes, num_cols + 1] on a multi-class handle; the bias is the last
         column.  Needs contribs=True and a background."""
-        import torch
-
-        self._check_data(data)
-        rows = data.shape[0]
-        shape = (rows, self.num_classes, self.num_cols + 1) if self.num_classes > 1 else (rows, self.num_cols + 1)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=data.device)
-        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == shape
-        _check(lib.tahoe_forest_predict_contribs_interventional(self._h, _ptr(out), _ptr(data), rows, _stream(stream)),
-               "tahoe_forest_predict_contribs_interventional")
-        return out
+        return self._shap_out("tahoe_forest_predict_contribs_interventional", data, 1, out, stream)
 
     def set_strategy(self, strategy: int) -> None:
         _check(lib.tahoe_forest_set_strategy(self._h, strategy), "tahoe_forest_set_strategy")

@@ -127,15 +127,8 @@ static tahoe_status finish_build(tahoe_forest *f, tahoe_astate *ap, const std::v
     }
     ap->waves = ap->slab ? (int)std::max<size_t>(1, std::min<size_t>(4, kApproxSlabBudget / wave_bytes)) : 4;
     ap->lds_bytes = ap->slab ? ap->waves * wave_bytes : 0;
-    auto up = [f](auto **dst, const auto &v) -> hipError_t {
-        const size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(v[0]);
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(dst), bytes);
-        if (e != hipSuccess) return e;
-        f->device_bytes += bytes;
-        return v.empty() ? hipSuccess : hipMemcpy(*dst, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice);
-    };
     hipError_t e;
-    if ((e = up(&ap->bias, h_bias)) != hipSuccess || (e = up(&ap->div, h_div)) != hipSuccess)
+    if ((e = upload(&ap->bias, h_bias, &f->device_bytes)) != hipSuccess || (e = upload(&ap->div, h_div, &f->device_bytes)) != hipSuccess)
         return fail(TAHOE_ERR_HIP, "approx_build: upload failed: %s", hipGetErrorString(e));
     const void *k = f->sp ? reinterpret_cast<const void *>(&approx_kernel<true, true>)
                           : reinterpret_cast<const void *>(&approx_kernel<false, true>);
@@ -207,12 +200,7 @@ tahoe_status approx_build(tahoe_forest *f, const tahoe_dense_node *nodes, const 
     });
     std::vector<float> h_bias, h_div;
     contribs_bias(f, nodes, h_bias, h_div);
-    const size_t bytes = std::max<size_t>(recs.size(), 1) * sizeof(uint4);
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&ap->recs), bytes);
-    if (e == hipSuccess) {
-        f->device_bytes += bytes;
-        if (!recs.empty()) e = hipMemcpy(ap->recs, recs.data(), recs.size() * sizeof(uint4), hipMemcpyHostToDevice);
-    }
+    const hipError_t e = upload(&ap->recs, recs, &f->device_bytes);
     if (e != hipSuccess) return fail(TAHOE_ERR_HIP, "approx_build: upload failed: %s", hipGetErrorString(e));
     return finish_build(f, ap, h_bias, h_div);
 }
@@ -259,12 +247,7 @@ tahoe_status approx_build_sparse(tahoe_forest *f, const int32_t *trees, const ta
     }
     std::vector<float> h_bias, h_div;
     contribs_bias_sparse(f, trees, nodes, covers, h_bias, h_div);
-    const size_t bytes = std::max<size_t>(stored.size(), 1) * sizeof(float2);
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&ap->dd), bytes);
-    if (e == hipSuccess) {
-        f->device_bytes += bytes;
-        if (!stored.empty()) e = hipMemcpy(ap->dd, stored.data(), stored.size() * sizeof(float2), hipMemcpyHostToDevice);
-    }
+    const hipError_t e = upload(&ap->dd, stored, &f->device_bytes);
     if (e != hipSuccess) return fail(TAHOE_ERR_HIP, "approx_build_sparse: upload failed: %s", hipGetErrorString(e));
     return finish_build(f, ap, h_bias, h_div);
 }
@@ -294,10 +277,7 @@ extern "C" tahoe_status tahoe_forest_predict_contribs_approx(tahoe_forest *f, fl
                                            "TAHOE_CREATE_APPROX_CONTRIBS and has no node deltas");
     if (rows == 0) return TAHOE_OK;
     if (!phi_dev || !data_dev) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_contribs_approx: null argument");
-    const size_t F1 = (size_t)f->p.num_cols + 1, C = (size_t)f->num_classes, limit = SIZE_MAX / sizeof(float);
-    if (C > limit / F1 || rows > limit / (C * F1))
-        return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_contribs_approx: rows x classes x (num_cols + 1) floats overflow "
-                                           "size_t (rows %zu)", rows);
+    if (tahoe_status st = check_shap_out(f, rows, 1, "tahoe_forest_predict_contribs_approx")) return st;
     const tahoe_astate *ap = f->ap;
     DeviceGuard on_device(f->device);
     const size_t per_block = (size_t)ap->waves * 64;

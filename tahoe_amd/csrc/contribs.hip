@@ -17,12 +17,6 @@
 
 namespace tahoe {
 
-static inline uint32_t elem_word(int fid, int rank, int len, int round, bool missing_ok, bool nan_ok)
-{
-    return (uint32_t)fid | (uint32_t)rank << 15 | (uint32_t)(len - 1) << 20 | (uint32_t)round << 25 | (missing_ok ? 1u << 30 : 0u) |
-           (nan_ok ? 1u << 31 : 0u);
-}
-
 // 1 / k, correctly rounded (constant folding), for the uniform factors of the recursions
 __constant__ float c_inv[34] = {0.0f,        1.0f,        1.0f / 2.0f,  1.0f / 3.0f,  1.0f / 4.0f,  1.0f / 5.0f,  1.0f / 6.0f,
                                 1.0f / 7.0f,  1.0f / 8.0f,  1.0f / 9.0f,  1.0f / 10.0f, 1.0f / 11.0f, 1.0f / 12.0f, 1.0f / 13.0f,
@@ -30,14 +24,6 @@ __constant__ float c_inv[34] = {0.0f,        1.0f,        1.0f / 2.0f,  1.0f / 3
                                 1.0f / 21.0f, 1.0f / 22.0f, 1.0f / 23.0f, 1.0f / 24.0f, 1.0f / 25.0f, 1.0f / 26.0f, 1.0f / 27.0f,
                                 1.0f / 28.0f, 1.0f / 29.0f, 1.0f / 30.0f, 1.0f / 31.0f, 1.0f / 32.0f, 1.0f / 33.0f};
 
-__device__ __forceinline__ float lane_read(float v, int src_lane)
-{
-    return __int_as_float(__builtin_amdgcn_ds_bpermute(src_lane << 2, __float_as_int(v)));
-}
-__device__ __forceinline__ uint32_t lane_read_u(uint32_t v, int src_lane)
-{
-    return (uint32_t)__builtin_amdgcn_ds_bpermute(src_lane << 2, (int)v);
-}
 // value of lane - 1 (0 in lane 0): DPP wave_shr:1
 __device__ __forceinline__ float from_left_lane(float v)
 {
@@ -81,18 +67,14 @@ __device__ __forceinline__ void contribs_tile(float *__restrict__ phi, const flo
             const uint32_t info = bin_info[b];
             const int steps = (int)(info & 0xffu), rounds = (int)(info >> 8);
             const float lower = __uint_as_float(e.x), upper = __uint_as_float(e.y), z = __uint_as_float(e.z);
-            const int fid = (int)(e.w & kElemFidMask), rank = (int)((e.w >> 15) & 31u), ud = (int)((e.w >> 20) & 31u);
-            const int round = (int)((e.w >> 25) & 31u);
-            const bool missing_ok = (e.w >> 30) & 1u, nan_ok = (e.w >> 31) != 0;
+            const int fid = elem_fid(e.w), rank = elem_rank(e.w), ud = elem_ud(e.w), round = elem_round(e.w);
+            const bool missing_ok = elem_missing_ok(e.w), nan_ok = elem_nan_ok(e.w);
             const int gs = lane - rank;  // lane of the path's root element
             const float leaf = lane_read(lower, gs);
             const float zdiv = z / (float)(ud + 1);
             const float udp1 = (float)(ud + 1);
             for (int r = 0; r < nr; ++r) {
-                // one-fraction: does the row follow every edge of this feature on the path?  (go_right's rule)
-                const float x = tile[r * F + fid];
-                const bool is_missing = fabsf(x - missing) <= kMissingEps;
-                const bool o = is_missing ? missing_ok : (x != x ? nan_ok : (x >= lower && !(x >= upper)));
+                const bool o = follows(tile[r * F + fid], lower, upper, missing_ok, nan_ok, missing);
                 const uint32_t zo = e.z | (o ? 0x80000000u : 0u);
                 // extend: after step d, lanes of rank <= d hold the permutation weights of the first d + 1 elements
                 float pw = rank == 0 ? 1.0f : 0.0f;
@@ -194,18 +176,13 @@ __device__ __forceinline__ void interaction_bins(float *acc, size_t acc_row, int
         const uint4 e = elems[(size_t)b * 64 + lane];
         const float om = one_minus_z[(size_t)b * 64 + lane];
         const float lower = __uint_as_float(e.x), upper = __uint_as_float(e.y), z = __uint_as_float(e.z);
-        const int fid = (int)(e.w & kElemFidMask), rank = (int)((e.w >> 15) & 31u), ud = (int)((e.w >> 20) & 31u);
-        const bool missing_ok = (e.w >> 30) & 1u, nan_ok = (e.w >> 31) != 0;
+        const int fid = elem_fid(e.w), rank = elem_rank(e.w), ud = elem_ud(e.w);
+        const bool missing_ok = elem_missing_ok(e.w), nan_ok = elem_nan_ok(e.w);
         const int gs = lane - rank;  // lane of the path's root element
         const float leaf = lane_read(lower, gs);
-        // one-fractions of this lane's element, bit r for row r (go_right's rule, as in contribs_tile)
+        // one-fractions of this lane's element, bit r for row r
         uint32_t omask = 0;
-        for (int r = 0; r < nr; ++r) {
-            const float x = tile[r * F + fid];
-            const bool is_missing = fabsf(x - missing) <= kMissingEps;
-            const bool o = is_missing ? missing_ok : (x != x ? nan_ok : (x >= lower && !(x >= upper)));
-            omask |= (o ? 1u : 0u) << r;
-        }
+        for (int r = 0; r < nr; ++r) omask |= (follows(tile[r * F + fid], lower, upper, missing_ok, nan_ok, missing) ? 1u : 0u) << r;
         // on the path without element k, element j (rank > k) has unique depth ud - 1
         const int udk = ud - 1;
         const float zdiv = z / (float)max(ud, 1);
@@ -615,13 +592,13 @@ static tahoe_status build_tables(tahoe_forest *f, std::vector<TreePaths> &trees)
             int rounds = 0;
             for (int l = 0; l < 64; ++l) {
                 uint4 &u = h_elems[start + l];
-                if (((u.w >> 15) & 31u) == 0) continue;
+                if (elem_rank(u.w) == 0) continue;
                 int round = 0;
                 for (int k = 0; k < l; ++k) {
                     const uint4 &v = h_elems[start + k];
-                    if (((v.w >> 15) & 31u) != 0 && (v.w & kElemFidMask) == (u.w & kElemFidMask)) ++round;
+                    if (elem_rank(v.w) != 0 && elem_fid(v.w) == elem_fid(u.w)) ++round;
                 }
-                u.w |= (uint32_t)round << 25;
+                u.w |= (uint32_t)round << kElemRoundShift;
                 rounds = std::max(rounds, round + 1);
             }
             h_info.push_back((uint32_t)steps | (uint32_t)rounds << 8);
@@ -637,7 +614,7 @@ static tahoe_status build_tables(tahoe_forest *f, std::vector<TreePaths> &trees)
                 if (fill + len > 64) flush();
                 for (int j = 0; j < len; ++j) {
                     uint4 u = tp.elems[off + j];
-                    u.w = (u.w & ~(0x3ffu << 15)) | (uint32_t)j << 15 | (uint32_t)(len - 1) << 20;
+                    u.w = (u.w & ~kElemRankLenMask) | (uint32_t)j << kElemRankShift | (uint32_t)(len - 1) << kElemLenShift;
                     h_elems.push_back(u);
                     h_om.push_back(tp.om[off + j]);
                 }
@@ -671,18 +648,11 @@ static tahoe_status build_tables(tahoe_forest *f, std::vector<TreePaths> &trees)
         for (RI = kInterMaxRows; RI > 1 && RI * inter_row > (size_t)kInterSlabMaxBytes;) RI /= 2;
     cs->inter_rows = (int)RI;
     cs->inter_lds_bytes = cs->inter_slabs ? RI * inter_row : kContribWaves * (size_t)F * sizeof(float);
-    auto up = [f](auto **dst, const auto &v) -> hipError_t {
-        const size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(v[0]);
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(dst), bytes);
-        if (e != hipSuccess) return e;
-        f->device_bytes += bytes;
-        return v.empty() ? hipSuccess : hipMemcpy(*dst, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice);
-    };
+    size_t *total = &f->device_bytes;
     hipError_t e;
-    if ((e = up(&cs->elems, h_elems)) != hipSuccess || (e = up(&cs->one_minus_z, h_om)) != hipSuccess ||
-        (e = up(&cs->bin_info, h_info)) != hipSuccess ||
-        (e = up(&cs->class_bins, h_class_bins)) != hipSuccess || (e = up(&cs->bias, h_bias)) != hipSuccess ||
-        (e = up(&cs->class_div, h_div)) != hipSuccess)
+    if ((e = upload(&cs->elems, h_elems, total)) != hipSuccess || (e = upload(&cs->one_minus_z, h_om, total)) != hipSuccess ||
+        (e = upload(&cs->bin_info, h_info, total)) != hipSuccess || (e = upload(&cs->class_bins, h_class_bins, total)) != hipSuccess ||
+        (e = upload(&cs->bias, h_bias, total)) != hipSuccess || (e = upload(&cs->class_div, h_div, total)) != hipSuccess)
         return fail(TAHOE_ERR_HIP, "contribs_build: upload failed: %s", hipGetErrorString(e));
     if ((e = allow_max_lds(reinterpret_cast<const void *>(&contribs_kernel), f->lds_limit)) != hipSuccess)
         return fail(TAHOE_ERR_HIP, "hipFuncSetAttribute(contribs) failed: %s", hipGetErrorString(e));
@@ -792,14 +762,10 @@ extern "C" tahoe_status tahoe_forest_predict_contribs(tahoe_forest *f, float *ph
                                                       void *stream)
 {
     if (!f) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_contribs: null forest");
-    if (f->sp && !f->cs)
-        return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_contribs: a sparse handle created without TAHOE_CREATE_CONTRIBS "
-                                           "has no node covers and no path tables (tahoe_sparse_forest_create_ex)");
-    if (!f->cs)
-        return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_contribs: the handle was created without TAHOE_CREATE_CONTRIBS "
-                                           "and has no path tables");
+    if (tahoe_status st = need_path_tables(f, "tahoe_forest_predict_contribs")) return st;
     if (rows == 0) return TAHOE_OK;
     if (!phi_dev || !data_dev) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_contribs: null argument");
+    if (tahoe_status st = check_shap_out(f, rows, 1, "tahoe_forest_predict_contribs")) return st;
     const tahoe_cstate *cs = f->cs;
     DeviceGuard on_device(f->device);
     const size_t R = (size_t)cs->rows_per_tile;
@@ -816,19 +782,11 @@ extern "C" tahoe_status tahoe_forest_predict_interactions(tahoe_forest *f, float
                                                           void *stream)
 {
     if (!f) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_interactions: null forest");
-    if (f->sp && !f->cs)
-        return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_interactions: a sparse handle created without "
-                                           "TAHOE_CREATE_CONTRIBS has no node covers and no path tables (tahoe_sparse_forest_create_ex)");
-    if (!f->cs)
-        return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_interactions: the handle was created without "
-                                           "TAHOE_CREATE_CONTRIBS and has no path tables");
+    if (tahoe_status st = need_path_tables(f, "tahoe_forest_predict_interactions")) return st;
     if (rows == 0) return TAHOE_OK;
     if (!out_dev || !data_dev) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_interactions: null argument");
+    if (tahoe_status st = check_shap_out(f, rows, 2, "tahoe_forest_predict_interactions")) return st;
     const int F = f->p.num_cols, C = f->num_classes;
-    const size_t F1 = (size_t)F + 1, limit = SIZE_MAX / sizeof(float);
-    if (F1 > limit / F1 || (size_t)C > limit / (F1 * F1) || rows > limit / ((size_t)C * F1 * F1))
-        return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_interactions: rows x classes x (num_cols + 1)^2 floats overflow "
-                                           "size_t (rows %zu)", rows);
     const tahoe_cstate *cs = f->cs;
     DeviceGuard on_device(f->device);
     hipStream_t s = (hipStream_t)stream;

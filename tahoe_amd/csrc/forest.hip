@@ -969,17 +969,6 @@ static int reference_bits_bytes(int max_fid)
     return len == 0 ? 1 : (len == 1 ? 2 : 4);
 }
 
-template <typename T>
-static hipError_t upload(T **dst, const std::vector<T> &src, size_t *total)
-{
-    const size_t bytes = std::max<size_t>(src.size(), 1) * sizeof(T);
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(dst), bytes);
-    if (e != hipSuccess) return e;
-    *total += bytes;
-    if (!src.empty()) e = hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice);
-    return e;
-}
-
 }  // namespace tahoe
 
 using namespace tahoe;

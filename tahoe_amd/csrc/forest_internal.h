@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <vector>
 
@@ -151,6 +152,18 @@ struct DeviceGuard {
     DeviceGuard &operator=(const DeviceGuard &) = delete;
 };
 
+// hipMalloc max(n, 1) elements for the n of src, counted in *total (the handle's device_bytes), and copy src there
+template <typename T>
+inline hipError_t upload(T **dst, const std::vector<T> &src, size_t *total)
+{
+    const size_t bytes = std::max<size_t>(src.size(), 1) * sizeof(T);
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(dst), bytes);
+    if (e != hipSuccess) return e;
+    *total += bytes;
+    if (!src.empty()) e = hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice);
+    return e;
+}
+
 // The branch rule of infer_one_tree, BaseTahoeTest.h:450-453: 1 = right child.
 __device__ __forceinline__ uint32_t go_right(float x, float thr, bool def_left, float missing)
 {
@@ -229,6 +242,30 @@ void contribs_bias_sparse(const tahoe_forest *f, const int32_t *trees, const tah
                           std::vector<float> &bias, std::vector<float> &div);
 tahoe_status contribs_build_sparse(tahoe_forest *f, const int32_t *trees, const tahoe_sparse_node *nodes, const float *covers);
 void contribs_destroy(tahoe_forest *f);
+// The first refusal of every TreeSHAP entry point (fn: its name): TAHOE_ERR_UNSUPPORTED unless the handle has path tables
+inline tahoe_status need_path_tables(const tahoe_forest *f, const char *fn)
+{
+    if (f->cs) return TAHOE_OK;
+    if (f->sp)
+        return fail(TAHOE_ERR_UNSUPPORTED, "%s: a sparse handle created without TAHOE_CREATE_CONTRIBS has no node covers and no path "
+                                           "tables (tahoe_sparse_forest_create_ex)", fn);
+    return fail(TAHOE_ERR_UNSUPPORTED, "%s: the handle was created without TAHOE_CREATE_CONTRIBS and has no path tables", fn);
+}
+// TAHOE_ERR_INVALID_ARG unless the output of a SHAP entry point, rows x classes x (num_cols + 1)^k floats, fits in size_t
+inline tahoe_status check_shap_out(const tahoe_forest *f, size_t rows, int k, const char *fn)
+{
+    const size_t F1 = (size_t)f->p.num_cols + 1, limit = SIZE_MAX / sizeof(float);
+    size_t per_row = (size_t)f->num_classes;
+    bool over = false;
+    for (int i = 0; i < k && !over; ++i) {
+        over = per_row > limit / F1;
+        per_row *= F1;
+    }
+    if (over || rows > limit / per_row)
+        return fail(TAHOE_ERR_INVALID_ARG, "%s: rows x classes x (num_cols + 1)%s floats overflow size_t (rows %zu)", fn,
+                    k == 2 ? "^2" : "", rows);
+    return TAHOE_OK;
+}
 // interventional TreeSHAP (interventional.hip): frees the background, if any
 void interventional_destroy(tahoe_forest *f);
 // Saabas contributions (approx.hip).  approx_build runs on a dense handle's final layout (h_inner / h_real after re-layout,

@@ -34,18 +34,6 @@ constexpr int kIvMaxTileRows = 8;               // rows of a workgroup's tile: s
 constexpr size_t kIvLdsBudget = 80 * 1024;      // two workgroups per CU where the tile allows it, as contribs_kernel
 constexpr int kIvUnroll = 8;                    // background rows whose mask and weight loads are issued together
 
-__device__ __forceinline__ float iv_lane_read(float v, int src_lane)
-{
-    return __int_as_float(__builtin_amdgcn_ds_bpermute(src_lane << 2, __float_as_int(v)));
-}
-
-// go_right's rule folded over every edge of the element's feature on its path (as contribs_tile computes o)
-__device__ __forceinline__ bool iv_follows(float x, float lower, float upper, bool missing_ok, bool nan_ok, float missing)
-{
-    const bool is_missing = fabsf(x - missing) <= kMissingEps;
-    return is_missing ? missing_ok : (x != x ? nan_ok : (x >= lower && !(x >= upper)));
-}
-
 // One wave per bin: masks[b][r] = ballot over the bin's lanes of "background row r follows this element" (rank-0 lanes: 0).
 __global__ __launch_bounds__(256) void background_mask_kernel(unsigned long long *__restrict__ masks, const float *__restrict__ bg,
                                                               size_t B, int F, size_t bins, const uint4 *__restrict__ elems,
@@ -56,11 +44,11 @@ __global__ __launch_bounds__(256) void background_mask_kernel(unsigned long long
     if (b >= bins) return;
     const uint4 e = elems[b * 64 + lane];
     const float lower = __uint_as_float(e.x), upper = __uint_as_float(e.y);
-    const int fid = (int)(e.w & kElemFidMask), rank = (int)((e.w >> 15) & 31u);
-    const bool missing_ok = (e.w >> 30) & 1u, nan_ok = (e.w >> 31) != 0;
+    const int fid = elem_fid(e.w), rank = elem_rank(e.w);
+    const bool missing_ok = elem_missing_ok(e.w), nan_ok = elem_nan_ok(e.w);
     unsigned long long *out = masks + b * B;
     for (size_t r = 0; r < B; ++r) {
-        const bool o = rank != 0 && iv_follows(bg[r * F + fid], lower, upper, missing_ok, nan_ok, missing);
+        const bool o = rank != 0 && follows(bg[r * F + fid], lower, upper, missing_ok, nan_ok, missing);
         const unsigned long long m = __ballot(o);
         if (lane == 0) out[r] = m;
     }
@@ -107,16 +95,15 @@ __global__ __launch_bounds__(256) void interventional_kernel(float *__restrict__
             const uint4 e = elems[(size_t)b * 64 + lane];
             const int rounds = (int)(bin_info[b] >> 8);
             const float lower = __uint_as_float(e.x), upper = __uint_as_float(e.y);
-            const int fid = (int)(e.w & kElemFidMask), rank = (int)((e.w >> 15) & 31u), ud = (int)((e.w >> 20) & 31u);
-            const int round = (int)((e.w >> 25) & 31u);
-            const bool missing_ok = (e.w >> 30) & 1u, nan_ok = (e.w >> 31) != 0;
+            const int fid = elem_fid(e.w), rank = elem_rank(e.w), ud = elem_ud(e.w), round = elem_round(e.w);
+            const bool missing_ok = elem_missing_ok(e.w), nan_ok = elem_nan_ok(e.w);
             const int gs = lane - rank;  // lane of the path's root element
-            const float leaf = iv_lane_read(lower, gs);
+            const float leaf = lane_read(lower, gs);
             // the lanes of this lane's path but its root: gs + 1 .. gs + ud (a path never leaves its bin)
             const unsigned long long pm = ud == 0 ? 0ull : ((1ull << ud) - 1ull) << (gs + 1);
             const unsigned long long *mb = masks + (size_t)b * B;
             for (int r = 0; r < nr; ++r) {
-                const bool o = rank != 0 && iv_follows(tile[r * F + fid], lower, upper, missing_ok, nan_ok, missing);
+                const bool o = rank != 0 && follows(tile[r * F + fid], lower, upper, missing_ok, nan_ok, missing);
                 const unsigned long long mx = __ballot(o);
                 const unsigned long long pa = pm & mx, pb = pm & ~mx;
                 const int nb = __popcll(pb);
@@ -143,7 +130,8 @@ __global__ __launch_bounds__(256) void interventional_kernel(float *__restrict__
                 }
                 for (; k < B; ++k) acc += weight(k);
                 const float term = (o ? acc : -acc) * leaf;
-                // two lanes of a bin on one feature add in lane order (round = earlier lanes of the bin on that feature)
+                // the round-ordered add and the epilogue below are contribs_tile's, written out again: as shared helpers
+                // they change both kernels' instruction streams
                 for (int k = 0; k < rounds; ++k)
                     if (rank != 0 && round == k) slab[r * F + fid] += term;
             }
@@ -211,12 +199,7 @@ using namespace tahoe;
 extern "C" tahoe_status tahoe_forest_set_background(tahoe_forest *f, const float *bg_dev, size_t bg_rows, void *stream)
 {
     if (!f) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_set_background: null forest");
-    if (f->sp && !f->cs)
-        return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_set_background: a sparse handle created without TAHOE_CREATE_CONTRIBS "
-                                           "has no path tables (tahoe_sparse_forest_create_ex)");
-    if (!f->cs)
-        return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_set_background: the handle was created without TAHOE_CREATE_CONTRIBS "
-                                           "and has no path tables");
+    if (tahoe_status st = need_path_tables(f, "tahoe_forest_set_background")) return st;
     if (bg_rows > 0 && !bg_dev) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_set_background: null background");
     const size_t F = (size_t)f->p.num_cols, C = (size_t)f->num_classes, bins = f->cs->bins;
     if (F > 0 && bg_rows > SIZE_MAX / sizeof(float) / F)
@@ -305,22 +288,14 @@ extern "C" tahoe_status tahoe_forest_predict_contribs_interventional(tahoe_fores
                                                                      size_t rows, void *stream)
 {
     if (!f) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_contribs_interventional: null forest");
-    if (f->sp && !f->cs)
-        return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_contribs_interventional: a sparse handle created without "
-                                           "TAHOE_CREATE_CONTRIBS has no path tables (tahoe_sparse_forest_create_ex)");
-    if (!f->cs)
-        return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_contribs_interventional: the handle was created without "
-                                           "TAHOE_CREATE_CONTRIBS and has no path tables");
+    if (tahoe_status st = need_path_tables(f, "tahoe_forest_predict_contribs_interventional")) return st;
     if (!f->iv)
         return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_contribs_interventional: no background set "
                                            "(tahoe_forest_set_background)");
     if (rows == 0) return TAHOE_OK;
     if (!phi_dev || !data_dev) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_contribs_interventional: null argument");
+    if (tahoe_status st = check_shap_out(f, rows, 1, "tahoe_forest_predict_contribs_interventional")) return st;
     const int F = f->p.num_cols, C = f->num_classes;
-    const size_t F1 = (size_t)F + 1, limit = SIZE_MAX / sizeof(float);
-    if ((size_t)C > limit / F1 || rows > limit / ((size_t)C * F1))
-        return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_contribs_interventional: rows x classes x (num_cols + 1) floats "
-                                           "overflow size_t (rows %zu)", rows);
     const IvShape sh = iv_shape(f);
     const size_t grid = (rows + (size_t)sh.rows - 1) / (size_t)sh.rows;
     if (grid > 0x7fffffffu)

@@ -932,9 +932,9 @@ static tahoe_status build_group(tahoe_forest *f, const std::vector<InnerNode> &h
     }
     hipError_t e;
     auto bad = [&](const char *what) { return fail(TAHOE_ERR_HIP, "qring_build: %s failed: %s", what, hipGetErrorString(e)); };
-    if ((e = q_upload(&g.top, h_top.data(), h_top.size(), &f->device_bytes)) != hipSuccess) return bad("top");
-    if ((e = q_upload(&g.blocks, h_blocks.data(), h_blocks.size(), &f->device_bytes)) != hipSuccess) return bad("blocks");
-    if (q->have_mid && (e = q_upload(&g.qinner, h_qinner.data(), h_qinner.size(), &f->device_bytes)) != hipSuccess)
+    if ((e = upload(&g.top, h_top, &f->device_bytes)) != hipSuccess) return bad("top");
+    if ((e = upload(&g.blocks, h_blocks, &f->device_bytes)) != hipSuccess) return bad("blocks");
+    if (q->have_mid && (e = upload(&g.qinner, h_qinner, &f->device_bytes)) != hipSuccess)
         return bad("qinner");
     return TAHOE_OK;
 }

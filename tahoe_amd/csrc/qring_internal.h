@@ -222,17 +222,6 @@ __device__ __forceinline__ void q_store_code(uint16_t *xq, size_t r, int f, int 
 
 constexpr int kQuantPairThreads = 1024;
 
-template <typename T>
-inline hipError_t q_upload(T **dst, const T *src, size_t count, size_t *total)
-{
-    const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(dst), bytes);
-    if (e != hipSuccess) return e;
-    *total += bytes;
-    if (count) e = hipMemcpy(*dst, src, count * sizeof(T), hipMemcpyHostToDevice);
-    return e;
-}
-
 // ---- device helpers of the walks on codes (qring.hip, sparse.hip) ----
 // The branch rule on codes: right <=> (missing ? !def_left : code(x) >= code(thr)).  Written on wave
 // masks: three v_cmp into SGPR pairs, three SALU ops, and the result is used directly as the lane

@@ -501,10 +501,10 @@ static tahoe_status build_buckets(tahoe_forest *f, const std::vector<std::vector
             std::copy(tab[c].begin(), tab[c].end(), bsorted.begin() + boffsets[c]);
             at += tab[c].size();
         }
-        if ((e = q_upload(&g.bsorted, bsorted.data(), bsorted.size(), &f->device_bytes)) != hipSuccess) return bad("bsorted");
-        if ((e = q_upload(&g.boffsets, boffsets.data(), boffsets.size(), &f->device_bytes)) != hipSuccess) return bad("boffsets");
-        if ((e = q_upload(&g.bstarts, starts.data(), starts.size(), &f->device_bytes)) != hipSuccess) return bad("bstarts");
-        if ((e = q_upload(&g.bparams, params.data(), params.size(), &f->device_bytes)) != hipSuccess) return bad("bparams");
+        if ((e = upload(&g.bsorted, bsorted, &f->device_bytes)) != hipSuccess) return bad("bsorted");
+        if ((e = upload(&g.boffsets, boffsets, &f->device_bytes)) != hipSuccess) return bad("boffsets");
+        if ((e = upload(&g.bstarts, starts, &f->device_bytes)) != hipSuccess) return bad("bstarts");
+        if ((e = upload(&g.bparams, params, &f->device_bytes)) != hipSuccess) return bad("bparams");
         g.buckets = B;
         g.bucket_lds_bytes = lds;
         break;
@@ -573,8 +573,8 @@ tahoe_status quantize_build_tables(tahoe_forest *f, const std::vector<std::vecto
     }
     hipError_t e;
     auto bad = [&](const char *what) { return fail(TAHOE_ERR_HIP, "qring_build: %s failed: %s", what, hipGetErrorString(e)); };
-    if ((e = q_upload(&g.tables, tables.data(), tables.size(), &f->device_bytes)) != hipSuccess) return bad("tables");
-    if ((e = q_upload(&g.offsets, offsets.data(), offsets.size(), &f->device_bytes)) != hipSuccess) return bad("offsets");
+    if ((e = upload(&g.tables, tables, &f->device_bytes)) != hipSuccess) return bad("tables");
+    if ((e = upload(&g.offsets, offsets, &f->device_bytes)) != hipSuccess) return bad("offsets");
     return TAHOE_OK;
 }
 

@@ -1017,11 +1017,11 @@ static tahoe_status sparse_q_build(tahoe_forest *f, const std::vector<uint2> &cn
     });
     hipError_t e;
     auto bad = [&](const char *what) { return fail(TAHOE_ERR_HIP, "sparse_q_build: %s failed: %s", what, hipGetErrorString(e)); };
-    if ((e = q_upload(&sp->qtop, h_top.data(), h_top.size(), &f->device_bytes)) != hipSuccess) return bad("qtop");
-    if ((e = q_upload(&sp->qbotpos, h_botpos.data(), h_botpos.size(), &f->device_bytes)) != hipSuccess) return bad("qbotpos");
-    if ((e = q_upload(&sp->qblocks, h_blocks.data(), h_blocks.size(), &f->device_bytes)) != hipSuccess) return bad("qblocks");
-    if ((e = q_upload(&sp->qblkpos, h_blkpos.data(), h_blkpos.size(), &f->device_bytes)) != hipSuccess) return bad("qblkpos");
-    if ((e = q_upload(&sp->qblkoff, h_blkoff.data(), h_blkoff.size(), &f->device_bytes)) != hipSuccess) return bad("qblkoff");
+    if ((e = upload(&sp->qtop, h_top, &f->device_bytes)) != hipSuccess) return bad("qtop");
+    if ((e = upload(&sp->qbotpos, h_botpos, &f->device_bytes)) != hipSuccess) return bad("qbotpos");
+    if ((e = upload(&sp->qblocks, h_blocks, &f->device_bytes)) != hipSuccess) return bad("qblocks");
+    if ((e = upload(&sp->qblkpos, h_blkpos, &f->device_bytes)) != hipSuccess) return bad("qblkpos");
+    if ((e = upload(&sp->qblkoff, h_blkoff, &f->device_bytes)) != hipSuccess) return bad("qblkoff");
     for (const void *k : {(const void *)&sparse_q_kernel<kReg3Walkers, false, 3, kReg3Ring>, (const void *)&sparse_q_kernel<kReg3Walkers, true, 3, kReg3Ring>,
                           (const void *)&sparse_q_kernel<15, false, 2, kQRing>, (const void *)&sparse_q_kernel<15, true, 2, kQRing>,
                           (const void *)&sparse_q_kernel<kReg3Walkers, false, 3, kReg3Ring, true>,

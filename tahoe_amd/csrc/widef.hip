@@ -350,15 +350,8 @@ tahoe_status widef_build(tahoe_forest *f, const std::vector<InnerNode> &h_inner,
     });
     hipError_t e;
     auto bad = [&](const char *what) { return fail(TAHOE_ERR_HIP, "widef_build: %s failed: %s", what, hipGetErrorString(e)); };
-    auto up = [&](auto **dst, const auto &src) {
-        const size_t bytes = std::max<size_t>(src.size(), 1) * sizeof(src[0]);
-        hipError_t er = hipMalloc(reinterpret_cast<void **>(dst), bytes);
-        if (er != hipSuccess) return er;
-        f->device_bytes += bytes;
-        return src.empty() ? hipSuccess : hipMemcpy(*dst, src.data(), src.size() * sizeof(src[0]), hipMemcpyHostToDevice);
-    };
-    if ((e = up(&w->ftop, h_top)) != hipSuccess) return bad("ftop");
-    if ((e = up(&w->fblocks, h_blocks)) != hipSuccess) return bad("fblocks");
+    if ((e = upload(&w->ftop, h_top, &f->device_bytes)) != hipSuccess) return bad("ftop");
+    if ((e = upload(&w->fblocks, h_blocks, &f->device_bytes)) != hipSuccess) return bad("fblocks");
     e = rt == 32 ? (nwalk == 15 ? wf_allow<32, 15>(f->lds_limit) : wf_allow<32, 12>(f->lds_limit))
         : rt == 16 ? (nwalk == 15 ? wf_allow<16, 15>(f->lds_limit) : wf_allow<16, 12>(f->lds_limit))
                    : (nwalk == 15 ? wf_allow<8, 15>(f->lds_limit) : wf_allow<8, 12>(f->lds_limit));

@@ -687,17 +687,10 @@ tahoe_status wkey_build(tahoe_forest *f, const std::vector<InnerNode> &h_inner, 
             }
         }
     });
-    auto up = [&](auto **dst, const auto &src) {
-        const size_t bytes = std::max<size_t>(src.size(), 1) * sizeof(src[0]);
-        hipError_t er = hipMalloc(reinterpret_cast<void **>(dst), bytes);
-        if (er != hipSuccess) return er;
-        f->device_bytes += bytes;
-        return src.empty() ? hipSuccess : hipMemcpy(*dst, src.data(), src.size() * sizeof(src[0]), hipMemcpyHostToDevice);
-    };
     uint32_t *d_img = nullptr;
-    if ((e = up(&d_img, h_img)) != hipSuccess) return bad("kimg");
+    if ((e = upload(&d_img, h_img, &f->device_bytes)) != hipSuccess) return bad("kimg");
     w->kimg = reinterpret_cast<unsigned char *>(d_img);
-    if ((e = up(&w->kblocks, h_kb)) != hipSuccess) return bad("kblocks");
+    if ((e = upload(&w->kblocks, h_kb, &f->device_bytes)) != hipSuccess) return bad("kblocks");
     w->s_lw = s_lw;
     w->s_ts = s_ts;
     w->s_slots = slots;

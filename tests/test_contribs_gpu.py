@@ -192,6 +192,22 @@ def test_refusals(env, k_forest):
     assert ta.lib.tahoe_forest_predict_contribs(f._h, None, None, 0, None) == 0
 
 
+@pytest.mark.parametrize("name,kw", [("tahoe_forest_predict_contribs", {"contribs": True}),
+                                     ("tahoe_forest_predict_contribs_approx", {"approx_contribs": True})])
+def test_huge_rows_overflow(env, k_forest, name, kw):
+    ta, torch = env
+    nodes, T, D, F, x, f, ref = k_forest
+    g = ta.Forest(nodes, T, D, F, missing=MISSING, **kw)
+    xd = torch.from_numpy(x).cuda()
+    out = torch.full((x.shape[0], F + 1), 7.0, device="cuda")
+    huge = (1 << 64) // (4 * (F + 1)) + 1  # rows x (F + 1) x 4 overflows size_t
+    assert getattr(ta.lib, name)(g._h, out.data_ptr(), xd.data_ptr(), huge, None) == 1
+    assert "overflow" in ta.lib.tahoe_last_error().decode()
+    torch.cuda.synchronize()
+    assert torch.all(out == 7.0).item()  # nothing was launched
+    g.close()
+
+
 def test_zero_rows(env, k_forest):
     ta, torch = env
     nodes, T, D, F, x, f, ref = k_forest
