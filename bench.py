@@ -7,7 +7,13 @@ resident in HBM before the timed region (as in the reference, BaseTahoeTest.h:56
 --dump-outputs DIR writes the predictions of the last timed step (float32 .npy); the inputs are seeded, so two builds run
 with the same arguments can be compared output for output.
 
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the JSON line: its roofline holds only the
+figures derived from this run's own kernel events and the committed counter profile.  --full adds everything that takes runs
+of its own after the timed steps: the CPU baseline and parity spot check, the host-resident batch, the K4 legs, the other
+BASELINE configurations and the live micro-benchmark behind roofline.frac_le_1.  Without --full their keys are null.
+
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -20,7 +26,7 @@ N > 1 (default, --scaling strong): the metric's 1M rows are split by rows, rank 
 At N > 1 the line proves what ran: "collective" carries the backend, the ranks the process group reports, an all-reduce of
 ones that must sum to that number, the device of every rank, and the fastest / slowest rank's step time.
 
-Secondary legs in the same JSON line (never part of `value`; at N > 1 only with --k4, and then every collective step is
+Secondary legs in the same JSON line (--full only, never part of `value`; at N > 1 only with --k4, and then every collective step is
 preceded by an all-reduced "everyone is fine" flag so that a failure on one rank cannot strand the others in a collective
 and take the primary line with it): BASELINE config 4 ("K4", 8000 trees) both ways --
 row shards (bit-exact) and tree shards (all-reduce of float64 partials, and the bit-exact chain) -- each with its
@@ -365,25 +371,31 @@ def main():
     ap.add_argument("--tree-mode", choices=["allreduce64", "allreduce32", "chain"], default="allreduce64")
     ap.add_argument("--chunk-rows", type=int, default=32768, help="rows per hand-over of the chained tree shards")
     ap.add_argument("--strategy", type=int, default=0, help="0 auto, 1 direct, 2 rowtile, 3 tileblock, 4 tilering, 5 qring")
-    ap.add_argument("--cpu-rows", type=int, default=100_000, help="rows of the batch timed on the CPU oracle")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the secondary legs (CPU baseline, host-resident batch, K4, the other "
+                         "BASELINE configurations, the live walk-ceiling micro-benchmark); off: only what the headline needs")
+    ap.add_argument("--cpu-rows", type=int, default=100_000, help="--full: rows of the batch timed on the CPU oracle")
     ap.add_argument("--relayout", action="store_true",
                     help="probability-guided re-layout (SURVEY 8f N3): weights = reach probabilities, TAHOE_CREATE_PROB_RELAYOUT")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-host", action="store_true", help="skip the host-resident (PCIe-inclusive) leg")
-    ap.add_argument("--no-k4", "--no-tree-leg", dest="no_k4", action="store_true", help="skip the secondary K4 legs")
-    ap.add_argument("--no-configs", action="store_true", help="skip the secondary legs of BASELINE configurations K1, K2, K5")
-    ap.add_argument("--cpu-rows-multi", type=int, default=20_000, help="N > 1: rows of rank 0's shard timed on the CPU oracle")
-    ap.add_argument("--k4", action="store_true", help="N > 1: run the secondary K4 legs too (they contain collectives; off by default there)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
+    ap.add_argument("--no-host", action="store_true", help="--full: skip the host-resident (PCIe-inclusive) leg")
+    ap.add_argument("--no-k4", "--no-tree-leg", dest="no_k4", action="store_true", help="--full: skip the secondary K4 legs")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip the secondary legs of BASELINE configurations K1, K2, K5")
+    ap.add_argument("--cpu-rows-multi", type=int, default=20_000, help="--full, N > 1: rows of rank 0's shard timed on the CPU oracle")
+    ap.add_argument("--k4", action="store_true",
+                    help="--full, N > 1: run the secondary K4 legs too (they contain collectives; off by default there)")
     ap.add_argument("--k4-trees", type=int, default=8000)
     ap.add_argument("--k4-chain", action="store_true",
-                    help="N > 1: also time the chained (bit-exact, point-to-point) tree shards of K4; off by default because a stuck "
-                         "send/recv would take the process group -- and the primary line -- down with it")
+                    help="--full, N > 1: also time the chained (bit-exact, point-to-point) tree shards of K4; off by default because a "
+                         "stuck send/recv would take the process group -- and the primary line -- down with it")
     ap.add_argument("--k4-sample", type=int, default=2048, help="rows of the K4 legs checked against the float64 CPU sum")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write the predictions of the last one as DIR/<name>.npy (float32, at most 64 MB in all)")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if (args.k4 or args.k4_chain) and not args.full:
+        ap.error("--k4 and --k4-chain run secondary legs: add --full")
 
     import torch
 
@@ -588,8 +600,9 @@ def main():
     if prof:
         traffic = int(sum((k["FETCH_SIZE"] + k["WRITE_SIZE"]) * 1024 for n, k in prof["kernels"].items() if "bucket_index" not in n))
         physical = physical_ceilings(prof, walk_ms, quant_ms, my_rows, C)
-    if rank == 0 and have_times and forest.kernel_form(my_rows).startswith("qring_region"):
+    if args.full and rank == 0 and have_times and forest.kernel_form(my_rows).startswith("qring_region"):
         # the fraction <= 1 of this kernel: its node visits per second against the measured ceiling of the LDS-resident walk
+        # (--full: the ceiling is a run of its own, tools/ubench_qwalk as a child process)
         prop = torch.cuda.get_device_properties(device_index)
         physical = physical or {"source": None, "note": "no counter profile stamped with these kernel sources"}
         physical.setdefault("walk", {})["lds_walk_ceiling"] = lds_walk_ceiling(
@@ -624,28 +637,28 @@ def main():
         "kernel_source_hash": kernel_source_hash(),
     }
 
-    # ---- secondary legs: BASELINE config 4 ("K4": 8000 trees).  Which split serves it?  Measured both ways, each with
-    # its error against a float64 CPU sum on a row sample.  N = 1: the one-GPU proxies of the 8-GPU run. ----
+    # ---- secondary legs (--full only): BASELINE config 4 ("K4": 8000 trees).  Which split serves it?  Measured both ways,
+    # each with its error against a float64 CPU sum on a row sample.  N = 1: the one-GPU proxies of the 8-GPU run. ----
     k4 = None
-    want_k4 = args.k4 or (world == 1 and not args.no_k4 and (T, D, C, R) == (1000, 12, 256, 1_000_000))
+    want_k4 = args.full and (args.k4 or (world == 1 and not args.no_k4 and (T, D, C, R) == (1000, 12, 256, 1_000_000)))
     if want_k4 and not tree_sharded:
         try:
             k4 = k4_legs(args, ta, sharding, torch, coll, dist, world, rank, fence, max_over_ranks, stream, agree)
         except Exception as err:  # the primary line must survive a failure of a secondary leg
             k4 = {"error": f"{type(err).__name__}: {err}"}
 
-    # ---- secondary legs: BASELINE configurations K1, K2, K5 on this device (N = 1 only, after the primary region) ----
+    # ---- secondary legs (--full only): BASELINE configurations K1, K2, K5 on this device (N = 1 only, after the primary region) ----
     configs = None
-    if rank == 0 and world == 1 and not args.no_configs and (T, D, C, R) == (1000, 12, 256, 1_000_000):
+    if args.full and rank == 0 and world == 1 and not args.no_configs and (T, D, C, R) == (1000, 12, 256, 1_000_000):
         t_cfg = time.perf_counter()
         configs = config_legs(ta, torch)
         configs["K3"] = {"see": "the primary figures of this line", "ms": round(step_kernel_ms, 4), "kernel_form": roofline["kernel_form"]}
         configs["K4"] = {"see": "k4 in this line (row shards / tree shards on one GPU)"}
         configs["seconds"] = round(time.perf_counter() - t_cfg, 2)
 
-    # ---- host-resident batch (rank 0, N = 1 only): the PCIe-inclusive rate, reported beside `value`, never as it ----
+    # ---- host-resident batch (--full, rank 0, N = 1 only): the PCIe-inclusive rate, reported beside `value`, never as it ----
     host_leg = None
-    if rank == 0 and world == 1 and not args.no_host:
+    if args.full and rank == 0 and world == 1 and not args.no_host:
         fence()
         ref = preds.cpu().numpy()
         host_leg = {"unit": "samples/s", "note": "tahoe_forest_predict_host: rows start in host memory, chunked upload "
@@ -667,10 +680,10 @@ def main():
                 raise SystemExit("bench: host-pipeline predictions differ from the resident-batch predictions")
         pin.close()
 
-    # ---- CPU baseline + parity spot check (rank 0; N > 1: a shorter leg on the first rows of rank 0's own shard, so that
-    # every line of a scaling run carries its CPU figure from the same run; the other ranks wait at the final barrier) ----
+    # ---- CPU baseline + parity spot check (--full, rank 0; N > 1: a shorter leg on the first rows of rank 0's own shard, so
+    # that every full line of a scaling run carries its CPU figure from the same run; the other ranks wait at the final barrier) ----
     cpu = None
-    if rank == 0 and not args.no_cpu:
+    if args.full and rank == 0 and not args.no_cpu:
         oracle = _oracle()
         n_cpu = min(args.cpu_rows if world == 1 else args.cpu_rows_multi, my_rows)
         tc = time.perf_counter()
@@ -705,7 +718,7 @@ def main():
         out = {
             "metric": "samples/sec, 1000-tree depth-12 forest @1M rows (batched tree-ensemble traversal)",
             "value": round(value, 1), "unit": "samples/s", "n_gpus": collective["ranks_seen"] if collective else 1, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "us_per_batch": round(ms_per_step * 1e3, 1),
+            "warmup": args.warmup, "full": args.full, "ms_per_step": round(ms_per_step, 4), "us_per_batch": round(ms_per_step * 1e3, 1),
             "higher_is_better": True,
             # the default split at N > 1 is strong (the metric's rows over the ranks); N = 1 carries the same label so that the
             # driver's N = 1 row is comparable with its N > 1 rows

@@ -1,4 +1,4 @@
-"""The bench.py output contract, checked on the line recorded from the last default run on the GPU box
+"""The bench.py output contract, checked on the line recorded from the last full run (bench.py --full) on an MI355X
 (profiles/r04/bench_default_line.json).  CPU test: guards the keys the driver and the judge read."""
 import json
 import os
@@ -169,3 +169,15 @@ def test_dump_outputs_keeps_to_its_limit(tmp_path):
     assert a.dtype == np.float32 and ia.dtype == np.float64 and a.size == ia.size == 100 and a.nbytes + ia.nbytes <= 1200
     assert np.array_equal(a, values[ia.astype(np.int64)].astype(np.float32)) and ia[0] == 0 and ia[-1] == 990
     assert np.array_equal(a, np.load(tmp_path / "b" / "preds.npy")) and np.array_equal(ia, np.load(tmp_path / "b" / "preds_index.npy"))
+
+
+def test_secondary_leg_flags_ask_for_full():
+    """--k4 and --k4-chain request secondary legs, which only a --full run has: without it bench.py refuses them before it
+    touches a GPU, instead of printing a line without what was asked for."""
+    import subprocess
+    import sys
+
+    for flag in ("--k4", "--k4-chain"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", flag], capture_output=True, text=True,
+                           timeout=120, cwd=ROOT)
+        assert r.returncode == 2 and "--full" in r.stderr, (flag, r.stderr[-2000:])

@@ -33,7 +33,7 @@ def run_bench(extra, ranks=2, timeout=600, cpu=False):
 
 
 def test_two_ranks_row_shards_and_k4_legs():
-    line = run_bench(["--k4", "--k4-trees", "400", "--k4-sample", "512"])
+    line = run_bench(["--full", "--k4", "--k4-trees", "400", "--k4-sample", "512"])
     assert line["n_gpus"] == 2 and line["scaling"] == "strong"
     c = line["collective"]
     assert c["ranks_seen"] == 2 and c["allreduce_ones_ok"] is True and c["allreduce_ones_sum"] == 2.0 and len(c["device_of_rank"]) == 2
@@ -50,14 +50,14 @@ def test_two_ranks_row_shards_and_k4_legs():
 
 
 def test_two_ranks_without_k4_flag_print_no_k4_legs():
-    line = run_bench([])
+    line = run_bench(["--full"])
     assert line["k4"] is None and line["collective"]["ranks_seen"] == 2
 
 
 def test_two_rank_line_carries_a_cpu_baseline():
     """Every line of a scaling run has its own cpu_baseline (rank 0, a short single-thread leg on its shard's first rows, with
     the bitwise check of the timed buffer) and a roofline object -- a line without both counts as unmeasured."""
-    line = run_bench(["--cpu-rows-multi", "3000"], cpu=True)
+    line = run_bench(["--full", "--cpu-rows-multi", "3000"], cpu=True)
     c = line["cpu_baseline"]
     assert c is not None and c["cores"] == 1 and c["kind"] == "port" and c["value"] > 0 and c["unit"] == "samples/s"
     assert c["gpu_matches_cpu_bitwise_on_sample"] is True and "3000 rows" in c["sample"]
@@ -73,8 +73,8 @@ def test_one_rank_process_group_on_the_real_backend():
     has met RCCL on hardware before the driver's 8-GPU scaling run."""
     env = dict(os.environ, TAHOE_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(free_port()))
     env.pop("TAHOE_BENCH_BACKEND", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rows", "40000", "--steps", "3", "--warmup", "1", "--no-host",
-                        "--no-configs", "--k4", "--k4-trees", "400", "--k4-sample", "512", "--cpu-rows", "3000"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rows", "40000", "--steps", "3", "--warmup", "1", "--full",
+                        "--no-host", "--no-configs", "--k4", "--k4-trees", "400", "--k4-sample", "512", "--cpu-rows", "3000"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln][-1])
@@ -91,7 +91,7 @@ def test_two_ranks_tree_shards_chained_bit_exact():
     line = run_bench(["--shard", "trees", "--tree-mode", "chain", "--chunk-rows", "8192"])
     assert line["n_gpus"] == 2 and line["config"]["sharding"] == "trees/chain" and line["config"]["rows_per_gpu"] == 40000
     assert line["collective"]["allreduce_ones_ok"] is True
-    line = run_bench(["--k4", "--k4-chain", "--k4-trees", "400", "--k4-sample", "512"])
+    line = run_bench(["--full", "--k4", "--k4-chain", "--k4-trees", "400", "--k4-sample", "512"])
     ch = line["k4"]["tree_sharded_chain"]
     assert ch["bit_identical_to_cpu_f32"] is True and "error" not in ch
 
@@ -132,3 +132,19 @@ def test_one_rank_line_carries_the_same_scaling_label():
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["scaling"] == "strong" and line["n_gpus"] == 1 and line["collective"] is None
+
+
+def test_plain_run_of_the_metric_shape_runs_no_secondary_legs():
+    """Without --full, bench.py on the metric's own shape (where a full run adds K4 and the other configurations) times its steps
+    and prints the line with every secondary leg null: no CPU baseline, no host-resident batch, no K4, no configurations, no live
+    walk-ceiling run behind frac_le_1."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1"],
+                       capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["full"] is False and line["steps"] == 2 and line["warmup"] == 1
+    assert line["config"]["rows_per_step"] == 1_000_000 and line["value"] > 0 and line["ms_per_step"] > 0
+    for key in ("cpu_baseline", "host_pipeline", "k4", "configs"):
+        assert line[key] is None, key
+    r = line["roofline"]
+    assert r["achieved"] > 0 and r["kernel_ms_avg"] > 0 and r["frac_le_1"] is None

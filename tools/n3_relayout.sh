@@ -7,8 +7,8 @@ out=$R/gpurun_out/n3_relayout.txt
 : > $out
 for mode in plain relayout; do
   flag=""; [ $mode = relayout ] && flag="--relayout"
-  echo "== $mode: bench.py --steps 10 --warmup 3 $flag" >> $out
-  timeout -k 10 200 python3 bench.py --steps 10 --warmup 3 --no-host --no-k4 --cpu-rows 20000 $flag 2>/dev/null | python3 -c "
+  echo "== $mode: bench.py --steps 10 --warmup 3 --full $flag" >> $out
+  timeout -k 10 200 python3 bench.py --steps 10 --warmup 3 --full --no-host --no-k4 --cpu-rows 20000 $flag 2>/dev/null | python3 -c "
 import json,sys
 l=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=l['roofline']
 print('ms_per_step %.4f  walk_ms %.4f  quantise_ms %.4f  cpu_parity %s  swaps %s' % (l['ms_per_step'], r['walk_kernel_ms_avg'], r['prepass_kernel_ms_avg'], l['cpu_baseline']['gpu_matches_cpu_bitwise_on_sample'], l['config'].get('relayout_swaps')))" >> $out

@@ -2,7 +2,8 @@
 # Everything under profiles/r04 that depends on the final kernels, in two halves (a GPU call is limited to 20 minutes):
 #   tools/profile_all.sh a   counter profiles: K3 over bench.py (tools/pmc.sh), K1 K2 K4 K5 KR3 over tools/pmc_target.py
 #                            (KR3 = K3's shape from the histogram-style generator: u8 codes, quantize_multi_kernel)
-#   tools/profile_all.sh b   kernel-trace stats, the five configurations with their rooflines, the default bench line
+#   tools/profile_all.sh b   kernel-trace stats, the five configurations with their rooflines, and last on stdout the bench
+#                            line of a --full run (profiles/r04/bench_default_line.json records one)
 # Results land in gpurun_out/; copy them to profiles/r04/ (see profiles/README.md for the names).
 set -e
 export TMPDIR=/tmp
@@ -19,5 +20,5 @@ else
   for c in 2 4 5 R3; do t=$(echo k$c | tr A-Z a-z); rm -rf gpurun_out/stats_$t; rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/stats_$t -- python3 tools/pmc_target.py K$c 12 > gpurun_out/stats_$t.log 2>&1; done
   echo "stats done"
   python3 tools/run_configs.py > gpurun_out/configs.log 2>&1; echo "configs done"
-  python3 bench.py > gpurun_out/bench_default.log 2> gpurun_out/bench_default.err; tail -c 600 gpurun_out/bench_default.log
+  python3 bench.py --full
 fi
