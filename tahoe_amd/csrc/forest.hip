@@ -800,14 +800,11 @@ static void launch_tileblock(tahoe_forest *f, float *sums, uint32_t *leaf_out, c
     const unsigned grid = (unsigned)((rows + ROWS - 1) / ROWS);
     const int lds = (int)tileblock_lds_bytes(f, ROWS);
     const int stride = top_stride_bytes(f->top_levels);
-    if (leaf_out)
-        hipLaunchKernelGGL((tileblock_kernel<ROWS, true>), dim3(grid), dim3(kSlots * ROWS), lds, stream, f->top,
+    with_leaf(leaf_out != nullptr, [&](auto wl) {
+        hipLaunchKernelGGL((tileblock_kernel<ROWS, decltype(wl)::value>), dim3(grid), dim3(kSlots * ROWS), lds, stream, f->top,
                            f->blocks, f->inner, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
                            f->p.num_trees, f->depth, f->top_levels, stride, f->p.missing, vec4_ok);
-    else
-        hipLaunchKernelGGL((tileblock_kernel<ROWS, false>), dim3(grid), dim3(kSlots * ROWS), lds, stream, f->top,
-                           f->blocks, f->inner, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
-                           f->p.num_trees, f->depth, f->top_levels, stride, f->p.missing, vec4_ok);
+    });
 }
 
 template <int ROWS, int NWALK>
@@ -817,14 +814,11 @@ static void launch_tilering(tahoe_forest *f, float *sums, uint32_t *leaf_out, co
     const unsigned grid = (unsigned)((rows + ROWS - 1) / ROWS);
     const int lds = (int)tilering_lds_bytes(f, ROWS);
     const int stride = top_stride_bytes(f->top_levels);
-    if (leaf_out)
-        hipLaunchKernelGGL((tilering_kernel<ROWS, NWALK, true>), dim3(grid), dim3((NWALK + 1) * 64), lds, stream,
+    with_leaf(leaf_out != nullptr, [&](auto wl) {
+        hipLaunchKernelGGL((tilering_kernel<ROWS, NWALK, decltype(wl)::value>), dim3(grid), dim3((NWALK + 1) * 64), lds, stream,
                            f->top, f->blocks, f->inner, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
                            f->p.num_trees, f->depth, f->top_levels, stride, f->p.missing, vec4_ok, f->error_flag);
-    else
-        hipLaunchKernelGGL((tilering_kernel<ROWS, NWALK, false>), dim3(grid), dim3((NWALK + 1) * 64), lds, stream,
-                           f->top, f->blocks, f->inner, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
-                           f->p.num_trees, f->depth, f->top_levels, stride, f->p.missing, vec4_ok, f->error_flag);
+    });
 }
 
 // sums_in (optional, may be `sums` itself): running float32 sums of the trees BEFORE this forest -- every kernel then
@@ -891,42 +885,20 @@ static tahoe_status launch_traversal(tahoe_forest *f, float *sums, uint32_t *lea
         const size_t grid = (rows + kTileRows - 1) / kTileRows;
         const int lds = rowtile_lds_bytes(f->p.num_cols, f->lds_levels);
         const int nc = f->num_classes;
-        if (leaf_out && nc > 1)
-            hipLaunchKernelGGL((rowtile_kernel<true, true>), dim3((unsigned)grid), dim3(kBlock), lds, stream, f->inner,
-                               f->leaf_val, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
+        with_leaf_mc(leaf_out != nullptr, nc > 1, [&](auto wl, auto mc) {
+            hipLaunchKernelGGL((rowtile_kernel<decltype(wl)::value, decltype(mc)::value>), dim3((unsigned)grid), dim3(kBlock), lds,
+                               stream, f->inner, f->leaf_val, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
                                f->p.num_trees, f->depth, f->lds_levels, f->p.missing, vec4_ok, nc);
-        else if (nc > 1)
-            hipLaunchKernelGGL((rowtile_kernel<false, true>), dim3((unsigned)grid), dim3(kBlock), lds, stream, f->inner,
-                               f->leaf_val, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
-                               f->p.num_trees, f->depth, f->lds_levels, f->p.missing, vec4_ok, nc);
-        else if (leaf_out)
-            hipLaunchKernelGGL(rowtile_kernel<true>, dim3((unsigned)grid), dim3(kBlock), lds, stream, f->inner,
-                               f->leaf_val, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
-                               f->p.num_trees, f->depth, f->lds_levels, f->p.missing, vec4_ok, nc);
-        else
-            hipLaunchKernelGGL(rowtile_kernel<false>, dim3((unsigned)grid), dim3(kBlock), lds, stream, f->inner,
-                               f->leaf_val, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
-                               f->p.num_trees, f->depth, f->lds_levels, f->p.missing, vec4_ok, nc);
+        });
         TAHOE_HIP_TRY(hipGetLastError());
     } else if (strategy == TAHOE_STRATEGY_DIRECT) {
         const size_t grid = (rows + kBlock - 1) / kBlock;
         const int nc = f->num_classes;
-        if (leaf_out && nc > 1)
-            hipLaunchKernelGGL((direct_kernel<true, true>), dim3((unsigned)grid), dim3(kBlock), 0, stream, f->inner,
-                               f->leaf_val, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
+        with_leaf_mc(leaf_out != nullptr, nc > 1, [&](auto wl, auto mc) {
+            hipLaunchKernelGGL((direct_kernel<decltype(wl)::value, decltype(mc)::value>), dim3((unsigned)grid), dim3(kBlock), 0,
+                               stream, f->inner, f->leaf_val, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
                                f->p.num_trees, f->depth, f->p.missing, nc);
-        else if (nc > 1)
-            hipLaunchKernelGGL((direct_kernel<false, true>), dim3((unsigned)grid), dim3(kBlock), 0, stream, f->inner,
-                               f->leaf_val, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
-                               f->p.num_trees, f->depth, f->p.missing, nc);
-        else if (leaf_out)
-            hipLaunchKernelGGL(direct_kernel<true>, dim3((unsigned)grid), dim3(kBlock), 0, stream, f->inner,
-                               f->leaf_val, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
-                               f->p.num_trees, f->depth, f->p.missing, nc);
-        else
-            hipLaunchKernelGGL(direct_kernel<false>, dim3((unsigned)grid), dim3(kBlock), 0, stream, f->inner,
-                               f->leaf_val, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
-                               f->p.num_trees, f->depth, f->p.missing, nc);
+        });
         TAHOE_HIP_TRY(hipGetLastError());
     } else {
         return fail(TAHOE_ERR_INVALID_ARG, "unknown strategy %d", strategy);
@@ -1221,16 +1193,13 @@ static tahoe_status create_dense(tahoe_forest **out, const tahoe_dense_node *nod
 
     // Kernels that may need more than the default 64 KiB of dynamic LDS.
     if (rowtile_fits(f)) {
-        if ((e = allow_max_lds(reinterpret_cast<const void *>(&rowtile_kernel<false>), f->lds_limit)) != hipSuccess) return bail(e, "hipFuncSetAttribute(rowtile)");
-        if ((e = allow_max_lds(reinterpret_cast<const void *>(&rowtile_kernel<true>), f->lds_limit)) != hipSuccess) return bail(e, "hipFuncSetAttribute(rowtile)");
-        if (num_classes > 1) {
-            if ((e = allow_max_lds(reinterpret_cast<const void *>(&rowtile_kernel<false, true>), f->lds_limit)) != hipSuccess) return bail(e, "hipFuncSetAttribute(rowtile)");
-            if ((e = allow_max_lds(reinterpret_cast<const void *>(&rowtile_kernel<true, true>), f->lds_limit)) != hipSuccess) return bail(e, "hipFuncSetAttribute(rowtile)");
-        }
+        if ((e = allow_max_lds_leaf([](auto wl) { return &rowtile_kernel<decltype(wl)::value>; }, f->lds_limit)) != hipSuccess ||
+            (num_classes > 1 && (e = allow_max_lds_leaf([](auto wl) { return &rowtile_kernel<decltype(wl)::value, true>; }, f->lds_limit)) != hipSuccess))
+            return bail(e, "hipFuncSetAttribute(rowtile)");
     }
     if (f->has_blocks && tileblock_lds_bytes(f, 128) <= f->lds_limit) {
-        if ((e = allow_max_lds(reinterpret_cast<const void *>(&tileblock_kernel<128, false>), f->lds_limit)) != hipSuccess) return bail(e, "hipFuncSetAttribute(tileblock)");
-        if ((e = allow_max_lds(reinterpret_cast<const void *>(&tileblock_kernel<128, true>), f->lds_limit)) != hipSuccess) return bail(e, "hipFuncSetAttribute(tileblock)");
+        if ((e = allow_max_lds_leaf([](auto wl) { return &tileblock_kernel<128, decltype(wl)::value>; }, f->lds_limit)) != hipSuccess)
+            return bail(e, "hipFuncSetAttribute(tileblock)");
     }
     if ((e = hipMalloc(reinterpret_cast<void **>(&f->error_flag), sizeof(int))) != hipSuccess)
         return bail(e, "hipMalloc(error_flag)");
@@ -1250,16 +1219,16 @@ static tahoe_status create_dense(tahoe_forest **out, const tahoe_dense_node *nod
         }
     }
     if (f->has_blocks && tilering_lds_bytes(f, 64) <= f->lds_limit) {
-        if ((e = allow_max_lds(reinterpret_cast<const void *>(&tilering_kernel<64, 8, false>), f->lds_limit)) != hipSuccess) return bail(e, "hipFuncSetAttribute(tilering)");
-        if ((e = allow_max_lds(reinterpret_cast<const void *>(&tilering_kernel<64, 8, true>), f->lds_limit)) != hipSuccess) return bail(e, "hipFuncSetAttribute(tilering)");
+        if ((e = allow_max_lds_leaf([](auto wl) { return &tilering_kernel<64, 8, decltype(wl)::value>; }, f->lds_limit)) != hipSuccess)
+            return bail(e, "hipFuncSetAttribute(tilering)");
     }
     if (f->has_blocks && tilering_lds_bytes(f, 128) <= f->lds_limit) {
-        if ((e = allow_max_lds(reinterpret_cast<const void *>(&tilering_kernel<128, 4, false>), f->lds_limit)) != hipSuccess) return bail(e, "hipFuncSetAttribute(tilering)");
-        if ((e = allow_max_lds(reinterpret_cast<const void *>(&tilering_kernel<128, 4, true>), f->lds_limit)) != hipSuccess) return bail(e, "hipFuncSetAttribute(tilering)");
+        if ((e = allow_max_lds_leaf([](auto wl) { return &tilering_kernel<128, 4, decltype(wl)::value>; }, f->lds_limit)) != hipSuccess)
+            return bail(e, "hipFuncSetAttribute(tilering)");
     }
     if (f->has_blocks && tileblock_lds_bytes(f, 64) <= f->lds_limit) {
-        if ((e = allow_max_lds(reinterpret_cast<const void *>(&tileblock_kernel<64, false>), f->lds_limit)) != hipSuccess) return bail(e, "hipFuncSetAttribute(tileblock)");
-        if ((e = allow_max_lds(reinterpret_cast<const void *>(&tileblock_kernel<64, true>), f->lds_limit)) != hipSuccess) return bail(e, "hipFuncSetAttribute(tileblock)");
+        if ((e = allow_max_lds_leaf([](auto wl) { return &tileblock_kernel<64, decltype(wl)::value>; }, f->lds_limit)) != hipSuccess)
+            return bail(e, "hipFuncSetAttribute(tileblock)");
     }
     if (flags & TAHOE_CREATE_CONTRIBS) {
         const tahoe_status cs = contribs_build(f, nodes);

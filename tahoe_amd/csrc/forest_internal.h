@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <type_traits>
 #include <vector>
 
 #include "common.h"
@@ -133,6 +134,35 @@ inline hipError_t allow_max_lds(const void *fn, int limit)
     hipError_t e = hipFuncGetAttributes(&a, fn);
     if (e != hipSuccess) return e;
     return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, limit - (int)a.sharedSizeBytes);
+}
+
+// The launch switch over (write leaf indices) x (multi-class): calls fn(wl, mc) with std::true_type / std::false_type for the
+// runtime pair, so that a launch site names its kernel once, as kernel<decltype(wl)::value, ..., decltype(mc)::value>.
+// with_leaf serves the kernels that have no multi-class flag.
+template <class Fn>
+inline void with_leaf_mc(bool leaf, bool mc, Fn &&fn)
+{
+    if (mc) {
+        if (leaf) fn(std::true_type{}, std::true_type{});
+        else fn(std::false_type{}, std::true_type{});
+    } else if (leaf) {
+        fn(std::true_type{}, std::false_type{});
+    } else {
+        fn(std::false_type{}, std::false_type{});
+    }
+}
+template <class Fn>
+inline void with_leaf(bool leaf, Fn &&fn)
+{
+    if (leaf) fn(std::true_type{});
+    else fn(std::false_type{});
+}
+// allow_max_lds for both leaf-index instantiations of one kernel form: kern(wl) returns the kernel's address for wl as above.
+template <class Kern>
+inline hipError_t allow_max_lds_leaf(Kern &&kern, int limit)
+{
+    const hipError_t e = allow_max_lds(reinterpret_cast<const void *>(kern(std::false_type{})), limit);
+    return e != hipSuccess ? e : allow_max_lds(reinterpret_cast<const void *>(kern(std::true_type{})), limit);
 }
 
 // A process that drives several GPUs (one handle per device) calls predict with any device current: the launches

@@ -36,26 +36,16 @@
 // fid/flag word; here the threshold is compressed too, losslessly).
 #include "qring_internal.h"
 
+namespace tahoe {
+
 // s_sleep arguments of the two spin loops (consumer polling ready flags, walker waiting for ring space).  With the 192-row
 // tile's ring of 10 for 14 walkers a finished walker does wait for ring space: walker sleep 4 / 8 / 16 / 32 / 64 -> 3.66 / 3.62 /
 // 3.60 / 3.70 / 5.10 ms on K3; consumer sleep 1 / 4 / 8 -> 3.645 / 3.657 / 3.669.  Raising the consumer wave's priority
 // (s_setprio): no difference.
-#ifndef TAHOE_CONS_SLEEP
-#define TAHOE_CONS_SLEEP 1
-#endif
-#ifndef TAHOE_WALK_SLEEP
-#define TAHOE_WALK_SLEEP 16
-#endif
+constexpr int kConsSleep = 1, kWalkSleep = 16;
 // ... of the 384-row u8 tile (ring of 5 for 14 walkers of six chains: a walker waits for ring space more often, a tree takes twice as
 // long); KR3 walk (profiles/r04/tune_sleep8.txt): walker 8 / 16 / 32 -> 2.76 / 2.80 / 2.93 ms, consumer 1 / 2 -> 2.80 / 2.79
-#ifndef TAHOE_WALK_SLEEP8
-#define TAHOE_WALK_SLEEP8 8
-#endif
-#ifndef TAHOE_CONS_SLEEP8
-#define TAHOE_CONS_SLEEP8 1
-#endif
-
-namespace tahoe {
+constexpr int kConsSleep8 = 1, kWalkSleep8 = 8;
 
 // ------------------------------------------------------------------------------------------------
 // (2) the walk.  Dynamic LDS: tile [cols][128] u16 | NWALK slots of (4 << L) bytes | ring [RING][64 K] f32 |
@@ -184,7 +174,7 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
                     dead = true;
                     break;
                 }
-                __builtin_amdgcn_s_sleep(CODE8 && K > 2 ? TAHOE_CONS_SLEEP8 : TAHOE_CONS_SLEEP);
+                __builtin_amdgcn_s_sleep(CODE8 && K > 2 ? kConsSleep8 : kConsSleep);
             }
             if (dead) break;
             TAHOE_LDS_ACQUIRE();  // the values are read after the flags
@@ -295,7 +285,7 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
                         dead = true;
                         break;
                     }
-                    __builtin_amdgcn_s_sleep(CODE8 && K > 2 ? TAHOE_WALK_SLEEP8 : TAHOE_WALK_SLEEP);
+                    __builtin_amdgcn_s_sleep(CODE8 && K > 2 ? kWalkSleep8 : kWalkSleep);
                 }
             }
             const int e = t % RING;
@@ -443,10 +433,8 @@ __global__ void __launch_bounds__(16 * 64)
     constexpr int TPW = 64 / RT;                       // trees a walker wave walks at once, per chain
     constexpr int TPG = TPW * KG;                      // ... in all: the consecutive trees of one walker iteration
     constexpr int RE = RB / (RT * 4);                  // ring entries (trees)
-#ifndef TAHOE_WIDE_BATCH
-#define TAHOE_WIDE_BATCH 64  // K2 (four trees per wave): 64 -> 1.07 ms, 16 -> 1.16, 8 -> 1.44
-#endif
-    constexpr int NBATCH = RE / 2 < TAHOE_WIDE_BATCH ? RE / 2 : TAHOE_WIDE_BATCH;  // trees the consumer takes per poll (<= 64)
+    constexpr int kWideBatch = 64;  // K2 (four trees per wave): 64 -> 1.07 ms, 16 -> 1.16, 8 -> 1.44
+    constexpr int NBATCH = RE / 2 < kWideBatch ? RE / 2 : kWideBatch;  // trees the consumer takes per poll (<= 64)
     constexpr int CSHIFT = RT == 64 ? 7 : RT == 32 ? 6 : 5;  // log2 of a feature column's bytes
     static_assert(NBATCH <= 64 && RE >= (KG == 1 ? 2 : 1) * NWALK * TPG, "ring too small");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -817,33 +805,69 @@ long long qring_lds_bytes(const tahoe_forest *f)
     return n ? qring_lds_for(f, n, qring_lds_tile(f)) : 0;
 }
 
-template <int NWALK>
-static hipError_t q_allow(long long lds)
+// ---- the forms of qring_kernel the library runs, each named once ----
+// A form is the kernel's template arguments less the leaf-index and multi-class flags.  QForm holds the defaults (128-slot columns
+// of u16 codes, 15 walkers); each form states only what it changes.  q_kernel<F, WL, MC> is the kernel of form F.
+struct QForm {
+    static constexpr int nwalk = 15, k = 2, ring = kQRing, batch = kQBatch, regb = kRegBytes;
+    static constexpr bool ldsx = true, narrow = false, exch = false, reg = false, split = false, code8 = false, dep = false;
+};
+template <int N> struct QColumns : QForm { static constexpr int nwalk = N; };  // 15 / 12 / 8 / 4 walkers
+struct QNarrow : QForm { static constexpr bool narrow = true; };                // NARROW node words (num_cols <= 256)
+struct QExch : QNarrow { static constexpr bool exch = true; };                  // ... with the exchange bit of the re-layout
+struct QGx : QForm {                                                            // no LDS tile: features read from L2
+    static constexpr int nwalk = kGxWalkers;
+    static constexpr bool ldsx = false;
+};
+// region forms (see qring_kernel): the 128-row tile and its SPLIT variant, on u16 and on u8 codes
+struct QReg2 : QNarrow { static constexpr bool reg = true; };
+struct QReg2Split : QReg2 { static constexpr bool split = true; };
+struct QReg2U8 : QReg2 { static constexpr bool code8 = true; };
+struct QReg2U8Split : QReg2U8 { static constexpr bool split = true; };
+struct QReg3 : QReg2 {  // the 192-row u16 tile
+    static constexpr int nwalk = kReg3Walkers, k = 3, ring = kReg3Ring, batch = kReg3Batch;
+    static constexpr bool dep = kReg3Dep;
+};
+struct QReg8 : QReg2 {  // the 384-row u8 tile (32-KiB region stride)
+    static constexpr int nwalk = kReg8Walkers, k = 6, ring = kReg8Ring, batch = kReg8Batch;
+    static constexpr bool code8 = true, dep = kReg8Dep;
+};
+struct QReg8N : QReg2U8 {  // the 384-row u8 tile of forests of <= 128 features: 16-KiB stride, 15 walkers, ring of 24
+    static constexpr int k = 6, regb = kRegBytes / 2;
+    static constexpr bool dep = kReg8Dep;
+};
+struct QSix16 : QReg8 {  // six 16-KiB regions of u16 codes (forests of <= 128 features): the u8 tile's walkers and ring
+    static constexpr int regb = kRegBytes / 2;
+    static constexpr bool code8 = false;
+};
+template <class F, bool WL, bool MC>
+constexpr auto q_kernel = &qring_kernel<F::nwalk, WL, F::ldsx, F::narrow, F::exch, F::k, F::reg, F::ring, F::split, F::batch, F::code8,
+                                        F::dep, F::regb, MC>;
+
+// Raises the dynamic-LDS limit of each form's two leaf-index instantiations (the multi-class ones with MC).
+template <bool MC, class... F>
+static hipError_t q_allow(int limit)
 {
-    hipError_t e = allow_max_lds(reinterpret_cast<const void *>(&qring_kernel<NWALK, false, true>), (int)lds);
-    if (e != hipSuccess) return e;
-    e = allow_max_lds(reinterpret_cast<const void *>(&qring_kernel<NWALK, true, true>), (int)lds);
-    if (e != hipSuccess || NWALK != 15) return e;
-    for (const void *k : {(const void *)&qring_kernel<15, false, true, true>, (const void *)&qring_kernel<15, true, true, true>,
-                          (const void *)&qring_kernel<15, false, true, true, true>, (const void *)&qring_kernel<15, true, true, true, true>,
-                          (const void *)&qring_kernel<15, false, true, true, false, 2, true>, (const void *)&qring_kernel<15, true, true, true, false, 2, true>,
-                          (const void *)&qring_kernel<kReg3Walkers, false, true, true, false, 3, true, kReg3Ring, false, kReg3Batch, false, kReg3Dep>,
-                          (const void *)&qring_kernel<kReg3Walkers, true, true, true, false, 3, true, kReg3Ring, false, kReg3Batch, false, kReg3Dep>,
-                          (const void *)&qring_kernel<15, false, true, true, false, 2, true, kQRing, true>,
-                          (const void *)&qring_kernel<15, true, true, true, false, 2, true, kQRing, true>,
-                          (const void *)&qring_kernel<kReg8Walkers, false, true, true, false, 6, true, kReg8Ring, false, kReg8Batch, true, kReg8Dep>,
-                          (const void *)&qring_kernel<kReg8Walkers, true, true, true, false, 6, true, kReg8Ring, false, kReg8Batch, true, kReg8Dep>,
-                          (const void *)&qring_kernel<15, false, true, true, false, 2, true, kQRing, false, kQBatch, true>,
-                          (const void *)&qring_kernel<15, true, true, true, false, 2, true, kQRing, false, kQBatch, true>,
-                          (const void *)&qring_kernel<15, false, true, true, false, 2, true, kQRing, true, kQBatch, true>,
-                          (const void *)&qring_kernel<15, true, true, true, false, 2, true, kQRing, true, kQBatch, true>,
-                          // <= 128 features: six 16-KiB regions of u16 codes; three 16-KiB regions of u8 codes, 15 walkers, ring of 24
-                          (const void *)&qring_kernel<kReg8Walkers, false, true, true, false, 6, true, kReg8Ring, false, kReg8Batch, false, kReg8Dep, kRegBytes / 2>,
-                          (const void *)&qring_kernel<kReg8Walkers, true, true, true, false, 6, true, kReg8Ring, false, kReg8Batch, false, kReg8Dep, kRegBytes / 2>,
-                          (const void *)&qring_kernel<15, false, true, true, false, 6, true, kQRing, false, kQBatch, true, kReg8Dep, kRegBytes / 2>,
-                          (const void *)&qring_kernel<15, true, true, true, false, 6, true, kQRing, false, kQBatch, true, kReg8Dep, kRegBytes / 2>})
-        if ((e = allow_max_lds(k, (int)lds)) != hipSuccess) return e;
-    return hipSuccess;
+    hipError_t e = hipSuccess;
+    (void)(((e = allow_max_lds_leaf([](auto wl) { return q_kernel<F, decltype(wl)::value, MC>; }, limit)) == hipSuccess) && ...);
+    return e;
+}
+
+// The region forms of a handle, picked here only: fn(large, small, split) with its large tile (192 or 384 rows), its 128-row tile
+// and that tile's SPLIT variant.
+template <class Fn>
+static auto with_qreg_forms(const tahoe_qstate *q, Fn &&fn)
+{
+    if (q->code8 && q->narrow128) return fn(QReg8N{}, QReg2U8{}, QReg2U8Split{});
+    if (q->code8) return fn(QReg8{}, QReg2U8{}, QReg2U8Split{});
+    if (q->narrow128) return fn(QSix16{}, QReg2{}, QReg2Split{});
+    return fn(QReg3{}, QReg2{}, QReg2Split{});
+}
+
+template <int RT, int KG, int RB, bool MC = false>
+static hipError_t qwide_allow(int limit)
+{
+    return allow_max_lds_leaf([](auto wl) { return &qwide_kernel<RT, decltype(wl)::value, KG, RB, MC>; }, limit);
 }
 
 // Builds one tree group [lo, hi).  Returns TAHOE_OK with *too_many = the largest per-feature count when that
@@ -1046,20 +1070,20 @@ tahoe_status qring_build(tahoe_forest *f, const std::vector<InnerNode> &h_inner,
     // kernels that need more than 64 KiB of dynamic LDS
     hipError_t e;
     auto bad = [&](const char *what) { return fail(TAHOE_ERR_HIP, "qring_build: %s failed: %s", what, hipGetErrorString(e)); };
-    if (qring_lds_for(f, 15) <= f->lds_limit && (e = q_allow<15>(f->lds_limit)) != hipSuccess) return bad("attr15");
-    if (qring_lds_for(f, 12) <= f->lds_limit && (e = q_allow<12>(f->lds_limit)) != hipSuccess) return bad("attr12");
-    if (qring_lds_for(f, 8) <= f->lds_limit && (e = q_allow<8>(f->lds_limit)) != hipSuccess) return bad("attr8");
-    if (qring_lds_for(f, 4) <= f->lds_limit && (e = q_allow<4>(f->lds_limit)) != hipSuccess) return bad("attr4");
-    if ((e = allow_max_lds(reinterpret_cast<const void *>(&qring_kernel<kGxWalkers, false, false>), f->lds_limit)) != hipSuccess)
-        return bad("attr(gx)");
-    if ((e = allow_max_lds(reinterpret_cast<const void *>(&qring_kernel<kGxWalkers, true, false>), f->lds_limit)) != hipSuccess)
-        return bad("attr(gx)");
-    for (const void *k : {(const void *)&qwide_kernel<64, false>, (const void *)&qwide_kernel<64, true>, (const void *)&qwide_kernel<32, false>,
-                          (const void *)&qwide_kernel<32, true>, (const void *)&qwide_kernel<16, false>, (const void *)&qwide_kernel<16, true>,
-                          (const void *)&qwide_kernel<64, false, 3, kWideRingBytesK>, (const void *)&qwide_kernel<64, true, 3, kWideRingBytesK>,
-                          (const void *)&qwide_kernel<32, false, 3, kWideRingBytesK>, (const void *)&qwide_kernel<32, true, 3, kWideRingBytesK>,
-                          (const void *)&qwide_kernel<16, false, 3, kWideRingBytesK>, (const void *)&qwide_kernel<16, true, 3, kWideRingBytesK>})
-        if ((e = allow_max_lds(k, f->lds_limit)) != hipSuccess) return bad("attr(qwide)");
+    if (qring_lds_for(f, 15) <= f->lds_limit && (e = q_allow<false, QColumns<15>, QNarrow, QExch>(f->lds_limit)) != hipSuccess)
+        return bad("attr15");
+    if (q->reg && (e = with_qreg_forms(q, [&](auto large, auto small, auto split) {
+                       return q_allow<false, decltype(large), decltype(small), decltype(split)>(f->lds_limit);
+                   })) != hipSuccess)
+        return bad("attr(regions)");
+    if (qring_lds_for(f, 12) <= f->lds_limit && (e = q_allow<false, QColumns<12>>(f->lds_limit)) != hipSuccess) return bad("attr12");
+    if (qring_lds_for(f, 8) <= f->lds_limit && (e = q_allow<false, QColumns<8>>(f->lds_limit)) != hipSuccess) return bad("attr8");
+    if (qring_lds_for(f, 4) <= f->lds_limit && (e = q_allow<false, QColumns<4>>(f->lds_limit)) != hipSuccess) return bad("attr4");
+    if ((e = q_allow<false, QGx>(f->lds_limit)) != hipSuccess) return bad("attr(gx)");
+    if ((e = qwide_allow<64, 1, kWideRingBytes>(f->lds_limit)) != hipSuccess || (e = qwide_allow<32, 1, kWideRingBytes>(f->lds_limit)) != hipSuccess ||
+        (e = qwide_allow<16, 1, kWideRingBytes>(f->lds_limit)) != hipSuccess || (e = qwide_allow<64, 3, kWideRingBytesK>(f->lds_limit)) != hipSuccess ||
+        (e = qwide_allow<32, 3, kWideRingBytesK>(f->lds_limit)) != hipSuccess || (e = qwide_allow<16, 3, kWideRingBytesK>(f->lds_limit)) != hipSuccess)
+        return bad("attr(qwide)");
     if ((e = quantize_allow_lds(f)) != hipSuccess) return bad("attr(quantise kernels)");
     return TAHOE_OK;
 }
@@ -1164,46 +1188,36 @@ static tahoe_status qring_reserve_leafbuf(tahoe_forest *f, size_t rows, int tree
     return TAHOE_OK;
 }
 
-template <int NWALK, bool LDSX = true, bool NARROW = false, bool EXCH = false, int K = 2, bool REG = false, int RING = kQRing,
-          bool SPLIT = false, int BATCH = (RING >= 2 * kQBatch ? kQBatch : RING / 2), bool CODE8 = false, bool DEP = false, int REGB = kRegBytes>
+template <class F>
 static void q_launch(tahoe_forest *f, const tahoe_qgroup &g, float *sums, const float *sums_in, uint32_t *leaf_out,
                      size_t rows, hipStream_t stream, int cshift, int slices = 1, size_t row_begin = 0)
 {
     tahoe_qstate *q = f->q;
-    const unsigned grid = (unsigned)((rows - row_begin + 64 * K - 1) / (64 * K)) * (unsigned)(SPLIT ? slices : 1);
+    const unsigned grid = (unsigned)((rows - row_begin + 64 * F::k - 1) / (64 * F::k)) * (unsigned)(F::split ? slices : 1);
     if (grid == 0) return;
-    float *leafbuf = SPLIT ? q->leafbuf : nullptr;
-    const size_t leaf_stride = SPLIT ? q->leaf_stride : 0;
-    const int lds = REG ? (int)qreg_lds_for(K, NWALK, RING, CODE8, REGB) : (int)qring_lds_for(f, NWALK, LDSX);
+    float *leafbuf = F::split ? q->leafbuf : nullptr;
+    const size_t leaf_stride = F::split ? q->leaf_stride : 0;
+    const int lds = F::reg ? (int)qreg_lds_for(F::k, F::nwalk, F::ring, F::code8, F::regb) : (int)qring_lds_for(f, F::nwalk, F::ldsx);
     const uint32_t *leaf_orig = f->leaf_orig + (size_t)g.tree_lo * f->n_leaf;
     const int nc = f->num_classes;
-#define TAHOE_Q_LAUNCH(WL, MCF)                                                                                                        \
-    hipLaunchKernelGGL((qring_kernel<NWALK, WL, LDSX, NARROW, EXCH, K, REG, RING, SPLIT, BATCH, CODE8, DEP, REGB, MCF>), dim3(grid),   \
-                       dim3((NWALK + 1) * 64), lds, stream, q->xq, g.top, g.blocks, g.qinner, leaf_orig, sums, leaf_out, rows,        \
-                       f->p.num_cols, g.num_trees, f->depth, q->top_levels, q->top_stride, q->chunk_flags, f->error_flag, sums_in,    \
-                       g.tree_lo, f->p.num_trees, cshift, leafbuf, leaf_stride, slices, row_begin, nc)
     if (nc > 1) {
         // multi-class instantiations: their LDS limit is raised on first use (process-wide, like allow_max_lds at create)
-        static const bool allowed = allow_max_lds(reinterpret_cast<const void *>(&qring_kernel<NWALK, false, LDSX, NARROW, EXCH, K, REG, RING, SPLIT, BATCH, CODE8, DEP, REGB, true>), f->lds_limit) == hipSuccess &&
-                                    allow_max_lds(reinterpret_cast<const void *>(&qring_kernel<NWALK, true, LDSX, NARROW, EXCH, K, REG, RING, SPLIT, BATCH, CODE8, DEP, REGB, true>), f->lds_limit) == hipSuccess;
+        static const bool allowed = q_allow<true, F>(f->lds_limit) == hipSuccess;
         (void)allowed;  // a failure shows as the launch error
-        if (leaf_out)
-            TAHOE_Q_LAUNCH(true, true);
-        else
-            TAHOE_Q_LAUNCH(false, true);
-    } else if (leaf_out) {
-        TAHOE_Q_LAUNCH(true, false);
-    } else {
-        TAHOE_Q_LAUNCH(false, false);
     }
-#undef TAHOE_Q_LAUNCH
+    with_leaf_mc(leaf_out != nullptr, nc > 1, [&](auto wl, auto mc) {
+        hipLaunchKernelGGL((q_kernel<F, decltype(wl)::value, decltype(mc)::value>), dim3(grid), dim3((F::nwalk + 1) * 64), lds, stream,
+                           q->xq, g.top, g.blocks, g.qinner, leaf_orig, sums, leaf_out, rows, f->p.num_cols, g.num_trees, f->depth,
+                           q->top_levels, q->top_stride, q->chunk_flags, f->error_flag, sums_in, g.tree_lo, f->p.num_trees, cshift,
+                           leafbuf, leaf_stride, slices, row_begin, nc);
+    });
     const unsigned sum_blocks = (unsigned)((rows - row_begin + kOrderedSumThreads - 1) / kOrderedSumThreads);
-    if (SPLIT && sums && nc > 1) {
+    if (F::split && sums && nc > 1) {
         const int ctrees = f->p.num_trees / nc;
         const unsigned classes = (unsigned)((g.tree_lo + g.num_trees - 1) / ctrees - g.tree_lo / ctrees + 1);  // classes the group overlaps
         hipLaunchKernelGGL(ordered_sum_mc_kernel, dim3(sum_blocks, classes), dim3(kOrderedSumThreads), 0, stream, leafbuf, leaf_stride, g.num_trees,
                            sums_in, sums, rows, row_begin, g.tree_lo, f->p.num_trees, nc);
-    } else if (SPLIT && sums) {
+    } else if (F::split && sums) {
         hipLaunchKernelGGL(ordered_sum_kernel, dim3(sum_blocks), dim3(kOrderedSumThreads), 0, stream,
                            leafbuf, leaf_stride, g.num_trees, sums_in, sums, rows, row_begin);
     }
@@ -1219,24 +1233,16 @@ static void qwide_launch_form(tahoe_forest *f, const tahoe_qgroup &g, float *sum
     const int slot_bytes = KG * (int)qwide_slot_bytes(q->wide_lw, RT);
     const uint32_t *leaf_orig = f->leaf_orig + (size_t)g.tree_lo * f->n_leaf;
     const int nc = f->num_classes;
-#define TAHOE_QW_LAUNCH(WL, MCF)                                                                                                      \
-    hipLaunchKernelGGL((qwide_kernel<RT, WL, KG, RB, MCF>), dim3(grid), dim3(16 * 64), lds, stream, q->xq, g.top, g.blocks, g.qinner, \
-                       leaf_orig, sums, leaf_out, rows, f->p.num_cols, g.num_trees, f->depth, q->top_levels, q->top_stride,          \
-                       q->chunk_flags, f->error_flag, sums_in, g.tree_lo, f->p.num_trees, slot_bytes, q->wide_lw, cshift, nc)
     if (nc > 1) {
-        static const bool allowed = allow_max_lds(reinterpret_cast<const void *>(&qwide_kernel<RT, false, KG, RB, true>), f->lds_limit) == hipSuccess &&
-                                    allow_max_lds(reinterpret_cast<const void *>(&qwide_kernel<RT, true, KG, RB, true>), f->lds_limit) == hipSuccess;
+        static const bool allowed = qwide_allow<RT, KG, RB, true>(f->lds_limit) == hipSuccess;
         (void)allowed;  // (as in q_launch)
-        if (leaf_out)
-            TAHOE_QW_LAUNCH(true, true);
-        else
-            TAHOE_QW_LAUNCH(false, true);
-    } else if (leaf_out) {
-        TAHOE_QW_LAUNCH(true, false);
-    } else {
-        TAHOE_QW_LAUNCH(false, false);
     }
-#undef TAHOE_QW_LAUNCH
+    with_leaf_mc(leaf_out != nullptr, nc > 1, [&](auto wl, auto mc) {
+        hipLaunchKernelGGL((qwide_kernel<RT, decltype(wl)::value, KG, RB, decltype(mc)::value>), dim3(grid), dim3(16 * 64), lds, stream,
+                           q->xq, g.top, g.blocks, g.qinner, leaf_orig, sums, leaf_out, rows, f->p.num_cols, g.num_trees, f->depth,
+                           q->top_levels, q->top_stride, q->chunk_flags, f->error_flag, sums_in, g.tree_lo, f->p.num_trees, slot_bytes,
+                           q->wide_lw, cshift, nc);
+    });
 }
 
 template <int RT>
@@ -1247,6 +1253,50 @@ static void qwide_launch(tahoe_forest *f, const tahoe_qgroup &g, float *sums, co
         qwide_launch_form<RT, 3, kWideRingBytesK>(f, g, sums, sums_in, leaf_out, rows, stream, cshift);
     else
         qwide_launch_form<RT, 1, kWideRingBytes>(f, g, sums, sums_in, leaf_out, rows, stream, cshift);
+}
+
+// How the region form walks a batch (qring_launch runs it, qring_form reports it).  slices > 1: SPLIT -- every 128-row tile by
+// `slices` workgroups, each a slice of the trees.  Otherwise rows [0, rows3) in whole waves of the handle's large tile, then the
+// remainder [rows3, rows) as large tiles (chains == 3), in tree slices (rem_slices > 1) or as plain 128-row tiles.
+struct QPlan {
+    int slices = 1;
+    int most = 1;        // trees of the largest group (the leaf buffer of the sliced forms)
+    size_t rows3 = 0;    // a multiple of 384
+    int chains = 2;
+    int rem_slices = 1;
+};
+static QPlan qring_plan(const tahoe_forest *f, size_t rows)
+{
+    const tahoe_qstate *q = f->q;
+    QPlan p;
+    p.slices = q_slices(f, rows, &p.most);
+    if (!q->reg || p.slices > 1) return p;
+    // TAHOE_QRING_CHAINS = 2 / 3 forces one form, TAHOE_QRING_SLICES = 1 keeps every remainder in plain tiles.  u8 codes and
+    // forests of <= 128 features plan 384-row tiles against 128-row ones, u16 codes 192-row tiles.
+    const int slice_trees = f->knob_qring_slices == 1 ? 0 : p.most;
+    if (q->code8 || q->narrow128)
+        qreg_plan(rows, f->num_cus, f->knob_qring_chains, &p.rows3, &p.chains, kReg8Cost, 384, slice_trees);
+    else
+        qreg_plan(rows, f->num_cus, f->knob_qring_chains, &p.rows3, &p.chains, 133, 192, slice_trees);
+    // A remainder of few 128-row tiles behind the whole waves of large tiles would leave most of the chip idle for a whole tile
+    // time (250 k rows of K3's forest: 5 waves of 192-row tiles + 34 tiles of 128): it is walked in tree slices too -- every
+    // remainder tile by rem_slices workgroups, then the ordered sum over those rows (bit-identical: the same sequential sum).
+    if (p.rows3 > 0 && p.chains == 2) p.rem_slices = qreg_rem_slices(rows - p.rows3, f->num_cus, slice_trees);  // as the planner priced it
+    return p;
+}
+
+template <class LARGE, class SMALL, class SPLIT>
+static void qreg_walk(const QPlan &p, tahoe_forest *f, const tahoe_qgroup &g, float *sums, const float *sums_in, uint32_t *leaf_out,
+                      size_t rows, hipStream_t stream, int cshift)
+{
+    if (p.slices > 1) return q_launch<SPLIT>(f, g, sums, sums_in, leaf_out, rows, stream, cshift, p.slices);
+    if (p.rows3 > 0) q_launch<LARGE>(f, g, sums, sums_in, leaf_out, p.rows3, stream, cshift);
+    if (p.chains == 3)
+        q_launch<LARGE>(f, g, sums, sums_in, leaf_out, rows, stream, cshift, 1, p.rows3);
+    else if (p.rem_slices > 1)
+        q_launch<SPLIT>(f, g, sums, sums_in, leaf_out, rows, stream, cshift, p.rem_slices, p.rows3);
+    else
+        q_launch<SMALL>(f, g, sums, sums_in, leaf_out, rows, stream, cshift, 1, p.rows3);
 }
 
 tahoe_status qring_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data, size_t rows,
@@ -1262,39 +1312,17 @@ tahoe_status qring_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, cons
     if (s != TAHOE_OK) return s;
     const int wide = qwide_rows(f);  // 0: 128-row tiles; else rows per tile of the wide-row form
     const int trs = q->reg ? 6 : wide == 64 ? 6 : wide == 32 ? 5 : wide == 16 ? 4 : 7;
-    size_t rows3 = 0;   // rows [0, rows3) in 192-row tiles, a multiple of 384
-    int chains = 2;     // form of the remaining rows [rows3, rows)
-    int most = 1;
-    const int slices = q_slices(f, rows, &most);  // small batches of the region form: tree slices per tile (SPLIT)
-    const bool code8 = q->code8;                  // u8 codes: 384-row tiles for whole waves, 128-row tiles for the remainder and for tree slices
-    const bool six16 = !code8 && q->reg && q->narrow128 && slices <= 1;  // u16 codes, <= 128 features: six 16-KiB regions, the same plan
-    if ((code8 && slices <= 1) || six16)
-        qreg_plan(rows, f->num_cus, f->knob_qring_chains, &rows3, &chains, kReg8Cost, 384, f->knob_qring_slices == 1 ? 0 : most);
-    else if (q->reg)  // TAHOE_QRING_CHAINS = 2 / 3 forces one form, TAHOE_QRING_SLICES = 1 keeps every remainder in plain tiles
-        qreg_plan(rows, f->num_cus, f->knob_qring_chains, &rows3, &chains, 133, 192, f->knob_qring_slices == 1 ? 0 : most);
-    if (slices > 1) {
-        const tahoe_status ls = qring_reserve_leafbuf(f, rows, most);  // no-op after tahoe_forest_reserve / a first predict
+    const QPlan plan = qring_plan(f, rows);
+    if (plan.slices > 1 || plan.rem_slices > 1) {  // no-op after tahoe_forest_reserve / a first predict
+        const tahoe_status ls = qring_reserve_leafbuf(f, plan.slices > 1 ? rows : rows - plan.rows3, plan.most);
         if (ls != TAHOE_OK) return ls;
-        chains = 2;
-        rows3 = 0;
-    }
-    // A remainder of few 128-row tiles behind the whole waves of large tiles would leave most of the chip idle for a whole tile
-    // time (250 k rows of K3's forest: 5 waves of 192-row tiles + 34 tiles of 128): it is walked in tree slices too -- every
-    // remainder tile by rem_slices workgroups, then the ordered sum over those rows (bit-identical: the same sequential sum).
-    int rem_slices = 1;
-    if (q->reg && slices <= 1 && rows3 > 0 && chains == 2 && f->knob_qring_slices != 1) {
-        rem_slices = qreg_rem_slices(rows - rows3, f->num_cus, most);  // the planner priced the remainder with the same rule
-        if (rem_slices > 1) {
-            const tahoe_status ls = qring_reserve_leafbuf(f, rows - rows3, most);  // no-op after tahoe_forest_reserve / a first predict
-            if (ls != TAHOE_OK) return ls;
-        }
     }
     bool first = true;
     for (const tahoe_qgroup &g : q->groups) {  // stream order: quantise for the group, walk the group, next group
         TAHOE_HIP_TRY(hipMemsetAsync(q->chunk_flags, 0, q->n_chunk_flags * sizeof(uint32_t), stream));
         int cshift = 0;  // rows per quantise workgroup = rows per "missing seen" flag, as a shift
         {
-            const tahoe_status qs = quantize_launch(f, g, data, rows, trs, code8 ? 2 : q->reg ? 1 : 0, stream, &cshift);
+            const tahoe_status qs = quantize_launch(f, g, data, rows, trs, q->code8 ? 2 : q->reg ? 1 : 0, stream, &cshift);
             if (qs != TAHOE_OK) return qs;
         }
         TAHOE_HIP_TRY(hipGetLastError());
@@ -1307,75 +1335,30 @@ tahoe_status qring_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, cons
         else if (wide == 16)
             qwide_launch<16>(f, g, sums, sums_in, leaf_out, rows, stream, cshift);
         else if (!qring_lds_tile(f))
-            q_launch<kGxWalkers, false>(f, g, sums, sums_in, leaf_out, rows, stream, cshift);
+            q_launch<QGx>(f, g, sums, sums_in, leaf_out, rows, stream, cshift);
+        else if (q->reg)
+            with_qreg_forms(q, [&](auto large, auto small, auto split) {
+                qreg_walk<decltype(large), decltype(small), decltype(split)>(plan, f, g, sums, sums_in, leaf_out, rows, stream, cshift);
+            });
+        else if (nwalk == 15 && q->narrow && f->relayout)
+            q_launch<QExch>(f, g, sums, sums_in, leaf_out, rows, stream, cshift);
+        else if (nwalk == 15 && q->narrow)
+            q_launch<QNarrow>(f, g, sums, sums_in, leaf_out, rows, stream, cshift);
+        else if (nwalk == 15)
+            q_launch<QColumns<15>>(f, g, sums, sums_in, leaf_out, rows, stream, cshift);
+        else if (nwalk == 12)
+            q_launch<QColumns<12>>(f, g, sums, sums_in, leaf_out, rows, stream, cshift);
+        else if (nwalk == 8)
+            q_launch<QColumns<8>>(f, g, sums, sums_in, leaf_out, rows, stream, cshift);
         else
-        switch (nwalk) {
-            case 15:
-                if (q->reg && slices > 1 && code8)
-                    q_launch<15, true, true, false, 2, true, kQRing, true, kQBatch, true>(f, g, sums, sums_in, leaf_out, rows, stream, cshift, slices);
-                else if (q->reg && slices > 1)
-                    q_launch<15, true, true, false, 2, true, kQRing, true>(f, g, sums, sums_in, leaf_out, rows, stream, cshift, slices);
-                else if (code8 && q->narrow128) {  // u8 codes, <= 128 features: three 16-KiB regions, 15 walkers, ring of 24
-                    if (rows3 > 0)
-                        q_launch<15, true, true, false, 6, true, kQRing, false, kQBatch, true, kReg8Dep, kRegBytes / 2>(f, g, sums, sums_in, leaf_out, rows3, stream, cshift);
-                    if (chains == 3)
-                        q_launch<15, true, true, false, 6, true, kQRing, false, kQBatch, true, kReg8Dep, kRegBytes / 2>(f, g, sums, sums_in, leaf_out, rows, stream, cshift, 1, rows3);
-                    else if (rem_slices > 1)
-                        q_launch<15, true, true, false, 2, true, kQRing, true, kQBatch, true>(f, g, sums, sums_in, leaf_out, rows, stream, cshift, rem_slices, rows3);
-                    else
-                        q_launch<15, true, true, false, 2, true, kQRing, false, kQBatch, true>(f, g, sums, sums_in, leaf_out, rows, stream, cshift, 1, rows3);
-                }
-                else if (code8) {
-                    if (rows3 > 0)
-                        q_launch<kReg8Walkers, true, true, false, 6, true, kReg8Ring, false, kReg8Batch, true, kReg8Dep>(f, g, sums, sums_in, leaf_out, rows3, stream, cshift);
-                    if (chains == 3)
-                        q_launch<kReg8Walkers, true, true, false, 6, true, kReg8Ring, false, kReg8Batch, true, kReg8Dep>(f, g, sums, sums_in, leaf_out, rows, stream, cshift, 1,
-                                                                                                         rows3);
-                    else if (rem_slices > 1)
-                        q_launch<15, true, true, false, 2, true, kQRing, true, kQBatch, true>(f, g, sums, sums_in, leaf_out, rows, stream, cshift, rem_slices, rows3);
-                    else
-                        q_launch<15, true, true, false, 2, true, kQRing, false, kQBatch, true>(f, g, sums, sums_in, leaf_out, rows, stream, cshift, 1, rows3);
-                }
-                else if (six16) {  // u16 codes, <= 128 features: six 16-KiB regions = 384-row tiles, the u8 tile's walkers and ring
-                    if (rows3 > 0)
-                        q_launch<kReg8Walkers, true, true, false, 6, true, kReg8Ring, false, kReg8Batch, false, kReg8Dep, kRegBytes / 2>(f, g, sums, sums_in, leaf_out, rows3, stream, cshift);
-                    if (chains == 3)
-                        q_launch<kReg8Walkers, true, true, false, 6, true, kReg8Ring, false, kReg8Batch, false, kReg8Dep, kRegBytes / 2>(f, g, sums, sums_in, leaf_out, rows, stream, cshift, 1,
-                                                                                                                        rows3);
-                    else if (rem_slices > 1)
-                        q_launch<15, true, true, false, 2, true, kQRing, true>(f, g, sums, sums_in, leaf_out, rows, stream, cshift, rem_slices, rows3);
-                    else
-                        q_launch<15, true, true, false, 2, true>(f, g, sums, sums_in, leaf_out, rows, stream, cshift, 1, rows3);
-                }
-                else if (q->reg) {
-                    if (rows3 > 0)
-                        q_launch<kReg3Walkers, true, true, false, 3, true, kReg3Ring, false, kReg3Batch, false, kReg3Dep>(f, g, sums, sums_in, leaf_out, rows3, stream, cshift);
-                    if (chains == 3)
-                        q_launch<kReg3Walkers, true, true, false, 3, true, kReg3Ring, false, kReg3Batch, false, kReg3Dep>(f, g, sums, sums_in, leaf_out, rows, stream, cshift, 1,
-                                                                                      rows3);
-                    else if (rem_slices > 1)
-                        q_launch<15, true, true, false, 2, true, kQRing, true>(f, g, sums, sums_in, leaf_out, rows, stream, cshift, rem_slices, rows3);
-                    else
-                        q_launch<15, true, true, false, 2, true>(f, g, sums, sums_in, leaf_out, rows, stream, cshift, 1, rows3);
-                }
-                else if (q->narrow && f->relayout)
-                    q_launch<15, true, true, true>(f, g, sums, sums_in, leaf_out, rows, stream, cshift);
-                else if (q->narrow)
-                    q_launch<15, true, true>(f, g, sums, sums_in, leaf_out, rows, stream, cshift);
-                else
-                    q_launch<15>(f, g, sums, sums_in, leaf_out, rows, stream, cshift);
-                break;
-            case 12: q_launch<12>(f, g, sums, sums_in, leaf_out, rows, stream, cshift); break;
-            case 8: q_launch<8>(f, g, sums, sums_in, leaf_out, rows, stream, cshift); break;
-            default: q_launch<4>(f, g, sums, sums_in, leaf_out, rows, stream, cshift); break;
-        }
+            q_launch<QColumns<4>>(f, g, sums, sums_in, leaf_out, rows, stream, cshift);
         TAHOE_HIP_TRY(hipGetLastError());
         first = false;
     }
     return TAHOE_OK;
 }
 
-// The form qring_launch takes for a batch of `rows` rows (TAHOE_FORM_*): the same decisions, nothing launched.
+// The form qring_launch takes for a batch of `rows` rows (TAHOE_FORM_*): the same plan, nothing launched.
 int qring_form(const tahoe_forest *f, size_t rows)
 {
     const tahoe_qstate *q = f->q;
@@ -1383,15 +1366,12 @@ int qring_form(const tahoe_forest *f, size_t rows)
     if (qwide_rows(f)) return TAHOE_FORM_QRING_WIDE;
     if (!qring_lds_tile(f)) return TAHOE_FORM_QRING_GX;
     if (!q->reg) return TAHOE_FORM_QRING_COLUMNS;
-    int most = 1;
-    if (q_slices(f, rows, &most) > 1) return TAHOE_FORM_QRING_SPLIT;
-    size_t rows3 = 0;
-    int chains = 2;
+    const QPlan p = qring_plan(f, rows);
+    if (p.slices > 1) return TAHOE_FORM_QRING_SPLIT;
     if (q->code8) return TAHOE_FORM_QRING_REGION8;
     if (q->narrow128) return TAHOE_FORM_QRING_REGION6;
-    qreg_plan(rows, f->num_cus, f->knob_qring_chains, &rows3, &chains, 133, 192, f->knob_qring_slices == 1 ? 0 : most);
-    if (rows3 > 0 && chains == 2) return TAHOE_FORM_QRING_REGION_MIXED;
-    return chains == 3 ? TAHOE_FORM_QRING_REGION3 : TAHOE_FORM_QRING_REGION2;
+    if (p.rows3 > 0 && p.chains == 2) return TAHOE_FORM_QRING_REGION_MIXED;
+    return p.chains == 3 ? TAHOE_FORM_QRING_REGION3 : TAHOE_FORM_QRING_REGION2;
 }
 
 }  // namespace tahoe

@@ -63,16 +63,10 @@ namespace tahoe {
 
 
 constexpr int kQRows = 128;                 // rows per tile
-// Ring depth and consumer batch, tuned on K3 (tools/ablate_walk.sh style builds): 16/8 4.20 ms, 16/4 4.11, 24/4 4.08,
+// Ring depth and consumer batch, tuned on K3 (rebuilds with other values): 16/8 4.20 ms, 16/4 4.11, 24/4 4.08,
 // 32/4 4.14, 24/6 4.10, 24/3 4.28; a batch of 2 or 1 makes the consumer's polling the bottleneck (4.9 / 6.6 ms).
-#ifndef TAHOE_QRING_RING
-#define TAHOE_QRING_RING 24
-#endif
-#ifndef TAHOE_QRING_BATCH
-#define TAHOE_QRING_BATCH 4
-#endif
-constexpr int kQRing = TAHOE_QRING_RING;    // ring entries (trees)
-constexpr int kQBatch = TAHOE_QRING_BATCH;  // trees the consumer takes per poll
+constexpr int kQRing = 24;   // ring entries (trees)
+constexpr int kQBatch = 4;   // trees the consumer takes per poll
 constexpr int kQSpinLimit = 1 << 22;
 constexpr int kQSlotBytes = 4096;            // LDS per walker: a 10-level top (2^10 u32)
 // Region form (NARROW, num_cols <= 256): a tile is K regions of 64 rows, each [fid][64] u16 at a multiple of 32 KiB in LDS.
@@ -81,14 +75,8 @@ constexpr int kQSlotBytes = 4096;            // LDS per walker: a 10-level top (
 // a ring shorter than the walker count only makes a walker that finishes early wait for the trees before its own.
 constexpr int kRegRows = 64;
 constexpr int kRegBytes = 32768;
-#ifndef TAHOE_R3_WALKERS
-#define TAHOE_R3_WALKERS 14
-#endif
-#ifndef TAHOE_R3_RING
-#define TAHOE_R3_RING 10
-#endif
-constexpr int kReg3Walkers = TAHOE_R3_WALKERS;
-constexpr int kReg3Ring = TAHOE_R3_RING;
+constexpr int kReg3Walkers = 14;
+constexpr int kReg3Ring = 10;
 constexpr int kQMaxTable = 32767;
 // LDS of the region form: K regions of 32 KiB, walker slots, ring
 inline long long qreg_lds_for(int k, int nwalk, int ring, bool code8 = false, int regb = kRegBytes)
@@ -98,33 +86,16 @@ inline long long qreg_lds_for(int k, int nwalk, int ring, bool code8 = false, in
 // u8 form: six chains (384-row tiles of three 128-row regions) for whole waves of workgroups, two chains (one region) for
 // the remainder; walkers / ring / consumer batch of the 384-row tile: 14 / 5 / 2 (96 KiB + 14 x 4 KiB + 5 x 1.5 KiB = 163,352 B); KR3
 // (profiles/r04/tune_q8.txt): 13 / 7 / 3 2.98 ms, 14 / 5 / 2 2.79, 12 / 10 / 4 2.96, 12 / 10 / 5 2.94
-#ifndef TAHOE_Q8_WALKERS
-#define TAHOE_Q8_WALKERS 14
-#endif
-#ifndef TAHOE_Q8_RING
-#define TAHOE_Q8_RING 5
-#endif
-#ifndef TAHOE_Q8_BATCH
-#define TAHOE_Q8_BATCH 2
-#endif
-constexpr int kReg8Walkers = TAHOE_Q8_WALKERS, kReg8Ring = TAHOE_Q8_RING, kReg8Batch = TAHOE_Q8_BATCH;
+constexpr int kReg8Walkers = 14, kReg8Ring = 5, kReg8Batch = 2;
 // top walk of the 384-row u8 tile / of the 192-row u16 tile: 1 = only the chosen child is read, after the compare (4 VALU + 2 LDS
 // per chain-level, two dependent LDS round trips), 0 = both children beside the feature read (5 VALU + 2 LDS, one round trip).
 // Measured (profiles/r04/tune_dep.txt): KR3's u8 walk 2.799 -> 2.731 ms, K3's u16 walk 3.469 -> 3.418 ms: on for both (round 2
 // measured "no faster" on the 128-row tile; with three / six chains per lane the second round trip hides behind the other chains)
-#ifndef TAHOE_Q8_DEP
-#define TAHOE_Q8_DEP 1
-#endif
-#ifndef TAHOE_R3_DEP
-#define TAHOE_R3_DEP 1
-#endif
-constexpr bool kReg8Dep = TAHOE_Q8_DEP != 0, kReg3Dep = TAHOE_R3_DEP != 0;
+constexpr bool kReg8Dep = true, kReg3Dep = true;
 constexpr int kReg3Batch = kReg3Ring >= 2 * kQBatch ? kQBatch : kReg3Ring / 2;  // consumer batch of the 192-row tile (the kernel's default rule)
-#ifndef TAHOE_Q8_COST
-#define TAHOE_Q8_COST 218  // time of a 384-row u8 tile in percent of a 128-row u8 tile: KR3, 983,040 rows, 10 waves of 384-row tiles 2.665 ms
-                           // against 30 waves of 128-row tiles 3.672 ms (profiles/r04/q8_cost.txt)
-#endif
-constexpr size_t kReg8Cost = TAHOE_Q8_COST;
+// time of a 384-row u8 tile in percent of a 128-row u8 tile: KR3, 983,040 rows, 10 waves of 384-row tiles 2.665 ms against 30 waves
+// of 128-row tiles 3.672 ms (profiles/r04/q8_cost.txt)
+constexpr size_t kReg8Cost = 218;
 // Region form: 192-row tiles (three chains, 14 walkers) take 1.33 x the time of 128-row tiles (two chains, 15 walkers),
 // i.e. 0.89 per row -- but a last, partly filled wave of workgroups costs a whole tile time.  A batch is therefore
 // walked as n whole waves of 192-row tiles followed by a remainder in whichever form is cheaper, n chosen to minimise
@@ -172,10 +143,9 @@ inline void qreg_plan(size_t rows, int num_cus, int force, size_t *rows3, int *c
         }
     }
 }
-#ifndef TAHOE_QUANT_MAX_SHIFT
-#define TAHOE_QUANT_MAX_SHIFT 16  // K3: 15 -> 0.907 ms, 16 -> 0.874 ms (half the table staging per row)
-#endif
-constexpr int kQuantMaxShift = TAHOE_QUANT_MAX_SHIFT;  // a quantise workgroup converts 2^cshift rows of its features; at most 65536
+// a quantise workgroup converts 2^cshift rows of its features; at most 65536 (K3: 15 -> 0.907 ms, 16 -> 0.874 ms: half the table
+// staging per row)
+constexpr int kQuantMaxShift = 16;
 constexpr int kQuantMinRowsPerBlock = 512;  // ... and the fewest
 constexpr int kQuantThreads = 512;
 constexpr uint32_t kCodeMissing = 0xFFFFu;

@@ -387,12 +387,9 @@ __global__ void __launch_bounds__(kQuantPairThreads)
     if (__ballot(saw_missing) != 0 && (threadIdx.x & 63) == 0) atomicOr(&chunk_flags[chunk], 1u);
 }
 
-// Features per workgroup of the many-features form: 4 x kQuantMultiMax at most (make QMULTI=4 keeps 16; 8 = 32 features: a row's
-// 32 values are one whole 128-byte line, read by eight adjacent lanes).
-#ifndef TAHOE_QUANT_MULTI_MAX
-#define TAHOE_QUANT_MULTI_MAX 4  // 32 features per workgroup measured slower (profiles/r04/tune_qmulti.txt: KR3 0.47 -> 0.61 ms, K2 0.94 -> 1.10)
-#endif
-constexpr int kQuantMultiMax = TAHOE_QUANT_MULTI_MAX;
+// Features per workgroup of the many-features form: 4 x kQuantMultiMax at most (8 = 32 features: a row's 32 values are one whole
+// 128-byte line, read by eight adjacent lanes -- measured slower, profiles/r04/tune_qmulti.txt: KR3 0.47 -> 0.61 ms, K2 0.94 -> 1.10).
+constexpr int kQuantMultiMax = 4;
 
 // ------------------------------------------------------------------------------------------------
 // host side

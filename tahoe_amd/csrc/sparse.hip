@@ -156,10 +156,7 @@ __global__ void __launch_bounds__(kBlock) sparse_kernel(const tahoe_sparse_node 
 // cannot be blocked; every spin is bounded and raises the error flag.
 constexpr int kSTop = 512;    // nodes per slot (8 B each)
 constexpr int kSRing = 32;    // ring entries (trees)
-#ifndef TAHOE_SPARSE_BATCH
-#define TAHOE_SPARSE_BATCH 4  // K5: 16 -> 5.34 ms, 8 -> 5.19, 4 -> 5.15
-#endif
-constexpr int kSBatch = TAHOE_SPARSE_BATCH;   // trees the consumer takes per poll
+constexpr int kSBatch = 4;    // trees the consumer takes per poll (K5: 16 -> 5.34 ms, 8 -> 5.19, 4 -> 5.15)
 constexpr int kSSpinLimit = 1 << 22;
 // MC: as sparse_kernel's, in the consumer wave.
 template <int NW, bool WRITE_LEAF, bool MC = false>
@@ -325,10 +322,7 @@ __global__ void __launch_bounds__(NW * 64) sparse_top_kernel(const uint2 *__rest
 // bit-identical to a sequential CPU sum.  Tree groups (a feature with more than 32767 distinct thresholds) chain their
 // sums like the dense form.
 constexpr int kSQLevels = 9;
-#ifndef TAHOE_SQ_DEP
-#define TAHOE_SQ_DEP 0  // 1: the top walk reads only the chosen child (make SQDEP=1; K5 measured in profiles/r04/tune_dep.txt)
-#endif
-constexpr bool kSparseQDep = TAHOE_SQ_DEP != 0;
+constexpr bool kSparseQDep = false;  // true: the top walk reads only the chosen child (K5 measured in profiles/r04/tune_dep.txt)
 // MC: the consumer of qring_kernel's MC form -- a group that starts inside class c continues its partial sum from
 // sums_in[row * num_classes + c], one that ends inside a class leaves its partial sum in sums.
 template <int NWALK, bool WRITE_LEAF, int K, int RING, bool MC = false>
@@ -647,23 +641,12 @@ static void sparse_q_launch_form(tahoe_forest *f, const tahoe_qgroup &g, float *
     if (grid == 0) return;
     const int lds = (int)qreg_lds_for(K, NWALK, RING);
     const int nc = f->num_classes;
-#define TAHOE_SPARSE_Q(LEAF_, MC_)                                                                                                  \
-    hipLaunchKernelGGL((sparse_q_kernel<NWALK, LEAF_, K, RING, MC_>), dim3(grid), dim3((NWALK + 1) * 64), lds, stream, f->q->xq,  \
-                       sp->qtop, sp->qblocks, sp->qblkoff, sp->qbotpos, sp->qblkpos, sp->ctrees, sp->corig, sums, leaf_out,       \
-                       rows_end, f->p.num_cols, g.tree_lo, g.num_trees, f->p.num_trees, f->q->chunk_flags, f->error_flag, sums_in, \
-                       cshift, row_begin, nc)
-    if (nc > 1) {
-        if (leaf_out)
-            TAHOE_SPARSE_Q(true, true);
-        else
-            TAHOE_SPARSE_Q(false, true);
-    } else {
-        if (leaf_out)
-            TAHOE_SPARSE_Q(true, false);
-        else
-            TAHOE_SPARSE_Q(false, false);
-    }
-#undef TAHOE_SPARSE_Q
+    with_leaf_mc(leaf_out != nullptr, nc > 1, [&](auto wl, auto mc) {
+        hipLaunchKernelGGL((sparse_q_kernel<NWALK, decltype(wl)::value, K, RING, decltype(mc)::value>), dim3(grid), dim3((NWALK + 1) * 64),
+                           lds, stream, f->q->xq, sp->qtop, sp->qblocks, sp->qblkoff, sp->qbotpos, sp->qblkpos, sp->ctrees, sp->corig,
+                           sums, leaf_out, rows_end, f->p.num_cols, g.tree_lo, g.num_trees, f->p.num_trees, f->q->chunk_flags,
+                           f->error_flag, sums_in, cshift, row_begin, nc);
+    });
 }
 
 // quantise + walk per tree group, in stream order; the tile plan of the dense region form (qreg_plan)
@@ -731,66 +714,31 @@ tahoe_status sparse_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, con
         if (nw == 0) return fail(TAHOE_ERR_UNSUPPORTED, "sparse TILEBLOCK: the compact form or its LDS tile is unavailable");
         const int lds = (int)sparse_top_lds(f, nw);
         const int nc = f->num_classes;
-#define TAHOE_SPARSE_TOP(NW_, LEAF_, MC_)                                                                                     \
-    hipLaunchKernelGGL((sparse_top_kernel<NW_, LEAF_, MC_>), dim3(grid), dim3(NW_ * 64), lds, stream, sp->cnodes, sp->ctrees, \
-                       sp->corig, data, sums, leaf_out, sums_in, rows, f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, f->error_flag, nc)
-        if (nc > 1) {
-            if (nw == 16) {
-                if (leaf_out)
-                    TAHOE_SPARSE_TOP(16, true, true);
-                else
-                    TAHOE_SPARSE_TOP(16, false, true);
-            } else {
-                if (leaf_out)
-                    TAHOE_SPARSE_TOP(8, true, true);
-                else
-                    TAHOE_SPARSE_TOP(8, false, true);
-            }
-        } else if (nw == 16) {
-            if (leaf_out)
-                TAHOE_SPARSE_TOP(16, true, false);
-            else
-                TAHOE_SPARSE_TOP(16, false, false);
-        } else {
-            if (leaf_out)
-                TAHOE_SPARSE_TOP(8, true, false);
-            else
-                TAHOE_SPARSE_TOP(8, false, false);
-        }
-#undef TAHOE_SPARSE_TOP
+        with_leaf_mc(leaf_out != nullptr, nc > 1, [&](auto wl, auto mc) {
+            auto launch = [&](auto nw_c) {
+                constexpr int NW = decltype(nw_c)::value;
+                hipLaunchKernelGGL((sparse_top_kernel<NW, decltype(wl)::value, decltype(mc)::value>), dim3(grid), dim3(NW * 64), lds,
+                                   stream, sp->cnodes, sp->ctrees, sp->corig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
+                                   f->p.num_trees, f->p.missing, vec4_ok, f->error_flag, nc);
+            };
+            if (nw == 16) launch(std::integral_constant<int, 16>{});
+            else launch(std::integral_constant<int, 8>{});
+        });
         TAHOE_HIP_TRY(hipGetLastError());
         return TAHOE_OK;
     }
     const bool tile = strategy == TAHOE_STRATEGY_ROWTILE;
     const int lds = (int)sparse_lds(f, tile);
     const int nc = f->num_classes;
-#define TAHOE_SPARSE_LAUNCH(TILE_, LEAF_, MC_)                                                                            \
-    hipLaunchKernelGGL((sparse_kernel<TILE_, LEAF_, MC_>), dim3(grid), dim3(kBlock), lds, stream, sp->nodes, sp->trees, data, \
-                       sums, leaf_out, sums_in, rows, f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, nc)
-    if (nc > 1) {
-        if (tile) {
-            if (leaf_out)
-                TAHOE_SPARSE_LAUNCH(true, true, true);
-            else
-                TAHOE_SPARSE_LAUNCH(true, false, true);
-        } else {
-            if (leaf_out)
-                TAHOE_SPARSE_LAUNCH(false, true, true);
-            else
-                TAHOE_SPARSE_LAUNCH(false, false, true);
-        }
-    } else if (tile) {
-        if (leaf_out)
-            TAHOE_SPARSE_LAUNCH(true, true, false);
-        else
-            TAHOE_SPARSE_LAUNCH(true, false, false);
-    } else {
-        if (leaf_out)
-            TAHOE_SPARSE_LAUNCH(false, true, false);
-        else
-            TAHOE_SPARSE_LAUNCH(false, false, false);
-    }
-#undef TAHOE_SPARSE_LAUNCH
+    with_leaf_mc(leaf_out != nullptr, nc > 1, [&](auto wl, auto mc) {
+        auto launch = [&](auto tile_c) {
+            hipLaunchKernelGGL((sparse_kernel<decltype(tile_c)::value, decltype(wl)::value, decltype(mc)::value>), dim3(grid), dim3(kBlock),
+                               lds, stream, sp->nodes, sp->trees, data, sums, leaf_out, sums_in, rows, f->p.num_cols, f->p.num_trees,
+                               f->p.missing, vec4_ok, nc);
+        };
+        if (tile) launch(std::true_type{});
+        else launch(std::false_type{});
+    });
     TAHOE_HIP_TRY(hipGetLastError());
     return TAHOE_OK;
 }
@@ -1022,13 +970,11 @@ static tahoe_status sparse_q_build(tahoe_forest *f, const std::vector<uint2> &cn
     if ((e = upload(&sp->qblocks, h_blocks, &f->device_bytes)) != hipSuccess) return bad("qblocks");
     if ((e = upload(&sp->qblkpos, h_blkpos, &f->device_bytes)) != hipSuccess) return bad("qblkpos");
     if ((e = upload(&sp->qblkoff, h_blkoff, &f->device_bytes)) != hipSuccess) return bad("qblkoff");
-    for (const void *k : {(const void *)&sparse_q_kernel<kReg3Walkers, false, 3, kReg3Ring>, (const void *)&sparse_q_kernel<kReg3Walkers, true, 3, kReg3Ring>,
-                          (const void *)&sparse_q_kernel<15, false, 2, kQRing>, (const void *)&sparse_q_kernel<15, true, 2, kQRing>,
-                          (const void *)&sparse_q_kernel<kReg3Walkers, false, 3, kReg3Ring, true>,
-                          (const void *)&sparse_q_kernel<kReg3Walkers, true, 3, kReg3Ring, true>,
-                          (const void *)&sparse_q_kernel<15, false, 2, kQRing, true>, (const void *)&sparse_q_kernel<15, true, 2, kQRing, true>})
-        if ((e = allow_max_lds(k, f->lds_limit)) != hipSuccess)
-            return fail(TAHOE_ERR_HIP, "sparse_q_build: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
+    if ((e = allow_max_lds_leaf([](auto wl) { return &sparse_q_kernel<kReg3Walkers, decltype(wl)::value, 3, kReg3Ring>; }, f->lds_limit)) != hipSuccess ||
+        (e = allow_max_lds_leaf([](auto wl) { return &sparse_q_kernel<15, decltype(wl)::value, 2, kQRing>; }, f->lds_limit)) != hipSuccess ||
+        (e = allow_max_lds_leaf([](auto wl) { return &sparse_q_kernel<kReg3Walkers, decltype(wl)::value, 3, kReg3Ring, true>; }, f->lds_limit)) != hipSuccess ||
+        (e = allow_max_lds_leaf([](auto wl) { return &sparse_q_kernel<15, decltype(wl)::value, 2, kQRing, true>; }, f->lds_limit)) != hipSuccess)
+        return fail(TAHOE_ERR_HIP, "sparse_q_build: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
     if ((e = quantize_allow_lds(f)) != hipSuccess)
         return fail(TAHOE_ERR_HIP, "sparse_q_build: hipFuncSetAttribute(quantise kernels) failed: %s", hipGetErrorString(e));
     return TAHOE_OK;
@@ -1140,13 +1086,8 @@ static tahoe_status create_sparse(tahoe_forest **out, const int32_t *trees, cons
     if ((e = hipMalloc(reinterpret_cast<void **>(&f->error_flag), sizeof(int))) != hipSuccess) return bail(e, "hipMalloc(error_flag)");
     if ((e = hipMemset(f->error_flag, 0, sizeof(int))) != hipSuccess) return bail(e, "hipMemset(error_flag)");
     if (sparse_tile_fits(f)) {
-        if ((e = allow_max_lds(reinterpret_cast<const void *>(&sparse_kernel<true, false>), f->lds_limit)) != hipSuccess)
-            return bail(e, "hipFuncSetAttribute(sparse)");
-        if ((e = allow_max_lds(reinterpret_cast<const void *>(&sparse_kernel<true, true>), f->lds_limit)) != hipSuccess)
-            return bail(e, "hipFuncSetAttribute(sparse)");
-        if (num_classes > 1 &&
-            ((e = allow_max_lds(reinterpret_cast<const void *>(&sparse_kernel<true, false, true>), f->lds_limit)) != hipSuccess ||
-             (e = allow_max_lds(reinterpret_cast<const void *>(&sparse_kernel<true, true, true>), f->lds_limit)) != hipSuccess))
+        if ((e = allow_max_lds_leaf([](auto wl) { return &sparse_kernel<true, decltype(wl)::value>; }, f->lds_limit)) != hipSuccess ||
+            (num_classes > 1 && (e = allow_max_lds_leaf([](auto wl) { return &sparse_kernel<true, decltype(wl)::value, true>; }, f->lds_limit)) != hipSuccess))
             return bail(e, "hipFuncSetAttribute(sparse)");
     }
     // ---- compact breadth-first copy (sparse_top_kernel) ----
@@ -1204,13 +1145,12 @@ static tahoe_status create_sparse(tahoe_forest **out, const int32_t *trees, cons
             if ((e = hipMemcpy(sp->ctrees, ct.data(), ct.size() * sizeof(int32_t), hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy(ctrees)");
             if ((e = hipMemcpy(sp->corig, orig.data(), orig.size() * sizeof(uint32_t), hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy(corig)");
             f->device_bytes += cn.size() * sizeof(uint2) + ct.size() * sizeof(int32_t) + orig.size() * sizeof(uint32_t);
-            for (const void *k : {(const void *)&sparse_top_kernel<16, false>, (const void *)&sparse_top_kernel<16, true>,
-                                  (const void *)&sparse_top_kernel<8, false>, (const void *)&sparse_top_kernel<8, true>})
-                if ((e = allow_max_lds(k, f->lds_limit)) != hipSuccess) return bail(e, "hipFuncSetAttribute(sparse_top)");
-            if (num_classes > 1)
-                for (const void *k : {(const void *)&sparse_top_kernel<16, false, true>, (const void *)&sparse_top_kernel<16, true, true>,
-                                      (const void *)&sparse_top_kernel<8, false, true>, (const void *)&sparse_top_kernel<8, true, true>})
-                    if ((e = allow_max_lds(k, f->lds_limit)) != hipSuccess) return bail(e, "hipFuncSetAttribute(sparse_top)");
+            if ((e = allow_max_lds_leaf([](auto wl) { return &sparse_top_kernel<16, decltype(wl)::value>; }, f->lds_limit)) != hipSuccess ||
+                (e = allow_max_lds_leaf([](auto wl) { return &sparse_top_kernel<8, decltype(wl)::value>; }, f->lds_limit)) != hipSuccess ||
+                (num_classes > 1 &&
+                 ((e = allow_max_lds_leaf([](auto wl) { return &sparse_top_kernel<16, decltype(wl)::value, true>; }, f->lds_limit)) != hipSuccess ||
+                  (e = allow_max_lds_leaf([](auto wl) { return &sparse_top_kernel<8, decltype(wl)::value, true>; }, f->lds_limit)) != hipSuccess)))
+                return bail(e, "hipFuncSetAttribute(sparse_top)");
             const tahoe_status qs = sparse_q_build(f, cn, ct);
             if (qs != TAHOE_OK) {
                 tahoe_forest_destroy(f);

@@ -280,9 +280,7 @@ void widef_destroy(tahoe_forest *f)
 template <int RT, int NWALK>
 static hipError_t wf_allow(int limit)
 {
-    hipError_t e = allow_max_lds(reinterpret_cast<const void *>(&widef_kernel<RT, NWALK, false>), limit);
-    if (e != hipSuccess) return e;
-    return allow_max_lds(reinterpret_cast<const void *>(&widef_kernel<RT, NWALK, true>), limit);
+    return allow_max_lds_leaf([](auto wl) { return &widef_kernel<RT, NWALK, decltype(wl)::value>; }, limit);
 }
 
 // Builds the tops and blocks of the wide float32 form when it is the only float32 tile kernel this shape can have (the caller
@@ -366,14 +364,11 @@ static void wf_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, const fl
     const tahoe_wstate *w = f->wf;
     const unsigned grid = (unsigned)((rows + RT - 1) / RT);
     const int lds = (int)wf_lds(f->p.num_cols, RT, NWALK, w->lw);
-    if (leaf_out)
-        hipLaunchKernelGGL((widef_kernel<RT, NWALK, true>), dim3(grid), dim3((NWALK + 1) * 64), lds, stream, data, w->ftop, w->fblocks,
-                           f->inner, f->leaf_orig, sums, leaf_out, sums_in, rows, f->p.num_cols, f->p.num_trees, f->depth, w->lw,
-                           w->tstride, f->p.missing, vec4_ok, f->error_flag);
-    else
-        hipLaunchKernelGGL((widef_kernel<RT, NWALK, false>), dim3(grid), dim3((NWALK + 1) * 64), lds, stream, data, w->ftop, w->fblocks,
-                           f->inner, f->leaf_orig, sums, leaf_out, sums_in, rows, f->p.num_cols, f->p.num_trees, f->depth, w->lw,
-                           w->tstride, f->p.missing, vec4_ok, f->error_flag);
+    with_leaf(leaf_out != nullptr, [&](auto wl) {
+        hipLaunchKernelGGL((widef_kernel<RT, NWALK, decltype(wl)::value>), dim3(grid), dim3((NWALK + 1) * 64), lds, stream, data,
+                           w->ftop, w->fblocks, f->inner, f->leaf_orig, sums, leaf_out, sums_in, rows, f->p.num_cols, f->p.num_trees,
+                           f->depth, w->lw, w->tstride, f->p.missing, vec4_ok, f->error_flag);
+    });
 }
 
 tahoe_status widef_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data, size_t rows, hipStream_t stream,

@@ -55,68 +55,25 @@
 
 namespace tahoe {
 
-#ifndef TAHOE_WK_LOADERS
-#define TAHOE_WK_LOADERS 4
-#endif
-#ifndef TAHOE_WK_WALKERS
-#define TAHOE_WK_WALKERS 11
-#endif
-constexpr int kWkLoaders = TAHOE_WK_LOADERS;  // loader waves (= the fewest row slots)
-constexpr int kWkWalkers = TAHOE_WK_WALKERS;  // walker waves; 4 loaders + 1 summer + 11 walkers = 16 waves (K2: 0.59 ms; 5 + 10: 0.60, 3 + 12: 0.62)
+constexpr int kWkLoaders = 4;   // loader waves (= the fewest row slots)
+constexpr int kWkWalkers = 11;  // walker waves; 4 loaders + 1 summer + 11 walkers = 16 waves (K2: 0.59 ms; 5 + 10: 0.60, 3 + 12: 0.62)
 constexpr int kWkSumRows = 64;                // rows the summer wave adds at once, one lane each
-#ifndef TAHOE_WK_CHAINS
-#define TAHOE_WK_CHAINS 2
-#endif
-constexpr int kWkChains = TAHOE_WK_CHAINS;  // 64-tree chunks of one row a walker wave walks at once (chains per lane; 3: 0.63 ms, 4: 0.61)
+constexpr int kWkChains = 2;  // 64-tree chunks of one row a walker wave walks at once (chains per lane; 3: 0.63 ms, 4: 0.61)
 constexpr int kWkSpinLimit = 1 << 22;
 constexpr uint32_t kWkMissing = 0xFFFFu;
 // Largest estimated share of compares with equal keys at which the create-time rule still takes this form (K2's uniform
 // thresholds: 1.6e-5, i.e. 0.1 % of the wave-levels on the float32 path; 1e-4 is ~0.6 % of them).
 constexpr float kWkTieLimit = 1.0e-4f;
 
-// Timing-only ablation builds (make ABLATE=n; results are wrong on purpose; never shipped): 1 = no bottom-block gathers,
-// 2 = walkers only pass the rows on, 3 = the loaders load nothing, 4 = the summer adds nothing; 5 = 2 + 4 (loaders alone),
-// 6 = 3 + 4 (walkers alone).
-#ifndef TAHOE_WS_ABLATE
-#define TAHOE_WS_ABLATE 0
-#endif
-// Non-temporal hints on the two read-once / write-once streams that share L2 with the bottom blocks (make WKNT=bits; an
-// experiment knob, profiles/r04/experiments.json): bit 0 = the loaders' row loads, bit 1 = the walkers' leaf-value stores and
-// the summer wave's loads of them.  Results are unchanged (only the cache policy of the instructions differs).
-#ifndef TAHOE_WK_NT
-#define TAHOE_WK_NT 1  // measured on K2 (profiles/r04/k2_nt.txt): row loads nt 0.597 -> 0.574 ms; leaf stores + summer loads nt 0.684 (worse)
-#endif
+// The loaders' row loads carry a non-temporal hint (a read-once stream that shares L2 with the bottom blocks; K2,
+// profiles/r04/k2_nt.txt: 0.597 -> 0.574 ms).  The same hint on the walkers' leaf-value stores and the summer wave's loads of
+// them was measured worse (0.684 ms): those stay plain.
 typedef float __attribute__((ext_vector_type(4))) wk_f4;  // (HIP's float4 is a struct: __builtin_nontemporal_load wants a native vector)
 __device__ __forceinline__ float4 wk_load_row16(const unsigned char *p)
 {
-#if TAHOE_WK_NT & 1
     const wk_f4 v = __builtin_nontemporal_load(reinterpret_cast<const wk_f4 *>(p));
     return make_float4(v.x, v.y, v.z, v.w);
-#else
-    return *reinterpret_cast<const float4 *>(p);
-#endif
 }
-__device__ __forceinline__ float4 wk_load_leaf16(const float *p)
-{
-#if TAHOE_WK_NT & 2
-    const wk_f4 v = __builtin_nontemporal_load(reinterpret_cast<const wk_f4 *>(p));
-    return make_float4(v.x, v.y, v.z, v.w);
-#else
-    return *reinterpret_cast<const float4 *>(p);
-#endif
-}
-__device__ __forceinline__ void wk_store_leaf(float *p, float v)
-{
-#if TAHOE_WK_NT & 2
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
-#define WK_NO_GATHER (TAHOE_WS_ABLATE == 1)
-#define WK_NO_WALK (TAHOE_WS_ABLATE == 2 || TAHOE_WS_ABLATE == 5)
-#define WK_NO_LOAD (TAHOE_WS_ABLATE == 3 || TAHOE_WS_ABLATE == 6)
-#define WK_NO_ADD (TAHOE_WS_ABLATE == 4 || TAHOE_WS_ABLATE == 5 || TAHOE_WS_ABLATE == 6)
 
 // The key of a non-missing value: NaN -> 0 (v_max_f32 returns its other operand), below lo -> 0, above hi -> 65534.
 __device__ __forceinline__ uint32_t wk_key(float x, float lo, float scale)
@@ -207,10 +164,7 @@ __global__ void __launch_bounds__((kWkLoaders + 1 + kWkWalkers) * 64)
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int off = min((c * 4 + u) * 1024 + lane * 16, row_bytes - 16);
-                r[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-#if !WK_NO_LOAD
                 r[u] = wk_load_row16(src + off);
-#endif
             }
         };
         uint64_t ms_seen = 0;  // a missing value among the keys of the row under way (any lane)
@@ -315,9 +269,8 @@ __global__ void __launch_bounds__((kWkLoaders + 1 + kWkWalkers) * 64)
                 const float *v = leafbuf + (r0 + k) * (size_t)tv;
                 float sum = sums_in ? sums_in[r0 + k] : 0.0f;
                 int t = 0;
-#if !WK_NO_ADD
                 for (; t + 8 <= num_trees; t += 8) {
-                    const float4 p = wk_load_leaf16(v + t), q = wk_load_leaf16(v + t + 4);
+                    const float4 p = *reinterpret_cast<const float4 *>(v + t), q = *reinterpret_cast<const float4 *>(v + t + 4);
                     sum += p.x;
                     sum += p.y;
                     sum += p.z;
@@ -328,7 +281,6 @@ __global__ void __launch_bounds__((kWkLoaders + 1 + kWkWalkers) * 64)
                     sum += q.w;
                 }
                 for (; t < num_trees; ++t) sum += v[t];
-#endif
                 sums[r0 + k] = sum;
             }
         }
@@ -410,9 +362,6 @@ __global__ void __launch_bounds__((kWkLoaders + 1 + kWkWalkers) * 64)
                 cbase[g] = 4u * (uint32_t)tt[J0 + g] - (4u << TSL);  // children of p: position 2p at ((2p - 1) << TSL) + tt dwords
                 node[g] = lw > 0 ? *reinterpret_cast<wk_lds_u32>(4u * (uint32_t)tt[J0 + g]) : 0u;
             }
-#if WK_NO_WALK
-            if (false)
-#endif
             if (lw > 0) {
                 for (int l = 0; l < lw - 1; ++l) {
                     // one LDS round trip per level: the feature key of the node and BOTH children (one tree stride apart)
@@ -440,10 +389,6 @@ __global__ void __launch_bounds__((kWkLoaders + 1 + kWkWalkers) * 64)
             constexpr int J0 = decltype(j0c)::value;
 #pragma unroll
             for (int j = J0; j < J0 + GS; ++j) {
-#if WK_NO_GATHER || WK_NO_WALK
-                bsel[j] = c0[j] = c1[j] = idx[j] = 0;
-                leaf[j] = __uint_as_float(p[j]);
-#else
                 idx[j] = p[j] - 1u;  // 0-based heap index on level lw
                 for (int l = lw; l < depth - 2; ++l) {  // the float32 rule on the heap records in global memory
                     const InnerNode nd = tree[j][idx[j]];
@@ -454,12 +399,10 @@ __global__ void __launch_bounds__((kWkLoaders + 1 + kWkWalkers) * 64)
                 const uint4 *bp = kblocks + ((size_t)tt[j] * n_blocks + bsel[j]) * 2;
                 qa[j] = bp[0];
                 qb[j] = bp[1];
-#endif
             }
         };
         auto bottom = [&](auto j0c) {
             constexpr int J0 = decltype(j0c)::value;
-#if !(WK_NO_GATHER || WK_NO_WALK)
 #pragma unroll
             for (int j = J0; j < J0 + GS; ++j) {
                 const bool r0b = __builtin_amdgcn_inverse_ballot_w64(right_mask(qa[j].x, xkey(qa[j].x), tree[j], idx[j]));
@@ -470,7 +413,6 @@ __global__ void __launch_bounds__((kWkLoaders + 1 + kWkWalkers) * 64)
                 const uint32_t lo = r0b ? qb[j].y : qa[j].w, hi = r0b ? qb[j].z : qb[j].x;
                 leaf[j] = __uint_as_float(r1b ? hi : lo);
             }
-#endif
         };
         top(std::integral_constant<int, 0>{});
         gather(std::integral_constant<int, 0>{});
@@ -482,7 +424,7 @@ __global__ void __launch_bounds__((kWkLoaders + 1 + kWkWalkers) * 64)
         if constexpr (KC > GS) bottom(std::integral_constant<int, GS>{});
 #pragma unroll
         for (int j = 0; j < KC; ++j) {
-            if (leafbuf && t[j] < num_trees) wk_store_leaf(&leafbuf[(r0 + k) * (size_t)tv + t[j]], leaf[j]);
+            if (leafbuf && t[j] < num_trees) leafbuf[(r0 + k) * (size_t)tv + t[j]] = leaf[j];
             if (WRITE_LEAF) {
                 if (t[j] < num_trees)
                     leaf_out[(r0 + k) * (size_t)num_trees + t[j]] =
