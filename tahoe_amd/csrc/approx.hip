@@ -120,11 +120,8 @@ static tahoe_status finish_build(tahoe_forest *f, tahoe_astate *ap, const std::v
     // the slab while two waves' slabs fit a CU: on K3 (F = 256, one 66-KB wave slab per workgroup) it takes 258 ms per 1 M rows
     // against 581 ms in place (profiles/approx_contribs), the read-modify-write of phi_dev costing more than the lost occupancy
     ap->slab = 2 * wave_bytes <= (size_t)f->lds_limit;
-    if (const char *e = getenv("TAHOE_APPROX_FORM")) {  // experiments: 1 = the LDS slab wherever one wave's slab fits, 2 = in place
-        const int v = atoi(e);
-        if (v == 1) ap->slab = wave_bytes <= (size_t)f->lds_limit;
-        if (v == 2) ap->slab = false;
-    }
+    if (f->knobs.approx_form == 1) ap->slab = wave_bytes <= (size_t)f->lds_limit;  // TAHOE_APPROX_FORM
+    if (f->knobs.approx_form == 2) ap->slab = false;
     ap->waves = ap->slab ? (int)std::max<size_t>(1, std::min<size_t>(4, kApproxSlabBudget / wave_bytes)) : 4;
     ap->lds_bytes = ap->slab ? ap->waves * wave_bytes : 0;
     hipError_t e;

@@ -726,7 +726,7 @@ static long long tileblock_lds_bytes(const tahoe_forest *f, int tile_rows)
 static int tileblock_rows(const tahoe_forest *f)
 {
     if (!f->has_blocks || f->p.num_cols < 1) return 0;
-    if (const int r = f->knob_tile_rows)  // TAHOE_TILE_ROWS, read at create
+    if (const int r = f->knobs.tile_rows)  // TAHOE_TILE_ROWS
         if ((r == 64 || r == 128) && tileblock_lds_bytes(f, r) <= f->lds_limit) return r;
     if (tileblock_lds_bytes(f, 128) <= f->lds_limit) return 128;
     if (tileblock_lds_bytes(f, 64) <= f->lds_limit) return 64;
@@ -745,7 +745,7 @@ static long long tilering_lds_bytes(const tahoe_forest *f, int tile_rows)
 static int tilering_rows(const tahoe_forest *f)
 {
     if (!f->has_blocks || f->p.num_cols < 1) return 0;
-    if (const int r = f->knob_tile_rows)  // TAHOE_TILE_ROWS, read at create
+    if (const int r = f->knobs.tile_rows)  // TAHOE_TILE_ROWS
         if ((r == 64 || r == 128) && tilering_lds_bytes(f, r) <= f->lds_limit) return r;
     if (tilering_lds_bytes(f, 64) <= f->lds_limit) return 64;
     return 0;
@@ -793,6 +793,35 @@ static int resolve_strategy(const tahoe_forest *f, size_t rows)
     return rowtile_fits(f) ? TAHOE_STRATEGY_ROWTILE : TAHOE_STRATEGY_DIRECT;
 }
 
+tahoe_status strategy_available(const tahoe_forest *f, int strategy)
+{
+    if (f->sp) {
+        if ((strategy > TAHOE_STRATEGY_TILEBLOCK && strategy != TAHOE_STRATEGY_QRING) ||
+            (strategy == TAHOE_STRATEGY_ROWTILE && !sparse_tile_fits(f)) ||
+            (strategy == TAHOE_STRATEGY_TILEBLOCK && sparse_top_waves(f) == 0) ||
+            (strategy == TAHOE_STRATEGY_QRING && !sparse_q_available(f)))
+            return fail(TAHOE_ERR_UNSUPPORTED,
+                        "a sparse forest runs AUTO, DIRECT, ROWTILE (a 64-row tile fits LDS), TILEBLOCK (tile + tree tops in LDS; "
+                        "trees of <= 65535 nodes, num_cols <= 32767) or QRING (quantised tile + tree tops; also num_cols <= 256)");
+        return TAHOE_OK;
+    }
+    if (f->num_classes > 1 && (strategy == TAHOE_STRATEGY_TILEBLOCK || strategy == TAHOE_STRATEGY_TILERING))
+        return fail(TAHOE_ERR_UNSUPPORTED, "a multi-class handle runs AUTO, DIRECT, ROWTILE or QRING (no float32 tile forms)");
+    if (strategy == TAHOE_STRATEGY_ROWTILE && !rowtile_fits(f))
+        return fail(TAHOE_ERR_UNSUPPORTED, "ROWTILE needs %d B of LDS for %d columns; device offers %d",
+                    rowtile_lds_bytes(f->p.num_cols, f->lds_levels), f->p.num_cols, f->lds_limit);
+    if (strategy == TAHOE_STRATEGY_TILEBLOCK && tileblock_rows(f) == 0)
+        return fail(TAHOE_ERR_UNSUPPORTED, "TILEBLOCK needs num_cols <= %d and a 64-row tile that fits %d B of LDS",
+                    kBlockMaxCols, f->lds_limit);
+    if (strategy == TAHOE_STRATEGY_TILERING && tilering_rows(f) == 0 && widef_rows(f) == 0)
+        return fail(TAHOE_ERR_UNSUPPORTED, "TILERING needs a 64-row tile (num_cols <= %d) or an 8-row tile that fits %d B of LDS",
+                    kBlockMaxCols, f->lds_limit);
+    if (strategy == TAHOE_STRATEGY_QRING && qring_walkers(f) == 0)
+        return fail(TAHOE_ERR_UNSUPPORTED,
+                    "QRING needs <= 32767 distinct thresholds per feature, num_cols <= 32767 and a 128-row u16 tile in LDS");
+    return TAHOE_OK;
+}
+
 template <int ROWS>
 static void launch_tileblock(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *sums_in, const float *data, size_t rows,
                              hipStream_t stream, int vec4_ok)
@@ -830,6 +859,7 @@ static tahoe_status launch_traversal(tahoe_forest *f, float *sums, uint32_t *lea
     DeviceGuard on_device(f->device);
     const int strategy = resolve_strategy(f, rows);
     if ((rows + 63) / 64 > 0x7fffffffu) return fail(TAHOE_ERR_INVALID_ARG, "too many rows for one launch: %zu", rows);
+    if (const tahoe_status s = strategy_available(f, strategy)) return s;  // (set_strategy has refused it already)
     const bool timed = f->profiling && f->prof_count < f->ev_start.size();
     if (timed) TAHOE_HIP_TRY(hipEventRecord(f->ev_start[f->prof_count], stream));
     bool mid_recorded = false;
@@ -846,8 +876,6 @@ static tahoe_status launch_traversal(tahoe_forest *f, float *sums, uint32_t *lea
             TAHOE_HIP_TRY(hipMemcpyAsync(sums, sums_in, rows * sizeof(float), hipMemcpyDeviceToDevice, stream));
         else if (sums && !sums_in)
             TAHOE_HIP_TRY(hipMemsetAsync(sums, 0, rows * (size_t)f->num_classes * sizeof(float), stream));
-    } else if (!f->sp && f->num_classes > 1 && (strategy == TAHOE_STRATEGY_TILERING || strategy == TAHOE_STRATEGY_TILEBLOCK)) {
-        return fail(TAHOE_ERR_UNSUPPORTED, "the float32 tile forms (TILEBLOCK, TILERING) do not serve multi-class handles");
     } else if (f->sp) {
         const tahoe_status ss = sparse_launch(f, sums, leaf_out, data, rows, stream, strategy, sums_in);
         if (ss != TAHOE_OK) return ss;
@@ -859,29 +887,18 @@ static tahoe_status launch_traversal(tahoe_forest *f, float *sums, uint32_t *lea
         const tahoe_status ws = widef_launch(f, sums, leaf_out, data, rows, stream, sums_in);  // rows too wide for a 64-row tile
         if (ws != TAHOE_OK) return ws;
     } else if (strategy == TAHOE_STRATEGY_TILERING) {
-        const int tr = tilering_rows(f);
-        if (tr == 0)
-            return fail(TAHOE_ERR_UNSUPPORTED, "TILERING needs a 64-row tile (num_cols <= %d) or an 8-row tile that fits %d B of LDS",
-                        kBlockMaxCols, f->lds_limit);
-        if (tr == 128)
+        if (tilering_rows(f) == 128)
             launch_tilering<128, 4>(f, sums, leaf_out, sums_in, data, rows, stream, vec4_ok);
         else
             launch_tilering<64, 8>(f, sums, leaf_out, sums_in, data, rows, stream, vec4_ok);
         TAHOE_HIP_TRY(hipGetLastError());
     } else if (strategy == TAHOE_STRATEGY_TILEBLOCK) {
-        const int tr = tileblock_rows(f);
-        if (tr == 0)
-            return fail(TAHOE_ERR_UNSUPPORTED, "TILEBLOCK needs num_cols <= %d and a 64-row tile that fits %d B of LDS",
-                        kBlockMaxCols, f->lds_limit);
-        if (tr == 128)
+        if (tileblock_rows(f) == 128)
             launch_tileblock<128>(f, sums, leaf_out, sums_in, data, rows, stream, vec4_ok);
         else
             launch_tileblock<64>(f, sums, leaf_out, sums_in, data, rows, stream, vec4_ok);
         TAHOE_HIP_TRY(hipGetLastError());
     } else if (strategy == TAHOE_STRATEGY_ROWTILE) {
-        if (!rowtile_fits(f))
-            return fail(TAHOE_ERR_UNSUPPORTED, "ROWTILE needs %d B of LDS for %d columns; device offers %d",
-                        rowtile_lds_bytes(f->p.num_cols, f->lds_levels), f->p.num_cols, f->lds_limit);
         const size_t grid = (rows + kTileRows - 1) / kTileRows;
         const int lds = rowtile_lds_bytes(f->p.num_cols, f->lds_levels);
         const int nc = f->num_classes;
@@ -941,6 +958,108 @@ static int reference_bits_bytes(int max_fid)
     return len == 0 ? 1 : (len == 1 ? 2 : 4);
 }
 
+tahoe_status check_params(const tahoe_forest_params *p, int num_classes, bool have_nodes, const char *nodes)
+{
+    if (p->num_trees < 0) return fail(TAHOE_ERR_INVALID_ARG, "num_trees must be non-negative");
+    if (p->num_cols < 0) return fail(TAHOE_ERR_INVALID_ARG, "num_cols must be non-negative");
+    if ((p->output & ~(TAHOE_OUT_AVG | TAHOE_OUT_SIGMOID | TAHOE_OUT_THRESHOLD | (num_classes > 1 ? TAHOE_OUT_SOFTMAX : 0))) != 0)
+        return fail(TAHOE_ERR_INVALID_ARG, "output should be a combination of RAW, AVG, SIGMOID and THRESHOLD");
+    if (p->num_trees > 0 && !have_nodes) return fail(TAHOE_ERR_INVALID_ARG, "%s is null", nodes);
+    return TAHOE_OK;
+}
+
+tahoe_status check_classes(const tahoe_forest_params *p, int num_classes)
+{
+    if (num_classes < 1 || num_classes > 1024) return fail(TAHOE_ERR_INVALID_ARG, "num_classes must be in [1,1024], got %d", num_classes);
+    if (p->num_trees < 0 || p->num_trees % num_classes != 0)
+        return fail(TAHOE_ERR_INVALID_ARG, "num_trees (%d) must be a non-negative multiple of num_classes (%d)", p->num_trees, num_classes);
+    if ((p->output & TAHOE_OUT_SOFTMAX) != 0 && num_classes == 1)
+        return fail(TAHOE_ERR_INVALID_ARG, "SOFTMAX needs num_classes > 1");
+    if ((p->output & TAHOE_OUT_SOFTMAX) != 0 && (p->output & TAHOE_OUT_SIGMOID) != 0)
+        return fail(TAHOE_ERR_INVALID_ARG, "SOFTMAX and SIGMOID exclude each other");
+    if ((p->output & TAHOE_OUT_THRESHOLD) != 0 && num_classes > 1)
+        return fail(TAHOE_ERR_INVALID_ARG, "THRESHOLD needs num_classes == 1");
+    return TAHOE_OK;
+}
+
+// The one reader of the handle knobs (struct tahoe_knobs)
+static tahoe_knobs read_knobs()
+{
+    auto num = [](const char *name, int unset) {
+        const char *e = getenv(name);
+        return e ? atoi(e) : unset;
+    };
+    auto on = [&](const char *name) { return num(name, 1) != 0; };  // the knobs that "= 0" turns off
+    tahoe_knobs k;
+    k.lds_levels = num("TAHOE_LDS_LEVELS", k.lds_levels);
+    k.tile_rows = num("TAHOE_TILE_ROWS", k.tile_rows);
+    k.qring_walkers = num("TAHOE_QRING_WALKERS", k.qring_walkers);
+    k.qring_chains = num("TAHOE_QRING_CHAINS", k.qring_chains);
+    k.qring_slices = num("TAHOE_QRING_SLICES", k.qring_slices);
+    k.qring_groups = num("TAHOE_QRING_GROUPS", k.qring_groups);
+    k.qring_wide_chains = num("TAHOE_QRING_WIDE_CHAINS", k.qring_wide_chains);
+    k.qring_wide = on("TAHOE_QRING_WIDE");
+    k.qring_narrow = on("TAHOE_QRING_NARROW");
+    k.qring_regions = on("TAHOE_QRING_REGIONS");
+    k.qring_code8 = on("TAHOE_QRING_CODE8");
+    k.qring_narrow128 = on("TAHOE_QRING_NARROW128");
+    k.quant_buckets = on("TAHOE_QUANT_BUCKETS");
+    k.quant_multi = on("TAHOE_QUANT_MULTI");
+    k.sparse_qring = on("TAHOE_SPARSE_QRING");
+    k.widef = on("TAHOE_WIDEF");
+    k.wstream = num("TAHOE_WSTREAM", k.wstream);
+    k.wstream_slab_mb = num("TAHOE_WSTREAM_SLAB_MB", k.wstream_slab_mb);
+    k.approx_form = num("TAHOE_APPROX_FORM", k.approx_form);
+    return k;
+}
+
+tahoe_status open_handle(const tahoe_forest_params *p, int num_classes, ForestPtr &f)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail(TAHOE_ERR_NO_DEVICE, "no HIP device is visible; libtahoe_amd has no CPU path");
+    int dev = 0;
+    TAHOE_HIP_TRY(hipGetDevice(&dev));
+    hipDeviceProp_t prop;
+    TAHOE_HIP_TRY(hipGetDeviceProperties(&prop, dev));
+    f.reset(new (std::nothrow) tahoe_forest());
+    if (!f) return fail(TAHOE_ERR_NO_MEMORY, "tahoe_forest_create");
+    f->p = *p;
+    f->num_classes = num_classes;
+    f->class_trees = p->num_trees / num_classes;
+    f->device = dev;
+    f->num_cus = prop.multiProcessorCount;
+    f->lds_limit = (int)prop.maxSharedMemoryPerMultiProcessor > 0 ? (int)prop.maxSharedMemoryPerMultiProcessor
+                                                                   : (int)prop.sharedMemPerBlock;
+    f->knobs = read_knobs();
+    if (const tahoe_status s = hip_status(hipMalloc(reinterpret_cast<void **>(&f->error_flag), sizeof(int)), "hipMalloc(error_flag)"))
+        return s;
+    return hip_status(hipMemset(f->error_flag, 0, sizeof(int)), "hipMemset(error_flag)");
+}
+
+// The float32 kernels of a dense handle that may need more than the default 64 KiB of dynamic LDS: every form its shape can take
+static tahoe_status allow_float32_lds(const tahoe_forest *f)
+{
+    const int lim = f->lds_limit;
+    hipError_t e = hipSuccess;
+    if (rowtile_fits(f) &&
+        ((e = allow_max_lds_leaf([](auto wl) { return &rowtile_kernel<decltype(wl)::value>; }, lim)) != hipSuccess ||
+         (f->num_classes > 1 && (e = allow_max_lds_leaf([](auto wl) { return &rowtile_kernel<decltype(wl)::value, true>; }, lim)) != hipSuccess)))
+        return hip_status(e, "hipFuncSetAttribute(rowtile)");
+    if (!f->has_blocks) return TAHOE_OK;
+    if ((tileblock_lds_bytes(f, 128) <= lim &&
+         (e = allow_max_lds_leaf([](auto wl) { return &tileblock_kernel<128, decltype(wl)::value>; }, lim)) != hipSuccess) ||
+        (tileblock_lds_bytes(f, 64) <= lim &&
+         (e = allow_max_lds_leaf([](auto wl) { return &tileblock_kernel<64, decltype(wl)::value>; }, lim)) != hipSuccess))
+        return hip_status(e, "hipFuncSetAttribute(tileblock)");
+    if ((tilering_lds_bytes(f, 64) <= lim &&
+         (e = allow_max_lds_leaf([](auto wl) { return &tilering_kernel<64, 8, decltype(wl)::value>; }, lim)) != hipSuccess) ||
+        (tilering_lds_bytes(f, 128) <= lim &&
+         (e = allow_max_lds_leaf([](auto wl) { return &tilering_kernel<128, 4, decltype(wl)::value>; }, lim)) != hipSuccess))
+        return hip_status(e, "hipFuncSetAttribute(tilering)");
+    return TAHOE_OK;
+}
+
 }  // namespace tahoe
 
 using namespace tahoe;
@@ -963,50 +1082,25 @@ static tahoe_status create_dense(tahoe_forest **out, const tahoe_dense_node *nod
     if ((flags & ~(unsigned)(TAHOE_CREATE_PROB_RELAYOUT | TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS)) != 0)
         return fail(TAHOE_ERR_INVALID_ARG, "unknown create flags 0x%x", flags);
     *out = nullptr;
-    // check_params, BaseTahoeTest.h:490-516
     if (p->depth < 0 || p->depth > 30) return fail(TAHOE_ERR_INVALID_ARG, "depth must be in [0,30], got %d", p->depth);
-    if (p->num_trees < 0) return fail(TAHOE_ERR_INVALID_ARG, "num_trees must be non-negative");
-    if (p->num_cols < 0) return fail(TAHOE_ERR_INVALID_ARG, "num_cols must be non-negative");
     if (p->algo < TAHOE_ALGO_NAIVE || p->algo > TAHOE_ALGO_BATCH_TREE_REORG)
         return fail(TAHOE_ERR_INVALID_ARG, "algo should be NAIVE, TREE_REORG or BATCH_TREE_REORG");
-    if ((p->output & ~(TAHOE_OUT_AVG | TAHOE_OUT_SIGMOID | TAHOE_OUT_THRESHOLD | (num_classes > 1 ? TAHOE_OUT_SOFTMAX : 0))) != 0)
-        return fail(TAHOE_ERR_INVALID_ARG, "output should be a combination of RAW, AVG, SIGMOID and THRESHOLD");
-    if (p->num_trees > 0 && !nodes) return fail(TAHOE_ERR_INVALID_ARG, "nodes is null");
+    if (const tahoe_status s = check_params(p, num_classes, nodes != nullptr, "nodes")) return s;
     if (flags & (TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS)) {  // the cover weights, on the caller's nodes, before a device is touched
         const tahoe_status cs = contribs_validate(nodes, p);
         if (cs != TAHOE_OK) return cs;
     }
 
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(TAHOE_ERR_NO_DEVICE, "no HIP device is visible; libtahoe_amd has no CPU path");
-    int dev = 0;
-    TAHOE_HIP_TRY(hipGetDevice(&dev));
-    hipDeviceProp_t prop;
-    TAHOE_HIP_TRY(hipGetDeviceProperties(&prop, dev));
-
-    tahoe_forest *f = new (std::nothrow) tahoe_forest();
-    if (!f) return fail(TAHOE_ERR_NO_MEMORY, "tahoe_forest_create");
+    ForestPtr f;
+    if (const tahoe_status s = open_handle(p, num_classes, f)) return s;
     const int D = p->depth;             // depth of the trees as given
     const int De = std::max(D, 2);      // depth of the normalised trees
-    f->p = *p;
-    f->num_classes = num_classes;
-    f->class_trees = p->num_trees / num_classes;
     f->depth = De;
     f->n_inner = ((size_t)1 << De) - 1;
     f->n_leaf = (size_t)1 << De;
-    f->device = dev;
-    f->num_cus = prop.multiProcessorCount;
-    f->lds_limit = (int)prop.maxSharedMemoryPerMultiProcessor > 0 ? (int)prop.maxSharedMemoryPerMultiProcessor
-                                                                   : (int)prop.sharedMemPerBlock;
-    f->lds_levels = std::min(De, kMaxLdsLevels);
-    f->top_levels = std::min(De - 2, kTopLevelsMax);
-    if (const char *e = getenv("TAHOE_LDS_LEVELS")) {  // tuning knob for experiments; never raises the caps
-        f->lds_levels = std::max(0, std::min(f->lds_levels, atoi(e)));
-        f->top_levels = std::max(0, std::min(f->top_levels, atoi(e)));
-    }
-    if (const char *e = getenv("TAHOE_TILE_ROWS")) f->knob_tile_rows = atoi(e);
-    if (const char *e = getenv("TAHOE_QRING_WALKERS")) f->knob_qring_walkers = atoi(e);
+    // (TAHOE_LDS_LEVELS never raises the caps)
+    f->lds_levels = std::max(0, std::min({De, kMaxLdsLevels, f->knobs.lds_levels}));
+    f->top_levels = std::max(0, std::min({De - 2, kTopLevelsMax, f->knobs.lds_levels}));
     f->relayout = (flags & TAHOE_CREATE_PROB_RELAYOUT) != 0;
     // the float32 top / block views pack fid and def_left into 10 / 16 bits: no room for the exchange bit
     f->has_blocks = p->num_cols <= kBlockMaxCols && !f->relayout;
@@ -1085,7 +1179,6 @@ static tahoe_status create_dense(tahoe_forest **out, const tahoe_dense_node *nod
     });
     if (!bad_of.empty()) {
         const Bad bad = *std::min_element(bad_of.begin(), bad_of.end(), [](const Bad &x, const Bad &y) { return x.tree < y.tree; });
-        delete f;
         if (bad.kind == 1)
             return fail(TAHOE_ERR_INVALID_FOREST,
                         "tree %zu: reachable bottom-level node %zu is not a leaf (the reference would walk out of the tree)",
@@ -1178,74 +1271,20 @@ static tahoe_status create_dense(tahoe_forest **out, const tahoe_dense_node *nod
         });
     }
 
-    auto bail = [&](hipError_t e, const char *what) {
-        tahoe_forest_destroy(f);
-        return fail(TAHOE_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
-    };
-    hipError_t e;
-    if ((e = upload(&f->inner, h_inner, &f->device_bytes)) != hipSuccess) return bail(e, "upload(inner)");
-    if ((e = upload(&f->leaf_val, h_leaf, &f->device_bytes)) != hipSuccess) return bail(e, "upload(leaf_val)");
-    if ((e = upload(&f->leaf_orig, h_orig, &f->device_bytes)) != hipSuccess) return bail(e, "upload(leaf_orig)");
-    if (f->has_blocks) {
-        if ((e = upload(&f->top, h_top, &f->device_bytes)) != hipSuccess) return bail(e, "upload(top)");
-        if ((e = upload(&f->blocks, h_blocks, &f->device_bytes)) != hipSuccess) return bail(e, "upload(blocks)");
-    }
-
-    // Kernels that may need more than the default 64 KiB of dynamic LDS.
-    if (rowtile_fits(f)) {
-        if ((e = allow_max_lds_leaf([](auto wl) { return &rowtile_kernel<decltype(wl)::value>; }, f->lds_limit)) != hipSuccess ||
-            (num_classes > 1 && (e = allow_max_lds_leaf([](auto wl) { return &rowtile_kernel<decltype(wl)::value, true>; }, f->lds_limit)) != hipSuccess))
-            return bail(e, "hipFuncSetAttribute(rowtile)");
-    }
-    if (f->has_blocks && tileblock_lds_bytes(f, 128) <= f->lds_limit) {
-        if ((e = allow_max_lds_leaf([](auto wl) { return &tileblock_kernel<128, decltype(wl)::value>; }, f->lds_limit)) != hipSuccess)
-            return bail(e, "hipFuncSetAttribute(tileblock)");
-    }
-    if ((e = hipMalloc(reinterpret_cast<void **>(&f->error_flag), sizeof(int))) != hipSuccess)
-        return bail(e, "hipMalloc(error_flag)");
-    if ((e = hipMemset(f->error_flag, 0, sizeof(int))) != hipSuccess) return bail(e, "hipMemset(error_flag)");
-    {
-        const tahoe_status qs = qring_build(f, h_inner, h_real, h_leaf);
-        if (qs != TAHOE_OK) {
-            tahoe_forest_destroy(f);
-            return qs;
-        }
-    }
-    if (tilering_rows(f) == 0 && tileblock_rows(f) == 0) {  // no 64-row float32 tile kernel for this shape: the wide-row form
-        const tahoe_status ws = widef_build(f, h_inner, h_real, h_leaf);
-        if (ws != TAHOE_OK) {
-            tahoe_forest_destroy(f);
-            return ws;
-        }
-    }
-    if (f->has_blocks && tilering_lds_bytes(f, 64) <= f->lds_limit) {
-        if ((e = allow_max_lds_leaf([](auto wl) { return &tilering_kernel<64, 8, decltype(wl)::value>; }, f->lds_limit)) != hipSuccess)
-            return bail(e, "hipFuncSetAttribute(tilering)");
-    }
-    if (f->has_blocks && tilering_lds_bytes(f, 128) <= f->lds_limit) {
-        if ((e = allow_max_lds_leaf([](auto wl) { return &tilering_kernel<128, 4, decltype(wl)::value>; }, f->lds_limit)) != hipSuccess)
-            return bail(e, "hipFuncSetAttribute(tilering)");
-    }
-    if (f->has_blocks && tileblock_lds_bytes(f, 64) <= f->lds_limit) {
-        if ((e = allow_max_lds_leaf([](auto wl) { return &tileblock_kernel<64, decltype(wl)::value>; }, f->lds_limit)) != hipSuccess)
-            return bail(e, "hipFuncSetAttribute(tileblock)");
-    }
-    if (flags & TAHOE_CREATE_CONTRIBS) {
-        const tahoe_status cs = contribs_build(f, nodes);
-        if (cs != TAHOE_OK) {
-            tahoe_forest_destroy(f);
-            return cs;
-        }
-    }
-    if (flags & TAHOE_CREATE_APPROX_CONTRIBS) {  // the Saabas records of the final (class-major, re-laid-out) layout
-        const tahoe_status as = approx_build(f, nodes, h_inner, h_real);
-        if (as != TAHOE_OK) {
-            tahoe_forest_destroy(f);
-            return as;
-        }
-    }
-    *out = f;
-    return TAHOE_OK;
+    tahoe_status s;
+    if ((s = hip_status(upload(&f->inner, h_inner, &f->device_bytes), "upload(inner)")) ||
+        (s = hip_status(upload(&f->leaf_val, h_leaf, &f->device_bytes), "upload(leaf_val)")) ||
+        (s = hip_status(upload(&f->leaf_orig, h_orig, &f->device_bytes), "upload(leaf_orig)")))
+        return s;
+    if (f->has_blocks && ((s = hip_status(upload(&f->top, h_top, &f->device_bytes), "upload(top)")) ||
+                          (s = hip_status(upload(&f->blocks, h_blocks, &f->device_bytes), "upload(blocks)"))))
+        return s;
+    if ((s = allow_float32_lds(f.get())) || (s = qring_build(f.get(), h_inner, h_real, h_leaf))) return s;
+    // no 64-row float32 tile kernel for this shape: the wide-row form
+    if (tilering_rows(f.get()) == 0 && tileblock_rows(f.get()) == 0 && (s = widef_build(f.get(), h_inner, h_real, h_leaf))) return s;
+    // contributions from the caller's nodes, the Saabas records of the final (class-major, re-laid-out) layout
+    return finish_create(f, flags, out, [&] { return contribs_build(f.get(), nodes); },
+                         [&] { return approx_build(f.get(), nodes, h_inner, h_real); });
 }
 
 tahoe_status tahoe_forest_create_ex(tahoe_forest **out, const tahoe_dense_node *nodes, const tahoe_forest_params *p, unsigned flags)
@@ -1259,15 +1298,7 @@ tahoe_status tahoe_forest_create_multiclass(tahoe_forest **out, const tahoe_dens
     // every check here runs before a device is touched
     if (!out || !p) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_create_multiclass: null argument");
     *out = nullptr;
-    if (num_classes < 1 || num_classes > 1024) return fail(TAHOE_ERR_INVALID_ARG, "num_classes must be in [1,1024], got %d", num_classes);
-    if (p->num_trees < 0 || p->num_trees % num_classes != 0)
-        return fail(TAHOE_ERR_INVALID_ARG, "num_trees (%d) must be a non-negative multiple of num_classes (%d)", p->num_trees, num_classes);
-    if ((p->output & TAHOE_OUT_SOFTMAX) != 0 && num_classes == 1)
-        return fail(TAHOE_ERR_INVALID_ARG, "SOFTMAX needs num_classes > 1");
-    if ((p->output & TAHOE_OUT_SOFTMAX) != 0 && (p->output & TAHOE_OUT_SIGMOID) != 0)
-        return fail(TAHOE_ERR_INVALID_ARG, "SOFTMAX and SIGMOID exclude each other");
-    if ((p->output & TAHOE_OUT_THRESHOLD) != 0 && num_classes > 1)
-        return fail(TAHOE_ERR_INVALID_ARG, "THRESHOLD needs num_classes == 1");
+    if (const tahoe_status s = check_classes(p, num_classes)) return s;
     return create_dense(out, nodes, p, flags, num_classes);
 }
 
@@ -1345,31 +1376,7 @@ tahoe_status tahoe_forest_set_strategy(tahoe_forest *f, int strategy)
     if (!f) return fail(TAHOE_ERR_INVALID_ARG, "null forest");
     if (strategy < TAHOE_STRATEGY_AUTO || strategy > TAHOE_STRATEGY_QRING)
         return fail(TAHOE_ERR_INVALID_ARG, "unknown strategy %d", strategy);
-    if (f->sp) {
-        if ((strategy > TAHOE_STRATEGY_TILEBLOCK && strategy != TAHOE_STRATEGY_QRING) ||
-            (strategy == TAHOE_STRATEGY_ROWTILE && !sparse_tile_fits(f)) ||
-            (strategy == TAHOE_STRATEGY_TILEBLOCK && sparse_top_waves(f) == 0) ||
-            (strategy == TAHOE_STRATEGY_QRING && !sparse_q_available(f)))
-            return fail(TAHOE_ERR_UNSUPPORTED,
-                        "a sparse forest runs AUTO, DIRECT, ROWTILE (a 64-row tile fits LDS), TILEBLOCK (tile + tree tops in LDS; "
-                        "trees of <= 65535 nodes, num_cols <= 32767) or QRING (quantised tile + tree tops; also num_cols <= 256)");
-        f->strategy = strategy;
-        return TAHOE_OK;
-    }
-    if (f->num_classes > 1 && (strategy == TAHOE_STRATEGY_TILEBLOCK || strategy == TAHOE_STRATEGY_TILERING))
-        return fail(TAHOE_ERR_UNSUPPORTED, "a multi-class handle runs AUTO, DIRECT, ROWTILE or QRING (no float32 tile forms)");
-    if (strategy == TAHOE_STRATEGY_ROWTILE && !rowtile_fits(f))
-        return fail(TAHOE_ERR_UNSUPPORTED, "ROWTILE needs %d B of LDS for %d columns; device offers %d",
-                    rowtile_lds_bytes(f->p.num_cols, f->lds_levels), f->p.num_cols, f->lds_limit);
-    if (strategy == TAHOE_STRATEGY_TILEBLOCK && tileblock_rows(f) == 0)
-        return fail(TAHOE_ERR_UNSUPPORTED, "TILEBLOCK needs num_cols <= %d and a 64-row tile that fits %d B of LDS",
-                    kBlockMaxCols, f->lds_limit);
-    if (strategy == TAHOE_STRATEGY_TILERING && tilering_rows(f) == 0 && widef_rows(f) == 0)
-        return fail(TAHOE_ERR_UNSUPPORTED, "TILERING needs a 64-row tile (num_cols <= %d) or an 8-row tile that fits %d B of LDS",
-                    kBlockMaxCols, f->lds_limit);
-    if (strategy == TAHOE_STRATEGY_QRING && qring_walkers(f) == 0)
-        return fail(TAHOE_ERR_UNSUPPORTED,
-                    "QRING needs <= 32767 distinct thresholds per feature, num_cols <= 32767 and a 128-row u16 tile in LDS");
+    if (const tahoe_status s = strategy_available(f, strategy)) return s;
     f->strategy = strategy;
     return TAHOE_OK;
 }
@@ -1435,24 +1442,16 @@ tahoe_status tahoe_forest_get_info(const tahoe_forest *f, tahoe_forest_info *inf
     if (!f || !info) return fail(TAHOE_ERR_INVALID_ARG, "null argument");
     memset(info, 0, sizeof(*info));
     info->is_sparse = f->sp != nullptr;
-    if (f->sp) {
-        info->num_trees = f->p.num_trees;
-        info->num_cols = f->p.num_cols;
-        info->bits_bytes = f->bits_bytes;
-        info->device_bytes = f->device_bytes;
-        info->device_id = f->device;
-        info->num_cus = f->num_cus;
-        return TAHOE_OK;
-    }
     info->num_trees = f->p.num_trees;
-    info->depth = f->p.depth;
     info->num_cols = f->p.num_cols;
     info->bits_bytes = f->bits_bytes;
-    info->lds_levels = f->lds_levels;
     info->device_bytes = f->device_bytes;
-    info->lds_bytes_per_block = rowtile_fits(f) ? rowtile_lds_bytes(f->p.num_cols, f->lds_levels) : 0;
     info->device_id = f->device;
     info->num_cus = f->num_cus;
+    if (f->sp) return TAHOE_OK;
+    info->depth = f->p.depth;
+    info->lds_levels = f->lds_levels;
+    info->lds_bytes_per_block = rowtile_fits(f) ? rowtile_lds_bytes(f->p.num_cols, f->lds_levels) : 0;
     info->top_levels = f->top_levels;
     info->tile_rows = tileblock_rows(f);
     info->tileblock_lds_bytes = info->tile_rows ? (int)tileblock_lds_bytes(f, info->tile_rows) : 0;

@@ -4,7 +4,9 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cstdint>
+#include <memory>
 #include <type_traits>
 #include <vector>
 
@@ -52,6 +54,31 @@ static inline int top_stride_bytes(int top_levels)
 
 }  // namespace tahoe
 
+// Tuning knobs for experiments: environment variables read ONCE per handle, by open_handle (never on the predict path).  A field
+// holds atoi of its variable (a bool: atoi != 0), or the default below when the variable is unset; a knob touches only the forms
+// named beside it.  tools/README.md lists the same table.
+struct tahoe_knobs {
+    int lds_levels = INT_MAX;     // TAHOE_LDS_LEVELS: cap on ROWTILE's and TILEBLOCK's levels in LDS (dense; never raises the caps)
+    int tile_rows = 0;            // TAHOE_TILE_ROWS = 64 / 128: rows per TILEBLOCK / TILERING tile (dense)
+    int qring_walkers = 0;        // TAHOE_QRING_WALKERS = 15 / 12 / 8 / 4: walkers of QRING's 128-slot column form
+    int qring_chains = 0;         // TAHOE_QRING_CHAINS = 2 / 3: force the tile form of QRING's region layout (dense and sparse)
+    int qring_slices = 0;         // TAHOE_QRING_SLICES >= 1: force the tree slices per tile of QRING's SPLIT form
+    int qring_groups = 0;         // TAHOE_QRING_GROUPS: at least this many tree groups
+    int qring_wide_chains = 0;    // TAHOE_QRING_WIDE_CHAINS = 1: one tree group per walker of the wide-row form
+    bool qring_wide = true;       // TAHOE_QRING_WIDE = 0: the GX form instead of the wide-row tiles
+    bool qring_narrow = true;     // TAHOE_QRING_NARROW = 0: the general node layout
+    bool qring_regions = true;    // TAHOE_QRING_REGIONS = 0: the 128-slot column layout instead of the region form
+    bool qring_code8 = true;      // TAHOE_QRING_CODE8 = 0: u16 codes where u8 codes would serve
+    bool qring_narrow128 = true;  // TAHOE_QRING_NARROW128 = 0: the 32-KiB region stride for forests of <= 128 features
+    bool quant_buckets = true;    // TAHOE_QUANT_BUCKETS = 0: no bucketed quantise kernel
+    bool quant_multi = true;      // TAHOE_QUANT_MULTI = 0: the pair quantise kernels instead of the many-features ones
+    bool sparse_qring = true;     // TAHOE_SPARSE_QRING = 0: a sparse handle keeps the float32 kernels only
+    bool widef = true;            // TAHOE_WIDEF = 0: no float32 wide-row form of TILERING
+    int wstream = -1;             // TAHOE_WSTREAM: 0 = never the row-streaming form, 1 = wherever it can be built, -1 = the shape rule
+    int wstream_slab_mb = 1024;   // TAHOE_WSTREAM_SLAB_MB: cap of the row-streaming form's leaf-value workspace (at least 1 MiB)
+    int approx_form = 0;          // TAHOE_APPROX_FORM: 1 = the LDS slab wherever one wave's slab fits, 2 = in place
+};
+
 struct tahoe_forest {
     tahoe_forest_params p{};
     int depth = 0;        // De: depth of the normalised trees, max(p.depth, 2)
@@ -84,16 +111,11 @@ struct tahoe_forest {
     // sums[row * num_classes + class].  1 / num_trees on every other handle.
     int num_classes = 1;
     int class_trees = 0;
-    // Tuning knobs for experiments, read from the environment ONCE, in tahoe_forest_create (never on the predict path):
-    // TAHOE_TILE_ROWS (64 / 128: rows per TILEBLOCK / TILERING tile), TAHOE_QRING_WALKERS (15 / 12 / 8 / 4).  0 = unset.
+    tahoe_knobs knobs;
     // Probability-guided re-layout (TAHOE_CREATE_PROB_RELAYOUT; Struct.h:1775-1825): subtrees swapped so that the likelier
     // child is the left one, nodes carry an exchange bit.  Served by DIRECT, ROWTILE and the NARROW form of QRING.
     bool relayout = false;
     size_t relayout_swaps = 0;
-    int knob_tile_rows = 0;
-    int knob_qring_walkers = 0;
-    int knob_qring_slices = 0;  // TAHOE_QRING_SLICES >= 1: force the tree slices per tile of QRING's SPLIT form
-    int knob_qring_chains = 0;  // TAHOE_QRING_CHAINS = 2 / 3: force the tile form of QRING's region layout
     // Profiling: one hipEvent pair per traversal launch, read back after the stream has drained.
     bool profiling = false;
     std::vector<hipEvent_t> ev_start, ev_mid, ev_stop;  // mid: between a pre-pass kernel and the walk kernel
@@ -182,17 +204,54 @@ struct DeviceGuard {
     DeviceGuard &operator=(const DeviceGuard &) = delete;
 };
 
-// hipMalloc max(n, 1) elements for the n of src, counted in *total (the handle's device_bytes), and copy src there
+// hipMalloc max(n, 1) elements, counted in *total (the handle's device_bytes), and copy the n elements of src there
 template <typename T>
-inline hipError_t upload(T **dst, const std::vector<T> &src, size_t *total)
+inline hipError_t upload(T **dst, const T *src, size_t n, size_t *total)
 {
-    const size_t bytes = std::max<size_t>(src.size(), 1) * sizeof(T);
+    const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
     hipError_t e = hipMalloc(reinterpret_cast<void **>(dst), bytes);
     if (e != hipSuccess) return e;
     *total += bytes;
-    if (!src.empty()) e = hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice);
+    if (n) e = hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice);
     return e;
 }
+template <typename T>
+inline hipError_t upload(T **dst, const std::vector<T> &src, size_t *total)
+{
+    return upload(dst, src.data(), src.size(), total);
+}
+// TAHOE_ERR_HIP, "<what> failed: <HIP error>", unless e is hipSuccess
+inline tahoe_status hip_status(hipError_t e, const char *what)
+{
+    return e == hipSuccess ? TAHOE_OK : fail(TAHOE_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
+}
+
+// ---- creating a handle (forest.hip); every refusal of a bad argument comes before the first HIP call ----
+// The owner of a handle under construction: a failed create destroys what it has built so far, a finished one is released.
+struct ForestDeleter {
+    void operator()(tahoe_forest *f) const { tahoe_forest_destroy(f); }
+};
+using ForestPtr = std::unique_ptr<tahoe_forest, ForestDeleter>;
+// check_params (BaseTahoeTest.h:490-516), the rules of dense and sparse forests alike; have_nodes: the caller passed its node
+// array(s), named `nodes` in the refusal
+tahoe_status check_params(const tahoe_forest_params *p, int num_classes, bool have_nodes, const char *nodes);
+// The class and output rules of tahoe_forest_create_multiclass and tahoe_sparse_forest_create_ex
+tahoe_status check_classes(const tahoe_forest_params *p, int num_classes);
+// A handle on the current device with what dense and sparse handles share: params, classes, device limits, the error flag, knobs
+tahoe_status open_handle(const tahoe_forest_params *p, int num_classes, ForestPtr &f);
+// The last step of every create: the SHAP builds the flags ask for (contribs(), then approx()), then the handle goes to *out
+template <class Contribs, class Approx>
+inline tahoe_status finish_create(ForestPtr &f, unsigned flags, tahoe_forest **out, Contribs &&contribs, Approx &&approx)
+{
+    tahoe_status s = TAHOE_OK;
+    if (flags & TAHOE_CREATE_CONTRIBS) s = contribs();
+    if (s == TAHOE_OK && (flags & TAHOE_CREATE_APPROX_CONTRIBS)) s = approx();
+    if (s == TAHOE_OK) *out = f.release();
+    return s;
+}
+// TAHOE_OK when handle f can run `strategy` (a valid TAHOE_STRATEGY_*), else the refusal (TAHOE_ERR_UNSUPPORTED) saying why.
+// AUTO always resolves to an available strategy.
+tahoe_status strategy_available(const tahoe_forest *f, int strategy);
 
 // The branch rule of infer_one_tree, BaseTahoeTest.h:450-453: 1 = right child.
 __device__ __forceinline__ uint32_t go_right(float x, float thr, bool def_left, float missing)

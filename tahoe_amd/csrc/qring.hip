@@ -758,8 +758,7 @@ static long long qwide_lds_for(const tahoe_forest *f, int rt, int lw, int kg = 1
 // fit LDS beside the tile and the larger ring, else 1
 static int qwide_kg(const tahoe_forest *f, int rt, int lw)
 {
-    if (const char *e = getenv("TAHOE_QRING_WIDE_CHAINS"))  // experiments: 1 keeps one group per walker
-        if (atoi(e) == 1) return 1;
+    if (f->knobs.qring_wide_chains == 1) return 1;
     const long long chunks = 3LL * qwide_slot_bytes(lw, rt) / 16;
     return (chunks <= 256 && qwide_lds_for(f, rt, lw, 3) <= f->lds_limit) ? 3 : 1;
 }
@@ -772,8 +771,7 @@ static void qwide_pick(const tahoe_forest *f, int *rt_out, int *lw_out)
 {
     *rt_out = *lw_out = 0;
     if (!f->q || qring_lds_tile(f)) return;
-    if (const char *e = getenv("TAHOE_QRING_WIDE"))  // experiments: 0 keeps the GX form
-        if (atoi(e) == 0) return;
+    if (!f->knobs.qring_wide) return;
     for (int rt : {64, 32, 16}) {
         const int hi = qwide_lw_max(f->q->top_levels, rt);
         for (int lw = hi; lw >= std::max(0, hi - 3); --lw)
@@ -790,7 +788,7 @@ int qring_walkers(const tahoe_forest *f)
     if (!f->q) return 0;
     if (f->q->narrow) return 15;  // the node words were encoded for that form at create
     static const int options[] = {15, 12, 8, 4};
-    if (const int want = f->knob_qring_walkers)  // TAHOE_QRING_WALKERS, read at create
+    if (const int want = f->knobs.qring_walkers)  // TAHOE_QRING_WALKERS
         for (int n : options)
             if (n == want && qring_lds_for(f, n) <= f->lds_limit) return n;
     for (int n : options)
@@ -986,16 +984,8 @@ tahoe_status qring_build(tahoe_forest *f, const std::vector<InnerNode> &h_inner,
     q->wide_kg = q->wide_rt ? qwide_kg(f, q->wide_rt, q->wide_lw) : 1;
     if (q->wide_rt) q->have_mid = q->have_mid || f->depth - 2 > q->wide_lw;  // smaller tops in LDS
     q->top_stride = (int)std::max<size_t>((size_t)1 << q->top_levels, 4);  // >= 16 bytes per tree
-    {
-        const char *e = getenv("TAHOE_QRING_NARROW");  // experiments: 0 keeps the general node layout
-        q->narrow = cols <= 256 && qring_walkers(f) == 15 && qring_lds_tile(f) && !(e && atoi(e) == 0);
-    }
-    {
-        const char *e = getenv("TAHOE_QRING_REGIONS");  // experiments: 0 keeps the 128-slot column layout
-        q->reg = q->narrow && !f->relayout && qreg_lds_for(3, kReg3Walkers, kReg3Ring) <= f->lds_limit && !(e && atoi(e) == 0);
-        if (const char *k = getenv("TAHOE_QRING_CHAINS")) f->knob_qring_chains = atoi(k);  // 2 / 3: force the tile form
-        if (const char *k = getenv("TAHOE_QRING_SLICES")) f->knob_qring_slices = atoi(k);  // >= 1: force the tree slices per tile
-    }
+    q->narrow = cols <= 256 && qring_walkers(f) == 15 && qring_lds_tile(f) && f->knobs.qring_narrow;
+    q->reg = q->narrow && !f->relayout && qreg_lds_for(3, kReg3Walkers, kReg3Ring) <= f->lds_limit && f->knobs.qring_regions;
     if (f->relayout && !q->narrow) {  // only the NARROW node word has room for the exchange bit: the strategy steps aside
         qring_destroy(f);
         return TAHOE_OK;
@@ -1026,10 +1016,11 @@ tahoe_status qring_build(tahoe_forest *f, const std::vector<InnerNode> &h_inner,
         if (most > (size_t)kQMaxTable) G = (most + kQMaxTable - 1) / kQMaxTable;  // a group sees at most the forest's distinct count
         // u8 codes (histogram-trained forests: <= 254 thresholds per feature): decided here, before the node words are encoded --
         // such a handle has its own node encoding and only ever quantises to u8 (large batches, remainders and tree slices alike)
-        const char *e8 = getenv("TAHOE_QRING_CODE8");  // experiments: 0 keeps u16 codes
-        q->code8 = q->reg && most <= (size_t)kQMaxTable8 && qreg_lds_for(6, kReg8Walkers, kReg8Ring, true) <= f->lds_limit && !(e8 && atoi(e8) == 0);
-        if (const char *k = getenv("TAHOE_QRING_GROUPS"))  // experiments: at least this many groups (K4: 8 groups of 1000 trees
-            G = std::max(G, (size_t)std::max(atoi(k), 1));  // take the bucketed quantise kernel, 4 of 2000 the two-pass one)
+        q->code8 = q->reg && most <= (size_t)kQMaxTable8 && qreg_lds_for(6, kReg8Walkers, kReg8Ring, true) <= f->lds_limit &&
+                   f->knobs.qring_code8;
+        // TAHOE_QRING_GROUPS: at least this many groups (K4: 8 groups of 1000 trees take the bucketed quantise kernel, 4 of 2000
+        // the two-pass one)
+        G = std::max(G, (size_t)std::max(f->knobs.qring_groups, 1));
     }
     const size_t bytes_before = f->device_bytes;
     for (;;) {
@@ -1062,11 +1053,9 @@ tahoe_status qring_build(tahoe_forest *f, const std::vector<InnerNode> &h_inner,
         }
         G = std::max(G + 1, (size_t)((double)G * worst / kQMaxTable + 0.999));
     }
-    {   // <= 128 features: regions at a 16-KiB LDS stride
-        const char *e6 = getenv("TAHOE_QRING_NARROW128");  // experiments: 0 keeps the 32-KiB region stride for forests of <= 128 features
-        q->narrow128 = q->reg && cols <= 128 && qreg_lds_for(6, kReg8Walkers, kReg8Ring, false, kRegBytes / 2) <= f->lds_limit &&
-                       qreg_lds_for(6, 15, kQRing, true, kRegBytes / 2) <= f->lds_limit && !(e6 && atoi(e6) == 0);
-    }
+    // <= 128 features: regions at a 16-KiB LDS stride
+    q->narrow128 = q->reg && cols <= 128 && qreg_lds_for(6, kReg8Walkers, kReg8Ring, false, kRegBytes / 2) <= f->lds_limit &&
+                   qreg_lds_for(6, 15, kQRing, true, kRegBytes / 2) <= f->lds_limit && f->knobs.qring_narrow128;
     // kernels that need more than 64 KiB of dynamic LDS
     hipError_t e;
     auto bad = [&](const char *what) { return fail(TAHOE_ERR_HIP, "qring_build: %s failed: %s", what, hipGetErrorString(e)); };
@@ -1146,7 +1135,7 @@ tahoe_status qring_reserve(tahoe_forest *f, size_t rows)
     // rows must find it in place -- also a small one after a large reserve -- so it is sized for the largest split batch
     // that fits in `rows` (slices fall to 1 once the 128-row tiles outnumber half the CUs).
     int most = 1;
-    const size_t split_max = f->knob_qring_slices >= 1 ? rows : std::min<size_t>(rows, (size_t)std::max(f->num_cus, 2) / 2 * 128);
+    const size_t split_max = f->knobs.qring_slices >= 1 ? rows : std::min<size_t>(rows, (size_t)std::max(f->num_cus, 2) / 2 * 128);
     if (q_slices(f, split_max, &most) > 1) return qring_reserve_leafbuf(f, split_max, most);
     return TAHOE_OK;
 }
@@ -1163,7 +1152,7 @@ static int q_slices(const tahoe_forest *f, size_t rows, int *most_out)
     const size_t tiles = (rows + 127) / 128;
     const int fit = (int)std::min<size_t>((size_t)std::max(f->num_cus, 1) / tiles, 8);
     int slices = std::max(1, std::min(fit, most / (4 * 15)));
-    if (f->knob_qring_slices >= 1) slices = std::min(f->knob_qring_slices, most);
+    if (f->knobs.qring_slices >= 1) slices = std::min(f->knobs.qring_slices, most);
     return slices;
 }
 
@@ -1273,11 +1262,11 @@ static QPlan qring_plan(const tahoe_forest *f, size_t rows)
     if (!q->reg || p.slices > 1) return p;
     // TAHOE_QRING_CHAINS = 2 / 3 forces one form, TAHOE_QRING_SLICES = 1 keeps every remainder in plain tiles.  u8 codes and
     // forests of <= 128 features plan 384-row tiles against 128-row ones, u16 codes 192-row tiles.
-    const int slice_trees = f->knob_qring_slices == 1 ? 0 : p.most;
+    const int slice_trees = f->knobs.qring_slices == 1 ? 0 : p.most;
     if (q->code8 || q->narrow128)
-        qreg_plan(rows, f->num_cus, f->knob_qring_chains, &p.rows3, &p.chains, kReg8Cost, 384, slice_trees);
+        qreg_plan(rows, f->num_cus, f->knobs.qring_chains, &p.rows3, &p.chains, kReg8Cost, 384, slice_trees);
     else
-        qreg_plan(rows, f->num_cus, f->knob_qring_chains, &p.rows3, &p.chains, 133, 192, slice_trees);
+        qreg_plan(rows, f->num_cus, f->knobs.qring_chains, &p.rows3, &p.chains, 133, 192, slice_trees);
     // A remainder of few 128-row tiles behind the whole waves of large tiles would leave most of the chip idle for a whole tile
     // time (250 k rows of K3's forest: 5 waves of 192-row tiles + 34 tiles of 128): it is walked in tree slices too -- every
     // remainder tile by rem_slices workgroups, then the ordered sum over those rows (bit-identical: the same sequential sum).
@@ -1303,11 +1292,7 @@ tahoe_status qring_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, cons
                           hipStream_t stream, hipEvent_t mid_event, const float *sums_in0)
 {
     tahoe_qstate *q = f->q;
-    const int nwalk = qring_walkers(f);
-    if (!q || nwalk == 0)
-        return fail(TAHOE_ERR_UNSUPPORTED,
-                    "QRING needs <= %d distinct thresholds per feature within one tree, num_cols <= 32767 and a 128-row "
-                    "u16 tile in LDS", kQMaxTable);
+    const int nwalk = qring_walkers(f);  // > 0: launch_traversal has checked strategy_available
     tahoe_status s = qring_reserve(f, rows);  // no-op unless this batch is larger than any before
     if (s != TAHOE_OK) return s;
     const int wide = qwide_rows(f);  // 0: 128-row tiles; else rows per tile of the wide-row form

@@ -400,8 +400,7 @@ static tahoe_status build_buckets(tahoe_forest *f, const std::vector<std::vector
     const int cols = f->p.num_cols;
     g.buckets = 0;
     if (cols % 2 != 0) return TAHOE_OK;
-    if (const char *e = getenv("TAHOE_QUANT_BUCKETS"))
-        if (atoi(e) == 0) return TAHOE_OK;
+    if (!f->knobs.quant_buckets) return TAHOE_OK;
     size_t total = 0;
     for (int c = 0; c < cols; ++c) total += tab[c].size();
     std::vector<float> vals;
@@ -555,15 +554,12 @@ tahoe_status quantize_build_tables(tahoe_forest *f, const std::vector<std::vecto
         g.pair_lds_floats = std::max(need, 1);
     }
     g.multi_q = 0;
-    {
-        const char *e = getenv("TAHOE_QUANT_MULTI");  // experiments: 0 keeps the pair kernels
-        if (!(e && atoi(e) == 0))
-            for (int qd : {kQuantMultiMax, 4, 2})
-                if (qd <= kQuantMultiMax && cols % (4 * qd) == 0 && (long long)4 * qd * max_size * 4 <= f->lds_limit - 256) {
-                    g.multi_q = qd;
-                    break;
-                }
-    }
+    if (f->knobs.quant_multi)
+        for (int qd : {kQuantMultiMax, 4, 2})
+            if (qd <= kQuantMultiMax && cols % (4 * qd) == 0 && (long long)4 * qd * max_size * 4 <= f->lds_limit - 256) {
+                g.multi_q = qd;
+                break;
+            }
     {
         const tahoe_status bs = build_buckets(f, tab, g);
         if (bs != TAHOE_OK) return bs;

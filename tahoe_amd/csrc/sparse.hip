@@ -653,15 +653,12 @@ static void sparse_q_launch_form(tahoe_forest *f, const tahoe_qgroup &g, float *
 static tahoe_status sparse_q_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data, size_t rows,
                                     hipStream_t stream, const float *sums_in0)
 {
-    if (!sparse_q_available(f))
-        return fail(TAHOE_ERR_UNSUPPORTED, "sparse QRING needs num_cols <= 256, trees of <= 65535 nodes and <= %d distinct thresholds "
-                                           "per feature within one tree", kQMaxTable);
     tahoe_qstate *q = f->q;
     const tahoe_status rs = qring_reserve(f, rows);  // no-op unless this batch is larger than any before
     if (rs != TAHOE_OK) return rs;
     size_t rows3 = 0;
     int chains = 2;
-    qreg_plan(rows, f->num_cus, f->knob_qring_chains, &rows3, &chains, 161);  // K5: 0.555 ms per wave of 192-row tiles, 0.344 of 128
+    qreg_plan(rows, f->num_cus, f->knobs.qring_chains, &rows3, &chains, 161);  // K5: 0.555 ms per wave of 192-row tiles, 0.344 of 128
     bool first = true;
     for (const tahoe_qgroup &g : q->groups) {
         TAHOE_HIP_TRY(hipMemsetAsync(q->chunk_flags, 0, q->n_chunk_flags * sizeof(uint32_t), stream));
@@ -710,8 +707,7 @@ tahoe_status sparse_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, con
     const int vec4_ok = (f->p.num_cols % 4 == 0) && ((reinterpret_cast<uintptr_t>(data) & 15u) == 0);
     if (strategy == TAHOE_STRATEGY_QRING) return sparse_q_launch(f, sums, leaf_out, data, rows, stream, sums_in);
     if (strategy == TAHOE_STRATEGY_TILEBLOCK) {
-        const int nw = sparse_top_waves(f);
-        if (nw == 0) return fail(TAHOE_ERR_UNSUPPORTED, "sparse TILEBLOCK: the compact form or its LDS tile is unavailable");
+        const int nw = sparse_top_waves(f);  // > 0: launch_traversal has checked strategy_available
         const int lds = (int)sparse_top_lds(f, nw);
         const int nc = f->num_classes;
         with_leaf_mc(leaf_out != nullptr, nc > 1, [&](auto wl, auto mc) {
@@ -765,16 +761,13 @@ static tahoe_status sparse_q_build(tahoe_forest *f, const std::vector<uint2> &cn
     tahoe_sstate *sp = f->sp;
     const int cols = f->p.num_cols;
     const size_t T = (size_t)f->p.num_trees;
-    if (const char *e = getenv("TAHOE_SPARSE_QRING"))  // experiments: 0 keeps the float32 kernels only
-        if (atoi(e) == 0) return TAHOE_OK;
-    if (cols < 1 || cols > 256 || T == 0 || qreg_lds_for(3, kReg3Walkers, kReg3Ring) > f->lds_limit ||
+    if (!f->knobs.sparse_qring || cols < 1 || cols > 256 || T == 0 || qreg_lds_for(3, kReg3Walkers, kReg3Ring) > f->lds_limit ||
         qreg_lds_for(2, 15, kQRing) > f->lds_limit)
         return TAHOE_OK;
     tahoe_qstate *q = new (std::nothrow) tahoe_qstate();
     if (!q) return fail(TAHOE_ERR_NO_MEMORY, "sparse_q_build");
     f->q = q;
     q->narrow = q->reg = q->sparse = true;  // region workspace (qring_reserve), region node words
-    if (const char *k = getenv("TAHOE_QRING_CHAINS")) f->knob_qring_chains = atoi(k);  // 2 / 3: force the tile form
     auto is_inner = [](const uint2 &c) { return (c.y >> 16) != 0u; };
     auto thr_of = [](const uint2 &c) {
         float v;
@@ -980,6 +973,68 @@ static tahoe_status sparse_q_build(tahoe_forest *f, const std::vector<uint2> &cn
     return TAHOE_OK;
 }
 
+// The compact breadth-first copy of the stored trees (sparse_top_kernel), then its quantised form (sparse_q_build).  Leaves both
+// unavailable (TAHOE_OK, sp->cnodes null) when a tree has more than 65535 reachable nodes.
+static tahoe_status sparse_top_build(tahoe_forest *f, const int32_t *trees, const tahoe_sparse_node *nodes)
+{
+    tahoe_sstate *sp = f->sp;
+    const int T = f->p.num_trees;
+    std::vector<uint2> cn;
+    std::vector<uint32_t> orig;
+    std::vector<int32_t> ct((size_t)T + 1, 0);
+    std::vector<uint32_t> order, newpos;
+    for (int t = 0; t < T; ++t) {
+        const long long lo = trees[t], hi = (t + 1 < T) ? trees[t + 1] : (long long)sp->num_nodes;
+        const tahoe_sparse_node *tn = nodes + lo;
+        // breadth-first order of the reachable nodes; a child pair stays adjacent
+        order.assign(1, 0u);
+        for (size_t q = 0; q < order.size() && order.size() <= 65535; ++q) {
+            const tahoe_sparse_node &n = tn[order[q]];
+            if (n.bits & kSIsLeaf) continue;
+            order.push_back((uint32_t)n.left_idx);
+            order.push_back((uint32_t)n.left_idx + 1u);
+        }
+        if (order.size() > 65535) return TAHOE_OK;
+        // position 0 of a tree is padding and the root sits at 1, so that every child pair (appended two at a time)
+        // starts at an even position: one aligned 16-byte read fetches both children
+        newpos.assign((size_t)(hi - lo), 0u);
+        for (size_t q = 0; q < order.size(); ++q) newpos[order[q]] = (uint32_t)q + 1u;
+        ct[(size_t)t] = (int32_t)cn.size();
+        cn.push_back(make_uint2(0u, 0u));
+        orig.push_back(0u);
+        for (size_t q = 0; q < order.size(); ++q) {
+            const tahoe_sparse_node &n = tn[order[q]];
+            uint2 c;
+            memcpy(&c.x, &n.val, 4);
+            if (n.bits & kSIsLeaf)
+                c.y = 0u;
+            else  // the left child of any node sits at a position >= 2: 0 marks a leaf
+                c.y = (newpos[(size_t)n.left_idx] << 16) | ((n.bits & kSDefLeft) ? 0x8000u : 0u) | (uint32_t)(n.bits & kSFidMask);
+            cn.push_back(c);
+            orig.push_back(order[q]);
+        }
+        if (cn.size() & 1) {  // next tree starts on a 16-byte boundary
+            cn.push_back(make_uint2(0u, 0u));
+            orig.push_back(0u);
+        }
+        if (cn.size() > 0x7fffffffu) return TAHOE_OK;
+    }
+    ct[(size_t)T] = (int32_t)cn.size();
+    tahoe_status s;
+    if ((s = hip_status(upload(&sp->cnodes, cn, &f->device_bytes), "upload(cnodes)")) ||
+        (s = hip_status(upload(&sp->ctrees, ct, &f->device_bytes), "upload(ctrees)")) ||
+        (s = hip_status(upload(&sp->corig, orig, &f->device_bytes), "upload(corig)")))
+        return s;
+    hipError_t e;
+    if ((e = allow_max_lds_leaf([](auto wl) { return &sparse_top_kernel<16, decltype(wl)::value>; }, f->lds_limit)) != hipSuccess ||
+        (e = allow_max_lds_leaf([](auto wl) { return &sparse_top_kernel<8, decltype(wl)::value>; }, f->lds_limit)) != hipSuccess ||
+        (f->num_classes > 1 &&
+         ((e = allow_max_lds_leaf([](auto wl) { return &sparse_top_kernel<16, decltype(wl)::value, true>; }, f->lds_limit)) != hipSuccess ||
+          (e = allow_max_lds_leaf([](auto wl) { return &sparse_top_kernel<8, decltype(wl)::value, true>; }, f->lds_limit)) != hipSuccess)))
+        return hip_status(e, "hipFuncSetAttribute(sparse_top)");
+    return sparse_q_build(f, cn, ct);
+}
+
 void sparse_device_views(const tahoe_forest *f, const tahoe_sparse_node **nodes, const int32_t **trees)
 {
     *nodes = f->sp->nodes;
@@ -993,14 +1048,9 @@ static tahoe_status create_sparse(tahoe_forest **out, const int32_t *trees, cons
 {
     if (!out || !p) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_sparse_forest_create: null argument");
     *out = nullptr;
-    // check_params(params, dense = false), BaseTahoeTest.h:490-516
     if (p->num_nodes < 0) return fail(TAHOE_ERR_INVALID_ARG, "num_nodes must be non-negative for sparse forests");
     if (p->algo != TAHOE_ALGO_NAIVE) return fail(TAHOE_ERR_INVALID_ARG, "only NAIVE algorithm is supported for sparse forests");
-    if (p->num_trees < 0) return fail(TAHOE_ERR_INVALID_ARG, "num_trees must be non-negative");
-    if (p->num_cols < 0) return fail(TAHOE_ERR_INVALID_ARG, "num_cols must be non-negative");
-    if ((p->output & ~(TAHOE_OUT_AVG | TAHOE_OUT_SIGMOID | TAHOE_OUT_THRESHOLD | (num_classes > 1 ? TAHOE_OUT_SOFTMAX : 0))) != 0)
-        return fail(TAHOE_ERR_INVALID_ARG, "output should be a combination of RAW, AVG, SIGMOID and THRESHOLD");
-    if (p->num_trees > 0 && (!trees || !nodes)) return fail(TAHOE_ERR_INVALID_ARG, "trees / nodes is null");
+    if (const tahoe_status s = check_params(p, num_classes, trees && nodes, "trees / nodes")) return s;
     // Structure check (the reference trusts its input): roots ascending, every child pair inside its tree
     // and after its parent (which also rules out cycles, so device walks terminate), fid < num_cols.
     int max_tree_nodes = 0;
@@ -1025,29 +1075,12 @@ static tahoe_status create_sparse(tahoe_forest **out, const int32_t *trees, cons
         const tahoe_status cs = contribs_validate_sparse(trees, nodes, covers, p, (flags & TAHOE_CREATE_CONTRIBS) != 0);
         if (cs != TAHOE_OK) return cs;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(TAHOE_ERR_NO_DEVICE, "no HIP device is visible; libtahoe_amd has no CPU path");
-    int dev = 0;
-    TAHOE_HIP_TRY(hipGetDevice(&dev));
-    hipDeviceProp_t prop;
-    TAHOE_HIP_TRY(hipGetDeviceProperties(&prop, dev));
-    tahoe_forest *f = new (std::nothrow) tahoe_forest();
+    ForestPtr f;
+    if (const tahoe_status s = open_handle(p, num_classes, f)) return s;
     tahoe_sstate *sp = new (std::nothrow) tahoe_sstate();
-    if (!f || !sp) {
-        delete f;
-        delete sp;
-        return fail(TAHOE_ERR_NO_MEMORY, "tahoe_sparse_forest_create");
-    }
+    if (!sp) return fail(TAHOE_ERR_NO_MEMORY, "tahoe_sparse_forest_create");
     f->sp = sp;
-    f->p = *p;
-    f->num_classes = num_classes;
-    f->class_trees = p->num_trees / num_classes;
     f->depth = 0;  // a placeholder value, as in sparse_forest::init (Struct.h:2332)
-    f->device = dev;
-    f->num_cus = prop.multiProcessorCount;
-    f->lds_limit = (int)prop.maxSharedMemoryPerMultiProcessor > 0 ? (int)prop.maxSharedMemoryPerMultiProcessor
-                                                                   : (int)prop.sharedMemPerBlock;
     f->bits_bytes = 4;
     sp->num_nodes = (size_t)p->num_nodes;
     sp->max_tree_nodes = max_tree_nodes;
@@ -1069,111 +1102,20 @@ static tahoe_status create_sparse(tahoe_forest **out, const int32_t *trees, cons
         trees = mc_trees.data();
         nodes = mc_nodes.data();
     }
-    auto bail = [&](hipError_t e, const char *what) {
-        tahoe_forest_destroy(f);
-        return fail(TAHOE_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
-    };
+    tahoe_status s;
+    if ((s = hip_status(upload(&sp->nodes, nodes, sp->num_nodes, &f->device_bytes), "upload(nodes)")) ||
+        (s = hip_status(upload(&sp->trees, trees, (size_t)p->num_trees, &f->device_bytes), "upload(trees)")))
+        return s;
     hipError_t e;
-    const size_t nbytes = std::max<size_t>(sp->num_nodes, 1) * sizeof(tahoe_sparse_node);
-    const size_t tbytes = std::max<size_t>((size_t)p->num_trees, 1) * sizeof(int32_t);
-    if ((e = hipMalloc(reinterpret_cast<void **>(&sp->nodes), nbytes)) != hipSuccess) return bail(e, "hipMalloc(nodes)");
-    if ((e = hipMalloc(reinterpret_cast<void **>(&sp->trees), tbytes)) != hipSuccess) return bail(e, "hipMalloc(trees)");
-    f->device_bytes = nbytes + tbytes;
-    if (sp->num_nodes && (e = hipMemcpy(sp->nodes, nodes, sp->num_nodes * sizeof(tahoe_sparse_node), hipMemcpyHostToDevice)) != hipSuccess)
-        return bail(e, "hipMemcpy(nodes)");
-    if (p->num_trees && (e = hipMemcpy(sp->trees, trees, (size_t)p->num_trees * sizeof(int32_t), hipMemcpyHostToDevice)) != hipSuccess)
-        return bail(e, "hipMemcpy(trees)");
-    if ((e = hipMalloc(reinterpret_cast<void **>(&f->error_flag), sizeof(int))) != hipSuccess) return bail(e, "hipMalloc(error_flag)");
-    if ((e = hipMemset(f->error_flag, 0, sizeof(int))) != hipSuccess) return bail(e, "hipMemset(error_flag)");
-    if (sparse_tile_fits(f)) {
-        if ((e = allow_max_lds_leaf([](auto wl) { return &sparse_kernel<true, decltype(wl)::value>; }, f->lds_limit)) != hipSuccess ||
-            (num_classes > 1 && (e = allow_max_lds_leaf([](auto wl) { return &sparse_kernel<true, decltype(wl)::value, true>; }, f->lds_limit)) != hipSuccess))
-            return bail(e, "hipFuncSetAttribute(sparse)");
-    }
-    // ---- compact breadth-first copy (sparse_top_kernel) ----
-    if (p->num_cols <= 32767 && p->num_trees > 0) {
-        std::vector<uint2> cn;
-        std::vector<uint32_t> orig;
-        std::vector<int32_t> ct((size_t)p->num_trees + 1, 0);
-        std::vector<uint32_t> order, newpos;
-        bool ok = true;
-        for (int t = 0; t < p->num_trees && ok; ++t) {
-            const long long lo = trees[t], hi = (t + 1 < p->num_trees) ? trees[t + 1] : (long long)sp->num_nodes;
-            const tahoe_sparse_node *tn = nodes + lo;
-            // breadth-first order of the reachable nodes; a child pair stays adjacent
-            order.assign(1, 0u);
-            for (size_t q = 0; q < order.size() && order.size() <= 65535; ++q) {
-                const tahoe_sparse_node &n = tn[order[q]];
-                if (n.bits & kSIsLeaf) continue;
-                order.push_back((uint32_t)n.left_idx);
-                order.push_back((uint32_t)n.left_idx + 1u);
-            }
-            if (order.size() > 65535) {
-                ok = false;
-                break;
-            }
-            // position 0 of a tree is padding and the root sits at 1, so that every child pair (appended two at a time)
-            // starts at an even position: one aligned 16-byte read fetches both children
-            newpos.assign((size_t)(hi - lo), 0u);
-            for (size_t q = 0; q < order.size(); ++q) newpos[order[q]] = (uint32_t)q + 1u;
-            ct[(size_t)t] = (int32_t)cn.size();
-            cn.push_back(make_uint2(0u, 0u));
-            orig.push_back(0u);
-            for (size_t q = 0; q < order.size(); ++q) {
-                const tahoe_sparse_node &n = tn[order[q]];
-                uint2 c;
-                memcpy(&c.x, &n.val, 4);
-                if (n.bits & kSIsLeaf)
-                    c.y = 0u;
-                else  // the left child of any node sits at a position >= 2: 0 marks a leaf
-                    c.y = (newpos[(size_t)n.left_idx] << 16) | ((n.bits & kSDefLeft) ? 0x8000u : 0u) | (uint32_t)(n.bits & kSFidMask);
-                cn.push_back(c);
-                orig.push_back(order[q]);
-            }
-            if (cn.size() & 1) {  // next tree starts on a 16-byte boundary
-                cn.push_back(make_uint2(0u, 0u));
-                orig.push_back(0u);
-            }
-            if (cn.size() > 0x7fffffffu) ok = false;
-        }
-        if (ok) {
-            ct[(size_t)p->num_trees] = (int32_t)cn.size();
-            if ((e = hipMalloc(reinterpret_cast<void **>(&sp->cnodes), cn.size() * sizeof(uint2))) != hipSuccess) return bail(e, "hipMalloc(cnodes)");
-            if ((e = hipMalloc(reinterpret_cast<void **>(&sp->ctrees), ct.size() * sizeof(int32_t))) != hipSuccess) return bail(e, "hipMalloc(ctrees)");
-            if ((e = hipMalloc(reinterpret_cast<void **>(&sp->corig), orig.size() * sizeof(uint32_t))) != hipSuccess) return bail(e, "hipMalloc(corig)");
-            if ((e = hipMemcpy(sp->cnodes, cn.data(), cn.size() * sizeof(uint2), hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy(cnodes)");
-            if ((e = hipMemcpy(sp->ctrees, ct.data(), ct.size() * sizeof(int32_t), hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy(ctrees)");
-            if ((e = hipMemcpy(sp->corig, orig.data(), orig.size() * sizeof(uint32_t), hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy(corig)");
-            f->device_bytes += cn.size() * sizeof(uint2) + ct.size() * sizeof(int32_t) + orig.size() * sizeof(uint32_t);
-            if ((e = allow_max_lds_leaf([](auto wl) { return &sparse_top_kernel<16, decltype(wl)::value>; }, f->lds_limit)) != hipSuccess ||
-                (e = allow_max_lds_leaf([](auto wl) { return &sparse_top_kernel<8, decltype(wl)::value>; }, f->lds_limit)) != hipSuccess ||
-                (num_classes > 1 &&
-                 ((e = allow_max_lds_leaf([](auto wl) { return &sparse_top_kernel<16, decltype(wl)::value, true>; }, f->lds_limit)) != hipSuccess ||
-                  (e = allow_max_lds_leaf([](auto wl) { return &sparse_top_kernel<8, decltype(wl)::value, true>; }, f->lds_limit)) != hipSuccess)))
-                return bail(e, "hipFuncSetAttribute(sparse_top)");
-            const tahoe_status qs = sparse_q_build(f, cn, ct);
-            if (qs != TAHOE_OK) {
-                tahoe_forest_destroy(f);
-                return qs;
-            }
-        }
-    }
-    if (flags & TAHOE_CREATE_CONTRIBS) {  // from the caller's trees, in the caller's numbering (contribs_build's order)
-        const tahoe_status cs = contribs_build_sparse(f, caller_trees, caller_nodes, covers);
-        if (cs != TAHOE_OK) {
-            tahoe_forest_destroy(f);
-            return cs;
-        }
-    }
-    if (flags & TAHOE_CREATE_APPROX_CONTRIBS) {  // per-node child deltas in the stored (class-major) order
-        const tahoe_status as = approx_build_sparse(f, caller_trees, caller_nodes, covers);
-        if (as != TAHOE_OK) {
-            tahoe_forest_destroy(f);
-            return as;
-        }
-    }
-    *out = f;
-    return TAHOE_OK;
+    if (sparse_tile_fits(f.get()) &&
+        ((e = allow_max_lds_leaf([](auto wl) { return &sparse_kernel<true, decltype(wl)::value>; }, f->lds_limit)) != hipSuccess ||
+         (num_classes > 1 && (e = allow_max_lds_leaf([](auto wl) { return &sparse_kernel<true, decltype(wl)::value, true>; }, f->lds_limit)) != hipSuccess)))
+        return hip_status(e, "hipFuncSetAttribute(sparse)");
+    if (p->num_cols <= 32767 && p->num_trees > 0 && (s = sparse_top_build(f.get(), trees, nodes))) return s;
+    // contributions from the caller's trees, in the caller's numbering (contribs_build's order); Saabas deltas in the stored
+    // (class-major) order
+    return finish_create(f, flags, out, [&] { return contribs_build_sparse(f.get(), caller_trees, caller_nodes, covers); },
+                         [&] { return approx_build_sparse(f.get(), caller_trees, caller_nodes, covers); });
 }
 
 }  // namespace tahoe
@@ -1194,15 +1136,7 @@ tahoe_status tahoe_sparse_forest_create_ex(tahoe_forest **out, const int32_t *tr
     // every check here (and in create_sparse) runs before a device is touched
     if (!out || !p) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_sparse_forest_create_ex: null argument");
     *out = nullptr;
-    if (num_classes < 1 || num_classes > 1024) return fail(TAHOE_ERR_INVALID_ARG, "num_classes must be in [1,1024], got %d", num_classes);
-    if (p->num_trees < 0 || p->num_trees % num_classes != 0)
-        return fail(TAHOE_ERR_INVALID_ARG, "num_trees (%d) must be a non-negative multiple of num_classes (%d)", p->num_trees, num_classes);
-    if ((p->output & TAHOE_OUT_SOFTMAX) != 0 && num_classes == 1)
-        return fail(TAHOE_ERR_INVALID_ARG, "SOFTMAX needs num_classes > 1");
-    if ((p->output & TAHOE_OUT_SOFTMAX) != 0 && (p->output & TAHOE_OUT_SIGMOID) != 0)
-        return fail(TAHOE_ERR_INVALID_ARG, "SOFTMAX and SIGMOID exclude each other");
-    if ((p->output & TAHOE_OUT_THRESHOLD) != 0 && num_classes > 1)
-        return fail(TAHOE_ERR_INVALID_ARG, "THRESHOLD needs num_classes == 1");
+    if (const tahoe_status s = check_classes(p, num_classes)) return s;
     if ((flags & ~(unsigned)(TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS)) != 0)
         return fail(TAHOE_ERR_INVALID_ARG, "unknown create flags 0x%x (a sparse handle takes TAHOE_CREATE_CONTRIBS and "
                                            "TAHOE_CREATE_APPROX_CONTRIBS only)", flags);

@@ -291,8 +291,7 @@ tahoe_status widef_build(tahoe_forest *f, const std::vector<InnerNode> &h_inner,
     const int cols = f->p.num_cols, De = f->depth;
     const size_t T = (size_t)f->p.num_trees;
     if (T == 0 || cols < 1 || De < 2 || f->relayout) return TAHOE_OK;  // the exchange bit is not part of this walk
-    if (const char *e = getenv("TAHOE_WIDEF"))  // experiments: 0 leaves the shape to QRING / DIRECT
-        if (atoi(e) == 0) return TAHOE_OK;
+    if (!f->knobs.widef) return TAHOE_OK;  // (TAHOE_WIDEF = 0 leaves the shape to QRING / DIRECT)
     int rt = 0, nwalk = 0, lw = 0;
     for (int cand : {32, 16, 8}) {
         const int hi = std::min(De - 2, wf_lw_max(cand));

@@ -513,8 +513,7 @@ tahoe_status wkey_build(tahoe_forest *f, const std::vector<InnerNode> &h_inner, 
     if (!w) return TAHOE_OK;
     const int cols = f->p.num_cols, De = f->depth;
     const size_t T = (size_t)f->p.num_trees, n_inner = f->n_inner, n_leaf = f->n_leaf;
-    int knob = -1;  // TAHOE_WSTREAM: 0 = never, 1 = whenever it can be built (experiments, tests), unset = the shape rule
-    if (const char *e = getenv("TAHOE_WSTREAM")) knob = atoi(e);
+    const int knob = f->knobs.wstream;  // TAHOE_WSTREAM: 0 = never, 1 = whenever it can be built (experiments, tests), -1 = the shape rule
     if (knob == 0 || cols % 4 != 0 || cols > 3072 || T > ((size_t)1 << 20) || De < 2) return TAHOE_OK;
     int s_lw = -1, s_ts = 64;  // tree stride of the image: a power of two, 64 .. 1024 (the walk's shifts are immediates)
     while (s_ts < (int)T) s_ts *= 2;
@@ -637,8 +636,7 @@ tahoe_status wkey_build(tahoe_forest *f, const std::vector<InnerNode> &h_inner, 
     w->s_ts = s_ts;
     w->s_slots = slots;
     w->s_img_bytes = (int)img;
-    w->slab_bytes = (size_t)1 << 30;
-    if (const char *sm = getenv("TAHOE_WSTREAM_SLAB_MB")) w->slab_bytes = (size_t)std::max(atoi(sm), 1) << 20;
+    w->slab_bytes = (size_t)std::max(f->knobs.wstream_slab_mb, 1) << 20;  // 1 GiB unless TAHOE_WSTREAM_SLAB_MB says otherwise
     w->key_lo = lo;
     w->key_scale = scale;
     w->s_on = true;
