@@ -411,12 +411,9 @@ __global__ void __launch_bounds__(kSlots *ROWS)
 //     trees w, w+NWALK, ... for all ROWS rows of the tile (K = ROWS/64 interleaved chains per lane), and
 //     prefetches the next top into registers meanwhile.  Waves drift freely, so one wave's global
 //     gather latency is covered by the others' LDS walks.
-//   * One consumer wave adds the leaf values in tree order (bit-exact float32 sums).  Walkers hand
-//     them over through a ring in LDS: vals[RING][ROWS] + ready[RING] (holds tree+1) + one `consumed`
-//     counter; single-CU LDS traffic is processed in order, so a flag written after its data is seen
-//     after its data.  Every spin is bounded: on timeout the kernel sets *error_flag and drains.
-// Dynamic LDS: [cols][ROWS] float | NWALK x top_stride | [RING][ROWS] float | ready[RING] | consumed.
-constexpr int kRingSpinLimit = 1 << 22;
+//   * One consumer wave adds the leaf values in tree order (bit-exact float32 sums), handed over through the LDS tree ring
+//     (forest_internal.h; DESIGN.md, "The LDS tree ring").
+// Dynamic LDS: [cols][ROWS] float | NWALK x top_stride | ring.
 
 template <int ROWS>
 struct RingGeom {
@@ -445,10 +442,7 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
 
     float *tile = reinterpret_cast<float *>(smem);
     unsigned char *slots = smem + (size_t)cols * ROWS * sizeof(float);
-    volatile float *ring_vals = reinterpret_cast<volatile float *>(slots + (size_t)NWALK * top_stride);
-    volatile uint32_t *ring_ready = reinterpret_cast<volatile uint32_t *>(
-        slots + (size_t)NWALK * top_stride + (size_t)RING * ROWS * sizeof(float));
-    volatile uint32_t *consumed = ring_ready + RING;
+    const LdsRing<RING, ROWS> ring(slots + (size_t)NWALK * top_stride);
 
     const size_t row0 = (size_t)blockIdx.x * ROWS;
 
@@ -472,8 +466,7 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
             tile[f * ROWS + trow] = grow < rows ? data[grow * (size_t)cols + f] : 0.0f;
         }
     }
-    if (tid < RING) ring_ready[tid] = 0u;
-    if (tid == RING) *consumed = 0u;
+    TAHOE_RING_RESET(ring, RING, tid);
 
     if (wave == NWALK) {
         // ================= consumer: ordered accumulation =================
@@ -487,26 +480,17 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
         bool dead = false;
         for (int t0 = 0; t0 < num_trees && !dead; t0 += BATCH) {
             const int nb = min(BATCH, num_trees - t0);
-            int spins = 0;
-            for (;;) {
-                const bool ok = lane >= nb || ring_ready[(t0 + lane) % RING] == (uint32_t)(t0 + lane + 1);
-                if (__ballot(ok) == ~0ull) break;
-                if (++spins > kRingSpinLimit) {
-                    dead = true;
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(2);
-            }
+            TAHOE_RING_WAIT_READY(ring, RING, t0, nb, lane, 2, dead);
             if (dead) break;
+            TAHOE_LDS_ACQUIRE();  // the values are read after the flags
             for (int j = 0; j < nb; ++j) {
                 const int e = (t0 + j) % RING;
 #pragma unroll
-                for (int k = 0; k < K; ++k) sum[k] += ring_vals[e * ROWS + k * 64 + lane];  // tree order
+                for (int k = 0; k < K; ++k) sum[k] += ring.vals[e * ROWS + k * 64 + lane];  // tree order
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if (lane == 0) *consumed = (uint32_t)(t0 + nb);
+            ring.release(t0 + nb, lane);
         }
-        if (dead && lane == 0) atomicOr(error_flag, 1);
+        ring_dead(dead, lane, error_flag);
         if (sums) {
 #pragma unroll
             for (int k = 0; k < K; ++k) {
@@ -640,24 +624,14 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
             }
         }
         // ---- hand the leaf values to the consumer ----
-        if (t >= RING) {
-            int spins = 0;
-            while (*consumed < (uint32_t)(t - RING + 1)) {
-                if (++spins > kRingSpinLimit) {
-                    dead = true;
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(2);
-            }
-        }
+        TAHOE_RING_WAIT_FREE(ring, RING, t, 2, dead);
         const int e = t % RING;
 #pragma unroll
-        for (int k = 0; k < K; ++k) ring_vals[e * ROWS + k * 64 + lane] = v[k];
-        TAHOE_LDS_RELEASE();  // values before the flag: a wave's LDS operations are performed in issue order
-        if (lane == 0) ring_ready[e] = (uint32_t)(t + 1);
+        for (int k = 0; k < K; ++k) ring.vals[e * ROWS + k * 64 + lane] = v[k];
+        TAHOE_RING_PUBLISH(ring, RING, t, lane == 0);
         if (more) commit_top();  // this wave's reads of its slot are done (in-order LDS)
     }
-    if (dead && lane == 0) atomicOr(error_flag, 1);
+    ring_dead(dead, lane, error_flag);
 }
 
 // transform_k (Struct.h:196-209) with the CPU predictor's arithmetic (BaseTahoeTest.h:467-472):
@@ -738,7 +712,7 @@ static long long tilering_lds_bytes(const tahoe_forest *f, int tile_rows)
     const int nwalk = tile_rows == 64 ? 8 : 4;
     const int ring = tile_rows == 64 ? RingGeom<64>::RING : RingGeom<128>::RING;
     return (long long)f->p.num_cols * tile_rows * 4 + (long long)nwalk * top_stride_bytes(f->top_levels) +
-           (long long)ring * tile_rows * 4 + (ring + 1) * 4LL;
+           RingLayout{ring, tile_rows}.bytes();
 }
 
 // Rows per TILERING tile: 64 (8 walkers x 1 chain) or 128 (4 walkers x 2 chains); 0 = unavailable.

@@ -148,6 +148,91 @@ __device__ __forceinline__ void lds_flag_store(uint32_t *p, uint32_t v)
 #define TAHOE_LDS_ACQUIRE() asm volatile("" ::: "memory")
 #endif
 
+// ---- the LDS tree ring ("The LDS tree ring") ----
+// Walker waves hand the leaf values of tree t to one consumer wave, which adds them in tree order.  LDS: vals[RING][ROWS] f32 |
+// ready[RING] (tree + 1 of the entry's values) | consumed (trees the consumer has added).  Every spin is bounded.
+constexpr int kRingSpinLimit = 1 << 22;
+
+// Where the three parts lie, for the host's LDS sizes and the kernels' pointers alike
+struct RingLayout {
+    int entries, rows;  // trees in flight, floats per tree
+    __host__ __device__ constexpr long long ready_offset() const { return 4LL * entries * rows; }
+    __host__ __device__ constexpr long long consumed_offset() const { return ready_offset() + 4LL * entries; }
+    __host__ __device__ constexpr long long bytes() const { return consumed_offset() + 4; }
+};
+
+// A kernel's view of its ring at `base`
+template <int RING, int ROWS>
+struct LdsRing {
+    float *vals;
+    uint32_t *ready;
+    uint32_t *consumed;
+    __device__ __forceinline__ explicit LdsRing(unsigned char *base)
+        : vals(reinterpret_cast<float *>(base)), ready(reinterpret_cast<uint32_t *>(vals + RING * ROWS)), consumed(ready + RING)
+    {
+    }
+    // Consumer: trees before `upto` are added -- their entries are free once the wave's reads of them have completed
+    __device__ __forceinline__ void release(int upto, int lane) const
+    {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        if (lane == 0) lds_flag_store(consumed, (uint32_t)upto);
+    }
+};
+
+// The other steps are statement macros over a view `ring` of RING entries: a helper function is optimised on its own before it is
+// inlined, and comes out of that as other code than the same statements written in the kernel.
+// Every flag 0 (nothing published, nothing consumed), by the workgroup's threads tid, before the first barrier
+#define TAHOE_RING_RESET(ring, RING, tid)                   \
+    {                                                       \
+        if ((tid) < (RING)) (ring).ready[tid] = 0u;         \
+        if ((tid) == (RING)) *(ring).consumed = 0u;         \
+    }
+// ... for rings of more entries than the workgroup has threads (NT)
+#define TAHOE_RING_RESET_STRIDED(ring, RING, tid, NT)                    \
+    {                                                                    \
+        for (int e_ = (tid); e_ < (RING); e_ += (NT)) (ring).ready[e_] = 0u; \
+        if ((tid) == 0) *(ring).consumed = 0u;                           \
+    }
+// Consumer: wait until trees t0 .. t0 + nb - 1 (nb <= 64) are published; a spin-out sets dead (the caller then stops)
+#define TAHOE_RING_WAIT_READY(ring, RING, t0, nb, lane, SLEEP, dead)                                                          \
+    {                                                                                                                       \
+        int spins_ = 0;                                                                                                     \
+        for (;;) {                                                                                                          \
+            const bool ok_ = (lane) >= (nb) || lds_flag_load(&(ring).ready[((t0) + (lane)) % (RING)]) == (uint32_t)((t0) + (lane) + 1); \
+            if (__ballot(ok_) == ~0ull) break;                                                                              \
+            if (++spins_ > kRingSpinLimit) {                                                                                \
+                dead = true;                                                                                                \
+                break;                                                                                                      \
+            }                                                                                                               \
+            __builtin_amdgcn_s_sleep(SLEEP);                                                                                \
+        }                                                                                                                   \
+    }
+// Walker: wait until the entry of tree t is free (tree t - RING consumed); a spin-out sets dead, and the walker still publishes
+#define TAHOE_RING_WAIT_FREE(ring, RING, t, SLEEP, dead)                                   \
+    if ((t) >= (RING)) {                                                                   \
+        int spins_ = 0;                                                                    \
+        while (lds_flag_load((ring).consumed) < (uint32_t)((t) - (RING) + 1)) {            \
+            if (++spins_ > kRingSpinLimit) {                                               \
+                dead = true;                                                               \
+                break;                                                                     \
+            }                                                                              \
+            __builtin_amdgcn_s_sleep(SLEEP);                                               \
+        }                                                                                  \
+    }
+// Walker, after storing tree t's values to vals[t % RING]: the values before the flag (a wave's LDS operations are performed in
+// issue order), the flag from the lane(s) `leader`
+#define TAHOE_RING_PUBLISH(ring, RING, t, leader)                                                  \
+    {                                                                                              \
+        TAHOE_LDS_RELEASE();                                                                       \
+        if (leader) lds_flag_store(&(ring).ready[(t) % (RING)], (uint32_t)((t) + 1));              \
+    }
+
+// The error flag of a wave whose ring spin ran out
+__device__ __forceinline__ void ring_dead(bool dead, int lane, int *error_flag)
+{
+    if (dead && lane == 0) atomicOr(error_flag, 1);
+}
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is per function and process-wide, not per handle: always raise it to
 // the device limit (less the kernel's static LDS), so that handles of different shapes can coexist in one process.
 inline hipError_t allow_max_lds(const void *fn, int limit)

@@ -48,8 +48,8 @@ constexpr int kConsSleep = 1, kWalkSleep = 16;
 constexpr int kConsSleep8 = 1, kWalkSleep8 = 8;
 
 // ------------------------------------------------------------------------------------------------
-// (2) the walk.  Dynamic LDS: tile [cols][128] u16 | NWALK slots of (4 << L) bytes | ring [RING][64 K] f32 |
-// ready[RING] | consumed.
+// (2) the walk.  Dynamic LDS: tile [cols][128] u16 | NWALK slots of (4 << L) bytes | the LDS tree ring of RING entries x 64 K
+// rows (forest_internal.h; DESIGN.md, "The LDS tree ring").
 // REG (the form K3 runs; NARROW node words with fid << 7, num_cols <= 256): the tile is K regions of 64 rows, region k =
 // [fid][64] u16 at LDS address k * 32 KiB (so that the column offset fid * 128 and the region base never share a bit and
 // one v_bfi forms the read address), chain k of a lane walks row 64 k + lane.  K = 3: a top staged once serves 192 rows
@@ -106,9 +106,7 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
     const int t_end = SPLIT ? (int)((long long)num_trees * (slice + 1) / slices) : num_trees;
     unsigned char *slots = smem + (REG ? (size_t)NREG * REGB : LDSX ? (size_t)cols * TR * sizeof(uint16_t) : 0);
     const unsigned char *gx = reinterpret_cast<const unsigned char *>(xq + (size_t)tile_id * ((size_t)cols * TR));
-    float *ring_vals = reinterpret_cast<float *>(slots + (size_t)NWALK * slot_bytes);
-    uint32_t *ring_ready = reinterpret_cast<uint32_t *>(ring_vals + RING * TR);
-    uint32_t *consumed = ring_ready + RING;
+    const LdsRing<RING, TR> ring(slots + (size_t)NWALK * slot_bytes);
 
     const size_t row0 = row_begin + (size_t)tile_id * TR;
     if (LDSX && NARROW && (uint32_t)reinterpret_cast<uintptr_t>(tile) != 0u) {
@@ -133,8 +131,7 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
         const int n16 = cols * TR * 2 / 16;
         for (int e = tid; e < n16; e += NT) dst[e] = src[e];
     }
-    if (tid < RING) ring_ready[tid] = 0u;
-    if (tid == RING) *consumed = 0u;
+    TAHOE_RING_RESET(ring, RING, tid);
 
     if (wave == NWALK) {
         // ================= consumer: ordered accumulation =================
@@ -166,22 +163,13 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
         bool dead = false;
         for (int t0 = 0; t0 < num_trees && !dead; t0 += BATCH) {
             const int nb = min(BATCH, num_trees - t0);
-            int spins = 0;
-            for (;;) {
-                const bool ok = lane >= nb || lds_flag_load(&ring_ready[(t0 + lane) % RING]) == (uint32_t)(t0 + lane + 1);
-                if (__ballot(ok) == ~0ull) break;
-                if (++spins > kQSpinLimit) {
-                    dead = true;
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(CODE8 && K > 2 ? kConsSleep8 : kConsSleep);
-            }
+            TAHOE_RING_WAIT_READY(ring, RING, t0, nb, lane, (CODE8 && K > 2 ? kConsSleep8 : kConsSleep), dead);
             if (dead) break;
             TAHOE_LDS_ACQUIRE();  // the values are read after the flags
             for (int j = 0; j < nb; ++j) {
                 const int e = (t0 + j) % RING;
 #pragma unroll
-                for (int k = 0; k < K; ++k) sum[k] += ring_vals[e * TR + k * 64 + lane];  // tree order
+                for (int k = 0; k < K; ++k) sum[k] += ring.vals[e * TR + k * 64 + lane];  // tree order
                 if (MC && t0 + j + 1 == cend) {
                     flush();
 #pragma unroll
@@ -190,10 +178,9 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
                     cend += ctrees;
                 }
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if (lane == 0) lds_flag_store(consumed, (uint32_t)(t0 + nb));
+            ring.release(t0 + nb, lane);
         }
-        if (dead && lane == 0) atomicOr(error_flag, 1);
+        ring_dead(dead, lane, error_flag);
         if (MC) {
             if (num_trees > cend - ctrees) flush();  // the group ends inside class cls
         } else if (sums) {
@@ -278,21 +265,11 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
                 }
                 return;
             }
-            if (t >= RING) {  // ring entry still in use by tree t - RING?
-                int spins = 0;
-                while (lds_flag_load(consumed) < (uint32_t)(t - RING + 1)) {
-                    if (++spins > kQSpinLimit) {
-                        dead = true;
-                        break;
-                    }
-                    __builtin_amdgcn_s_sleep(CODE8 && K > 2 ? kWalkSleep8 : kWalkSleep);
-                }
-            }
+            TAHOE_RING_WAIT_FREE(ring, RING, t, (CODE8 && K > 2 ? kWalkSleep8 : kWalkSleep), dead);
             const int e = t % RING;
     #pragma unroll
-            for (int k = 0; k < K; ++k) ring_vals[e * TR + k * 64 + lane] = v[k];
-            TAHOE_LDS_RELEASE();  // values before the flag: a wave's LDS operations are performed in issue order
-            if (lane == 0) lds_flag_store(&ring_ready[e], (uint32_t)(t + 1));
+            for (int k = 0; k < K; ++k) ring.vals[e * TR + k * 64 + lane] = v[k];
+            TAHOE_RING_PUBLISH(ring, RING, t, lane == 0);
         };
         int t_p = -1;  // tree whose bottom blocks are in flight
         uint4 na_p[K] = {}, nb_p[K] = {};
@@ -402,7 +379,7 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
         run(std::true_type{});
     else
         run(std::false_type{});
-    if (dead && lane == 0) atomicOr(error_flag, 1);
+    ring_dead(dead, lane, error_flag);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -443,9 +420,7 @@ __global__ void __launch_bounds__(16 * 64)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     uint16_t *tile = reinterpret_cast<uint16_t *>(smem);
     unsigned char *slots = smem + (size_t)cols * RT * sizeof(uint16_t);
-    float *ring_vals = reinterpret_cast<float *>(slots + (size_t)NWALK * slot_bytes);  // slot = TPW tops, <= 4 KiB
-    uint32_t *ring_ready = reinterpret_cast<uint32_t *>(ring_vals + RE * RT);
-    uint32_t *consumed = ring_ready + RE;
+    const LdsRing<RE, RT> ring(slots + (size_t)NWALK * slot_bytes);  // slot = TPW tops, <= 4 KiB
     const size_t row0 = (size_t)blockIdx.x * RT;
     {
         const uint4 *src = reinterpret_cast<const uint4 *>(xq + (size_t)blockIdx.x * ((size_t)cols * RT));
@@ -453,8 +428,7 @@ __global__ void __launch_bounds__(16 * 64)
         const int n16 = cols * RT * 2 / 16;
         for (int e = tid; e < n16; e += NT) dst[e] = src[e];
     }
-    for (int e = tid; e < RE; e += NT) ring_ready[e] = 0u;
-    if (tid == 0) *consumed = 0u;
+    TAHOE_RING_RESET_STRIDED(ring, RE, tid, NT);
 
     if (wave == NWALK) {
         // ================= consumer: ordered accumulation, lane = row =================
@@ -477,16 +451,7 @@ __global__ void __launch_bounds__(16 * 64)
         bool dead = false;
         for (int t0 = 0; t0 < num_trees && !dead; t0 += NBATCH) {
             const int nb = min(NBATCH, num_trees - t0);
-            int spins = 0;
-            for (;;) {
-                const bool ok = lane >= nb || lds_flag_load(&ring_ready[(t0 + lane) % RE]) == (uint32_t)(t0 + lane + 1);
-                if (__ballot(ok) == ~0ull) break;
-                if (++spins > kQSpinLimit) {
-                    dead = true;
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(2);
-            }
+            TAHOE_RING_WAIT_READY(ring, RE, t0, nb, lane, 2, dead);
             if (dead) break;
             TAHOE_LDS_ACQUIRE();  // the values are read after the flags
             if (lane < RT) {  // tree order; eight loads in flight, eight adds in order (one tree at a time, a load's
@@ -495,7 +460,7 @@ __global__ void __launch_bounds__(16 * 64)
                 for (; jj + 8 <= nb; jj += 8) {
                     float v[8];
 #pragma unroll
-                    for (int u = 0; u < 8; ++u) v[u] = ring_vals[((t0 + jj + u) % RE) * RT + lane];
+                    for (int u = 0; u < 8; ++u) v[u] = ring.vals[((t0 + jj + u) % RE) * RT + lane];
                     if (MC) {
 #pragma unroll
                         for (int u = 0; u < 8; ++u) add(v[u], t0 + jj + u);
@@ -505,14 +470,13 @@ __global__ void __launch_bounds__(16 * 64)
                     }
                 }
                 if (MC)
-                    for (; jj < nb; ++jj) add(ring_vals[((t0 + jj) % RE) * RT + lane], t0 + jj);
+                    for (; jj < nb; ++jj) add(ring.vals[((t0 + jj) % RE) * RT + lane], t0 + jj);
                 else
-                    for (; jj < nb; ++jj) sum += ring_vals[((t0 + jj) % RE) * RT + lane];
+                    for (; jj < nb; ++jj) sum += ring.vals[((t0 + jj) % RE) * RT + lane];
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if (lane == 0) lds_flag_store(consumed, (uint32_t)(t0 + nb));
+            ring.release(t0 + nb, lane);
         }
-        if (dead && lane == 0) atomicOr(error_flag, 1);
+        ring_dead(dead, lane, error_flag);
         if (MC) {
             if (sums && lane < RT && irow < rows && num_trees > cend - ctrees) sums[irow * (size_t)num_classes + cls] = sum;  // ends inside a class
         } else if (sums && lane < RT && irow < rows) {
@@ -583,26 +547,17 @@ __global__ void __launch_bounds__(16 * 64)
                 }
             }
             const int t_last = min(g * TPG + TPG - 1, num_trees - 1);
-            if (t_last >= RE) {  // the iteration's ring entries still in use?
-                int spins = 0;
-                while (lds_flag_load(consumed) < (uint32_t)(t_last - RE + 1)) {
-                    if (++spins > kQSpinLimit) {
-                        dead = true;
-                        break;
-                    }
-                    __builtin_amdgcn_s_sleep(1);
-                }
-            }
+            TAHOE_RING_WAIT_FREE(ring, RE, t_last, 1, dead);  // the iteration's entries
 #pragma unroll
             for (int k = 0; k < KG; ++k) {
                 const int t = g * TPG + k * TPW + j;
-                if (t < num_trees) ring_vals[(t % RE) * RT + r] = v[k];
+                if (t < num_trees) ring.vals[(t % RE) * RT + r] = v[k];
             }
-            TAHOE_LDS_RELEASE();  // values before the flags: a wave's LDS operations are performed in issue order
+            TAHOE_LDS_RELEASE();  // TAHOE_RING_PUBLISH for KG trees: one release before the KG flags
 #pragma unroll
             for (int k = 0; k < KG; ++k) {
                 const int t = g * TPG + k * TPW + j;
-                if (r == 0 && t < num_trees) lds_flag_store(&ring_ready[t % RE], (uint32_t)(t + 1));
+                if (r == 0 && t < num_trees) lds_flag_store(&ring.ready[t % RE], (uint32_t)(t + 1));
             }
         };
         int g_p = -1;  // iteration whose bottom blocks are in flight
@@ -674,7 +629,7 @@ __global__ void __launch_bounds__(16 * 64)
         run(std::true_type{});
     else
         run(std::false_type{});
-    if (dead && lane == 0) atomicOr(error_flag, 1);
+    ring_dead(dead, lane, error_flag);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -738,8 +693,7 @@ __global__ void __launch_bounds__(kOrderedSumThreads) ordered_sum_mc_kernel(cons
 
 static long long qring_lds_for(const tahoe_forest *f, int nwalk, bool lds_tile = true)
 {
-    return (lds_tile ? (long long)f->p.num_cols * kQRows * 2 : 0) + (long long)nwalk * kQSlotBytes +
-           (long long)kQRing * kQRows * 4 + (kQRing + 1) * 4LL;
+    return (lds_tile ? (long long)f->p.num_cols * kQRows * 2 : 0) + (long long)nwalk * kQSlotBytes + RingLayout{kQRing, kQRows}.bytes();
 }
 
 constexpr int kGxWalkers = 15;  // walkers of the GX form (no LDS tile)
@@ -751,8 +705,8 @@ static int qwide_lw_max(int top_levels, int rt) { return std::min(top_levels, rt
 static long long qwide_slot_bytes(int lw, int rt) { return (64 / rt) * (long long)std::max(1, (1 << lw) >> 2) * 16; }
 static long long qwide_lds_for(const tahoe_forest *f, int rt, int lw, int kg = 1)
 {
-    const long long ring = kg > 1 ? kWideRingBytesK : kWideRingBytes;
-    return (long long)f->p.num_cols * rt * 2 + 15LL * kg * qwide_slot_bytes(lw, rt) + ring + (ring / (rt * 4) + 1) * 4LL;
+    const int ring = kg > 1 ? kWideRingBytesK : kWideRingBytes;
+    return (long long)f->p.num_cols * rt * 2 + 15LL * kg * qwide_slot_bytes(lw, rt) + RingLayout{ring / (rt * 4), rt}.bytes();
 }
 // tree groups per walker (chains per lane) of the wide form: 3 when three groups of tops fill at most 256 16-byte chunks and
 // fit LDS beside the tile and the larger ring, else 1

@@ -67,7 +67,6 @@ constexpr int kQRows = 128;                 // rows per tile
 // 32/4 4.14, 24/6 4.10, 24/3 4.28; a batch of 2 or 1 makes the consumer's polling the bottleneck (4.9 / 6.6 ms).
 constexpr int kQRing = 24;   // ring entries (trees)
 constexpr int kQBatch = 4;   // trees the consumer takes per poll
-constexpr int kQSpinLimit = 1 << 22;
 constexpr int kQSlotBytes = 4096;            // LDS per walker: a 10-level top (2^10 u32)
 // Region form (NARROW, num_cols <= 256): a tile is K regions of 64 rows, each [fid][64] u16 at a multiple of 32 KiB in LDS.
 // K = 3: 14 walkers x 3 chains and a ring of 10 (96 + 56 + 7.5 KiB = 163,372 B of the 163,840); K = 2: 15 walkers x 2
@@ -81,7 +80,7 @@ constexpr int kQMaxTable = 32767;
 // LDS of the region form: K regions of 32 KiB, walker slots, ring
 inline long long qreg_lds_for(int k, int nwalk, int ring, bool code8 = false, int regb = kRegBytes)
 {
-    return (long long)(code8 ? k / 2 : k) * regb + (long long)nwalk * kQSlotBytes + (long long)ring * k * kRegRows * 4 + (ring + 1) * 4LL;
+    return (long long)(code8 ? k / 2 : k) * regb + (long long)nwalk * kQSlotBytes + RingLayout{ring, k * kRegRows}.bytes();
 }
 // u8 form: six chains (384-row tiles of three 128-row regions) for whole waves of workgroups, two chains (one region) for
 // the remainder; walkers / ring / consumer batch of the 384-row tile: 14 / 5 / 2 (96 KiB + 14 x 4 KiB + 5 x 1.5 KiB = 163,352 B); KR3

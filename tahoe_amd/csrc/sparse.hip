@@ -150,14 +150,12 @@ __global__ void __launch_bounds__(kBlock) sparse_kernel(const tahoe_sparse_node 
 // what bounds the plain kernel (64 lanes = 64 cache lines per step through the texture path, 12-byte nodes);
 // here only the steps below the top pay them, with 8-byte nodes.
 // Sums: irregular trees take 4 to 24 steps, so a barrier per round of trees would make every wave wait for the
-// deepest tree of the round.  Instead the walkers publish leaf values through an LDS ring (vals, then a ready flag;
-// LDS operations of one CU complete in order) and the last wave adds them in tree order, exactly the scheme of
-// qring_kernel: walkers wait only for `consumed` (ring capacity), the consumer only for trees whose walkers
-// cannot be blocked; every spin is bounded and raises the error flag.
+// deepest tree of the round.  Instead the walkers publish leaf values through the LDS tree ring (forest_internal.h;
+// DESIGN.md, "The LDS tree ring") and the last wave adds them in tree order.  This kernel writes the ring's steps out
+// by hand: through the shared view and macros its walker compiles to a different instruction schedule.
 constexpr int kSTop = 512;    // nodes per slot (8 B each)
 constexpr int kSRing = 32;    // ring entries (trees)
 constexpr int kSBatch = 4;    // trees the consumer takes per poll (K5: 16 -> 5.34 ms, 8 -> 5.19, 4 -> 5.15)
-constexpr int kSSpinLimit = 1 << 22;
 // MC: as sparse_kernel's, in the consumer wave.
 template <int NW, bool WRITE_LEAF, bool MC = false>
 __global__ void __launch_bounds__(NW * 64) sparse_top_kernel(const uint2 *__restrict__ cnodes, const int32_t *__restrict__ ctrees,
@@ -208,7 +206,7 @@ __global__ void __launch_bounds__(NW * 64) sparse_top_kernel(const uint2 *__rest
             for (;;) {
                 const bool ok = lane >= nb || lds_flag_load(&ring_ready[(t0 + lane) % kSRing]) == (uint32_t)(t0 + lane + 1);
                 if (__ballot(ok) == ~0ull) break;
-                if (++spins > kSSpinLimit) {
+                if (++spins > kRingSpinLimit) {
                     dead = true;
                     break;
                 }
@@ -289,7 +287,7 @@ __global__ void __launch_bounds__(NW * 64) sparse_top_kernel(const uint2 *__rest
         if (t >= kSRing) {  // ring entry still in use by tree t - kSRing?
             int spins = 0;
             while (lds_flag_load(consumed) < (uint32_t)(t - kSRing + 1)) {
-                if (++spins > kSSpinLimit) {
+                if (++spins > kRingSpinLimit) {
                     dead = true;
                     break;
                 }
@@ -346,9 +344,7 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     unsigned char *slots = smem + (size_t)K * kRegBytes;
-    float *ring_vals = reinterpret_cast<float *>(slots + (size_t)NWALK * kQSlotBytes);
-    uint32_t *ring_ready = reinterpret_cast<uint32_t *>(ring_vals + RING * TR);
-    uint32_t *consumed = ring_ready + RING;
+    const LdsRing<RING, TR> ring(slots + (size_t)NWALK * kQSlotBytes);
     const size_t row0 = row_begin + (size_t)blockIdx.x * TR;
     if ((uint32_t)reinterpret_cast<uintptr_t>(smem) != 0u) {  // q_xread's v_bfi needs the regions at LDS address 0
         if (tid == 0) atomicOr(error_flag, 2);
@@ -362,8 +358,7 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
             for (int e = tid; e < n16; e += NT) dst[e] = src[e];
         }
     }
-    if (tid < RING) ring_ready[tid] = 0u;
-    if (tid == RING) *consumed = 0u;
+    TAHOE_RING_RESET(ring, RING, tid);
 
     if (wave == NWALK) {
         // ================= consumer: ordered accumulation =================
@@ -394,22 +389,13 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
         bool dead = false;
         for (int t0 = 0; t0 < num_trees && !dead; t0 += BATCH) {
             const int nb = min(BATCH, num_trees - t0);
-            int spins = 0;
-            for (;;) {
-                const bool ok = lane >= nb || lds_flag_load(&ring_ready[(t0 + lane) % RING]) == (uint32_t)(t0 + lane + 1);
-                if (__ballot(ok) == ~0ull) break;
-                if (++spins > kSSpinLimit) {
-                    dead = true;
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(1);
-            }
+            TAHOE_RING_WAIT_READY(ring, RING, t0, nb, lane, 1, dead);
             if (dead) break;
             TAHOE_LDS_ACQUIRE();  // the values are read after the flags
             for (int j = 0; j < nb; ++j) {
                 const int e = (t0 + j) % RING;
 #pragma unroll
-                for (int k = 0; k < K; ++k) sum[k] += ring_vals[e * TR + k * 64 + lane];  // tree order
+                for (int k = 0; k < K; ++k) sum[k] += ring.vals[e * TR + k * 64 + lane];  // tree order
                 if (MC && t0 + j + 1 == cend) {
                     flush();
 #pragma unroll
@@ -418,10 +404,9 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
                     cend += class_trees;
                 }
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if (lane == 0) lds_flag_store(consumed, (uint32_t)(t0 + nb));
+            ring.release(t0 + nb, lane);
         }
-        if (dead && lane == 0) atomicOr(error_flag, 1);
+        ring_dead(dead, lane, error_flag);
         if (MC) {
             if (num_trees > cend - class_trees) flush();  // the group ends inside class cls
         } else if (sums) {
@@ -512,21 +497,11 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
                                     : row * (size_t)total_trees + tree_lo + t] = corig[ctrees[tree_lo + t] + cpos_p[k]];
                 }
             }
-            if (t >= RING) {  // ring entry still in use by tree t - RING?
-                int spins = 0;
-                while (lds_flag_load(consumed) < (uint32_t)(t - RING + 1)) {
-                    if (++spins > kSSpinLimit) {
-                        dead = true;
-                        break;
-                    }
-                    __builtin_amdgcn_s_sleep(8);
-                }
-            }
+            TAHOE_RING_WAIT_FREE(ring, RING, t, 8, dead);
             const int e = t % RING;
 #pragma unroll
-            for (int k = 0; k < K; ++k) ring_vals[e * TR + k * 64 + lane] = __uint_as_float(entry_p[k]);
-            TAHOE_LDS_RELEASE();  // values before the flag: a wave's LDS operations are performed in issue order
-            if (lane == 0) lds_flag_store(&ring_ready[e], (uint32_t)(t + 1));
+            for (int k = 0; k < K; ++k) ring.vals[e * TR + k * 64 + lane] = __uint_as_float(entry_p[k]);
+            TAHOE_RING_PUBLISH(ring, RING, t, lane == 0);
         };
         for (int t = wave; t < num_trees && !dead; t += NWALK) {
             const bool more = t + NWALK < num_trees;
@@ -627,7 +602,7 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
         run(std::true_type{});
     else
         run(std::false_type{});
-    if (dead && lane == 0) atomicOr(error_flag, 1);
+    ring_dead(dead, lane, error_flag);
 }
 
 bool sparse_q_available(const tahoe_forest *f) { return f->sp && f->sp->qtop && f->q; }
@@ -679,8 +654,7 @@ static tahoe_status sparse_q_launch(tahoe_forest *f, float *sums, uint32_t *leaf
 
 static long long sparse_top_lds(const tahoe_forest *f, int nw)
 {
-    return (long long)f->p.num_cols * kTileRows * 4 + (long long)(nw - 1) * kSTop * 8 + (long long)kSRing * kTileRows * 4 +
-           (kSRing + 1) * 4LL;
+    return (long long)f->p.num_cols * kTileRows * 4 + (long long)(nw - 1) * kSTop * 8 + RingLayout{kSRing, kTileRows}.bytes();
 }
 
 // waves per workgroup of sparse_top_kernel for this handle; 0 = that form is unavailable

@@ -27,7 +27,6 @@
 namespace tahoe {
 
 constexpr int kWfRingBytes = 8192;
-constexpr int kWfSpinLimit = 1 << 22;
 
 template <int RT, int NWALK, bool WRITE_LEAF>
 __global__ void __launch_bounds__((NWALK + 1) * 64)
@@ -49,15 +48,13 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
     float *tile = reinterpret_cast<float *>(smem);
     const int slot_bytes = TPW * tstride * 8;
     unsigned char *slots = smem + (size_t)RT * stride * sizeof(float);
-    float *ring_vals = reinterpret_cast<float *>(slots + (size_t)NWALK * slot_bytes);
-    uint32_t *ring_ready = reinterpret_cast<uint32_t *>(ring_vals + RE * RT);
-    uint32_t *consumed = ring_ready + RE;
-    uint32_t *ms_seen = consumed + 1;
+    const LdsRing<RE, RT> ring(slots + (size_t)NWALK * slot_bytes);
+    uint32_t *ms_seen = ring.consumed + 1;
     const size_t row0 = (size_t)blockIdx.x * RT;
 
-    for (int e = tid; e < RE; e += NT) ring_ready[e] = 0u;
+    for (int e = tid; e < RE; e += NT) ring.ready[e] = 0u;  // TAHOE_RING_RESET_STRIDED, and ms_seen
     if (tid == 0) {
-        *consumed = 0u;
+        *ring.consumed = 0u;
         *ms_seen = 0u;
     }
     __syncthreads();  // ms_seen is zero before anyone sets it
@@ -94,16 +91,7 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
         bool dead = false;
         for (int t0 = 0; t0 < num_trees && !dead; t0 += NBATCH) {
             const int nb = min(NBATCH, num_trees - t0);
-            int spins = 0;
-            for (;;) {
-                const bool ok = lane >= nb || lds_flag_load(&ring_ready[(t0 + lane) % RE]) == (uint32_t)(t0 + lane + 1);
-                if (__ballot(ok) == ~0ull) break;
-                if (++spins > kWfSpinLimit) {
-                    dead = true;
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(2);
-            }
+            TAHOE_RING_WAIT_READY(ring, RE, t0, nb, lane, 2, dead);
             if (dead) break;
             TAHOE_LDS_ACQUIRE();  // the values are read after the flags
             if (lane < RT) {  // tree order; eight loads in flight, eight adds in order (one tree at a time, a load's
@@ -112,16 +100,15 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
                 for (; jj + 8 <= nb; jj += 8) {
                     float v[8];
 #pragma unroll
-                    for (int u = 0; u < 8; ++u) v[u] = ring_vals[((t0 + jj + u) % RE) * RT + lane];
+                    for (int u = 0; u < 8; ++u) v[u] = ring.vals[((t0 + jj + u) % RE) * RT + lane];
 #pragma unroll
                     for (int u = 0; u < 8; ++u) sum += v[u];
                 }
-                for (; jj < nb; ++jj) sum += ring_vals[((t0 + jj) % RE) * RT + lane];
+                for (; jj < nb; ++jj) sum += ring.vals[((t0 + jj) % RE) * RT + lane];
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if (lane == 0) lds_flag_store(consumed, (uint32_t)(t0 + nb));
+            ring.release(t0 + nb, lane);
         }
-        if (dead && lane == 0) atomicOr(error_flag, 1);
+        ring_dead(dead, lane, error_flag);
         if (sums && lane < RT && irow < rows) sums[irow] = sum;
         return;
     }
@@ -184,19 +171,9 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
                     leaf_out[row * (size_t)num_trees + t] = leaf_orig[(size_t)t * ((size_t)n_blocks * 4) + (size_t)bs * 4 + 2 * c0 + c1];
             }
             const int t_last = min(g * TPW + TPW - 1, num_trees - 1);
-            if (t_last >= RE) {  // the group's ring entries still in use?
-                int spins = 0;
-                while (lds_flag_load(consumed) < (uint32_t)(t_last - RE + 1)) {
-                    if (++spins > kWfSpinLimit) {
-                        dead = true;
-                        break;
-                    }
-                    __builtin_amdgcn_s_sleep(1);
-                }
-            }
-            if (t < num_trees) ring_vals[(t % RE) * RT + r] = v;
-            TAHOE_LDS_RELEASE();  // values before the flags: a wave's LDS operations are performed in issue order
-            if (r == 0 && t < num_trees) lds_flag_store(&ring_ready[t % RE], (uint32_t)(t + 1));
+            TAHOE_RING_WAIT_FREE(ring, RE, t_last, 1, dead);  // the group's entries
+            if (t < num_trees) ring.vals[(t % RE) * RT + r] = v;
+            TAHOE_RING_PUBLISH(ring, RE, t, r == 0 && t < num_trees);
         };
         int g_p = -1;  // group whose bottom blocks are in flight
         uint4 a_p = {}, b_p = {}, c_p = {};
@@ -241,7 +218,7 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
         run(std::true_type{});
     else
         run(std::false_type{});
-    if (dead && lane == 0) atomicOr(error_flag, 1);
+    ring_dead(dead, lane, error_flag);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -250,8 +227,8 @@ static int wf_lw_max(int rt) { return rt == 32 ? 8 : rt == 16 ? 7 : 6; }  // (64
 static int wf_tstride(int lw) { return std::max(2, 1 << lw); }
 static long long wf_lds(int cols, int rt, int nwalk, int lw)
 {
-    const long long re = kWfRingBytes / (rt * 4);
-    return (long long)rt * (cols + 4) * 4 + (long long)nwalk * (64 / rt) * wf_tstride(lw) * 8 + kWfRingBytes + (re + 2) * 4;
+    return (long long)rt * (cols + 4) * 4 + (long long)nwalk * (64 / rt) * wf_tstride(lw) * 8 + RingLayout{kWfRingBytes / (rt * 4), rt}.bytes() +
+           4;  // ring, ms_seen
 }
 
 int widef_rows(const tahoe_forest *f) { return f->wf ? f->wf->rt : 0; }

@@ -59,7 +59,6 @@ constexpr int kWkLoaders = 4;   // loader waves (= the fewest row slots)
 constexpr int kWkWalkers = 11;  // walker waves; 4 loaders + 1 summer + 11 walkers = 16 waves (K2: 0.59 ms; 5 + 10: 0.60, 3 + 12: 0.62)
 constexpr int kWkSumRows = 64;                // rows the summer wave adds at once, one lane each
 constexpr int kWkChains = 2;  // 64-tree chunks of one row a walker wave walks at once (chains per lane; 3: 0.63 ms, 4: 0.61)
-constexpr int kWkSpinLimit = 1 << 22;
 constexpr uint32_t kWkMissing = 0xFFFFu;
 // Largest estimated share of compares with equal keys at which the create-time rule still takes this form (K2's uniform
 // thresholds: 1.6e-5, i.e. 0.1 % of the wave-levels on the float32 path; 1e-4 is ~0.6 % of them).
@@ -207,7 +206,7 @@ __global__ void __launch_bounds__((kWkLoaders + 1 + kWkWalkers) * 64)
                 const uint32_t need = (uint32_t)nit * (uint32_t)(k / S);
                 int spins = 0;
                 while (lds_flag_load(&walked[slot]) < need) {
-                    if (++spins > kWkSpinLimit || lds_flag_load(abort_flag) != 0u) {
+                    if (++spins > kRingSpinLimit || lds_flag_load(abort_flag) != 0u) {
                         dead = true;
                         break;
                     }
@@ -247,7 +246,7 @@ __global__ void __launch_bounds__((kWkLoaders + 1 + kWkWalkers) * 64)
             for (;;) {
                 const bool ok = lds_flag_load(&prog[w]) >= need;
                 if (__ballot(ok) == ~0ull) break;
-                if (++spins > kWkSpinLimit || lds_flag_load(abort_flag) != 0u) {
+                if (++spins > kRingSpinLimit || lds_flag_load(abort_flag) != 0u) {
                     dead = true;
                     break;
                 }
@@ -437,7 +436,7 @@ __global__ void __launch_bounds__((kWkLoaders + 1 + kWkWalkers) * 64)
         {   // the row's keys are in LDS
             int spins = 0;
             while (lds_flag_load(&row_ready[slot]) != (uint32_t)(k + 1)) {
-                if (++spins > kWkSpinLimit || lds_flag_load(abort_flag) != 0u) {
+                if (++spins > kRingSpinLimit || lds_flag_load(abort_flag) != 0u) {
                     dead = true;
                     break;
                 }
