@@ -345,6 +345,49 @@ tahoe_status tahoe_sparse_forest_create(tahoe_forest **out, const int32_t *trees
 tahoe_status tahoe_sparse_forest_create_ex(tahoe_forest **out, const int32_t *trees, const tahoe_sparse_node *nodes,
                                            const float *covers, const tahoe_forest_params *params, int num_classes,
                                            unsigned flags);
+
+/* Categorical splits (XGBoost enable_categorical, LightGBM categorical_feature): internal nodes whose branch tests whether the
+ * row's category is in a set.  The word layout is LightGBM's cat_boundaries / cat_threshold; XGBoost's categories_nodes /
+ * categories_segments / categories lists convert to it directly. */
+typedef struct {
+    int32_t num_splits;            /* categorical internal nodes; 0 = none */
+    const int32_t *node;           /* [num_splits] strictly ascending indices into nodes[] */
+    const int32_t *offset;         /* [num_splits + 1] ascending word offsets into words[], offset[0] == 0 */
+    const uint32_t *words;         /* category c is a member of split k iff c < 32 * (offset[k+1] - offset[k])
+                                      and bit c % 32 of words[offset[k] + c / 32] is set */
+    const uint8_t *members_left;   /* NULL: members go right at every split (XGBoost); else per split, 1 = members go left
+                                      (LightGBM) */
+} tahoe_categorical_splits;
+
+/* tahoe_sparse_forest_create_ex with categorical splits.  At the node of split k (node[k]) `val` is ignored and fid / def_left
+ * keep their meaning; with x = the row's value of feature fid:
+ *   1. If fabsf(x - missing) <= 1e-6f, the row takes the default branch, as at any node: right iff !def_left.
+ *   2. Otherwise member = (x >= 0.0f && x < 32 * nwords) && bit((uint32_t)x), nwords = offset[k+1] - offset[k].  The cast
+ *      truncates, so 2.7 is category 2 and -0.0 is category 0.  NaN, negative values and values past the bitset are never
+ *      members.
+ *   3. right = member != members_left[k] (members_left NULL: right = member).
+ * With members_left == NULL this is XGBoost's Decision rule: members go right, everything else goes left, and NaN goes left as at
+ * every numeric node here.  LightGBM differs in two places: it maps NaN to category 0 unless its missing type is NaN, and it
+ * truncates -0.5 to category 0.  A caller who needs those bits maps such values before the call.
+ * Checks, all before a device is touched, in this order:
+ *   - the checks of tahoe_sparse_forest_create_ex on out, params, num_classes, flags and covers;
+ *   - cats (when not NULL): num_splits < 0 or > num_nodes, NULL node / offset / words with num_splits > 0, node indices not
+ *     strictly ascending or outside [0, num_nodes), offset[0] != 0, offsets that decrease, or a split wider than 2^19 words
+ *     (categories < 2^24, exact in float32): TAHOE_ERR_INVALID_ARG;
+ *   - the forest's structure, as tahoe_sparse_forest_create_ex checks it (TAHOE_ERR_INVALID_FOREST);
+ *   - a listed node that is a leaf, or lies in no tree: TAHOE_ERR_INVALID_FOREST naming the tree and the node (relative to its
+ *     root);
+ *   - num_splits > 0 with TAHOE_CREATE_CONTRIBS or TAHOE_CREATE_APPROX_CONTRIBS (TreeSHAP's path elements are intervals per
+ *     feature and a category set is not one), or with num_cols > 2^29: TAHOE_ERR_UNSUPPORTED.
+ * cats == NULL or num_splits == 0 gives the handle of tahoe_sparse_forest_create_ex.  A handle with splits serves DIRECT, ROWTILE
+ * and TILEBLOCK (AUTO: TILEBLOCK when available, else ROWTILE, else DIRECT) with the float32 sums added in tree order, classes,
+ * output bits, tahoe_forest_predict_accumulate and tahoe_forest_predict_host as tahoe_sparse_forest_create_ex describes them;
+ * QRING is TAHOE_ERR_UNSUPPORTED (its 4-byte node word and its quantiser hold no set test).  Leaf indices stay relative to the
+ * tree's root in the caller's numbering.  The bitsets live on the device (one header word per split beside its words), counted
+ * in tahoe_forest_info.device_bytes. */
+tahoe_status tahoe_sparse_forest_create_cat(tahoe_forest **out, const int32_t *trees, const tahoe_sparse_node *nodes,
+                                            const float *covers, const tahoe_forest_params *params, int num_classes,
+                                            unsigned flags, const tahoe_categorical_splits *cats);
 /* dense2sparse (BaseTahoeTest.h:728-764).  *nodes_out / *trees_out: tahoe_free_host. */
 tahoe_status tahoe_dense_to_sparse(const tahoe_dense_node *dense, int num_trees, int depth,
                                    tahoe_sparse_node **nodes_out, int32_t **trees_out, size_t *num_nodes_out);

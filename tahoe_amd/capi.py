@@ -99,6 +99,18 @@ class ForestInfo(C.Structure):
     ]
 
 
+class CategoricalSplits(C.Structure):
+    """tahoe_categorical_splits: the arrays are owned by the caller (pack_categorical keeps them alive)."""
+
+    _fields_ = [
+        ("num_splits", C.c_int32),
+        ("node", C.c_void_p),
+        ("offset", C.c_void_p),
+        ("words", C.c_void_p),
+        ("members_left", C.c_void_p),
+    ]
+
+
 class TahoeError(RuntimeError):
     def __init__(self, status: int, where: str):
         self.status = status
@@ -130,6 +142,8 @@ _PROTOS = {
     "tahoe_forest_predict_contribs_approx": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "tahoe_sparse_forest_create": (_i, [C.POINTER(_vp), _vp, _vp, C.POINTER(ForestParams)]),
     "tahoe_sparse_forest_create_ex": (_i, [C.POINTER(_vp), _vp, _vp, _vp, C.POINTER(ForestParams), _i, C.c_uint]),
+    "tahoe_sparse_forest_create_cat": (_i, [C.POINTER(_vp), _vp, _vp, _vp, C.POINTER(ForestParams), _i, C.c_uint,
+                                            C.POINTER(CategoricalSplits)]),
     "tahoe_dense_to_sparse": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz)]),
     "tahoe_dense_to_sparse_ex": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz)]),
     "tahoe_synth_sparse_forest": (_i, [_vp, _vp, C.POINTER(_sz), _i, _i, _i, _i, _f, _i, C.c_uint64]),
@@ -605,22 +619,59 @@ def synth_sparse_forest(num_trees: int, num_cols: int, min_depth: int = 4, max_d
     return nodes, trees
 
 
+def pack_categorical(categories, members_left=()):
+    """(CategoricalSplits, arrays) for tahoe_sparse_forest_create_cat: categories = {node index: iterable of category ids >= 0},
+    members_left = node indices whose members go left.  Each split's bitset is as many 32-bit words as its largest category
+    needs (none for an empty set); `arrays` owns the memory the struct points to."""
+    keys = sorted(int(k) for k in categories)
+    node = np.array(keys, dtype=np.int32)
+    sets = [np.unique(np.asarray(list(categories[k]), dtype=np.int64)) for k in keys]
+    for k, c in zip(keys, sets):
+        if c.size and (c[0] < 0 or c[-1] >= 1 << 24):
+            raise ValueError(f"categories of node {k} must be in [0, 2^24)")
+    nwords = [int(c[-1]) // 32 + 1 if c.size else 0 for c in sets]
+    offset = np.zeros(len(keys) + 1, dtype=np.int32)
+    offset[1:] = np.cumsum(nwords)
+    words = np.zeros(max(int(offset[-1]), 1), dtype=np.uint32)
+    for k, c in enumerate(sets):
+        np.bitwise_or.at(words, offset[k] + c // 32, (np.uint32(1) << (c % 32).astype(np.uint32)))
+    left = set(int(k) for k in members_left)
+    if not left <= set(keys):
+        raise ValueError("members_left names a node without categories")
+    ml = np.array([k in left for k in keys], dtype=np.uint8) if left else None
+    arrays = (node, offset, words, ml)
+    cats = CategoricalSplits(len(keys), node.ctypes.data if node.size else None, offset.ctypes.data, words.ctypes.data,
+                             ml.ctypes.data if ml is not None else None)
+    return cats, arrays
+
+
 class SparseForest(Forest):
     """tahoe_sparse_forest_create: nodes[SPARSE_NODE_DTYPE] + root offsets; predict* as Forest.  covers (float32, one per
     node), num_classes, contribs and approx_contribs go through tahoe_sparse_forest_create_ex: tree t belongs to class
     t % num_classes, contribs=True builds the TreeSHAP path tables from the covers and approx_contribs=True the Saabas node
-    deltas."""
+    deltas.  categories ({node index: category ids}) makes those nodes categorical splits, members going right unless the
+    node is in members_left (tahoe_sparse_forest_create_cat; the node's val is then ignored)."""
 
     def __init__(self, nodes: np.ndarray, trees: np.ndarray, num_cols: int, missing: float = 0.0, output: int = OUT_RAW,
                  threshold: float = 0.0, global_bias: float = 0.0, covers=None, num_classes: int = 1,
-                 contribs: bool = False, approx_contribs: bool = False):
+                 contribs: bool = False, approx_contribs: bool = False, categories=None, members_left=()):
         nodes = np.ascontiguousarray(nodes, dtype=SPARSE_NODE_DTYPE)
         trees = np.ascontiguousarray(trees, dtype=np.int32)
         self.params = ForestParams(int(nodes.size), 0, int(trees.size), num_cols, 0, output, threshold, global_bias, 0,
                                    missing)
         self._h = _vp()
         flags = (CREATE_CONTRIBS if contribs else 0) | (CREATE_APPROX_CONTRIBS if approx_contribs else 0)
-        if covers is not None or num_classes != 1 or flags:
+        if categories:
+            cv = None if covers is None else np.ascontiguousarray(covers, dtype=np.float32)
+            if cv is not None and cv.size != nodes.size:
+                raise ValueError("covers.size != nodes.size")
+            cats, _keep = pack_categorical(categories, members_left)
+            _check(lib.tahoe_sparse_forest_create_cat(C.byref(self._h), trees.ctypes.data if trees.size else None,
+                                                      nodes.ctypes.data if nodes.size else None,
+                                                      cv.ctypes.data if cv is not None else None,
+                                                      C.byref(self.params), num_classes, flags, C.byref(cats)),
+                   "tahoe_sparse_forest_create_cat")
+        elif covers is not None or num_classes != 1 or flags:
             cv = None if covers is None else np.ascontiguousarray(covers, dtype=np.float32)
             if cv is not None and cv.size != nodes.size:
                 raise ValueError("covers.size != nodes.size")

@@ -770,6 +770,10 @@ static int resolve_strategy(const tahoe_forest *f, size_t rows)
 tahoe_status strategy_available(const tahoe_forest *f, int strategy)
 {
     if (f->sp) {
+        if (strategy == TAHOE_STRATEGY_QRING && sparse_has_cats(f))
+            return fail(TAHOE_ERR_UNSUPPORTED,
+                        "QRING does not serve categorical splits: its 4-byte node word (code << 16 | def_left << 15 | fid << 7) "
+                        "and its rank quantiser have no room for a category-set test; use AUTO, TILEBLOCK, ROWTILE or DIRECT");
         if ((strategy > TAHOE_STRATEGY_TILEBLOCK && strategy != TAHOE_STRATEGY_QRING) ||
             (strategy == TAHOE_STRATEGY_ROWTILE && !sparse_tile_fits(f)) ||
             (strategy == TAHOE_STRATEGY_TILEBLOCK && sparse_top_waves(f) == 0) ||

@@ -345,6 +345,22 @@ __device__ __forceinline__ uint32_t go_right(float x, float thr, bool def_left, 
     const bool cond = is_missing ? !def_left : (x >= thr);
     return cond ? 1u : 0u;
 }
+// ... at a categorical split (tahoe_sparse_forest_create_cat).  pool[off] = members_left << 31 | nwords, the split's nwords
+// bitset words follow it; pool_words bounds the word read (an empty or short set may sit at the pool's end).  Below 2^24 a
+// float32 is exact and (uint32_t)x truncates, so x < 32 * nwords <=> (c >> 5) < nwords; NaN fails x >= 0.0f.
+__device__ __forceinline__ uint32_t go_right_cat(float x, const uint32_t *__restrict__ pool, uint32_t off, uint32_t pool_words,
+                                                 bool def_left, float missing)
+{
+    const bool is_missing = fabsf(x - missing) <= kMissingEps;
+    const bool in = x >= 0.0f && x < 16777216.0f;
+    const uint32_t c = in ? (uint32_t)x : 0u;
+    const uint32_t wi = off + 1u + (c >> 5);
+    const uint32_t head = pool[off];
+    const uint32_t word = wi < pool_words ? pool[wi] : 0u;  // issued beside the header read: one round trip
+    const bool member = in && (c >> 5) < (head & 0xfffffu) && ((word >> (c & 31u)) & 1u) != 0u;
+    const bool cond = is_missing ? !def_left : (member != ((head >> 31) != 0u));
+    return cond ? 1u : 0u;
+}
 // ... on a heap record: the stored children are swapped where the exchange bit is set (Struct.h:1060-1063: cond = !cond)
 __device__ __forceinline__ uint32_t go_right_meta(float x, float thr, uint32_t meta, float missing)
 {
@@ -385,6 +401,7 @@ tahoe_status sparse_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, con
                            hipStream_t stream, int strategy, const float *sums_in = nullptr);
 int sparse_top_waves(const tahoe_forest *f);
 bool sparse_q_available(const tahoe_forest *f);  // the walk on quantised codes (strategy QRING on a sparse handle)
+bool sparse_has_cats(const tahoe_forest *f);     // categorical splits (tahoe_sparse_forest_create_cat): no QRING
 void sparse_destroy(tahoe_forest *f);
 void sparse_device_views(const tahoe_forest *f, const tahoe_sparse_node **nodes, const int32_t **trees);  // the stored nodes and roots
 void pipeline_destroy(tahoe_forest *f);

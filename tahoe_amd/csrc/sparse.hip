@@ -54,6 +54,11 @@ struct tahoe_sstate {
     int32_t *qblkoff = nullptr;
     uint32_t *qbotpos = nullptr;
     uint32_t *qblkpos = nullptr;
+    // categorical splits (tahoe_sparse_forest_create_cat; null / 0 without): per split a header word members_left << 31 | nwords,
+    // then its nwords bitset words (go_right_cat).  A categorical node carries its header's index in `val` (cnodes: in x) and is
+    // flagged by kSCat in the device copy of `bits` (cnodes: kSCCat in y)
+    uint32_t *cat_pool = nullptr;
+    uint32_t cat_words = 0;
 };
 
 namespace tahoe {
@@ -61,15 +66,22 @@ namespace tahoe {
 constexpr int32_t kSFidMask = (int32_t)((1u << 30) - 1u);
 constexpr int32_t kSDefLeft = (int32_t)(1u << 30);
 constexpr int32_t kSIsLeaf = (int32_t)(1u << 31);
+constexpr int32_t kSCat = (int32_t)(1u << 29);          // device copy of a categorical handle: the node is a categorical split
+constexpr int32_t kSCatFidMask = (int32_t)((1u << 29) - 1u);  // ... whose fid then has 29 bits (num_cols <= 2^29)
+constexpr uint32_t kSCCat = 0x4000u;   // compact node of a categorical handle: the node is a categorical split (fid: 14 bits)
+constexpr int kSCatMaxCompactCols = 1 << 14;
+constexpr long long kCatMaxWords = 1 << 19;  // categories < 2^24: exact in float32
 
 // MC (multi-class handle, trees class-major): the owner lanes store the sum to sums[row * num_classes + c] at the last tree of
 // class c and restart from 0.0f (sums_in is not read); leaf indices go to the caller's tree numbering.
-template <bool TILE, bool WRITE_LEAF, bool MC = false>
+// CAT (a handle with categorical splits): a node flagged kSCat takes go_right_cat on the pool entry its `val` bits name.
+template <bool TILE, bool WRITE_LEAF, bool MC = false, bool CAT = false>
 __global__ void __launch_bounds__(kBlock) sparse_kernel(const tahoe_sparse_node *__restrict__ nodes,
                                                         const int32_t *__restrict__ trees, const float *__restrict__ data,
                                                         float *sums, uint32_t *__restrict__ leaf_out,
                                                         const float *sums_in, size_t rows, int cols, int num_trees, float missing,
-                                                        int vec4_ok, int num_classes)
+                                                        int vec4_ok, int num_classes, const uint32_t *__restrict__ cat_pool,
+                                                        uint32_t cat_words)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
@@ -112,9 +124,12 @@ __global__ void __launch_bounds__(kBlock) sparse_kernel(const tahoe_sparse_node 
                     v = n.val;
                     break;
                 }
-                const int fid = n.bits & kSFidMask;
+                const int fid = n.bits & (CAT ? kSCatFidMask : kSFidMask);
                 const float x = TILE ? tile[fid * kTileRows + lane] : xrow[fid];
-                curr = (uint32_t)n.left_idx + go_right(x, n.val, (n.bits & kSDefLeft) != 0, missing);
+                if (CAT && (n.bits & kSCat))
+                    curr = (uint32_t)n.left_idx + go_right_cat(x, cat_pool, __float_as_uint(n.val), cat_words, (n.bits & kSDefLeft) != 0, missing);
+                else
+                    curr = (uint32_t)n.left_idx + go_right(x, n.val, (n.bits & kSDefLeft) != 0, missing);
             }
             if (WRITE_LEAF) {
                 if (row_ok) leaf_out[row * (size_t)num_trees + (MC ? mc_orig_tree(t, num_classes, class_trees) : t)] = curr;
@@ -156,13 +171,14 @@ __global__ void __launch_bounds__(kBlock) sparse_kernel(const tahoe_sparse_node 
 constexpr int kSTop = 512;    // nodes per slot (8 B each)
 constexpr int kSRing = 32;    // ring entries (trees)
 constexpr int kSBatch = 4;    // trees the consumer takes per poll (K5: 16 -> 5.34 ms, 8 -> 5.19, 4 -> 5.15)
-// MC: as sparse_kernel's, in the consumer wave.
-template <int NW, bool WRITE_LEAF, bool MC = false>
+// MC: as sparse_kernel's, in the consumer wave.  CAT: a node flagged kSCCat takes go_right_cat on the pool entry in its x word.
+template <int NW, bool WRITE_LEAF, bool MC = false, bool CAT = false>
 __global__ void __launch_bounds__(NW * 64) sparse_top_kernel(const uint2 *__restrict__ cnodes, const int32_t *__restrict__ ctrees,
                                                              const uint32_t *__restrict__ corig, const float *__restrict__ data,
                                                              float *sums, uint32_t *__restrict__ leaf_out,
                                                              const float *sums_in, size_t rows, int cols, int num_trees, float missing,
-                                                             int vec4_ok, int *__restrict__ error_flag, int num_classes)
+                                                             int vec4_ok, int *__restrict__ error_flag, int num_classes,
+                                                             const uint32_t *__restrict__ cat_pool, uint32_t cat_words)
 {
     constexpr int NWALK = NW - 1;
     static_assert(kSRing >= 2 * kSBatch && kSRing > NWALK, "ring too small");
@@ -269,13 +285,14 @@ __global__ void __launch_bounds__(NW * 64) sparse_top_kernel(const uint2 *__rest
                 break;
             }
             // the feature value and BOTH children (an aligned pair) are fetched together: one LDS round trip per level
-            const float x = tile[(n.y & 0x7fffu) * kTileRows + lane];
+            const float x = tile[(n.y & (CAT ? 0x3fffu : 0x7fffu)) * kTileRows + lane];
             uint4 pr;
             if (left < (uint32_t)kSTop)
                 pr = *reinterpret_cast<const uint4 *>(slot + left);
             else
                 pr = *reinterpret_cast<const uint4 *>(root + left);
-            const uint32_t r = go_right(x, __uint_as_float(n.x), (n.y & 0x8000u) != 0u, missing);
+            const uint32_t r = (CAT && (n.y & kSCCat)) ? go_right_cat(x, cat_pool, n.x, cat_words, (n.y & 0x8000u) != 0u, missing)
+                                                       : go_right(x, __uint_as_float(n.x), (n.y & 0x8000u) != 0u, missing);
             n = r ? make_uint2(pr.z, pr.w) : make_uint2(pr.x, pr.y);
             curr = left + r;
         }
@@ -607,6 +624,8 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
 
 bool sparse_q_available(const tahoe_forest *f) { return f->sp && f->sp->qtop && f->q; }
 
+bool sparse_has_cats(const tahoe_forest *f) { return f->sp && f->sp->cat_pool; }
+
 template <int NWALK, int K, int RING>
 static void sparse_q_launch_form(tahoe_forest *f, const tahoe_qgroup &g, float *sums, const float *sums_in, uint32_t *leaf_out,
                                  size_t row_begin, size_t rows_end, hipStream_t stream, int cshift)
@@ -685,14 +704,18 @@ tahoe_status sparse_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, con
         const int lds = (int)sparse_top_lds(f, nw);
         const int nc = f->num_classes;
         with_leaf_mc(leaf_out != nullptr, nc > 1, [&](auto wl, auto mc) {
-            auto launch = [&](auto nw_c) {
+            auto launch = [&](auto nw_c, auto cat) {
                 constexpr int NW = decltype(nw_c)::value;
-                hipLaunchKernelGGL((sparse_top_kernel<NW, decltype(wl)::value, decltype(mc)::value>), dim3(grid), dim3(NW * 64), lds,
-                                   stream, sp->cnodes, sp->ctrees, sp->corig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
-                                   f->p.num_trees, f->p.missing, vec4_ok, f->error_flag, nc);
+                hipLaunchKernelGGL((sparse_top_kernel<NW, decltype(wl)::value, decltype(mc)::value, decltype(cat)::value>), dim3(grid),
+                                   dim3(NW * 64), lds, stream, sp->cnodes, sp->ctrees, sp->corig, data, sums, leaf_out, sums_in, rows,
+                                   f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, f->error_flag, nc, sp->cat_pool, sp->cat_words);
             };
-            if (nw == 16) launch(std::integral_constant<int, 16>{});
-            else launch(std::integral_constant<int, 8>{});
+            auto with_cat = [&](auto nw_c) {
+                if (sp->cat_pool) launch(nw_c, std::true_type{});
+                else launch(nw_c, std::false_type{});
+            };
+            if (nw == 16) with_cat(std::integral_constant<int, 16>{});
+            else with_cat(std::integral_constant<int, 8>{});
         });
         TAHOE_HIP_TRY(hipGetLastError());
         return TAHOE_OK;
@@ -701,13 +724,17 @@ tahoe_status sparse_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, con
     const int lds = (int)sparse_lds(f, tile);
     const int nc = f->num_classes;
     with_leaf_mc(leaf_out != nullptr, nc > 1, [&](auto wl, auto mc) {
-        auto launch = [&](auto tile_c) {
-            hipLaunchKernelGGL((sparse_kernel<decltype(tile_c)::value, decltype(wl)::value, decltype(mc)::value>), dim3(grid), dim3(kBlock),
-                               lds, stream, sp->nodes, sp->trees, data, sums, leaf_out, sums_in, rows, f->p.num_cols, f->p.num_trees,
-                               f->p.missing, vec4_ok, nc);
+        auto launch = [&](auto tile_c, auto cat) {
+            hipLaunchKernelGGL((sparse_kernel<decltype(tile_c)::value, decltype(wl)::value, decltype(mc)::value, decltype(cat)::value>),
+                               dim3(grid), dim3(kBlock), lds, stream, sp->nodes, sp->trees, data, sums, leaf_out, sums_in, rows,
+                               f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, nc, sp->cat_pool, sp->cat_words);
         };
-        if (tile) launch(std::true_type{});
-        else launch(std::false_type{});
+        auto with_cat = [&](auto tile_c) {
+            if (sp->cat_pool) launch(tile_c, std::true_type{});
+            else launch(tile_c, std::false_type{});
+        };
+        if (tile) with_cat(std::true_type{});
+        else with_cat(std::false_type{});
     });
     TAHOE_HIP_TRY(hipGetLastError());
     return TAHOE_OK;
@@ -721,6 +748,7 @@ void sparse_destroy(tahoe_forest *f)
     if (f->sp->cnodes) (void)hipFree(f->sp->cnodes);
     if (f->sp->ctrees) (void)hipFree(f->sp->ctrees);
     if (f->sp->corig) (void)hipFree(f->sp->corig);
+    if (f->sp->cat_pool) (void)hipFree(f->sp->cat_pool);
     for (void *p : {(void *)f->sp->qtop, (void *)f->sp->qblocks, (void *)f->sp->qblkoff, (void *)f->sp->qbotpos, (void *)f->sp->qblkpos})
         if (p) (void)hipFree(p);
     delete f->sp;
@@ -948,11 +976,14 @@ static tahoe_status sparse_q_build(tahoe_forest *f, const std::vector<uint2> &cn
 }
 
 // The compact breadth-first copy of the stored trees (sparse_top_kernel), then its quantised form (sparse_q_build).  Leaves both
-// unavailable (TAHOE_OK, sp->cnodes null) when a tree has more than 65535 reachable nodes.
+// unavailable (TAHOE_OK, sp->cnodes null) when a tree has more than 65535 reachable nodes.  A handle with categorical splits
+// (its pool is built) flags them with kSCCat, needs num_cols <= 2^14 for that and gets no quantised form.
 static tahoe_status sparse_top_build(tahoe_forest *f, const int32_t *trees, const tahoe_sparse_node *nodes)
 {
     tahoe_sstate *sp = f->sp;
     const int T = f->p.num_trees;
+    const bool cat = sp->cat_pool != nullptr;
+    if (cat && f->p.num_cols > kSCatMaxCompactCols) return TAHOE_OK;
     std::vector<uint2> cn;
     std::vector<uint32_t> orig;
     std::vector<int32_t> ct((size_t)T + 1, 0);
@@ -982,6 +1013,9 @@ static tahoe_status sparse_top_build(tahoe_forest *f, const int32_t *trees, cons
             memcpy(&c.x, &n.val, 4);
             if (n.bits & kSIsLeaf)
                 c.y = 0u;
+            else if (cat)
+                c.y = (newpos[(size_t)n.left_idx] << 16) | ((n.bits & kSDefLeft) ? 0x8000u : 0u) | ((n.bits & kSCat) ? kSCCat : 0u) |
+                      (uint32_t)(n.bits & kSCatFidMask);
             else  // the left child of any node sits at a position >= 2: 0 marks a leaf
                 c.y = (newpos[(size_t)n.left_idx] << 16) | ((n.bits & kSDefLeft) ? 0x8000u : 0u) | (uint32_t)(n.bits & kSFidMask);
             cn.push_back(c);
@@ -1006,6 +1040,14 @@ static tahoe_status sparse_top_build(tahoe_forest *f, const int32_t *trees, cons
          ((e = allow_max_lds_leaf([](auto wl) { return &sparse_top_kernel<16, decltype(wl)::value, true>; }, f->lds_limit)) != hipSuccess ||
           (e = allow_max_lds_leaf([](auto wl) { return &sparse_top_kernel<8, decltype(wl)::value, true>; }, f->lds_limit)) != hipSuccess)))
         return hip_status(e, "hipFuncSetAttribute(sparse_top)");
+    if (cat) {
+        if ((e = allow_max_lds_leaf([](auto wl) { return &sparse_top_kernel<16, decltype(wl)::value, false, true>; }, f->lds_limit)) != hipSuccess ||
+            (e = allow_max_lds_leaf([](auto wl) { return &sparse_top_kernel<8, decltype(wl)::value, false, true>; }, f->lds_limit)) != hipSuccess ||
+            (e = allow_max_lds_leaf([](auto wl) { return &sparse_top_kernel<16, decltype(wl)::value, true, true>; }, f->lds_limit)) != hipSuccess ||
+            (e = allow_max_lds_leaf([](auto wl) { return &sparse_top_kernel<8, decltype(wl)::value, true, true>; }, f->lds_limit)) != hipSuccess)
+            return hip_status(e, "hipFuncSetAttribute(sparse_top, categorical)");
+        return TAHOE_OK;  // QRING's node word has no room for a set test
+    }
     return sparse_q_build(f, cn, ct);
 }
 
@@ -1015,16 +1057,49 @@ void sparse_device_views(const tahoe_forest *f, const tahoe_sparse_node **nodes,
     *trees = f->sp->trees;
 }
 
+// The argument checks of the categorical splits (TAHOE_ERR_INVALID_ARG), in the header's order.
+static tahoe_status check_cat_args(const tahoe_categorical_splits *c, int num_nodes)
+{
+    const int ns = c->num_splits;
+    if (ns < 0 || ns > num_nodes)
+        return fail(TAHOE_ERR_INVALID_ARG, "categorical splits: num_splits %d is not in [0, num_nodes = %d]", ns, num_nodes);
+    if (ns == 0) return TAHOE_OK;
+    if (!c->node || !c->offset || !c->words)
+        return fail(TAHOE_ERR_INVALID_ARG, "categorical splits: node, offset and words must not be NULL with num_splits > 0");
+    for (int k = 0; k < ns; ++k) {
+        if (c->node[k] < 0 || c->node[k] >= num_nodes)
+            return fail(TAHOE_ERR_INVALID_ARG, "categorical splits: node[%d] = %d is outside [0, num_nodes = %d)", k, c->node[k], num_nodes);
+        if (k > 0 && c->node[k] <= c->node[k - 1])
+            return fail(TAHOE_ERR_INVALID_ARG, "categorical splits: node[] must be strictly ascending (node[%d] = %d after %d)", k,
+                        c->node[k], c->node[k - 1]);
+    }
+    if (c->offset[0] != 0) return fail(TAHOE_ERR_INVALID_ARG, "categorical splits: offset[0] = %d, must be 0", c->offset[0]);
+    for (int k = 0; k < ns; ++k) {
+        const long long w = (long long)c->offset[k + 1] - c->offset[k];
+        if (w < 0) return fail(TAHOE_ERR_INVALID_ARG, "categorical splits: offset[%d] = %d decreases from %d", k + 1, c->offset[k + 1], c->offset[k]);
+        if (w > kCatMaxWords)
+            return fail(TAHOE_ERR_INVALID_ARG, "categorical splits: split %d has %lld words, more than 2^19 (categories must be < 2^24)", k, w);
+    }
+    return TAHOE_OK;
+}
+
 // num_classes > 1 / covers: tahoe_sparse_forest_create_ex, whose own checks have run.  A multi-class forest is stored
 // class-major (internal tree p = the caller's tree (p % Tc) C + p / Tc); every builder below then runs on that order unchanged.
+// cats (tahoe_sparse_forest_create_cat): the bitset pool is built here and the caller's nodes are copied with each split's pool
+// index in `val` and kSCat in `bits`, before the class-major copy -- the splits move with their nodes.
 static tahoe_status create_sparse(tahoe_forest **out, const int32_t *trees, const tahoe_sparse_node *nodes, const float *covers,
-                                  const tahoe_forest_params *p, int num_classes, unsigned flags)
+                                  const tahoe_forest_params *p, int num_classes, unsigned flags,
+                                  const tahoe_categorical_splits *cats = nullptr)
 {
     if (!out || !p) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_sparse_forest_create: null argument");
     *out = nullptr;
     if (p->num_nodes < 0) return fail(TAHOE_ERR_INVALID_ARG, "num_nodes must be non-negative for sparse forests");
     if (p->algo != TAHOE_ALGO_NAIVE) return fail(TAHOE_ERR_INVALID_ARG, "only NAIVE algorithm is supported for sparse forests");
     if (const tahoe_status s = check_params(p, num_classes, trees && nodes, "trees / nodes")) return s;
+    if (cats) {
+        if (const tahoe_status s = check_cat_args(cats, p->num_nodes)) return s;
+        if (cats->num_splits == 0) cats = nullptr;  // the handle of tahoe_sparse_forest_create_ex
+    }
     // Structure check (the reference trusts its input): roots ascending, every child pair inside its tree
     // and after its parent (which also rules out cycles, so device walks terminate), fid < num_cols.
     int max_tree_nodes = 0;
@@ -1044,6 +1119,24 @@ static tahoe_status create_sparse(tahoe_forest **out, const int32_t *trees, cons
                             p->num_cols);
         }
     }
+    if (cats) {
+        for (int k = 0; k < cats->num_splits; ++k) {
+            const int32_t i = cats->node[k];
+            const int32_t *it = std::upper_bound(trees, trees + p->num_trees, i);  // roots are ascending (checked above)
+            if (it == trees)
+                return fail(TAHOE_ERR_INVALID_FOREST, "categorical split %d: node %d lies in no tree (before the first root)", k, i);
+            const int t = (int)(it - trees) - 1;
+            if (nodes[i].bits & kSIsLeaf)
+                return fail(TAHOE_ERR_INVALID_FOREST, "tree %d node %d: categorical split %d names a leaf", t, i - trees[t], k);
+        }
+        if (flags & (TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS))
+            return fail(TAHOE_ERR_UNSUPPORTED, "categorical splits do not combine with TAHOE_CREATE_CONTRIBS or "
+                                               "TAHOE_CREATE_APPROX_CONTRIBS: TreeSHAP's path elements are intervals per feature, "
+                                               "and a category set is not an interval");
+        if (p->num_cols > (1 << 29))
+            return fail(TAHOE_ERR_UNSUPPORTED, "categorical splits need num_cols <= 2^29 (the device node keeps bit 29 as the "
+                                               "categorical flag); num_cols = %d", p->num_cols);
+    }
     if (flags & (TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS)) {
         // the covers (and, for the path bins, the path lengths), on the caller's nodes, before a device is touched
         const tahoe_status cs = contribs_validate_sparse(trees, nodes, covers, p, (flags & TAHOE_CREATE_CONTRIBS) != 0);
@@ -1060,6 +1153,24 @@ static tahoe_status create_sparse(tahoe_forest **out, const int32_t *trees, cons
     sp->max_tree_nodes = max_tree_nodes;
     const int32_t *const caller_trees = trees;
     const tahoe_sparse_node *const caller_nodes = nodes;
+    std::vector<tahoe_sparse_node> cat_nodes;
+    if (cats) {  // pool: split k's header at offset[k] + k, its words after it
+        const int ns = cats->num_splits;
+        std::vector<uint32_t> pool((size_t)cats->offset[ns] + (size_t)ns);
+        cat_nodes.assign(nodes, nodes + sp->num_nodes);
+        for (int k = 0; k < ns; ++k) {
+            const uint32_t at = (uint32_t)cats->offset[k] + (uint32_t)k, nw = (uint32_t)(cats->offset[k + 1] - cats->offset[k]);
+            const bool ml = cats->members_left && cats->members_left[k];
+            pool[at] = (ml ? 0x80000000u : 0u) | nw;
+            std::copy(cats->words + cats->offset[k], cats->words + cats->offset[k + 1], pool.begin() + at + 1);
+            tahoe_sparse_node &n = cat_nodes[(size_t)cats->node[k]];
+            memcpy(&n.val, &at, 4);
+            n.bits |= kSCat;
+        }
+        sp->cat_words = (uint32_t)pool.size();
+        if (const tahoe_status s = hip_status(upload(&sp->cat_pool, pool, &f->device_bytes), "upload(categorical splits)")) return s;
+        nodes = cat_nodes.data();
+    }
     std::vector<int32_t> mc_trees;
     std::vector<tahoe_sparse_node> mc_nodes;
     if (num_classes > 1) {  // class-major copy: each tree's node range moves as a block (child links are root-relative)
@@ -1083,7 +1194,9 @@ static tahoe_status create_sparse(tahoe_forest **out, const int32_t *trees, cons
     hipError_t e;
     if (sparse_tile_fits(f.get()) &&
         ((e = allow_max_lds_leaf([](auto wl) { return &sparse_kernel<true, decltype(wl)::value>; }, f->lds_limit)) != hipSuccess ||
-         (num_classes > 1 && (e = allow_max_lds_leaf([](auto wl) { return &sparse_kernel<true, decltype(wl)::value, true>; }, f->lds_limit)) != hipSuccess)))
+         (num_classes > 1 && (e = allow_max_lds_leaf([](auto wl) { return &sparse_kernel<true, decltype(wl)::value, true>; }, f->lds_limit)) != hipSuccess) ||
+         (cats && ((e = allow_max_lds_leaf([](auto wl) { return &sparse_kernel<true, decltype(wl)::value, false, true>; }, f->lds_limit)) != hipSuccess ||
+                   (e = allow_max_lds_leaf([](auto wl) { return &sparse_kernel<true, decltype(wl)::value, true, true>; }, f->lds_limit)) != hipSuccess))))
         return hip_status(e, "hipFuncSetAttribute(sparse)");
     if (p->num_cols <= 32767 && p->num_trees > 0 && (s = sparse_top_build(f.get(), trees, nodes))) return s;
     // contributions from the caller's trees, in the caller's numbering (contribs_build's order); Saabas deltas in the stored
@@ -1107,6 +1220,13 @@ tahoe_status tahoe_sparse_forest_create(tahoe_forest **out, const int32_t *trees
 tahoe_status tahoe_sparse_forest_create_ex(tahoe_forest **out, const int32_t *trees, const tahoe_sparse_node *nodes,
                                            const float *covers, const tahoe_forest_params *p, int num_classes, unsigned flags)
 {
+    return tahoe_sparse_forest_create_cat(out, trees, nodes, covers, p, num_classes, flags, nullptr);
+}
+
+tahoe_status tahoe_sparse_forest_create_cat(tahoe_forest **out, const int32_t *trees, const tahoe_sparse_node *nodes,
+                                            const float *covers, const tahoe_forest_params *p, int num_classes, unsigned flags,
+                                            const tahoe_categorical_splits *cats)
+{
     // every check here (and in create_sparse) runs before a device is touched
     if (!out || !p) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_sparse_forest_create_ex: null argument");
     *out = nullptr;
@@ -1118,7 +1238,7 @@ tahoe_status tahoe_sparse_forest_create_ex(tahoe_forest **out, const int32_t *tr
         return fail(TAHOE_ERR_INVALID_ARG, "TAHOE_CREATE_CONTRIBS needs covers (one per node)");
     if ((flags & TAHOE_CREATE_APPROX_CONTRIBS) && !covers)
         return fail(TAHOE_ERR_INVALID_ARG, "TAHOE_CREATE_APPROX_CONTRIBS needs covers (one per node)");
-    return create_sparse(out, trees, nodes, covers, p, num_classes, flags);
+    return create_sparse(out, trees, nodes, covers, p, num_classes, flags, cats);
 }
 
 // dense2sparse, BaseTahoeTest.h:728-764: per tree a root, then for every inner node its two children are

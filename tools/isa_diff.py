@@ -8,7 +8,8 @@ then   python tools/isa_diff.py <old_dir> <new_dir> [forest qring ...] [-v]
 (dirs = where the *-hip-amdgcn-amd-amdhsa-gfx950.s files are).  Local branch labels are renumbered and the kernel descriptor's
 name, section and kernarg_size lines are left out of the comparison (a kernel argument appended at the end changes only those).
 A template flag appended with a default (`bool MC = false`) is matched by dropping a trailing `, false` template argument; new
-instantiations with `, true` there are counted, not compared.  --exact: both builds have the same template parameters (no appended
+instantiations with `, true` there are counted, not compared.  A function whose full name exists in both builds is matched by
+that name first, so kernels of the list that did not get the flag in this change are compared as they are.  --exact: both builds have the same template parameters (no appended
 flag): functions are matched by their full names.  A translation unit that exists only in <new_dir> is listed as new."""
 import difflib
 import re
@@ -46,9 +47,9 @@ def demangle(names):
     return dict(zip(names, res))
 
 
-def key(name, new):
+def key(name, new, old_names=()):
     base = name.split("(")[0]
-    if new and any(k in base for k in FLAGGED):
+    if new and base not in old_names and any(k in base for k in FLAGGED):
         if base.endswith(", false>"):
             return base[: -len(", false>")] + ">"
         if base.endswith(", true>"):
@@ -72,7 +73,7 @@ def main(argv):
         old_by = {key(od[k], False): k for k in old}
         new_by = {}
         for k in new:
-            kk = key(nd[k], not exact)
+            kk = key(nd[k], not exact, old_by)
             if kk is not None:
                 new_by[kk] = k
         same = 0
@@ -88,7 +89,7 @@ def main(argv):
                 if verbose:
                     print("\n".join(list(difflib.unified_diff(old[k], new[new_by[name]], lineterm=""))[:60]))
         added = [n for n in new_by if n not in old_by]
-        flagged = 0 if exact else sum(1 for k in new if key(nd[k], True) is None)
+        flagged = 0 if exact else sum(1 for k in new if key(nd[k], True, old_by) is None)
         print(f"{unit}: {same} of {len(old_by)} pre-existing functions identical; new: {added}; new flagged instantiations: {flagged}")
     return 1 if changed else 0
 
