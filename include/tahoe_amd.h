@@ -410,6 +410,36 @@ tahoe_status tahoe_synth_sparse_forest(tahoe_sparse_node *nodes, int32_t *trees,
 tahoe_status tahoe_forest_predict(tahoe_forest *f, float *preds_dev, const float *data_dev, size_t rows,
                                   void *stream);
 
+/* tahoe_forest_predict on rows given as CSR, without a dense copy of the batch.  Row r has values_dev[k] in column
+ * indices_dev[k] for k in [indptr_dev[r], indptr_dev[r + 1]) and the missing sentinel (params.missing) in every other column:
+ * an entry that is not stored is missing and takes the node's default branch, as in XGBoost and LightGBM.  preds_dev gets, bit
+ * for bit, what tahoe_forest_predict writes for that dense matrix -- rows values, or rows x num_classes on a multi-class
+ * handle, output transform included -- under every strategy setting (every kernel adds a row's leaf values in tree order).
+ *   - Stored values are ordinary values: a stored sentinel is missing, a stored NaN goes left, -0.0 stays -0.0.
+ *   - Column ids within a row need not be sorted; rows may be empty.  A row must not name a column twice: if it does, one of the
+ *     two values is used, which one is unspecified, and nothing else is affected.
+ *   - The kernels never read outside [0, nnz) of indices_dev / values_dev nor outside [0, rows] of indptr_dev, whatever
+ *     indptr_dev holds: entry ranges are clamped to nnz.  An entry whose column id is outside [0, num_cols) is skipped (its row
+ *     reads the sentinel there) and raises a flag of its own in the handle: the next tahoe_forest_check returns
+ *     TAHOE_ERR_INVALID_ARG with a text that says "column" and clears that flag, so a later clean call checks TAHOE_OK.
+ *   - Served on dense, multi-class, sparse, multi-class sparse and categorical handles.  rows == 0: TAHOE_OK, nothing launched;
+ *     nnz == 0 with rows > 0 is valid (every value missing).  NULL preds_dev / indptr_dev with rows > 0, NULL indices_dev /
+ *     values_dev with nnz > 0, or nnz > INT64_MAX: TAHOE_ERR_INVALID_ARG, checked before the handle or a device is touched.
+ *   - Asynchronous on `stream`.  ROWTILE, and on sparse handles TILEBLOCK, stage their 64-row LDS tile straight from the CSR
+ *     arrays (kernel forms TAHOE_FORM_CSR_*); every other kernel form gets the batch densified chunk by chunk into a buffer the
+ *     handle owns -- at most TAHOE_CSR_CHUNK_MB MiB (read at create, default 64; at least one 64-row tile), counted in
+ *     device_bytes -- and runs on each chunk in turn.  Under AUTO the path is picked from num_cols, the trees and nnz / rows
+ *     (tahoe_forest_get_csr_plan tells).  The buffer and the kernels' workspace grow on demand, which allocates and
+ *     synchronises; after tahoe_forest_reserve_csr(rows, nnz) a call with at most that many rows and entries allocates nothing
+ *     and can be captured.
+ * Leaf indices, predict_accumulate, predict_host and the SHAP entry points take dense rows only. */
+tahoe_status tahoe_forest_predict_csr(tahoe_forest *f, float *preds_dev, const int64_t *indptr_dev, const int32_t *indices_dev,
+                                      const float *values_dev, size_t rows, size_t nnz, void *stream);
+tahoe_status tahoe_forest_reserve_csr(tahoe_forest *f, size_t rows, size_t nnz);
+/* How tahoe_forest_predict_csr runs a batch of `rows` rows with nnz entries: *chunk_rows = 0 and *form = the fused kernel
+ * (TAHOE_FORM_CSR_*), or *chunk_rows = rows per densified chunk and *form = the kernel form that runs on a chunk. */
+tahoe_status tahoe_forest_get_csr_plan(const tahoe_forest *f, size_t rows, size_t nnz, int *form, size_t *chunk_rows);
+
 /* Raw float32 per-row sums only (no output transform) -- the quantity tree shards exchange. */
 tahoe_status tahoe_forest_predict_raw(tahoe_forest *f, float *sums_dev, const float *data_dev, size_t rows,
                                       void *stream);
@@ -436,7 +466,8 @@ tahoe_status tahoe_transform_preds(float *preds_dev, size_t rows, int output, in
 
 tahoe_status tahoe_forest_set_strategy(tahoe_forest *f, int strategy);
 /* Waits for `stream` and reports TAHOE_ERR_HIP if a kernel flagged an internal error (a bounded
- * LDS wait of TILERING timing out); TAHOE_OK otherwise. */
+ * LDS wait of TILERING timing out); else TAHOE_ERR_INVALID_ARG, once, if a tahoe_forest_predict_csr since the last check
+ * skipped an entry with a column id outside [0, num_cols); TAHOE_OK otherwise. */
 tahoe_status tahoe_forest_check(tahoe_forest *f, void *stream);
 /* Sizes the handle's device workspace for batches of up to `rows` rows: QRING's 2-byte-per-value quantised copy of
  * the batch and, for the batches small enough to be walked in tree slices (up to 64 rows per CU), one float per
@@ -520,8 +551,11 @@ enum {
     TAHOE_FORM_SPARSE_QRING = 17,         /* sparse_q_kernel */
     TAHOE_FORM_QRING_REGION8 = 18,        /* qring_kernel on 8-bit rank codes (<= 254 thresholds per feature): 384-row tiles of three
                                              128-row regions, six chains per lane (<= 128 features: 15 walkers, ring of 24) */
-    TAHOE_FORM_QRING_REGION6 = 19         /* qring_kernel on u16 codes, num_cols <= 128: 384-row tiles of six 64-row regions at a
+    TAHOE_FORM_QRING_REGION6 = 19,        /* qring_kernel on u16 codes, num_cols <= 128: 384-row tiles of six 64-row regions at a
                                              16-KiB stride, six chains per lane */
+    TAHOE_FORM_CSR_ROWTILE = 20,          /* tahoe_forest_predict_csr only: rowtile_kernel staging its tile from the CSR arrays */
+    TAHOE_FORM_CSR_SPARSE_ROWTILE = 21,   /* ... sparse_kernel with the tile */
+    TAHOE_FORM_CSR_SPARSE_TOP = 22        /* ... sparse_top_kernel */
 };
 int tahoe_forest_get_kernel_form(const tahoe_forest *f, size_t rows);
 const char *tahoe_kernel_form_name(int form);

@@ -148,6 +148,9 @@ _PROTOS = {
     "tahoe_dense_to_sparse_ex": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz)]),
     "tahoe_synth_sparse_forest": (_i, [_vp, _vp, C.POINTER(_sz), _i, _i, _i, _i, _f, _i, C.c_uint64]),
     "tahoe_forest_predict": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "tahoe_forest_predict_csr": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp]),
+    "tahoe_forest_reserve_csr": (_i, [_vp, _sz, _sz]),
+    "tahoe_forest_get_csr_plan": (_i, [_vp, _sz, _sz, C.POINTER(_i), C.POINTER(_sz)]),
     "tahoe_forest_predict_raw": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "tahoe_forest_predict_accumulate": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "tahoe_forest_predict_leaf_idx": (_i, [_vp, _vp, _vp, _vp, _sz, _vp]),
@@ -360,6 +363,19 @@ def set_probability_weights(nodes: np.ndarray, num_trees: int, depth: int, lo: f
     return nodes
 
 
+def dense_to_csr(x: np.ndarray, missing: float):
+    """(indptr int64[rows + 1], indices int32[nnz], values float32[nnz]) of a dense float32 matrix: the entries the library
+    reads as missing (|x - missing| <= 1e-6 in float32, its own test) are dropped, everything else is stored, NaN included."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim != 2:
+        raise ValueError("x must be [rows, cols]")
+    with np.errstate(invalid="ignore"):
+        keep = ~(np.abs(x - np.float32(missing)) <= np.float32(1.0e-6))
+    indptr = np.zeros(x.shape[0] + 1, dtype=np.int64)
+    np.cumsum(keep.sum(axis=1), out=indptr[1:])
+    return indptr, np.nonzero(keep)[1].astype(np.int32), x[keep]
+
+
 def encode_nodes(fid, value, def_left, weight, is_leaf) -> np.ndarray:
     """Vector form of encode_node (Struct.h:103-108) for building test forests by hand."""
     fid = np.asarray(fid, dtype=np.int64)
@@ -443,6 +459,39 @@ class Forest:
         _check(lib.tahoe_forest_predict(self._h, _ptr(preds), _ptr(data), rows, _stream(stream)),
                "tahoe_forest_predict")
         return preds
+
+    def predict_csr(self, indptr, indices=None, values=None, out=None, stream=None):
+        """predict on rows given as CSR (tahoe_forest_predict_csr): an entry that is not stored is missing.  CUDA tensors indptr
+        [rows + 1], indices [nnz], values [nnz] (cast to int64 / int32 / float32 where needed), or one torch.sparse_csr tensor
+        of shape [rows, num_cols].  Bit for bit what predict returns for the densified rows."""
+        import torch
+
+        if indices is None and values is None:
+            t = indptr
+            assert t.layout == torch.sparse_csr and tuple(t.shape)[1] == self.num_cols, (t.layout, tuple(t.shape), self.num_cols)
+            indptr, indices, values = t.crow_indices(), t.col_indices(), t.values()
+        assert indptr.is_cuda and indices.is_cuda and values.is_cuda and indptr.dim() == 1 and indptr.numel() >= 1
+        assert indices.dim() == 1 and values.dim() == 1 and indices.numel() == values.numel()
+        indptr = indptr.to(torch.int64).contiguous()
+        indices = indices.to(torch.int32).contiguous()
+        values = values.to(torch.float32).contiguous()
+        rows, nnz = indptr.numel() - 1, values.numel()
+        if out is None:
+            out = torch.empty(self._out_shape(rows), dtype=torch.float32, device=values.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == self._out_shape(rows)
+        _check(lib.tahoe_forest_predict_csr(self._h, _ptr(out), _ptr(indptr), _ptr(indices) if nnz else None,
+                                            _ptr(values) if nnz else None, rows, nnz, _stream(stream)), "tahoe_forest_predict_csr")
+        return out
+
+    def reserve_csr(self, rows: int, nnz: int) -> None:
+        """Sizes the workspace of predict_csr for batches of up to `rows` rows and `nnz` entries (tahoe_forest_reserve_csr)."""
+        _check(lib.tahoe_forest_reserve_csr(self._h, rows, nnz), "tahoe_forest_reserve_csr")
+
+    def csr_plan(self, rows: int, nnz: int):
+        """(kernel form name, rows per densified chunk; 0 = the fused CSR kernel) of a predict_csr of that size."""
+        form, chunk = _i(), _sz()
+        _check(lib.tahoe_forest_get_csr_plan(self._h, rows, nnz, C.byref(form), C.byref(chunk)), "tahoe_forest_get_csr_plan")
+        return lib.tahoe_kernel_form_name(form.value).decode(), chunk.value
 
     def predict_raw(self, data, sums=None, stream=None):
         import torch

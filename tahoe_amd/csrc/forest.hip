@@ -96,14 +96,15 @@ __global__ void __launch_bounds__(kBlock) direct_kernel(const InnerNode *__restr
 //
 // Dynamic LDS: [cols][64] float | kWaves slots of slot_nodes InnerNode | [2][kWaves][64] float.
 // MC: the owner lane stores its sum at the end of every class (direct_kernel).
-template <bool WRITE_LEAF, bool MC = false>
+// CSR: the tile is staged from csr by csr_stage_tile (forest_internal.h) and `data` is not read.
+template <bool WRITE_LEAF, bool MC = false, bool CSR = false>
 __global__ void __launch_bounds__(kBlock) rowtile_kernel(const InnerNode *__restrict__ inner,
                                                          const float *__restrict__ leaf_val,
                                                          const uint32_t *__restrict__ leaf_orig,
                                                          const float *__restrict__ data, float *sums,
                                                          uint32_t *__restrict__ leaf_out, const float *sums_in, size_t rows, int cols,
                                                          int num_trees, int depth, int lds_levels, float missing,
-                                                         int vec4_ok, int num_classes)
+                                                         int vec4_ok, int num_classes, CsrView csr)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
@@ -120,7 +121,9 @@ __global__ void __launch_bounds__(kBlock) rowtile_kernel(const InnerNode *__rest
     const bool row_ok = row < rows;
 
     // ---- stage the row tile, transposed to feature-major ----
-    {
+    if constexpr (CSR) {
+        csr_stage_tile<kBlock>(tile, reinterpret_cast<int64_t *>(vals), cols, row0, rows, csr, missing, threadIdx.x);
+    } else {
         const float *src = data + (row_ok ? row : row0) * (size_t)cols;
         if (vec4_ok) {
             const float4 *src4 = reinterpret_cast<const float4 *>(src);
@@ -830,12 +833,14 @@ static void launch_tilering(tahoe_forest *f, float *sums, uint32_t *leaf_out, co
 
 // sums_in (optional, may be `sums` itself): running float32 sums of the trees BEFORE this forest -- every kernel then
 // continues that sum in tree order instead of starting from 0.0f (tahoe_forest_predict_accumulate).
+// csr (optional): the rows come from there through the fused loader of csr_strategy's tile kernel; `data` is not read.
 static tahoe_status launch_traversal(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data,
-                                     size_t rows, hipStream_t stream, const float *sums_in = nullptr)
+                                     size_t rows, hipStream_t stream, const float *sums_in = nullptr, const CsrView *csr = nullptr,
+                                     int csr_strategy = 0)
 {
     if (rows == 0) return TAHOE_OK;
     DeviceGuard on_device(f->device);
-    const int strategy = resolve_strategy(f, rows);
+    const int strategy = csr ? csr_strategy : resolve_strategy(f, rows);
     if ((rows + 63) / 64 > 0x7fffffffu) return fail(TAHOE_ERR_INVALID_ARG, "too many rows for one launch: %zu", rows);
     if (const tahoe_status s = strategy_available(f, strategy)) return s;  // (set_strategy has refused it already)
     const bool timed = f->profiling && f->prof_count < f->ev_start.size();
@@ -855,7 +860,7 @@ static tahoe_status launch_traversal(tahoe_forest *f, float *sums, uint32_t *lea
         else if (sums && !sums_in)
             TAHOE_HIP_TRY(hipMemsetAsync(sums, 0, rows * (size_t)f->num_classes * sizeof(float), stream));
     } else if (f->sp) {
-        const tahoe_status ss = sparse_launch(f, sums, leaf_out, data, rows, stream, strategy, sums_in);
+        const tahoe_status ss = sparse_launch(f, sums, leaf_out, data, rows, stream, strategy, sums_in, csr);
         if (ss != TAHOE_OK) return ss;
     } else if (strategy == TAHOE_STRATEGY_QRING) {
         const tahoe_status qs = qring_launch(f, sums, leaf_out, data, rows, stream, timed ? f->ev_mid[f->prof_count] : nullptr, sums_in);
@@ -881,9 +886,14 @@ static tahoe_status launch_traversal(tahoe_forest *f, float *sums, uint32_t *lea
         const int lds = rowtile_lds_bytes(f->p.num_cols, f->lds_levels);
         const int nc = f->num_classes;
         with_leaf_mc(leaf_out != nullptr, nc > 1, [&](auto wl, auto mc) {
-            hipLaunchKernelGGL((rowtile_kernel<decltype(wl)::value, decltype(mc)::value>), dim3((unsigned)grid), dim3(kBlock), lds,
-                               stream, f->inner, f->leaf_val, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
-                               f->p.num_trees, f->depth, f->lds_levels, f->p.missing, vec4_ok, nc);
+            if (csr)  // (predictions only: no leaf-index form)
+                hipLaunchKernelGGL((rowtile_kernel<false, decltype(mc)::value, true>), dim3((unsigned)grid), dim3(kBlock), lds, stream,
+                                   f->inner, f->leaf_val, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
+                                   f->p.num_trees, f->depth, f->lds_levels, f->p.missing, vec4_ok, nc, *csr);
+            else
+                hipLaunchKernelGGL((rowtile_kernel<decltype(wl)::value, decltype(mc)::value>), dim3((unsigned)grid), dim3(kBlock), lds,
+                                   stream, f->inner, f->leaf_val, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
+                                   f->p.num_trees, f->depth, f->lds_levels, f->p.missing, vec4_ok, nc, CsrView{});
         });
         TAHOE_HIP_TRY(hipGetLastError());
     } else if (strategy == TAHOE_STRATEGY_DIRECT) {
@@ -988,6 +998,8 @@ static tahoe_knobs read_knobs()
     k.wstream = num("TAHOE_WSTREAM", k.wstream);
     k.wstream_slab_mb = num("TAHOE_WSTREAM_SLAB_MB", k.wstream_slab_mb);
     k.approx_form = num("TAHOE_APPROX_FORM", k.approx_form);
+    k.csr_chunk_mb = num("TAHOE_CSR_CHUNK_MB", k.csr_chunk_mb);
+    k.csr_fused = num("TAHOE_CSR_FUSED", k.csr_fused);
     return k;
 }
 
@@ -1010,9 +1022,9 @@ tahoe_status open_handle(const tahoe_forest_params *p, int num_classes, ForestPt
     f->lds_limit = (int)prop.maxSharedMemoryPerMultiProcessor > 0 ? (int)prop.maxSharedMemoryPerMultiProcessor
                                                                    : (int)prop.sharedMemPerBlock;
     f->knobs = read_knobs();
-    if (const tahoe_status s = hip_status(hipMalloc(reinterpret_cast<void **>(&f->error_flag), sizeof(int)), "hipMalloc(error_flag)"))
+    if (const tahoe_status s = hip_status(hipMalloc(reinterpret_cast<void **>(&f->error_flag), 2 * sizeof(int)), "hipMalloc(error_flag)"))
         return s;
-    return hip_status(hipMemset(f->error_flag, 0, sizeof(int)), "hipMemset(error_flag)");
+    return hip_status(hipMemset(f->error_flag, 0, 2 * sizeof(int)), "hipMemset(error_flag)");
 }
 
 // The float32 kernels of a dense handle that may need more than the default 64 KiB of dynamic LDS: every form its shape can take
@@ -1022,7 +1034,9 @@ static tahoe_status allow_float32_lds(const tahoe_forest *f)
     hipError_t e = hipSuccess;
     if (rowtile_fits(f) &&
         ((e = allow_max_lds_leaf([](auto wl) { return &rowtile_kernel<decltype(wl)::value>; }, lim)) != hipSuccess ||
-         (f->num_classes > 1 && (e = allow_max_lds_leaf([](auto wl) { return &rowtile_kernel<decltype(wl)::value, true>; }, lim)) != hipSuccess)))
+         (f->num_classes > 1 && (e = allow_max_lds_leaf([](auto wl) { return &rowtile_kernel<decltype(wl)::value, true>; }, lim)) != hipSuccess) ||
+         (e = allow_max_lds(reinterpret_cast<const void *>(&rowtile_kernel<false, false, true>), lim)) != hipSuccess ||
+         (e = allow_max_lds(reinterpret_cast<const void *>(&rowtile_kernel<false, true, true>), lim)) != hipSuccess))
         return hip_status(e, "hipFuncSetAttribute(rowtile)");
     if (!f->has_blocks) return TAHOE_OK;
     if ((tileblock_lds_bytes(f, 128) <= lim &&
@@ -1036,6 +1050,40 @@ static tahoe_status allow_float32_lds(const tahoe_forest *f)
          (e = allow_max_lds_leaf([](auto wl) { return &tilering_kernel<128, 4, decltype(wl)::value>; }, lim)) != hipSuccess))
         return hip_status(e, "hipFuncSetAttribute(tilering)");
     return TAHOE_OK;
+}
+
+tahoe_status predict_rows(tahoe_forest *f, float *preds, const float *data, size_t rows, hipStream_t stream, const CsrView *csr,
+                          int csr_strategy)
+{
+    DeviceGuard on_device(f->device);
+    tahoe_status s = launch_traversal(f, preds, nullptr, data, rows, stream, nullptr, csr, csr_strategy);
+    if (s != TAHOE_OK) return s;
+    if (f->num_classes > 1) return launch_transform_mc(f, preds, rows, stream);
+    return launch_transform(preds, rows, f->p.output, f->p.num_trees, f->p.threshold, f->p.global_bias, stream);
+}
+
+int csr_fused_strategy(const tahoe_forest *f, size_t rows, size_t nnz)
+{
+    if (f->p.num_trees == 0) return -1;
+    const bool tile = f->sp ? sparse_tile_fits(f) : rowtile_fits(f);
+    const bool top = f->sp && sparse_top_waves(f) > 0;
+    // a forced strategy is honoured: the tile kernels that have the loader take it, every other strategy gets dense chunks
+    if (f->strategy == TAHOE_STRATEGY_ROWTILE) return tile ? TAHOE_STRATEGY_ROWTILE : -1;
+    if (f->strategy == TAHOE_STRATEGY_TILEBLOCK) return top ? TAHOE_STRATEGY_TILEBLOCK : -1;
+    if (f->strategy != TAHOE_STRATEGY_AUTO || f->knobs.csr_fused == 0) return -1;
+    const int fused = top ? TAHOE_STRATEGY_TILEBLOCK : tile ? TAHOE_STRATEGY_ROWTILE : -1;
+    if (f->knobs.csr_fused > 0) return fused;
+    // AUTO, as measured (tools/csr_time.py, profiles/csr/csr_time.json).  Where AUTO runs that tile kernel
+    // on dense rows anyway, the same kernel fed from CSR saves writing the chunk and reading it back: faster at every density.
+    if (resolve_strategy(f, rows) == fused) return fused;
+    // A dense handle whose AUTO is another form (QRING, TILERING): ROWTILE from CSR beats densify + AUTO while the forest is
+    // light for its width (trees x depth <= 8 x num_cols, the heaviest shape it was measured to win on) and at most a quarter
+    // of the entries is stored (500 x depth 8 on 500 features: 1.9 - 2.2 ms against 3.3 - 3.6 ms; with every entry stored 3.4
+    // against 2.8 ms).  Heavier forests are where QRING outruns ROWTILE by more than the densify pass costs.
+    if (!f->sp && tile && (long long)f->p.num_trees * f->depth <= 8LL * f->p.num_cols &&
+        4.0 * (double)nnz <= (double)rows * (double)f->p.num_cols)
+        return TAHOE_STRATEGY_ROWTILE;
+    return -1;
 }
 
 }  // namespace tahoe
@@ -1292,6 +1340,7 @@ void tahoe_forest_destroy(tahoe_forest *f)
     if (f->blocks) (void)hipFree(f->blocks);
     if (f->error_flag) (void)hipFree(f->error_flag);
     pipeline_destroy(f);
+    csr_destroy(f);
     qring_destroy(f);
     sparse_destroy(f);
     widef_destroy(f);
@@ -1326,12 +1375,7 @@ tahoe_status tahoe_forest_predict(tahoe_forest *f, float *preds_dev, const float
 {
     if (!f || (rows && (!preds_dev || !data_dev)))
         return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict: null argument");
-    DeviceGuard on_device(f->device);
-    tahoe_status s = launch_traversal(f, preds_dev, nullptr, data_dev, rows, (hipStream_t)stream);
-    if (s != TAHOE_OK) return s;
-    if (f->num_classes > 1) return launch_transform_mc(f, preds_dev, rows, (hipStream_t)stream);
-    return launch_transform(preds_dev, rows, f->p.output, f->p.num_trees, f->p.threshold, f->p.global_bias,
-                            (hipStream_t)stream);
+    return predict_rows(f, preds_dev, data_dev, rows, (hipStream_t)stream);
 }
 
 tahoe_status tahoe_forest_predict_leaf_idx(tahoe_forest *f, uint32_t *leaf_dev, float *sums_dev,
@@ -1372,9 +1416,14 @@ tahoe_status tahoe_forest_check(tahoe_forest *f, void *stream)
     if (!f) return fail(TAHOE_ERR_INVALID_ARG, "null forest");
     TAHOE_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     if (f->error_flag) {
-        int flag = 0;
-        TAHOE_HIP_TRY(hipMemcpy(&flag, f->error_flag, sizeof(int), hipMemcpyDeviceToHost));
-        if (flag != 0) return fail(TAHOE_ERR_HIP, "a bounded LDS ring wait timed out (TILERING/QRING); results are invalid");
+        int flags[2] = {0, 0};
+        TAHOE_HIP_TRY(hipMemcpy(flags, f->error_flag, sizeof(flags), hipMemcpyDeviceToHost));
+        if (flags[0] != 0) return fail(TAHOE_ERR_HIP, "a bounded LDS ring wait timed out (TILERING/QRING); results are invalid");
+        if (flags[1] != 0) {  // reported once: a later clean call checks OK
+            TAHOE_HIP_TRY(hipMemset(f->error_flag + 1, 0, sizeof(int)));
+            return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_csr: an entry named a column outside [0, %d); such entries were "
+                                               "skipped (their rows read the missing value there)", f->p.num_cols);
+        }
     }
     return TAHOE_OK;
 }
@@ -1411,7 +1460,8 @@ const char *tahoe_kernel_form_name(int form)
     static const char *const names[] = {"none", "direct", "rowtile", "tileblock", "tilering_tile", "tilering_wide_tile",
                                         "tilering_wide_stream", "qring_region3", "qring_region2", "qring_region_mixed",
                                         "qring_split", "qring_columns", "qring_wide", "qring_gx", "sparse_direct",
-                                        "sparse_rowtile", "sparse_top", "sparse_qring", "qring_region8", "qring_region6"};
+                                        "sparse_rowtile", "sparse_top", "sparse_qring", "qring_region8", "qring_region6",
+                                        "csr_rowtile", "csr_sparse_rowtile", "csr_sparse_top"};
     return form >= 0 && form < (int)(sizeof(names) / sizeof(names[0])) ? names[form] : "?";
 }
 

@@ -77,6 +77,8 @@ struct tahoe_knobs {
     int wstream = -1;             // TAHOE_WSTREAM: 0 = never the row-streaming form, 1 = wherever it can be built, -1 = the shape rule
     int wstream_slab_mb = 1024;   // TAHOE_WSTREAM_SLAB_MB: cap of the row-streaming form's leaf-value workspace (at least 1 MiB)
     int approx_form = 0;          // TAHOE_APPROX_FORM: 1 = the LDS slab wherever one wave's slab fits, 2 = in place
+    int csr_chunk_mb = 64;        // TAHOE_CSR_CHUNK_MB: cap of tahoe_forest_predict_csr's densify chunk (at least one 64-row tile)
+    int csr_fused = -1;           // TAHOE_CSR_FUSED: under AUTO, 0 = never the fused CSR tile kernels, 1 = wherever one exists, -1 = the rule
 };
 
 struct tahoe_forest {
@@ -97,7 +99,10 @@ struct tahoe_forest {
     uint32_t *leaf_orig = nullptr;
     unsigned char *top = nullptr;  // [T][top_stride]
     uint4 *blocks = nullptr;       // [T][2^(De-2)][2]
-    int *error_flag = nullptr;     // set by TILERING if a bounded spin ever times out
+    int *error_flag = nullptr;     // [0] set by TILERING if a bounded spin ever times out; [1] by a CSR loader that skipped an
+                                   // entry whose column id is outside [0, num_cols) (tahoe_forest_check reports and clears it)
+    float *csr_chunk = nullptr;    // tahoe_forest_predict_csr's fallback: csr_chunk_rows x num_cols densified rows (csr.hip)
+    size_t csr_chunk_rows = 0;
     tahoe_qstate *q = nullptr;     // QRING: rank-quantised forest + row workspace (qring.hip)
     tahoe_sstate *sp = nullptr;    // non-null: this handle is a sparse forest (sparse.hip); the dense views are unused
     tahoe_pstate *pipe = nullptr;  // tahoe_forest_predict_host: chunk buffers, streams, events (created on first use)
@@ -233,6 +238,54 @@ __device__ __forceinline__ void ring_dead(bool dead, int lane, int *error_flag)
     if (dead && lane == 0) atomicOr(error_flag, 1);
 }
 
+// ---- CSR rows (tahoe_forest_predict_csr; DESIGN.md, "CSR rows") ----
+// Row r holds values[k] in column indices[k] for k in [indptr[r], indptr[r + 1]), the missing sentinel everywhere else.
+struct CsrView {
+    const int64_t *indptr = nullptr;  // rows + 1
+    const int32_t *indices = nullptr;
+    const float *values = nullptr;
+    size_t nnz = 0;                   // entry ranges are clamped to [0, nnz]: no read outside indices / values
+    int *bad_column = nullptr;        // raised when an entry names a column outside [0, num_cols); the entry is skipped
+};
+constexpr int kCsrLanes = 8;  // lanes that stride over one row's entries
+
+// indptr[row] clamped to [0, nnz]; rows past the batch get the empty range at indptr[rows]
+__device__ __forceinline__ int64_t csr_row_begin(const CsrView &csr, size_t row, size_t rows)
+{
+    const int64_t p = csr.indptr[row < rows ? row : rows];
+    return p < 0 ? 0 : (p > (int64_t)csr.nnz ? (int64_t)csr.nnz : p);
+}
+
+// The fused loader of the 64-row float32 tile kernels (NT threads): tile[f * 64 + r] = missing everywhere (ds_write_b128, no
+// global traffic), barrier, then the stored entries of rows row0 .. row0 + 63 over it.  range: 65 int64 of LDS scratch that
+// nothing else uses before the caller's next barrier -- the tile's indptr values, read once per workgroup.  kCsrLanes lanes
+// stride over a row, so a wave scatters 8 rows at once: a ds_write_b32 banks on (address / 4) % 32 = row % 32 here, whatever
+// the column, and lanes of one row therefore serialise -- 8-way with 8 lanes per row where one row per wave would be 32-way --
+// while each row's indices / values are still read as 32-byte runs.  The caller's barrier after this completes the tile.
+template <int NT>
+__device__ __forceinline__ void csr_stage_tile(float *tile, int64_t *range, int cols, size_t row0, size_t rows, const CsrView &csr,
+                                               float missing, int tid)
+{
+    static_assert(NT > kTileRows && NT % kCsrLanes == 0, "one thread per indptr value of the tile");
+    float4 *tile4 = reinterpret_cast<float4 *>(tile);
+    const float4 m4 = make_float4(missing, missing, missing, missing);
+    for (int i = tid; i < cols * (kTileRows / 4); i += NT) tile4[i] = m4;
+    if (tid <= kTileRows) range[tid] = csr_row_begin(csr, row0 + tid, rows);
+    __syncthreads();  // the fill lands before the scatter (s_waitcnt lgkmcnt(0) + s_barrier)
+    const int sub = tid % kCsrLanes;
+    bool bad = false;
+    for (int r = tid / kCsrLanes; r < kTileRows; r += NT / kCsrLanes) {
+        const int64_t end = range[r + 1];
+        for (int64_t k = range[r] + sub; k < end; k += kCsrLanes) {
+            const int32_t c = csr.indices[k];
+            const float v = csr.values[k];
+            if ((uint32_t)c < (uint32_t)cols) tile[c * kTileRows + r] = v;
+            else bad = true;
+        }
+    }
+    if (bad) atomicOr(csr.bad_column, 1);
+}
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is per function and process-wide, not per handle: always raise it to
 // the device limit (less the kernel's static LDS), so that handles of different shapes can coexist in one process.
 inline hipError_t allow_max_lds(const void *fn, int limit)
@@ -337,6 +390,14 @@ inline tahoe_status finish_create(ForestPtr &f, unsigned flags, tahoe_forest **o
 // TAHOE_OK when handle f can run `strategy` (a valid TAHOE_STRATEGY_*), else the refusal (TAHOE_ERR_UNSUPPORTED) saying why.
 // AUTO always resolves to an available strategy.
 tahoe_status strategy_available(const tahoe_forest *f, int strategy);
+// tahoe_forest_predict on device rows (forest.hip).  With csr the rows come from there through the fused loader of the tile
+// kernel of csr_strategy (a value csr_fused_strategy returned) and `data` is not read.
+tahoe_status predict_rows(tahoe_forest *f, float *preds, const float *data, size_t rows, hipStream_t stream,
+                          const CsrView *csr = nullptr, int csr_strategy = 0);
+// The strategy whose fused CSR kernel serves a batch of `rows` rows with nnz stored entries (ROWTILE, or TILEBLOCK on a sparse
+// handle), or -1: the batch is densified in chunks and takes the handle's own path (csr.hip)
+int csr_fused_strategy(const tahoe_forest *f, size_t rows, size_t nnz);
+void csr_destroy(tahoe_forest *f);
 
 // The branch rule of infer_one_tree, BaseTahoeTest.h:450-453: 1 = right child.
 __device__ __forceinline__ uint32_t go_right(float x, float thr, bool def_left, float missing)
@@ -398,7 +459,7 @@ int qring_form(const tahoe_forest *f, size_t rows);  // TAHOE_FORM_* of the laun
 // sparse forests (sparse.hip)
 bool sparse_tile_fits(const tahoe_forest *f);
 tahoe_status sparse_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data, size_t rows,
-                           hipStream_t stream, int strategy, const float *sums_in = nullptr);
+                           hipStream_t stream, int strategy, const float *sums_in = nullptr, const CsrView *csr = nullptr);
 int sparse_top_waves(const tahoe_forest *f);
 bool sparse_q_available(const tahoe_forest *f);  // the walk on quantised codes (strategy QRING on a sparse handle)
 bool sparse_has_cats(const tahoe_forest *f);     // categorical splits (tahoe_sparse_forest_create_cat): no QRING

@@ -75,14 +75,16 @@ constexpr long long kCatMaxWords = 1 << 19;  // categories < 2^24: exact in floa
 // MC (multi-class handle, trees class-major): the owner lanes store the sum to sums[row * num_classes + c] at the last tree of
 // class c and restart from 0.0f (sums_in is not read); leaf indices go to the caller's tree numbering.
 // CAT (a handle with categorical splits): a node flagged kSCat takes go_right_cat on the pool entry its `val` bits name.
-template <bool TILE, bool WRITE_LEAF, bool MC = false, bool CAT = false>
+// CSR (with TILE): the tile is staged from csr by csr_stage_tile (forest_internal.h) and `data` is not read.
+template <bool TILE, bool WRITE_LEAF, bool MC = false, bool CAT = false, bool CSR = false>
 __global__ void __launch_bounds__(kBlock) sparse_kernel(const tahoe_sparse_node *__restrict__ nodes,
                                                         const int32_t *__restrict__ trees, const float *__restrict__ data,
                                                         float *sums, uint32_t *__restrict__ leaf_out,
                                                         const float *sums_in, size_t rows, int cols, int num_trees, float missing,
                                                         int vec4_ok, int num_classes, const uint32_t *__restrict__ cat_pool,
-                                                        uint32_t cat_words)
+                                                        uint32_t cat_words, CsrView csr)
 {
+    static_assert(TILE || !CSR, "the CSR loader fills a tile");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -92,7 +94,10 @@ __global__ void __launch_bounds__(kBlock) sparse_kernel(const tahoe_sparse_node 
     const size_t row = row0 + lane;
     const bool row_ok = row < rows;
     const float *xrow = data + (row_ok ? row : row0) * (size_t)cols;
-    if (TILE) {
+    if constexpr (CSR) {
+        csr_stage_tile<kBlock>(tile, reinterpret_cast<int64_t *>(vals), cols, row0, rows, csr, missing, threadIdx.x);
+        __syncthreads();
+    } else if (TILE) {
         if (vec4_ok) {
             const float4 *src4 = reinterpret_cast<const float4 *>(xrow);
             for (int f4 = wave; f4 < cols / 4; f4 += kWaves) {
@@ -172,13 +177,14 @@ constexpr int kSTop = 512;    // nodes per slot (8 B each)
 constexpr int kSRing = 32;    // ring entries (trees)
 constexpr int kSBatch = 4;    // trees the consumer takes per poll (K5: 16 -> 5.34 ms, 8 -> 5.19, 4 -> 5.15)
 // MC: as sparse_kernel's, in the consumer wave.  CAT: a node flagged kSCCat takes go_right_cat on the pool entry in its x word.
-template <int NW, bool WRITE_LEAF, bool MC = false, bool CAT = false>
+// CSR: as sparse_kernel's.
+template <int NW, bool WRITE_LEAF, bool MC = false, bool CAT = false, bool CSR = false>
 __global__ void __launch_bounds__(NW * 64) sparse_top_kernel(const uint2 *__restrict__ cnodes, const int32_t *__restrict__ ctrees,
                                                              const uint32_t *__restrict__ corig, const float *__restrict__ data,
                                                              float *sums, uint32_t *__restrict__ leaf_out,
                                                              const float *sums_in, size_t rows, int cols, int num_trees, float missing,
                                                              int vec4_ok, int *__restrict__ error_flag, int num_classes,
-                                                             const uint32_t *__restrict__ cat_pool, uint32_t cat_words)
+                                                             const uint32_t *__restrict__ cat_pool, uint32_t cat_words, CsrView csr)
 {
     constexpr int NWALK = NW - 1;
     static_assert(kSRing >= 2 * kSBatch && kSRing > NWALK, "ring too small");
@@ -194,7 +200,9 @@ __global__ void __launch_bounds__(NW * 64) sparse_top_kernel(const uint2 *__rest
     const size_t row = row0 + lane;
     const bool row_ok = row < rows;
     const float *xrow = data + (row_ok ? row : row0) * (size_t)cols;
-    if (vec4_ok) {
+    if constexpr (CSR) {
+        csr_stage_tile<NW * 64>(tile, reinterpret_cast<int64_t *>(ring_vals), cols, row0, rows, csr, missing, threadIdx.x);
+    } else if (vec4_ok) {
         const float4 *src4 = reinterpret_cast<const float4 *>(xrow);
         for (int f4 = wave; f4 < cols / 4; f4 += NW) {
             const float4 v = row_ok ? src4[f4] : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -693,7 +701,7 @@ static long long sparse_lds(const tahoe_forest *f, bool tile)
 bool sparse_tile_fits(const tahoe_forest *f) { return f->p.num_cols >= 1 && sparse_lds(f, true) <= f->lds_limit; }
 
 tahoe_status sparse_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data, size_t rows,
-                           hipStream_t stream, int strategy, const float *sums_in)
+                           hipStream_t stream, int strategy, const float *sums_in, const CsrView *csr)
 {
     const tahoe_sstate *sp = f->sp;
     const unsigned grid = (unsigned)((rows + kTileRows - 1) / kTileRows);
@@ -706,9 +714,16 @@ tahoe_status sparse_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, con
         with_leaf_mc(leaf_out != nullptr, nc > 1, [&](auto wl, auto mc) {
             auto launch = [&](auto nw_c, auto cat) {
                 constexpr int NW = decltype(nw_c)::value;
-                hipLaunchKernelGGL((sparse_top_kernel<NW, decltype(wl)::value, decltype(mc)::value, decltype(cat)::value>), dim3(grid),
-                                   dim3(NW * 64), lds, stream, sp->cnodes, sp->ctrees, sp->corig, data, sums, leaf_out, sums_in, rows,
-                                   f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, f->error_flag, nc, sp->cat_pool, sp->cat_words);
+                if (csr)  // (predictions only: no leaf-index form)
+                    hipLaunchKernelGGL((sparse_top_kernel<NW, false, decltype(mc)::value, decltype(cat)::value, true>), dim3(grid),
+                                       dim3(NW * 64), lds, stream, sp->cnodes, sp->ctrees, sp->corig, data, sums, leaf_out, sums_in, rows,
+                                       f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, f->error_flag, nc, sp->cat_pool,
+                                       sp->cat_words, *csr);
+                else
+                    hipLaunchKernelGGL((sparse_top_kernel<NW, decltype(wl)::value, decltype(mc)::value, decltype(cat)::value>), dim3(grid),
+                                       dim3(NW * 64), lds, stream, sp->cnodes, sp->ctrees, sp->corig, data, sums, leaf_out, sums_in, rows,
+                                       f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, f->error_flag, nc, sp->cat_pool,
+                                       sp->cat_words, CsrView{});
             };
             auto with_cat = [&](auto nw_c) {
                 if (sp->cat_pool) launch(nw_c, std::true_type{});
@@ -725,9 +740,17 @@ tahoe_status sparse_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, con
     const int nc = f->num_classes;
     with_leaf_mc(leaf_out != nullptr, nc > 1, [&](auto wl, auto mc) {
         auto launch = [&](auto tile_c, auto cat) {
+            if constexpr (decltype(tile_c)::value) {
+                if (csr) {  // (predictions only: no leaf-index form)
+                    hipLaunchKernelGGL((sparse_kernel<true, false, decltype(mc)::value, decltype(cat)::value, true>), dim3(grid),
+                                       dim3(kBlock), lds, stream, sp->nodes, sp->trees, data, sums, leaf_out, sums_in, rows,
+                                       f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, nc, sp->cat_pool, sp->cat_words, *csr);
+                    return;
+                }
+            }
             hipLaunchKernelGGL((sparse_kernel<decltype(tile_c)::value, decltype(wl)::value, decltype(mc)::value, decltype(cat)::value>),
                                dim3(grid), dim3(kBlock), lds, stream, sp->nodes, sp->trees, data, sums, leaf_out, sums_in, rows,
-                               f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, nc, sp->cat_pool, sp->cat_words);
+                               f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, nc, sp->cat_pool, sp->cat_words, CsrView{});
         };
         auto with_cat = [&](auto tile_c) {
             if (sp->cat_pool) launch(tile_c, std::true_type{});
@@ -1040,6 +1063,17 @@ static tahoe_status sparse_top_build(tahoe_forest *f, const int32_t *trees, cons
          ((e = allow_max_lds_leaf([](auto wl) { return &sparse_top_kernel<16, decltype(wl)::value, true>; }, f->lds_limit)) != hipSuccess ||
           (e = allow_max_lds_leaf([](auto wl) { return &sparse_top_kernel<8, decltype(wl)::value, true>; }, f->lds_limit)) != hipSuccess)))
         return hip_status(e, "hipFuncSetAttribute(sparse_top)");
+    {  // the CSR-loader forms (tahoe_forest_predict_csr) of this handle's kind
+        auto allow = [&](auto mc, auto ct_) {
+            constexpr bool M = decltype(mc)::value, K = decltype(ct_)::value;
+            const hipError_t a = allow_max_lds(reinterpret_cast<const void *>(&sparse_top_kernel<16, false, M, K, true>), f->lds_limit);
+            return a != hipSuccess ? a : allow_max_lds(reinterpret_cast<const void *>(&sparse_top_kernel<8, false, M, K, true>), f->lds_limit);
+        };
+        const bool mc = f->num_classes > 1;
+        e = cat ? (mc ? allow(std::true_type{}, std::true_type{}) : allow(std::false_type{}, std::true_type{}))
+                : (mc ? allow(std::true_type{}, std::false_type{}) : allow(std::false_type{}, std::false_type{}));
+        if (e != hipSuccess) return hip_status(e, "hipFuncSetAttribute(sparse_top, csr)");
+    }
     if (cat) {
         if ((e = allow_max_lds_leaf([](auto wl) { return &sparse_top_kernel<16, decltype(wl)::value, false, true>; }, f->lds_limit)) != hipSuccess ||
             (e = allow_max_lds_leaf([](auto wl) { return &sparse_top_kernel<8, decltype(wl)::value, false, true>; }, f->lds_limit)) != hipSuccess ||
@@ -1198,6 +1232,13 @@ static tahoe_status create_sparse(tahoe_forest **out, const int32_t *trees, cons
          (cats && ((e = allow_max_lds_leaf([](auto wl) { return &sparse_kernel<true, decltype(wl)::value, false, true>; }, f->lds_limit)) != hipSuccess ||
                    (e = allow_max_lds_leaf([](auto wl) { return &sparse_kernel<true, decltype(wl)::value, true, true>; }, f->lds_limit)) != hipSuccess))))
         return hip_status(e, "hipFuncSetAttribute(sparse)");
+    if (sparse_tile_fits(f.get())) {  // the CSR-loader form (tahoe_forest_predict_csr) of this handle's kind
+        const void *k = cats ? (num_classes > 1 ? (const void *)&sparse_kernel<true, false, true, true, true>
+                                                : (const void *)&sparse_kernel<true, false, false, true, true>)
+                             : (num_classes > 1 ? (const void *)&sparse_kernel<true, false, true, false, true>
+                                                : (const void *)&sparse_kernel<true, false, false, false, true>);
+        if ((e = allow_max_lds(k, f->lds_limit)) != hipSuccess) return hip_status(e, "hipFuncSetAttribute(sparse, csr)");
+    }
     if (p->num_cols <= 32767 && p->num_trees > 0 && (s = sparse_top_build(f.get(), trees, nodes))) return s;
     // contributions from the caller's trees, in the caller's numbering (contribs_build's order); Saabas deltas in the stored
     // (class-major) order
