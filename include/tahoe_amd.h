@@ -453,6 +453,39 @@ tahoe_status tahoe_forest_predict_raw(tahoe_forest *f, float *sums_dev, const fl
 tahoe_status tahoe_forest_predict_accumulate(tahoe_forest *f, float *sums_dev, const float *data_dev, size_t rows,
                                              void *stream);
 
+/* Staged prediction: the output after the first n boosting rounds, for many n, in one walk over the forest (XGBoost
+ * iteration_range=(0, n), LightGBM num_iteration=n, scikit-learn staged_predict).  Every kernel adds a row's leaf values in tree
+ * order from 0.0f, so the running sum after tree n - 1 is, bit for bit, the sum of the forest cut to its first n trees; the
+ * staged kernels store it there and go on.
+ *
+ * tahoe_forest_set_stages: rounds[0 .. num_stages) in host memory, strictly ascending, every value in [1, Tc], Tc = num_trees /
+ * C, C = tahoe_forest_num_classes(f) (so num_stages <= Tc).  Stage s is the forest of the caller's trees 0 .. rounds[s] * C - 1:
+ * the first rounds[s] trees of every class.  The handle keeps a device copy (num_stages ints, counted in
+ * tahoe_forest_info.device_bytes).  Synchronous, and it allocates: not graph-capturable.  A second call replaces the stages;
+ * (NULL, 0) clears them.  Refusals, TAHOE_ERR_INVALID_ARG with a text that names the offending index, checked before a device is
+ * touched: a NULL handle, num_stages < 0, NULL rounds with num_stages > 0, a value outside [1, Tc], a value not above its
+ * predecessor.  On any refusal the previous stages stay.  Served on dense, multi-class, sparse, multi-class sparse and
+ * categorical handles. */
+tahoe_status tahoe_forest_set_stages(tahoe_forest *f, const int32_t *rounds, int num_stages);
+/* out_dev[(row * S + s) * C + c], S = num_stages <- bit for bit what tahoe_forest_predict writes for that row and class on a
+ * handle created with the same parameters from the trees of stage s, output bits included, applied as that handle applies
+ * them: AVG divides by (float)rounds[s], global_bias is added, SIGMOID, THRESHOLD, then TAHOE_OUT_SOFTMAX over the C values of
+ * one (row, stage).  Asynchronous on `stream`; allocates nothing (graph-capturable after set_stages); deterministic: the same
+ * bits for a row in any batch, under every strategy that serves the call.
+ * Strategies with a staged form: DIRECT and ROWTILE on dense and multi-class handles; DIRECT, ROWTILE and TILEBLOCK on sparse,
+ * multi-class sparse and categorical handles.  A forced strategy of that set is honoured.  Under AUTO a dense handle takes
+ * ROWTILE when its tile fits LDS, else DIRECT; a sparse handle TILEBLOCK when available, else ROWTILE, else DIRECT -- whatever
+ * AUTO picks for tahoe_forest_predict.  QRING, TILERING and dense TILEBLOCK have no staged form.
+ * Refusals, in this order, nothing launched: a NULL handle: TAHOE_ERR_INVALID_ARG; no stages set: TAHOE_ERR_UNSUPPORTED
+ * (tahoe_last_error says so); a forced strategy without a staged form: TAHOE_ERR_UNSUPPORTED; then rows == 0: TAHOE_OK; NULL
+ * out_dev / data_dev with rows > 0: TAHOE_ERR_INVALID_ARG; rows * S * C * 4 overflowing size_t: TAHOE_ERR_INVALID_ARG.
+ * Out of scope: CSR rows (densify, or use tahoe_forest_predict_csr per truncated handle), a staged
+ * tahoe_forest_predict_accumulate, staged leaf indices, and a start round other than 0. */
+tahoe_status tahoe_forest_predict_staged(tahoe_forest *f, float *out_dev, const float *data_dev, size_t rows, void *stream);
+/* The strategy tahoe_forest_predict_staged runs for `rows` rows (TAHOE_STRATEGY_DIRECT, _ROWTILE or _TILEBLOCK); 0 when the call
+ * would be refused (no stages set, or a forced strategy without a staged form); -1 for a NULL handle. */
+int tahoe_forest_get_staged_strategy(const tahoe_forest *f, size_t rows);
+
 /* leaf_dev[row * num_trees + tree] <- index of the leaf the row ends in, in the tree's original heap
  * numbering (final `curr` of infer_one_tree, BaseTahoeTest.h:441-455).  sums_dev may be NULL (else rows x num_classes
  * raw sums on a multi-class handle). */

@@ -154,6 +154,9 @@ _PROTOS = {
     "tahoe_forest_predict_raw": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "tahoe_forest_predict_accumulate": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "tahoe_forest_predict_leaf_idx": (_i, [_vp, _vp, _vp, _vp, _sz, _vp]),
+    "tahoe_forest_set_stages": (_i, [_vp, _vp, _i]),
+    "tahoe_forest_predict_staged": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "tahoe_forest_get_staged_strategy": (_i, [_vp, _sz]),
     "tahoe_transform_preds": (_i, [_vp, _sz, _i, _i, _f, _f, _vp]),
     "tahoe_forest_set_strategy": (_i, [_vp, _i]),
     "tahoe_forest_get_strategy": (_i, [_vp, _sz]),
@@ -525,6 +528,37 @@ class Forest:
                                                  _ptr(data), rows, _stream(stream)),
                "tahoe_forest_predict_leaf_idx")
         return leaf, sums
+
+    def set_stages(self, rounds) -> None:
+        """Stages of predict_staged (tahoe_forest_set_stages): strictly ascending counts of boosting rounds in
+        [1, num_trees / num_classes]; None clears them.  Synchronous; a second call replaces the stages."""
+        if rounds is None:
+            _check(lib.tahoe_forest_set_stages(self._h, None, 0), "tahoe_forest_set_stages")
+            self.num_stages = 0
+            return
+        r = np.ascontiguousarray([int(v) for v in rounds], dtype=np.int32)
+        _check(lib.tahoe_forest_set_stages(self._h, r.ctypes.data if r.size else None, int(r.size)), "tahoe_forest_set_stages")
+        self.num_stages = int(r.size)
+
+    def predict_staged(self, data, out=None, stream=None):
+        """The output after the first rounds[s] boosting rounds, for every stage s of set_stages, in one walk
+        (tahoe_forest_predict_staged): float32 [rows, S], or [rows, S, num_classes] on a multi-class handle; out[:, s] carries
+        the bits of predict on a handle created from the first rounds[s] * num_classes trees."""
+        import torch
+
+        self._check_data(data)
+        rows, S = data.shape[0], getattr(self, "num_stages", 0)
+        shape = (rows, S) + ((self.num_classes,) if self.num_classes > 1 else ())
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=data.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == shape
+        _check(lib.tahoe_forest_predict_staged(self._h, _ptr(out), _ptr(data), rows, _stream(stream)),
+               "tahoe_forest_predict_staged")
+        return out
+
+    def staged_strategy(self, rows: int) -> int:
+        """Strategy predict_staged runs for `rows` rows; 0 when it would be refused (tahoe_forest_get_staged_strategy)."""
+        return lib.tahoe_forest_get_staged_strategy(self._h, rows)
 
     def _shap_out(self, name, data, k, out, stream):
         """The SHAP predict_* methods: runs the C function `name` into `out` (allocated if None), float32 [rows, num_cols + 1

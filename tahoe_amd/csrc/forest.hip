@@ -50,14 +50,19 @@ __device__ __forceinline__ uint32_t step(uint32_t idx, float thr, uint32_t meta,
 // Analogue of infer_adaptive_reorg_* (Struct.h:1196-1240).
 // MC (multi-class handle, trees class-major): the sum is stored to sums[row * num_classes + c] at the end of class c's
 // trees and restarts from 0.0f; leaf indices go to the original tree's column.
-template <bool WRITE_LEAF, bool MC = false>
+// STAGED (tahoe_forest_predict_staged): `sums` is out[rows][S][num_classes] and stages[0..S) the strictly ascending counts of
+// trees per class after which the running sum is stored -- to sums[(row * S + si) * num_classes + cls], without resetting it
+// -- by a stage cursor si that goes back to 0 at a class end; the final per-class / per-row store is not done.
+template <bool WRITE_LEAF, bool MC = false, bool STAGED = false>
 __global__ void __launch_bounds__(kBlock) direct_kernel(const InnerNode *__restrict__ inner,
                                                         const float *__restrict__ leaf_val,
                                                         const uint32_t *__restrict__ leaf_orig,
                                                         const float *__restrict__ data, float *sums,
                                                         uint32_t *__restrict__ leaf_out, const float *sums_in, size_t rows, int cols,
-                                                        int num_trees, int depth, float missing, int num_classes)
+                                                        int num_trees, int depth, float missing, int num_classes,
+                                                        const int32_t *__restrict__ stages, int S)
 {
+    static_assert(!STAGED || !WRITE_LEAF, "no staged leaf indices");
     const size_t row = (size_t)blockIdx.x * kBlock + threadIdx.x;
     if (row >= rows) return;
     const float *x = data + row * (size_t)cols;
@@ -66,6 +71,7 @@ __global__ void __launch_bounds__(kBlock) direct_kernel(const InnerNode *__restr
     float sum = sums_in ? sums_in[row] : 0.0f;  // continues a running sum (tree shards chained in order)
     const int ctrees = MC ? num_trees / num_classes : 0;
     int cls = 0, cend = ctrees;  // MC: class of tree t and the end of its trees
+    int si = 0, cbeg = 0, send = STAGED ? stages[0] : 0;  // STAGED: the cursor, the class's first tree, the tree after the stage's last
     for (int t = 0; t < num_trees; ++t) {
         const InnerNode *tree = inner + (size_t)t * n_inner;
         uint32_t idx = 0;
@@ -76,14 +82,26 @@ __global__ void __launch_bounds__(kBlock) direct_kernel(const InnerNode *__restr
         const size_t b = (size_t)t * n_leaf + (idx - (uint32_t)n_inner);
         sum += leaf_val[b];
         if (WRITE_LEAF) leaf_out[MC ? row * (size_t)num_trees + (t - cls * ctrees) * num_classes + cls : row * (size_t)num_trees + t] = leaf_orig[b];
+        if constexpr (STAGED) {
+            if (t + 1 == send) {
+                sums[(row * (size_t)S + si) * (size_t)(MC ? num_classes : 1) + cls] = sum;
+                ++si;
+                send = si < S ? cbeg + stages[si] : -1;
+            }
+        }
         if (MC && t + 1 == cend) {
-            if (sums) sums[row * (size_t)num_classes + cls] = sum;
+            if (!STAGED && sums) sums[row * (size_t)num_classes + cls] = sum;
             sum = 0.0f;
             ++cls;
             cend += ctrees;
+            if constexpr (STAGED) {
+                si = 0;
+                cbeg = t + 1;
+                send = cbeg + stages[0];
+            }
         }
     }
-    if (!MC && sums) sums[row] = sum;
+    if (!MC && !STAGED && sums) sums[row] = sum;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -97,15 +115,18 @@ __global__ void __launch_bounds__(kBlock) direct_kernel(const InnerNode *__restr
 // Dynamic LDS: [cols][64] float | kWaves slots of slot_nodes InnerNode | [2][kWaves][64] float.
 // MC: the owner lane stores its sum at the end of every class (direct_kernel).
 // CSR: the tile is staged from csr by csr_stage_tile (forest_internal.h) and `data` is not read.
-template <bool WRITE_LEAF, bool MC = false, bool CSR = false>
+// STAGED: direct_kernel's stage cursor, kept by the owner lanes; a stage can end at any of a round's four trees.
+template <bool WRITE_LEAF, bool MC = false, bool CSR = false, bool STAGED = false>
 __global__ void __launch_bounds__(kBlock) rowtile_kernel(const InnerNode *__restrict__ inner,
                                                          const float *__restrict__ leaf_val,
                                                          const uint32_t *__restrict__ leaf_orig,
                                                          const float *__restrict__ data, float *sums,
                                                          uint32_t *__restrict__ leaf_out, const float *sums_in, size_t rows, int cols,
                                                          int num_trees, int depth, int lds_levels, float missing,
-                                                         int vec4_ok, int num_classes, CsrView csr)
+                                                         int vec4_ok, int num_classes, CsrView csr,
+                                                         const int32_t *__restrict__ stages, int S)
 {
+    static_assert(!STAGED || (!WRITE_LEAF && !CSR), "staged output: predictions from dense rows");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -170,6 +191,7 @@ __global__ void __launch_bounds__(kBlock) rowtile_kernel(const InnerNode *__rest
     if (sums_in && lane < 16 && row0 + 16 * wave + lane < rows) sum = sums_in[row0 + 16 * wave + lane];
     const int ctrees = MC ? num_trees / num_classes : 0;
     int cls = 0, cend = ctrees;  // MC: class being summed and the end of its trees
+    int si = 0, cbeg = 0, send = STAGED ? stages[0] : 0;  // STAGED: the cursor, the class's first tree, the tree after the stage's last
     const int rounds = (num_trees + kWaves - 1) / kWaves;
     for (int r = 0; r < rounds; ++r) {
         const int t = r * kWaves + wave;
@@ -203,7 +225,26 @@ __global__ void __launch_bounds__(kBlock) rowtile_kernel(const InnerNode *__rest
         if (lane < 16) {
             const int rr = 16 * wave + lane;
             const int nt = min(kWaves, num_trees - r * kWaves);
-            if (MC) {
+            if constexpr (STAGED) {
+                const size_t orow = row0 + rr;
+                for (int j = 0; j < nt; ++j) {
+                    sum += vb[j * kTileRows + rr];  // tree order
+                    const int done = r * kWaves + j + 1;
+                    if (done == send) {
+                        if (orow < rows) sums[(orow * (size_t)S + si) * (size_t)(MC ? num_classes : 1) + cls] = sum;
+                        ++si;
+                        send = si < S ? cbeg + stages[si] : -1;
+                    }
+                    if (MC && done == cend) {
+                        sum = 0.0f;
+                        ++cls;
+                        cend += ctrees;
+                        si = 0;
+                        cbeg = done;
+                        send = cbeg + stages[0];
+                    }
+                }
+            } else if (MC) {
                 const size_t orow = row0 + rr;
                 for (int j = 0; j < nt; ++j) {
                     sum += vb[j * kTileRows + rr];  // tree order
@@ -219,7 +260,7 @@ __global__ void __launch_bounds__(kBlock) rowtile_kernel(const InnerNode *__rest
             }
         }
     }
-    if (!MC && sums && lane < 16) {
+    if (!MC && !STAGED && sums && lane < 16) {
         const size_t orow = row0 + 16 * wave + lane;
         if (orow < rows) sums[orow] = sum;
     }
@@ -639,17 +680,21 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
 
 // transform_k (Struct.h:196-209) with the CPU predictor's arithmetic (BaseTahoeTest.h:467-472):
 // AVG divides by num_trees (the reference's GPU epilogue multiplies by 1/T instead).
+__device__ __forceinline__ float transform_value(float r, int output, int num_trees, float threshold, float global_bias)
+{
+    if ((output & TAHOE_OUT_AVG) != 0) r = r / (float)num_trees;
+    r += global_bias;
+    if ((output & TAHOE_OUT_SIGMOID) != 0) r = 1.0f / (1.0f + expf(-r));
+    if ((output & TAHOE_OUT_THRESHOLD) != 0) r = r > threshold ? 1.0f : 0.0f;
+    return r;
+}
+
 __global__ void transform_kernel(float *preds, size_t n, int output, int num_trees, float threshold,
                                  float global_bias)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    float r = preds[i];
-    if ((output & TAHOE_OUT_AVG) != 0) r = r / (float)num_trees;
-    r += global_bias;
-    if ((output & TAHOE_OUT_SIGMOID) != 0) r = 1.0f / (1.0f + expf(-r));
-    if ((output & TAHOE_OUT_THRESHOLD) != 0) r = r > threshold ? 1.0f : 0.0f;
-    preds[i] = r;
+    preds[i] = transform_value(preds[i], output, num_trees, threshold, global_bias);
 }
 
 // Epilogue of a multi-class handle, one thread per row of preds[rows][num_classes]: per element AVG (by the trees of a
@@ -677,6 +722,42 @@ __global__ void transform_mc_kernel(float *preds, size_t rows, int num_classes, 
         s += e;
     }
     for (int c = 0; c < num_classes; ++c) p[c] = p[c] / s;
+}
+
+// transform_mc_kernel's statements on the classes of one (row, stage).  That kernel keeps them written out: routed through
+// this function it compiles to other (equivalent) code, and the pre-existing kernels stay as they were, instruction for
+// instruction; per element it is transform_value, which both share.
+__device__ __forceinline__ void transform_classes(float *p, int num_classes, int output, int class_trees, float global_bias)
+{
+    float m = -INFINITY;
+    for (int c = 0; c < num_classes; ++c) {
+        const float r = transform_value(p[c], output & ~TAHOE_OUT_THRESHOLD, class_trees, 0.0f, global_bias);
+        p[c] = r;
+        m = fmaxf(m, r);
+    }
+    if ((output & TAHOE_OUT_SOFTMAX) == 0) return;
+    float s = 0.0f;
+    for (int c = 0; c < num_classes; ++c) {
+        const float e = expf(p[c] - m);
+        p[c] = e;
+        s += e;
+    }
+    for (int c = 0; c < num_classes; ++c) p[c] = p[c] / s;
+}
+
+// Epilogue of tahoe_forest_predict_staged, one thread per (row, stage) of out[rows][S][num_classes]: what transform_kernel
+// (num_classes == 1) or transform_mc_kernel does on a handle of the first stages[s] trees of every class, whose AVG divides
+// by (float)stages[s]; the softmax runs over the classes of one (row, stage), in class order.
+__global__ void transform_staged_kernel(float *out, size_t n, int S, int num_classes, int output, const int32_t *__restrict__ stages,
+                                        float threshold, float global_bias)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int stage_trees = stages[i % (size_t)S];
+    if (num_classes == 1)
+        out[i] = transform_value(out[i], output, stage_trees, threshold, global_bias);
+    else
+        transform_classes(out + i * (size_t)num_classes, num_classes, output, stage_trees, global_bias);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -889,11 +970,11 @@ static tahoe_status launch_traversal(tahoe_forest *f, float *sums, uint32_t *lea
             if (csr)  // (predictions only: no leaf-index form)
                 hipLaunchKernelGGL((rowtile_kernel<false, decltype(mc)::value, true>), dim3((unsigned)grid), dim3(kBlock), lds, stream,
                                    f->inner, f->leaf_val, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
-                                   f->p.num_trees, f->depth, f->lds_levels, f->p.missing, vec4_ok, nc, *csr);
+                                   f->p.num_trees, f->depth, f->lds_levels, f->p.missing, vec4_ok, nc, *csr, nullptr, 0);
             else
                 hipLaunchKernelGGL((rowtile_kernel<decltype(wl)::value, decltype(mc)::value>), dim3((unsigned)grid), dim3(kBlock), lds,
                                    stream, f->inner, f->leaf_val, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
-                                   f->p.num_trees, f->depth, f->lds_levels, f->p.missing, vec4_ok, nc, CsrView{});
+                                   f->p.num_trees, f->depth, f->lds_levels, f->p.missing, vec4_ok, nc, CsrView{}, nullptr, 0);
         });
         TAHOE_HIP_TRY(hipGetLastError());
     } else if (strategy == TAHOE_STRATEGY_DIRECT) {
@@ -902,7 +983,7 @@ static tahoe_status launch_traversal(tahoe_forest *f, float *sums, uint32_t *lea
         with_leaf_mc(leaf_out != nullptr, nc > 1, [&](auto wl, auto mc) {
             hipLaunchKernelGGL((direct_kernel<decltype(wl)::value, decltype(mc)::value>), dim3((unsigned)grid), dim3(kBlock), 0,
                                stream, f->inner, f->leaf_val, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
-                               f->p.num_trees, f->depth, f->p.missing, nc);
+                               f->p.num_trees, f->depth, f->p.missing, nc, nullptr, 0);
         });
         TAHOE_HIP_TRY(hipGetLastError());
     } else {
@@ -1060,6 +1141,53 @@ tahoe_status predict_rows(tahoe_forest *f, float *preds, const float *data, size
     if (s != TAHOE_OK) return s;
     if (f->num_classes > 1) return launch_transform_mc(f, preds, rows, stream);
     return launch_transform(preds, rows, f->p.output, f->p.num_trees, f->p.threshold, f->p.global_bias, stream);
+}
+
+// The strategy of tahoe_forest_predict_staged: a forced one that has a staged form, or AUTO's -- the tile kernel that needs no
+// pre-pass (a sparse handle: TILEBLOCK, else ROWTILE, else DIRECT; a dense one: ROWTILE when its tile fits LDS, else DIRECT).
+// 0: no stages are set, or the forced strategy (QRING, TILERING, dense TILEBLOCK) has no staged form.
+static int staged_strategy(const tahoe_forest *f)
+{
+    if (!f->stages_dev) return 0;
+    const int forced = f->strategy;  // (tahoe_forest_set_strategy has checked that the handle can run it)
+    if (forced == TAHOE_STRATEGY_DIRECT || forced == TAHOE_STRATEGY_ROWTILE) return forced;
+    if (f->sp) {
+        if (forced == TAHOE_STRATEGY_TILEBLOCK) return forced;
+        if (forced != TAHOE_STRATEGY_AUTO) return 0;
+        if (sparse_top_waves(f) > 0) return TAHOE_STRATEGY_TILEBLOCK;
+        return sparse_tile_fits(f) ? TAHOE_STRATEGY_ROWTILE : TAHOE_STRATEGY_DIRECT;
+    }
+    if (forced != TAHOE_STRATEGY_AUTO) return 0;
+    return rowtile_fits(f) ? TAHOE_STRATEGY_ROWTILE : TAHOE_STRATEGY_DIRECT;
+}
+
+// The walk of tahoe_forest_predict_staged over a dense handle: DIRECT or ROWTILE with the stage stores
+static tahoe_status launch_staged_dense(tahoe_forest *f, float *out, const float *data, size_t rows, hipStream_t stream, int strategy)
+{
+    const int nc = f->num_classes, S = (int)f->num_stages;
+    const int vec4_ok = (f->p.num_cols % 4 == 0) && ((reinterpret_cast<uintptr_t>(data) & 15u) == 0);
+    auto with_mc = [&](auto &&fn) {
+        if (nc > 1) fn(std::true_type{});
+        else fn(std::false_type{});
+    };
+    if (strategy == TAHOE_STRATEGY_ROWTILE) {
+        const size_t grid = (rows + kTileRows - 1) / kTileRows;
+        const int lds = rowtile_lds_bytes(f->p.num_cols, f->lds_levels);
+        with_mc([&](auto mc) {
+            hipLaunchKernelGGL((rowtile_kernel<false, decltype(mc)::value, false, true>), dim3((unsigned)grid), dim3(kBlock), lds, stream,
+                               f->inner, f->leaf_val, f->leaf_orig, data, out, nullptr, nullptr, rows, f->p.num_cols, f->p.num_trees,
+                               f->depth, f->lds_levels, f->p.missing, vec4_ok, nc, CsrView{}, f->stages_dev, S);
+        });
+    } else {
+        const size_t grid = (rows + kBlock - 1) / kBlock;
+        with_mc([&](auto mc) {
+            hipLaunchKernelGGL((direct_kernel<false, decltype(mc)::value, true>), dim3((unsigned)grid), dim3(kBlock), 0, stream, f->inner,
+                               f->leaf_val, f->leaf_orig, data, out, nullptr, nullptr, rows, f->p.num_cols, f->p.num_trees, f->depth,
+                               f->p.missing, nc, f->stages_dev, S);
+        });
+    }
+    TAHOE_HIP_TRY(hipGetLastError());
+    return TAHOE_OK;
 }
 
 int csr_fused_strategy(const tahoe_forest *f, size_t rows, size_t nnz)
@@ -1339,6 +1467,7 @@ void tahoe_forest_destroy(tahoe_forest *f)
     if (f->top) (void)hipFree(f->top);
     if (f->blocks) (void)hipFree(f->blocks);
     if (f->error_flag) (void)hipFree(f->error_flag);
+    if (f->stages_dev) (void)hipFree(f->stages_dev);
     pipeline_destroy(f);
     csr_destroy(f);
     qring_destroy(f);
@@ -1376,6 +1505,86 @@ tahoe_status tahoe_forest_predict(tahoe_forest *f, float *preds_dev, const float
     if (!f || (rows && (!preds_dev || !data_dev)))
         return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict: null argument");
     return predict_rows(f, preds_dev, data_dev, rows, (hipStream_t)stream);
+}
+
+tahoe_status tahoe_forest_set_stages(tahoe_forest *f, const int32_t *rounds, int num_stages)
+{
+    // every check here runs before a device is touched
+    if (!f) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_set_stages: null forest");
+    if (num_stages < 0) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_set_stages: num_stages must be non-negative, got %d", num_stages);
+    if (num_stages > 0 && !rounds) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_set_stages: rounds is null with num_stages %d", num_stages);
+    for (int s = 0; s < num_stages; ++s) {
+        if (rounds[s] < 1 || rounds[s] > f->class_trees)
+            return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_set_stages: rounds[%d] = %d is outside [1, %d] (the trees of a class)", s,
+                        rounds[s], f->class_trees);
+        if (s > 0 && rounds[s] <= rounds[s - 1])
+            return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_set_stages: rounds[%d] = %d is not above rounds[%d] = %d (strictly ascending)",
+                        s, rounds[s], s - 1, rounds[s - 1]);
+    }
+    DeviceGuard on_device(f->device);
+    int32_t *dev = nullptr;
+    if (num_stages > 0) {
+        // the staged tile kernels of this handle's kind may need more than the default 64 KiB of dynamic LDS
+        hipError_t e = hipSuccess;
+        if (f->sp) {
+            if (const tahoe_status s = sparse_allow_staged_lds(f)) return s;
+        } else if (rowtile_fits(f) &&
+                   (e = allow_max_lds(f->num_classes > 1 ? reinterpret_cast<const void *>(&rowtile_kernel<false, true, false, true>)
+                                                         : reinterpret_cast<const void *>(&rowtile_kernel<false, false, false, true>),
+                                      f->lds_limit)) != hipSuccess) {
+            return hip_status(e, "hipFuncSetAttribute(rowtile, staged)");
+        }
+        size_t counted = 0;
+        e = upload(&dev, rounds, (size_t)num_stages, &counted);
+        if (e != hipSuccess) {
+            if (dev) (void)hipFree(dev);
+            return e == hipErrorOutOfMemory ? fail(TAHOE_ERR_NO_MEMORY, "tahoe_forest_set_stages: hipMalloc of %d stages failed", num_stages)
+                                            : hip_status(e, "upload(stages)");
+        }
+    }
+    TAHOE_HIP_TRY(hipDeviceSynchronize());  // a staged predict in flight may still read the stages it was launched with
+    if (f->stages_dev) {
+        (void)hipFree(f->stages_dev);
+        f->device_bytes -= f->num_stages * sizeof(int32_t);
+    }
+    f->stages_dev = dev;
+    f->num_stages = (size_t)num_stages;
+    f->device_bytes += f->num_stages * sizeof(int32_t);
+    return TAHOE_OK;
+}
+
+int tahoe_forest_get_staged_strategy(const tahoe_forest *f, size_t rows) { return f ? staged_strategy(f) : -1; }
+
+tahoe_status tahoe_forest_predict_staged(tahoe_forest *f, float *out_dev, const float *data_dev, size_t rows, void *stream)
+{
+    if (!f) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_staged: null forest");
+    if (!f->stages_dev)
+        return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_staged: no stages are set (tahoe_forest_set_stages)");
+    const int strategy = staged_strategy(f);
+    if (strategy == 0)
+        return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_staged: the forced strategy %d has no staged form; a %s handle serves "
+                                           "AUTO, DIRECT%s", f->strategy, f->sp ? "sparse" : "dense",
+                    f->sp ? ", ROWTILE and TILEBLOCK" : " and ROWTILE");
+    if (rows == 0) return TAHOE_OK;
+    if (!out_dev || !data_dev) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_staged: null argument");
+    const size_t per_row = f->num_stages * (size_t)f->num_classes;  // <= num_trees
+    if (rows > SIZE_MAX / sizeof(float) / per_row)
+        return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_staged: rows x stages x classes floats overflow size_t (rows %zu)", rows);
+    if ((rows + 63) / 64 > 0x7fffffffu) return fail(TAHOE_ERR_INVALID_ARG, "too many rows for one launch: %zu", rows);
+    DeviceGuard on_device(f->device);
+    hipStream_t st = (hipStream_t)stream;
+    const tahoe_status ws = f->sp ? sparse_launch_staged(f, out_dev, data_dev, rows, st, strategy)
+                                  : launch_staged_dense(f, out_dev, data_dev, rows, st, strategy);
+    if (ws != TAHOE_OK) return ws;
+    // (as predict_rows: the transform runs only when it changes something)
+    if (f->p.output == TAHOE_OUT_RAW && f->p.global_bias == 0.0f) return TAHOE_OK;
+    const size_t n = rows * f->num_stages;
+    if ((n + kBlock - 1) / kBlock > 0x7fffffffu)
+        return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_staged: too many (row, stage) pairs for one launch: %zu", n);
+    hipLaunchKernelGGL(transform_staged_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, out_dev, n,
+                       (int)f->num_stages, f->num_classes, f->p.output, f->stages_dev, f->p.threshold, f->p.global_bias);
+    TAHOE_HIP_TRY(hipGetLastError());
+    return TAHOE_OK;
 }
 
 tahoe_status tahoe_forest_predict_leaf_idx(tahoe_forest *f, uint32_t *leaf_dev, float *sums_dev,

@@ -125,6 +125,10 @@ struct tahoe_forest {
     bool profiling = false;
     std::vector<hipEvent_t> ev_start, ev_mid, ev_stop;  // mid: between a pre-pass kernel and the walk kernel
     size_t prof_count = 0;  // launches recorded since profiling was (re-)enabled
+    // Stages of tahoe_forest_predict_staged (tahoe_forest_set_stages): num_stages strictly ascending counts of boosting rounds
+    // (trees per class), on the device; null = none set
+    int32_t *stages_dev = nullptr;
+    size_t num_stages = 0;
 };
 
 namespace tahoe {
@@ -461,6 +465,10 @@ bool sparse_tile_fits(const tahoe_forest *f);
 tahoe_status sparse_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data, size_t rows,
                            hipStream_t stream, int strategy, const float *sums_in = nullptr, const CsrView *csr = nullptr);
 int sparse_top_waves(const tahoe_forest *f);
+// tahoe_forest_predict_staged on a sparse handle: the walk of `strategy` (DIRECT, ROWTILE or TILEBLOCK) with the stage stores to
+// out[rows][num_stages][num_classes]; sparse_allow_staged_lds lets those kernels take the device's LDS (set_stages calls it)
+tahoe_status sparse_launch_staged(tahoe_forest *f, float *out, const float *data, size_t rows, hipStream_t stream, int strategy);
+tahoe_status sparse_allow_staged_lds(const tahoe_forest *f);
 bool sparse_q_available(const tahoe_forest *f);  // the walk on quantised codes (strategy QRING on a sparse handle)
 bool sparse_has_cats(const tahoe_forest *f);     // categorical splits (tahoe_sparse_forest_create_cat): no QRING
 void sparse_destroy(tahoe_forest *f);

@@ -76,15 +76,19 @@ constexpr long long kCatMaxWords = 1 << 19;  // categories < 2^24: exact in floa
 // class c and restart from 0.0f (sums_in is not read); leaf indices go to the caller's tree numbering.
 // CAT (a handle with categorical splits): a node flagged kSCat takes go_right_cat on the pool entry its `val` bits name.
 // CSR (with TILE): the tile is staged from csr by csr_stage_tile (forest_internal.h) and `data` is not read.
-template <bool TILE, bool WRITE_LEAF, bool MC = false, bool CAT = false, bool CSR = false>
+// STAGED (tahoe_forest_predict_staged): `sums` is out[rows][S][num_classes]; the owner lanes keep a stage cursor si and store the
+// running sum, without resetting it, to sums[(row * S + si) * num_classes + cls] after the tree that completes stages[si]
+// trees of the class; the cursor goes back to 0 at a class end and the final per-class / per-row store is not done.
+template <bool TILE, bool WRITE_LEAF, bool MC = false, bool CAT = false, bool CSR = false, bool STAGED = false>
 __global__ void __launch_bounds__(kBlock) sparse_kernel(const tahoe_sparse_node *__restrict__ nodes,
                                                         const int32_t *__restrict__ trees, const float *__restrict__ data,
                                                         float *sums, uint32_t *__restrict__ leaf_out,
                                                         const float *sums_in, size_t rows, int cols, int num_trees, float missing,
                                                         int vec4_ok, int num_classes, const uint32_t *__restrict__ cat_pool,
-                                                        uint32_t cat_words, CsrView csr)
+                                                        uint32_t cat_words, CsrView csr, const int32_t *__restrict__ stages, int S)
 {
     static_assert(TILE || !CSR, "the CSR loader fills a tile");
+    static_assert(!STAGED || (!WRITE_LEAF && !CSR), "staged output: predictions from dense rows");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -116,6 +120,7 @@ __global__ void __launch_bounds__(kBlock) sparse_kernel(const tahoe_sparse_node 
     if (!MC && sums_in && lane < 16 && row0 + 16 * wave + lane < rows) sum = sums_in[row0 + 16 * wave + lane];
     const int class_trees = MC ? num_trees / num_classes : 0;
     int cls = 0, cend = class_trees;  // MC: the class being summed, and the tree after its last
+    int si = 0, cbeg = 0, send = STAGED ? stages[0] : 0;  // STAGED: the cursor, the class's first tree, the tree after the stage's last
     const int rounds = (num_trees + kWaves - 1) / kWaves;
     for (int r = 0; r < rounds; ++r) {
         const int t = r * kWaves + wave;
@@ -148,16 +153,28 @@ __global__ void __launch_bounds__(kBlock) sparse_kernel(const tahoe_sparse_node 
             const int nt = min(kWaves, num_trees - r * kWaves);
             for (int j = 0; j < nt; ++j) {
                 sum += vb[j * kTileRows + rr];  // tree order
+                if constexpr (STAGED) {
+                    if (r * kWaves + j + 1 == send) {
+                        if (row0 + rr < rows) sums[((row0 + rr) * (size_t)S + si) * (size_t)(MC ? num_classes : 1) + cls] = sum;
+                        ++si;
+                        send = si < S ? cbeg + stages[si] : -1;
+                    }
+                }
                 if (MC && r * kWaves + j + 1 == cend) {
-                    if (sums && row0 + rr < rows) sums[(row0 + rr) * (size_t)num_classes + cls] = sum;
+                    if (!STAGED && sums && row0 + rr < rows) sums[(row0 + rr) * (size_t)num_classes + cls] = sum;
                     sum = 0.0f;
                     ++cls;
                     cend += class_trees;
+                    if constexpr (STAGED) {
+                        si = 0;
+                        cbeg = r * kWaves + j + 1;
+                        send = cbeg + stages[0];
+                    }
                 }
             }
         }
     }
-    if (!MC && sums && lane < 16) {
+    if (!MC && !STAGED && sums && lane < 16) {
         const size_t orow = row0 + 16 * wave + lane;
         if (orow < rows) sums[orow] = sum;
     }
@@ -177,15 +194,18 @@ constexpr int kSTop = 512;    // nodes per slot (8 B each)
 constexpr int kSRing = 32;    // ring entries (trees)
 constexpr int kSBatch = 4;    // trees the consumer takes per poll (K5: 16 -> 5.34 ms, 8 -> 5.19, 4 -> 5.15)
 // MC: as sparse_kernel's, in the consumer wave.  CAT: a node flagged kSCCat takes go_right_cat on the pool entry in its x word.
-// CSR: as sparse_kernel's.
-template <int NW, bool WRITE_LEAF, bool MC = false, bool CAT = false, bool CSR = false>
+// CSR: as sparse_kernel's.  STAGED: sparse_kernel's stage cursor, in a consumer loop of its own; the walkers and the ring
+// hand-over are the same code.
+template <int NW, bool WRITE_LEAF, bool MC = false, bool CAT = false, bool CSR = false, bool STAGED = false>
 __global__ void __launch_bounds__(NW * 64) sparse_top_kernel(const uint2 *__restrict__ cnodes, const int32_t *__restrict__ ctrees,
                                                              const uint32_t *__restrict__ corig, const float *__restrict__ data,
                                                              float *sums, uint32_t *__restrict__ leaf_out,
                                                              const float *sums_in, size_t rows, int cols, int num_trees, float missing,
                                                              int vec4_ok, int *__restrict__ error_flag, int num_classes,
-                                                             const uint32_t *__restrict__ cat_pool, uint32_t cat_words, CsrView csr)
+                                                             const uint32_t *__restrict__ cat_pool, uint32_t cat_words, CsrView csr,
+                                                             const int32_t *__restrict__ stages, int S)
 {
+    static_assert(!STAGED || (!WRITE_LEAF && !CSR), "staged output: predictions from dense rows");
     constexpr int NWALK = NW - 1;
     static_assert(kSRing >= 2 * kSBatch && kSRing > NWALK, "ring too small");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -220,6 +240,51 @@ __global__ void __launch_bounds__(NW * 64) sparse_top_kernel(const uint2 *__rest
     if (wave == NWALK) {
         // ================= consumer: lane = row, trees in order =================
         __syncthreads();
+        if constexpr (STAGED) {
+            // The staged consumer: the loop below with the stage cursor where it adds each tree and without the final store.  It
+            // is written out a second time, in a discarded branch, because the plain consumer's instruction schedule moves with
+            // any statement added to its loop.
+            float sum = 0.0f;
+            const int class_trees = MC ? num_trees / num_classes : 0;
+            int cls = 0, cend = class_trees;
+            int si = 0, cbeg = 0, send = stages[0];  // the cursor, the class's first tree, the tree after the stage's last
+            bool dead = false;
+            for (int t0 = 0; t0 < num_trees && !dead; t0 += kSBatch) {
+                const int nb = min(kSBatch, num_trees - t0);
+                int spins = 0;
+                for (;;) {
+                    const bool ok = lane >= nb || lds_flag_load(&ring_ready[(t0 + lane) % kSRing]) == (uint32_t)(t0 + lane + 1);
+                    if (__ballot(ok) == ~0ull) break;
+                    if (++spins > kRingSpinLimit) {
+                        dead = true;
+                        break;
+                    }
+                    __builtin_amdgcn_s_sleep(2);
+                }
+                if (dead) break;
+                TAHOE_LDS_ACQUIRE();  // the values are read after the flags
+                for (int j = 0; j < nb; ++j) {
+                    sum += ring_vals[((t0 + j) % kSRing) * kTileRows + lane];  // tree order
+                    if (t0 + j + 1 == send) {
+                        if (row_ok) sums[(row * (size_t)S + si) * (size_t)(MC ? num_classes : 1) + cls] = sum;
+                        ++si;
+                        send = si < S ? cbeg + stages[si] : -1;
+                    }
+                    if (MC && t0 + j + 1 == cend) {
+                        sum = 0.0f;
+                        ++cls;
+                        cend += class_trees;
+                        si = 0;
+                        cbeg = t0 + j + 1;
+                        send = cbeg + stages[0];
+                    }
+                }
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                if (lane == 0) lds_flag_store(consumed, (uint32_t)(t0 + nb));
+            }
+            if (dead && lane == 0) atomicOr(error_flag, 1);
+            return;
+        }
         float sum = (!MC && sums_in && row_ok) ? sums_in[row] : 0.0f;
         const int class_trees = MC ? num_trees / num_classes : 0;
         int cls = 0, cend = class_trees;  // MC: the class being summed, and the tree after its last
@@ -718,12 +783,12 @@ tahoe_status sparse_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, con
                     hipLaunchKernelGGL((sparse_top_kernel<NW, false, decltype(mc)::value, decltype(cat)::value, true>), dim3(grid),
                                        dim3(NW * 64), lds, stream, sp->cnodes, sp->ctrees, sp->corig, data, sums, leaf_out, sums_in, rows,
                                        f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, f->error_flag, nc, sp->cat_pool,
-                                       sp->cat_words, *csr);
+                                       sp->cat_words, *csr, nullptr, 0);
                 else
                     hipLaunchKernelGGL((sparse_top_kernel<NW, decltype(wl)::value, decltype(mc)::value, decltype(cat)::value>), dim3(grid),
                                        dim3(NW * 64), lds, stream, sp->cnodes, sp->ctrees, sp->corig, data, sums, leaf_out, sums_in, rows,
                                        f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, f->error_flag, nc, sp->cat_pool,
-                                       sp->cat_words, CsrView{});
+                                       sp->cat_words, CsrView{}, nullptr, 0);
             };
             auto with_cat = [&](auto nw_c) {
                 if (sp->cat_pool) launch(nw_c, std::true_type{});
@@ -744,13 +809,13 @@ tahoe_status sparse_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, con
                 if (csr) {  // (predictions only: no leaf-index form)
                     hipLaunchKernelGGL((sparse_kernel<true, false, decltype(mc)::value, decltype(cat)::value, true>), dim3(grid),
                                        dim3(kBlock), lds, stream, sp->nodes, sp->trees, data, sums, leaf_out, sums_in, rows,
-                                       f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, nc, sp->cat_pool, sp->cat_words, *csr);
+                                       f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, nc, sp->cat_pool, sp->cat_words, *csr, nullptr, 0);
                     return;
                 }
             }
             hipLaunchKernelGGL((sparse_kernel<decltype(tile_c)::value, decltype(wl)::value, decltype(mc)::value, decltype(cat)::value>),
                                dim3(grid), dim3(kBlock), lds, stream, sp->nodes, sp->trees, data, sums, leaf_out, sums_in, rows,
-                               f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, nc, sp->cat_pool, sp->cat_words, CsrView{});
+                               f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, nc, sp->cat_pool, sp->cat_words, CsrView{}, nullptr, 0);
         };
         auto with_cat = [&](auto tile_c) {
             if (sp->cat_pool) launch(tile_c, std::true_type{});
@@ -761,6 +826,74 @@ tahoe_status sparse_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, con
     });
     TAHOE_HIP_TRY(hipGetLastError());
     return TAHOE_OK;
+}
+
+// fn(mc, cat) with std::true_type / std::false_type for the handle's kind
+template <class Fn>
+static void with_mc_cat(const tahoe_forest *f, Fn &&fn)
+{
+    const bool mc = f->num_classes > 1, cat = f->sp->cat_pool != nullptr;
+    if (mc) {
+        if (cat) fn(std::true_type{}, std::true_type{});
+        else fn(std::true_type{}, std::false_type{});
+    } else if (cat) {
+        fn(std::false_type{}, std::true_type{});
+    } else {
+        fn(std::false_type{}, std::false_type{});
+    }
+}
+
+tahoe_status sparse_launch_staged(tahoe_forest *f, float *out, const float *data, size_t rows, hipStream_t stream, int strategy)
+{
+    const tahoe_sstate *sp = f->sp;
+    const unsigned grid = (unsigned)((rows + kTileRows - 1) / kTileRows);
+    const int vec4_ok = (f->p.num_cols % 4 == 0) && ((reinterpret_cast<uintptr_t>(data) & 15u) == 0);
+    const int nc = f->num_classes, S = (int)f->num_stages;
+    if (strategy == TAHOE_STRATEGY_TILEBLOCK) {
+        const int nw = sparse_top_waves(f);
+        if (nw == 0) return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_staged: TILEBLOCK is not available on this sparse handle");
+        const int lds = (int)sparse_top_lds(f, nw);
+        with_mc_cat(f, [&](auto mc, auto cat) {
+            auto launch = [&](auto nw_c) {
+                constexpr int NW = decltype(nw_c)::value;
+                hipLaunchKernelGGL((sparse_top_kernel<NW, false, decltype(mc)::value, decltype(cat)::value, false, true>), dim3(grid),
+                                   dim3(NW * 64), lds, stream, sp->cnodes, sp->ctrees, sp->corig, data, out, nullptr, nullptr, rows,
+                                   f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, f->error_flag, nc, sp->cat_pool, sp->cat_words,
+                                   CsrView{}, f->stages_dev, S);
+            };
+            if (nw == 16) launch(std::integral_constant<int, 16>{});
+            else launch(std::integral_constant<int, 8>{});
+        });
+    } else {
+        const bool tile = strategy == TAHOE_STRATEGY_ROWTILE;
+        if (tile && !sparse_tile_fits(f)) return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_staged: no 64-row tile fits LDS");
+        const int lds = (int)sparse_lds(f, tile);
+        with_mc_cat(f, [&](auto mc, auto cat) {
+            auto launch = [&](auto tile_c) {
+                hipLaunchKernelGGL((sparse_kernel<decltype(tile_c)::value, false, decltype(mc)::value, decltype(cat)::value, false, true>),
+                                   dim3(grid), dim3(kBlock), lds, stream, sp->nodes, sp->trees, data, out, nullptr, nullptr, rows,
+                                   f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, nc, sp->cat_pool, sp->cat_words, CsrView{},
+                                   f->stages_dev, S);
+            };
+            if (tile) launch(std::true_type{});
+            else launch(std::false_type{});
+        });
+    }
+    TAHOE_HIP_TRY(hipGetLastError());
+    return TAHOE_OK;
+}
+
+tahoe_status sparse_allow_staged_lds(const tahoe_forest *f)
+{
+    hipError_t e = hipSuccess;
+    with_mc_cat(f, [&](auto mc, auto cat) {
+        constexpr bool M = decltype(mc)::value, K = decltype(cat)::value;
+        if (sparse_tile_fits(f)) e = allow_max_lds(reinterpret_cast<const void *>(&sparse_kernel<true, false, M, K, false, true>), f->lds_limit);
+        if (e == hipSuccess && sparse_top_waves(f) > 0 &&
+            (e = allow_max_lds(reinterpret_cast<const void *>(&sparse_top_kernel<16, false, M, K, false, true>), f->lds_limit)) == hipSuccess)
+            e = allow_max_lds(reinterpret_cast<const void *>(&sparse_top_kernel<8, false, M, K, false, true>), f->lds_limit);
+    });
+    return hip_status(e, "hipFuncSetAttribute(sparse, staged)");
 }
 
 void sparse_destroy(tahoe_forest *f)
