@@ -78,7 +78,8 @@ def _walk(phi, S, N, c, arrays, left, x, missing):
         f = fid[i]
         go = _go_right(x[r, f], val[i], def_left[i], missing)
         child = left[i] + go.astype(np.int64)
-        phi[r, c, f] += d[child]  # one float32 add per row: rows are distinct
+        with np.errstate(over="ignore", invalid="ignore"):  # leaves near FLT_MAX: +-inf and NaN sums are the IEEE results
+            phi[r, c, f] += d[child]  # one float32 add per row: rows are distinct
         if S is not None:
             S[r, c] += np.abs(d[child].astype(np.float64))
             N[r, c] += 1

@@ -1,6 +1,7 @@
-"""Adversarial inputs for the three SHAP entry points, and the checks the GPU file applies to them: test infrastructure, not
-product.  Shared by tests/test_shap_edges_capi.py (the float64 references against their subset brute force) and
-tests/test_shap_edges_gpu.py (the kernels against the same references).
+"""Adversarial inputs for the three SHAP entry points and the Saabas one, and the checks the GPU files apply to them: test
+infrastructure, not product.  Shared by tests/test_shap_edges_capi.py (the float64 references against their subset brute force,
+the Saabas reference against its float64 restatement), tests/test_shap_edges_gpu.py (the exact kernels against the same
+references) and tests/test_approx_edges_gpu.py (approx_kernel against tests/approx_contribs_ref.py, bit for bit).
 
 Pools: covers (zero, spanning 1e-30 .. 1e30, ratios within 1e-8 of 1, float32 subnormals, a float32 sum that overflows, ratios
 down to 1e-300 for the float64 references), thresholds and data (+-0, +-inf, NaN, subnormals, float32 neighbours of the
@@ -10,6 +11,7 @@ from __future__ import annotations
 
 import numpy as np
 
+import approx_contribs_ref
 import contribs_ref
 import interactions_ref
 import interventional_ref as ivr
@@ -232,6 +234,21 @@ def interventional_shape(F, lds=160 * 1024):
     while R > 1 and R * per_row + table > 80 * 1024:
         R //= 2
     return R, R * per_row + table <= lds
+
+
+def approx_form(F, lds_bytes, forced=0):
+    """(LDS slab form?, waves per workgroup) of approx_kernel by the rule of finish_build (approx.hip): a wave's slab is 64 rows
+    of stride (F + 1) | 1 floats; the slab while two wave slabs fit lds_bytes, then as many waves (1 .. 4) as fit 64 KiB; in
+    place, 4 waves.  forced = TAHOE_APPROX_FORM: 1 takes the slab while one wave slab fits, 2 never.  The library does not
+    report the form it picks, so tests assert this restatement against an expected table, not the library itself: a later
+    change to the rule in finish_build must update it, or the cases drift off the boundaries without failing."""
+    wave_bytes = 64 * ((F + 1) | 1) * 4
+    slab = 2 * wave_bytes <= lds_bytes
+    if forced == 1:
+        slab = wave_bytes <= lds_bytes
+    if forced == 2:
+        slab = False
+    return slab, (min(max(65536 // wave_bytes, 1), 4) if slab else 4)
 
 
 def max_abs_leaf(nodes, T, num_classes=1, avg=False):
@@ -522,3 +539,185 @@ def tiny_stump_case(zero_on_path):
         T, D, F = 1, 2, 2
         x = np.array([[0.0, 0.0], [1.0, 0.0], [1.0, 1.0], [0.0, 1.0], [0.5, 0.5]], F32)
     return nodes, T, D, F, x
+
+
+# ---- Saabas contributions (tahoe_forest_predict_contribs_approx): cases, host-side facts, GPU checks ----
+UNSUPPORTED = 7
+SPARSE_STRATEGIES = (0, 1, 2, 3, 5)  # the strategies a sparse handle serves
+SPARSE_QRING_MAX_COLS = 256  # ... QRING (5) up to this width only (include/tahoe_amd.h, "On a sparse handle"); wider, it is refused
+FLT_MAX = float(np.finfo(F32).max)
+FLT_MIN = float(np.finfo(F32).tiny)
+LEAF_POOLS = {"subnormal": (1e-45, 1e-40, 1.2e-38, 1e-30), "large": (1e30, 1e37), "overflow": (3e38, FLT_MAX)}
+# (T, D, F) per pool; "large": 2 T D max |leaf| = 3.2e38 < FLT_MAX, so no delta and no partial sum of a row can overflow
+LEAF_SHAPES = {"subnormal": (6, 4, 5), "large": (4, 4, 5), "overflow": (6, 3, 12)}
+
+
+def leaf_case(kind, seed=0):
+    """-> (nodes, T, D, F, x, missing): benign covers, leaves drawn from +-LEAF_POOLS[kind], 120 rows of the data pool."""
+    rng = np.random.default_rng(7000 + 10 * seed + len(kind))
+    mags = np.array(LEAF_POOLS[kind], F32)
+    T, D, F = LEAF_SHAPES[kind]
+    missing = -999.0
+    nodes = random_forest(rng, T, D, F, missing, covers="benign", leaf_prob=0.1, leaves=np.concatenate([mags, -mags]))
+    return nodes, T, D, F, random_data(rng, 120, F, missing), missing
+
+
+def reachable(tree):
+    """Heap indices of the nodes of one tree that a walk can reach, parents before children."""
+    leaf = (tree["bits"].view(np.uint32) >> 31) == 1
+    out, level = [], [0]
+    while level:
+        out += level
+        level = [c for i in level if not leaf[i] for c in (2 * i + 1, 2 * i + 2)]
+    return np.array(out, np.int64)
+
+
+def reachable_leaves(nodes, T):
+    """float32 values of every reachable leaf, root leaves included."""
+    per = nodes.size // max(T, 1)
+    vals = [np.zeros(0, F32)]
+    for tree in (nodes.reshape(T, per) if T else []):
+        r = reachable(tree)
+        vals.append(tree["val"][r][(tree["bits"].view(np.uint32)[r] >> 31) == 1])
+    return np.concatenate(vals)
+
+
+def approx_walks(nodes, T, D, x, missing):
+    """Per tree (E, path): E[per] the float64 node means of approx_contribs_ref (garbage at unreachable nodes) and
+    path[rows, D + 1] the heap indices a row visits, root first, -1 after its leaf."""
+    per = (1 << (D + 1)) - 1
+    left = 2 * np.arange(per, dtype=np.int64) + 1
+    x = np.ascontiguousarray(x, F32)
+    out = []
+    for tree in nodes.reshape(T, per):
+        fid, dl, leaf, val, w = contribs_ref._decode(tree)
+        E = approx_contribs_ref._means(val.astype(F32), leaf, left, w, True)
+        path = np.full((x.shape[0], D + 1), -1, np.int64)
+        path[:, 0] = 0
+        for l in range(D):
+            i = path[:, l]
+            r = np.nonzero((i >= 0) & ~leaf[np.maximum(i, 0)])[0]
+            n = i[r]
+            path[r, l + 1] = left[n] + approx_contribs_ref._go_right(x[r, fid[n]], val[n], dl[n], missing)
+        out.append((E, path))
+    return out
+
+
+def zero_cover_visits(nodes, T, D, x, missing):
+    """(taken, avoided): over every visit of a (row, tree) walk to an internal node one of whose children has cover 0, how many
+    go to that child and how many to its sibling."""
+    per = (1 << (D + 1)) - 1
+    taken = avoided = 0
+    for tree, (_, path) in zip(nodes.reshape(T, per), approx_walks(nodes, T, D, x, missing)):
+        w = tree["weight"]
+        child = path[:, 1:]
+        on = child >= 0
+        c = np.maximum(child, 0)
+        sibling = np.where(c % 2 == 1, c + 1, c - 1)
+        taken += int((on & (w[c] == 0)).sum())
+        avoided += int((on & (w[c] != 0) & (w[sibling] == 0)).sum())
+    return taken, avoided
+
+
+GUARD_ROWS = 256  # the most rows a workgroup of approx_kernel covers (4 waves of 64)
+GUARD_VALUE = F32(-12345.678)
+
+
+def gpu_approx(env, forest, x):
+    """predict_contribs_approx into the first rows of a buffer GUARD_ROWS rows longer, filled with GUARD_VALUE: the rows past
+    the batch must come back untouched (a write-out that counts rows by another wave's tile would land there)."""
+    torch = env[1]
+    n, width = x.shape[0], forest.num_classes * (forest.num_cols + 1)
+    shape = (n + GUARD_ROWS,) + ((forest.num_classes,) if forest.num_classes > 1 else ()) + (forest.num_cols + 1,)
+    big = dev(torch, np.full(shape, GUARD_VALUE, F32))
+    forest.predict_contribs_approx(dev(torch, x), out=big[:n])
+    torch.cuda.synchronize()
+    a = big.cpu().numpy().reshape(n + GUARD_ROWS, width)
+    touched = np.argwhere(bits(a[n:]) != bits(GUARD_VALUE))
+    assert touched.size == 0, f"{len(touched)} values written past the batch's {n} rows, first at row {n + touched[0][0]}"
+    return a[:n].reshape(n, forest.num_classes, forest.num_cols + 1)
+
+
+def assert_same_bits(got, want, label):
+    """uint32 equality; a NaN need only be a NaN at the same place (host and device produce different default NaNs, so sign
+    and payload are not compared)."""
+    got, want = np.ascontiguousarray(got, F32), np.ascontiguousarray(want, F32)
+    assert got.shape == want.shape, f"{label}: shapes {got.shape} and {want.shape}"
+    bad = (bits(got) != bits(want)) & ~(np.isnan(got) & np.isnan(want))
+    if bad.any():
+        i = tuple(np.argwhere(bad)[0])
+        raise AssertionError(f"{label}: {int(bad.sum())} outputs differ, first at {i}: {got[i]!r} vs {want[i]!r}")
+
+
+def approx_handles(env, nodes, T, D, F, missing, num_classes=1, output=0, bias=0.0, sparse=True):
+    """The handles check_approx_batch compares: 'dense' (approx_contribs=True), 'relayout' (the same with
+    TAHOE_CREATE_PROB_RELAYOUT: exchange bits wherever a left child is the lighter one; None without trees), 'exact'
+    (contribs=True; None where create answers TAHOE_ERR_UNSUPPORTED), 'sparse' (the tahoe_dense_to_sparse_ex conversion with
+    approx_contribs=True; None without trees or with sparse=False)."""
+    ta, _ = env
+    kw = dict(missing=missing, output=output, global_bias=bias, num_classes=num_classes)
+    h = {"dense": ta.Forest(nodes, T, D, F, approx_contribs=True, **kw), "relayout": None, "exact": None, "sparse": None}
+    if T > 0:
+        h["relayout"] = ta.Forest(nodes, T, D, F, approx_contribs=True, relayout=True, **kw)
+    try:
+        h["exact"] = ta.Forest(nodes, T, D, F, contribs=True, **kw)
+    except ta.TahoeError as e:
+        if e.status != UNSUPPORTED:
+            raise
+    if sparse and T > 0:
+        sn, tr, cv = ta.capi.dense_to_sparse(nodes, T, D, covers=True)
+        h["sparse"] = ta.capi.SparseForest(sn, tr, F, covers=cv, approx_contribs=True, **kw)
+    return h
+
+
+def check_approx_batch(env, h, nodes, T, D, F, x, missing, num_classes=1, output=0, bias=0.0, label=""):
+    """One batch on the handles of approx_handles: the checks of check_approx.  -> the dense handle's output."""
+    from test_approx_contribs_gpu import check_additivity
+
+    ta, torch = env
+    f = h["dense"]
+    got = gpu_approx(env, f, x)
+    want, S, N = approx_contribs_ref.dense(nodes, T, D, F, x, missing, num_classes=num_classes,
+                                           avg=(output & ta.OUT_AVG) != 0, global_bias=bias, scale=True)
+    assert_same_bits(got, want, f"{label}: against the reference")
+    if h["exact"] is not None:
+        assert_same_bits(got[..., -1], gpu_phi(env, h["exact"], x)[..., -1], f"{label}: bias column against predict_contribs")
+    if T > 0:
+        # the bound counts roundings, so it holds on rows without an overflow: a finite reference, and a float32 margin of
+        # the library that stayed finite (leaves near FLT_MAX can overflow predict_raw's sum where no delta overflows)
+        raw = f.predict_raw(dev(torch, x)).cpu().numpy().reshape(x.shape[0], num_classes)
+        ok = np.isfinite(want).all(axis=(1, 2)) & np.isfinite(raw).all(axis=1)
+        if ok.any():
+            check_additivity(env, f, np.ascontiguousarray(x[ok]), got[ok], S[ok], N[ok], T // num_classes,
+                             reachable_leaves(nodes, T), label)
+    single_rows_match(lambda g, xx: gpu_approx(env, g, xx), f, x, got)
+    if h["relayout"] is not None:
+        assert_same_bits(gpu_approx(env, h["relayout"], x), got, f"{label}: re-laid-out handle")
+    if h["sparse"] is not None:
+        for s in SPARSE_STRATEGIES:
+            if s == ta.STRATEGY_QRING and F > SPARSE_QRING_MAX_COLS:
+                try:
+                    h["sparse"].set_strategy(s)
+                except ta.TahoeError as e:
+                    assert e.status == UNSUPPORTED, f"{label}: {e}"
+                    continue
+                raise AssertionError(f"{label}: QRING accepted on a sparse handle of {F} columns")
+            h["sparse"].set_strategy(s)  # every other refusal fails the test
+            assert_same_bits(gpu_approx(env, h["sparse"], x), got, f"{label}: converted sparse handle, strategy {s}")
+    return got
+
+
+def check_approx(env, nodes, T, D, F, x, missing, num_classes=1, output=0, bias=0.0, label="", sparse=True):
+    """predict_contribs_approx on a dense handle against approx_contribs_ref.dense, bit for bit (assert_same_bits); the bias
+    column bit for bit predict_contribs' of a contribs=True handle; additivity against predict_raw within the bound of
+    tests/test_approx_contribs_gpu.py, (2 N + Tc + 8) 2^-24 (S + |bias| + sum |leaf|), on the rows without an overflow;
+    single-row batches bitwise equal to the full batch; the handle created with TAHOE_CREATE_PROB_RELAYOUT bit for bit the
+    plain one; with sparse=True the tahoe_dense_to_sparse_ex handle under every strategy a sparse handle serves, bit for bit
+    the dense handle; every call writes nothing past its rows (gpu_approx).  -> (the dense handle, its output)."""
+    h = approx_handles(env, nodes, T, D, F, missing, num_classes, output, bias, sparse)
+    assert h["exact"] is not None, f"{label}: the contribs=True handle of the bias check was refused"
+    got = check_approx_batch(env, h, nodes, T, D, F, x, missing, num_classes, output, bias, label)
+    for k in ("relayout", "exact", "sparse"):
+        if h[k] is not None:
+            h[k].close()
+    return h["dense"], got

@@ -2,7 +2,12 @@
 interactions_ref.poly, interventional_ref.paths), checked against their subset brute force on the adversarial pools of
 tests/shap_edges.py: extreme covers (zero, 1e-30 .. 1e30, within 1e-8 of 1, float32 subnormals, a float32 sum that overflows,
 ratios down to 1e-300), branch-rule edges (+-0, +-inf, NaN and subnormal thresholds and data, the missing band, contradictory
-bounds on a repeated feature) and long paths.  Bar: within 1e-12 of sum |phi| per row (bias column included).  No GPU."""
+bounds on a repeated feature) and long paths.  Bar: within 1e-12 of sum |phi| per row (bias column included).
+
+The Saabas reference (approx_contribs_ref.dense, which tests/test_approx_edges_gpu.py compares approx_kernel with bit for bit) on
+the same pools: against its float64 restatement direct64 within (N + 1) 2^-24 S per row and class (N float32 adds of deltas
+rounded once, S the sum of |delta|), the float64 deltas of every (row, tree) path telescoping to leaf - E(root), and the
+preconditions that keep the GPU cases from passing vacuously.  No GPU."""
 import os
 import sys
 
@@ -10,6 +15,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import approx_contribs_ref as aref  # noqa: E402
 import contribs_ref  # noqa: E402
 import interactions_ref  # noqa: E402
 import interventional_ref as ivr  # noqa: E402
@@ -125,3 +131,76 @@ def test_interactions_absolute_magnitude(lib, D):
     assert np.all(Aabs >= A * (1 - 1e-12))
     if D == 12:
         assert np.max(Aabs[A > 0] / A[A > 0]) > 10
+
+
+# ---- the Saabas reference on the same pools ----
+U = 2.0 ** -24
+APPROX_CASES = ([(f"covers:{m}", 10 * s + len(m)) for m in se.COVER_MODES for s in range(2)]
+                + [(f"branch:{m}", 100 + s) for m in se.MISSINGS for s in range(2)]
+                + [(f"contradictory:{m}", 7) for m in se.MISSINGS] + [("sweep", 1000 + s) for s in range(6)])
+
+
+def stored_deltas(nodes, T, D):
+    """[(E(n), float32 d(left), float32 d(right))] over the reachable internal nodes of every tree."""
+    per = (1 << (D + 1)) - 1
+    left = 2 * np.arange(per, dtype=np.int64) + 1
+    out = []
+    for tree in nodes.reshape(T, per):
+        fid, dl, leaf, val, w = contribs_ref._decode(tree)
+        E = aref._means(val.astype(F32), leaf, left, w, True)
+        for n in se.reachable(tree):
+            if not leaf[n]:
+                out.append((E[n], F32(E[2 * n + 1] - E[n]), F32(E[2 * n + 2] - E[n])))
+    return out
+
+
+@pytest.mark.parametrize("kind, seed", APPROX_CASES)
+def test_approx_reference_telescopes(lib, kind, seed):
+    nodes, T, D, F, x, bg, m = se.edge_case(kind, seed)
+    label = f"{kind} seed {seed}"
+    phi, S, N = aref.dense(nodes, T, D, F, x, m, scale=True)
+    assert np.all(np.isfinite(phi)), f"{label}: the reference is finite on this case"
+    want = aref.direct64(nodes, T, D, F, x, m)
+    err = np.abs(phi.astype(np.float64) - want)[..., :F]
+    tol = ((N + 1) * U * S)[:, :, None]
+    assert np.all(err <= tol), f"{label}: dense vs direct64, worst {np.max(err / np.maximum(tol, 1e-300)):.3g} of the bound"
+    for t, (E, path) in enumerate(se.approx_walks(nodes, T, D, x, m)):
+        for r in range(x.shape[0]):
+            p = path[r][path[r] >= 0]
+            total = 0.0
+            for a, b in zip(p[:-1], p[1:]):
+                total += E[b] - E[a]
+            bound = D * 2.0 ** -52 * np.max(np.abs(E[p]))
+            assert abs(total - (E[p[-1]] - E[0])) <= bound, f"{label}: row {r} tree {t} does not telescope"
+
+
+@pytest.mark.parametrize("seed", range(2))
+def test_approx_zero_cover_children_taken_and_not(lib, seed):
+    nodes, T, D, F, x, bg, m = se.edge_case("covers:zero", 10 * seed + len("zero"))
+    taken, avoided = se.zero_cover_visits(nodes, T, D, x, m)
+    assert taken > 0 and avoided > 0, "at splits with a zero-cover child, rows take that child and rows take its sibling"
+
+
+@pytest.mark.parametrize("seed", range(2))
+def test_approx_near_one_cancels(lib, seed):
+    nodes, T, D, F, x, bg, m = se.edge_case("covers:near_one", 10 * seed + len("near_one"))
+    small = [d for E, a, b in stored_deltas(nodes, T, D) for d in (a, b) if 0 < abs(float(d)) < 2.0 ** -20 * abs(E)]
+    assert small, "a stored delta below 2^-20 |E(n)|: the difference of the means cancels almost completely"
+
+
+def test_approx_leaf_pools(lib):
+    """The leaf-magnitude cases of tests/test_approx_edges_gpu.py: subnormal deltas and sums that stay nonzero, large leaves
+    with a finite reference, and leaves near FLT_MAX with between 1 % and 99 % of the feature outputs non-finite."""
+    nodes, T, D, F, x, m = se.leaf_case("subnormal")
+    d = np.array([float(v) for _, a, b in stored_deltas(nodes, T, D) for v in (a, b)])
+    assert np.any((d != 0) & (np.abs(d) < se.FLT_MIN)), "subnormal stored deltas"
+    for avg in (False, True):
+        phi = aref.dense(nodes, T, D, F, x, m, avg=avg)[..., :F]
+        assert np.all(np.isfinite(phi)) and np.any((phi != 0) & (np.abs(phi) < se.FLT_MIN)), "subnormal outputs"
+    nodes, T, D, F, x, m = se.leaf_case("large")
+    assert 2 * T * D * float(np.max(np.abs(se.reachable_leaves(nodes, T)))) < se.FLT_MAX
+    assert np.all(np.isfinite(aref.dense(nodes, T, D, F, x, m)))
+    nodes, T, D, F, x, m = se.leaf_case("overflow")
+    bad = ~np.isfinite(aref.dense(nodes, T, D, F, x, m)[..., :F])
+    assert 0.01 <= bad.mean() <= 0.99, f"{bad.mean():.3f} of the feature outputs are non-finite"
+    assert np.any(np.isnan(aref.dense(nodes, T, D, F, x, m)[..., :F])), "inf - inf on some row"
