@@ -228,7 +228,9 @@ int tahoe_forest_num_classes(const tahoe_forest *f);
  * TAHOE_OK, nothing launched; NULL phi_dev / data_dev with rows > 0: TAHOE_ERR_INVALID_ARG; a handle (dense or sparse) created
  * without TAHOE_CREATE_CONTRIBS: TAHOE_ERR_UNSUPPORTED, nothing launched.  A sparse handle created with the flag
  * (tahoe_sparse_forest_create_ex, covers given per node) is served the same way: its paths are walked pre-order, left child
- * first, so a forest converted with tahoe_dense_to_sparse_ex holds the dense handle's path bins and gives its bits. */
+ * first, so a forest converted with tahoe_dense_to_sparse_ex holds the dense handle's path bins and gives its bits.  On a handle
+ * with categorical splits (tahoe_sparse_forest_create_cat with TAHOE_CREATE_CAT_CONTRIBS) the row's branch at a categorical node
+ * is that function's rule; everything else, the determinism included, is as above. */
 tahoe_status tahoe_forest_predict_contribs(tahoe_forest *f, float *phi_dev, const float *data_dev, size_t rows, void *stream);
 
 /* SHAP interaction values (XGBoost pred_interactions, SHAP's TreeExplainer.shap_interaction_values) of the game that
@@ -246,7 +248,7 @@ tahoe_status tahoe_forest_predict_contribs(tahoe_forest *f, float *phi_dev, cons
  * Asynchronous on `stream`; allocates nothing (graph-capturable).  rows == 0: TAHOE_OK, nothing launched; NULL out_dev /
  * data_dev with rows > 0, or rows * C * (F + 1)^2 * 4 overflowing size_t: TAHOE_ERR_INVALID_ARG; a handle (dense or sparse)
  * created without TAHOE_CREATE_CONTRIBS: TAHOE_ERR_UNSUPPORTED; nothing launched on any refusal.  Sparse handles created with
- * the flag are served as by tahoe_forest_predict_contribs. */
+ * the flag, those with categorical splits included, are served as by tahoe_forest_predict_contribs. */
 tahoe_status tahoe_forest_predict_interactions(tahoe_forest *f, float *out_dev, const float *data_dev, size_t rows, void *stream);
 
 /* Interventional TreeSHAP (SHAP's TreeExplainer(model, data=bg), feature_perturbation="interventional"; Lundberg et al. 2020):
@@ -279,7 +281,8 @@ tahoe_status tahoe_forest_set_background(tahoe_forest *f, const float *bg_dev, s
  * the same background.  No atomics.  Asynchronous on `stream`; allocates nothing (graph-capturable after set_background).
  * Refusals, nothing launched: a handle (dense or sparse) created without TAHOE_CREATE_CONTRIBS, or one with no background:
  * TAHOE_ERR_UNSUPPORTED (tahoe_last_error says which); then rows == 0: TAHOE_OK; NULL phi_dev / data_dev with rows > 0, or
- * rows x C x (num_cols + 1) x 4 overflowing size_t: TAHOE_ERR_INVALID_ARG. */
+ * rows x C x (num_cols + 1) x 4 overflowing size_t: TAHOE_ERR_INVALID_ARG.  On a handle with categorical splits
+ * (TAHOE_CREATE_CAT_CONTRIBS) x and the background rows take tahoe_sparse_forest_create_cat's rule at a categorical node. */
 tahoe_status tahoe_forest_predict_contribs_interventional(tahoe_forest *f, float *phi_dev, const float *data_dev, size_t rows,
                                                           void *stream);
 
@@ -308,8 +311,15 @@ tahoe_status tahoe_forest_predict_contribs_interventional(tahoe_forest *f, float
  * sub-forest; a sparse handle converted with tahoe_dense_to_sparse_ex gives the dense handle's bits.  No atomics.  Asynchronous
  * on `stream`; allocates nothing (graph-capturable).  Refusals, nothing launched, in this order: NULL handle:
  * TAHOE_ERR_INVALID_ARG; a handle created without TAHOE_CREATE_APPROX_CONTRIBS: TAHOE_ERR_UNSUPPORTED; then rows == 0: TAHOE_OK;
- * NULL phi_dev / data_dev with rows > 0, or rows x C x (num_cols + 1) x 4 overflowing size_t: TAHOE_ERR_INVALID_ARG. */
+ * NULL phi_dev / data_dev with rows > 0, or rows x C x (num_cols + 1) x 4 overflowing size_t: TAHOE_ERR_INVALID_ARG.  On a handle
+ * with categorical splits (TAHOE_CREATE_CAT_CONTRIBS) the row follows tahoe_sparse_forest_create_cat's path; the deltas are per
+ * child whatever the kind of the split. */
 tahoe_status tahoe_forest_predict_contribs_approx(tahoe_forest *f, float *phi_dev, const float *data_dev, size_t rows, void *stream);
+
+/* TreeSHAP and Saabas contributions on a handle with categorical splits.  A create flag for tahoe_sparse_forest_create_cat only
+ * (every other create: TAHOE_ERR_INVALID_ARG); it goes with TAHOE_CREATE_CONTRIBS and / or TAHOE_CREATE_APPROX_CONTRIBS and says
+ * that their tables may cross categorical splits; alone it is TAHOE_ERR_INVALID_ARG.  See tahoe_sparse_forest_create_cat. */
+#define TAHOE_CREATE_CAT_CONTRIBS 0x20u
 
 /* ---- sparse (irregular) forests: sparse_node_t Struct.h:50-54, sparse_storage Struct.h:343-354,
  * init_sparse / sparse_forest::init (BaseTahoeTest.h:766-772, Struct.h:2329-2343) ---- */
@@ -377,8 +387,23 @@ typedef struct {
  *   - the forest's structure, as tahoe_sparse_forest_create_ex checks it (TAHOE_ERR_INVALID_FOREST);
  *   - a listed node that is a leaf, or lies in no tree: TAHOE_ERR_INVALID_FOREST naming the tree and the node (relative to its
  *     root);
- *   - num_splits > 0 with TAHOE_CREATE_CONTRIBS or TAHOE_CREATE_APPROX_CONTRIBS (TreeSHAP's path elements are intervals per
- *     feature and a category set is not one), or with num_cols > 2^29: TAHOE_ERR_UNSUPPORTED.
+ *   - num_splits > 0 with TAHOE_CREATE_CONTRIBS or TAHOE_CREATE_APPROX_CONTRIBS and without TAHOE_CREATE_CAT_CONTRIBS (plain
+ *     path elements are intervals per feature and a category set is not one), or with num_cols > 2^29: TAHOE_ERR_UNSUPPORTED;
+ *   - TAHOE_CREATE_CAT_CONTRIBS with neither TAHOE_CREATE_CONTRIBS nor TAHOE_CREATE_APPROX_CONTRIBS (cats NULL or not):
+ *     TAHOE_ERR_INVALID_ARG naming the flag;
+ *   - the covers and the path lengths, as tahoe_sparse_forest_create_ex checks them for the two flags.
+ * flags: those of tahoe_sparse_forest_create_ex and TAHOE_CREATE_CAT_CONTRIBS, which this function alone accepts.  With it and
+ * splits, TAHOE_CREATE_CONTRIBS serves tahoe_forest_predict_contribs, _predict_interactions, _set_background and
+ * _predict_contribs_interventional, and TAHOE_CREATE_APPROX_CONTRIBS serves tahoe_forest_predict_contribs_approx, with the rule
+ * above at the categorical nodes.  A path's categorical edges on one feature make one path element: at split k the path going
+ * right needs member == !members_left[k], going left member == members_left[k]; the element allows category c < 32 W (W the
+ * widest of those splits, narrower ones zero-extended) iff every edge's bit of c equals what the edge needs, and it allows
+ * every other non-missing value (beyond the words, negative, >= 2^24, NaN) iff no edge needs a member.  Numeric edges on the same
+ * feature keep their interval and a value must pass both; the missing sentinel follows iff every edge's default branch is the
+ * path's.  Covers, zero fractions, the bias column, the 31-features limit, num_cols <= LDS / 20 and every determinism promise of
+ * the four calls are unchanged.  The sets live on the device beside the path bins (identical sets once), counted in
+ * tahoe_forest_info.device_bytes.  With the flag and no splits the handle is tahoe_sparse_forest_create_ex's with the remaining
+ * flags.
  * cats == NULL or num_splits == 0 gives the handle of tahoe_sparse_forest_create_ex.  A handle with splits serves DIRECT, ROWTILE
  * and TILEBLOCK (AUTO: TILEBLOCK when available, else ROWTILE, else DIRECT) with the float32 sums added in tree order, classes,
  * output bits, tahoe_forest_predict_accumulate and tahoe_forest_predict_host as tahoe_sparse_forest_create_ex describes them;

@@ -37,6 +37,7 @@ STRATEGY_AUTO, STRATEGY_DIRECT, STRATEGY_ROWTILE, STRATEGY_TILEBLOCK, STRATEGY_T
 CREATE_PROB_RELAYOUT = 0x1
 CREATE_CONTRIBS = 0x4  # per-feature contributions (tahoe_forest_predict_contribs); node weights are covers
 CREATE_APPROX_CONTRIBS = 0x10  # Saabas contributions (tahoe_forest_predict_contribs_approx); node weights are covers
+CREATE_CAT_CONTRIBS = 0x20  # tahoe_sparse_forest_create_cat: the two flags above on a handle with categorical splits
 STRATEGY_NAMES = {1: "direct", 2: "rowtile", 3: "tileblock", 4: "tilering", 5: "qring"}
 STATUS_NAMES = {
     0: "TAHOE_OK",
@@ -733,7 +734,8 @@ class SparseForest(Forest):
     node), num_classes, contribs and approx_contribs go through tahoe_sparse_forest_create_ex: tree t belongs to class
     t % num_classes, contribs=True builds the TreeSHAP path tables from the covers and approx_contribs=True the Saabas node
     deltas.  categories ({node index: category ids}) makes those nodes categorical splits, members going right unless the
-    node is in members_left (tahoe_sparse_forest_create_cat; the node's val is then ignored)."""
+    node is in members_left (tahoe_sparse_forest_create_cat; the node's val is then ignored).  categories together with
+    contribs / approx_contribs sets TAHOE_CREATE_CAT_CONTRIBS: the four explanation calls then follow the category sets."""
 
     def __init__(self, nodes: np.ndarray, trees: np.ndarray, num_cols: int, missing: float = 0.0, output: int = OUT_RAW,
                  threshold: float = 0.0, global_bias: float = 0.0, covers=None, num_classes: int = 1,
@@ -749,6 +751,8 @@ class SparseForest(Forest):
             if cv is not None and cv.size != nodes.size:
                 raise ValueError("covers.size != nodes.size")
             cats, _keep = pack_categorical(categories, members_left)
+            if flags:  # the path elements / the Saabas walk then test category sets
+                flags |= CREATE_CAT_CONTRIBS
             _check(lib.tahoe_sparse_forest_create_cat(C.byref(self._h), trees.ctypes.data if trees.size else None,
                                                       nodes.ctypes.data if nodes.size else None,
                                                       cv.ctypes.data if cv is not None else None,

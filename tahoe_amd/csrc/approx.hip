@@ -38,13 +38,20 @@ constexpr size_t kApproxSlabBudget = 64 * 1024;  // LDS per workgroup of the sla
 
 // One wave's rows of the workgroup: zero the accumulators of class c, walk class c's trees, write the rows out.  Every wave of
 // the workgroup runs the same class loop, so the barriers are uniform.
-template <bool SPARSE, bool SLAB>
+// CAT (a sparse handle with categorical splits): a node flagged kSCat takes go_right_cat on the pool entry its `val` bits name,
+// as sparse_kernel does; the deltas are per child whatever the split's kind.  The pool and its length come in the two arguments
+// that only the dense form reads (recs, depth): this kernel reads blockDim, a hidden argument that lies behind the declared ones,
+// so an appended argument would change an immediate in every existing instantiation.
+template <bool SPARSE, bool SLAB, bool CAT = false>
 __global__ __launch_bounds__(256) void approx_kernel(float *__restrict__ phi, const float *__restrict__ data, size_t rows, int F,
                                                      int C, int Tc, int depth, const uint4 *__restrict__ recs,
                                                      const tahoe_sparse_node *__restrict__ snodes, const int32_t *__restrict__ strees,
                                                      const float2 *__restrict__ dd, const float *__restrict__ bias,
                                                      const float *__restrict__ div, float missing, int stride)
 {
+    static_assert(SPARSE || !CAT, "categorical splits exist on sparse handles only");
+    const uint32_t *__restrict__ cat_pool = reinterpret_cast<const uint32_t *>(recs);  // CAT only
+    const uint32_t cat_words = (uint32_t)depth;
     extern __shared__ __attribute__((aligned(16))) float slab[];
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -55,7 +62,7 @@ __global__ __launch_bounds__(256) void approx_kernel(float *__restrict__ phi, co
     const size_t F1 = (size_t)F + 1, out_row = (size_t)C * F1;
     const float *x = data + (row_ok ? row : 0) * (size_t)F;
     float *wslab = SLAB ? slab + (size_t)wave * 64 * stride : nullptr;
-    const size_t n_inner = ((size_t)1 << depth) - 1;
+    const size_t n_inner = ((size_t)1 << (CAT ? 0 : depth)) - 1;  // (CAT: depth carries the pool length)
     for (int c = 0; c < C; ++c) {
         // ---- zero the accumulators ----
         if (SLAB) {
@@ -78,8 +85,10 @@ __global__ __launch_bounds__(256) void approx_kernel(float *__restrict__ phi, co
                         const tahoe_sparse_node n = tn[i];
                         if (n.bits < 0) break;  // a leaf
                         const float2 d = td[i];
-                        const int fid = n.bits & 0x3fffffff;
-                        const uint32_t r = go_right(x[fid], n.val, ((uint32_t)n.bits >> 30) & 1u, missing);
+                        const int fid = n.bits & (CAT ? kSCatFidMask : 0x3fffffff);
+                        const uint32_t r = (CAT && (n.bits & kSCat))
+                                               ? go_right_cat(x[fid], cat_pool, __float_as_uint(n.val), cat_words, ((uint32_t)n.bits >> 30) & 1u, missing)
+                                               : go_right(x[fid], n.val, ((uint32_t)n.bits >> 30) & 1u, missing);
                         acc[fid] += r ? d.y : d.x;
                         i = n.left_idx + (int32_t)r;
                     }
@@ -127,8 +136,9 @@ static tahoe_status finish_build(tahoe_forest *f, tahoe_astate *ap, const std::v
     hipError_t e;
     if ((e = upload(&ap->bias, h_bias, &f->device_bytes)) != hipSuccess || (e = upload(&ap->div, h_div, &f->device_bytes)) != hipSuccess)
         return fail(TAHOE_ERR_HIP, "approx_build: upload failed: %s", hipGetErrorString(e));
-    const void *k = f->sp ? reinterpret_cast<const void *>(&approx_kernel<true, true>)
-                          : reinterpret_cast<const void *>(&approx_kernel<false, true>);
+    const void *k = sparse_has_cats(f) ? reinterpret_cast<const void *>(&approx_kernel<true, true, true>)
+                    : f->sp            ? reinterpret_cast<const void *>(&approx_kernel<true, true>)
+                                       : reinterpret_cast<const void *>(&approx_kernel<false, true>);
     if (ap->slab && (e = allow_max_lds(k, f->lds_limit)) != hipSuccess)
         return fail(TAHOE_ERR_HIP, "hipFuncSetAttribute(approx) failed: %s", hipGetErrorString(e));
     return TAHOE_OK;
@@ -283,8 +293,17 @@ extern "C" tahoe_status tahoe_forest_predict_contribs_approx(tahoe_forest *f, fl
     const int F = f->p.num_cols, Cn = f->num_classes, Tc = f->class_trees;
     const tahoe_sparse_node *sn = nullptr;
     const int32_t *st = nullptr;
+    const uint32_t *cat_pool = nullptr;
+    uint32_t cat_words = 0;
     if (f->sp) sparse_device_views(f, &sn, &st);
-    if (f->sp && ap->slab)
+    if (f->sp) sparse_cat_view(f, &cat_pool, &cat_words);
+    if (cat_pool && ap->slab)
+        hipLaunchKernelGGL((approx_kernel<true, true, true>), grid, block, ap->lds_bytes, s, phi_dev, data_dev, rows, F, Cn, Tc,
+                           (int)cat_words, reinterpret_cast<const uint4 *>(cat_pool), sn, st, ap->dd, ap->bias, ap->div, f->p.missing, ap->stride);
+    else if (cat_pool)
+        hipLaunchKernelGGL((approx_kernel<true, false, true>), grid, block, 0, s, phi_dev, data_dev, rows, F, Cn, Tc, (int)cat_words,
+                           reinterpret_cast<const uint4 *>(cat_pool), sn, st, ap->dd, ap->bias, ap->div, f->p.missing, ap->stride);
+    else if (f->sp && ap->slab)
         hipLaunchKernelGGL((approx_kernel<true, true>), grid, block, ap->lds_bytes, s, phi_dev, data_dev, rows, F, Cn, Tc, 0, nullptr,
                            sn, st, ap->dd, ap->bias, ap->div, f->p.missing, ap->stride);
     else if (f->sp)

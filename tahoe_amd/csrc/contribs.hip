@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <map>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -35,11 +36,14 @@ __device__ __forceinline__ float from_left_lane(float v)
 // same order whatever its batch, tile or position: results are bitwise reproducible.
 // SPARE = false: phi[rows][C][F + 1] (contribs_kernel).  SPARE = true: the same values into row F of each (row, class) matrix of
 // out[rows][C][F + 1][F + 1] (tahoe_forest_predict_interactions, contribs_spare_kernel).
-template <bool SPARE>
+// SETS (a handle whose path elements carry category sets): the one-fraction is follows_set() on elem_set / set_pool.
+template <bool SPARE, bool SETS>
 __device__ __forceinline__ void contribs_tile(float *__restrict__ phi, const float *__restrict__ data, size_t rows, int F, int C,
                                               int R, const uint4 *__restrict__ elems, const float *__restrict__ one_minus_z,
                                               const uint32_t *__restrict__ bin_info, const int *__restrict__ class_bins,
-                                              const float *__restrict__ bias, const float *__restrict__ class_div, float missing)
+                                              const float *__restrict__ bias, const float *__restrict__ class_div, float missing,
+                                              const uint32_t *__restrict__ elem_set, const uint32_t *__restrict__ set_pool,
+                                              uint32_t set_words)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     if (SPARE) phi += (size_t)F * (F + 1);
@@ -73,8 +77,16 @@ __device__ __forceinline__ void contribs_tile(float *__restrict__ phi, const flo
             const float leaf = lane_read(lower, gs);
             const float zdiv = z / (float)(ud + 1);
             const float udp1 = (float)(ud + 1);
+            ElemSet es{};
+            bool gather = false;
+            if constexpr (SETS) {
+                es = elem_set_load(elem_set, set_pool, set_words, (size_t)b * 64 + lane);
+                gather = elem_sets_gather(es);
+            }
             for (int r = 0; r < nr; ++r) {
-                const bool o = follows(tile[r * F + fid], lower, upper, missing_ok, nan_ok, missing);
+                bool o;
+                if constexpr (SETS) o = follows_set(tile[r * F + fid], lower, upper, missing_ok, nan_ok, missing, es, set_pool, set_words, gather);
+                else o = follows(tile[r * F + fid], lower, upper, missing_ok, nan_ok, missing);
                 const uint32_t zo = e.z | (o ? 0x80000000u : 0u);
                 // extend: after step d, lanes of rank <= d hold the permutation weights of the first d + 1 elements
                 float pw = rank == 0 ? 1.0f : 0.0f;
@@ -119,14 +131,17 @@ __device__ __forceinline__ void contribs_tile(float *__restrict__ phi, const flo
     }
 }
 
+template <bool SETS = false>
 __global__ __launch_bounds__(256) void contribs_kernel(float *__restrict__ phi, const float *__restrict__ data, size_t rows, int F,
                                                        int C, int R, const uint4 *__restrict__ elems,
                                                        const float *__restrict__ one_minus_z,
                                                        const uint32_t *__restrict__ bin_info, const int *__restrict__ class_bins,
                                                        const float *__restrict__ bias, const float *__restrict__ class_div,
-                                                       float missing)
+                                                       float missing, const uint32_t *__restrict__ elem_set,
+                                                       const uint32_t *__restrict__ set_pool, uint32_t set_words)
 {
-    contribs_tile<false>(phi, data, rows, F, C, R, elems, one_minus_z, bin_info, class_bins, bias, class_div, missing);
+    contribs_tile<false, SETS>(phi, data, rows, F, C, R, elems, one_minus_z, bin_info, class_bins, bias, class_div, missing, elem_set,
+                               set_pool, set_words);
 }
 
 // ---- SHAP interaction values (tahoe_forest_predict_interactions) ----
@@ -148,25 +163,30 @@ __global__ __launch_bounds__(256) void contribs_kernel(float *__restrict__ phi, 
 constexpr int kInterSlabMaxBytes = 80 * 1024;
 constexpr int kInterMaxRows = 32;  // rows of a tile: one bit each in the per-lane one-fraction mask
 
+template <bool SETS = false>
 __global__ __launch_bounds__(256) void contribs_spare_kernel(float *__restrict__ out, const float *__restrict__ data, size_t rows,
                                                              int F, int C, int R, const uint4 *__restrict__ elems,
                                                              const float *__restrict__ one_minus_z,
                                                              const uint32_t *__restrict__ bin_info,
                                                              const int *__restrict__ class_bins, const float *__restrict__ bias,
-                                                             const float *__restrict__ class_div, float missing)
+                                                             const float *__restrict__ class_div, float missing,
+                                                             const uint32_t *__restrict__ elem_set,
+                                                             const uint32_t *__restrict__ set_pool, uint32_t set_words)
 {
-    contribs_tile<true>(out, data, rows, F, C, R, elems, one_minus_z, bin_info, class_bins, bias, class_div, missing);
+    contribs_tile<true, SETS>(out, data, rows, F, C, R, elems, one_minus_z, bin_info, class_bins, bias, class_div, missing, elem_set,
+                              set_pool, set_words);
 }
 
 __device__ __forceinline__ void vm_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // The off-diagonal terms of bins b_first, b_first + b_step, ... < b_end for the nr rows of `tile` (row r at tile + r F), added
 // into acc + r acc_row + a ld + b for the pair (a, b).
-template <bool SLABS>
+template <bool SLABS, bool SETS>
 __device__ __forceinline__ void interaction_bins(float *acc, size_t acc_row, int ld, const float *tile, int nr, int F, int b_first,
                                                  int b_end, int b_step, const uint4 *__restrict__ elems,
                                                  const float *__restrict__ one_minus_z, const uint32_t *__restrict__ bin_info,
-                                                 float missing)
+                                                 float missing, const uint32_t *__restrict__ elem_set,
+                                                 const uint32_t *__restrict__ set_pool, uint32_t set_words)
 {
     const int lane = threadIdx.x & 63;
     if (nr == 0) return;  // a wave past the last row (in place)
@@ -182,7 +202,14 @@ __device__ __forceinline__ void interaction_bins(float *acc, size_t acc_row, int
         const float leaf = lane_read(lower, gs);
         // one-fractions of this lane's element, bit r for row r
         uint32_t omask = 0;
-        for (int r = 0; r < nr; ++r) omask |= (follows(tile[r * F + fid], lower, upper, missing_ok, nan_ok, missing) ? 1u : 0u) << r;
+        if constexpr (SETS) {
+            const ElemSet es = elem_set_load(elem_set, set_pool, set_words, (size_t)b * 64 + lane);
+            const bool gather = elem_sets_gather(es);
+            for (int r = 0; r < nr; ++r)
+                omask |= (follows_set(tile[r * F + fid], lower, upper, missing_ok, nan_ok, missing, es, set_pool, set_words, gather) ? 1u : 0u) << r;
+        } else {
+            for (int r = 0; r < nr; ++r) omask |= (follows(tile[r * F + fid], lower, upper, missing_ok, nan_ok, missing) ? 1u : 0u) << r;
+        }
         // on the path without element k, element j (rank > k) has unique depth ud - 1
         const int udk = ud - 1;
         const float zdiv = z / (float)max(ud, 1);
@@ -250,13 +277,15 @@ __device__ __forceinline__ void interaction_bins(float *acc, size_t acc_row, int
     }
 }
 
-template <bool SLABS>
+template <bool SLABS, bool SETS = false>
 __global__ __launch_bounds__(256) void interactions_kernel(float *out, const float *__restrict__ data, size_t rows, int F, int C,
                                                            int R, const uint4 *__restrict__ elems,
                                                            const float *__restrict__ one_minus_z,
                                                            const uint32_t *__restrict__ bin_info,
                                                            const int *__restrict__ class_bins, const float *__restrict__ bias,
-                                                           const float *__restrict__ class_div, float missing)
+                                                           const float *__restrict__ class_div, float missing,
+                                                           const uint32_t *__restrict__ elem_set,
+                                                           const uint32_t *__restrict__ set_pool, uint32_t set_words)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -279,8 +308,8 @@ __global__ __launch_bounds__(256) void interactions_kernel(float *out, const flo
         for (int c = 0; c < C; ++c) {
             for (int i = lane; i < nt * FF; i += 64) slab[i] = 0.0f;
             __syncthreads();
-            interaction_bins<true>(slab, (size_t)FF, F, tile, nt, F, class_bins[c] + wave, class_bins[c + 1], kContribWaves, elems,
-                                   one_minus_z, bin_info, missing);
+            interaction_bins<true, SETS>(slab, (size_t)FF, F, tile, nt, F, class_bins[c] + wave, class_bins[c + 1], kContribWaves,
+                                         elems, one_minus_z, bin_info, missing, elem_set, set_pool, set_words);
             __syncthreads();
             const float div = class_div[c];
             for (int i = tid; i < nt * FF; i += 256) s0[i] = (((s0[i] + s1[i]) + s2[i]) + s3[i]) / div;
@@ -312,8 +341,8 @@ __global__ __launch_bounds__(256) void interactions_kernel(float *out, const flo
             for (int r = 0; r < nr; ++r)
                 for (size_t i = lane; i < (size_t)F * F1; i += 64) acc[r * row_stride + i] = 0.0f;
             vm_drain();
-            interaction_bins<false>(acc, row_stride, F1, wtile, nr, F, class_bins[c], class_bins[c + 1], 1, elems, one_minus_z,
-                                    bin_info, missing);
+            interaction_bins<false, SETS>(acc, row_stride, F1, wtile, nr, F, class_bins[c], class_bins[c + 1], 1, elems, one_minus_z,
+                                          bin_info, missing, elem_set, set_pool, set_words);
             const float div = class_div[c];
             for (int r = 0; r < nr; ++r) {
                 float *m = acc + r * row_stride;
@@ -336,10 +365,18 @@ __global__ __launch_bounds__(256) void interactions_kernel(float *out, const flo
     }
 }
 
-template __global__ void interactions_kernel<true>(float *, const float *, size_t, int, int, int, const uint4 *, const float *,
-                                                   const uint32_t *, const int *, const float *, const float *, float);
-template __global__ void interactions_kernel<false>(float *, const float *, size_t, int, int, int, const uint4 *, const float *,
-                                                    const uint32_t *, const int *, const float *, const float *, float);
+#define TAHOE_SHAP_KERNEL_ARGS                                                                                                     \
+    float *, const float *, size_t, int, int, int, const uint4 *, const float *, const uint32_t *, const int *, const float *,   \
+        const float *, float, const uint32_t *, const uint32_t *, uint32_t
+template __global__ void contribs_kernel<false>(TAHOE_SHAP_KERNEL_ARGS);
+template __global__ void contribs_kernel<true>(TAHOE_SHAP_KERNEL_ARGS);
+template __global__ void contribs_spare_kernel<false>(TAHOE_SHAP_KERNEL_ARGS);
+template __global__ void contribs_spare_kernel<true>(TAHOE_SHAP_KERNEL_ARGS);
+template __global__ void interactions_kernel<true>(TAHOE_SHAP_KERNEL_ARGS);
+template __global__ void interactions_kernel<false>(TAHOE_SHAP_KERNEL_ARGS);
+template __global__ void interactions_kernel<true, true>(TAHOE_SHAP_KERNEL_ARGS);
+template __global__ void interactions_kernel<false, true>(TAHOE_SHAP_KERNEL_ARGS);
+#undef TAHOE_SHAP_KERNEL_ARGS
 
 tahoe_status contribs_validate(const tahoe_dense_node *nodes, const tahoe_forest_params *p)
 {
@@ -373,6 +410,10 @@ struct TreePaths {
     std::vector<float> om;          // 1 - zero fraction of each element
     std::vector<unsigned char> len;  // elements per path
     double expect = 0.0;             // E_t (tree_expect)
+    // category sets (a tree with categorical splits): per element 0 = none, else 1 + its index in sets; a set is its pool
+    // entry, header first
+    std::vector<uint32_t> set_of;
+    std::vector<std::vector<uint32_t>> sets;
 };
 
 struct Elem {
@@ -380,12 +421,29 @@ struct Elem {
     float lower, upper;
     bool missing_ok, nan_ok;
     double rho;
+    // the categorical edges of the feature, folded: ids below 32 set.size() are allowed where their bit is set, every other
+    // non-missing value (beyond the words, negative, >= 2^24, NaN) iff outside_ok
+    bool has_set = false, outside_ok = true;
+    std::vector<uint32_t> set;
+    // One more edge: the path needs member == need of a split with nw words.  A shorter set is zero-extended; the ids a
+    // growing element gains were outside its words so far.
+    void fold(const uint32_t *words, size_t nw, bool need)
+    {
+        has_set = true;
+        if (nw > set.size()) set.resize(nw, outside_ok ? ~0u : 0u);
+        for (size_t i = 0; i < set.size(); ++i) {
+            const uint32_t w = i < nw ? words[i] : 0u;
+            set[i] &= need ? w : ~w;
+        }
+        outside_ok = outside_ok && !need;
+    }
 };
 
 // The two node formats as one tree for tree_paths: val, bits (fid[0:29] | def_left << 30 | is_leaf << 31 in both), the left
 // child (the right one follows it) and a node's cover.
 struct DenseTree {
     const tahoe_dense_node *n;
+    int cat(size_t) const { return -1; }
     float val(size_t i) const { return n[i].val; }
     int32_t bits(size_t i) const { return n[i].bits; }
     size_t left(size_t i) const { return 2 * i + 1; }
@@ -394,6 +452,16 @@ struct DenseTree {
 struct SparseTree {
     const tahoe_sparse_node *n;
     const float *covers;  // parallel to n
+    const tahoe_categorical_splits *cats = nullptr;  // the handle's categorical splits (null: none) ...
+    int32_t root = 0;                                // ... whose node[] counts from the forest's first node: n = nodes + root
+    // the categorical split at node i, or -1 (a numeric node, whose val is its threshold)
+    int cat(size_t i) const
+    {
+        if (!cats) return -1;
+        const int32_t g = root + (int32_t)i;
+        const int32_t *end = cats->node + cats->num_splits, *it = std::lower_bound(cats->node, end, g);
+        return it != end && *it == g ? (int)(it - cats->node) : -1;
+    }
     float val(size_t i) const { return n[i].val; }
     int32_t bits(size_t i) const { return n[i].bits; }
     size_t left(size_t i) const { return (size_t)n[i].left_idx; }
@@ -427,7 +495,7 @@ double tree_expect(const Tree &tree)
 }
 
 template <typename Tree>
-void tree_paths(const Tree &tree, TreePaths &out)
+void tree_paths(const Tree &tree, TreePaths &out, const tahoe_categorical_splits *cats = nullptr)
 {
     struct Edge {
         size_t node;
@@ -466,10 +534,16 @@ void tree_paths(const Tree &tree, TreePaths &out)
             const double rho = (edges[k].right ? wr : wl) / (wl + wr);
             size_t j = 0;
             while (j < el.size() && el[j].fid != fid) ++j;
-            if (j == el.size()) el.push_back({fid, -INFINITY, NAN, true, true, 1.0});
+            if (j == el.size()) el.push_back(Elem{fid, -INFINITY, NAN, true, true, 1.0, false, true, {}});
             Elem &m = el[j];
             m.rho *= rho;
-            if (edges[k].right) {  // x >= thr; NaN never satisfies it, missing does iff the default is right
+            const int split = tree.cat(a);
+            if (split >= 0) {  // member == (right != members_left); missing takes the default branch, NaN is no member
+                const bool ml = cats->members_left && cats->members_left[split];
+                m.fold(cats->words + cats->offset[split], (size_t)(cats->offset[split + 1] - cats->offset[split]),
+                       edges[k].right != ml);
+                m.missing_ok = m.missing_ok && (edges[k].right != def_left);
+            } else if (edges[k].right) {  // x >= thr; NaN never satisfies it, missing does iff the default is right
                 m.lower = (std::isnan(thr) || std::isnan(m.lower)) ? NAN : std::max(m.lower, thr);
                 m.nan_ok = false;
                 m.missing_ok = m.missing_ok && !def_left;
@@ -501,6 +575,12 @@ void tree_paths(const Tree &tree, TreePaths &out)
             u.w = elem_word(el[j].fid, 0, 1, 0, el[j].missing_ok, el[j].nan_ok);
             out.elems.push_back(u);
             out.om.push_back((float)(1.0 - el[j].rho));
+            if (el[j].has_set) {
+                out.set_of.resize(out.elems.size(), 0u);
+                out.sets.emplace_back(1, (el[j].outside_ok ? kSetOutsideOk : 0u) | (uint32_t)el[j].set.size());
+                out.sets.back().insert(out.sets.back().end(), el[j].set.begin(), el[j].set.end());
+                out.set_of.back() = (uint32_t)out.sets.size();
+            }
         }
         out.len.push_back((unsigned char)(ne + 1));
     }
@@ -565,6 +645,12 @@ static tahoe_status build_tables(tahoe_forest *f, std::vector<TreePaths> &trees)
     std::vector<uint4> h_elems;
     std::vector<float> h_om;
     std::vector<uint32_t> h_info;
+    // category sets: the pool (identical sets share one entry) and, per lane, 1 + the offset of its set's header
+    bool any_sets = false;
+    for (const TreePaths &tp : trees) any_sets = any_sets || !tp.sets.empty();
+    std::vector<uint32_t> h_set, h_pool;
+    std::map<std::vector<uint32_t>, uint32_t> pool_at;
+    std::vector<uint32_t> tree_at;  // per set of the current tree: 1 + its header's offset
     std::vector<int> h_class_bins(C + 1, 0);
     std::vector<float> h_bias, h_div;
     {
@@ -589,6 +675,7 @@ static tahoe_status build_tables(tahoe_forest *f, std::vector<TreePaths> &trees)
             if (fill == 0) return;
             h_elems.resize(start + 64, pad);
             h_om.resize(start + 64, 0.0f);
+            if (any_sets) h_set.resize(start + 64, 0u);
             int rounds = 0;
             for (int l = 0; l < 64; ++l) {
                 uint4 &u = h_elems[start + l];
@@ -610,6 +697,12 @@ static tahoe_status build_tables(tahoe_forest *f, std::vector<TreePaths> &trees)
             const size_t t = k * (size_t)C + (size_t)c;
             TreePaths &tp = trees[t];
             size_t off = 0;
+            tree_at.clear();
+            for (const std::vector<uint32_t> &set : tp.sets) {
+                const auto it = pool_at.emplace(set, (uint32_t)h_pool.size()).first;
+                if (it->second == h_pool.size()) h_pool.insert(h_pool.end(), set.begin(), set.end());
+                tree_at.push_back(it->second + 1u);
+            }
             for (unsigned char len : tp.len) {
                 if (fill + len > 64) flush();
                 for (int j = 0; j < len; ++j) {
@@ -617,6 +710,10 @@ static tahoe_status build_tables(tahoe_forest *f, std::vector<TreePaths> &trees)
                     u.w = (u.w & ~kElemRankLenMask) | (uint32_t)j << kElemRankShift | (uint32_t)(len - 1) << kElemLenShift;
                     h_elems.push_back(u);
                     h_om.push_back(tp.om[off + j]);
+                    if (any_sets) {
+                        const uint32_t local = off + j < tp.set_of.size() ? tp.set_of[off + j] : 0u;
+                        h_set.push_back(local ? tree_at[local - 1u] : 0u);
+                    }
                 }
                 fill += len;
                 steps = std::max(steps, (int)len);
@@ -626,6 +723,7 @@ static tahoe_status build_tables(tahoe_forest *f, std::vector<TreePaths> &trees)
             }
             std::vector<uint4>().swap(tp.elems);
             std::vector<float>().swap(tp.om);
+            std::vector<std::vector<uint32_t>>().swap(tp.sets);
         }
         flush();
     }
@@ -654,12 +752,24 @@ static tahoe_status build_tables(tahoe_forest *f, std::vector<TreePaths> &trees)
         (e = upload(&cs->bin_info, h_info, total)) != hipSuccess || (e = upload(&cs->class_bins, h_class_bins, total)) != hipSuccess ||
         (e = upload(&cs->bias, h_bias, total)) != hipSuccess || (e = upload(&cs->class_div, h_div, total)) != hipSuccess)
         return fail(TAHOE_ERR_HIP, "contribs_build: upload failed: %s", hipGetErrorString(e));
-    if ((e = allow_max_lds(reinterpret_cast<const void *>(&contribs_kernel), f->lds_limit)) != hipSuccess)
+    if (any_sets) {
+        if (h_pool.size() >= 0xffffffffu) return fail(TAHOE_ERR_UNSUPPORTED, "contribs_build: %zu words of category sets (at most 2^32 - 2)", h_pool.size());
+        cs->set_words = (uint32_t)h_pool.size();
+        if ((e = upload(&cs->elem_set, h_set, total)) != hipSuccess || (e = upload(&cs->set_pool, h_pool, total)) != hipSuccess)
+            return fail(TAHOE_ERR_HIP, "contribs_build: upload of the category sets failed: %s", hipGetErrorString(e));
+    }
+    if ((e = allow_max_lds(reinterpret_cast<const void *>(&contribs_kernel<false>), f->lds_limit)) != hipSuccess)
         return fail(TAHOE_ERR_HIP, "hipFuncSetAttribute(contribs) failed: %s", hipGetErrorString(e));
-    if ((e = allow_max_lds(reinterpret_cast<const void *>(&contribs_spare_kernel), f->lds_limit)) != hipSuccess ||
+    if ((e = allow_max_lds(reinterpret_cast<const void *>(&contribs_spare_kernel<false>), f->lds_limit)) != hipSuccess ||
         (e = allow_max_lds(reinterpret_cast<const void *>(&interactions_kernel<true>), f->lds_limit)) != hipSuccess ||
         (e = allow_max_lds(reinterpret_cast<const void *>(&interactions_kernel<false>), f->lds_limit)) != hipSuccess)
         return fail(TAHOE_ERR_HIP, "hipFuncSetAttribute(interactions) failed: %s", hipGetErrorString(e));
+    if (any_sets &&
+        ((e = allow_max_lds(reinterpret_cast<const void *>(&contribs_kernel<true>), f->lds_limit)) != hipSuccess ||
+         (e = allow_max_lds(reinterpret_cast<const void *>(&contribs_spare_kernel<true>), f->lds_limit)) != hipSuccess ||
+         (e = allow_max_lds(reinterpret_cast<const void *>(&interactions_kernel<true, true>), f->lds_limit)) != hipSuccess ||
+         (e = allow_max_lds(reinterpret_cast<const void *>(&interactions_kernel<false, true>), f->lds_limit)) != hipSuccess))
+        return fail(TAHOE_ERR_HIP, "hipFuncSetAttribute(contribs, category sets) failed: %s", hipGetErrorString(e));
     return TAHOE_OK;
 }
 
@@ -727,13 +837,14 @@ tahoe_status contribs_validate_sparse(const int32_t *trees, const tahoe_sparse_n
     return TAHOE_OK;
 }
 
-tahoe_status contribs_build_sparse(tahoe_forest *f, const int32_t *tree_roots, const tahoe_sparse_node *nodes, const float *covers)
+tahoe_status contribs_build_sparse(tahoe_forest *f, const int32_t *tree_roots, const tahoe_sparse_node *nodes, const float *covers,
+                                   const tahoe_categorical_splits *cats)
 {
     const size_t T = (size_t)f->p.num_trees;
     std::vector<TreePaths> trees(T);  // in the caller's tree numbering
     parallel_for(T, 4, [&](size_t lo, size_t hi) {
         for (size_t t = lo; t < hi; ++t) {
-            tree_paths(SparseTree{nodes + tree_roots[t], covers + tree_roots[t]}, trees[t]);
+            tree_paths(SparseTree{nodes + tree_roots[t], covers + tree_roots[t], cats, tree_roots[t]}, trees[t], cats);
             trees[t].expect = tree_expect(SparseTree{nodes + tree_roots[t], covers + tree_roots[t]});
         }
     });
@@ -750,6 +861,8 @@ void contribs_destroy(tahoe_forest *f)
     if (cs->class_bins) (void)hipFree(cs->class_bins);
     if (cs->bias) (void)hipFree(cs->bias);
     if (cs->class_div) (void)hipFree(cs->class_div);
+    if (cs->elem_set) (void)hipFree(cs->elem_set);
+    if (cs->set_pool) (void)hipFree(cs->set_pool);
     delete cs;
     f->cs = nullptr;
 }
@@ -770,9 +883,13 @@ extern "C" tahoe_status tahoe_forest_predict_contribs(tahoe_forest *f, float *ph
     DeviceGuard on_device(f->device);
     const size_t R = (size_t)cs->rows_per_tile;
     const size_t grid = (rows + R - 1) / R;
-    hipLaunchKernelGGL(contribs_kernel, dim3((unsigned)grid), dim3(256), cs->lds_bytes, (hipStream_t)stream, phi_dev, data_dev, rows,
-                       f->p.num_cols, f->num_classes, (int)R, cs->elems, cs->one_minus_z, cs->bin_info, cs->class_bins, cs->bias, cs->class_div,
-                       f->p.missing);
+    auto launch = [&](auto sets) {
+        hipLaunchKernelGGL(contribs_kernel<decltype(sets)::value>, dim3((unsigned)grid), dim3(256), cs->lds_bytes, (hipStream_t)stream,
+                           phi_dev, data_dev, rows, f->p.num_cols, f->num_classes, (int)R, cs->elems, cs->one_minus_z, cs->bin_info,
+                           cs->class_bins, cs->bias, cs->class_div, f->p.missing, cs->elem_set, cs->set_pool, cs->set_words);
+    };
+    if (cs->elem_set) launch(std::true_type{});
+    else launch(std::false_type{});
     TAHOE_HIP_TRY(hipGetLastError());
     return TAHOE_OK;
 }
@@ -791,18 +908,29 @@ extern "C" tahoe_status tahoe_forest_predict_interactions(tahoe_forest *f, float
     DeviceGuard on_device(f->device);
     hipStream_t s = (hipStream_t)stream;
     const size_t R = (size_t)cs->rows_per_tile;
-    hipLaunchKernelGGL(contribs_spare_kernel, dim3((unsigned)((rows + R - 1) / R)), dim3(256), cs->lds_bytes, s, out_dev, data_dev,
-                       rows, F, C, (int)R, cs->elems, cs->one_minus_z, cs->bin_info, cs->class_bins, cs->bias, cs->class_div,
-                       f->p.missing);
+    auto spare = [&](auto sets) {
+        hipLaunchKernelGGL(contribs_spare_kernel<decltype(sets)::value>, dim3((unsigned)((rows + R - 1) / R)), dim3(256), cs->lds_bytes,
+                           s, out_dev, data_dev, rows, F, C, (int)R, cs->elems, cs->one_minus_z, cs->bin_info, cs->class_bins, cs->bias,
+                           cs->class_div, f->p.missing, cs->elem_set, cs->set_pool, cs->set_words);
+    };
+    if (cs->elem_set) spare(std::true_type{});
+    else spare(std::false_type{});
     TAHOE_HIP_TRY(hipGetLastError());
     const size_t RI = (size_t)cs->inter_rows, per_block = cs->inter_slabs ? RI : RI * kContribWaves;
     const dim3 grid((unsigned)((rows + per_block - 1) / per_block));
-    if (cs->inter_slabs)
-        hipLaunchKernelGGL(interactions_kernel<true>, grid, dim3(256), cs->inter_lds_bytes, s, out_dev, data_dev, rows, F, C, (int)RI,
-                           cs->elems, cs->one_minus_z, cs->bin_info, cs->class_bins, cs->bias, cs->class_div, f->p.missing);
-    else
-        hipLaunchKernelGGL(interactions_kernel<false>, grid, dim3(256), cs->inter_lds_bytes, s, out_dev, data_dev, rows, F, C,
-                           (int)RI, cs->elems, cs->one_minus_z, cs->bin_info, cs->class_bins, cs->bias, cs->class_div, f->p.missing);
+    auto inter = [&](auto slabs, auto sets) {
+        hipLaunchKernelGGL((interactions_kernel<decltype(slabs)::value, decltype(sets)::value>), grid, dim3(256), cs->inter_lds_bytes,
+                           s, out_dev, data_dev, rows, F, C, (int)RI, cs->elems, cs->one_minus_z, cs->bin_info, cs->class_bins, cs->bias,
+                           cs->class_div, f->p.missing, cs->elem_set, cs->set_pool, cs->set_words);
+    };
+    if (cs->inter_slabs) {
+        if (cs->elem_set) inter(std::true_type{}, std::true_type{});
+        else inter(std::true_type{}, std::false_type{});
+    } else if (cs->elem_set) {
+        inter(std::false_type{}, std::true_type{});
+    } else {
+        inter(std::false_type{}, std::false_type{});
+    }
     TAHOE_HIP_TRY(hipGetLastError());
     return TAHOE_OK;
 }

@@ -26,6 +26,12 @@ struct tahoe_cstate {
     bool inter_slabs = false;
     int inter_rows = 0;
     size_t inter_lds_bytes = 0;
+    // Category sets (TAHOE_CREATE_CAT_CONTRIBS; null / 0 on a handle whose paths cross no categorical split): set_pool holds,
+    // per distinct set, a header outside_ok << 31 | nwords and its nwords bitset words (the split pool's layout); elem_set
+    // [bins][64] names an element's header as offset + 1, 0 = the element has no set
+    uint32_t *elem_set = nullptr;
+    uint32_t *set_pool = nullptr;
+    uint32_t set_words = 0;         // words of set_pool: bounds every word read
 };
 
 namespace tahoe {
@@ -63,6 +69,48 @@ __device__ __forceinline__ bool follows(float x, float lower, float upper, bool 
 {
     const bool is_missing = fabsf(x - missing) <= kMissingEps;
     return is_missing ? missing_ok : (x != x ? nan_ok : (x >= lower && !(x >= upper)));
+}
+
+// A lane's view of its element's category set: the pool index of its first word (0: no set), its header and its first word.
+// An element without a set reads as "no member anywhere, everything outside allowed", which follows_set() passes.
+struct ElemSet {
+    uint32_t at, head, word0;
+};
+constexpr uint32_t kSetOutsideOk = 0x80000000u, kSetWordsMask = 0xfffffu;
+
+// The set of lane `idx` of the bins (loop-invariant: once per bin, outside the row loop)
+__device__ __forceinline__ ElemSet elem_set_load(const uint32_t *__restrict__ elem_set, const uint32_t *__restrict__ pool,
+                                                 uint32_t pool_words, size_t idx)
+{
+    ElemSet s{elem_set[idx], kSetOutsideOk, 0u};
+    if (s.at != 0u) {
+        s.head = pool[s.at - 1u];
+        s.word0 = ((s.head & kSetWordsMask) != 0u && s.at < pool_words) ? pool[s.at] : 0u;
+    }
+    return s;
+}
+// Does some lane of the wave hold a set of more than one word?  (Else no lane gathers: every lane holds its whole set.)
+__device__ __forceinline__ bool elem_sets_gather(const ElemSet &s) { return __ballot((s.head & kSetWordsMask) > 1u) != 0ull; }
+
+// one-fraction of an element that may carry a category set: follows() on the interval, and, for a non-missing x, bit trunc(x)
+// of the set where go_right_cat's range test holds (0 <= x < 2^24 and trunc(x) < 32 nwords), else outside_ok.  gather
+// (wave-uniform, elem_sets_gather): read the word trunc(x) selects from the pool, bounded by pool_words; without it the lane's
+// held word serves (nwords <= 1).
+__device__ __forceinline__ bool follows_set(float x, float lower, float upper, bool missing_ok, bool nan_ok, float missing,
+                                            const ElemSet &s, const uint32_t *__restrict__ pool, uint32_t pool_words, bool gather)
+{
+    const bool is_missing = fabsf(x - missing) <= kMissingEps;
+    const bool in = x >= 0.0f && x < 16777216.0f;
+    const uint32_t c = in ? (uint32_t)x : 0u;
+    const bool in_range = in && (c >> 5) < (s.head & kSetWordsMask);
+    uint32_t word = s.word0;
+    if (gather) {
+        const uint32_t wi = s.at + (c >> 5);
+        word = (in_range && wi < pool_words) ? pool[wi] : 0u;
+    }
+    const bool set_ok = in_range ? ((word >> (c & 31u)) & 1u) != 0u : (s.head & kSetOutsideOk) != 0u;
+    const bool num_ok = x != x ? nan_ok : (x >= lower && !(x >= upper));
+    return is_missing ? missing_ok : (num_ok && set_ok);
 }
 
 // v of lane src_lane (ds_bpermute)

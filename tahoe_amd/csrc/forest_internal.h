@@ -426,6 +426,10 @@ __device__ __forceinline__ uint32_t go_right_cat(float x, const uint32_t *__rest
     const bool cond = is_missing ? !def_left : (member != ((head >> 31) != 0u));
     return cond ? 1u : 0u;
 }
+// The device copy of a categorical handle's sparse nodes (sparse.hip builds it): a categorical split carries kSCat in `bits`
+// (its fid then has 29 bits, num_cols <= 2^29) and its pool entry's index in `val`
+constexpr int32_t kSCat = (int32_t)(1u << 29);
+constexpr int32_t kSCatFidMask = (int32_t)((1u << 29) - 1u);
 // ... on a heap record: the stored children are swapped where the exchange bit is set (Struct.h:1060-1063: cond = !cond)
 __device__ __forceinline__ uint32_t go_right_meta(float x, float thr, uint32_t meta, float missing)
 {
@@ -473,6 +477,7 @@ bool sparse_q_available(const tahoe_forest *f);  // the walk on quantised codes 
 bool sparse_has_cats(const tahoe_forest *f);     // categorical splits (tahoe_sparse_forest_create_cat): no QRING
 void sparse_destroy(tahoe_forest *f);
 void sparse_device_views(const tahoe_forest *f, const tahoe_sparse_node **nodes, const int32_t **trees);  // the stored nodes and roots
+void sparse_cat_view(const tahoe_forest *f, const uint32_t **pool, uint32_t *pool_words);  // the split pool (null / 0: no splits)
 void pipeline_destroy(tahoe_forest *f);
 // TILERING for rows too wide for a 64-row float32 tile (widef.hip)
 tahoe_status widef_build(tahoe_forest *f, const std::vector<InnerNode> &h_inner, const std::vector<unsigned char> &h_real,
@@ -500,7 +505,9 @@ tahoe_status contribs_validate_sparse(const int32_t *trees, const tahoe_sparse_n
 void contribs_bias(const tahoe_forest *f, const tahoe_dense_node *nodes, std::vector<float> &bias, std::vector<float> &div);
 void contribs_bias_sparse(const tahoe_forest *f, const int32_t *trees, const tahoe_sparse_node *nodes, const float *covers,
                           std::vector<float> &bias, std::vector<float> &div);
-tahoe_status contribs_build_sparse(tahoe_forest *f, const int32_t *trees, const tahoe_sparse_node *nodes, const float *covers);
+// cats: the categorical splits of the caller's nodes (TAHOE_CREATE_CAT_CONTRIBS), or null; their path elements carry category sets
+tahoe_status contribs_build_sparse(tahoe_forest *f, const int32_t *trees, const tahoe_sparse_node *nodes, const float *covers,
+                                   const tahoe_categorical_splits *cats = nullptr);
 void contribs_destroy(tahoe_forest *f);
 // The first refusal of every TreeSHAP entry point (fn: its name): TAHOE_ERR_UNSUPPORTED unless the handle has path tables
 inline tahoe_status need_path_tables(const tahoe_forest *f, const char *fn)

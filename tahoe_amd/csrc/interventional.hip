@@ -35,9 +35,12 @@ constexpr size_t kIvLdsBudget = 80 * 1024;      // two workgroups per CU where t
 constexpr int kIvUnroll = 8;                    // background rows whose mask and weight loads are issued together
 
 // One wave per bin: masks[b][r] = ballot over the bin's lanes of "background row r follows this element" (rank-0 lanes: 0).
+// SETS (both kernels): the handle's path elements carry category sets, the one-fraction is follows_set() (contribs_internal.h).
+template <bool SETS = false>
 __global__ __launch_bounds__(256) void background_mask_kernel(unsigned long long *__restrict__ masks, const float *__restrict__ bg,
                                                               size_t B, int F, size_t bins, const uint4 *__restrict__ elems,
-                                                              float missing)
+                                                              float missing, const uint32_t *__restrict__ elem_set,
+                                                              const uint32_t *__restrict__ set_pool, uint32_t set_words)
 {
     const int lane = threadIdx.x & 63;
     const size_t b = (size_t)blockIdx.x * kContribWaves + (size_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -47,8 +50,16 @@ __global__ __launch_bounds__(256) void background_mask_kernel(unsigned long long
     const int fid = elem_fid(e.w), rank = elem_rank(e.w);
     const bool missing_ok = elem_missing_ok(e.w), nan_ok = elem_nan_ok(e.w);
     unsigned long long *out = masks + b * B;
+    ElemSet es{};
+    bool gather = false;
+    if constexpr (SETS) {
+        es = elem_set_load(elem_set, set_pool, set_words, b * 64 + lane);
+        gather = elem_sets_gather(es);
+    }
     for (size_t r = 0; r < B; ++r) {
-        const bool o = rank != 0 && follows(bg[r * F + fid], lower, upper, missing_ok, nan_ok, missing);
+        bool o;
+        if constexpr (SETS) o = rank != 0 && follows_set(bg[r * F + fid], lower, upper, missing_ok, nan_ok, missing, es, set_pool, set_words, gather);
+        else o = rank != 0 && follows(bg[r * F + fid], lower, upper, missing_ok, nan_ok, missing);
         const unsigned long long m = __ballot(o);
         if (lane == 0) out[r] = m;
     }
@@ -59,14 +70,16 @@ __global__ __launch_bounds__(256) void background_mask_kernel(unsigned long long
 // register; the sum times +-leaf goes into the slab in the bin's round order; the four slabs are summed in wave order, divided
 // by B, then by (float)Tc with AVG.  Every row sees the same operations in the same order whatever its batch, tile or position.
 // WLDS: the weight table sits in LDS after the slabs (else, for the widest rows, it is read from global memory).
-template <bool WLDS>
+template <bool WLDS, bool SETS = false>
 __global__ __launch_bounds__(256) void interventional_kernel(float *__restrict__ phi, const float *__restrict__ data, size_t rows,
                                                              int F, int C, int R, const uint4 *__restrict__ elems,
                                                              const uint32_t *__restrict__ bin_info,
                                                              const int *__restrict__ class_bins,
                                                              const float *__restrict__ class_div,
                                                              const unsigned long long *__restrict__ masks, int B,
-                                                             const float *__restrict__ consts, float missing)
+                                                             const float *__restrict__ consts, float missing,
+                                                             const uint32_t *__restrict__ elem_set,
+                                                             const uint32_t *__restrict__ set_pool, uint32_t set_words)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -102,8 +115,16 @@ __global__ __launch_bounds__(256) void interventional_kernel(float *__restrict__
             // the lanes of this lane's path but its root: gs + 1 .. gs + ud (a path never leaves its bin)
             const unsigned long long pm = ud == 0 ? 0ull : ((1ull << ud) - 1ull) << (gs + 1);
             const unsigned long long *mb = masks + (size_t)b * B;
+            ElemSet es{};
+            bool gather = false;
+            if constexpr (SETS) {
+                es = elem_set_load(elem_set, set_pool, set_words, (size_t)b * 64 + lane);
+                gather = elem_sets_gather(es);
+            }
             for (int r = 0; r < nr; ++r) {
-                const bool o = rank != 0 && follows(tile[r * F + fid], lower, upper, missing_ok, nan_ok, missing);
+                bool o;
+                if constexpr (SETS) o = rank != 0 && follows_set(tile[r * F + fid], lower, upper, missing_ok, nan_ok, missing, es, set_pool, set_words, gather);
+                else o = rank != 0 && follows(tile[r * F + fid], lower, upper, missing_ok, nan_ok, missing);
                 const unsigned long long mx = __ballot(o);
                 const unsigned long long pa = pm & mx, pb = pm & ~mx;
                 const int nb = __popcll(pb);
@@ -148,12 +169,14 @@ __global__ __launch_bounds__(256) void interventional_kernel(float *__restrict__
     }
 }
 
-template __global__ void interventional_kernel<true>(float *, const float *, size_t, int, int, int, const uint4 *, const uint32_t *,
-                                                     const int *, const float *, const unsigned long long *, int, const float *,
-                                                     float);
-template __global__ void interventional_kernel<false>(float *, const float *, size_t, int, int, int, const uint4 *, const uint32_t *,
-                                                      const int *, const float *, const unsigned long long *, int, const float *,
-                                                      float);
+#define TAHOE_IV_KERNEL_ARGS                                                                                                  \
+    float *, const float *, size_t, int, int, int, const uint4 *, const uint32_t *, const int *, const float *,              \
+        const unsigned long long *, int, const float *, float, const uint32_t *, const uint32_t *, uint32_t
+template __global__ void interventional_kernel<true>(TAHOE_IV_KERNEL_ARGS);
+template __global__ void interventional_kernel<false>(TAHOE_IV_KERNEL_ARGS);
+template __global__ void interventional_kernel<true, true>(TAHOE_IV_KERNEL_ARGS);
+template __global__ void interventional_kernel<false, true>(TAHOE_IV_KERNEL_ARGS);
+#undef TAHOE_IV_KERNEL_ARGS
 
 namespace {
 
@@ -244,8 +267,14 @@ extern "C" tahoe_status tahoe_forest_set_background(tahoe_forest *f, const float
     iv->bg_rows = bg_rows;
     iv->bytes = mask_bytes + const_bytes;
     if (bins > 0) {
-        hipLaunchKernelGGL(background_mask_kernel, dim3((unsigned)((bins + kContribWaves - 1) / kContribWaves)), dim3(256), 0, s,
-                           iv->masks, bg_dev, bg_rows, (int)F, bins, f->cs->elems, f->p.missing);
+        const tahoe_cstate *cs = f->cs;
+        auto launch = [&](auto sets) {
+            hipLaunchKernelGGL(background_mask_kernel<decltype(sets)::value>, dim3((unsigned)((bins + kContribWaves - 1) / kContribWaves)),
+                               dim3(256), 0, s, iv->masks, bg_dev, bg_rows, (int)F, bins, cs->elems, f->p.missing, cs->elem_set,
+                               cs->set_pool, cs->set_words);
+        };
+        if (cs->elem_set) launch(std::true_type{});
+        else launch(std::false_type{});
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess)
             return bail(fail(TAHOE_ERR_HIP, "tahoe_forest_set_background: mask kernel: %s", hipGetErrorString(e)));
@@ -276,7 +305,10 @@ extern "C" tahoe_status tahoe_forest_set_background(tahoe_forest *f, const float
     (void)hipFree(sums);
     sums = nullptr;
     if ((e = allow_max_lds(reinterpret_cast<const void *>(&interventional_kernel<true>), f->lds_limit)) != hipSuccess ||
-        (e = allow_max_lds(reinterpret_cast<const void *>(&interventional_kernel<false>), f->lds_limit)) != hipSuccess)
+        (e = allow_max_lds(reinterpret_cast<const void *>(&interventional_kernel<false>), f->lds_limit)) != hipSuccess ||
+        (f->cs->elem_set &&
+         ((e = allow_max_lds(reinterpret_cast<const void *>(&interventional_kernel<true, true>), f->lds_limit)) != hipSuccess ||
+          (e = allow_max_lds(reinterpret_cast<const void *>(&interventional_kernel<false, true>), f->lds_limit)) != hipSuccess)))
         return bail(fail(TAHOE_ERR_HIP, "hipFuncSetAttribute(interventional) failed: %s", hipGetErrorString(e)));
     interventional_destroy(f);
     f->iv = iv;
@@ -303,14 +335,20 @@ extern "C" tahoe_status tahoe_forest_predict_contribs_interventional(tahoe_fores
     const tahoe_cstate *cs = f->cs;
     const tahoe_istate *iv = f->iv;
     DeviceGuard on_device(f->device);
-    if (sh.wlds)
-        hipLaunchKernelGGL(interventional_kernel<true>, dim3((unsigned)grid), dim3(256), sh.lds_bytes, (hipStream_t)stream, phi_dev,
-                           data_dev, rows, F, C, sh.rows, cs->elems, cs->bin_info, cs->class_bins, cs->class_div, iv->masks,
-                           (int)iv->bg_rows, iv->consts, f->p.missing);
-    else
-        hipLaunchKernelGGL(interventional_kernel<false>, dim3((unsigned)grid), dim3(256), sh.lds_bytes, (hipStream_t)stream,
-                           phi_dev, data_dev, rows, F, C, sh.rows, cs->elems, cs->bin_info, cs->class_bins, cs->class_div,
-                           iv->masks, (int)iv->bg_rows, iv->consts, f->p.missing);
+    auto launch = [&](auto wlds, auto sets) {
+        hipLaunchKernelGGL((interventional_kernel<decltype(wlds)::value, decltype(sets)::value>), dim3((unsigned)grid), dim3(256),
+                           sh.lds_bytes, (hipStream_t)stream, phi_dev, data_dev, rows, F, C, sh.rows, cs->elems, cs->bin_info,
+                           cs->class_bins, cs->class_div, iv->masks, (int)iv->bg_rows, iv->consts, f->p.missing, cs->elem_set,
+                           cs->set_pool, cs->set_words);
+    };
+    if (sh.wlds) {
+        if (cs->elem_set) launch(std::true_type{}, std::true_type{});
+        else launch(std::true_type{}, std::false_type{});
+    } else if (cs->elem_set) {
+        launch(std::false_type{}, std::true_type{});
+    } else {
+        launch(std::false_type{}, std::false_type{});
+    }
     TAHOE_HIP_TRY(hipGetLastError());
     return TAHOE_OK;
 }

@@ -66,8 +66,7 @@ namespace tahoe {
 constexpr int32_t kSFidMask = (int32_t)((1u << 30) - 1u);
 constexpr int32_t kSDefLeft = (int32_t)(1u << 30);
 constexpr int32_t kSIsLeaf = (int32_t)(1u << 31);
-constexpr int32_t kSCat = (int32_t)(1u << 29);          // device copy of a categorical handle: the node is a categorical split
-constexpr int32_t kSCatFidMask = (int32_t)((1u << 29) - 1u);  // ... whose fid then has 29 bits (num_cols <= 2^29)
+// kSCat / kSCatFidMask (forest_internal.h): the device copy of a categorical handle flags a categorical split in bit 29
 constexpr uint32_t kSCCat = 0x4000u;   // compact node of a categorical handle: the node is a categorical split (fid: 14 bits)
 constexpr int kSCatMaxCompactCols = 1 << 14;
 constexpr long long kCatMaxWords = 1 << 19;  // categories < 2^24: exact in float32
@@ -1224,6 +1223,12 @@ void sparse_device_views(const tahoe_forest *f, const tahoe_sparse_node **nodes,
     *trees = f->sp->trees;
 }
 
+void sparse_cat_view(const tahoe_forest *f, const uint32_t **pool, uint32_t *pool_words)
+{
+    *pool = f->sp->cat_pool;
+    *pool_words = f->sp->cat_words;
+}
+
 // The argument checks of the categorical splits (TAHOE_ERR_INVALID_ARG), in the header's order.
 static tahoe_status check_cat_args(const tahoe_categorical_splits *c, int num_nodes)
 {
@@ -1296,14 +1301,18 @@ static tahoe_status create_sparse(tahoe_forest **out, const int32_t *trees, cons
             if (nodes[i].bits & kSIsLeaf)
                 return fail(TAHOE_ERR_INVALID_FOREST, "tree %d node %d: categorical split %d names a leaf", t, i - trees[t], k);
         }
-        if (flags & (TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS))
+        if ((flags & (TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS)) && !(flags & TAHOE_CREATE_CAT_CONTRIBS))
             return fail(TAHOE_ERR_UNSUPPORTED, "categorical splits do not combine with TAHOE_CREATE_CONTRIBS or "
                                                "TAHOE_CREATE_APPROX_CONTRIBS: TreeSHAP's path elements are intervals per feature, "
-                                               "and a category set is not an interval");
+                                               "and a category set is not an interval (TAHOE_CREATE_CAT_CONTRIBS builds the "
+                                               "elements with category sets)");
         if (p->num_cols > (1 << 29))
             return fail(TAHOE_ERR_UNSUPPORTED, "categorical splits need num_cols <= 2^29 (the device node keeps bit 29 as the "
                                                "categorical flag); num_cols = %d", p->num_cols);
     }
+    if ((flags & TAHOE_CREATE_CAT_CONTRIBS) && !(flags & (TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS)))
+        return fail(TAHOE_ERR_INVALID_ARG, "TAHOE_CREATE_CAT_CONTRIBS needs TAHOE_CREATE_CONTRIBS or TAHOE_CREATE_APPROX_CONTRIBS "
+                                           "(it says how their tables treat categorical splits and builds nothing alone)");
     if (flags & (TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS)) {
         // the covers (and, for the path bins, the path lengths), on the caller's nodes, before a device is touched
         const tahoe_status cs = contribs_validate_sparse(trees, nodes, covers, p, (flags & TAHOE_CREATE_CONTRIBS) != 0);
@@ -1375,7 +1384,7 @@ static tahoe_status create_sparse(tahoe_forest **out, const int32_t *trees, cons
     if (p->num_cols <= 32767 && p->num_trees > 0 && (s = sparse_top_build(f.get(), trees, nodes))) return s;
     // contributions from the caller's trees, in the caller's numbering (contribs_build's order); Saabas deltas in the stored
     // (class-major) order
-    return finish_create(f, flags, out, [&] { return contribs_build_sparse(f.get(), caller_trees, caller_nodes, covers); },
+    return finish_create(f, flags, out, [&] { return contribs_build_sparse(f.get(), caller_trees, caller_nodes, covers, cats); },
                          [&] { return approx_build_sparse(f.get(), caller_trees, caller_nodes, covers); });
 }
 
@@ -1391,21 +1400,18 @@ tahoe_status tahoe_sparse_forest_create(tahoe_forest **out, const int32_t *trees
     return create_sparse(out, trees, nodes, nullptr, p, 1, 0u);
 }
 
-tahoe_status tahoe_sparse_forest_create_ex(tahoe_forest **out, const int32_t *trees, const tahoe_sparse_node *nodes,
-                                           const float *covers, const tahoe_forest_params *p, int num_classes, unsigned flags)
-{
-    return tahoe_sparse_forest_create_cat(out, trees, nodes, covers, p, num_classes, flags, nullptr);
-}
-
-tahoe_status tahoe_sparse_forest_create_cat(tahoe_forest **out, const int32_t *trees, const tahoe_sparse_node *nodes,
-                                            const float *covers, const tahoe_forest_params *p, int num_classes, unsigned flags,
-                                            const tahoe_categorical_splits *cats)
+// tahoe_sparse_forest_create_ex (cats NULL) and tahoe_sparse_forest_create_cat; only the latter knows TAHOE_CREATE_CAT_CONTRIBS
+static tahoe_status create_sparse_checked(tahoe_forest **out, const int32_t *trees, const tahoe_sparse_node *nodes,
+                                          const float *covers, const tahoe_forest_params *p, int num_classes, unsigned flags,
+                                          const tahoe_categorical_splits *cats, bool from_create_cat)
 {
     // every check here (and in create_sparse) runs before a device is touched
     if (!out || !p) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_sparse_forest_create_ex: null argument");
     *out = nullptr;
     if (const tahoe_status s = check_classes(p, num_classes)) return s;
-    if ((flags & ~(unsigned)(TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS)) != 0)
+    // tahoe_sparse_forest_create_ex comes here with cats == NULL and keeps its "any other bit" rule
+    const unsigned known = TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS | (from_create_cat ? TAHOE_CREATE_CAT_CONTRIBS : 0u);
+    if ((flags & ~known) != 0)
         return fail(TAHOE_ERR_INVALID_ARG, "unknown create flags 0x%x (a sparse handle takes TAHOE_CREATE_CONTRIBS and "
                                            "TAHOE_CREATE_APPROX_CONTRIBS only)", flags);
     if ((flags & TAHOE_CREATE_CONTRIBS) && !covers)
@@ -1413,6 +1419,19 @@ tahoe_status tahoe_sparse_forest_create_cat(tahoe_forest **out, const int32_t *t
     if ((flags & TAHOE_CREATE_APPROX_CONTRIBS) && !covers)
         return fail(TAHOE_ERR_INVALID_ARG, "TAHOE_CREATE_APPROX_CONTRIBS needs covers (one per node)");
     return create_sparse(out, trees, nodes, covers, p, num_classes, flags, cats);
+}
+
+tahoe_status tahoe_sparse_forest_create_ex(tahoe_forest **out, const int32_t *trees, const tahoe_sparse_node *nodes,
+                                           const float *covers, const tahoe_forest_params *p, int num_classes, unsigned flags)
+{
+    return create_sparse_checked(out, trees, nodes, covers, p, num_classes, flags, nullptr, false);
+}
+
+tahoe_status tahoe_sparse_forest_create_cat(tahoe_forest **out, const int32_t *trees, const tahoe_sparse_node *nodes,
+                                            const float *covers, const tahoe_forest_params *p, int num_classes, unsigned flags,
+                                            const tahoe_categorical_splits *cats)
+{
+    return create_sparse_checked(out, trees, nodes, covers, p, num_classes, flags, cats, true);
 }
 
 // dense2sparse, BaseTahoeTest.h:728-764: per tree a root, then for every inner node its two children are

@@ -8,7 +8,8 @@ then   python tools/isa_diff.py <old_dir> <new_dir> [forest qring ...] [-v]
 (dirs = where the *-hip-amdgcn-amd-amdhsa-gfx950.s files are).  Local branch labels are renumbered and the kernel descriptor's
 name, section and kernarg_size lines are left out of the comparison (a kernel argument appended at the end changes only those).
 A template flag appended with a default (`bool MC = false`) is matched by dropping a trailing `, false` template argument; new
-instantiations with `, true` there are counted, not compared.  A function whose full name exists in both builds is matched by
+instantiations with `, true` there are counted, not compared; a kernel that became a template for the flag is matched by dropping
+`<false>`.  A function whose full name exists in both builds is matched by
 that name first, so kernels of the list that did not get the flag in this change are compared as they are.  --exact: both builds have the same template parameters (no appended
 flag): functions are matched by their full names.  A translation unit that exists only in <new_dir> is listed as new."""
 import difflib
@@ -17,7 +18,9 @@ import subprocess
 import sys
 
 FLAGGED = ("direct_kernel", "rowtile_kernel", "qring_kernel", "qwide_kernel",  # kernels that carry the appended flag
-           "sparse_kernel", "sparse_top_kernel", "sparse_q_kernel")
+           "sparse_kernel", "sparse_top_kernel", "sparse_q_kernel",
+           "contribs_kernel", "contribs_spare_kernel", "interactions_kernel", "background_mask_kernel",  # SETS / CAT
+           "interventional_kernel", "approx_kernel")
 
 
 def functions(path):
@@ -37,6 +40,8 @@ def functions(path):
             text = re.sub(r"\.Ltmp\d+", ".Ltmp", text)
             if any(x in text for x in (".amdhsa_kernel ", ".section", ".amdhsa_kernarg_size")):
                 continue
+            if text.strip() == ".text":  # (a kernel that became a template moves from .text to a section of its own)
+                continue
             if text.strip():
                 body.append(text)
     return out
@@ -53,6 +58,10 @@ def key(name, new, old_names=()):
         if base.endswith(", false>"):
             return base[: -len(", false>")] + ">"
         if base.endswith(", true>"):
+            return None
+        if base.endswith("<false>"):  # a kernel that became a template for the flag
+            return base[: -len("<false>")].split(" ")[-1]  # (a template's demangled name leads with its return type)
+        if base.endswith("<true>"):
             return None
     return base
 
