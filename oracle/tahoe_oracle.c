@@ -124,7 +124,13 @@ float oracle_infer_one_tree(const oracle_node *root, const float *row, float mis
     return value;                                                                    /* :455 */
 }
 
-static float oracle_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); } /* Struct.h:13 */
+/* Struct.h:13, but for the tail where expf(-x) overflows (x < -88.72): there 1 / inf would flush the value, a float32
+ * subnormal down to x = -103.97, to 0.  1 + e^-x rounds to e^-x long before, so the value is expf(x). */
+static float oracle_sigmoid(float x)
+{
+    const float e = expf(-x);
+    return e == INFINITY ? expf(x) : 1.0f / (1.0f + e);
+}
 
 void oracle_predict(const oracle_node *nodes, int num_trees, int depth, const float *data,
                     size_t row_begin, size_t row_end, int num_cols, float missing, int output,

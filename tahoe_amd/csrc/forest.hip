@@ -680,11 +680,19 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
 
 // transform_k (Struct.h:196-209) with the CPU predictor's arithmetic (BaseTahoeTest.h:467-472):
 // AVG divides by num_trees (the reference's GPU epilogue multiplies by 1/T instead).
+// sigmoid: 1 / (1 + expf(-r)), except where expf(-r) overflows (r < -88.72): 1 / inf would flush the subnormal tail (down to
+// r = -103.97) to 0; there 1 + e^-r has long rounded to e^-r, so the value is expf(r).
+__device__ __forceinline__ float sigmoid_value(float r)
+{
+    const float e = expf(-r);
+    return e == INFINITY ? expf(r) : 1.0f / (1.0f + e);
+}
+
 __device__ __forceinline__ float transform_value(float r, int output, int num_trees, float threshold, float global_bias)
 {
     if ((output & TAHOE_OUT_AVG) != 0) r = r / (float)num_trees;
     r += global_bias;
-    if ((output & TAHOE_OUT_SIGMOID) != 0) r = 1.0f / (1.0f + expf(-r));
+    if ((output & TAHOE_OUT_SIGMOID) != 0) r = sigmoid_value(r);
     if ((output & TAHOE_OUT_THRESHOLD) != 0) r = r > threshold ? 1.0f : 0.0f;
     return r;
 }
@@ -710,7 +718,7 @@ __global__ void transform_mc_kernel(float *preds, size_t rows, int num_classes, 
         float r = p[c];
         if ((output & TAHOE_OUT_AVG) != 0) r = r / (float)class_trees;
         r += global_bias;
-        if ((output & TAHOE_OUT_SIGMOID) != 0) r = 1.0f / (1.0f + expf(-r));
+        if ((output & TAHOE_OUT_SIGMOID) != 0) r = sigmoid_value(r);
         p[c] = r;
         m = fmaxf(m, r);
     }

@@ -195,7 +195,10 @@ class BaseTahoeTest {
                 pred += infer_one_tree(&nodes[(size_t)t * per_tree], &data_h[(size_t)r * ps.num_cols]);
             if (ps.output & output_t::AVG) pred = pred / ps.num_trees;
             pred += ps.global_bias;
-            if (ps.output & output_t::SIGMOID) pred = 1.0f / (1.0f + expf(-pred));
+            if (ps.output & output_t::SIGMOID) {  // (expf(-pred) overflows below -88.72: the subnormal tail is expf(pred))
+                const float e = expf(-pred);
+                pred = std::isinf(e) ? expf(pred) : 1.0f / (1.0f + e);
+            }
             if (ps.output & output_t::THRESHOLD) pred = pred > ps.threshold ? 1.0f : 0.0f;
             want[r] = pred;
         }
