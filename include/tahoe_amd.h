@@ -413,6 +413,41 @@ typedef struct {
 tahoe_status tahoe_sparse_forest_create_cat(tahoe_forest **out, const int32_t *trees, const tahoe_sparse_node *nodes,
                                             const float *covers, const tahoe_forest_params *params, int num_classes,
                                             unsigned flags, const tahoe_categorical_splits *cats);
+/* ---- oblivious (symmetric) forests: CatBoost models.  Every node of a level shares one split, so a tree of depth D is D
+ * (feature, border) records and a table of 2^D leaves; no counterpart in the reference. ---- */
+typedef struct {
+    float thr;
+    int32_t bits; /* fid[0:29] | def_left<<30 */
+} tahoe_oblivious_split;
+/* depths[t] in [0, 16], one per tree (trees may differ; depth 0 is a single leaf).  splits holds sum_t depths[t] records,
+ * tree-major, record l of tree t the split of level l (may be NULL when that sum is 0).  leaf_values holds sum_t 2^depths[t] *
+ * leaf_dim floats in CatBoost's layout: tree-major, then leaf index, then the K = leaf_dim values of that leaf.  Of `params`,
+ * num_trees, num_cols, output, threshold, global_bias and missing are used; depth, num_nodes, algo and strategy are ignored.
+ * Level l applies the rule of tahoe_forest_predict to the row's value x of its feature: fabsf(x - missing) <= 1e-6f takes the
+ * default branch (right iff !def_left), NaN goes left, else right iff x >= thr.  Leaf index = sum_l bit_l << l: level 0 is the
+ * least significant bit (CatBoost's numbering); tahoe_forest_predict_leaf_idx reports it.  margin[row][k] is the float32 sum
+ * from +0.0f over trees 0..T-1 in order of leaf_values[t][idx_t][k] -- bit for bit what the heap expansion of the forest gives on
+ * a handle of tahoe_forest_create (K == 1) or, with tree t * K + k carrying class k's leaves, of tahoe_forest_create_multiclass.
+ * Output bits: K == 1 as tahoe_forest_create; K > 1 the contract of tahoe_forest_create_multiclass with C = K, except that AVG
+ * divides by (float)num_trees (every tree feeds every class).  tahoe_forest_num_classes returns K.
+ * Checks, all before a device is touched, in this order: NULL out / depths / leaf_values / params, num_trees < 0, NULL splits with
+ * a positive sum of depths, leaf_dim outside [1, 1024], num_cols < 0 or unknown output bits, the output combinations
+ * tahoe_forest_create_multiclass refuses (SOFTMAX with K == 1 or with SIGMOID, THRESHOLD with K > 1): TAHOE_ERR_INVALID_ARG; a
+ * depth outside [0, 16]: TAHOE_ERR_INVALID_ARG naming the tree; a fid >= num_cols: TAHOE_ERR_INVALID_FOREST naming the tree and
+ * the level.
+ * The handle keeps 8 bytes per split, 12 bytes per tree and the leaf table (tahoe_forest_info.device_bytes; depth = the largest
+ * depth, is_sparse = 0).  Served: tahoe_forest_predict, _predict_raw, _predict_leaf_idx (leaf_dev[row * num_trees + tree], sums
+ * rows x K), _predict_accumulate (K == 1; K > 1 TAHOE_ERR_UNSUPPORTED), _reserve (nothing to size: predict allocates nothing and
+ * can be captured), set/get_strategy, get_kernel_form, get_info, check, profiling, destroy.  Strategies: DIRECT (kernel form
+ * TAHOE_OBLIVIOUS_FORM_DIRECT: features from global memory, any num_cols), ROWTILE (TAHOE_OBLIVIOUS_FORM_TILE: one wave per
+ * 64-row float32 tile in LDS; needs 256 x num_cols bytes of LDS), AUTO = ROWTILE when the tile fits, else DIRECT; TILEBLOCK,
+ * TILERING and QRING are TAHOE_ERR_UNSUPPORTED.
+ * Out of scope, TAHOE_ERR_UNSUPPORTED with nothing launched and a text that says "oblivious": tahoe_forest_predict_csr,
+ * _reserve_csr (and _get_csr_plan: form TAHOE_FORM_NONE), _predict_host, _set_stages, _predict_staged (_get_staged_strategy: 0),
+ * the four SHAP calls and _set_background.  CatBoost's one-hot and CTR splits are not represented. */
+tahoe_status tahoe_oblivious_forest_create(tahoe_forest **out, const int32_t *depths, const tahoe_oblivious_split *splits,
+                                           const float *leaf_values, const tahoe_forest_params *params, int leaf_dim);
+
 /* dense2sparse (BaseTahoeTest.h:728-764).  *nodes_out / *trees_out: tahoe_free_host. */
 tahoe_status tahoe_dense_to_sparse(const tahoe_dense_node *dense, int num_trees, int depth,
                                    tahoe_sparse_node **nodes_out, int32_t **trees_out, size_t *num_nodes_out);
@@ -614,6 +649,13 @@ enum {
     TAHOE_FORM_CSR_ROWTILE = 20,          /* tahoe_forest_predict_csr only: rowtile_kernel staging its tile from the CSR arrays */
     TAHOE_FORM_CSR_SPARSE_ROWTILE = 21,   /* ... sparse_kernel with the tile */
     TAHOE_FORM_CSR_SPARSE_TOP = 22        /* ... sparse_top_kernel */
+};
+/* The kernel forms of an oblivious handle (tahoe_oblivious_forest_create).  They continue the numbering at 24: 23 stays
+ * unassigned, because tahoe_kernel_form_name(23) == "?" is behaviour callers of the CSR entry points were promised (the first
+ * value past TAHOE_FORM_CSR_SPARSE_TOP has no name). */
+enum {
+    TAHOE_OBLIVIOUS_FORM_DIRECT = 24,     /* oblivious_direct_kernel: features from global memory */
+    TAHOE_OBLIVIOUS_FORM_TILE = 25        /* oblivious_tile_kernel: one wave per 64-row float32 tile */
 };
 int tahoe_forest_get_kernel_form(const tahoe_forest *f, size_t rows);
 const char *tahoe_kernel_form_name(int form);

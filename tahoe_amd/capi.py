@@ -145,6 +145,7 @@ _PROTOS = {
     "tahoe_sparse_forest_create_ex": (_i, [C.POINTER(_vp), _vp, _vp, _vp, C.POINTER(ForestParams), _i, C.c_uint]),
     "tahoe_sparse_forest_create_cat": (_i, [C.POINTER(_vp), _vp, _vp, _vp, C.POINTER(ForestParams), _i, C.c_uint,
                                             C.POINTER(CategoricalSplits)]),
+    "tahoe_oblivious_forest_create": (_i, [C.POINTER(_vp), _vp, _vp, _vp, C.POINTER(ForestParams), _i]),
     "tahoe_dense_to_sparse": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz)]),
     "tahoe_dense_to_sparse_ex": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz)]),
     "tahoe_synth_sparse_forest": (_i, [_vp, _vp, C.POINTER(_sz), _i, _i, _i, _i, _f, _i, C.c_uint64]),
@@ -772,6 +773,49 @@ class SparseForest(Forest):
                                                   nodes.ctypes.data if nodes.size else None, C.byref(self.params)),
                    "tahoe_sparse_forest_create")
         self.num_trees, self.depth, self.num_cols = int(trees.size), 0, num_cols
+        self.num_classes = lib.tahoe_forest_num_classes(self._h)
+
+
+# ---- oblivious (symmetric) forests: CatBoost models ----
+OBLIVIOUS_SPLIT_DTYPE = np.dtype([("thr", "<f4"), ("bits", "<i4")])  # tahoe_oblivious_split
+
+
+def strict_borders(b) -> np.ndarray:
+    """Thresholds for CatBoost borders: CatBoost goes right iff x > border, this library iff x >= thr, and for every x that is
+    not NaN x > border <=> x >= nextafter(float32(border), +inf)."""
+    with np.errstate(over="ignore"):  # FLT_MAX -> +inf is meant
+        return np.nextafter(np.asarray(b, dtype=np.float32), np.float32(np.inf))
+
+
+class ObliviousForest(Forest):
+    """tahoe_oblivious_forest_create: trees whose levels share one split each.  depths [T] (0 .. 16); fids, thresholds and
+    def_left hold sum(depths) entries, tree-major, level 0 first; leaf_values holds sum(2 ** depths) * leaf_dim floats (tree,
+    leaf index, then the leaf_dim values); level l sets bit l of the leaf index.  predict* as Forest, with leaf_dim > 1 in the
+    shapes of a multi-class handle ([rows, leaf_dim]); AVG divides by the number of trees."""
+
+    def __init__(self, depths, fids, thresholds, def_left, leaf_values, num_cols: int, leaf_dim: int = 1, missing: float = 0.0,
+                 output: int = OUT_RAW, threshold: float = 0.5, global_bias: float = 0.0):
+        depths = np.ascontiguousarray(depths, dtype=np.int32).reshape(-1)
+        fids = np.asarray(fids, dtype=np.int64).reshape(-1)
+        nsplits = int(depths.astype(np.int64).sum())
+        if not (fids.size == nsplits == np.size(thresholds) == np.size(def_left)):
+            raise ValueError("fids, thresholds and def_left must hold sum(depths) entries")
+        if fids.size and (fids.min() < 0 or fids.max() >= 1 << 30):
+            raise ValueError("fids must be in [0, 2^30)")
+        splits = np.empty(max(nsplits, 1), dtype=OBLIVIOUS_SPLIT_DTYPE)
+        splits["thr"][:nsplits] = np.asarray(thresholds, dtype=np.float32).reshape(-1)
+        splits["bits"][:nsplits] = (fids | (np.asarray(def_left).reshape(-1).astype(bool).astype(np.int64) << 30)).astype(np.int32)
+        leaves = np.ascontiguousarray(leaf_values, dtype=np.float32).reshape(-1)
+        if bool(((depths >= 0) & (depths <= 16)).all()) and leaf_dim >= 1:  # (else the C function refuses with its own text)
+            if leaves.size != int((np.int64(1) << depths.astype(np.int64)).sum()) * leaf_dim:
+                raise ValueError("leaf_values.size != sum(2 ** depths) * leaf_dim")
+        dp = depths if depths.size else np.zeros(1, np.int32)  # (the C function refuses NULL arrays, also for no trees)
+        lv = leaves if leaves.size else np.zeros(1, np.float32)
+        self.params = ForestParams(0, 0, int(depths.size), num_cols, 0, output, threshold, global_bias, 0, missing)
+        self._h = _vp()
+        _check(lib.tahoe_oblivious_forest_create(C.byref(self._h), dp.ctypes.data, splits.ctypes.data if nsplits else None,
+                                                 lv.ctypes.data, C.byref(self.params), leaf_dim), "tahoe_oblivious_forest_create")
+        self.num_trees, self.depth, self.num_cols = int(depths.size), int(depths.max()) if depths.size else 0, num_cols
         self.num_classes = lib.tahoe_forest_num_classes(self._h)
 
 

@@ -279,6 +279,7 @@ extern "C" tahoe_status tahoe_forest_predict_contribs_approx(tahoe_forest *f, fl
                                                              void *stream)
 {
     if (!f) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_contribs_approx: null forest");
+    if (const tahoe_status st = refuse_oblivious(f, "tahoe_forest_predict_contribs_approx")) return st;
     if (!f->ap)
         return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_contribs_approx: the handle was created without "
                                            "TAHOE_CREATE_APPROX_CONTRIBS and has no node deltas");

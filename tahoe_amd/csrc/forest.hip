@@ -819,6 +819,10 @@ static int tilering_rows(const tahoe_forest *f)
 
 static int resolve_strategy(const tahoe_forest *f, size_t rows)
 {
+    if (f->ob) {  // oblivious handle: ROWTILE = one wave per 64-row float32 tile, DIRECT = features from global memory
+        if (f->strategy != TAHOE_STRATEGY_AUTO) return f->strategy;
+        return oblivious_tile_fits(f) ? TAHOE_STRATEGY_ROWTILE : TAHOE_STRATEGY_DIRECT;
+    }
     if (f->sp) {  // sparse handle: QRING = quantised 192-row tile + tree tops in LDS, TILEBLOCK = 64-row float32 tile + tree
                   // tops, ROWTILE = tile only, DIRECT = neither
         if (f->strategy == TAHOE_STRATEGY_DIRECT) return TAHOE_STRATEGY_DIRECT;
@@ -861,6 +865,12 @@ static int resolve_strategy(const tahoe_forest *f, size_t rows)
 
 tahoe_status strategy_available(const tahoe_forest *f, int strategy)
 {
+    if (f->ob) {
+        if (strategy > TAHOE_STRATEGY_ROWTILE || (strategy == TAHOE_STRATEGY_ROWTILE && !oblivious_tile_fits(f)))
+            return fail(TAHOE_ERR_UNSUPPORTED, "an oblivious forest runs AUTO, DIRECT or ROWTILE (a 64-row tile of %d columns in %d B "
+                                               "of LDS)", f->p.num_cols, f->lds_limit);
+        return TAHOE_OK;
+    }
     if (f->sp) {
         if (strategy == TAHOE_STRATEGY_QRING && sparse_has_cats(f))
             return fail(TAHOE_ERR_UNSUPPORTED,
@@ -948,6 +958,9 @@ static tahoe_status launch_traversal(tahoe_forest *f, float *sums, uint32_t *lea
             TAHOE_HIP_TRY(hipMemcpyAsync(sums, sums_in, rows * sizeof(float), hipMemcpyDeviceToDevice, stream));
         else if (sums && !sums_in)
             TAHOE_HIP_TRY(hipMemsetAsync(sums, 0, rows * (size_t)f->num_classes * sizeof(float), stream));
+    } else if (f->ob) {
+        const tahoe_status os = oblivious_launch(f, sums, leaf_out, data, rows, stream, strategy, sums_in);
+        if (os != TAHOE_OK) return os;
     } else if (f->sp) {
         const tahoe_status ss = sparse_launch(f, sums, leaf_out, data, rows, stream, strategy, sums_in, csr);
         if (ss != TAHOE_OK) return ss;
@@ -1156,7 +1169,7 @@ tahoe_status predict_rows(tahoe_forest *f, float *preds, const float *data, size
 // 0: no stages are set, or the forced strategy (QRING, TILERING, dense TILEBLOCK) has no staged form.
 static int staged_strategy(const tahoe_forest *f)
 {
-    if (!f->stages_dev) return 0;
+    if (!f->stages_dev) return 0;  // (an oblivious handle never has stages)
     const int forced = f->strategy;  // (tahoe_forest_set_strategy has checked that the handle can run it)
     if (forced == TAHOE_STRATEGY_DIRECT || forced == TAHOE_STRATEGY_ROWTILE) return forced;
     if (f->sp) {
@@ -1480,6 +1493,7 @@ void tahoe_forest_destroy(tahoe_forest *f)
     csr_destroy(f);
     qring_destroy(f);
     sparse_destroy(f);
+    oblivious_destroy(f);
     widef_destroy(f);
     interventional_destroy(f);
     contribs_destroy(f);
@@ -1519,6 +1533,7 @@ tahoe_status tahoe_forest_set_stages(tahoe_forest *f, const int32_t *rounds, int
 {
     // every check here runs before a device is touched
     if (!f) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_set_stages: null forest");
+    if (const tahoe_status s = refuse_oblivious(f, "tahoe_forest_set_stages")) return s;
     if (num_stages < 0) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_set_stages: num_stages must be non-negative, got %d", num_stages);
     if (num_stages > 0 && !rounds) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_set_stages: rounds is null with num_stages %d", num_stages);
     for (int s = 0; s < num_stages; ++s) {
@@ -1566,6 +1581,7 @@ int tahoe_forest_get_staged_strategy(const tahoe_forest *f, size_t rows) { retur
 tahoe_status tahoe_forest_predict_staged(tahoe_forest *f, float *out_dev, const float *data_dev, size_t rows, void *stream)
 {
     if (!f) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_staged: null forest");
+    if (const tahoe_status s = refuse_oblivious(f, "tahoe_forest_predict_staged")) return s;
     if (!f->stages_dev)
         return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_staged: no stages are set (tahoe_forest_set_stages)");
     const int strategy = staged_strategy(f);
@@ -1623,6 +1639,7 @@ tahoe_status tahoe_forest_set_strategy(tahoe_forest *f, int strategy)
 tahoe_status tahoe_forest_reserve(tahoe_forest *f, size_t rows)
 {
     if (!f) return fail(TAHOE_ERR_INVALID_ARG, "null forest");
+    if (f->ob) return TAHOE_OK;  // an oblivious handle has no workspace: predict allocates nothing
     const tahoe_status qs = qring_reserve(f, rows);
     if (qs != TAHOE_OK) return qs;
     return widef_reserve(f, rows);  // (the wide-row float32 form's leaf-value workspace, when it streams rows)
@@ -1651,6 +1668,7 @@ int tahoe_forest_get_kernel_form(const tahoe_forest *f, size_t rows)
 {
     if (!f) return -1;
     const int strategy = resolve_strategy(f, rows);
+    if (f->ob) return strategy == TAHOE_STRATEGY_ROWTILE ? TAHOE_OBLIVIOUS_FORM_TILE : TAHOE_OBLIVIOUS_FORM_DIRECT;
     if (f->sp) {
         switch (strategy) {
         case TAHOE_STRATEGY_QRING: return TAHOE_FORM_SPARSE_QRING;
@@ -1678,7 +1696,8 @@ const char *tahoe_kernel_form_name(int form)
                                         "tilering_wide_stream", "qring_region3", "qring_region2", "qring_region_mixed",
                                         "qring_split", "qring_columns", "qring_wide", "qring_gx", "sparse_direct",
                                         "sparse_rowtile", "sparse_top", "sparse_qring", "qring_region8", "qring_region6",
-                                        "csr_rowtile", "csr_sparse_rowtile", "csr_sparse_top"};
+                                        "csr_rowtile", "csr_sparse_rowtile", "csr_sparse_top", "?" /* 23: unassigned */, "oblivious_direct",
+                                        "oblivious_tile"};
     return form >= 0 && form < (int)(sizeof(names) / sizeof(names[0])) ? names[form] : "?";
 }
 
@@ -1695,6 +1714,7 @@ tahoe_status tahoe_forest_get_info(const tahoe_forest *f, tahoe_forest_info *inf
     info->num_cus = f->num_cus;
     if (f->sp) return TAHOE_OK;
     info->depth = f->p.depth;
+    if (f->ob) return TAHOE_OK;  // (depth: the largest of the trees)
     info->lds_levels = f->lds_levels;
     info->lds_bytes_per_block = rowtile_fits(f) ? rowtile_lds_bytes(f->p.num_cols, f->lds_levels) : 0;
     info->top_levels = f->top_levels;
