@@ -444,9 +444,38 @@ typedef struct {
  * TILERING and QRING are TAHOE_ERR_UNSUPPORTED.
  * Out of scope, TAHOE_ERR_UNSUPPORTED with nothing launched and a text that says "oblivious": tahoe_forest_predict_csr,
  * _reserve_csr (and _get_csr_plan: form TAHOE_FORM_NONE), _predict_host, _set_stages, _predict_staged (_get_staged_strategy: 0),
- * the four SHAP calls and _set_background.  CatBoost's one-hot and CTR splits are not represented. */
+ * _predict_interactions, _predict_contribs_interventional and _set_background; _predict_contribs and _predict_contribs_approx
+ * unless the handle comes from tahoe_oblivious_forest_create_ex with that call's flag.  CatBoost's one-hot and CTR splits are not
+ * represented. */
 tahoe_status tahoe_oblivious_forest_create(tahoe_forest **out, const int32_t *depths, const tahoe_oblivious_split *splits,
                                            const float *leaf_values, const tahoe_forest_params *params, int leaf_dim);
+/* The same handle with explanations.  flags: a subset of TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS; with flags == 0
+ * leaf_covers is ignored and the call is tahoe_oblivious_forest_create (which is this call with NULL, 0).  leaf_covers holds
+ * sum_t 2^depths[t] floats, one per leaf in the order of the leaves: the training weight that reached the leaf (CatBoost's
+ * leaf_weights).  Checks, before a device is touched and after those of tahoe_oblivious_forest_create: another flag bit, or a flag
+ * with leaf_covers == NULL: TAHOE_ERR_INVALID_ARG; a cover that is negative, NaN or infinite: TAHOE_ERR_INVALID_FOREST naming the
+ * tree and the leaf.
+ * Covers of the implicit nodes: the float64 sum of the leaf covers below.  A node of positive cover mixes its children by
+ * w_child / (w_l + w_r); a node of cover 0 mixes them 1/2 and 1/2 (the limit of adding one epsilon to every leaf cover).  Leaves
+ * and whole subtrees of cover 0 are therefore accepted -- CatBoost models have them -- where TAHOE_CREATE_CONTRIBS on a dense or
+ * sparse handle refuses a node whose children both have cover 0.  Node means E(n) = (w_l E(l) + w_r E(r)) / (w_l + w_r), or
+ * (E(l) + E(r)) / 2 at a node of cover 0, in float64.
+ * TAHOE_CREATE_CONTRIBS: tahoe_forest_predict_contribs is served -- path-dependent TreeSHAP as defined there (predict's branch
+ * rule, repeated features merged, contributions to the margin), phi_dev rows x K x (num_cols + 1), bias last; zero fractions below
+ * 2^-121 count as 0.  With AVG every column is divided by (float)num_trees.  Bias column k = sum_t E_t[k] / (AVG ? T : 1) +
+ * global_bias in float64, rounded once (E_t[k]: the sum over the tree's leaves of value x product of the path's mixing ratios).
+ * Per (row, class, feature) the float32 sum runs from +0.0f over the trees in order and, within a tree, over the leaves in order
+ * of their index (a leaf the row weighs 0 is skipped): results do not depend on the batch or the kernel form.
+ * TAHOE_CREATE_APPROX_CONTRIBS: tahoe_forest_predict_contribs_approx is served -- Saabas contributions as defined there on the
+ * implicit heap: each child carries d = (float)(E(child) - E(n)); per tree, level 0 first, the row adds the taken child's d to
+ * phi[k][fid of the level], one float32 add per (tree, level) from +0.0f, then / (float)num_trees with AVG; the same bias column,
+ * bit for bit.  On covers whose node sums are exact in float32 it gives the bits of the heap expansion on a dense handle.
+ * Both calls allocate nothing and can be captured.  The tables count in device_bytes: 8 bytes per (leaf, distinct feature of its
+ * tree) and 4 per leaf (TreeSHAP), 4 K bytes per implicit child (Saabas).  A call whose flag the handle lacks stays
+ * TAHOE_ERR_UNSUPPORTED as above. */
+tahoe_status tahoe_oblivious_forest_create_ex(tahoe_forest **out, const int32_t *depths, const tahoe_oblivious_split *splits,
+                                              const float *leaf_values, const float *leaf_covers,
+                                              const tahoe_forest_params *params, int leaf_dim, unsigned flags);
 
 /* dense2sparse (BaseTahoeTest.h:728-764).  *nodes_out / *trees_out: tahoe_free_host. */
 tahoe_status tahoe_dense_to_sparse(const tahoe_dense_node *dense, int num_trees, int depth,

@@ -146,6 +146,7 @@ _PROTOS = {
     "tahoe_sparse_forest_create_cat": (_i, [C.POINTER(_vp), _vp, _vp, _vp, C.POINTER(ForestParams), _i, C.c_uint,
                                             C.POINTER(CategoricalSplits)]),
     "tahoe_oblivious_forest_create": (_i, [C.POINTER(_vp), _vp, _vp, _vp, C.POINTER(ForestParams), _i]),
+    "tahoe_oblivious_forest_create_ex": (_i, [C.POINTER(_vp), _vp, _vp, _vp, _vp, C.POINTER(ForestParams), _i, C.c_uint]),
     "tahoe_dense_to_sparse": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz)]),
     "tahoe_dense_to_sparse_ex": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz)]),
     "tahoe_synth_sparse_forest": (_i, [_vp, _vp, C.POINTER(_sz), _i, _i, _i, _i, _f, _i, C.c_uint64]),
@@ -791,10 +792,13 @@ class ObliviousForest(Forest):
     """tahoe_oblivious_forest_create: trees whose levels share one split each.  depths [T] (0 .. 16); fids, thresholds and
     def_left hold sum(depths) entries, tree-major, level 0 first; leaf_values holds sum(2 ** depths) * leaf_dim floats (tree,
     leaf index, then the leaf_dim values); level l sets bit l of the leaf index.  predict* as Forest, with leaf_dim > 1 in the
-    shapes of a multi-class handle ([rows, leaf_dim]); AVG divides by the number of trees."""
+    shapes of a multi-class handle ([rows, leaf_dim]); AVG divides by the number of trees.  contribs=True / approx_contribs=True
+    (tahoe_oblivious_forest_create_ex) serve predict_contribs / predict_contribs_approx and need leaf_covers: sum(2 ** depths)
+    floats, the training weight of every leaf (CatBoost's leaf_weights); zeros are allowed."""
 
     def __init__(self, depths, fids, thresholds, def_left, leaf_values, num_cols: int, leaf_dim: int = 1, missing: float = 0.0,
-                 output: int = OUT_RAW, threshold: float = 0.5, global_bias: float = 0.0):
+                 output: int = OUT_RAW, threshold: float = 0.5, global_bias: float = 0.0, leaf_covers=None, contribs: bool = False,
+                 approx_contribs: bool = False):
         depths = np.ascontiguousarray(depths, dtype=np.int32).reshape(-1)
         fids = np.asarray(fids, dtype=np.int64).reshape(-1)
         nsplits = int(depths.astype(np.int64).sum())
@@ -813,8 +817,20 @@ class ObliviousForest(Forest):
         lv = leaves if leaves.size else np.zeros(1, np.float32)
         self.params = ForestParams(0, 0, int(depths.size), num_cols, 0, output, threshold, global_bias, 0, missing)
         self._h = _vp()
-        _check(lib.tahoe_oblivious_forest_create(C.byref(self._h), dp.ctypes.data, splits.ctypes.data if nsplits else None,
-                                                 lv.ctypes.data, C.byref(self.params), leaf_dim), "tahoe_oblivious_forest_create")
+        flags = (CREATE_CONTRIBS if contribs else 0) | (CREATE_APPROX_CONTRIBS if approx_contribs else 0)
+        if flags:
+            if leaf_covers is None:
+                raise ValueError("contribs / approx_contribs need leaf_covers")
+            covers = np.ascontiguousarray(leaf_covers, dtype=np.float32).reshape(-1)
+            if covers.size * leaf_dim != leaves.size:
+                raise ValueError("leaf_covers.size != sum(2 ** depths)")
+            cv = covers if covers.size else np.zeros(1, np.float32)
+            _check(lib.tahoe_oblivious_forest_create_ex(C.byref(self._h), dp.ctypes.data, splits.ctypes.data if nsplits else None,
+                                                        lv.ctypes.data, cv.ctypes.data, C.byref(self.params), leaf_dim, flags),
+                   "tahoe_oblivious_forest_create_ex")
+        else:
+            _check(lib.tahoe_oblivious_forest_create(C.byref(self._h), dp.ctypes.data, splits.ctypes.data if nsplits else None,
+                                                     lv.ctypes.data, C.byref(self.params), leaf_dim), "tahoe_oblivious_forest_create")
         self.num_trees, self.depth, self.num_cols = int(depths.size), int(depths.max()) if depths.size else 0, num_cols
         self.num_classes = lib.tahoe_forest_num_classes(self._h)
 

@@ -875,6 +875,9 @@ extern "C" tahoe_status tahoe_forest_predict_contribs(tahoe_forest *f, float *ph
                                                       void *stream)
 {
     if (!f) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_contribs: null forest");
+    if (oblivious_serves(f, TAHOE_CREATE_CONTRIBS))
+        return oblivious_predict_shap(f, TAHOE_CREATE_CONTRIBS, phi_dev, data_dev, rows, (hipStream_t)stream,
+                                      "tahoe_forest_predict_contribs");
     if (tahoe_status st = need_path_tables(f, "tahoe_forest_predict_contribs")) return st;
     if (rows == 0) return TAHOE_OK;
     if (!phi_dev || !data_dev) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_contribs: null argument");

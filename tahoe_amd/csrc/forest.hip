@@ -1102,6 +1102,7 @@ static tahoe_knobs read_knobs()
     k.approx_form = num("TAHOE_APPROX_FORM", k.approx_form);
     k.csr_chunk_mb = num("TAHOE_CSR_CHUNK_MB", k.csr_chunk_mb);
     k.csr_fused = num("TAHOE_CSR_FUSED", k.csr_fused);
+    k.oblivious_shap_inplace = num("TAHOE_OBLIVIOUS_SHAP_INPLACE", 0) != 0;
     return k;
 }
 

@@ -80,6 +80,7 @@ struct tahoe_knobs {
     int approx_form = 0;          // TAHOE_APPROX_FORM: 1 = the LDS slab wherever one wave's slab fits, 2 = in place
     int csr_chunk_mb = 64;        // TAHOE_CSR_CHUNK_MB: cap of tahoe_forest_predict_csr's densify chunk (at least one 64-row tile)
     int csr_fused = -1;           // TAHOE_CSR_FUSED: under AUTO, 0 = never the fused CSR tile kernels, 1 = wherever one exists, -1 = the rule
+    bool oblivious_shap_inplace = false;  // TAHOE_OBLIVIOUS_SHAP_INPLACE = 1: an oblivious handle's explanations accumulate in phi_dev
 };
 
 struct tahoe_forest {
@@ -517,6 +518,11 @@ bool oblivious_tile_fits(const tahoe_forest *f);
 tahoe_status oblivious_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data, size_t rows, hipStream_t stream,
                               int strategy, const float *sums_in);
 void oblivious_destroy(tahoe_forest *f);
+// ... its explanations (oblivious_shap.hip).  oblivious_serves: was the handle created with `flag` (TAHOE_CREATE_CONTRIBS or
+// TAHOE_CREATE_APPROX_CONTRIBS)?  oblivious_predict_shap: that flag's call on such a handle, entry checks included (fn: its name)
+bool oblivious_serves(const tahoe_forest *f, unsigned flag);
+tahoe_status oblivious_predict_shap(tahoe_forest *f, unsigned flag, float *phi_dev, const float *data_dev, size_t rows,
+                                    hipStream_t stream, const char *fn);
 // The refusal of the entry points an oblivious handle does not serve (fn: the entry point's name); TAHOE_OK on every other handle
 inline tahoe_status refuse_oblivious(const tahoe_forest *f, const char *fn)
 {

@@ -18,18 +18,10 @@
 #include <type_traits>
 #include <vector>
 
-#include "forest_internal.h"
-
-struct tahoe_ostate {
-    tahoe::InnerNode *splits = nullptr;
-    int32_t *split_off = nullptr;
-    int64_t *leaf_off = nullptr;
-    float *leaves = nullptr;
-};
+#include "oblivious_internal.h"
 
 namespace tahoe {
 
-constexpr int kObMaxDepth = 16;
 constexpr int kObTrees = 4;    // consecutive trees whose leaf indices and leaf reads are in flight before they are added in order
 constexpr int kObClasses = 8;  // accumulators a lane keeps: gridDim.y runs over blocks of 8 classes, each repeats the walk
 
@@ -178,6 +170,7 @@ void oblivious_destroy(tahoe_forest *f)
 {
     tahoe_ostate *o = f->ob;
     if (!o) return;
+    oblivious_shap_destroy(f);
     if (o->splits) (void)hipFree(o->splits);
     if (o->split_off) (void)hipFree(o->split_off);
     if (o->leaf_off) (void)hipFree(o->leaf_off);
@@ -201,8 +194,10 @@ static tahoe_status oblivious_allow_lds(const tahoe_forest *f)
 
 using namespace tahoe;
 
-extern "C" tahoe_status tahoe_oblivious_forest_create(tahoe_forest **out, const int32_t *depths, const tahoe_oblivious_split *splits,
-                                                      const float *leaf_values, const tahoe_forest_params *p, int leaf_dim)
+extern "C" tahoe_status tahoe_oblivious_forest_create_ex(tahoe_forest **out, const int32_t *depths,
+                                                         const tahoe_oblivious_split *splits, const float *leaf_values,
+                                                         const float *leaf_covers, const tahoe_forest_params *p, int leaf_dim,
+                                                         unsigned flags)
 {
     // every check here runs before a device is touched
     if (!out || !depths || !leaf_values || !p) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_oblivious_forest_create: null argument");
@@ -243,6 +238,15 @@ extern "C" tahoe_status tahoe_oblivious_forest_create(tahoe_forest **out, const 
         max_depth = std::max(max_depth, depths[t]);
     }
 
+    // ... and the checks of the explanation flags, after those every create makes
+    if (flags & ~(unsigned)(TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS))
+        return fail(TAHOE_ERR_INVALID_ARG, "tahoe_oblivious_forest_create_ex: flags 0x%x: only TAHOE_CREATE_CONTRIBS and "
+                                           "TAHOE_CREATE_APPROX_CONTRIBS are served", flags);
+    if (flags && !leaf_covers)
+        return fail(TAHOE_ERR_INVALID_ARG, "tahoe_oblivious_forest_create_ex: leaf_covers is null, and the flags need the covers");
+    if (flags)
+        if (const tahoe_status s = oblivious_shap_validate(depths, T, leaf_covers)) return s;
+
     ForestPtr f;
     if (const tahoe_status s = open_handle(p, leaf_dim, f)) return s;
     f->class_trees = T;  // AVG divides by (float)num_trees whatever K is
@@ -257,6 +261,16 @@ extern "C" tahoe_status tahoe_oblivious_forest_create(tahoe_forest **out, const 
         (s = hip_status(upload(&o->leaves, leaf_values, num_leaves * (size_t)leaf_dim, &f->device_bytes), "upload(leaves)")) ||
         (s = oblivious_allow_lds(f.get())))
         return s;
+    if (flags) {
+        const ObliviousSource src{depths, &h_splits, &h_split_off, &h_leaf_off, leaf_values, leaf_covers, num_leaves};
+        if ((s = oblivious_shap_build(f.get(), src, flags))) return s;
+    }
     *out = f.release();
     return TAHOE_OK;
+}
+
+extern "C" tahoe_status tahoe_oblivious_forest_create(tahoe_forest **out, const int32_t *depths, const tahoe_oblivious_split *splits,
+                                                      const float *leaf_values, const tahoe_forest_params *p, int leaf_dim)
+{
+    return tahoe_oblivious_forest_create_ex(out, depths, splits, leaf_values, nullptr, p, leaf_dim, 0u);
 }

@@ -1,0 +1,37 @@
+// What the translation units of an oblivious handle share (oblivious.hip: create and the walk; oblivious_shap.hip: the TreeSHAP
+// and Saabas tables and kernels).  Internal: not part of the ABI.
+#pragma once
+#include "forest_internal.h"
+
+struct tahoe_oshap;  // explanation tables of a handle of tahoe_oblivious_forest_create_ex with flags, owned by oblivious_shap.hip
+
+struct tahoe_ostate {
+    tahoe::InnerNode *splits = nullptr;
+    int32_t *split_off = nullptr;
+    int64_t *leaf_off = nullptr;
+    float *leaves = nullptr;
+    tahoe_oshap *shap = nullptr;
+};
+
+namespace tahoe {
+
+constexpr int kObMaxDepth = 16;
+
+// The caller's forest as the creates have checked it, for the table builds: h_splits holds {thr, fid | def_left << 31}
+struct ObliviousSource {
+    const int32_t *depths;
+    const std::vector<InnerNode> *h_splits;
+    const std::vector<int32_t> *h_split_off;
+    const std::vector<int64_t> *h_leaf_off;
+    const float *leaf_values;
+    const float *leaf_covers;
+    size_t num_leaves;
+};
+
+// TAHOE_ERR_INVALID_FOREST unless every leaf cover is finite and >= 0 (no device touched)
+tahoe_status oblivious_shap_validate(const int32_t *depths, int num_trees, const float *leaf_covers);
+// The tables `flags` (TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS) ask for, on the handle's device
+tahoe_status oblivious_shap_build(tahoe_forest *f, const ObliviousSource &src, unsigned flags);
+void oblivious_shap_destroy(tahoe_forest *f);
+
+}  // namespace tahoe

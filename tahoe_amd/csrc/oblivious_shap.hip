@@ -1,0 +1,538 @@
+// TreeSHAP and Saabas contributions on an oblivious handle (tahoe_oblivious_forest_create_ex with TAHOE_CREATE_CONTRIBS /
+// TAHOE_CREATE_APPROX_CONTRIBS).
+//
+// Every leaf of an oblivious tree tests the same m <= D distinct features in the same order, the cover ratios of a leaf's path
+// depend on (tree, leaf) alone, and a row follows the path's element of feature e exactly when its leaf index idx and the leaf j
+// agree on that feature's levels: ((idx ^ j) & mask_e) == 0.  Both kernels are lane = row: one wave owns 64 rows, reads every
+// table at wave-uniform addresses (scalar loads), and exchanges nothing between lanes.
+//
+// Tables, built once at create from the leaf covers (float64 on the host):
+//   splits[sum D_t]       {thr, id | def_left << 31}; id = the feature's compact id over the features the forest uses (LDS form)
+//                         or its column (in-place form)
+//   used[U]               column of compact id c, ascending
+//   elems[sum m_t]        {id, level mask} of tree t's distinct features in order of first appearance from level 0
+//   zz[sum 2^D_t m_t]     {z, 1 - z} of (tree, leaf, element): z = the product of the cover ratios on the leaf's path over the
+//                         element's levels, float64 rounded once (below kContribMinZ: 0), 1 - z from float64 beside it
+//   zmask[sum 2^D_t]      the level masks of the leaf's elements with z == 0: a row that leaves the path there weighs the leaf 0
+//   delta[sum 2 (2^D_t - 1)][K]  Saabas: (float)(E(child) - E(parent)) of the implicit heap's children, level by level
+//   bias[K]               the bias column; div = (float)T with TAHOE_OUT_AVG, else 1
+//
+// Accumulators: a lane's (class, feature) sums live in its own row of an LDS slab of odd stride (conflict-free both when the 64
+// lanes add to one feature and when they write whole rows out), or, where the row tile and the slab do not fit the LDS, in the
+// lane's own row of phi_dev.  Classes run in blocks of kObShapClasses over gridDim.y.
+//
+// Sum order, in every form and for any batch: phi[row][k][f] is the float32 sum from +0.0f, trees ascending, within a tree the
+// leaves ascending that the row weighs (TreeSHAP; a leaf the row weighs 0 adds nothing) or the levels ascending (Saabas); then
+// one division by div.  No atomics.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <new>
+#include <vector>
+
+#include "contribs_internal.h"
+#include "oblivious_internal.h"
+
+namespace tahoe {
+
+constexpr int kObShapClasses = 4;  // classes of one grid.y block: 16 x 4 accumulators in VGPRs at m = 16, (1 + 4) U x 256 B of LDS
+
+// What the kernels read, by value in the kernel arguments
+struct ObShapView {
+    const InnerNode *splits;
+    const int32_t *split_off;
+    const int64_t *leaf_off;
+    const float *leaves;
+    const int32_t *used;
+    const uint2 *elems;
+    const int32_t *elem_off;
+    const float2 *zz;
+    const int64_t *zz_off;
+    const uint32_t *zmask;
+    const float *delta;
+    const float *bias;
+    float div, missing;
+    int F, K, T, U, S;  // columns, leaf dimension, trees, used features, floats per slab row (odd)
+};
+
+}  // namespace tahoe
+
+struct tahoe_oshap {
+    tahoe::InnerNode *splits = nullptr;
+    int32_t *used = nullptr;
+    uint2 *elems = nullptr;
+    int32_t *elem_off = nullptr;
+    float2 *zz = nullptr;
+    int64_t *zz_off = nullptr;
+    uint32_t *zmask = nullptr;
+    float *delta = nullptr;
+    float *bias = nullptr;
+    bool contribs = false, approx = false;
+    bool inplace = false;  // accumulate in phi_dev (else in LDS)
+    size_t lds_bytes = 0;
+    tahoe::ObShapView view{};
+};
+
+namespace tahoe {
+
+// One wave's 64 rows and their accumulators for the classes [k0, k0 + kb) of this grid.y block
+template <int KB, bool INPLACE>
+struct ObShapRows {
+    int lane, nr, k0, kb;
+    size_t row0, F1, out_row;
+    bool row_ok;
+    const float *x;  // INPLACE: the lane's row
+    float *tile;     // else the 64 rows' used features, [U][64]
+    float *slab;     // ... and the accumulators, [64][S]
+    float *acc;      // the lane's accumulator of (class k0 + k, id) is acc[k * kstride + id]
+    size_t kstride;
+    __device__ __forceinline__ float feature(uint32_t id) const { return INPLACE ? x[id] : tile[id * 64u + (uint32_t)lane]; }
+    __device__ __forceinline__ float load(int k, uint32_t id) const
+    {
+        return (!INPLACE || row_ok) ? acc[(size_t)k * kstride + id] : 0.0f;
+    }
+    __device__ __forceinline__ void store(int k, uint32_t id, float v) const
+    {
+        if (!INPLACE || row_ok) acc[(size_t)k * kstride + id] = v;
+    }
+};
+
+// Zeroes the block's part of phi (every column: the ones no tree uses stay 0), stages the row tile and zeroes the slab
+template <int KB, bool INPLACE>
+__device__ __forceinline__ ObShapRows<KB, INPLACE> ob_shap_begin(const ObShapView &v, float *__restrict__ phi,
+                                                                 const float *__restrict__ data, size_t rows, float *smem)
+{
+    ObShapRows<KB, INPLACE> r;
+    r.lane = (int)threadIdx.x;
+    r.row0 = (size_t)blockIdx.x * 64;
+    const size_t row = r.row0 + (size_t)r.lane;
+    r.row_ok = row < rows;
+    r.nr = (int)std::min<size_t>(64, rows - r.row0);
+    r.k0 = (int)blockIdx.y * KB;
+    r.kb = std::min(KB, v.K - r.k0);
+    r.F1 = (size_t)v.F + 1;
+    r.out_row = (size_t)v.K * r.F1;
+    for (int q = 0; q < r.nr; ++q)
+        for (int k = 0; k < r.kb; ++k) {
+            float *o = phi + (r.row0 + (size_t)q) * r.out_row + (size_t)(r.k0 + k) * r.F1;
+            for (int i = r.lane; i < v.F; i += 64) o[i] = 0.0f;
+        }
+    const size_t my = r.row_ok ? row : r.row0;  // (a lane past the batch works on the tile's first row and stores nothing)
+    const float *src = data + my * (size_t)v.F;
+    r.x = src;
+    r.tile = smem;
+    r.slab = smem + (size_t)v.U * 64;
+    if (INPLACE) {
+        r.acc = phi + my * r.out_row + (size_t)r.k0 * r.F1;
+        r.kstride = r.F1;
+    } else {
+        for (int c = 0; c < v.U; ++c) r.tile[c * 64 + r.lane] = src[v.used[c]];
+        r.acc = r.slab + (size_t)r.lane * (size_t)v.S;
+        r.kstride = (size_t)v.U;
+        for (int i = 0; i < r.kb * v.U; ++i) r.acc[i] = 0.0f;
+    }
+    __syncthreads();  // the zeroes land before any lane adds to its row or writes a used column
+    return r;
+}
+
+// The used columns of every row out (the AVG division) and the bias column
+template <int KB, bool INPLACE>
+__device__ __forceinline__ void ob_shap_end(const ObShapView &v, const ObShapRows<KB, INPLACE> &r, float *__restrict__ phi)
+{
+    __syncthreads();
+    for (int q = 0; q < r.nr; ++q)
+        for (int k = 0; k < r.kb; ++k) {
+            float *o = phi + (r.row0 + (size_t)q) * r.out_row + (size_t)(r.k0 + k) * r.F1;
+            const float *s = r.slab + (size_t)q * (size_t)v.S + (size_t)k * (size_t)v.U;
+            for (int c = r.lane; c < v.U; c += 64) {
+                const int fid = v.used[c];
+                const float sum = INPLACE ? o[fid] : s[c];
+                o[fid] = sum / v.div;
+            }
+            if (r.lane == 0) o[v.F] = v.bias[r.k0 + k];
+        }
+}
+
+// The row's leaf index of tree t (level 0 = bit 0), as oblivious_walk computes it; each(l, id, idx) after level l's bit is in
+template <class Rows, class Each>
+__device__ __forceinline__ uint32_t ob_shap_leaf_index(const ObShapView &v, const Rows &r, int t, Each &&each)
+{
+    const int s0 = v.split_off[t];
+    const int d = v.split_off[t + 1] - s0;
+    uint32_t idx = 0;
+    for (int l = 0; l < d; ++l) {
+        const InnerNode n = v.splits[s0 + l];
+        const uint32_t id = n.meta & kMetaFidMask;
+        idx |= go_right_meta(r.feature(id), n.thr, n.meta, v.missing) << l;
+        each(l, id, idx);
+    }
+    return idx;
+}
+
+// One tree of M distinct features: the running sums of its features come into VGPRs, take the terms of the leaves in order, and
+// go back.  pw[] is indexed by unrolled loops only, so it stays in registers.  Per leaf, with z_e and o_e in {0, 1} of element e:
+//   EXTEND over the M elements (Lundberg et al. 2018, Algorithm 2), then per element the unwound sum:
+//     o_e = 1: the recurrence over pw with z_e;  the term is sum (1 - z_e) leaf
+//     o_e = 0: sum = S0 / z_e with S0 = sum_i pw[i] (M + 1) / (M - i) the same for every element, so the term sum (0 - z_e) leaf
+//              is -S0 leaf and the division is never made
+//   A leaf with z_e == 0 and o_e == 0 for some e has path weight 0 and is skipped (by the wave when no lane weighs it).
+template <int M, int KB, bool INPLACE>
+__device__ __forceinline__ void ob_shap_tree(const ObShapRows<KB, INPLACE> &r, const uint2 *__restrict__ el,
+                                             const float2 *__restrict__ zz, const uint32_t *__restrict__ zmask,
+                                             const float *__restrict__ lv, int nleaf, uint32_t idx, int K)
+{
+    uint32_t id[M], mask[M];
+    float a[M][KB];
+#pragma unroll
+    for (int e = 0; e < M; ++e) {
+        id[e] = el[e].x;
+        mask[e] = el[e].y;
+#pragma unroll
+        for (int k = 0; k < KB; ++k) a[e][k] = (KB == 1 || k < r.kb) ? r.load(k, id[e]) : 0.0f;
+    }
+    for (int j = 0; j < nleaf; ++j) {
+        const uint32_t mism = idx ^ (uint32_t)j;
+        const bool live = (mism & zmask[j]) == 0u;
+        if (__ballot(live) == 0ull) continue;
+        const float2 *zj = zz + (size_t)j * M;
+        float pw[M + 1], z[M], omz[M];
+        bool o[M];
+        pw[0] = 1.0f;
+#pragma unroll
+        for (int e = 0; e < M; ++e) {
+            const int l = e + 1;
+            const float2 zo = zj[e];
+            z[e] = zo.x;
+            omz[e] = zo.y;
+            o[e] = (mism & mask[e]) == 0u;
+            pw[l] = 0.0f;
+#pragma unroll
+            for (int i = l - 1; i >= 0; --i) {
+                const float t = pw[i] * (float)((double)(i + 1) / (double)(l + 1));
+                pw[i + 1] = pw[i + 1] + (o[e] ? t : 0.0f);
+                pw[i] = pw[i] * (z[e] * (float)((double)(l - i) / (double)(l + 1)));
+            }
+        }
+        float s0 = 0.0f;
+#pragma unroll
+        for (int i = 0; i < M; ++i) s0 = s0 + pw[i] * (float)((double)(M + 1) / (double)(M - i));
+        const float *lj = lv + (size_t)j * (size_t)K;
+#pragma unroll
+        for (int e = 0; e < M; ++e) {
+            float nxt = pw[M], tot = 0.0f;
+#pragma unroll
+            for (int i = M - 1; i >= 0; --i) {
+                const float tmp = nxt * (float)((double)(M + 1) / (double)(i + 1));
+                tot = tot + tmp;
+                if (i > 0) nxt = pw[i] - tmp * (z[e] * (float)((double)(M - i) / (double)(M + 1)));
+            }
+            const float w = o[e] ? tot * omz[e] : -s0;
+#pragma unroll
+            for (int k = 0; k < KB; ++k) {
+                const float leaf = (KB == 1 || k < r.kb) ? lj[k] : 0.0f;
+                const float sum = a[e][k] + w * leaf;
+                a[e][k] = live ? sum : a[e][k];
+            }
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < M; ++e)
+#pragma unroll
+        for (int k = 0; k < KB; ++k)
+            if (KB == 1 || k < r.kb) r.store(k, id[e], a[e][k]);
+}
+
+// TreeSHAP: grid (row tiles, class blocks), one wave per workgroup.  Dynamic LDS (not INPLACE): [U][64] tile | [64][S] slab.
+template <int KB, bool INPLACE>
+__global__ void __launch_bounds__(64) oblivious_shap_kernel(const ObShapView v, float *__restrict__ phi,
+                                                            const float *__restrict__ data, size_t rows)
+{
+    extern __shared__ __attribute__((aligned(16))) float ob_shap_smem[];
+    const ObShapRows<KB, INPLACE> r = ob_shap_begin<KB, INPLACE>(v, phi, data, rows, ob_shap_smem);
+    for (int t = 0; t < v.T; ++t) {
+        const int e0 = v.elem_off[t];
+        const int m = v.elem_off[t + 1] - e0;  // wave-uniform, as everything read below
+        if (m == 0) continue;                  // a single leaf: all of it is bias
+        const uint32_t idx = ob_shap_leaf_index(v, r, t, [](int, uint32_t, uint32_t) {});
+        const int nleaf = 1 << (v.split_off[t + 1] - v.split_off[t]);
+        const uint2 *el = v.elems + e0;
+        const float2 *zz = v.zz + v.zz_off[t];
+        const uint32_t *zm = v.zmask + v.leaf_off[t];
+        const float *lv = v.leaves + (size_t)v.leaf_off[t] * (size_t)v.K + r.k0;
+        switch (m) {
+#define TAHOE_OB_SHAP_CASE(M) \
+    case M: ob_shap_tree<M, KB, INPLACE>(r, el, zz, zm, lv, nleaf, idx, v.K); break;
+            TAHOE_OB_SHAP_CASE(1) TAHOE_OB_SHAP_CASE(2) TAHOE_OB_SHAP_CASE(3) TAHOE_OB_SHAP_CASE(4)
+            TAHOE_OB_SHAP_CASE(5) TAHOE_OB_SHAP_CASE(6) TAHOE_OB_SHAP_CASE(7) TAHOE_OB_SHAP_CASE(8)
+            TAHOE_OB_SHAP_CASE(9) TAHOE_OB_SHAP_CASE(10) TAHOE_OB_SHAP_CASE(11) TAHOE_OB_SHAP_CASE(12)
+            TAHOE_OB_SHAP_CASE(13) TAHOE_OB_SHAP_CASE(14) TAHOE_OB_SHAP_CASE(15) TAHOE_OB_SHAP_CASE(16)
+#undef TAHOE_OB_SHAP_CASE
+        default: break;
+        }
+    }
+    ob_shap_end<KB, INPLACE>(v, r, phi);
+}
+
+// Saabas: the walk of oblivious_walk with one add per level -- the taken child's delta to the level's feature
+template <int KB, bool INPLACE>
+__global__ void __launch_bounds__(64) oblivious_approx_kernel(const ObShapView v, float *__restrict__ phi,
+                                                              const float *__restrict__ data, size_t rows)
+{
+    extern __shared__ __attribute__((aligned(16))) float ob_shap_smem[];
+    const ObShapRows<KB, INPLACE> r = ob_shap_begin<KB, INPLACE>(v, phi, data, rows, ob_shap_smem);
+    for (int t = 0; t < v.T; ++t) {
+        // children of level l start at 2^(l + 1) - 2 of the tree's deltas; the child's index is the leaf index so far
+        const float *dt = v.delta + (size_t)(2 * (v.leaf_off[t] - t)) * (size_t)v.K + r.k0;
+        ob_shap_leaf_index(v, r, t, [&](int l, uint32_t id, uint32_t idx) {
+            const float *d = dt + (size_t)((2u << l) - 2u + idx) * (size_t)v.K;
+#pragma unroll
+            for (int k = 0; k < KB; ++k)
+                if (KB == 1 || k < r.kb) r.store(k, id, r.load(k, id) + d[k]);
+        });
+    }
+    ob_shap_end<KB, INPLACE>(v, r, phi);
+}
+
+tahoe_status oblivious_shap_validate(const int32_t *depths, int num_trees, const float *leaf_covers)
+{
+    size_t at = 0;
+    for (int t = 0; t < num_trees; ++t) {
+        const size_t n = (size_t)1 << depths[t];
+        for (size_t j = 0; j < n; ++j) {
+            const float c = leaf_covers[at + j];
+            if (!(c >= 0.0f) || std::isinf(c))
+                return fail(TAHOE_ERR_INVALID_FOREST, "tahoe_oblivious_forest_create_ex: tree %d leaf %zu: cover %g is negative or "
+                                                      "not finite", t, j, (double)c);
+        }
+        at += n;
+    }
+    return TAHOE_OK;
+}
+
+namespace {
+
+// The cover ratios of one tree's implicit heap.  Level l has 2^l nodes, numbered by the l low bits of the leaf index (the
+// decisions of levels 0 .. l - 1); the children of node p of level l are p (left) and p | 1 << l (right) of level l + 1.
+struct ObHeap {
+    int D = 0;
+    std::vector<std::vector<double>> cover;  // [l][node]: float64 sum of the leaf covers below
+    std::vector<std::vector<double>> ratio;  // [l][node], l >= 1: the share of its parent's mix; 1/2 under a node of cover 0
+    void build(int depth, const float *leaf_covers)
+    {
+        D = depth;
+        cover.assign((size_t)D + 1, {});
+        ratio.assign((size_t)D + 1, {});
+        cover[(size_t)D].assign(leaf_covers, leaf_covers + ((size_t)1 << D));
+        for (int l = D - 1; l >= 0; --l) {
+            const size_t n = (size_t)1 << l;
+            cover[(size_t)l].resize(n);
+            ratio[(size_t)l + 1].resize(2 * n);
+            for (size_t p = 0; p < n; ++p) {
+                const double wl = cover[(size_t)l + 1][p], wr = cover[(size_t)l + 1][p | n];
+                cover[(size_t)l][p] = wl + wr;
+                ratio[(size_t)l + 1][p] = wl + wr > 0.0 ? wl / (wl + wr) : 0.5;
+                ratio[(size_t)l + 1][p | n] = wl + wr > 0.0 ? wr / (wl + wr) : 0.5;
+            }
+        }
+    }
+};
+
+uint32_t bit_reverse(uint32_t p, int d)
+{
+    uint32_t r = 0;
+    for (int b = 0; b < d; ++b) r |= ((p >> b) & 1u) << (d - 1 - b);
+    return r;
+}
+
+}  // namespace
+
+tahoe_status oblivious_shap_build(tahoe_forest *f, const ObliviousSource &src, unsigned flags)
+{
+    tahoe_ostate *o = f->ob;
+    tahoe_oshap *sh = new (std::nothrow) tahoe_oshap();
+    if (!sh) return fail(TAHOE_ERR_NO_MEMORY, "oblivious_shap_build");
+    o->shap = sh;
+    sh->contribs = (flags & TAHOE_CREATE_CONTRIBS) != 0;
+    sh->approx = (flags & TAHOE_CREATE_APPROX_CONTRIBS) != 0;
+    const int T = f->p.num_trees, K = f->num_classes, F = f->p.num_cols;
+    const std::vector<InnerNode> &splits = *src.h_splits;
+    const std::vector<int32_t> &split_off = *src.h_split_off;
+    const std::vector<int64_t> &leaf_off = *src.h_leaf_off;
+
+    // ---- the features the forest uses, and the form ----
+    std::vector<int32_t> used;
+    used.reserve(splits.size());
+    for (const InnerNode &n : splits) used.push_back((int32_t)(n.meta & kMetaFidMask));
+    std::sort(used.begin(), used.end());
+    used.erase(std::unique(used.begin(), used.end()), used.end());
+    const int U = (int)used.size();
+    const int S = (std::min(K, kObShapClasses) * U) | 1;
+    sh->lds_bytes = ((size_t)U + (size_t)S) * 64 * sizeof(float);
+    sh->inplace = sh->lds_bytes > (size_t)f->lds_limit || f->knobs.oblivious_shap_inplace;  // TAHOE_OBLIVIOUS_SHAP_INPLACE
+    if (sh->inplace) sh->lds_bytes = 0;
+    auto id_of = [&](uint32_t fid) {
+        return sh->inplace ? fid : (uint32_t)(std::lower_bound(used.begin(), used.end(), (int32_t)fid) - used.begin());
+    };
+    std::vector<InnerNode> h_splits(splits.size());
+    for (size_t s = 0; s < splits.size(); ++s)
+        h_splits[s] = InnerNode{splits[s].thr, id_of(splits[s].meta & kMetaFidMask) | (splits[s].meta & (1u << 31))};
+
+    // ---- per tree: elements, zero fractions, deltas, E_t ----
+    std::vector<uint2> h_elems;
+    std::vector<int32_t> h_elem_off((size_t)T + 1, 0);
+    std::vector<float2> h_zz;
+    std::vector<int64_t> h_zz_off((size_t)T, 0);
+    std::vector<uint32_t> h_zmask(sh->contribs ? src.num_leaves : 0, 0u);
+    std::vector<float> h_delta(sh->approx ? 2 * (src.num_leaves - (size_t)T) * (size_t)K : 0, 0.0f);
+    std::vector<double> bias_sum((size_t)K, 0.0);
+    ObHeap heap;
+    std::vector<std::vector<double>> E;  // node means of one class, [l][node]
+    std::vector<double> prod, next;
+    for (int t = 0; t < T; ++t) {
+        const int D = src.depths[t];
+        const size_t nleaf = (size_t)1 << D, lo = (size_t)leaf_off[(size_t)t];
+        const InnerNode *ts = splits.data() + split_off[(size_t)t];
+        heap.build(D, src.leaf_covers + lo);
+        // E_t[k]: the leaves in heap order left to right (the leaf at heap position h is leaf bit_reverse(h)), each times the
+        // product of its path's ratios multiplied root first -- tree_expect's sum on the heap expansion, operation for operation
+        prod.assign(1, 1.0);
+        for (int l = 0; l < D; ++l) {
+            next.resize((size_t)2 << l);
+            for (size_t q = 0; q < next.size(); ++q) next[q] = prod[q & (((size_t)1 << l) - 1)] * heap.ratio[(size_t)l + 1][q];
+            prod.swap(next);
+        }
+        for (int k = 0; k < K; ++k) {
+            double e = 0.0;
+            for (size_t h = 0; h < nleaf; ++h) {
+                const size_t j = bit_reverse((uint32_t)h, D);
+                e += (double)src.leaf_values[(lo + j) * (size_t)K + (size_t)k] * prod[j];
+            }
+            bias_sum[(size_t)k] += e;
+        }
+        if (sh->approx) {
+            float *dt = h_delta.data() + 2 * (lo - (size_t)t) * (size_t)K;
+            E.resize((size_t)D + 1);
+            for (int k = 0; k < K; ++k) {
+                E[(size_t)D].resize(nleaf);
+                for (size_t j = 0; j < nleaf; ++j) E[(size_t)D][j] = (double)src.leaf_values[(lo + j) * (size_t)K + (size_t)k];
+                for (int l = D - 1; l >= 0; --l) {
+                    const size_t n = (size_t)1 << l;
+                    E[(size_t)l].resize(n);
+                    for (size_t p = 0; p < n; ++p) {
+                        const double wl = heap.cover[(size_t)l + 1][p], wr = heap.cover[(size_t)l + 1][p | n];
+                        const double el = E[(size_t)l + 1][p], er = E[(size_t)l + 1][p | n];
+                        const double e = wl + wr > 0.0 ? (wl * el + wr * er) / (wl + wr) : (el + er) / 2.0;
+                        E[(size_t)l][p] = e;
+                        dt[(2 * n - 2 + p) * (size_t)K + (size_t)k] = (float)(el - e);
+                        dt[(2 * n - 2 + (p | n)) * (size_t)K + (size_t)k] = (float)(er - e);
+                    }
+                }
+            }
+        }
+        if (sh->contribs) {
+            uint32_t fid[kObMaxDepth], mask[kObMaxDepth];
+            int m = 0;
+            for (int l = 0; l < D; ++l) {
+                const uint32_t fl = ts[l].meta & kMetaFidMask;
+                int e = 0;
+                while (e < m && fid[e] != fl) ++e;
+                if (e == m) {
+                    fid[m] = fl;
+                    mask[m++] = 0u;
+                }
+                mask[e] |= 1u << l;
+            }
+            for (int e = 0; e < m; ++e) h_elems.push_back(make_uint2(id_of(fid[e]), mask[e]));
+            h_zz_off[(size_t)t] = (int64_t)h_zz.size();
+            for (size_t j = 0; j < nleaf; ++j) {
+                uint32_t zm = 0u;
+                for (int e = 0; e < m; ++e) {
+                    double z = 1.0;
+                    for (int l = 0; l < D; ++l)
+                        if (mask[e] >> l & 1u) z *= heap.ratio[(size_t)l + 1][j & (((size_t)2 << l) - 1)];
+                    const float zf = z < kContribMinZ ? 0.0f : (float)z;  // the cut of contribs.hip's path tables
+                    if (zf == 0.0f) zm |= mask[e];
+                    h_zz.push_back(make_float2(zf, (float)(1.0 - z)));
+                }
+                h_zmask[lo + j] = zm;
+            }
+        }
+        h_elem_off[(size_t)t + 1] = (int32_t)h_elems.size();
+    }
+    const bool avg = (f->p.output & TAHOE_OUT_AVG) != 0 && T > 0;
+    std::vector<float> h_bias((size_t)K);
+    for (int k = 0; k < K; ++k)
+        h_bias[(size_t)k] = (float)((avg ? bias_sum[(size_t)k] / (double)T : bias_sum[(size_t)k]) + (double)f->p.global_bias);
+
+    tahoe_status s = TAHOE_OK;
+    if ((s = hip_status(upload(&sh->splits, h_splits, &f->device_bytes), "upload(shap splits)")) ||
+        (s = hip_status(upload(&sh->used, used, &f->device_bytes), "upload(used)")) ||
+        (s = hip_status(upload(&sh->elems, h_elems, &f->device_bytes), "upload(elems)")) ||
+        (s = hip_status(upload(&sh->elem_off, h_elem_off, &f->device_bytes), "upload(elem_off)")) ||
+        (s = hip_status(upload(&sh->zz, h_zz, &f->device_bytes), "upload(zz)")) ||
+        (s = hip_status(upload(&sh->zz_off, h_zz_off, &f->device_bytes), "upload(zz_off)")) ||
+        (s = hip_status(upload(&sh->zmask, h_zmask, &f->device_bytes), "upload(zmask)")) ||
+        (s = hip_status(upload(&sh->delta, h_delta, &f->device_bytes), "upload(delta)")) ||
+        (s = hip_status(upload(&sh->bias, h_bias, &f->device_bytes), "upload(bias)")))
+        return s;
+    sh->view = ObShapView{sh->splits, o->split_off, o->leaf_off, o->leaves, sh->used, sh->elems, sh->elem_off, sh->zz, sh->zz_off,
+                          sh->zmask, sh->delta, sh->bias, avg ? (float)T : 1.0f, f->p.missing, F, K, T, U, S};
+    if (!sh->inplace) {  // the LDS forms may need more than the default 64 KiB
+        hipError_t e = hipSuccess;
+        if ((e = allow_max_lds(reinterpret_cast<const void *>(&oblivious_shap_kernel<1, false>), f->lds_limit)) != hipSuccess ||
+            (e = allow_max_lds(reinterpret_cast<const void *>(&oblivious_shap_kernel<kObShapClasses, false>), f->lds_limit)) != hipSuccess ||
+            (e = allow_max_lds(reinterpret_cast<const void *>(&oblivious_approx_kernel<1, false>), f->lds_limit)) != hipSuccess ||
+            (e = allow_max_lds(reinterpret_cast<const void *>(&oblivious_approx_kernel<kObShapClasses, false>), f->lds_limit)) != hipSuccess)
+            return hip_status(e, "hipFuncSetAttribute(oblivious_shap)");
+    }
+    return TAHOE_OK;
+}
+
+void oblivious_shap_destroy(tahoe_forest *f)
+{
+    tahoe_oshap *sh = f->ob ? f->ob->shap : nullptr;
+    if (!sh) return;
+    for (void *p : {(void *)sh->splits, (void *)sh->used, (void *)sh->elems, (void *)sh->elem_off, (void *)sh->zz, (void *)sh->zz_off,
+                    (void *)sh->zmask, (void *)sh->delta, (void *)sh->bias})
+        if (p) (void)hipFree(p);
+    delete sh;
+    f->ob->shap = nullptr;
+}
+
+bool oblivious_serves(const tahoe_forest *f, unsigned flag)
+{
+    const tahoe_oshap *sh = f->ob ? f->ob->shap : nullptr;
+    return sh && (flag == TAHOE_CREATE_CONTRIBS ? sh->contribs : sh->approx);
+}
+
+tahoe_status oblivious_predict_shap(tahoe_forest *f, unsigned flag, float *phi_dev, const float *data_dev, size_t rows,
+                                    hipStream_t stream, const char *fn)
+{
+    if (rows == 0) return TAHOE_OK;
+    if (!phi_dev || !data_dev) return fail(TAHOE_ERR_INVALID_ARG, "%s: null argument", fn);
+    if (const tahoe_status st = check_shap_out(f, rows, 1, fn)) return st;
+    const tahoe_oshap *sh = f->ob->shap;
+    DeviceGuard on_device(f->device);
+    const int K = f->num_classes;
+    const dim3 grid((unsigned)((rows + 63) / 64), (unsigned)((K + kObShapClasses - 1) / kObShapClasses));
+    auto launch = [&](auto kb, auto inplace) {
+        constexpr int KB = decltype(kb)::value;
+        constexpr bool IP = decltype(inplace)::value;
+        if (flag == TAHOE_CREATE_CONTRIBS)
+            hipLaunchKernelGGL((oblivious_shap_kernel<KB, IP>), grid, dim3(64), sh->lds_bytes, stream, sh->view, phi_dev, data_dev, rows);
+        else
+            hipLaunchKernelGGL((oblivious_approx_kernel<KB, IP>), grid, dim3(64), sh->lds_bytes, stream, sh->view, phi_dev, data_dev,
+                               rows);
+    };
+    auto with_form = [&](auto kb) {
+        if (sh->inplace) launch(kb, std::true_type{});
+        else launch(kb, std::false_type{});
+    };
+    if (K == 1) with_form(std::integral_constant<int, 1>{});
+    else with_form(std::integral_constant<int, kObShapClasses>{});
+    TAHOE_HIP_TRY(hipGetLastError());
+    return TAHOE_OK;
+}
+
+}  // namespace tahoe
