@@ -11,6 +11,7 @@ cover mixes its children by w_child / (w_l + w_r), a node of cover 0 by 1/2 and 
 - brute: Shapley values from the definition, v(S) = E[f(x) | x_S], over the subsets of the features a tree uses (<= 8).
 - poly: per leaf j the EXTEND / unwound-sum recursion over the tree's m distinct features, o_e = ((idx ^ j) & mask_e) == 0, a leaf
   with z_e == 0 and o_e == 0 for some e skipped; also A = the sum of |per-leaf terms| and N = their count, per output.
+- emulate: the kernel's tables and its per-leaf recursion restated operation for operation in float32: bit-exact by construction.
 - saabas: float64 node means, float32 deltas, one float32 add per (tree, level) in order: bit-exact by construction.
 - expand_with_covers: the heap expansion (oblivious_ref.expand_to_dense) with `weight` = the subtree cover.
 - shap_form: the rule by which the library picks the LDS or the in-place form."""
@@ -219,6 +220,88 @@ def poly(forest, covers, data, missing=obr.MISSING, avg=False, global_bias=0.0):
     return phi, A, N
 
 
+def shap_tables(D, fids, ratio):
+    """-> (feats, masks, Z): a tree's elements in order of first appearance from level 0, their level masks, and Z[m, leaves] =
+    the float64 product of the leaf's path ratios over each element's levels, levels ascending (oblivious_shap_build's zz)"""
+    feats, masks = [], []
+    for l in range(D):
+        f = int(fids[l])
+        if f not in feats:
+            feats.append(f)
+            masks.append(0)
+        masks[feats.index(f)] |= 1 << l
+    j = np.arange(1 << D)
+    Z = np.ones((len(feats), 1 << D))
+    for e, mask in enumerate(masks):
+        for l in range(D):
+            if mask >> l & 1:
+                Z[e] = Z[e] * ratio[l + 1][j & ((2 << l) - 1)]
+    return feats, masks, Z
+
+
+def emulate(forest, covers, data, missing=obr.MISSING, avg=False, global_bias=0.0):
+    """-> phi [rows, K, F + 1] float32: oblivious_shap_build's tables and ob_shap_tree (oblivious_shap.hip) restated operation for
+    operation in np.float32, from the file's header comment and the kernel's loops: the bits of predict_contribs, not a bound.
+    Every coefficient is a float64 quotient rounded once; every product and sum below is one float32 operation (the library
+    is built without contraction), in the kernel's order."""
+    f32 = np.float32
+    data = np.ascontiguousarray(data, f32)
+    rows, k, F = data.shape[0], forest["k"], forest["cols"]
+    acc = np.zeros((rows, k, F + 1), f32)  # one accumulator per (row, class, column), from +0.0f through all trees in order
+    with np.errstate(all="ignore"):
+        for t, D, fids, sl, lv, cv in _trees(forest, covers):
+            _, ratio = heap(D, cv)
+            feats, masks, Z = shap_tables(D, fids, ratio)
+            M, nleaf = len(feats), 1 << D
+            if M == 0:
+                continue
+            zf = np.where(Z < MIN_Z, 0.0, Z).astype(f32)  # [M, leaves]
+            omz = (1.0 - Z).astype(f32)
+            zmask = np.zeros(nleaf, np.int64)
+            for e in range(M):
+                zmask |= np.where(zf[e] == 0, masks[e], 0)
+            right = _bits(forest, sl, data, missing)
+            idx = np.zeros(rows, np.int64)
+            for l in range(D):
+                idx |= right[l].astype(np.int64) << l
+            mism = idx[None, :] ^ np.arange(nleaf)[:, None]  # [leaves, rows]
+            live = (mism & zmask[:, None]) == 0
+            O = [(mism & masks[e]) == 0 for e in range(M)]
+            zero = np.zeros((nleaf, rows), f32)
+            pw = [np.ones((nleaf, rows), f32)]
+            for e in range(M):  # EXTEND
+                l = e + 1
+                pw.append(zero.copy())
+                for i in range(l - 1, -1, -1):
+                    tt = pw[i] * f32((i + 1) / (l + 1))
+                    pw[i + 1] = pw[i + 1] + np.where(O[e], tt, zero)
+                    pw[i] = pw[i] * (zf[e] * f32((l - i) / (l + 1)))[:, None]
+            s0 = zero.copy()
+            for i in range(M):
+                s0 = s0 + pw[i] * f32((M + 1) / (M - i))
+            leaf = np.ascontiguousarray(lv, f32)  # [leaves, K]
+            for e in range(M):
+                nxt, tot = pw[M], zero.copy()
+                for i in range(M - 1, -1, -1):
+                    tmp = nxt * f32((M + 1) / (i + 1))
+                    tot = tot + tmp
+                    if i > 0:
+                        nxt = pw[i] - tmp * (zf[e] * f32((M - i) / (M + 1)))[:, None]
+                w = np.where(O[e], tot * omz[e][:, None], -s0)
+                # The ordered sum stays sequential: np.add.accumulate adds the leaves' terms one by one, ascending, onto the
+                # running sum.  A leaf the row does not weigh (not live) adds +0.0f in place of being skipped, which gives the
+                # same bits: the accumulator starts at +0.0f, a float32 sum is -0.0f only when both its operands are, so it
+                # never becomes -0.0f, and x + 0.0f == x for every other x (a NaN stays a NaN).
+                term = np.where(live[:, :, None], w[:, :, None] * leaf[:, None, :], f32(0.0))  # [leaves, rows, K]
+                run = np.concatenate([acc[None, :, :, feats[e]], term], axis=0)
+                acc[:, :, feats[e]] = np.add.accumulate(run, axis=0, dtype=f32)[-1]
+        T = len(forest["depths"])
+        if avg and T > 0:
+            acc[:, :, :F] = acc[:, :, :F] / f32(T)
+    acc[:, :, F] = bias_f32(forest, covers, avg, global_bias)[None, :]
+    return acc
+
+
 def saabas(forest, covers, data, missing=obr.MISSING, avg=False, global_bias=0.0):
     """-> phi [rows, K, F + 1] float32"""
     data = np.ascontiguousarray(data, np.float32)
@@ -233,8 +316,8 @@ def saabas(forest, covers, data, missing=obr.MISSING, avg=False, global_bias=0.0
         for l in range(D):
             parent = idx.copy()
             idx |= right[l].astype(np.int64) << l
-            d = (E[l + 1][idx] - E[l][parent]).astype(np.float32)  # [rows, K]
-            with np.errstate(over="ignore", invalid="ignore"):
+            with np.errstate(over="ignore", invalid="ignore"):  # leaves near FLT_MAX: a delta rounds to +-inf, inf - inf is NaN
+                d = (E[l + 1][idx] - E[l][parent]).astype(np.float32)  # [rows, K]
                 phi[r, :, int(fids[l])] += d
     T = len(forest["depths"])
     if avg and T > 0:
