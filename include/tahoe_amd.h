@@ -248,7 +248,8 @@ tahoe_status tahoe_forest_predict_contribs(tahoe_forest *f, float *phi_dev, cons
  * Asynchronous on `stream`; allocates nothing (graph-capturable).  rows == 0: TAHOE_OK, nothing launched; NULL out_dev /
  * data_dev with rows > 0, or rows * C * (F + 1)^2 * 4 overflowing size_t: TAHOE_ERR_INVALID_ARG; a handle (dense or sparse)
  * created without TAHOE_CREATE_CONTRIBS: TAHOE_ERR_UNSUPPORTED; nothing launched on any refusal.  Sparse handles created with
- * the flag, those with categorical splits included, are served as by tahoe_forest_predict_contribs. */
+ * the flag, those with categorical splits included, are served as by tahoe_forest_predict_contribs.  An oblivious handle is
+ * served with TAHOE_CREATE_INTERACTIONS (tahoe_oblivious_forest_create_ex, which states the order of its sums). */
 tahoe_status tahoe_forest_predict_interactions(tahoe_forest *f, float *out_dev, const float *data_dev, size_t rows, void *stream);
 
 /* Interventional TreeSHAP (SHAP's TreeExplainer(model, data=bg), feature_perturbation="interventional"; Lundberg et al. 2020):
@@ -444,12 +445,16 @@ typedef struct {
  * TILERING and QRING are TAHOE_ERR_UNSUPPORTED.
  * Out of scope, TAHOE_ERR_UNSUPPORTED with nothing launched and a text that says "oblivious": tahoe_forest_predict_csr,
  * _reserve_csr (and _get_csr_plan: form TAHOE_FORM_NONE), _predict_host, _set_stages, _predict_staged (_get_staged_strategy: 0),
- * _predict_interactions, _predict_contribs_interventional and _set_background; _predict_contribs and _predict_contribs_approx
+ * _predict_contribs_interventional and _set_background; _predict_contribs, _predict_contribs_approx and _predict_interactions
  * unless the handle comes from tahoe_oblivious_forest_create_ex with that call's flag.  CatBoost's one-hot and CTR splits are not
  * represented. */
 tahoe_status tahoe_oblivious_forest_create(tahoe_forest **out, const int32_t *depths, const tahoe_oblivious_split *splits,
                                            const float *leaf_values, const tahoe_forest_params *params, int leaf_dim);
-/* The same handle with explanations.  flags: a subset of TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS; with flags == 0
+/* SHAP interaction values on an oblivious handle: accepted by tahoe_oblivious_forest_create_ex alone (every other create:
+ * TAHOE_ERR_INVALID_ARG), alone or with TAHOE_CREATE_CONTRIBS and / or TAHOE_CREATE_APPROX_CONTRIBS. */
+#define TAHOE_CREATE_INTERACTIONS 0x40u
+/* The same handle with explanations.  flags: a subset of TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS |
+ * TAHOE_CREATE_INTERACTIONS, each serving its own call and no other; with flags == 0
  * leaf_covers is ignored and the call is tahoe_oblivious_forest_create (which is this call with NULL, 0).  leaf_covers holds
  * sum_t 2^depths[t] floats, one per leaf in the order of the leaves: the training weight that reached the leaf (CatBoost's
  * leaf_weights).  Checks, before a device is touched and after those of tahoe_oblivious_forest_create: another flag bit, or a flag
@@ -470,8 +475,17 @@ tahoe_status tahoe_oblivious_forest_create(tahoe_forest **out, const int32_t *de
  * implicit heap: each child carries d = (float)(E(child) - E(n)); per tree, level 0 first, the row adds the taken child's d to
  * phi[k][fid of the level], one float32 add per (tree, level) from +0.0f, then / (float)num_trees with AVG; the same bias column,
  * bit for bit.  On covers whose node sums are exact in float32 it gives the bits of the heap expansion on a dense handle.
- * Both calls allocate nothing and can be captured.  The tables count in device_bytes: 8 bytes per (leaf, distinct feature of its
- * tree) and 4 per leaf (TreeSHAP), 4 K bytes per implicit child (Saabas).  A call whose flag the handle lacks stays
+ * TAHOE_CREATE_INTERACTIONS: tahoe_forest_predict_interactions is served -- the interaction values defined there of the game above,
+ * out_dev rows x K x (num_cols + 1)^2.  Per tree the elements are its distinct features in order of first appearance from level
+ * 0; per leaf the row weighs (the rule above) and per pair c < e of elements the term is w_e(P \ {c}) (o_c ? 1 - z_c : -z_c) / 2
+ * leaf[k], w_e(P \ {c}) the TreeSHAP weight of e on the path without c.  Off-diagonal [i][j], i != j < num_cols: one float32 sum
+ * per unordered pair from +0.0f, trees in order, within a tree the leaves in order, then / (float)num_trees with AVG, stored at
+ * [i][j] and [j][i].  [i][i] = phi_i - S_i in float32: phi_i the bits of tahoe_forest_predict_contribs on a handle with
+ * TAHOE_CREATE_CONTRIBS, S_i the sum from +0.0f of the final [i][j], j != i ascending.  [F][F] is the bias column above; the rest
+ * of row and column F, and the rows and columns of features no tree uses, are +0.0f.  Results do not depend on the batch.
+ * The calls allocate nothing and can be captured.  The tables count in device_bytes: 8 bytes per (leaf, distinct feature of its
+ * tree) and 4 per leaf (TreeSHAP and the interaction values, which share them), 4 K bytes per implicit child (Saabas), 8 bytes per
+ * split and per (tree, distinct feature) more for the interaction values.  A call whose flag the handle lacks stays
  * TAHOE_ERR_UNSUPPORTED as above. */
 tahoe_status tahoe_oblivious_forest_create_ex(tahoe_forest **out, const int32_t *depths, const tahoe_oblivious_split *splits,
                                               const float *leaf_values, const float *leaf_covers,

@@ -38,6 +38,7 @@ CREATE_PROB_RELAYOUT = 0x1
 CREATE_CONTRIBS = 0x4  # per-feature contributions (tahoe_forest_predict_contribs); node weights are covers
 CREATE_APPROX_CONTRIBS = 0x10  # Saabas contributions (tahoe_forest_predict_contribs_approx); node weights are covers
 CREATE_CAT_CONTRIBS = 0x20  # tahoe_sparse_forest_create_cat: the two flags above on a handle with categorical splits
+CREATE_INTERACTIONS = 0x40  # tahoe_oblivious_forest_create_ex: SHAP interaction values (tahoe_forest_predict_interactions)
 STRATEGY_NAMES = {1: "direct", 2: "rowtile", 3: "tileblock", 4: "tilering", 5: "qring"}
 STATUS_NAMES = {
     0: "TAHOE_OK",
@@ -585,7 +586,7 @@ class Forest:
     def predict_interactions(self, data, out=None, stream=None):
         """SHAP interaction values (tahoe_forest_predict_interactions): [rows, num_cols + 1, num_cols + 1] float32, or
         [rows, num_classes, num_cols + 1, num_cols + 1] on a multi-class handle; index num_cols is the bias.  Needs
-        contribs=True."""
+        contribs=True (an ObliviousForest: interactions=True)."""
         return self._shap_out("tahoe_forest_predict_interactions", data, 2, out, stream)
 
     def predict_contribs_approx(self, data, out=None, stream=None):
@@ -792,13 +793,14 @@ class ObliviousForest(Forest):
     """tahoe_oblivious_forest_create: trees whose levels share one split each.  depths [T] (0 .. 16); fids, thresholds and
     def_left hold sum(depths) entries, tree-major, level 0 first; leaf_values holds sum(2 ** depths) * leaf_dim floats (tree,
     leaf index, then the leaf_dim values); level l sets bit l of the leaf index.  predict* as Forest, with leaf_dim > 1 in the
-    shapes of a multi-class handle ([rows, leaf_dim]); AVG divides by the number of trees.  contribs=True / approx_contribs=True
-    (tahoe_oblivious_forest_create_ex) serve predict_contribs / predict_contribs_approx and need leaf_covers: sum(2 ** depths)
-    floats, the training weight of every leaf (CatBoost's leaf_weights); zeros are allowed."""
+    shapes of a multi-class handle ([rows, leaf_dim]); AVG divides by the number of trees.  contribs=True / approx_contribs=True /
+    interactions=True (tahoe_oblivious_forest_create_ex) serve predict_contribs / predict_contribs_approx / predict_interactions,
+    each its own call only, and need leaf_covers: sum(2 ** depths) floats, the training weight of every leaf (CatBoost's
+    leaf_weights); zeros are allowed."""
 
     def __init__(self, depths, fids, thresholds, def_left, leaf_values, num_cols: int, leaf_dim: int = 1, missing: float = 0.0,
                  output: int = OUT_RAW, threshold: float = 0.5, global_bias: float = 0.0, leaf_covers=None, contribs: bool = False,
-                 approx_contribs: bool = False):
+                 approx_contribs: bool = False, interactions: bool = False):
         depths = np.ascontiguousarray(depths, dtype=np.int32).reshape(-1)
         fids = np.asarray(fids, dtype=np.int64).reshape(-1)
         nsplits = int(depths.astype(np.int64).sum())
@@ -817,10 +819,11 @@ class ObliviousForest(Forest):
         lv = leaves if leaves.size else np.zeros(1, np.float32)
         self.params = ForestParams(0, 0, int(depths.size), num_cols, 0, output, threshold, global_bias, 0, missing)
         self._h = _vp()
-        flags = (CREATE_CONTRIBS if contribs else 0) | (CREATE_APPROX_CONTRIBS if approx_contribs else 0)
+        flags = ((CREATE_CONTRIBS if contribs else 0) | (CREATE_APPROX_CONTRIBS if approx_contribs else 0)
+                 | (CREATE_INTERACTIONS if interactions else 0))
         if flags:
             if leaf_covers is None:
-                raise ValueError("contribs / approx_contribs need leaf_covers")
+                raise ValueError("contribs / approx_contribs / interactions need leaf_covers")
             covers = np.ascontiguousarray(leaf_covers, dtype=np.float32).reshape(-1)
             if covers.size * leaf_dim != leaves.size:
                 raise ValueError("leaf_covers.size != sum(2 ** depths)")

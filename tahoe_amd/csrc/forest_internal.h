@@ -518,11 +518,14 @@ bool oblivious_tile_fits(const tahoe_forest *f);
 tahoe_status oblivious_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data, size_t rows, hipStream_t stream,
                               int strategy, const float *sums_in);
 void oblivious_destroy(tahoe_forest *f);
-// ... its explanations (oblivious_shap.hip).  oblivious_serves: was the handle created with `flag` (TAHOE_CREATE_CONTRIBS or
-// TAHOE_CREATE_APPROX_CONTRIBS)?  oblivious_predict_shap: that flag's call on such a handle, entry checks included (fn: its name)
+// ... its explanations (oblivious_shap.hip).  oblivious_serves: was the handle created with `flag` (TAHOE_CREATE_CONTRIBS,
+// TAHOE_CREATE_APPROX_CONTRIBS or TAHOE_CREATE_INTERACTIONS)?  oblivious_predict_shap: the call of one of the first two flags on
+// such a handle, oblivious_predict_interactions: that of the third; entry checks included (fn: the call's name)
 bool oblivious_serves(const tahoe_forest *f, unsigned flag);
 tahoe_status oblivious_predict_shap(tahoe_forest *f, unsigned flag, float *phi_dev, const float *data_dev, size_t rows,
                                     hipStream_t stream, const char *fn);
+tahoe_status oblivious_predict_interactions(tahoe_forest *f, float *out_dev, const float *data_dev, size_t rows, hipStream_t stream,
+                                            const char *fn);
 // The refusal of the entry points an oblivious handle does not serve (fn: the entry point's name); TAHOE_OK on every other handle
 inline tahoe_status refuse_oblivious(const tahoe_forest *f, const char *fn)
 {

@@ -239,9 +239,9 @@ extern "C" tahoe_status tahoe_oblivious_forest_create_ex(tahoe_forest **out, con
     }
 
     // ... and the checks of the explanation flags, after those every create makes
-    if (flags & ~(unsigned)(TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS))
-        return fail(TAHOE_ERR_INVALID_ARG, "tahoe_oblivious_forest_create_ex: flags 0x%x: only TAHOE_CREATE_CONTRIBS and "
-                                           "TAHOE_CREATE_APPROX_CONTRIBS are served", flags);
+    if (flags & ~(unsigned)(TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS | TAHOE_CREATE_INTERACTIONS))
+        return fail(TAHOE_ERR_INVALID_ARG, "tahoe_oblivious_forest_create_ex: flags 0x%x: only TAHOE_CREATE_CONTRIBS, "
+                                           "TAHOE_CREATE_APPROX_CONTRIBS and TAHOE_CREATE_INTERACTIONS are served", flags);
     if (flags && !leaf_covers)
         return fail(TAHOE_ERR_INVALID_ARG, "tahoe_oblivious_forest_create_ex: leaf_covers is null, and the flags need the covers");
     if (flags)

@@ -1,5 +1,5 @@
-// What the translation units of an oblivious handle share (oblivious.hip: create and the walk; oblivious_shap.hip: the TreeSHAP
-// and Saabas tables and kernels).  Internal: not part of the ABI.
+// What the translation units of an oblivious handle share (oblivious.hip: create and the walk; oblivious_shap.hip: the TreeSHAP,
+// Saabas and interaction tables and kernels).  Internal: not part of the ABI.
 #pragma once
 #include "forest_internal.h"
 
@@ -30,7 +30,8 @@ struct ObliviousSource {
 
 // TAHOE_ERR_INVALID_FOREST unless every leaf cover is finite and >= 0 (no device touched)
 tahoe_status oblivious_shap_validate(const int32_t *depths, int num_trees, const float *leaf_covers);
-// The tables `flags` (TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS) ask for, on the handle's device
+// The tables `flags` (TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS | TAHOE_CREATE_INTERACTIONS) ask for, on the handle's
+// device
 tahoe_status oblivious_shap_build(tahoe_forest *f, const ObliviousSource &src, unsigned flags);
 void oblivious_shap_destroy(tahoe_forest *f);
 

@@ -24,6 +24,26 @@
 // Sum order, in every form and for any batch: phi[row][k][f] is the float32 sum from +0.0f, trees ascending, within a tree the
 // leaves ascending that the row weighs (TreeSHAP; a leaf the row weighs 0 adds nothing) or the levels ascending (Saabas); then
 // one division by div.  No atomics.
+//
+// SHAP interaction values (TAHOE_CREATE_INTERACTIONS): oblivious_inter_kernel, lane = row as above, the
+// accumulators in place in the lane's own (F + 1) x (F + 1) matrices of out_dev, the features read from global memory.  It reads
+// elems, zz and zmask as they are, through copies of splits and elems that hold columns whatever the form of the other kernels.
+//   begin   the wave zeroes its rows' matrices (coalesced), then a barrier; afterwards a lane touches its own matrices only.
+//   tree    of m distinct features (m == 0: nothing):
+//     phi   ob_shap_tree<m> as it stands, its accumulators row F of the lane's matrix: predict_contribs' sums.
+//     pairs (m >= 2) for c = 0 .. m - 2, the conditioned element: the reduced path holds the other R = m - 1 elements in their
+//           order, position p = element e = p + (p >= c).  The sums of the pairs (c, e), e > c -- positions p >= c -- come
+//           from M[lo][hi] (lo < hi the two columns) into registers, take one add per leaf the row weighs, leaves ascending,
+//           and go back.  Per such leaf j, with mism = idx ^ j, o_e = (mism & mask_e) == 0 and {z_e, 1 - z_e} = zz[j][e]:
+//             cf = (o_c ? 1 - z_c : -z_c) * 0.5f
+//             EXTEND over the R positions: ob_shap_tree's loop with R for M
+//             S0' = sum_{i < R} pw[i] * (float)((R + 1) / (R - i)), i ascending from +0.0f
+//             per p >= c: tot = ob_shap_tree's unwound sum with R for M and z_e;  w = o_e ? tot * (1 - z_e) : -S0'
+//               per class: sum = sum + (w * cf) * leaf[j][k]
+//           Every coefficient is a float64 quotient rounded once, every product and sum one float32 operation.
+//   end     per lane and class, over the used columns u[0] < u[1] < ...: M[a][b] = M[b][a] = M[a][b] / div for a < b; then per
+//           used column a: S = +0.0f + M[a][b] for b != a ascending, M[a][a] = M[F][a] / div - S; then row F becomes +0.0f and
+//           M[F][F] = bias[k].  Everything else keeps the +0.0f of the begin.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -68,10 +88,13 @@ struct tahoe_oshap {
     uint32_t *zmask = nullptr;
     float *delta = nullptr;
     float *bias = nullptr;
-    bool contribs = false, approx = false;
+    tahoe::InnerNode *splits_col = nullptr;  // TAHOE_CREATE_INTERACTIONS: splits and elems with id = the column in either form
+    uint2 *elems_col = nullptr;
+    bool contribs = false, approx = false, inter = false;
     bool inplace = false;  // accumulate in phi_dev (else in LDS)
     size_t lds_bytes = 0;
     tahoe::ObShapView view{};
+    tahoe::ObShapView inter_view{};  // view with splits_col and elems_col
 };
 
 namespace tahoe {
@@ -294,6 +317,169 @@ __global__ void __launch_bounds__(64) oblivious_approx_kernel(const ObShapView v
     ob_shap_end<KB, INPLACE>(v, r, phi);
 }
 
+// The pairs of one tree of M >= 2 distinct features (the file's header: "pairs").  mat: the lane's matrix of class r.k0, the next
+// class mat_k floats on.  The conditioned element c is a wave-uniform loop; pw, z, o and a are indexed by unrolled loops only.
+template <int M, int KB>
+__device__ __forceinline__ void ob_inter_tree(const ObShapRows<KB, true> &r, float *__restrict__ mat, size_t mat_k,
+                                              const uint2 *__restrict__ el, const float2 *__restrict__ zz,
+                                              const uint32_t *__restrict__ zmask, const float *__restrict__ lv, int nleaf,
+                                              uint32_t idx, int K)
+{
+    constexpr int R = M - 1;
+    for (int c = 0; c < R; ++c) {
+        const uint32_t idc = el[c].x, maskc = el[c].y;
+        // M[lo][hi] of the pair (c, element at position p)
+        auto at = [&](int p) {
+            const uint32_t ide = el[p + (p >= c ? 1 : 0)].x;
+            return (size_t)std::min(idc, ide) * r.F1 + (size_t)std::max(idc, ide);
+        };
+        uint32_t mask[R];
+        float a[R][KB];
+#pragma unroll
+        for (int p = 0; p < R; ++p) {
+            mask[p] = el[p + (p >= c ? 1 : 0)].y;
+#pragma unroll
+            for (int k = 0; k < KB; ++k)
+                a[p][k] = (p >= c && (KB == 1 || k < r.kb) && r.row_ok) ? mat[(size_t)k * mat_k + at(p)] : 0.0f;
+        }
+        for (int j = 0; j < nleaf; ++j) {
+            const uint32_t mism = idx ^ (uint32_t)j;
+            const bool live = (mism & zmask[j]) == 0u;
+            if (__ballot(live) == 0ull) continue;
+            const float2 *zj = zz + (size_t)j * M;
+            const float2 zc = zj[c];
+            const float cf = ((mism & maskc) == 0u ? zc.y : -zc.x) * 0.5f;
+            float pw[R + 1], z[R], omz[R];
+            bool o[R];
+            pw[0] = 1.0f;
+#pragma unroll
+            for (int p = 0; p < R; ++p) {
+                const int l = p + 1;
+                const float2 zo = zj[p + (p >= c ? 1 : 0)];
+                z[p] = zo.x;
+                omz[p] = zo.y;
+                o[p] = (mism & mask[p]) == 0u;
+                pw[l] = 0.0f;
+#pragma unroll
+                for (int i = l - 1; i >= 0; --i) {
+                    const float t = pw[i] * (float)((double)(i + 1) / (double)(l + 1));
+                    pw[i + 1] = pw[i + 1] + (o[p] ? t : 0.0f);
+                    pw[i] = pw[i] * (z[p] * (float)((double)(l - i) / (double)(l + 1)));
+                }
+            }
+            float s0 = 0.0f;
+#pragma unroll
+            for (int i = 0; i < R; ++i) s0 = s0 + pw[i] * (float)((double)(R + 1) / (double)(R - i));
+            const float *lj = lv + (size_t)j * (size_t)K;
+#pragma unroll
+            for (int p = 0; p < R; ++p) {
+                if (p < c) continue;
+                float nxt = pw[R], tot = 0.0f;
+#pragma unroll
+                for (int i = R - 1; i >= 0; --i) {
+                    const float tmp = nxt * (float)((double)(R + 1) / (double)(i + 1));
+                    tot = tot + tmp;
+                    if (i > 0) nxt = pw[i] - tmp * (z[p] * (float)((double)(R - i) / (double)(R + 1)));
+                }
+                const float w = o[p] ? tot * omz[p] : -s0;
+                const float wc = w * cf;
+#pragma unroll
+                for (int k = 0; k < KB; ++k) {
+                    const float leaf = (KB == 1 || k < r.kb) ? lj[k] : 0.0f;
+                    const float sum = a[p][k] + wc * leaf;
+                    a[p][k] = live ? sum : a[p][k];
+                }
+            }
+        }
+#pragma unroll
+        for (int p = 0; p < R; ++p)
+#pragma unroll
+            for (int k = 0; k < KB; ++k)
+                if (p >= c && (KB == 1 || k < r.kb) && r.row_ok) mat[(size_t)k * mat_k + at(p)] = a[p][k];
+    }
+}
+
+// SHAP interaction values: grid (row tiles, class blocks), one wave per workgroup, no LDS.  v holds columns in splits and elems.
+template <int KB>
+__global__ void __launch_bounds__(64) oblivious_inter_kernel(const ObShapView vin, float *__restrict__ out,
+                                                             const float *__restrict__ data, size_t rows)
+{
+    // The view's pointers pass through an empty asm and are ordinary scalar values from here on.  As kernel-argument loads, which
+    // the register allocator may repeat instead of spilling, a 16-dword group of them left a spill slot behind that no
+    // instruction uses: 68 bytes of stack per lane in the resource table.  So: ScratchSize 0.
+    ObShapView v = vin;
+    asm volatile("" : "+s"(v.splits), "+s"(v.split_off), "+s"(v.leaf_off), "+s"(v.leaves), "+s"(v.used), "+s"(v.elems), "+s"(v.elem_off),
+                 "+s"(v.zz), "+s"(v.zz_off), "+s"(v.zmask), "+s"(v.bias));
+    ObShapRows<KB, true> r;
+    r.lane = (int)threadIdx.x;
+    r.row0 = (size_t)blockIdx.x * 64;
+    const size_t row = r.row0 + (size_t)r.lane;
+    r.row_ok = row < rows;
+    r.nr = (int)std::min<size_t>(64, rows - r.row0);
+    r.k0 = (int)blockIdx.y * KB;
+    r.kb = std::min(KB, v.K - r.k0);
+    r.F1 = (size_t)v.F + 1;
+    const size_t mat_k = r.F1 * r.F1;
+    r.out_row = (size_t)v.K * mat_k;
+    for (int q = 0; q < r.nr; ++q) {  // the block's matrices of a row are contiguous
+        float *o = out + (r.row0 + (size_t)q) * r.out_row + (size_t)r.k0 * mat_k;
+        for (size_t i = (size_t)r.lane; i < (size_t)r.kb * mat_k; i += 64) o[i] = 0.0f;
+    }
+    const size_t my = r.row_ok ? row : r.row0;  // (a lane past the batch reads the tile's first row and neither loads nor stores)
+    r.x = data + my * (size_t)v.F;
+    r.tile = r.slab = nullptr;
+    float *mat = out + my * r.out_row + (size_t)r.k0 * mat_k;
+    r.acc = mat + (size_t)v.F * r.F1;  // phi accumulates in row F, which ends as zeroes
+    r.kstride = mat_k;
+    __syncthreads();  // the zeroes land before any lane adds to its matrices
+    for (int t = 0; t < v.T; ++t) {
+        const int e0 = v.elem_off[t];
+        const int m = v.elem_off[t + 1] - e0;  // wave-uniform, as everything read below
+        if (m == 0) continue;
+        const uint32_t idx = ob_shap_leaf_index(v, r, t, [](int, uint32_t, uint32_t) {});
+        const int nleaf = 1 << (v.split_off[t + 1] - v.split_off[t]);
+        const uint2 *el = v.elems + e0;
+        const float2 *zz = v.zz + v.zz_off[t];
+        const uint32_t *zm = v.zmask + v.leaf_off[t];
+        const float *lv = v.leaves + (size_t)v.leaf_off[t] * (size_t)v.K + r.k0;
+        switch (m) {
+        case 1: ob_shap_tree<1, KB, true>(r, el, zz, zm, lv, nleaf, idx, v.K); break;  // no pair
+#define TAHOE_OB_INTER_CASE(M) \
+    case M: \
+        ob_shap_tree<M, KB, true>(r, el, zz, zm, lv, nleaf, idx, v.K); \
+        ob_inter_tree<M, KB>(r, mat, mat_k, el, zz, zm, lv, nleaf, idx, v.K); \
+        break;
+            TAHOE_OB_INTER_CASE(2) TAHOE_OB_INTER_CASE(3) TAHOE_OB_INTER_CASE(4) TAHOE_OB_INTER_CASE(5)
+            TAHOE_OB_INTER_CASE(6) TAHOE_OB_INTER_CASE(7) TAHOE_OB_INTER_CASE(8) TAHOE_OB_INTER_CASE(9)
+            TAHOE_OB_INTER_CASE(10) TAHOE_OB_INTER_CASE(11) TAHOE_OB_INTER_CASE(12) TAHOE_OB_INTER_CASE(13)
+            TAHOE_OB_INTER_CASE(14) TAHOE_OB_INTER_CASE(15) TAHOE_OB_INTER_CASE(16)
+#undef TAHOE_OB_INTER_CASE
+        default: break;
+        }
+    }
+    if (!r.row_ok) return;
+    for (int k = 0; k < r.kb; ++k) {
+        float *mk = mat + (size_t)k * mat_k;
+        for (int a = 0; a < v.U; ++a)
+            for (int b = a + 1; b < v.U; ++b) {
+                const size_t fa = (size_t)v.used[a], fb = (size_t)v.used[b];
+                const float q = mk[fa * r.F1 + fb] / v.div;
+                mk[fa * r.F1 + fb] = q;
+                mk[fb * r.F1 + fa] = q;
+            }
+        float *phi = mk + (size_t)v.F * r.F1;
+        for (int a = 0; a < v.U; ++a) {
+            const size_t fa = (size_t)v.used[a];
+            float s = 0.0f;
+            for (int b = 0; b < v.U; ++b)
+                if (b != a) s = s + mk[fa * r.F1 + (size_t)v.used[b]];
+            mk[fa * r.F1 + fa] = phi[fa] / v.div - s;
+        }
+        for (int a = 0; a < v.U; ++a) phi[v.used[a]] = 0.0f;
+        phi[v.F] = v.bias[r.k0 + k];
+    }
+}
+
 tahoe_status oblivious_shap_validate(const int32_t *depths, int num_trees, const float *leaf_covers)
 {
     size_t at = 0;
@@ -355,6 +541,8 @@ tahoe_status oblivious_shap_build(tahoe_forest *f, const ObliviousSource &src, u
     o->shap = sh;
     sh->contribs = (flags & TAHOE_CREATE_CONTRIBS) != 0;
     sh->approx = (flags & TAHOE_CREATE_APPROX_CONTRIBS) != 0;
+    sh->inter = (flags & TAHOE_CREATE_INTERACTIONS) != 0;
+    const bool paths = sh->contribs || sh->inter;  // elems, zz and zmask serve both
     const int T = f->p.num_trees, K = f->num_classes, F = f->p.num_cols;
     const std::vector<InnerNode> &splits = *src.h_splits;
     const std::vector<int32_t> &split_off = *src.h_split_off;
@@ -383,7 +571,8 @@ tahoe_status oblivious_shap_build(tahoe_forest *f, const ObliviousSource &src, u
     std::vector<int32_t> h_elem_off((size_t)T + 1, 0);
     std::vector<float2> h_zz;
     std::vector<int64_t> h_zz_off((size_t)T, 0);
-    std::vector<uint32_t> h_zmask(sh->contribs ? src.num_leaves : 0, 0u);
+    std::vector<uint32_t> h_zmask(paths ? src.num_leaves : 0, 0u);
+    std::vector<uint2> h_elems_col;
     std::vector<float> h_delta(sh->approx ? 2 * (src.num_leaves - (size_t)T) * (size_t)K : 0, 0.0f);
     std::vector<double> bias_sum((size_t)K, 0.0);
     ObHeap heap;
@@ -430,7 +619,7 @@ tahoe_status oblivious_shap_build(tahoe_forest *f, const ObliviousSource &src, u
                 }
             }
         }
-        if (sh->contribs) {
+        if (paths) {
             uint32_t fid[kObMaxDepth], mask[kObMaxDepth];
             int m = 0;
             for (int l = 0; l < D; ++l) {
@@ -444,6 +633,8 @@ tahoe_status oblivious_shap_build(tahoe_forest *f, const ObliviousSource &src, u
                 mask[e] |= 1u << l;
             }
             for (int e = 0; e < m; ++e) h_elems.push_back(make_uint2(id_of(fid[e]), mask[e]));
+            if (sh->inter)
+                for (int e = 0; e < m; ++e) h_elems_col.push_back(make_uint2(fid[e], mask[e]));
             h_zz_off[(size_t)t] = (int64_t)h_zz.size();
             for (size_t j = 0; j < nleaf; ++j) {
                 uint32_t zm = 0u;
@@ -476,8 +667,15 @@ tahoe_status oblivious_shap_build(tahoe_forest *f, const ObliviousSource &src, u
         (s = hip_status(upload(&sh->delta, h_delta, &f->device_bytes), "upload(delta)")) ||
         (s = hip_status(upload(&sh->bias, h_bias, &f->device_bytes), "upload(bias)")))
         return s;
+    if (sh->inter &&  // (src's splits hold columns)
+        ((s = hip_status(upload(&sh->splits_col, splits, &f->device_bytes), "upload(interaction splits)")) ||
+         (s = hip_status(upload(&sh->elems_col, h_elems_col, &f->device_bytes), "upload(interaction elems)"))))
+        return s;
     sh->view = ObShapView{sh->splits, o->split_off, o->leaf_off, o->leaves, sh->used, sh->elems, sh->elem_off, sh->zz, sh->zz_off,
                           sh->zmask, sh->delta, sh->bias, avg ? (float)T : 1.0f, f->p.missing, F, K, T, U, S};
+    sh->inter_view = sh->view;
+    sh->inter_view.splits = sh->splits_col;
+    sh->inter_view.elems = sh->elems_col;
     if (!sh->inplace) {  // the LDS forms may need more than the default 64 KiB
         hipError_t e = hipSuccess;
         if ((e = allow_max_lds(reinterpret_cast<const void *>(&oblivious_shap_kernel<1, false>), f->lds_limit)) != hipSuccess ||
@@ -494,7 +692,7 @@ void oblivious_shap_destroy(tahoe_forest *f)
     tahoe_oshap *sh = f->ob ? f->ob->shap : nullptr;
     if (!sh) return;
     for (void *p : {(void *)sh->splits, (void *)sh->used, (void *)sh->elems, (void *)sh->elem_off, (void *)sh->zz, (void *)sh->zz_off,
-                    (void *)sh->zmask, (void *)sh->delta, (void *)sh->bias})
+                    (void *)sh->zmask, (void *)sh->delta, (void *)sh->bias, (void *)sh->splits_col, (void *)sh->elems_col})
         if (p) (void)hipFree(p);
     delete sh;
     f->ob->shap = nullptr;
@@ -503,7 +701,8 @@ void oblivious_shap_destroy(tahoe_forest *f)
 bool oblivious_serves(const tahoe_forest *f, unsigned flag)
 {
     const tahoe_oshap *sh = f->ob ? f->ob->shap : nullptr;
-    return sh && (flag == TAHOE_CREATE_CONTRIBS ? sh->contribs : sh->approx);
+    if (!sh) return false;
+    return flag == TAHOE_CREATE_CONTRIBS ? sh->contribs : flag == TAHOE_CREATE_INTERACTIONS ? sh->inter : sh->approx;
 }
 
 tahoe_status oblivious_predict_shap(tahoe_forest *f, unsigned flag, float *phi_dev, const float *data_dev, size_t rows,
@@ -531,6 +730,22 @@ tahoe_status oblivious_predict_shap(tahoe_forest *f, unsigned flag, float *phi_d
     };
     if (K == 1) with_form(std::integral_constant<int, 1>{});
     else with_form(std::integral_constant<int, kObShapClasses>{});
+    TAHOE_HIP_TRY(hipGetLastError());
+    return TAHOE_OK;
+}
+
+tahoe_status oblivious_predict_interactions(tahoe_forest *f, float *out_dev, const float *data_dev, size_t rows, hipStream_t stream,
+                                            const char *fn)
+{
+    if (rows == 0) return TAHOE_OK;
+    if (!out_dev || !data_dev) return fail(TAHOE_ERR_INVALID_ARG, "%s: null argument", fn);
+    if (const tahoe_status st = check_shap_out(f, rows, 2, fn)) return st;
+    const tahoe_oshap *sh = f->ob->shap;
+    DeviceGuard on_device(f->device);
+    const int K = f->num_classes;
+    const dim3 grid((unsigned)((rows + 63) / 64), (unsigned)((K + kObShapClasses - 1) / kObShapClasses));
+    if (K == 1) hipLaunchKernelGGL((oblivious_inter_kernel<1>), grid, dim3(64), 0, stream, sh->inter_view, out_dev, data_dev, rows);
+    else hipLaunchKernelGGL((oblivious_inter_kernel<kObShapClasses>), grid, dim3(64), 0, stream, sh->inter_view, out_dev, data_dev, rows);
     TAHOE_HIP_TRY(hipGetLastError());
     return TAHOE_OK;
 }
