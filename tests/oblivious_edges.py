@@ -10,15 +10,23 @@ infrastructure, not product.
   branch    thresholds and data from shap_edges' pools (+-0, +-inf, NaN, subnormals, the sentinel, the edges of the missing
             band) under every `missing` of shap_edges.MISSINGS
   leaves    the covers forest with leaves near FLT_MAX: Saabas deltas that overflow
+  inter     SHAP interaction values only: no tree, trees of depth 0 alone, three used columns of 300, one column (no pair), and
+            the multi forest with exactly one full class block (K = 4)
 
 A case is a dict(forest, covers, data, missing, avg, bias, cut); cut says that its covers may put a zero fraction below 2^-121,
 so that its bar carries the floor (the cover cases; every other case is held to the bar alone).  reference(name) adds poly's
 (phi, A, N), emulate's and saabas' phi, computed once and read-only.  The cases of one element count share one forest of the most classes any of them needs and slice
-its leaves: every class is computed on its own, so the references of the widest forest serve them all."""
+its leaves: every class is computed on its own, so the references of the widest forest serve them all.
+
+inter_reference(name) does the same for predict_interactions with tests/oblivious_inter_ref.py: 'poly' = (Phi, A, N) in float64
+and 'emulate', the kernel's bits.  A family of 13 or more elements keeps its first 3 rows there (poly holds M 2^D rows doubles
+per conditioned element), which still leaves 61 lanes past the batch; poly is left out at M = 16 alone, where it takes 18 s
+(8 s at M = 15): the m:16 cases are held to emulate's bits and to the structural properties."""
 from __future__ import annotations
 
 import numpy as np
 
+import oblivious_inter_ref as oir
 import oblivious_ref as obr
 import oblivious_shap_ref as osr
 import shap_edges as se
@@ -37,6 +45,11 @@ COVER_POOLS = ("int", "zero", "most", "span", "near_one", "subnormal", "f32_over
 # not the dense one's), subnormal sums, or sums past FLT_MAX.
 EXPANSION_POOLS = ("int", "span", "near_one")
 OVERFLOW_LEAVES = np.array([3e38, -3e38, 1e38, -1e38, 1.0, -0.0], F32)
+WIDE_COLS, WIDE_USED, WIDE_DEPTHS = 300, (0, 149, 299), [3, 5, 2]
+WIDE_FIDS = [0, 1, 0, 1, 2, 0, 2, 1, 2, 0]  # of WIDE_USED, level by level: every pair shares a tree, features repeat within one
+INTER_DEEP = 13       # from this many elements on the interaction references keep INTER_DEEP_ROWS rows
+INTER_DEEP_ROWS = 3
+INTER_POLY_MAX = 15   # the most elements of an element case with a float64 poly (module docstring)
 
 
 def element_classes(M):
@@ -45,6 +58,18 @@ def element_classes(M):
 
 def element_rows(M):
     return 65 if M <= 10 else 5  # poly holds (M + 1) 2^M rows doubles; both counts leave lanes past the batch
+
+
+def inter_rows(name):
+    """How many of the case's rows the interaction references and tests use"""
+    parts = name.split(":")
+    M = int(parts[1]) if parts[0] == "m" else 0
+    return INTER_DEEP_ROWS if M >= INTER_DEEP else case(name)["data"].shape[0]
+
+
+def has_inter_poly(name):
+    parts = name.split(":")
+    return parts[0] != "m" or int(parts[1]) <= INTER_POLY_MAX
 
 
 def with_classes(forest, k):
@@ -107,6 +132,8 @@ def _base(name):
             arg = "half"
         return _case(forest, make_covers(forest, arg, seed=4710 + COVER_POOLS.index(arg) if arg in COVER_POOLS else 4709),
                      obr.make_data(65, 8, seed=4702), cut=head == "covers")
+    if head == "inter":
+        return _inter_base(arg)
     assert head == "branch"
     missing = se.MISSINGS[arg]
     rng = np.random.default_rng(4800 + list(se.MISSINGS).index(arg))
@@ -116,6 +143,27 @@ def _base(name):
     return _case(forest, osr.make_covers(forest, "half", seed=4820), se.random_data(rng, 257, 6, missing), missing=missing)
 
 
+def _inter_base(arg):
+    """The interaction-only families (module docstring)"""
+    if arg == "none:empty":
+        forest = obr.make_forest([], 4, 2, seed=4900)
+        return _case(forest, np.zeros(0, F32), obr.make_data(65, 4, seed=4901), bias=0.25)
+    if arg == "none:depth0":
+        forest = obr.make_forest([0, 0, 0], 4, 3, seed=4910)
+        return _case(forest, osr.make_covers(forest, "half", seed=4911), obr.make_data(65, 4, seed=4912), avg=True, bias=0.25)
+    if arg == "wide":
+        forest = obr.make_forest(WIDE_DEPTHS, len(WIDE_USED), 5, seed=4920)
+        forest["fids"] = np.asarray(WIDE_USED)[WIDE_FIDS]
+        forest["cols"] = WIDE_COLS
+        return _case(forest, osr.make_covers(forest, "half", seed=4921), obr.make_data(65, WIDE_COLS, seed=4922))
+    if arg == "one_col":
+        forest = obr.make_forest([1, 4], 1, 2, seed=4930)
+        return _case(forest, osr.make_covers(forest, "half", seed=4931), obr.make_data(65, 1, seed=4932))
+    assert arg == "k4"  # multi:avg's splits, covers and data under leaves of 4 classes (make_forest draws the leaves last)
+    forest = obr.make_forest(MULTI_DEPTHS, 12, 4, seed=4600)
+    return _case(forest, osr.make_covers(forest, "half", seed=4601), obr.make_data(65, 12, seed=4602), avg=True, bias=-0.375)
+
+
 ELEMENT_CASES = [f"m:{M}:k{k}" for M in ELEMENT_COUNTS for k in element_classes(M)]
 MERGED_CASES = [f"merged:{M}" for M in MERGED]
 MULTI_CASES = ["multi:sum", "multi:avg"]
@@ -123,13 +171,15 @@ COVER_CASES = [f"covers:{p}" for p in COVER_POOLS]
 BRANCH_CASES = [f"branch:{m}" for m in se.MISSINGS]
 LEAF_CASE = "leaves:overflow"
 SHAP_CASES = ELEMENT_CASES + MERGED_CASES + MULTI_CASES + COVER_CASES + BRANCH_CASES  # TreeSHAP is checked on these
-_bases, _refs = {}, {}
+INTER_ONLY_CASES = ["inter:none:empty", "inter:none:depth0", "inter:wide:k1", "inter:wide:k5", "inter:one_col", "inter:k4"]
+INTER_CASES = SHAP_CASES + [LEAF_CASE] + INTER_ONLY_CASES  # predict_interactions is checked on these
+_bases, _refs, _inter_refs = {}, {}, {}
 
 
 def _split(name):
     parts = name.split(":")
-    if parts[0] == "m":
-        return f"m:{parts[1]}", int(parts[2][1:])
+    if parts[0] == "m" or parts[:2] == ["inter", "wide"]:
+        return ":".join(parts[:2]), int(parts[2][1:])
     return name, None
 
 
@@ -169,6 +219,26 @@ def reference(name, shap=True):
     return out
 
 
+def inter_reference(name):
+    """case(name) on its first inter_rows(name) rows with 'emulate' = oblivious_inter_ref.emulate's Phi and 'poly' = its poly's
+    (Phi, A, N), or None where has_inter_poly(name) says no; computed once per family, read-only, sliced on the class axis"""
+    base, k = _split(name)
+    c = _base_of(base)
+    rows = inter_rows(name)
+    if base not in _inter_refs:
+        args = (c["forest"], c["covers"], c["data"][:rows])
+        kw = dict(missing=c["missing"], avg=c["avg"], global_bias=c["bias"])
+        with np.errstate(all="ignore"):
+            r = dict(emulate=oir.emulate(*args, **kw))
+        r["poly"] = oir.poly(*args, **kw) if has_inter_poly(name) else None
+        for a in (r["emulate"],) + (r["poly"] or ()):
+            a.setflags(write=False)
+        _inter_refs[base] = r
+    r = _inter_refs[base]
+    return dict(case(name), data=c["data"][:rows], emulate=r["emulate"][:, :k],
+                poly=None if r["poly"] is None else tuple(a[:, :k] for a in r["poly"]))
+
+
 def depth_of(forest):
     return int(max(forest["depths"], default=0))
 
@@ -184,6 +254,23 @@ def bar(c, A, N):
     if c["avg"] and T > 0:
         L /= T
     n = N + 4 * (D + 2)
+    floor = n * se.Z_MIN * L if c["cut"] else np.zeros_like(A)
+    return n * U * A + floor, floor
+
+
+def inter_bar(c, A, N):
+    """(bound, floor), [rows, K, F + 1, F + 1]: the off-diagonal bar of tests/test_oblivious_inter_gpu.py with bar's floor.  An
+    entry is the float32 sum of N terms whose absolute values sum to A, and a term carries the rounding of a conditioned extend
+    and unwind of at most D + 1 steps, of the conditioning factor, of w * cf and of the product with the leaf -- 6 (D + 2)
+    roundings are that test's count: n = N + 6 (D + 2), bound = n 2^-24 A + floor.  floor = n 2^-121 max |leaf| (/ T with AVG)
+    in a case whose covers reach the cut (create's cut of a zero fraction below 2^-121 moves a term by at most 2^-121 |leaf|,
+    bar's argument with this n) and 0 in every other case.  No margin beyond that."""
+    forest = c["forest"]
+    D, T = depth_of(forest), len(forest["depths"])
+    L = float(np.abs(np.asarray(forest["leaves"], np.float64)).max()) if np.size(forest["leaves"]) else 0.0
+    if c["avg"] and T > 0:
+        L /= T
+    n = N + 6 * (D + 2)
     floor = n * se.Z_MIN * L if c["cut"] else np.zeros_like(A)
     return n * U * A + floor, floor
 

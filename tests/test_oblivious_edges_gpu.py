@@ -10,7 +10,11 @@ kernel's header fixes.  Under it the bar of tests/test_oblivious_shap_gpu.py aga
 at most 0.14 of it (tests/test_oblivious_edges_capi.py prints the ratios), so the bar cannot see what the bits do.  Saabas, the
 bias column, the walks and everything said to be bitwise compare bits (shap_edges.assert_same_bits: a NaN need only be a NaN
 at the same place).  Every explanation call writes into the head of a buffer 256 rows longer whose tail must come back
-untouched."""
+untouched.
+
+SHAP interaction values (oblivious_inter_kernel, ob_inter_tree<M, KB>) on the same cases and on the inter:* ones: check_inter
+holds predict_interactions to the bits of oblivious_inter_ref.emulate, to oblivious_edges.inter_bar of the float64 poly off the
+diagonal, to the matrix's structure, and to oblivious_shap_ref.poly's phi in its row sums."""
 import os
 import sys
 
@@ -19,6 +23,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import approx_contribs_ref  # noqa: E402
+import interactions_ref  # noqa: E402
 import oblivious_edges as oe  # noqa: E402
 import oblivious_ref as obr  # noqa: E402
 import oblivious_shap_ref as osr  # noqa: E402
@@ -80,16 +85,19 @@ def expansion_handle(env, c, covers=True, **kw):
                      output=ta.OUT_AVG if c["avg"] else 0, global_bias=c["bias"], **kw)
 
 
-def run(env, f, call, x):
-    """f.<call>(x) into the head of a longer buffer -> numpy [rows, K, F + 1]; the tail must stay as it was"""
+def run(env, f, call, x, dims=1, shift=0):
+    """f.<call>(x) into the head of a longer buffer -> numpy [rows, K, (F + 1) x dims]; the tail must stay as it was.  shift: the
+    output starts that many floats past the buffer's (16-byte aligned) start, and the floats before it must stay too"""
     ta, torch = env
     rows, k, F1 = x.shape[0], f.num_classes, f.num_cols + 1
-    shape = (rows + TAIL,) + ((k,) if k > 1 else ()) + (F1,)
-    buf = torch.full(shape, SENTINEL, device="cuda")
-    getattr(f, call)(x, out=buf[:rows])
+    shape = (rows,) + ((k,) if k > 1 else ()) + (F1,) * dims
+    n = int(np.prod(shape))
+    buf = torch.full((shift + (n // max(rows, 1)) * (rows + TAIL),), SENTINEL, device="cuda")
+    assert buf.data_ptr() % 16 == 0
+    getattr(f, call)(x, out=buf[shift:shift + n].view(shape))
     torch.cuda.synchronize()
-    assert bool((buf[rows:] == SENTINEL).all()), f"{call} wrote past its {rows} rows"
-    return buf[:rows].cpu().numpy().reshape(rows, k, F1)
+    assert bool((buf[shift + n:] == SENTINEL).all()) and bool((buf[:shift] == SENTINEL).all()), f"{call} wrote past its {rows} rows"
+    return buf[shift:shift + n].cpu().numpy().reshape((rows, k) + (F1,) * dims)
 
 
 def check_shap(env, knob, name, forced, batches=(1, 64), additive=False):
@@ -126,6 +134,80 @@ def check_shap(env, knob, name, forced, batches=(1, 64), additive=False):
         assert np.all(np.abs(got.sum(axis=-1) - margin) <= tol), f"{label}: additivity"
     f.close()
     return got32, bound
+
+
+def check_inter(env, knob, name, forced=False):
+    """predict_interactions on the case (its first oe.inter_rows rows), the handle created in one form:
+      bits       emulate's; where leaves overflow a NaN need only be a NaN at the same place, and everywhere else no entry is
+                 non-finite
+      bar        inside oe.inter_bar of poly off the diagonal, where the case has a poly (on the finite entries)
+      structure  bitwise symmetric; row and column F zero but for [F][F], the bias bits; unused columns all-zero bits; the
+                 diagonal = predict_contribs of a contribs=True handle minus the float32 sum of the row's off-diagonals, j
+                 ascending from +0.0f
+      row sums   sum_j Phi[i][j] in float64 against oblivious_shap_ref.poly's phi_i within the sum of the two bars: the
+                 off-diagonals cancel against the diagonal up to the float32 sum and the subtraction that made it (at most U u
+                 sum_j |Phi_ij| for U used columns, inside the interaction bars of the row, whose n >= 6 (D + 2) exceeds U in
+                 every case here), which leaves the error of phi_i itself, TreeSHAP's bar.  It leans on neither emulate nor the
+                 kernel's order.
+    -> (got, worst err / bound or None)"""
+    ta, torch = env
+    c = oe.inter_reference(name)
+    forest, data, emu = c["forest"], c["data"], c["emulate"]
+    rows, F = data.shape[0], forest["cols"]
+    overflow = name == oe.LEAF_CASE
+    label = f"{name} interactions{' in place' if forced else ''}"
+    f = handle(env, c, knob, forced, interactions=True)
+    x = torch.from_numpy(data.copy()).cuda()
+    got = run(env, f, "predict_interactions", x, dims=2)
+    f.close()
+    finite = np.isfinite(got)
+    assert overflow or finite.all(), f"{label}: non-finite outputs at {np.argwhere(~finite)[:5]}"
+    differ = int(((se.bits(got) != se.bits(emu)) & ~(np.isnan(got) & np.isnan(emu))).sum())
+    eye = np.eye(F + 1, dtype=bool)
+    worst = None
+    if c["poly"] is not None:
+        want, A, N = c["poly"]
+        bound, floor = oe.inter_bar(c, A, N)
+        assert np.all(floor <= 1e-30), f"{label}: the floor {floor.max():.3e} could mask a normal-range error"
+        err, off = np.abs(got.astype(np.float64) - want), ~eye & finite
+        worst = float((err / np.where(bound > 0, bound, 1.0))[off].max()) if off.any() else 0.0
+    print(f"{label}: max err / bound = {'none' if worst is None else format(worst, '.4f')}; {differ} of {got.size} outputs differ "
+          f"from emulate")
+    se.assert_same_bits(got, emu, f"{label}: against emulate")
+    if worst is not None:
+        assert np.all(err[off] <= bound[off]), f"{label}: bound exceeded {worst:.3f}x at {np.argwhere(off & (err > bound))[:5]}"
+    # structure
+    assert np.array_equal(se.bits(got), se.bits(got.swapaxes(-1, -2))), f"{label}: not symmetric"
+    b = osr.bias_f32(forest, c["covers"], c["avg"], c["bias"])
+    assert np.array_equal(se.bits(got[:, :, F, F]), se.bits(np.broadcast_to(b, got.shape[:2]))), f"{label}: bias corner"
+    assert not se.bits(got[:, :, F, :F]).any() and not se.bits(got[:, :, :F, F]).any(), f"{label}: row / column F"
+    used = np.unique(forest["fids"]).astype(np.int64)
+    unused = np.setdiff1d(np.arange(F), used)
+    assert not se.bits(got[:, :, unused, :]).any() and not se.bits(got[:, :, :, unused]).any(), f"{label}: unused columns"
+    g = handle(env, c, knob, forced, contribs=True)
+    phi = run(env, g, "predict_contribs", x)
+    g.close()
+    diag = np.zeros(got.shape[:2] + (F,), np.float32)
+    with np.errstate(all="ignore"):
+        for i in used:
+            s = np.zeros(got.shape[:2], np.float32)
+            for j in range(F):
+                if j != i:
+                    s = s + got[:, :, i, j]
+            diag[:, :, i] = phi[:, :, i] - s
+    idx = np.arange(F)
+    se.assert_same_bits(got[:, :, idx, idx], diag, f"{label}: diagonal")
+    # row sums
+    if worst is not None:
+        with np.errstate(all="ignore"):
+            shap = oe.reference(name)
+        want_phi, A1, N1 = (a[:rows] for a in shap["poly"])
+        tol = oe.bar(c, A1, N1)[0][:, :, :F] + np.where(eye, 0.0, bound)[:, :, :F, :F].sum(axis=-1)
+        whole = finite[:, :, :F, :F].all(axis=-1)
+        with np.errstate(invalid="ignore"):
+            miss = np.abs(got.astype(np.float64)[:, :, :F, :F].sum(axis=-1) - want_phi[:, :, :F])
+        assert np.all(miss[whole] <= tol[whole]), f"{label}: row sums, {float((miss / np.where(tol > 0, tol, 1.0))[whole].max()):.3f}x"
+    return got, worst
 
 
 # ------------------------------------------------------------------------------------------------ a: every element count
@@ -216,7 +298,7 @@ def test_extreme_covers_against_the_heap_expansion(env, unforced, pool):
 @pytest.mark.parametrize("name", oe.BRANCH_CASES)
 def test_the_branch_rule_in_every_walk(env, unforced, name):
     """oblivious_walk under DIRECT and ROWTILE, the dense walk on the expansion, the Saabas walk and ob_shap_leaf_index with its
-    remapped split table (LDS form) and its plain one (in place): one rule, the reference's"""
+    remapped split table (LDS form), its plain one (in place) and the interaction kernel's copy: one rule, the reference's"""
     ta, torch = env
     c = oe.reference(name)
     forest, data, missing = c["forest"], c["data"], c["missing"]
@@ -243,6 +325,7 @@ def test_the_branch_rule_in_every_walk(env, unforced, name):
     f.close()
     for forced in FORMS:
         check_shap(env, unforced, name, forced, batches=(1, 64), additive=True)
+    check_inter(env, unforced, name)  # ob_shap_leaf_index on the column split table of oblivious_inter_kernel
 
 
 # ------------------------------------------------------------------------------------------------ d: Saabas overflow
@@ -262,3 +345,117 @@ def test_saabas_deltas_that_overflow(env, unforced, forced):
     for r in (1, 64):
         se.assert_same_bits(run(env, f, "predict_contribs_approx", x[:r].contiguous()), want[:r], f"overflowing leaves: {r} rows")
     f.close()
+
+
+# ------------------------------------------------------------------------------------------------ e: interaction values
+@pytest.mark.parametrize("name", oe.ELEMENT_CASES)
+def test_interaction_bits_for_every_element_count(env, unforced, name):
+    """ob_inter_tree<M, 1> and <M, 4> for M = 2 .. 16 (M = 1: no pair), with a full and a partial class block"""
+    check_inter(env, unforced, name)
+
+
+@pytest.mark.parametrize("name", oe.MERGED_CASES)
+def test_interaction_bits_at_depth_16_on_repeated_features(env, unforced, name):
+    check_inter(env, unforced, name)
+
+
+@pytest.mark.parametrize("name", oe.MULTI_CASES + ["inter:k4"])
+def test_interaction_bits_across_trees_that_share_columns(env, unforced, name):
+    got, _ = check_inter(env, unforced, name)
+    assert np.abs(got[:, :, :-1, :-1]).max() > 0
+
+
+@pytest.mark.parametrize("name", oe.COVER_CASES)
+def test_interactions_under_extreme_covers(env, unforced, name):
+    check_inter(env, unforced, name)
+
+
+@pytest.mark.parametrize("pool", oe.EXPANSION_POOLS)
+def test_interactions_against_the_heap_expansion(env, unforced, pool):
+    """The dense handle on the heap expansion with the subtree covers as node weights (the pools that allow it): the two
+    handles' off-diagonals within the sum of their bars -- inter_bar here, tests/test_interactions_gpu.py's
+    (N + 6 (D + 2)) 2^-24 A of interactions_ref.poly there -- and the bias corner bit for bit"""
+    ta, torch = env
+    name = f"covers:{pool}"
+    c = oe.inter_reference(name)
+    forest = c["forest"]
+    F, k, T = forest["cols"], forest["k"], len(forest["depths"])
+    nodes, D = expansion_nodes(c)
+    _, Ad, Nd = interactions_ref.poly(nodes, T * k, D, F, c["data"], c["missing"], num_classes=k)
+    f = handle(env, c, interactions=True)
+    g = expansion_handle(env, c, contribs=True)
+    x = torch.from_numpy(c["data"].copy()).cuda()
+    mine, theirs = run(env, f, "predict_interactions", x, dims=2), run(env, g, "predict_interactions", x, dims=2)
+    f.close()
+    g.close()
+    _, A, N = c["poly"]
+    bound = oe.inter_bar(c, A, N)[0] + (Nd[None] + 6 * (D + 2)) * U * Ad
+    off = ~np.eye(F + 1, dtype=bool)
+    err = np.abs(mine.astype(np.float64) - theirs.astype(np.float64))
+    worst = float((err / np.where(bound > 0, bound, 1.0))[..., off].max())
+    print(f"{name}: max |native - expansion| / (the two bars) = {worst:.4f}")
+    assert np.abs(theirs[..., off]).max() > 0 and np.all(err[..., off] <= bound[..., off]), f"{name}: {worst:.3f}x"
+    assert np.array_equal(se.bits(mine[:, :, F, F]), se.bits(theirs[:, :, F, F])), f"{name}: bias corner against the expansion"
+
+
+def test_interactions_with_leaves_near_flt_max(env, unforced):
+    """Terms and sums that overflow: +-inf with emulate's bits, NaN where emulate's is, the rest inside the bar"""
+    got, _ = check_inter(env, unforced, oe.LEAF_CASE)
+    assert np.isnan(got).any() or np.isinf(got).any()
+    assert np.isfinite(got[:, :, :-1, :-1]).any()
+
+
+@pytest.mark.parametrize("name", oe.INTER_ONLY_CASES)
+def test_interaction_only_cases(env, unforced, name):
+    """No tree, no used feature, 3 used columns of 300 (K 301^2 floats zeroed per row, size_t indexing), a single column, one
+    full class block.  The wide cases also as one row and as a 64-row batch, and with output and data both starting one float
+    past a 16-byte boundary: the same bits"""
+    ta, torch = env
+    got, _ = check_inter(env, unforced, name)
+    c = oe.inter_reference(name)
+    F = c["forest"]["cols"]
+    if name.startswith("inter:none") or name == "inter:one_col":
+        rest = got.copy()
+        rest[:, :, F, F] = 0
+        rest[:, :, np.arange(F), np.arange(F)] = 0
+        assert not se.bits(rest).any(), f"{name}: an off-diagonal entry is set"
+        assert name == "inter:one_col" or not se.bits(got[:, :, :F, :F]).any()
+    if name.startswith("inter:wide"):
+        f = handle(env, c, interactions=True)
+        x = torch.from_numpy(c["data"].copy()).cuda()
+        for r in (1, 64):
+            part = run(env, f, "predict_interactions", x[:r].contiguous(), dims=2)
+            assert np.array_equal(se.bits(part), se.bits(got[:r])), (name, r)
+        assert np.array_equal(se.bits(run(env, f, "predict_interactions", x[64:65].clone(), dims=2)), se.bits(got[64:65])), name
+        flat = torch.full((x.numel() + 1,), SENTINEL, device="cuda")
+        assert flat.data_ptr() % 16 == 0
+        flat[1:] = x.reshape(-1)
+        shifted = run(env, f, "predict_interactions", flat[1:].view(x.shape), dims=2, shift=1)
+        assert np.array_equal(se.bits(shifted), se.bits(got)), f"{name}: misaligned output and data"
+        f.close()
+
+
+@pytest.mark.parametrize("name", ["multi:sum", "covers:mixed"])
+def test_one_handle_serves_contribs_and_interactions_in_both_forms(env, unforced, name):
+    """contribs=True, interactions=True: TreeSHAP reads compact ids (LDS form) or columns (in place), the interaction kernel its
+    own column tables in either.  predict_interactions gives emulate's bits in both forms, those of the interactions-only
+    handle; predict_contribs on the same handle keeps the bits of the contribs-only handle of its form"""
+    ta, torch = env
+    c = oe.inter_reference(name)
+    shap = oe.reference(name)
+    x = torch.from_numpy(c["data"].copy()).cuda()
+    only = handle(env, c, interactions=True)
+    want = run(env, only, "predict_interactions", x, dims=2)
+    only.close()
+    se.assert_same_bits(want, c["emulate"], f"{name}: the interactions-only handle against emulate")
+    for forced in FORMS:
+        label = f"{name} {'in place' if forced else 'unforced'}"
+        both = handle(env, c, unforced, forced, contribs=True, interactions=True)
+        alone = handle(env, c, unforced, forced, contribs=True)
+        for _ in range(2):  # (the two calls do not disturb each other's tables)
+            assert np.array_equal(se.bits(run(env, both, "predict_interactions", x, dims=2)), se.bits(want)), f"{label}: interactions"
+            phi = run(env, both, "predict_contribs", x)
+            assert np.array_equal(se.bits(phi), se.bits(run(env, alone, "predict_contribs", x))), f"{label}: contribs"
+            se.assert_same_bits(phi, shap["emulate"], f"{label}: contribs against emulate")
+        both.close()
+        alone.close()
