@@ -491,6 +491,43 @@ tahoe_status tahoe_oblivious_forest_create_ex(tahoe_forest **out, const int32_t 
                                               const float *leaf_values, const float *leaf_covers,
                                               const tahoe_forest_params *params, int leaf_dim, unsigned flags);
 
+/* ---- vector-leaf forests: irregular trees whose leaves hold K = leaf_dim values (scikit-learn's RandomForestClassifier,
+ * ExtraTreesClassifier, DecisionTreeClassifier and multi-output regressors; XGBoost multi_strategy = "multi_output_tree"); no
+ * counterpart in the reference. ----
+ * trees and nodes are exactly what tahoe_sparse_forest_create takes: root offsets ascending, params->num_nodes the total, an
+ * internal node carries val = threshold and bits = fid | def_left<<30, its children are left_idx and left_idx + 1 relative to
+ * the root.  At a leaf (is_leaf<<31) val is ignored and left_idx is the index of the leaf's vector: leaf_values[left_idx * K ..
+ * + K), in [0, num_leaf_vectors).  Leaves may share a vector, and the vectors may come in any order.  Of `params`, num_nodes,
+ * num_trees, num_cols, output, threshold, global_bias and missing are used; depth, algo and strategy are ignored.
+ * Every node applies the rule of tahoe_forest_predict to the row's value x of its feature: fabsf(x - missing) <= 1e-6f takes the
+ * default branch (right iff !def_left), NaN goes left, else right iff x >= val.  margin[row][k] is the float32 sum from +0.0f
+ * over trees 0..T-1 in order of the row's leaf vector element k -- bit for bit what tahoe_sparse_forest_create_ex(num_classes =
+ * K) gives on the T x K-tree expansion whose tree t * K + k is tree t with val = leaf_values[left_idx * K + k] at its leaves,
+ * and with K == 1 what tahoe_sparse_forest_create gives.
+ * Output bits: K == 1 as tahoe_sparse_forest_create; K > 1 the contract of tahoe_forest_create_multiclass with C = K, AVG
+ * dividing by (float)num_trees (every tree feeds every class; the expansion has num_trees / C = T, so the two agree).
+ * tahoe_forest_num_classes returns K.
+ * Checks, all before a device is touched: NULL out / params, NULL trees / nodes with num_trees > 0, NULL leaf_values with
+ * num_leaf_vectors > 0, num_trees < 0, num_nodes < 0, num_leaf_vectors < 0, leaf_dim outside [1, 1024], num_cols < 0 or unknown
+ * output bits, the output combinations tahoe_forest_create_multiclass refuses (SOFTMAX with K == 1 or with SIGMOID, THRESHOLD with
+ * K > 1): TAHOE_ERR_INVALID_ARG; the structure checks of tahoe_sparse_forest_create (ascending roots, children after the node and
+ * inside the tree, fid < num_cols): TAHOE_ERR_INVALID_FOREST; a leaf whose left_idx is outside [0, num_leaf_vectors):
+ * TAHOE_ERR_INVALID_FOREST naming the tree and the node (relative to its root).
+ * The handle keeps 16 bytes per node (the 12-byte node padded: one aligned gather per step), 4 bytes per tree and the leaf table
+ * (tahoe_forest_info.device_bytes; depth = the deepest leaf, is_sparse = 0).  Served: tahoe_forest_predict, _predict_raw,
+ * _predict_leaf_idx (leaf_dev[row * num_trees + tree] = the leaf node's index relative to its root, as on a sparse handle; sums
+ * rows x K), _reserve (nothing to size: predict allocates nothing and can be captured), set/get_strategy, get_kernel_form,
+ * get_info, check, profiling, destroy.  Strategies: DIRECT (kernel form TAHOE_VECTOR_FORM_DIRECT: features from global memory,
+ * any num_cols), ROWTILE (TAHOE_VECTOR_FORM_TILE: one wave per 64-row float32 tile in LDS; needs 256 x num_cols bytes of LDS),
+ * AUTO = ROWTILE when the tile fits, else DIRECT; TILEBLOCK, TILERING and QRING are TAHOE_ERR_UNSUPPORTED.
+ * Out of scope, TAHOE_ERR_UNSUPPORTED with nothing launched and a text that names the call and says "vector-leaf":
+ * tahoe_forest_predict_accumulate, _predict_host, _predict_csr, _reserve_csr (and _get_csr_plan: form TAHOE_FORM_NONE),
+ * _set_stages, _predict_staged (_get_staged_strategy: 0), _predict_contribs, _predict_contribs_approx, _predict_interactions,
+ * _set_background and _predict_contribs_interventional.  Categorical splits are not represented. */
+tahoe_status tahoe_vector_forest_create(tahoe_forest **out, const int32_t *trees, const tahoe_sparse_node *nodes,
+                                        const float *leaf_values, int64_t num_leaf_vectors, const tahoe_forest_params *params,
+                                        int leaf_dim);
+
 /* dense2sparse (BaseTahoeTest.h:728-764).  *nodes_out / *trees_out: tahoe_free_host. */
 tahoe_status tahoe_dense_to_sparse(const tahoe_dense_node *dense, int num_trees, int depth,
                                    tahoe_sparse_node **nodes_out, int32_t **trees_out, size_t *num_nodes_out);
@@ -699,6 +736,12 @@ enum {
 enum {
     TAHOE_OBLIVIOUS_FORM_DIRECT = 24,     /* oblivious_direct_kernel: features from global memory */
     TAHOE_OBLIVIOUS_FORM_TILE = 25        /* oblivious_tile_kernel: one wave per 64-row float32 tile */
+};
+/* The kernel forms of a vector-leaf handle (tahoe_vector_forest_create).  26 stays unassigned for the same reason: the first
+ * value past TAHOE_OBLIVIOUS_FORM_TILE has no name (tahoe_kernel_form_name(26) == "?"). */
+enum {
+    TAHOE_VECTOR_FORM_DIRECT = 27,        /* vector_direct_kernel: features from global memory */
+    TAHOE_VECTOR_FORM_TILE = 28           /* vector_tile_kernel: one wave per 64-row float32 tile */
 };
 int tahoe_forest_get_kernel_form(const tahoe_forest *f, size_t rows);
 const char *tahoe_kernel_form_name(int form);

@@ -148,6 +148,7 @@ _PROTOS = {
                                             C.POINTER(CategoricalSplits)]),
     "tahoe_oblivious_forest_create": (_i, [C.POINTER(_vp), _vp, _vp, _vp, C.POINTER(ForestParams), _i]),
     "tahoe_oblivious_forest_create_ex": (_i, [C.POINTER(_vp), _vp, _vp, _vp, _vp, C.POINTER(ForestParams), _i, C.c_uint]),
+    "tahoe_vector_forest_create": (_i, [C.POINTER(_vp), _vp, _vp, _vp, C.c_int64, C.POINTER(ForestParams), _i]),
     "tahoe_dense_to_sparse": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz)]),
     "tahoe_dense_to_sparse_ex": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz)]),
     "tahoe_synth_sparse_forest": (_i, [_vp, _vp, C.POINTER(_sz), _i, _i, _i, _i, _f, _i, C.c_uint64]),
@@ -835,6 +836,40 @@ class ObliviousForest(Forest):
             _check(lib.tahoe_oblivious_forest_create(C.byref(self._h), dp.ctypes.data, splits.ctypes.data if nsplits else None,
                                                      lv.ctypes.data, C.byref(self.params), leaf_dim), "tahoe_oblivious_forest_create")
         self.num_trees, self.depth, self.num_cols = int(depths.size), int(depths.max()) if depths.size else 0, num_cols
+        self.num_classes = lib.tahoe_forest_num_classes(self._h)
+
+
+# ---- vector-leaf forests: irregular trees whose leaves hold leaf_dim values ----
+class VectorForest(Forest):
+    """tahoe_vector_forest_create: nodes[SPARSE_NODE_DTYPE] + root offsets as SparseForest takes them, except that a leaf's
+    left_idx is the index of its vector in leaf_values ([L, K], or flat with leaf_dim given) and its val is ignored.  Leaves may
+    share a vector.  predict* as Forest: [rows] for K == 1, [rows, K] otherwise; AVG divides by the number of trees; leaf
+    indices are relative to the tree's root, as on a SparseForest."""
+
+    def __init__(self, nodes: np.ndarray, trees: np.ndarray, leaf_values, num_cols: int, leaf_dim: int = None,
+                 missing: float = 0.0, output: int = OUT_RAW, threshold: float = 0.5, global_bias: float = 0.0):
+        nodes = np.ascontiguousarray(nodes, dtype=SPARSE_NODE_DTYPE)
+        trees = np.ascontiguousarray(trees, dtype=np.int32).reshape(-1)
+        lv = np.asarray(leaf_values, dtype=np.float32)
+        if leaf_dim is None:
+            if lv.ndim != 2:
+                raise ValueError("leaf_values must be [L, K], or flat with leaf_dim given")
+            leaf_dim = int(lv.shape[1])
+        elif lv.ndim == 2 and lv.shape[1] != leaf_dim:
+            raise ValueError(f"leaf_values.shape[1] = {lv.shape[1]} != leaf_dim = {leaf_dim}")
+        elif lv.ndim > 2:
+            raise ValueError("leaf_values must be [L, K], or flat with leaf_dim given")
+        leaves = np.ascontiguousarray(lv).reshape(-1)
+        if leaf_dim >= 1 and leaves.size % leaf_dim != 0:  # (leaf_dim < 1: the C function refuses with its own text)
+            raise ValueError(f"leaf_values.size = {leaves.size} is no multiple of leaf_dim = {leaf_dim}")
+        num_vectors = leaves.size // leaf_dim if leaf_dim >= 1 else 0
+        self.params = ForestParams(int(nodes.size), 0, int(trees.size), num_cols, 0, output, threshold, global_bias, 0, missing)
+        self._h = _vp()
+        _check(lib.tahoe_vector_forest_create(C.byref(self._h), trees.ctypes.data if trees.size else None,
+                                              nodes.ctypes.data if nodes.size else None,
+                                              leaves.ctypes.data if leaves.size else None, num_vectors, C.byref(self.params),
+                                              leaf_dim), "tahoe_vector_forest_create")
+        self.num_trees, self.depth, self.num_cols = int(trees.size), 0, num_cols
         self.num_classes = lib.tahoe_forest_num_classes(self._h)
 
 

@@ -283,6 +283,7 @@ extern "C" tahoe_status tahoe_forest_predict_contribs_approx(tahoe_forest *f, fl
         return oblivious_predict_shap(f, TAHOE_CREATE_APPROX_CONTRIBS, phi_dev, data_dev, rows, (hipStream_t)stream,
                                       "tahoe_forest_predict_contribs_approx");
     if (const tahoe_status st = refuse_oblivious(f, "tahoe_forest_predict_contribs_approx")) return st;
+    if (const tahoe_status st = refuse_vector(f, "tahoe_forest_predict_contribs_approx")) return st;
     if (!f->ap)
         return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_contribs_approx: the handle was created without "
                                            "TAHOE_CREATE_APPROX_CONTRIBS and has no node deltas");

@@ -113,6 +113,7 @@ tahoe_status tahoe_forest_predict_csr(tahoe_forest *f, float *preds_dev, const i
     if (nnz && (!indices_dev || !values_dev)) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_csr: null indices_dev / values_dev");
     if (nnz > (size_t)INT64_MAX) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_csr: nnz %zu does not fit indptr's int64", nnz);
     if (const tahoe_status st = refuse_oblivious(f, "tahoe_forest_predict_csr")) return st;
+    if (const tahoe_status st = refuse_vector(f, "tahoe_forest_predict_csr")) return st;
     if (rows == 0) return TAHOE_OK;
     hipStream_t stream = (hipStream_t)stream_;
     DeviceGuard on_device(f->device);
@@ -152,6 +153,7 @@ tahoe_status tahoe_forest_reserve_csr(tahoe_forest *f, size_t rows, size_t nnz)
 {
     if (!f) return fail(TAHOE_ERR_INVALID_ARG, "null forest");
     if (const tahoe_status st = refuse_oblivious(f, "tahoe_forest_reserve_csr")) return st;
+    if (const tahoe_status st = refuse_vector(f, "tahoe_forest_reserve_csr")) return st;
     // Which path a later call takes depends on its own rows and nnz, so the fallback's workspace is sized whatever `nnz` says: the
     // chunk buffer, and what the handle's kernels need for a batch of one chunk.  The fused kernels need no workspace.
     (void)nnz;
@@ -163,10 +165,10 @@ tahoe_status tahoe_forest_reserve_csr(tahoe_forest *f, size_t rows, size_t nnz)
 tahoe_status tahoe_forest_get_csr_plan(const tahoe_forest *f, size_t rows, size_t nnz, int *form, size_t *chunk_rows)
 {
     if (!f || !form || !chunk_rows) return fail(TAHOE_ERR_INVALID_ARG, "null argument");
-    if (f->ob) {  // no CSR path: nothing would be launched
+    if (f->ob || f->vl) {  // no CSR path: nothing would be launched
         *form = TAHOE_FORM_NONE;
         *chunk_rows = 0;
-        return refuse_oblivious(f, "tahoe_forest_get_csr_plan");
+        return f->ob ? refuse_oblivious(f, "tahoe_forest_get_csr_plan") : refuse_vector(f, "tahoe_forest_get_csr_plan");
     }
     const int fused = csr_fused_strategy(f, rows, nnz);
     *chunk_rows = fused >= 0 ? 0 : csr_chunk_cap(f);

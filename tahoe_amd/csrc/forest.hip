@@ -823,6 +823,10 @@ static int resolve_strategy(const tahoe_forest *f, size_t rows)
         if (f->strategy != TAHOE_STRATEGY_AUTO) return f->strategy;
         return oblivious_tile_fits(f) ? TAHOE_STRATEGY_ROWTILE : TAHOE_STRATEGY_DIRECT;
     }
+    if (f->vl) {  // vector-leaf handle: the same two forms
+        if (f->strategy != TAHOE_STRATEGY_AUTO) return f->strategy;
+        return vector_tile_fits(f) ? TAHOE_STRATEGY_ROWTILE : TAHOE_STRATEGY_DIRECT;
+    }
     if (f->sp) {  // sparse handle: QRING = quantised 192-row tile + tree tops in LDS, TILEBLOCK = 64-row float32 tile + tree
                   // tops, ROWTILE = tile only, DIRECT = neither
         if (f->strategy == TAHOE_STRATEGY_DIRECT) return TAHOE_STRATEGY_DIRECT;
@@ -868,6 +872,12 @@ tahoe_status strategy_available(const tahoe_forest *f, int strategy)
     if (f->ob) {
         if (strategy > TAHOE_STRATEGY_ROWTILE || (strategy == TAHOE_STRATEGY_ROWTILE && !oblivious_tile_fits(f)))
             return fail(TAHOE_ERR_UNSUPPORTED, "an oblivious forest runs AUTO, DIRECT or ROWTILE (a 64-row tile of %d columns in %d B "
+                                               "of LDS)", f->p.num_cols, f->lds_limit);
+        return TAHOE_OK;
+    }
+    if (f->vl) {
+        if (strategy > TAHOE_STRATEGY_ROWTILE || (strategy == TAHOE_STRATEGY_ROWTILE && !vector_tile_fits(f)))
+            return fail(TAHOE_ERR_UNSUPPORTED, "a vector-leaf forest runs AUTO, DIRECT or ROWTILE (a 64-row tile of %d columns in %d B "
                                                "of LDS)", f->p.num_cols, f->lds_limit);
         return TAHOE_OK;
     }
@@ -961,6 +971,9 @@ static tahoe_status launch_traversal(tahoe_forest *f, float *sums, uint32_t *lea
     } else if (f->ob) {
         const tahoe_status os = oblivious_launch(f, sums, leaf_out, data, rows, stream, strategy, sums_in);
         if (os != TAHOE_OK) return os;
+    } else if (f->vl) {
+        const tahoe_status vs = vector_launch(f, sums, leaf_out, data, rows, stream, strategy);
+        if (vs != TAHOE_OK) return vs;
     } else if (f->sp) {
         const tahoe_status ss = sparse_launch(f, sums, leaf_out, data, rows, stream, strategy, sums_in, csr);
         if (ss != TAHOE_OK) return ss;
@@ -1170,7 +1183,7 @@ tahoe_status predict_rows(tahoe_forest *f, float *preds, const float *data, size
 // 0: no stages are set, or the forced strategy (QRING, TILERING, dense TILEBLOCK) has no staged form.
 static int staged_strategy(const tahoe_forest *f)
 {
-    if (!f->stages_dev) return 0;  // (an oblivious handle never has stages)
+    if (!f->stages_dev) return 0;  // (an oblivious or vector-leaf handle never has stages)
     const int forced = f->strategy;  // (tahoe_forest_set_strategy has checked that the handle can run it)
     if (forced == TAHOE_STRATEGY_DIRECT || forced == TAHOE_STRATEGY_ROWTILE) return forced;
     if (f->sp) {
@@ -1495,6 +1508,7 @@ void tahoe_forest_destroy(tahoe_forest *f)
     qring_destroy(f);
     sparse_destroy(f);
     oblivious_destroy(f);
+    vector_destroy(f);
     widef_destroy(f);
     interventional_destroy(f);
     contribs_destroy(f);
@@ -1518,6 +1532,7 @@ tahoe_status tahoe_forest_predict_accumulate(tahoe_forest *f, float *sums_dev, c
 {
     if (!f || (rows && (!sums_dev || !data_dev)))
         return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_accumulate: null argument");
+    if (const tahoe_status s = refuse_vector(f, "tahoe_forest_predict_accumulate")) return s;
     if (f->num_classes > 1) return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_accumulate: not served on a multi-class handle");
     return launch_traversal(f, sums_dev, nullptr, data_dev, rows, (hipStream_t)stream, sums_dev);
 }
@@ -1535,6 +1550,7 @@ tahoe_status tahoe_forest_set_stages(tahoe_forest *f, const int32_t *rounds, int
     // every check here runs before a device is touched
     if (!f) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_set_stages: null forest");
     if (const tahoe_status s = refuse_oblivious(f, "tahoe_forest_set_stages")) return s;
+    if (const tahoe_status s = refuse_vector(f, "tahoe_forest_set_stages")) return s;
     if (num_stages < 0) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_set_stages: num_stages must be non-negative, got %d", num_stages);
     if (num_stages > 0 && !rounds) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_set_stages: rounds is null with num_stages %d", num_stages);
     for (int s = 0; s < num_stages; ++s) {
@@ -1583,6 +1599,7 @@ tahoe_status tahoe_forest_predict_staged(tahoe_forest *f, float *out_dev, const 
 {
     if (!f) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_staged: null forest");
     if (const tahoe_status s = refuse_oblivious(f, "tahoe_forest_predict_staged")) return s;
+    if (const tahoe_status s = refuse_vector(f, "tahoe_forest_predict_staged")) return s;
     if (!f->stages_dev)
         return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_staged: no stages are set (tahoe_forest_set_stages)");
     const int strategy = staged_strategy(f);
@@ -1640,7 +1657,7 @@ tahoe_status tahoe_forest_set_strategy(tahoe_forest *f, int strategy)
 tahoe_status tahoe_forest_reserve(tahoe_forest *f, size_t rows)
 {
     if (!f) return fail(TAHOE_ERR_INVALID_ARG, "null forest");
-    if (f->ob) return TAHOE_OK;  // an oblivious handle has no workspace: predict allocates nothing
+    if (f->ob || f->vl) return TAHOE_OK;  // an oblivious or vector-leaf handle has no workspace: predict allocates nothing
     const tahoe_status qs = qring_reserve(f, rows);
     if (qs != TAHOE_OK) return qs;
     return widef_reserve(f, rows);  // (the wide-row float32 form's leaf-value workspace, when it streams rows)
@@ -1670,6 +1687,7 @@ int tahoe_forest_get_kernel_form(const tahoe_forest *f, size_t rows)
     if (!f) return -1;
     const int strategy = resolve_strategy(f, rows);
     if (f->ob) return strategy == TAHOE_STRATEGY_ROWTILE ? TAHOE_OBLIVIOUS_FORM_TILE : TAHOE_OBLIVIOUS_FORM_DIRECT;
+    if (f->vl) return strategy == TAHOE_STRATEGY_ROWTILE ? TAHOE_VECTOR_FORM_TILE : TAHOE_VECTOR_FORM_DIRECT;
     if (f->sp) {
         switch (strategy) {
         case TAHOE_STRATEGY_QRING: return TAHOE_FORM_SPARSE_QRING;
@@ -1698,7 +1716,7 @@ const char *tahoe_kernel_form_name(int form)
                                         "qring_split", "qring_columns", "qring_wide", "qring_gx", "sparse_direct",
                                         "sparse_rowtile", "sparse_top", "sparse_qring", "qring_region8", "qring_region6",
                                         "csr_rowtile", "csr_sparse_rowtile", "csr_sparse_top", "?" /* 23: unassigned */, "oblivious_direct",
-                                        "oblivious_tile"};
+                                        "oblivious_tile", "?" /* 26: unassigned */, "vector_direct", "vector_tile"};
     return form >= 0 && form < (int)(sizeof(names) / sizeof(names[0])) ? names[form] : "?";
 }
 
@@ -1715,7 +1733,7 @@ tahoe_status tahoe_forest_get_info(const tahoe_forest *f, tahoe_forest_info *inf
     info->num_cus = f->num_cus;
     if (f->sp) return TAHOE_OK;
     info->depth = f->p.depth;
-    if (f->ob) return TAHOE_OK;  // (depth: the largest of the trees)
+    if (f->ob || f->vl) return TAHOE_OK;  // (depth: the largest of the trees)
     info->lds_levels = f->lds_levels;
     info->lds_bytes_per_block = rowtile_fits(f) ? rowtile_lds_bytes(f->p.num_cols, f->lds_levels) : 0;
     info->top_levels = f->top_levels;

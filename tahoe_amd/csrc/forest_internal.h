@@ -20,6 +20,7 @@ struct tahoe_cstate;  // TreeSHAP path tables (TAHOE_CREATE_CONTRIBS), owned by 
 struct tahoe_istate;  // background of interventional TreeSHAP (tahoe_forest_set_background), owned by interventional.hip
 struct tahoe_astate;  // Saabas node deltas (TAHOE_CREATE_APPROX_CONTRIBS), owned by approx.hip
 struct tahoe_ostate;  // oblivious (symmetric) forest, owned by oblivious.hip
+struct tahoe_vstate;  // vector-leaf forest, owned by vector.hip
 
 namespace tahoe {
 
@@ -114,6 +115,7 @@ struct tahoe_forest {
     tahoe_astate *ap = nullptr;    // non-null: created with TAHOE_CREATE_APPROX_CONTRIBS (approx.hip)
     tahoe_ostate *ob = nullptr;    // non-null: this handle is an oblivious forest (oblivious.hip); the dense views are unused,
                                    // num_classes is the leaf dimension K and class_trees = num_trees (every tree feeds every class)
+    tahoe_vstate *vl = nullptr;    // non-null: this handle is a vector-leaf forest (vector.hip); num_classes and class_trees as with ob
     size_t device_bytes = 0;
     // Multi-class handle (tahoe_forest_create_multiclass): the trees are stored class-major -- internal tree p belongs to class
     // p / class_trees and is original tree (p % class_trees) * num_classes + p / class_trees -- and every consumer writes
@@ -532,11 +534,23 @@ inline tahoe_status refuse_oblivious(const tahoe_forest *f, const char *fn)
     if (!f->ob) return TAHOE_OK;
     return fail(TAHOE_ERR_UNSUPPORTED, "%s: not served on an oblivious handle (tahoe_oblivious_forest_create)", fn);
 }
+// vector-leaf forests (vector.hip): strategy ROWTILE = vector_tile_kernel, DIRECT = vector_direct_kernel
+bool vector_tile_fits(const tahoe_forest *f);
+tahoe_status vector_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data, size_t rows, hipStream_t stream,
+                           int strategy);
+void vector_destroy(tahoe_forest *f);
+// The refusal of the entry points a vector-leaf handle does not serve (fn: the entry point's name); TAHOE_OK on every other handle
+inline tahoe_status refuse_vector(const tahoe_forest *f, const char *fn)
+{
+    if (!f->vl) return TAHOE_OK;
+    return fail(TAHOE_ERR_UNSUPPORTED, "%s: not served on a vector-leaf handle (tahoe_vector_forest_create)", fn);
+}
 // The first refusal of every TreeSHAP entry point (fn: its name): TAHOE_ERR_UNSUPPORTED unless the handle has path tables
 inline tahoe_status need_path_tables(const tahoe_forest *f, const char *fn)
 {
     if (f->cs) return TAHOE_OK;
     if (const tahoe_status s = refuse_oblivious(f, fn)) return s;
+    if (const tahoe_status s = refuse_vector(f, fn)) return s;
     if (f->sp)
         return fail(TAHOE_ERR_UNSUPPORTED, "%s: a sparse handle created without TAHOE_CREATE_CONTRIBS has no node covers and no path "
                                            "tables (tahoe_sparse_forest_create_ex)", fn);

@@ -163,6 +163,7 @@ extern "C" tahoe_status tahoe_forest_predict_host(tahoe_forest *f, float *preds_
     if (!f || (rows && (!preds_host || !data_host)))
         return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_host: null argument");
     if (const tahoe_status st = refuse_oblivious(f, "tahoe_forest_predict_host")) return st;
+    if (const tahoe_status st = refuse_vector(f, "tahoe_forest_predict_host")) return st;
     if (f->num_classes > 1) return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_host: not served on a multi-class handle");
     if (rows == 0) return TAHOE_OK;
     if (chunk_rows == 0) chunk_rows = auto_chunk_rows(f, rows);
