@@ -522,11 +522,35 @@ tahoe_status tahoe_oblivious_forest_create_ex(tahoe_forest **out, const int32_t 
  * AUTO = ROWTILE when the tile fits, else DIRECT; TILEBLOCK, TILERING and QRING are TAHOE_ERR_UNSUPPORTED.
  * Out of scope, TAHOE_ERR_UNSUPPORTED with nothing launched and a text that names the call and says "vector-leaf":
  * tahoe_forest_predict_accumulate, _predict_host, _predict_csr, _reserve_csr (and _get_csr_plan: form TAHOE_FORM_NONE),
- * _set_stages, _predict_staged (_get_staged_strategy: 0), _predict_contribs, _predict_contribs_approx, _predict_interactions,
- * _set_background and _predict_contribs_interventional.  Categorical splits are not represented. */
+ * _set_stages, _predict_staged (_get_staged_strategy: 0), _predict_contribs_approx, _predict_interactions, _set_background and
+ * _predict_contribs_interventional; _predict_contribs unless the handle comes from tahoe_vector_forest_create_ex with
+ * TAHOE_CREATE_CONTRIBS.  Categorical splits are not represented. */
 tahoe_status tahoe_vector_forest_create(tahoe_forest **out, const int32_t *trees, const tahoe_sparse_node *nodes,
                                         const float *leaf_values, int64_t num_leaf_vectors, const tahoe_forest_params *params,
                                         int leaf_dim);
+/* The same handle with path-dependent TreeSHAP.  flags: 0 or TAHOE_CREATE_CONTRIBS; with flags == 0 covers is ignored and the call
+ * is tahoe_vector_forest_create (which is this call with NULL, 0), bit for bit.  With the flag covers[i] is the cover of nodes[i]
+ * (num_nodes floats; scikit-learn's tree_.weighted_n_node_samples).
+ * Checks, before a device is touched and after those of tahoe_vector_forest_create, with the codes and texts of
+ * tahoe_sparse_forest_create_ex: another flag bit: TAHOE_ERR_INVALID_ARG naming the bit; the flag with covers == NULL:
+ * TAHOE_ERR_INVALID_ARG; a reachable internal node whose children's covers are not finite, negative or sum to 0:
+ * TAHOE_ERR_INVALID_FOREST naming the tree and the node; a reachable leaf whose path has more than 31 distinct features:
+ * TAHOE_ERR_UNSUPPORTED naming the tree.  With a device: num_cols above a fifth of the LDS in floats (20 B per column):
+ * TAHOE_ERR_UNSUPPORTED.
+ * Served with the flag: tahoe_forest_predict_contribs as defined there (predict's branch rule, repeated features merged,
+ * contributions to the margin, zero fractions below 2^-121 count as 0), phi_dev rows x K x (num_cols + 1), bias last; with AVG every
+ * column is divided by (float)num_trees.  phi[row][k] is bit for bit what tahoe_sparse_forest_create_ex(num_classes = K,
+ * TAHOE_CREATE_CONTRIBS) gives for class k on the T x K-tree expansion above when every copy of tree t carries tree t's covers;
+ * with K == 1 the bits of the sparse handle on the same trees, bias column included.  Bias column k = sum_t E_t[k] / (AVG ? T : 1)
+ * + global_bias in float64, rounded once, E_t[k] the cover-weighted mean of element k over tree t's leaves.  The K outputs of a
+ * leaf share one evaluation of its path; results do not depend on the batch, on how many outputs share an evaluation or on the
+ * strategy (which the call does not use).  The call is asynchronous, allocates nothing and can be captured.
+ * The tables count in device_bytes: 20 bytes per path element in 64-lane bins, once for the forest -- not once per output as on
+ * the expansion -- and 4 K bytes of bias.  tahoe_forest_predict_interactions, _set_background, _predict_contribs_interventional
+ * and _predict_contribs_approx stay TAHOE_ERR_UNSUPPORTED as above on every vector-leaf handle. */
+tahoe_status tahoe_vector_forest_create_ex(tahoe_forest **out, const int32_t *trees, const tahoe_sparse_node *nodes,
+                                           const float *leaf_values, int64_t num_leaf_vectors, const float *covers,
+                                           const tahoe_forest_params *params, int leaf_dim, unsigned flags);
 
 /* dense2sparse (BaseTahoeTest.h:728-764).  *nodes_out / *trees_out: tahoe_free_host. */
 tahoe_status tahoe_dense_to_sparse(const tahoe_dense_node *dense, int num_trees, int depth,

@@ -149,6 +149,7 @@ _PROTOS = {
     "tahoe_oblivious_forest_create": (_i, [C.POINTER(_vp), _vp, _vp, _vp, C.POINTER(ForestParams), _i]),
     "tahoe_oblivious_forest_create_ex": (_i, [C.POINTER(_vp), _vp, _vp, _vp, _vp, C.POINTER(ForestParams), _i, C.c_uint]),
     "tahoe_vector_forest_create": (_i, [C.POINTER(_vp), _vp, _vp, _vp, C.c_int64, C.POINTER(ForestParams), _i]),
+    "tahoe_vector_forest_create_ex": (_i, [C.POINTER(_vp), _vp, _vp, _vp, C.c_int64, _vp, C.POINTER(ForestParams), _i, C.c_uint]),
     "tahoe_dense_to_sparse": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz)]),
     "tahoe_dense_to_sparse_ex": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz)]),
     "tahoe_synth_sparse_forest": (_i, [_vp, _vp, C.POINTER(_sz), _i, _i, _i, _i, _f, _i, C.c_uint64]),
@@ -844,10 +845,13 @@ class VectorForest(Forest):
     """tahoe_vector_forest_create: nodes[SPARSE_NODE_DTYPE] + root offsets as SparseForest takes them, except that a leaf's
     left_idx is the index of its vector in leaf_values ([L, K], or flat with leaf_dim given) and its val is ignored.  Leaves may
     share a vector.  predict* as Forest: [rows] for K == 1, [rows, K] otherwise; AVG divides by the number of trees; leaf
-    indices are relative to the tree's root, as on a SparseForest."""
+    indices are relative to the tree's root, as on a SparseForest.  covers (float32, one per node; scikit-learn's
+    tree_.weighted_n_node_samples) and contribs=True go through tahoe_vector_forest_create_ex: predict_contribs then gives the
+    TreeSHAP values of every output, [rows, K, num_cols + 1] ([rows, num_cols + 1] for K == 1)."""
 
     def __init__(self, nodes: np.ndarray, trees: np.ndarray, leaf_values, num_cols: int, leaf_dim: int = None,
-                 missing: float = 0.0, output: int = OUT_RAW, threshold: float = 0.5, global_bias: float = 0.0):
+                 missing: float = 0.0, output: int = OUT_RAW, threshold: float = 0.5, global_bias: float = 0.0, covers=None,
+                 contribs: bool = False):
         nodes = np.ascontiguousarray(nodes, dtype=SPARSE_NODE_DTYPE)
         trees = np.ascontiguousarray(trees, dtype=np.int32).reshape(-1)
         lv = np.asarray(leaf_values, dtype=np.float32)
@@ -865,10 +869,21 @@ class VectorForest(Forest):
         num_vectors = leaves.size // leaf_dim if leaf_dim >= 1 else 0
         self.params = ForestParams(int(nodes.size), 0, int(trees.size), num_cols, 0, output, threshold, global_bias, 0, missing)
         self._h = _vp()
-        _check(lib.tahoe_vector_forest_create(C.byref(self._h), trees.ctypes.data if trees.size else None,
-                                              nodes.ctypes.data if nodes.size else None,
-                                              leaves.ctypes.data if leaves.size else None, num_vectors, C.byref(self.params),
-                                              leaf_dim), "tahoe_vector_forest_create")
+        if covers is not None or contribs:
+            cv = None if covers is None else np.ascontiguousarray(covers, dtype=np.float32).reshape(-1)
+            if cv is not None and cv.size != nodes.size:
+                raise ValueError("covers.size != nodes.size")
+            _check(lib.tahoe_vector_forest_create_ex(C.byref(self._h), trees.ctypes.data if trees.size else None,
+                                                     nodes.ctypes.data if nodes.size else None,
+                                                     leaves.ctypes.data if leaves.size else None, num_vectors,
+                                                     cv.ctypes.data if cv is not None else None, C.byref(self.params),
+                                                     leaf_dim, CREATE_CONTRIBS if contribs else 0),
+                   "tahoe_vector_forest_create_ex")
+        else:
+            _check(lib.tahoe_vector_forest_create(C.byref(self._h), trees.ctypes.data if trees.size else None,
+                                                  nodes.ctypes.data if nodes.size else None,
+                                                  leaves.ctypes.data if leaves.size else None, num_vectors, C.byref(self.params),
+                                                  leaf_dim), "tahoe_vector_forest_create")
         self.num_trees, self.depth, self.num_cols = int(trees.size), 0, num_cols
         self.num_classes = lib.tahoe_forest_num_classes(self._h)
 

@@ -19,17 +19,7 @@
 namespace tahoe {
 
 // 1 / k, correctly rounded (constant folding), for the uniform factors of the recursions
-__constant__ float c_inv[34] = {0.0f,        1.0f,        1.0f / 2.0f,  1.0f / 3.0f,  1.0f / 4.0f,  1.0f / 5.0f,  1.0f / 6.0f,
-                                1.0f / 7.0f,  1.0f / 8.0f,  1.0f / 9.0f,  1.0f / 10.0f, 1.0f / 11.0f, 1.0f / 12.0f, 1.0f / 13.0f,
-                                1.0f / 14.0f, 1.0f / 15.0f, 1.0f / 16.0f, 1.0f / 17.0f, 1.0f / 18.0f, 1.0f / 19.0f, 1.0f / 20.0f,
-                                1.0f / 21.0f, 1.0f / 22.0f, 1.0f / 23.0f, 1.0f / 24.0f, 1.0f / 25.0f, 1.0f / 26.0f, 1.0f / 27.0f,
-                                1.0f / 28.0f, 1.0f / 29.0f, 1.0f / 30.0f, 1.0f / 31.0f, 1.0f / 32.0f, 1.0f / 33.0f};
-
-// value of lane - 1 (0 in lane 0): DPP wave_shr:1
-__device__ __forceinline__ float from_left_lane(float v)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138, 0xf, 0xf, false));
-}
+__constant__ float c_inv[34] = TAHOE_CONTRIB_INV_TABLE;
 
 // One workgroup = a tile of R rows (staged in LDS) x all bins; wave w evaluates bins w, w + 4, ... of each class into its own
 // slab [R][F] of LDS; the four slabs are then summed in wave order and written out.  Every row sees the same operations in the
@@ -439,12 +429,20 @@ struct Elem {
     }
 };
 
+inline uint32_t float_word(float v)
+{
+    uint32_t w;
+    memcpy(&w, &v, 4);
+    return w;
+}
+
 // The two node formats as one tree for tree_paths: val, bits (fid[0:29] | def_left << 30 | is_leaf << 31 in both), the left
-// child (the right one follows it) and a node's cover.
+// child (the right one follows it), a node's cover, and what a leaf's root element carries in .x (leaf_word: the leaf value).
 struct DenseTree {
     const tahoe_dense_node *n;
     int cat(size_t) const { return -1; }
     float val(size_t i) const { return n[i].val; }
+    uint32_t leaf_word(size_t i) const { return float_word(n[i].val); }
     int32_t bits(size_t i) const { return n[i].bits; }
     size_t left(size_t i) const { return 2 * i + 1; }
     double cover(size_t i) const { return n[i].weight; }
@@ -463,9 +461,20 @@ struct SparseTree {
         return it != end && *it == g ? (int)(it - cats->node) : -1;
     }
     float val(size_t i) const { return n[i].val; }
+    uint32_t leaf_word(size_t i) const { return float_word(n[i].val); }
     int32_t bits(size_t i) const { return n[i].bits; }
     size_t left(size_t i) const { return (size_t)n[i].left_idx; }
     double cover(size_t i) const { return covers[i]; }
+};
+// A tree of a vector-leaf handle for tree_paths: a leaf's root element carries the index of the leaf's vector
+struct VectorTree : SparseTree {
+    uint32_t leaf_word(size_t i) const { return (uint32_t)n[i].left_idx; }
+};
+// ... and for tree_expect: element k of the leaf's vector as the leaf value
+struct VectorTreeK : SparseTree {
+    const float *leaves;
+    size_t K, k;
+    float val(size_t i) const { return ((n[i].bits >> 31) & 1) ? leaves[(size_t)n[i].left_idx * K + k] : n[i].val; }
 };
 
 // E_t: the sum over reachable leaves, pre-order (left before right), of leaf x the product of the cover ratios of its edges,
@@ -552,11 +561,10 @@ void tree_paths(const Tree &tree, TreePaths &out, const tahoe_categorical_splits
                 m.missing_ok = m.missing_ok && def_left;
             }
         }
-        const float leaf = tree.val(fr.node);
         const int ne = (int)el.size();
         if (ne == 0) continue;  // a root leaf: all of it is bias
         uint4 root;
-        memcpy(&root.x, &leaf, 4);
+        root.x = tree.leaf_word(fr.node);
         root.y = 0u;
         const float one = 1.0f;
         memcpy(&root.z, &one, 4);
@@ -626,39 +634,43 @@ void contribs_bias_sparse(const tahoe_forest *f, const int32_t *trees, const tah
     class_bias(f, expect, bias, div);
 }
 
-// The path tables from the paths of every tree (caller's tree numbering): packing, bias and LDS shapes.
-static tahoe_status build_tables(tahoe_forest *f, std::vector<TreePaths> &trees)
+// TAHOE_ERR_UNSUPPORTED unless a row tile and four slabs of one row each fit the LDS: 20 B per column
+static tahoe_status check_contrib_cols(const tahoe_forest *f)
 {
     const int F = f->p.num_cols;
-    // LDS: the row tile and four slabs, R rows each; R is the largest power of two <= 64 that fits 80 KiB (two workgroups
-    // per CU), else the whole LDS
-    size_t R = 64;
-    const size_t per_row = 5 * (size_t)F * sizeof(float);
-    while (R > 1 && R * per_row > 80 * 1024) R /= 2;
-    if (F > kContribMaxCols || per_row > (size_t)f->lds_limit)
+    if (F > kContribMaxCols || 5 * (size_t)F * sizeof(float) > (size_t)f->lds_limit)
         return fail(TAHOE_ERR_UNSUPPORTED, "TAHOE_CREATE_CONTRIBS needs 20 B of LDS per column (num_cols %d; device offers %d B)", F,
                     f->lds_limit);
+    return TAHOE_OK;
+}
 
-    const int C = f->num_classes;
-    const size_t Tc = (size_t)f->class_trees;
-
-    std::vector<uint4> h_elems;
-    std::vector<float> h_om;
-    std::vector<uint32_t> h_info;
-    // category sets: the pool (identical sets share one entry) and, per lane, 1 + the offset of its set's header
+// The paths of every tree packed into 64-lane bins, on the host
+struct PathBins {
+    std::vector<uint4> elems;
+    std::vector<float> om;
+    std::vector<uint32_t> info;
+    std::vector<uint32_t> set, pool;  // category sets: per lane 1 + the offset of its set's header, and the pool
+    std::vector<int> class_bins;
     bool any_sets = false;
+    size_t n_paths = 0, n_elems = 0;
+};
+
+// Next-fit packing of each class's paths, in tree order then leaf order: class c's trees are c, c + C, ... (Tc of them).  Padding
+// lanes, ranks, lengths, rounds and bin_info are set here; the trees' paths are released as they are packed.
+static void pack_paths(std::vector<TreePaths> &trees, int C, size_t Tc, PathBins &out)
+{
+    std::vector<uint4> &h_elems = out.elems;
+    std::vector<float> &h_om = out.om;
+    std::vector<uint32_t> &h_info = out.info;
+    // category sets: the pool (identical sets share one entry) and, per lane, 1 + the offset of its set's header
+    bool &any_sets = out.any_sets;
     for (const TreePaths &tp : trees) any_sets = any_sets || !tp.sets.empty();
-    std::vector<uint32_t> h_set, h_pool;
+    std::vector<uint32_t> &h_set = out.set, &h_pool = out.pool;
     std::map<std::vector<uint32_t>, uint32_t> pool_at;
     std::vector<uint32_t> tree_at;  // per set of the current tree: 1 + its header's offset
-    std::vector<int> h_class_bins(C + 1, 0);
-    std::vector<float> h_bias, h_div;
-    {
-        std::vector<double> expect(trees.size());
-        for (size_t t = 0; t < trees.size(); ++t) expect[t] = trees[t].expect;
-        class_bias(f, expect, h_bias, h_div);
-    }
-    size_t n_paths = 0, n_elems = 0;
+    std::vector<int> &h_class_bins = out.class_bins;
+    h_class_bins.assign(C + 1, 0);
+    size_t &n_paths = out.n_paths, &n_elems = out.n_elems;
     uint4 pad;
     {
         const float one = 1.0f;
@@ -666,7 +678,6 @@ static tahoe_status build_tables(tahoe_forest *f, std::vector<TreePaths> &trees)
         memcpy(&pad.z, &one, 4);
         pad.w = 0u;
     }
-    // next-fit packing of each class's paths, in tree order then leaf order
     for (int c = 0; c < C; ++c) {
         h_class_bins[c] = (int)(h_elems.size() / 64);
         size_t start = h_elems.size();
@@ -728,6 +739,33 @@ static tahoe_status build_tables(tahoe_forest *f, std::vector<TreePaths> &trees)
         flush();
     }
     h_class_bins[C] = (int)(h_elems.size() / 64);
+}
+
+// The path tables from the paths of every tree (caller's tree numbering): packing, bias and LDS shapes.
+static tahoe_status build_tables(tahoe_forest *f, std::vector<TreePaths> &trees)
+{
+    const int F = f->p.num_cols;
+    // LDS: the row tile and four slabs, R rows each; R is the largest power of two <= 64 that fits 80 KiB (two workgroups
+    // per CU), else the whole LDS
+    size_t R = 64;
+    const size_t per_row = 5 * (size_t)F * sizeof(float);
+    while (R > 1 && R * per_row > 80 * 1024) R /= 2;
+    if (const tahoe_status s = check_contrib_cols(f)) return s;
+
+    std::vector<float> h_bias, h_div;
+    {
+        std::vector<double> expect(trees.size());
+        for (size_t t = 0; t < trees.size(); ++t) expect[t] = trees[t].expect;
+        class_bias(f, expect, h_bias, h_div);
+    }
+    PathBins bins;
+    pack_paths(trees, f->num_classes, (size_t)f->class_trees, bins);
+    const std::vector<uint4> &h_elems = bins.elems;
+    const std::vector<float> &h_om = bins.om;
+    const std::vector<uint32_t> &h_info = bins.info, &h_set = bins.set, &h_pool = bins.pool;
+    const std::vector<int> &h_class_bins = bins.class_bins;
+    const bool any_sets = bins.any_sets;
+    const size_t n_paths = bins.n_paths, n_elems = bins.n_elems;
 
     tahoe_cstate *cs = new (std::nothrow) tahoe_cstate();
     if (!cs) return fail(TAHOE_ERR_NO_MEMORY, "contribs_build");
@@ -851,6 +889,31 @@ tahoe_status contribs_build_sparse(tahoe_forest *f, const int32_t *tree_roots, c
     return build_tables(f, trees);
 }
 
+tahoe_status contribs_tables_vector(const tahoe_forest *f, const int32_t *tree_roots, const tahoe_sparse_node *nodes,
+                                    const float *leaf_values, const float *covers, VectorPathTables &out)
+{
+    if (const tahoe_status s = check_contrib_cols(f)) return s;
+    const size_t T = (size_t)f->p.num_trees, K = (size_t)f->num_classes;
+    std::vector<TreePaths> trees(T);
+    std::vector<double> expect(T * K);  // [tree][k]: what class_bias reads on the expansion's tree t * K + k
+    parallel_for(T, 4, [&](size_t lo, size_t hi) {
+        for (size_t t = lo; t < hi; ++t) {
+            const SparseTree tree{nodes + tree_roots[t], covers + tree_roots[t]};
+            tree_paths(VectorTree{tree}, trees[t]);
+            for (size_t k = 0; k < K; ++k) expect[t * K + k] = tree_expect(VectorTreeK{tree, leaf_values, K, k});
+        }
+    });
+    class_bias(f, expect, out.bias, out.div);
+    PathBins bins;
+    pack_paths(trees, 1, T, bins);  // one set of bins: what the sparse handle builds for one class of the expansion
+    out.elems.swap(bins.elems);
+    out.one_minus_z.swap(bins.om);
+    out.bin_info.swap(bins.info);
+    out.paths = bins.n_paths;
+    out.path_elems = bins.n_elems;
+    return TAHOE_OK;
+}
+
 void contribs_destroy(tahoe_forest *f)
 {
     tahoe_cstate *cs = f->cs;
@@ -878,6 +941,8 @@ extern "C" tahoe_status tahoe_forest_predict_contribs(tahoe_forest *f, float *ph
     if (oblivious_serves(f, TAHOE_CREATE_CONTRIBS))
         return oblivious_predict_shap(f, TAHOE_CREATE_CONTRIBS, phi_dev, data_dev, rows, (hipStream_t)stream,
                                       "tahoe_forest_predict_contribs");
+    if (vector_serves_contribs(f))
+        return vector_predict_contribs(f, phi_dev, data_dev, rows, (hipStream_t)stream, "tahoe_forest_predict_contribs");
     if (tahoe_status st = need_path_tables(f, "tahoe_forest_predict_contribs")) return st;
     if (rows == 0) return TAHOE_OK;
     if (!phi_dev || !data_dev) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_contribs: null argument");

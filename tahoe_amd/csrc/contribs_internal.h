@@ -4,6 +4,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 #include <hip/hip_runtime.h>
 
@@ -113,6 +114,20 @@ __device__ __forceinline__ bool follows_set(float x, float lower, float upper, b
     return is_missing ? missing_ok : (num_ok && set_ok);
 }
 
+// 1 / k for k = 0 .. 33 (entry 0 unused), correctly rounded by constant folding: the uniform factors of the recursions.  Every
+// translation unit with a TreeSHAP kernel defines its own __constant__ table from this list.
+#define TAHOE_CONTRIB_INV_TABLE                                                                                                   \
+    {0.0f,         1.0f,         1.0f / 2.0f,  1.0f / 3.0f,  1.0f / 4.0f,  1.0f / 5.0f,  1.0f / 6.0f,  1.0f / 7.0f,  1.0f / 8.0f,    \
+     1.0f / 9.0f,  1.0f / 10.0f, 1.0f / 11.0f, 1.0f / 12.0f, 1.0f / 13.0f, 1.0f / 14.0f, 1.0f / 15.0f, 1.0f / 16.0f, 1.0f / 17.0f,   \
+     1.0f / 18.0f, 1.0f / 19.0f, 1.0f / 20.0f, 1.0f / 21.0f, 1.0f / 22.0f, 1.0f / 23.0f, 1.0f / 24.0f, 1.0f / 25.0f, 1.0f / 26.0f,   \
+     1.0f / 27.0f, 1.0f / 28.0f, 1.0f / 29.0f, 1.0f / 30.0f, 1.0f / 31.0f, 1.0f / 32.0f, 1.0f / 33.0f}
+
+// value of lane - 1 (0 in lane 0): DPP wave_shr:1
+__device__ __forceinline__ float from_left_lane(float v)
+{
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138, 0xf, 0xf, false));
+}
+
 // v of lane src_lane (ds_bpermute)
 __device__ __forceinline__ float lane_read(float v, int src_lane)
 {
@@ -122,5 +137,21 @@ __device__ __forceinline__ uint32_t lane_read_u(uint32_t v, int src_lane)
 {
     return (uint32_t)__builtin_amdgcn_ds_bpermute(src_lane << 2, (int)v);
 }
+
+// The path tables of a vector-leaf handle (tahoe_vector_forest_create_ex with TAHOE_CREATE_CONTRIBS), on the host: one set of
+// bins for the forest -- the bins tahoe_sparse_forest_create_ex builds for one class of the K-fold expansion -- whose root
+// elements carry in .x the index of the leaf's vector instead of a leaf value; bias[k] and div[k] as class_bias computes them on
+// the expansion.  contribs.hip builds them (tree_paths, pack_paths), vector_shap.hip uploads and reads them.  The forest has
+// passed contribs_validate_sparse; f->p, num_classes = K and class_trees = num_trees are set.  TAHOE_ERR_UNSUPPORTED when
+// num_cols is past the limit of 20 B of LDS per column.
+struct VectorPathTables {
+    std::vector<uint4> elems;
+    std::vector<float> one_minus_z;
+    std::vector<uint32_t> bin_info;
+    std::vector<float> bias, div;
+    size_t paths = 0, path_elems = 0;
+};
+tahoe_status contribs_tables_vector(const tahoe_forest *f, const int32_t *trees, const tahoe_sparse_node *nodes,
+                                    const float *leaf_values, const float *covers, VectorPathTables &out);
 
 }  // namespace tahoe

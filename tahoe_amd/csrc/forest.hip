@@ -1116,6 +1116,8 @@ static tahoe_knobs read_knobs()
     k.csr_chunk_mb = num("TAHOE_CSR_CHUNK_MB", k.csr_chunk_mb);
     k.csr_fused = num("TAHOE_CSR_FUSED", k.csr_fused);
     k.oblivious_shap_inplace = num("TAHOE_OBLIVIOUS_SHAP_INPLACE", 0) != 0;
+    k.vector_shap_kb = num("TAHOE_VECTOR_SHAP_KB", k.vector_shap_kb);
+    k.vector_shap_grid = num("TAHOE_VECTOR_SHAP_GRID", k.vector_shap_grid);
     return k;
 }
 

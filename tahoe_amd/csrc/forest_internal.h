@@ -20,7 +20,7 @@ struct tahoe_cstate;  // TreeSHAP path tables (TAHOE_CREATE_CONTRIBS), owned by 
 struct tahoe_istate;  // background of interventional TreeSHAP (tahoe_forest_set_background), owned by interventional.hip
 struct tahoe_astate;  // Saabas node deltas (TAHOE_CREATE_APPROX_CONTRIBS), owned by approx.hip
 struct tahoe_ostate;  // oblivious (symmetric) forest, owned by oblivious.hip
-struct tahoe_vstate;  // vector-leaf forest, owned by vector.hip
+struct tahoe_vstate;  // vector-leaf forest, owned by vector.hip (its TreeSHAP tables by vector_shap.hip)
 
 namespace tahoe {
 
@@ -82,6 +82,8 @@ struct tahoe_knobs {
     int csr_chunk_mb = 64;        // TAHOE_CSR_CHUNK_MB: cap of tahoe_forest_predict_csr's densify chunk (at least one 64-row tile)
     int csr_fused = -1;           // TAHOE_CSR_FUSED: under AUTO, 0 = never the fused CSR tile kernels, 1 = wherever one exists, -1 = the rule
     bool oblivious_shap_inplace = false;  // TAHOE_OBLIVIOUS_SHAP_INPLACE = 1: an oblivious handle's explanations accumulate in phi_dev
+    int vector_shap_kb = 0;       // TAHOE_VECTOR_SHAP_KB = 1 / 2 / 4 / 8: force the class block of a vector-leaf handle's TreeSHAP kernel
+    int vector_shap_grid = -1;    // TAHOE_VECTOR_SHAP_GRID: ... 0 = a workgroup loops over its class blocks, 1 = gridDim.y runs over them, -1 = the rule
 };
 
 struct tahoe_forest {
@@ -539,6 +541,11 @@ bool vector_tile_fits(const tahoe_forest *f);
 tahoe_status vector_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data, size_t rows, hipStream_t stream,
                            int strategy);
 void vector_destroy(tahoe_forest *f);
+// ... its TreeSHAP (vector_shap.hip).  vector_serves_contribs: was the handle created with TAHOE_CREATE_CONTRIBS?
+// vector_predict_contribs: tahoe_forest_predict_contribs on such a handle, entry checks included (fn: the call's name)
+bool vector_serves_contribs(const tahoe_forest *f);
+tahoe_status vector_predict_contribs(tahoe_forest *f, float *phi_dev, const float *data_dev, size_t rows, hipStream_t stream,
+                                     const char *fn);
 // The refusal of the entry points a vector-leaf handle does not serve (fn: the entry point's name); TAHOE_OK on every other handle
 inline tahoe_status refuse_vector(const tahoe_forest *f, const char *fn)
 {

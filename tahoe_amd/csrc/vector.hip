@@ -19,24 +19,7 @@
 #include <vector>
 
 #include "forest_internal.h"
-
-namespace tahoe {
-
-struct VNode {
-    float val;         // threshold (leaf: unused)
-    uint32_t bits;     // fid[0:29] | def_left << 30 | is_leaf << 31
-    uint32_t left_idx; // children left_idx, left_idx + 1 relative to the root; leaf: index of the leaf's vector
-    uint32_t pad;
-};
-static_assert(sizeof(VNode) == 16, "VNode must be 16 bytes");
-
-}  // namespace tahoe
-
-struct tahoe_vstate {
-    tahoe::VNode *nodes = nullptr;
-    int32_t *roots = nullptr;
-    float *leaves = nullptr;
-};
+#include "vector_internal.h"
 
 namespace tahoe {
 
@@ -209,6 +192,7 @@ void vector_destroy(tahoe_forest *f)
 {
     tahoe_vstate *v = f->vl;
     if (!v) return;
+    vector_shap_destroy(f);
     if (v->nodes) (void)hipFree(v->nodes);
     if (v->roots) (void)hipFree(v->roots);
     if (v->leaves) (void)hipFree(v->leaves);
@@ -231,9 +215,9 @@ static tahoe_status vector_allow_lds(const tahoe_forest *f)
 
 using namespace tahoe;
 
-extern "C" tahoe_status tahoe_vector_forest_create(tahoe_forest **out, const int32_t *trees, const tahoe_sparse_node *nodes,
-                                                   const float *leaf_values, int64_t num_leaf_vectors, const tahoe_forest_params *p,
-                                                   int leaf_dim)
+extern "C" tahoe_status tahoe_vector_forest_create_ex(tahoe_forest **out, const int32_t *trees, const tahoe_sparse_node *nodes,
+                                                      const float *leaf_values, int64_t num_leaf_vectors, const float *covers,
+                                                      const tahoe_forest_params *p, int leaf_dim, unsigned flags)
 {
     // every check here runs before a device is touched
     if (!out || !p) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_vector_forest_create: null argument");
@@ -284,6 +268,14 @@ extern "C" tahoe_status tahoe_vector_forest_create(tahoe_forest **out, const int
             level[(size_t)n.left_idx] = level[(size_t)n.left_idx + 1] = level[(size_t)i] + 1;
         }
     }
+    // the checks of tahoe_sparse_forest_create_ex for the flag: covers, and at most 31 distinct features on a leaf's path
+    if ((flags & ~TAHOE_CREATE_CONTRIBS) != 0)
+        return fail(TAHOE_ERR_INVALID_ARG, "unknown create flags 0x%x (a vector-leaf handle takes TAHOE_CREATE_CONTRIBS only)",
+                    flags & ~TAHOE_CREATE_CONTRIBS);
+    if (flags & TAHOE_CREATE_CONTRIBS) {
+        if (!covers) return fail(TAHOE_ERR_INVALID_ARG, "TAHOE_CREATE_CONTRIBS needs covers (one per node)");
+        if (const tahoe_status cs = contribs_validate_sparse(trees, nodes, covers, p, true)) return cs;
+    }
 
     ForestPtr f;
     if (const tahoe_status s = open_handle(p, leaf_dim, f)) return s;
@@ -299,6 +291,14 @@ extern "C" tahoe_status tahoe_vector_forest_create(tahoe_forest **out, const int
         (s = hip_status(upload(&v->leaves, leaf_values, (size_t)num_leaf_vectors * (size_t)leaf_dim, &f->device_bytes), "upload(leaves)")) ||
         (s = vector_allow_lds(f.get())))
         return s;
+    if ((flags & TAHOE_CREATE_CONTRIBS) && (s = vector_shap_build(f.get(), trees, nodes, leaf_values, covers))) return s;
     *out = f.release();
     return TAHOE_OK;
+}
+
+extern "C" tahoe_status tahoe_vector_forest_create(tahoe_forest **out, const int32_t *trees, const tahoe_sparse_node *nodes,
+                                                   const float *leaf_values, int64_t num_leaf_vectors, const tahoe_forest_params *p,
+                                                   int leaf_dim)
+{
+    return tahoe_vector_forest_create_ex(out, trees, nodes, leaf_values, num_leaf_vectors, nullptr, p, leaf_dim, 0u);
 }
