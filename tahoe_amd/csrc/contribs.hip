@@ -67,6 +67,7 @@ __device__ __forceinline__ void contribs_tile(float *__restrict__ phi, const flo
             const float leaf = lane_read(lower, gs);
             const float zdiv = z / (float)(ud + 1);
             const float udp1 = (float)(ud + 1);
+            const int split = unwind_split(z, ud);
             ElemSet es{};
             bool gather = false;
             if constexpr (SETS) {
@@ -98,9 +99,21 @@ __device__ __forceinline__ void contribs_tile(float *__restrict__ phi, const flo
                     const float tmp = next * udp1 * c_inv[i + 1];
                     const float t_one = total + tmp, n_one = pwi - tmp * pre;
                     const float t_zero = pre > 0.0f ? total + pwi * __builtin_amdgcn_rcpf(pre) : total;
-                    if (i < ud) {
+                    if (i < ud && (!o || i >= split)) {
                         total = o ? t_one : t_zero;
                         next = o ? n_one : next;
+                    }
+                }
+                // a followed element's weights below `split` come from the other end (unwind_split, contribs_internal.h)
+                if (__any(o && split > 0)) {
+                    float prev = 0.0f;
+                    for (int i = 0; i < steps - 1; ++i) {
+                        const float pwi = lane_read(pw, min(gs + i, 63));
+                        const float q = (pwi - prev * (float)i * c_inv[ud + 1]) * __builtin_amdgcn_rcpf((float)(ud - i) * zdiv);
+                        if (o && i < split) {
+                            total += q;
+                            prev = q;
+                        }
                     }
                 }
                 const float term = total * (o ? om : -z) * leaf;  // (one - zero) x leaf

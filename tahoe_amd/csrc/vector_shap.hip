@@ -76,6 +76,7 @@ __global__ __launch_bounds__(256) void vector_contribs_kernel(float *__restrict_
             }
             const float zdiv = z / (float)(ud + 1);
             const float udp1 = (float)(ud + 1);
+            const int split = unwind_split(z, ud);
             for (int r = 0; r < nr; ++r) {
                 const bool o = follows(tile[r * F + fid], lower, upper, missing_ok, nan_ok, missing);
                 const uint32_t zo = e.z | (o ? 0x80000000u : 0u);
@@ -99,9 +100,21 @@ __global__ __launch_bounds__(256) void vector_contribs_kernel(float *__restrict_
                     const float tmp = next * udp1 * c_inv[i + 1];
                     const float t_one = total + tmp, n_one = pwi - tmp * pre;
                     const float t_zero = pre > 0.0f ? total + pwi * __builtin_amdgcn_rcpf(pre) : total;
-                    if (i < ud) {
+                    if (i < ud && (!o || i >= split)) {
                         total = o ? t_one : t_zero;
                         next = o ? n_one : next;
+                    }
+                }
+                // a followed element's weights below `split` come from the other end (unwind_split, contribs_internal.h)
+                if (__any(o && split > 0)) {
+                    float prev = 0.0f;
+                    for (int i = 0; i < steps - 1; ++i) {
+                        const float pwi = lane_read(pw, min(gs + i, 63));
+                        const float q = (pwi - prev * (float)i * c_inv[ud + 1]) * __builtin_amdgcn_rcpf((float)(ud - i) * zdiv);
+                        if (o && i < split) {
+                            total += q;
+                            prev = q;
+                        }
                     }
                 }
                 const float tw = total * (o ? om : -z);  // (one - zero), shared by the block's classes

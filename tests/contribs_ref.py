@@ -179,12 +179,14 @@ def poly(nodes, T, D, F, data, missing, num_classes=1, avg=False, global_bias=0.
     return phi, A, N
 
 
-def _poly_chunk(paths, L, data, missing, phiT, AT, N):
+def _poly_chunk(paths, L, data, missing, phiT, AT, N, dtype=np.float64):
+    """dtype: the type the recursion runs in (phiT and AT should have it too): np.longdouble, where it is wider, for paths
+    long enough that the unwound sum loses digits a float64 comparison needs"""
     P, rows = len(paths), data.shape[0]
-    Z = np.ones((P, L))
-    O = np.ones((P, L, rows))
+    Z = np.ones((P, L), dtype)
+    O = np.ones((P, L, rows), dtype)
     fids = np.zeros((P, L), np.int64)
-    leafv = np.array([p[0] for p in paths])
+    leafv = np.array([p[0] for p in paths], dtype)
     for a, (_, elems) in enumerate(paths):
         for j, (f, z, edges) in enumerate(elems, start=1):
             Z[a, j], fids[a, j] = z, f
@@ -193,7 +195,7 @@ def _poly_chunk(paths, L, data, missing, phiT, AT, N):
                 o &= go_right(data[:, f], thr, dleft, missing) == right
             O[a, j] = o
     # EXTEND, element by element (the root element first: z = o = 1)
-    W = np.zeros((L, P, rows))
+    W = np.zeros((L, P, rows), dtype)
     W[0] = 1.0
     for j in range(1, L):
         zj, oj = Z[:, j][:, None], O[:, j]
@@ -204,8 +206,8 @@ def _poly_chunk(paths, L, data, missing, phiT, AT, N):
     for k in range(1, L):
         ok, zk = O[:, k], Z[:, k][:, None]
         nxt = W[ud].copy()
-        t_one = np.zeros((P, rows))
-        t_zero = np.zeros((P, rows))
+        t_one = np.zeros((P, rows), dtype)
+        t_zero = np.zeros((P, rows), dtype)
         for i in range(ud - 1, -1, -1):
             tmp = nxt * (ud + 1) / (i + 1)
             t_one += tmp
