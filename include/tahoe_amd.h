@@ -255,7 +255,9 @@ tahoe_status tahoe_forest_predict_interactions(tahoe_forest *f, float *out_dev, 
 /* Interventional TreeSHAP (SHAP's TreeExplainer(model, data=bg), feature_perturbation="interventional"; Lundberg et al. 2020):
  * the game v_r(S) = f(x_S, r_{N \ S}) against each row r of a background data set, averaged over the background.  Served on
  * dense, sparse and multi-class handles created with TAHOE_CREATE_CONTRIBS; it reads the path bins that flag builds.  The covers are
- * checked at create as for tahoe_forest_predict_contribs but this game does not use them.
+ * checked at create as for tahoe_forest_predict_contribs but this game does not use them.  A vector-leaf handle serves it with
+ * TAHOE_CREATE_INTERVENTIONAL (tahoe_vector_forest_create_ex), which takes no covers; without that flag both calls below are
+ * TAHOE_ERR_UNSUPPORTED on it, TAHOE_CREATE_CONTRIBS or not.
  *
  * tahoe_forest_set_background: bg_dev is row-major bg_rows x num_cols float32 on the handle's device; the handle keeps what it
  * needs (per path bin and background row, the 64-bit ballot of the bin's lanes whose element the row follows: bins x bg_rows x
@@ -266,7 +268,9 @@ tahoe_status tahoe_forest_predict_interactions(tahoe_forest *f, float *out_dev, 
  * float64 on the host, rounded once.  The handle's strategy setting is left as it was.  Refusals: NULL handle, NULL bg_dev with
  * bg_rows > 0, bg_rows x num_cols x 4 overflowing size_t or bg_rows >= 2^31: TAHOE_ERR_INVALID_ARG; a handle (dense or sparse)
  * created without TAHOE_CREATE_CONTRIBS: TAHOE_ERR_UNSUPPORTED; an allocation that fails: TAHOE_ERR_NO_MEMORY.  On any refusal
- * the previous background is kept. */
+ * the previous background is kept.  On a vector-leaf handle: the same contract with C = K and div = num_trees; the masks are
+ * stored once for the forest (bins x bg_rows x 8 bytes, not K times as on the T x K-tree expansion), raw_k(r) are the bits of
+ * tahoe_forest_predict_raw on that handle, and device_bytes grows by bins x bg_rows x 8 + (1024 + K) x 4. */
 tahoe_status tahoe_forest_set_background(tahoe_forest *f, const float *bg_dev, size_t bg_rows, void *stream);
 /* phi_dev[rows][num_classes][num_cols + 1] <- phi_i(x) = (1 / B) sum_r phi_i(x, r), B = background rows, phi_i(x, r) the exact
  * Shapley value of v_r(S) = f(x_S, r_{N \ S}) summed over class c's trees c, c + C, ... and divided by (float)Tc with
@@ -283,7 +287,13 @@ tahoe_status tahoe_forest_set_background(tahoe_forest *f, const float *bg_dev, s
  * Refusals, nothing launched: a handle (dense or sparse) created without TAHOE_CREATE_CONTRIBS, or one with no background:
  * TAHOE_ERR_UNSUPPORTED (tahoe_last_error says which); then rows == 0: TAHOE_OK; NULL phi_dev / data_dev with rows > 0, or
  * rows x C x (num_cols + 1) x 4 overflowing size_t: TAHOE_ERR_INVALID_ARG.  On a handle with categorical splits
- * (TAHOE_CREATE_CAT_CONTRIBS) x and the background rows take tahoe_sparse_forest_create_cat's rule at a categorical node. */
+ * (TAHOE_CREATE_CAT_CONTRIBS) x and the background rows take tahoe_sparse_forest_create_cat's rule at a categorical node.
+ * On a vector-leaf handle created with TAHOE_CREATE_INTERVENTIONAL: phi_dev[rows][K][num_cols + 1], bit for bit what
+ * tahoe_sparse_forest_create_ex(num_classes = K, TAHOE_CREATE_CONTRIBS) gives on the T x K-tree expansion of
+ * tahoe_vector_forest_create with the same background under any valid covers, bias column included (K == 1: the bits of the sparse
+ * handle on the same trees).  The K outputs of a leaf share one pass over the background per (row, path bin); the result does not
+ * depend on the batch, on how many outputs share a pass, on the strategy or on whether TAHOE_CREATE_CONTRIBS is also set.  The
+ * same refusals in the same order, the missing flag first (text: "vector-leaf" and the call's name). */
 tahoe_status tahoe_forest_predict_contribs_interventional(tahoe_forest *f, float *phi_dev, const float *data_dev, size_t rows,
                                                           void *stream);
 
@@ -522,17 +532,29 @@ tahoe_status tahoe_oblivious_forest_create_ex(tahoe_forest **out, const int32_t 
  * AUTO = ROWTILE when the tile fits, else DIRECT; TILEBLOCK, TILERING and QRING are TAHOE_ERR_UNSUPPORTED.
  * Out of scope, TAHOE_ERR_UNSUPPORTED with nothing launched and a text that names the call and says "vector-leaf":
  * tahoe_forest_predict_accumulate, _predict_host, _predict_csr, _reserve_csr (and _get_csr_plan: form TAHOE_FORM_NONE),
- * _set_stages, _predict_staged (_get_staged_strategy: 0), _predict_contribs_approx, _predict_interactions, _set_background and
- * _predict_contribs_interventional; _predict_contribs unless the handle comes from tahoe_vector_forest_create_ex with
- * TAHOE_CREATE_CONTRIBS.  Categorical splits are not represented. */
+ * _set_stages, _predict_staged (_get_staged_strategy: 0), _predict_contribs_approx, _predict_interactions; _predict_contribs
+ * unless the handle comes from tahoe_vector_forest_create_ex with TAHOE_CREATE_CONTRIBS; _set_background and
+ * _predict_contribs_interventional unless it comes from there with TAHOE_CREATE_INTERVENTIONAL.  Categorical splits are not
+ * represented. */
 tahoe_status tahoe_vector_forest_create(tahoe_forest **out, const int32_t *trees, const tahoe_sparse_node *nodes,
                                         const float *leaf_values, int64_t num_leaf_vectors, const tahoe_forest_params *params,
                                         int leaf_dim);
-/* The same handle with path-dependent TreeSHAP.  flags: 0 or TAHOE_CREATE_CONTRIBS; with flags == 0 covers is ignored and the call
- * is tahoe_vector_forest_create (which is this call with NULL, 0), bit for bit.  With the flag covers[i] is the cover of nodes[i]
- * (num_nodes floats; scikit-learn's tree_.weighted_n_node_samples).
+/* Interventional TreeSHAP on a vector-leaf handle: a create flag that tahoe_vector_forest_create_ex alone accepts (every other
+ * create: its "unknown create flags" refusal), alone or with TAHOE_CREATE_CONTRIBS. */
+#define TAHOE_CREATE_INTERVENTIONAL 0x80u
+/* The same handle with explanations.  flags: a subset of TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_INTERVENTIONAL; with flags == 0 covers
+ * is ignored and the call is tahoe_vector_forest_create (which is this call with NULL, 0), bit for bit; a handle created without
+ * TAHOE_CREATE_INTERVENTIONAL is bit for bit and byte for byte what it was before that flag existed.  With TAHOE_CREATE_CONTRIBS
+ * covers[i] is the cover of nodes[i] (num_nodes floats; scikit-learn's tree_.weighted_n_node_samples).
+ * TAHOE_CREATE_INTERVENTIONAL serves tahoe_forest_set_background and tahoe_forest_predict_contribs_interventional as defined there.
+ * Alone it ignores covers (NULL is fine: that game does not use them) and runs, of the checks below, the flag check and the
+ * 31-distinct-features check (same code and text) and the num_cols limit; the handle then keeps only what that game reads, 16
+ * bytes per path element in 64-lane bins and 4 bytes per bin -- the bins are built as if every cover were 1, which changes no
+ * feature, bound, missing / NaN flag, length, packing, rank or round, and an element's zero fraction is never read -- and
+ * tahoe_forest_predict_contribs stays TAHOE_ERR_UNSUPPORTED.  With both flags covers are required and checked, one set of tables
+ * serves both calls and device_bytes is that of the TAHOE_CREATE_CONTRIBS handle.
  * Checks, before a device is touched and after those of tahoe_vector_forest_create, with the codes and texts of
- * tahoe_sparse_forest_create_ex: another flag bit: TAHOE_ERR_INVALID_ARG naming the bit; the flag with covers == NULL:
+ * tahoe_sparse_forest_create_ex: another flag bit: TAHOE_ERR_INVALID_ARG naming the bit; TAHOE_CREATE_CONTRIBS with covers == NULL:
  * TAHOE_ERR_INVALID_ARG; a reachable internal node whose children's covers are not finite, negative or sum to 0:
  * TAHOE_ERR_INVALID_FOREST naming the tree and the node; a reachable leaf whose path has more than 31 distinct features:
  * TAHOE_ERR_UNSUPPORTED naming the tree.  With a device: num_cols above a fifth of the LDS in floats (20 B per column):
@@ -546,8 +568,9 @@ tahoe_status tahoe_vector_forest_create(tahoe_forest **out, const int32_t *trees
  * leaf share one evaluation of its path; results do not depend on the batch, on how many outputs share an evaluation or on the
  * strategy (which the call does not use).  The call is asynchronous, allocates nothing and can be captured.
  * The tables count in device_bytes: 20 bytes per path element in 64-lane bins, once for the forest -- not once per output as on
- * the expansion -- and 4 K bytes of bias.  tahoe_forest_predict_interactions, _set_background, _predict_contribs_interventional
- * and _predict_contribs_approx stay TAHOE_ERR_UNSUPPORTED as above on every vector-leaf handle. */
+ * the expansion -- and 4 K bytes of bias.  tahoe_forest_predict_interactions and _predict_contribs_approx stay
+ * TAHOE_ERR_UNSUPPORTED as above on every vector-leaf handle, _set_background and _predict_contribs_interventional on one created
+ * without TAHOE_CREATE_INTERVENTIONAL. */
 tahoe_status tahoe_vector_forest_create_ex(tahoe_forest **out, const int32_t *trees, const tahoe_sparse_node *nodes,
                                            const float *leaf_values, int64_t num_leaf_vectors, const float *covers,
                                            const tahoe_forest_params *params, int leaf_dim, unsigned flags);

@@ -39,6 +39,7 @@ CREATE_CONTRIBS = 0x4  # per-feature contributions (tahoe_forest_predict_contrib
 CREATE_APPROX_CONTRIBS = 0x10  # Saabas contributions (tahoe_forest_predict_contribs_approx); node weights are covers
 CREATE_CAT_CONTRIBS = 0x20  # tahoe_sparse_forest_create_cat: the two flags above on a handle with categorical splits
 CREATE_INTERACTIONS = 0x40  # tahoe_oblivious_forest_create_ex: SHAP interaction values (tahoe_forest_predict_interactions)
+CREATE_INTERVENTIONAL = 0x80  # tahoe_vector_forest_create_ex: interventional TreeSHAP (tahoe_forest_set_background), no covers needed
 STRATEGY_NAMES = {1: "direct", 2: "rowtile", 3: "tileblock", 4: "tilering", 5: "qring"}
 STATUS_NAMES = {
     0: "TAHOE_OK",
@@ -598,7 +599,8 @@ class Forest:
 
     def set_background(self, bg, stream=None) -> None:
         """Background data set of interventional TreeSHAP (tahoe_forest_set_background): float32 [B, num_cols], contiguous, on
-        the handle's device; None clears it.  Synchronous; the handle keeps what it needs, so `bg` may be freed afterwards."""
+        the handle's device; None clears it.  Synchronous; the handle keeps what it needs, so `bg` may be freed afterwards.
+        Needs contribs=True (a VectorForest: interventional=True)."""
         if bg is None:
             _check(lib.tahoe_forest_set_background(self._h, None, 0, None), "tahoe_forest_set_background")
             return
@@ -608,7 +610,7 @@ class Forest:
     def predict_contribs_interventional(self, data, out=None, stream=None):
         """Interventional TreeSHAP against the background of set_background (tahoe_forest_predict_contribs_interventional):
         [rows, num_cols + 1] float32, or [rows, num_classes, num_cols + 1] on a multi-class handle; the bias is the last
-        column.  Needs contribs=True and a background."""
+        column.  Needs contribs=True (a VectorForest: interventional=True) and a background."""
         return self._shap_out("tahoe_forest_predict_contribs_interventional", data, 1, out, stream)
 
     def set_strategy(self, strategy: int) -> None:
@@ -847,11 +849,13 @@ class VectorForest(Forest):
     share a vector.  predict* as Forest: [rows] for K == 1, [rows, K] otherwise; AVG divides by the number of trees; leaf
     indices are relative to the tree's root, as on a SparseForest.  covers (float32, one per node; scikit-learn's
     tree_.weighted_n_node_samples) and contribs=True go through tahoe_vector_forest_create_ex: predict_contribs then gives the
-    TreeSHAP values of every output, [rows, K, num_cols + 1] ([rows, num_cols + 1] for K == 1)."""
+    TreeSHAP values of every output, [rows, K, num_cols + 1] ([rows, num_cols + 1] for K == 1).  interventional=True
+    (TAHOE_CREATE_INTERVENTIONAL) serves set_background and predict_contribs_interventional in the same shape; alone it needs no
+    covers."""
 
     def __init__(self, nodes: np.ndarray, trees: np.ndarray, leaf_values, num_cols: int, leaf_dim: int = None,
                  missing: float = 0.0, output: int = OUT_RAW, threshold: float = 0.5, global_bias: float = 0.0, covers=None,
-                 contribs: bool = False):
+                 contribs: bool = False, interventional: bool = False):
         nodes = np.ascontiguousarray(nodes, dtype=SPARSE_NODE_DTYPE)
         trees = np.ascontiguousarray(trees, dtype=np.int32).reshape(-1)
         lv = np.asarray(leaf_values, dtype=np.float32)
@@ -869,7 +873,8 @@ class VectorForest(Forest):
         num_vectors = leaves.size // leaf_dim if leaf_dim >= 1 else 0
         self.params = ForestParams(int(nodes.size), 0, int(trees.size), num_cols, 0, output, threshold, global_bias, 0, missing)
         self._h = _vp()
-        if covers is not None or contribs:
+        flags = (CREATE_CONTRIBS if contribs else 0) | (CREATE_INTERVENTIONAL if interventional else 0)
+        if covers is not None or flags:
             cv = None if covers is None else np.ascontiguousarray(covers, dtype=np.float32).reshape(-1)
             if cv is not None and cv.size != nodes.size:
                 raise ValueError("covers.size != nodes.size")
@@ -877,7 +882,7 @@ class VectorForest(Forest):
                                                      nodes.ctypes.data if nodes.size else None,
                                                      leaves.ctypes.data if leaves.size else None, num_vectors,
                                                      cv.ctypes.data if cv is not None else None, C.byref(self.params),
-                                                     leaf_dim, CREATE_CONTRIBS if contribs else 0),
+                                                     leaf_dim, flags),
                    "tahoe_vector_forest_create_ex")
         else:
             _check(lib.tahoe_vector_forest_create(C.byref(self._h), trees.ctypes.data if trees.size else None,

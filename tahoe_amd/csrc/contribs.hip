@@ -483,6 +483,11 @@ struct SparseTree {
 struct VectorTree : SparseTree {
     uint32_t leaf_word(size_t i) const { return (uint32_t)n[i].left_idx; }
 };
+// ... of a handle created with TAHOE_CREATE_INTERVENTIONAL alone: every cover reads 1.  tree_paths uses covers for z and 1 - z
+// only -- features, bounds, missing_ok / nan_ok and lengths do not depend on them -- and that game reads neither.
+struct VectorTreeUnit : VectorTree {
+    double cover(size_t) const { return 1.0; }
+};
 // ... and for tree_expect: element k of the leaf's vector as the leaf value
 struct VectorTreeK : SparseTree {
     const float *leaves;
@@ -839,7 +844,7 @@ tahoe_status contribs_build(tahoe_forest *f, const tahoe_dense_node *nodes)
 }
 
 tahoe_status contribs_validate_sparse(const int32_t *trees, const tahoe_sparse_node *nodes, const float *covers,
-                                      const tahoe_forest_params *p, bool path_limit)
+                                      const tahoe_forest_params *p, bool path_limit, bool check_covers)
 {
     // per reachable internal node, the covers of its two children; per reachable leaf, the distinct features of its path (the
     // element word's 5-bit rank and length fields, and interventional.hip's 32 x 32 weight table, hold at most 31)
@@ -852,7 +857,7 @@ tahoe_status contribs_validate_sparse(const int32_t *trees, const tahoe_sparse_n
     std::vector<Frame> stack;
     for (int t = 0; t < p->num_trees; ++t) {
         const tahoe_sparse_node *tn = nodes + trees[t];
-        const float *tc = covers + trees[t];
+        const float *tc = check_covers ? covers + trees[t] : nullptr;
         int distinct = 0;
         path.clear();
         stack.assign(1, Frame{0, 0});
@@ -874,7 +879,7 @@ tahoe_status contribs_validate_sparse(const int32_t *trees, const tahoe_sparse_n
             const int fid = n.bits & 0x3fffffff;
             if (count[(size_t)fid]++ == 0) ++distinct;
             path.push_back(fid);
-            const float wl = tc[n.left_idx], wr = tc[n.left_idx + 1];
+            const float wl = tc ? tc[n.left_idx] : 1.0f, wr = tc ? tc[n.left_idx + 1] : 1.0f;
             if (!std::isfinite(wl) || !std::isfinite(wr) || !(wl >= 0.0f) || !(wr >= 0.0f) || !((double)wl + (double)wr > 0.0))
                 return fail(TAHOE_ERR_INVALID_FOREST,
                             "tree %d node %d: child covers %g and %g (TAHOE_CREATE_CONTRIBS needs finite covers >= 0 with a "
@@ -908,19 +913,23 @@ tahoe_status contribs_tables_vector(const tahoe_forest *f, const int32_t *tree_r
     if (const tahoe_status s = check_contrib_cols(f)) return s;
     const size_t T = (size_t)f->p.num_trees, K = (size_t)f->num_classes;
     std::vector<TreePaths> trees(T);
-    std::vector<double> expect(T * K);  // [tree][k]: what class_bias reads on the expansion's tree t * K + k
+    std::vector<double> expect(covers ? T * K : 0);  // [tree][k]: what class_bias reads on the expansion's tree t * K + k
     parallel_for(T, 4, [&](size_t lo, size_t hi) {
         for (size_t t = lo; t < hi; ++t) {
+            if (!covers) {
+                tree_paths(VectorTreeUnit{VectorTree{SparseTree{nodes + tree_roots[t], nullptr}}}, trees[t]);
+                continue;
+            }
             const SparseTree tree{nodes + tree_roots[t], covers + tree_roots[t]};
             tree_paths(VectorTree{tree}, trees[t]);
             for (size_t k = 0; k < K; ++k) expect[t * K + k] = tree_expect(VectorTreeK{tree, leaf_values, K, k});
         }
     });
-    class_bias(f, expect, out.bias, out.div);
+    if (covers) class_bias(f, expect, out.bias, out.div);
     PathBins bins;
     pack_paths(trees, 1, T, bins);  // one set of bins: what the sparse handle builds for one class of the expansion
     out.elems.swap(bins.elems);
-    out.one_minus_z.swap(bins.om);
+    if (covers) out.one_minus_z.swap(bins.om);
     out.bin_info.swap(bins.info);
     out.paths = bins.n_paths;
     out.path_elems = bins.n_elems;

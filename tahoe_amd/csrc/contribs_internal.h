@@ -35,7 +35,23 @@ struct tahoe_cstate {
     uint32_t set_words = 0;         // words of set_pool: bounds every word read
 };
 
+// The background of interventional TreeSHAP (tahoe_forest_set_background): interventional.hip builds it, its kernels and
+// vector_iv.hip's read it
+struct tahoe_istate {
+    unsigned long long *masks = nullptr;  // [bins][B] ballot of the lanes whose element background row r follows (rank-0 lanes 0)
+    float *consts = nullptr;              // [kIvTable] weight table, then [num_classes] the bias column
+    size_t bg_rows = 0;
+    size_t bytes = 0;                     // device bytes of the two buffers (counted in tahoe_forest::device_bytes)
+};
+
 namespace tahoe {
+
+// W[p * 32 + q] = (p - 1)! q! / (p + q)! = 1 / (p C(p + q, q)) for p >= 1, p + q <= 31 (a path has at most 31 features), from
+// float64 rounded once; 0 elsewhere.  A lane of A reads W[a][b], a lane of B W[b][a] (and subtracts).
+constexpr int kIvTable = 32 * 32;
+constexpr int kIvMaxTileRows = 8;               // rows of a workgroup's tile: small, so that a batch spreads over the CUs
+constexpr size_t kIvLdsBudget = 80 * 1024;      // two workgroups per CU where the tile allows it, as contribs_kernel
+constexpr int kIvUnroll = 8;                    // background rows whose mask and weight loads are issued together
 
 // Element word (.w): fid (15 bits) | rank in its path << 15 | (path length - 1) << 20 | round << 25 | missing_ok << 30 |
 // nan_ok << 31.  .x / .y / .z: the lower bound (x >= lower for every right edge), the upper bound (!(x >= upper) for every left
@@ -155,7 +171,9 @@ __device__ __forceinline__ uint32_t lane_read_u(uint32_t v, int src_lane)
 // elements carry in .x the index of the leaf's vector instead of a leaf value; bias[k] and div[k] as class_bias computes them on
 // the expansion.  contribs.hip builds them (tree_paths, pack_paths), vector_shap.hip uploads and reads them.  The forest has
 // passed contribs_validate_sparse; f->p, num_classes = K and class_trees = num_trees are set.  TAHOE_ERR_UNSUPPORTED when
-// num_cols is past the limit of 20 B of LDS per column.
+// num_cols is past the limit of 20 B of LDS per column.  covers == nullptr (TAHOE_CREATE_INTERVENTIONAL alone): the bins are built
+// as if every cover were 1 -- features, bounds, flags, lengths, packing, ranks and rounds do not depend on the covers; an
+// element's .z is then not to be read -- and one_minus_z, bias and div stay empty.
 struct VectorPathTables {
     std::vector<uint4> elems;
     std::vector<float> one_minus_z;

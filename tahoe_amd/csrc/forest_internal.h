@@ -82,7 +82,7 @@ struct tahoe_knobs {
     int csr_chunk_mb = 64;        // TAHOE_CSR_CHUNK_MB: cap of tahoe_forest_predict_csr's densify chunk (at least one 64-row tile)
     int csr_fused = -1;           // TAHOE_CSR_FUSED: under AUTO, 0 = never the fused CSR tile kernels, 1 = wherever one exists, -1 = the rule
     bool oblivious_shap_inplace = false;  // TAHOE_OBLIVIOUS_SHAP_INPLACE = 1: an oblivious handle's explanations accumulate in phi_dev
-    int vector_shap_kb = 0;       // TAHOE_VECTOR_SHAP_KB = 1 / 2 / 4 / 8: force the class block of a vector-leaf handle's TreeSHAP kernel
+    int vector_shap_kb = 0;       // TAHOE_VECTOR_SHAP_KB = 1 / 2 / 4 / 8: force the class block of a vector-leaf handle's TreeSHAP kernels
     int vector_shap_grid = -1;    // TAHOE_VECTOR_SHAP_GRID: ... 0 = a workgroup loops over its class blocks, 1 = gridDim.y runs over them, -1 = the rule
 };
 
@@ -505,9 +505,10 @@ tahoe_status widef_reserve(tahoe_forest *f, size_t rows);
 tahoe_status contribs_validate(const tahoe_dense_node *nodes, const tahoe_forest_params *p);
 tahoe_status contribs_build(tahoe_forest *f, const tahoe_dense_node *nodes);
 // ... the same for a sparse forest whose structure check has passed: covers[i] is the cover of nodes[i]; with path_limit the
-// validation also refuses (TAHOE_ERR_UNSUPPORTED) a leaf whose path has more than 31 distinct features
+// validation also refuses (TAHOE_ERR_UNSUPPORTED) a leaf whose path has more than 31 distinct features; without check_covers
+// covers is not read (it may be null) and the path check alone runs
 tahoe_status contribs_validate_sparse(const int32_t *trees, const tahoe_sparse_node *nodes, const float *covers,
-                                      const tahoe_forest_params *p, bool path_limit);
+                                      const tahoe_forest_params *p, bool path_limit, bool check_covers = true);
 // The bias column of tahoe_forest_predict_contribs (bias[c], float64 on the host, rounded once) and the AVG divisor (div[c]) of
 // every class, from the caller's validated trees; f->p, num_classes and class_trees must be set
 void contribs_bias(const tahoe_forest *f, const tahoe_dense_node *nodes, std::vector<float> &bias, std::vector<float> &div);
@@ -546,6 +547,13 @@ void vector_destroy(tahoe_forest *f);
 bool vector_serves_contribs(const tahoe_forest *f);
 tahoe_status vector_predict_contribs(tahoe_forest *f, float *phi_dev, const float *data_dev, size_t rows, hipStream_t stream,
                                      const char *fn);
+// ... its interventional TreeSHAP (vector_iv.hip).  vector_serves_interventional: was the handle created with
+// TAHOE_CREATE_INTERVENTIONAL?  vector_predict_interventional: the launch of tahoe_forest_predict_contribs_interventional on such a
+// handle with a background, after the entry checks (fn: the call's name); vector_iv_allow_lds: its kernel may take the device's LDS
+bool vector_serves_interventional(const tahoe_forest *f);
+tahoe_status vector_predict_interventional(tahoe_forest *f, float *phi_dev, const float *data_dev, size_t rows, hipStream_t stream,
+                                           const char *fn);
+hipError_t vector_iv_allow_lds(const tahoe_forest *f);
 // The refusal of the entry points a vector-leaf handle does not serve (fn: the entry point's name); TAHOE_OK on every other handle
 inline tahoe_status refuse_vector(const tahoe_forest *f, const char *fn)
 {
@@ -562,6 +570,11 @@ inline tahoe_status need_path_tables(const tahoe_forest *f, const char *fn)
         return fail(TAHOE_ERR_UNSUPPORTED, "%s: a sparse handle created without TAHOE_CREATE_CONTRIBS has no node covers and no path "
                                            "tables (tahoe_sparse_forest_create_ex)", fn);
     return fail(TAHOE_ERR_UNSUPPORTED, "%s: the handle was created without TAHOE_CREATE_CONTRIBS and has no path tables", fn);
+}
+// ... of the two interventional entry points: the path tables, or a vector-leaf handle's bins of TAHOE_CREATE_INTERVENTIONAL
+inline tahoe_status need_background_tables(const tahoe_forest *f, const char *fn)
+{
+    return vector_serves_interventional(f) ? TAHOE_OK : need_path_tables(f, fn);
 }
 // TAHOE_ERR_INVALID_ARG unless the output of a SHAP entry point, rows x classes x (num_cols + 1)^k floats, fits in size_t
 inline tahoe_status check_shap_out(const tahoe_forest *f, size_t rows, int k, const char *fn)
@@ -580,6 +593,10 @@ inline tahoe_status check_shap_out(const tahoe_forest *f, size_t rows, int k, co
 }
 // interventional TreeSHAP (interventional.hip): frees the background, if any
 void interventional_destroy(tahoe_forest *f);
+// ... masks[b][r] <- the ballot of bin b's lanes whose element background row r follows (background_mask_kernel<false>: elements
+// without category sets), for the `bins` > 0 bins at elems; rank-0 lanes give 0, so a root element's .x is never read as a bound
+void launch_background_masks(unsigned long long *masks, const float *bg_dev, size_t bg_rows, int num_cols, size_t bins,
+                             const uint4 *elems, float missing, hipStream_t stream);
 // Saabas contributions (approx.hip).  approx_build runs on a dense handle's final layout (h_inner / h_real after re-layout,
 // internal tree order) and the caller's validated nodes; approx_build_sparse on the caller's validated sparse trees.
 tahoe_status approx_build(tahoe_forest *f, const tahoe_dense_node *nodes, const std::vector<InnerNode> &h_inner,

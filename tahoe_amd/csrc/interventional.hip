@@ -1,6 +1,8 @@
 // Interventional TreeSHAP (Lundberg et al. 2020, "Independent Tree SHAP"; SHAP's feature_perturbation="interventional"):
 // per-feature contributions of v(S) = mean over background rows r of f(x_S, r_{N \ S}).  It reads the 64-lane path bins that
 // create builds for TAHOE_CREATE_CONTRIBS (contribs.hip) and uses only their bounds and missing / NaN flags, never the covers.
+// On a vector-leaf handle created with TAHOE_CREATE_INTERVENTIONAL the background is built here, by the same body, and the
+// contributions come from vector_iv.hip.
 //
 // For one pair (x, r) and one path with leaf value v: A = the path's features where only x follows every edge of the feature,
 // B = those where only r does; a feature where neither does kills the path.  Then i in A gets +v (|A| - 1)! |B|! / (|A| + |B|)!,
@@ -17,22 +19,9 @@
 
 #include "forest_internal.h"
 #include "contribs_internal.h"
-
-struct tahoe_istate {
-    unsigned long long *masks = nullptr;  // [bins][B] ballot of the lanes whose element background row r follows (rank-0 lanes 0)
-    float *consts = nullptr;              // [kIvTable] weight table, then [num_classes] the bias column
-    size_t bg_rows = 0;
-    size_t bytes = 0;                     // device bytes of the two buffers (counted in tahoe_forest::device_bytes)
-};
+#include "vector_internal.h"
 
 namespace tahoe {
-
-// W[p * 32 + q] = (p - 1)! q! / (p + q)! = 1 / (p C(p + q, q)) for p >= 1, p + q <= 31 (a path has at most 31 features), from
-// float64 rounded once; 0 elsewhere.  A lane of A reads W[a][b], a lane of B W[b][a] (and subtracts).
-constexpr int kIvTable = 32 * 32;
-constexpr int kIvMaxTileRows = 8;               // rows of a workgroup's tile: small, so that a batch spreads over the CUs
-constexpr size_t kIvLdsBudget = 80 * 1024;      // two workgroups per CU where the tile allows it, as contribs_kernel
-constexpr int kIvUnroll = 8;                    // background rows whose mask and weight loads are issued together
 
 // One wave per bin: masks[b][r] = ballot over the bin's lanes of "background row r follows this element" (rank-0 lanes: 0).
 // SETS (both kernels): the handle's path elements carry category sets, the one-fraction is follows_set() (contribs_internal.h).
@@ -205,7 +194,44 @@ void free_istate(tahoe_istate *iv)
     delete iv;
 }
 
+// Where a handle's path bins live: tahoe_cstate (dense, sparse and multi-class handles: every class's bins, class-major) or the
+// one set of a vector-leaf handle created with TAHOE_CREATE_INTERVENTIONAL, which carries no category sets
+struct IvBins {
+    const uint4 *elems;
+    size_t bins;
+    const uint32_t *elem_set, *set_pool;
+    uint32_t set_words;
+};
+
+IvBins iv_bins(const tahoe_forest *f)
+{
+    if (f->vl) return {f->vl->shap->elems, (size_t)f->vl->shap->bins, nullptr, nullptr, 0u};
+    const tahoe_cstate *cs = f->cs;
+    return {cs->elems, cs->bins, cs->elem_set, cs->set_pool, cs->set_words};
+}
+
+// The kernels that read the background may need more than the default 64 KiB of dynamic LDS
+hipError_t iv_allow_lds(const tahoe_forest *f)
+{
+    if (f->vl) return vector_iv_allow_lds(f);
+    hipError_t e = hipSuccess;
+    if ((e = allow_max_lds(reinterpret_cast<const void *>(&interventional_kernel<true>), f->lds_limit)) != hipSuccess ||
+        (e = allow_max_lds(reinterpret_cast<const void *>(&interventional_kernel<false>), f->lds_limit)) != hipSuccess ||
+        (f->cs->elem_set &&
+         ((e = allow_max_lds(reinterpret_cast<const void *>(&interventional_kernel<true, true>), f->lds_limit)) != hipSuccess ||
+          (e = allow_max_lds(reinterpret_cast<const void *>(&interventional_kernel<false, true>), f->lds_limit)) != hipSuccess)))
+        return e;
+    return hipSuccess;
+}
+
 }  // namespace
+
+void launch_background_masks(unsigned long long *masks, const float *bg_dev, size_t bg_rows, int num_cols, size_t bins,
+                             const uint4 *elems, float missing, hipStream_t stream)
+{
+    hipLaunchKernelGGL(background_mask_kernel<false>, dim3((unsigned)((bins + kContribWaves - 1) / kContribWaves)), dim3(256), 0, stream,
+                       masks, bg_dev, bg_rows, num_cols, bins, elems, missing, nullptr, nullptr, 0u);
+}
 
 void interventional_destroy(tahoe_forest *f)
 {
@@ -222,9 +248,11 @@ using namespace tahoe;
 extern "C" tahoe_status tahoe_forest_set_background(tahoe_forest *f, const float *bg_dev, size_t bg_rows, void *stream)
 {
     if (!f) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_set_background: null forest");
-    if (tahoe_status st = need_path_tables(f, "tahoe_forest_set_background")) return st;
+    if (tahoe_status st = need_background_tables(f, "tahoe_forest_set_background")) return st;
     if (bg_rows > 0 && !bg_dev) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_set_background: null background");
-    const size_t F = (size_t)f->p.num_cols, C = (size_t)f->num_classes, bins = f->cs->bins;
+    // one body for both kinds of handle: a vector-leaf handle has num_classes = K, class_trees = num_trees and one set of bins
+    const IvBins pb = iv_bins(f);
+    const size_t F = (size_t)f->p.num_cols, C = (size_t)f->num_classes, bins = pb.bins;
     if (F > 0 && bg_rows > SIZE_MAX / sizeof(float) / F)
         return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_set_background: rows x num_cols floats overflow size_t (rows %zu)", bg_rows);
     if (bg_rows > (size_t)INT32_MAX)
@@ -267,20 +295,19 @@ extern "C" tahoe_status tahoe_forest_set_background(tahoe_forest *f, const float
     iv->bg_rows = bg_rows;
     iv->bytes = mask_bytes + const_bytes;
     if (bins > 0) {
-        const tahoe_cstate *cs = f->cs;
-        auto launch = [&](auto sets) {
-            hipLaunchKernelGGL(background_mask_kernel<decltype(sets)::value>, dim3((unsigned)((bins + kContribWaves - 1) / kContribWaves)),
-                               dim3(256), 0, s, iv->masks, bg_dev, bg_rows, (int)F, bins, cs->elems, f->p.missing, cs->elem_set,
-                               cs->set_pool, cs->set_words);
-        };
-        if (cs->elem_set) launch(std::true_type{});
-        else launch(std::false_type{});
+        if (pb.elem_set)
+            hipLaunchKernelGGL(background_mask_kernel<true>, dim3((unsigned)((bins + kContribWaves - 1) / kContribWaves)), dim3(256), 0, s,
+                               iv->masks, bg_dev, bg_rows, (int)F, bins, pb.elems, f->p.missing, pb.elem_set, pb.set_pool,
+                               pb.set_words);
+        else
+            launch_background_masks(iv->masks, bg_dev, bg_rows, (int)F, bins, pb.elems, f->p.missing, s);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess)
             return bail(fail(TAHOE_ERR_HIP, "tahoe_forest_set_background: mask kernel: %s", hipGetErrorString(e)));
     }
     // raw_c(r): tahoe_forest_predict_raw's bits (the same under every strategy); DIRECT serves every dense shape and allocates
-    // nothing (on a sparse handle it is sparse_kernel).  The caller's strategy setting is restored.
+    // nothing (on a sparse handle it is sparse_kernel, on a vector-leaf handle vector_direct_kernel).  The caller's strategy
+    // setting is restored.
     const int saved = f->strategy;
     f->strategy = TAHOE_STRATEGY_DIRECT;
     const tahoe_status st = tahoe_forest_predict_raw(f, sums, bg_dev, bg_rows, stream);
@@ -304,11 +331,7 @@ extern "C" tahoe_status tahoe_forest_set_background(tahoe_forest *f, const float
     if (e != hipSuccess) return bail(fail(TAHOE_ERR_HIP, "tahoe_forest_set_background: %s", hipGetErrorString(e)));
     (void)hipFree(sums);
     sums = nullptr;
-    if ((e = allow_max_lds(reinterpret_cast<const void *>(&interventional_kernel<true>), f->lds_limit)) != hipSuccess ||
-        (e = allow_max_lds(reinterpret_cast<const void *>(&interventional_kernel<false>), f->lds_limit)) != hipSuccess ||
-        (f->cs->elem_set &&
-         ((e = allow_max_lds(reinterpret_cast<const void *>(&interventional_kernel<true, true>), f->lds_limit)) != hipSuccess ||
-          (e = allow_max_lds(reinterpret_cast<const void *>(&interventional_kernel<false, true>), f->lds_limit)) != hipSuccess)))
+    if ((e = iv_allow_lds(f)) != hipSuccess)
         return bail(fail(TAHOE_ERR_HIP, "hipFuncSetAttribute(interventional) failed: %s", hipGetErrorString(e)));
     interventional_destroy(f);
     f->iv = iv;
@@ -320,13 +343,15 @@ extern "C" tahoe_status tahoe_forest_predict_contribs_interventional(tahoe_fores
                                                                      size_t rows, void *stream)
 {
     if (!f) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_contribs_interventional: null forest");
-    if (tahoe_status st = need_path_tables(f, "tahoe_forest_predict_contribs_interventional")) return st;
+    if (tahoe_status st = need_background_tables(f, "tahoe_forest_predict_contribs_interventional")) return st;
     if (!f->iv)
         return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_contribs_interventional: no background set "
                                            "(tahoe_forest_set_background)");
     if (rows == 0) return TAHOE_OK;
     if (!phi_dev || !data_dev) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_contribs_interventional: null argument");
     if (tahoe_status st = check_shap_out(f, rows, 1, "tahoe_forest_predict_contribs_interventional")) return st;
+    if (f->vl)
+        return vector_predict_interventional(f, phi_dev, data_dev, rows, (hipStream_t)stream, "tahoe_forest_predict_contribs_interventional");
     const int F = f->p.num_cols, C = f->num_classes;
     const IvShape sh = iv_shape(f);
     const size_t grid = (rows + (size_t)sh.rows - 1) / (size_t)sh.rows;

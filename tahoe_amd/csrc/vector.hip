@@ -192,6 +192,7 @@ void vector_destroy(tahoe_forest *f)
 {
     tahoe_vstate *v = f->vl;
     if (!v) return;
+    interventional_destroy(f);  // the background of a handle created with TAHOE_CREATE_INTERVENTIONAL
     vector_shap_destroy(f);
     if (v->nodes) (void)hipFree(v->nodes);
     if (v->roots) (void)hipFree(v->roots);
@@ -268,14 +269,17 @@ extern "C" tahoe_status tahoe_vector_forest_create_ex(tahoe_forest **out, const 
             level[(size_t)n.left_idx] = level[(size_t)n.left_idx + 1] = level[(size_t)i] + 1;
         }
     }
-    // the checks of tahoe_sparse_forest_create_ex for the flag: covers, and at most 31 distinct features on a leaf's path
-    if ((flags & ~TAHOE_CREATE_CONTRIBS) != 0)
-        return fail(TAHOE_ERR_INVALID_ARG, "unknown create flags 0x%x (a vector-leaf handle takes TAHOE_CREATE_CONTRIBS only)",
-                    flags & ~TAHOE_CREATE_CONTRIBS);
-    if (flags & TAHOE_CREATE_CONTRIBS) {
-        if (!covers) return fail(TAHOE_ERR_INVALID_ARG, "TAHOE_CREATE_CONTRIBS needs covers (one per node)");
-        if (const tahoe_status cs = contribs_validate_sparse(trees, nodes, covers, p, true)) return cs;
-    }
+    // the checks of tahoe_sparse_forest_create_ex for the flags: covers (TAHOE_CREATE_CONTRIBS; TAHOE_CREATE_INTERVENTIONAL alone
+    // reads none), and at most 31 distinct features on a leaf's path
+    constexpr unsigned kShapFlags = TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_INTERVENTIONAL;
+    if ((flags & ~kShapFlags) != 0)
+        return fail(TAHOE_ERR_INVALID_ARG,
+                    "unknown create flags 0x%x (a vector-leaf handle takes TAHOE_CREATE_CONTRIBS and TAHOE_CREATE_INTERVENTIONAL only)",
+                    flags & ~kShapFlags);
+    const bool with_covers = (flags & TAHOE_CREATE_CONTRIBS) != 0;
+    if (with_covers && !covers) return fail(TAHOE_ERR_INVALID_ARG, "TAHOE_CREATE_CONTRIBS needs covers (one per node)");
+    if (flags & kShapFlags)
+        if (const tahoe_status cs = contribs_validate_sparse(trees, nodes, covers, p, true, with_covers)) return cs;
 
     ForestPtr f;
     if (const tahoe_status s = open_handle(p, leaf_dim, f)) return s;
@@ -291,7 +295,8 @@ extern "C" tahoe_status tahoe_vector_forest_create_ex(tahoe_forest **out, const 
         (s = hip_status(upload(&v->leaves, leaf_values, (size_t)num_leaf_vectors * (size_t)leaf_dim, &f->device_bytes), "upload(leaves)")) ||
         (s = vector_allow_lds(f.get())))
         return s;
-    if ((flags & TAHOE_CREATE_CONTRIBS) && (s = vector_shap_build(f.get(), trees, nodes, leaf_values, covers))) return s;
+    if ((flags & kShapFlags) && (s = vector_shap_build(f.get(), trees, nodes, leaf_values, with_covers ? covers : nullptr, flags)))
+        return s;
     *out = f.release();
     return TAHOE_OK;
 }

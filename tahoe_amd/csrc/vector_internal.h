@@ -18,14 +18,17 @@ struct VNode {
 };
 static_assert(sizeof(VNode) == 16, "VNode must be 16 bytes");
 
-// The TreeSHAP path tables of a handle created with TAHOE_CREATE_CONTRIBS: one set of bins for the
-// forest, laid out as tahoe_cstate's, except that a path's root element carries the index of the leaf's vector in .x.  They are
-// kept off tahoe_forest::cs on purpose: the kernels that read tahoe_cstate take .x of a root element for a leaf value.
+// The TreeSHAP path tables of a handle created with TAHOE_CREATE_CONTRIBS and / or TAHOE_CREATE_INTERVENTIONAL (DESIGN.md
+// sections 26 and 27): one set of bins for the forest, laid out as tahoe_cstate's, except that a path's root element carries the
+// index of the leaf's vector in .x.  They are kept off tahoe_forest::cs on purpose: the kernels that read tahoe_cstate take .x of
+// a root element for a leaf value.  Without TAHOE_CREATE_CONTRIBS the bins are built from unit covers: .z is not to be read.
 struct VectorShap {
+    bool contribs = false;         // TAHOE_CREATE_CONTRIBS: one_minus_z, bias and the elements' .z are those of the caller's covers
+    bool interventional = false;   // TAHOE_CREATE_INTERVENTIONAL: tahoe_forest_set_background and its predict are served
     uint4 *elems = nullptr;        // [bins][64]
-    float *one_minus_z = nullptr;  // [bins][64]
+    float *one_minus_z = nullptr;  // [bins][64]; null without contribs
     uint32_t *bin_info = nullptr;  // [bins]
-    float *bias = nullptr;         // [K]
+    float *bias = nullptr;         // [K]; null without contribs
     float div = 1.0f;              // (float)num_trees with TAHOE_OUT_AVG, else 1.0f
     int bins = 0;
     size_t paths = 0, path_elems = 0;
@@ -33,6 +36,12 @@ struct VectorShap {
     int rows_per_tile = 0;         // R
     size_t lds_bytes = 0;          // (1 + 4 KB) R num_cols floats
     bool grid_blocks = false;      // gridDim.y runs over the class blocks (else a workgroup loops over them)
+    // vector_interventional_kernel<KB, WLDS> (vector_iv.hip): its class block, rows per tile, whether the weight table sits in LDS,
+    // and its LDS bytes ((1 + 4 KB) R num_cols floats and the table); fixed per handle by num_cols and K
+    int iv_class_block = 1;
+    int iv_rows = 0;
+    bool iv_wlds = true;
+    size_t iv_lds_bytes = 0;
 };
 
 }  // namespace tahoe
@@ -41,15 +50,18 @@ struct tahoe_vstate {
     tahoe::VNode *nodes = nullptr;
     int32_t *roots = nullptr;
     float *leaves = nullptr;
-    tahoe::VectorShap *shap = nullptr;  // non-null: created with TAHOE_CREATE_CONTRIBS
+    tahoe::VectorShap *shap = nullptr;  // non-null: created with TAHOE_CREATE_CONTRIBS and / or TAHOE_CREATE_INTERVENTIONAL
 };
 
 namespace tahoe {
 
-// vector_shap.hip.  vector_shap_build: the tables of a forest that has passed contribs_validate_sparse, from the caller's arrays;
+// vector_shap.hip.  vector_shap_build: the tables of a forest that has passed contribs_validate_sparse, from the caller's arrays,
+// for flags = TAHOE_CREATE_CONTRIBS and / or TAHOE_CREATE_INTERVENTIONAL (covers: null without the former);
 // vector_predict_contribs: tahoe_forest_predict_contribs on a handle with tables, entry checks included (fn: the call's name)
 tahoe_status vector_shap_build(tahoe_forest *f, const int32_t *trees, const tahoe_sparse_node *nodes, const float *leaf_values,
-                               const float *covers);
+                               const float *covers, unsigned flags);
 void vector_shap_destroy(tahoe_forest *f);
+// vector_iv.hip: class block, tile rows and LDS form of vector_interventional_kernel on f (sh->iv_*), from num_cols, K and the knobs
+void vector_iv_shape(const tahoe_forest *f, VectorShap *sh);
 
 }  // namespace tahoe

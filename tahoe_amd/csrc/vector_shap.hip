@@ -172,18 +172,21 @@ static size_t tile_rows(int F, int kb, size_t min_rows)
 }
 
 tahoe_status vector_shap_build(tahoe_forest *f, const int32_t *trees, const tahoe_sparse_node *nodes, const float *leaf_values,
-                               const float *covers)
+                               const float *covers, unsigned flags)
 {
     VectorPathTables h;
     if (const tahoe_status s = contribs_tables_vector(f, trees, nodes, leaf_values, covers, h)) return s;
     VectorShap *sh = new (std::nothrow) VectorShap();
     if (!sh) return fail(TAHOE_ERR_NO_MEMORY, "vector_shap_build");
     f->vl->shap = sh;
+    sh->contribs = (flags & TAHOE_CREATE_CONTRIBS) != 0;
+    sh->interventional = (flags & TAHOE_CREATE_INTERVENTIONAL) != 0;
     const int F = f->p.num_cols, K = f->num_classes;
     sh->bins = (int)h.bin_info.size();
     sh->paths = h.paths;
     sh->path_elems = h.path_elems;
-    sh->div = h.div.empty() ? 1.0f : h.div[0];  // (every tree feeds every class: one divisor)
+    // every tree feeds every class: one divisor, class_bias's (h.div, which a handle without TAHOE_CREATE_CONTRIBS does not get)
+    sh->div = ((f->p.output & TAHOE_OUT_AVG) != 0 && f->class_trees > 0) ? (float)f->class_trees : 1.0f;
     // The class block: the largest of 8, 4, 2 -- not above K rounded up to one of them -- that leaves a tile of >= 4 rows, else 1.
     // TAHOE_VECTOR_SHAP_KB forces one that leaves a tile of >= 1 row.  Neither changes a bit of the result.
     int kb = 1;
@@ -201,8 +204,11 @@ tahoe_status vector_shap_build(tahoe_forest *f, const int32_t *trees, const taho
     size_t *total = &f->device_bytes;
     tahoe_status s = TAHOE_OK;
     if ((s = hip_status(upload(&sh->elems, h.elems, total), "upload(path elements)")) ||
-        (s = hip_status(upload(&sh->one_minus_z, h.one_minus_z, total), "upload(one_minus_z)")) ||
-        (s = hip_status(upload(&sh->bin_info, h.bin_info, total), "upload(bin_info)")) ||
+        (s = hip_status(upload(&sh->bin_info, h.bin_info, total), "upload(bin_info)")))
+        return s;
+    if (sh->interventional) vector_iv_shape(f, sh);
+    if (!sh->contribs) return TAHOE_OK;  // only what the interventional game reads: no one_minus_z, no TreeSHAP bias
+    if ((s = hip_status(upload(&sh->one_minus_z, h.one_minus_z, total), "upload(one_minus_z)")) ||
         (s = hip_status(upload(&sh->bias, h.bias, total), "upload(bias)")))
         return s;
     hipError_t e = hipSuccess;
@@ -224,7 +230,7 @@ void vector_shap_destroy(tahoe_forest *f)
     f->vl->shap = nullptr;
 }
 
-bool vector_serves_contribs(const tahoe_forest *f) { return f->vl && f->vl->shap; }
+bool vector_serves_contribs(const tahoe_forest *f) { return f->vl && f->vl->shap && f->vl->shap->contribs; }
 
 tahoe_status vector_predict_contribs(tahoe_forest *f, float *phi_dev, const float *data_dev, size_t rows, hipStream_t stream,
                                      const char *fn)
