@@ -249,7 +249,9 @@ tahoe_status tahoe_forest_predict_contribs(tahoe_forest *f, float *phi_dev, cons
  * data_dev with rows > 0, or rows * C * (F + 1)^2 * 4 overflowing size_t: TAHOE_ERR_INVALID_ARG; a handle (dense or sparse)
  * created without TAHOE_CREATE_CONTRIBS: TAHOE_ERR_UNSUPPORTED; nothing launched on any refusal.  Sparse handles created with
  * the flag, those with categorical splits included, are served as by tahoe_forest_predict_contribs.  An oblivious handle is
- * served with TAHOE_CREATE_INTERACTIONS (tahoe_oblivious_forest_create_ex, which states the order of its sums). */
+ * served with TAHOE_CREATE_INTERACTIONS (tahoe_oblivious_forest_create_ex, which states the order of its sums), a vector-leaf
+ * handle with TAHOE_CREATE_VECTOR_INTERACTIONS (tahoe_vector_forest_create_ex): C = K there, and out[row][k] carries the bits of
+ * class k on the T x K-tree expansion on a sparse handle. */
 tahoe_status tahoe_forest_predict_interactions(tahoe_forest *f, float *out_dev, const float *data_dev, size_t rows, void *stream);
 
 /* Interventional TreeSHAP (SHAP's TreeExplainer(model, data=bg), feature_perturbation="interventional"; Lundberg et al. 2020):
@@ -532,20 +534,24 @@ tahoe_status tahoe_oblivious_forest_create_ex(tahoe_forest **out, const int32_t 
  * AUTO = ROWTILE when the tile fits, else DIRECT; TILEBLOCK, TILERING and QRING are TAHOE_ERR_UNSUPPORTED.
  * Out of scope, TAHOE_ERR_UNSUPPORTED with nothing launched and a text that names the call and says "vector-leaf":
  * tahoe_forest_predict_accumulate, _predict_host, _predict_csr, _reserve_csr (and _get_csr_plan: form TAHOE_FORM_NONE),
- * _set_stages, _predict_staged (_get_staged_strategy: 0), _predict_contribs_approx, _predict_interactions; _predict_contribs
- * unless the handle comes from tahoe_vector_forest_create_ex with TAHOE_CREATE_CONTRIBS; _set_background and
- * _predict_contribs_interventional unless it comes from there with TAHOE_CREATE_INTERVENTIONAL.  Categorical splits are not
- * represented. */
+ * _set_stages, _predict_staged (_get_staged_strategy: 0), _predict_contribs_approx; _predict_contribs unless the handle comes
+ * from tahoe_vector_forest_create_ex with TAHOE_CREATE_CONTRIBS; _set_background and _predict_contribs_interventional unless it
+ * comes from there with TAHOE_CREATE_INTERVENTIONAL; _predict_interactions unless it comes from there with
+ * TAHOE_CREATE_VECTOR_INTERACTIONS.  Categorical splits are not represented. */
 tahoe_status tahoe_vector_forest_create(tahoe_forest **out, const int32_t *trees, const tahoe_sparse_node *nodes,
                                         const float *leaf_values, int64_t num_leaf_vectors, const tahoe_forest_params *params,
                                         int leaf_dim);
 /* Interventional TreeSHAP on a vector-leaf handle: a create flag that tahoe_vector_forest_create_ex alone accepts (every other
  * create: its "unknown create flags" refusal), alone or with TAHOE_CREATE_CONTRIBS. */
 #define TAHOE_CREATE_INTERVENTIONAL 0x80u
-/* The same handle with explanations.  flags: a subset of TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_INTERVENTIONAL; with flags == 0 covers
- * is ignored and the call is tahoe_vector_forest_create (which is this call with NULL, 0), bit for bit; a handle created without
- * TAHOE_CREATE_INTERVENTIONAL is bit for bit and byte for byte what it was before that flag existed.  With TAHOE_CREATE_CONTRIBS
- * covers[i] is the cover of nodes[i] (num_nodes floats; scikit-learn's tree_.weighted_n_node_samples).
+/* SHAP interaction values on a vector-leaf handle: a create flag that tahoe_vector_forest_create_ex alone accepts (every other
+ * create: its refusal of an unknown flag), and only together with TAHOE_CREATE_CONTRIBS; TAHOE_CREATE_INTERVENTIONAL may join. */
+#define TAHOE_CREATE_VECTOR_INTERACTIONS 0x100u
+/* The same handle with explanations.  flags: a subset of TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_INTERVENTIONAL |
+ * TAHOE_CREATE_VECTOR_INTERACTIONS; with flags == 0 covers is ignored and the call is tahoe_vector_forest_create (which is this
+ * call with NULL, 0), bit for bit; a handle created without TAHOE_CREATE_INTERVENTIONAL or without
+ * TAHOE_CREATE_VECTOR_INTERACTIONS is bit for bit and byte for byte what it was before that flag existed.  With
+ * TAHOE_CREATE_CONTRIBS covers[i] is the cover of nodes[i] (num_nodes floats; scikit-learn's tree_.weighted_n_node_samples).
  * TAHOE_CREATE_INTERVENTIONAL serves tahoe_forest_set_background and tahoe_forest_predict_contribs_interventional as defined there.
  * Alone it ignores covers (NULL is fine: that game does not use them) and runs, of the checks below, the flag check and the
  * 31-distinct-features check (same code and text) and the num_cols limit; the handle then keeps only what that game reads, 16
@@ -554,7 +560,8 @@ tahoe_status tahoe_vector_forest_create(tahoe_forest **out, const int32_t *trees
  * tahoe_forest_predict_contribs stays TAHOE_ERR_UNSUPPORTED.  With both flags covers are required and checked, one set of tables
  * serves both calls and device_bytes is that of the TAHOE_CREATE_CONTRIBS handle.
  * Checks, before a device is touched and after those of tahoe_vector_forest_create, with the codes and texts of
- * tahoe_sparse_forest_create_ex: another flag bit: TAHOE_ERR_INVALID_ARG naming the bit; TAHOE_CREATE_CONTRIBS with covers == NULL:
+ * tahoe_sparse_forest_create_ex: another flag bit: TAHOE_ERR_INVALID_ARG naming the bit; TAHOE_CREATE_VECTOR_INTERACTIONS without
+ * TAHOE_CREATE_CONTRIBS: TAHOE_ERR_INVALID_ARG naming both flags; TAHOE_CREATE_CONTRIBS with covers == NULL:
  * TAHOE_ERR_INVALID_ARG; a reachable internal node whose children's covers are not finite, negative or sum to 0:
  * TAHOE_ERR_INVALID_FOREST naming the tree and the node; a reachable leaf whose path has more than 31 distinct features:
  * TAHOE_ERR_UNSUPPORTED naming the tree.  With a device: num_cols above a fifth of the LDS in floats (20 B per column):
@@ -568,8 +575,19 @@ tahoe_status tahoe_vector_forest_create(tahoe_forest **out, const int32_t *trees
  * leaf share one evaluation of its path; results do not depend on the batch, on how many outputs share an evaluation or on the
  * strategy (which the call does not use).  The call is asynchronous, allocates nothing and can be captured.
  * The tables count in device_bytes: 20 bytes per path element in 64-lane bins, once for the forest -- not once per output as on
- * the expansion -- and 4 K bytes of bias.  tahoe_forest_predict_interactions and _predict_contribs_approx stay
- * TAHOE_ERR_UNSUPPORTED as above on every vector-leaf handle, _set_background and _predict_contribs_interventional on one created
+ * the expansion -- and 4 K bytes of bias.
+ * TAHOE_CREATE_VECTOR_INTERACTIONS (with TAHOE_CREATE_CONTRIBS: covers required and checked as above) adds no table -- device_bytes
+ * is that of the handle without it -- and serves tahoe_forest_predict_interactions as defined there: out_dev rows x K x
+ * (num_cols + 1) x (num_cols + 1), asynchronous, allocating nothing, capturable, two kernels in stream order; rows == 0 is
+ * TAHOE_OK, then NULL pointers and an output that overflows size_t are TAHOE_ERR_INVALID_ARG.  out[row][k] is bit for bit what
+ * tahoe_sparse_forest_create_ex(num_classes = K, TAHOE_CREATE_CONTRIBS) gives for class k on the expansion with tree t's covers on
+ * every copy (K == 1: the sparse handle's bits on the same trees): the accumulation form is the sparse handle's, chosen by num_cols
+ * alone (LDS partial sums of four waves to num_cols = 71, in place in the output above), the diagonal is phi_i minus the row's
+ * off-diagonal sum ascending from 0.0f, row and column num_cols are +0.0f but the corner, which is the bias.  The conditioned
+ * recursion of a (row, path, conditioning element) runs once for a block of up to 8 outputs; results do not depend on the block,
+ * the batch or the strategy.
+ * tahoe_forest_predict_contribs_approx stays TAHOE_ERR_UNSUPPORTED as above on every vector-leaf handle, _predict_interactions on
+ * one created without TAHOE_CREATE_VECTOR_INTERACTIONS, _set_background and _predict_contribs_interventional on one created
  * without TAHOE_CREATE_INTERVENTIONAL. */
 tahoe_status tahoe_vector_forest_create_ex(tahoe_forest **out, const int32_t *trees, const tahoe_sparse_node *nodes,
                                            const float *leaf_values, int64_t num_leaf_vectors, const float *covers,

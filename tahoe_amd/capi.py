@@ -40,6 +40,7 @@ CREATE_APPROX_CONTRIBS = 0x10  # Saabas contributions (tahoe_forest_predict_cont
 CREATE_CAT_CONTRIBS = 0x20  # tahoe_sparse_forest_create_cat: the two flags above on a handle with categorical splits
 CREATE_INTERACTIONS = 0x40  # tahoe_oblivious_forest_create_ex: SHAP interaction values (tahoe_forest_predict_interactions)
 CREATE_INTERVENTIONAL = 0x80  # tahoe_vector_forest_create_ex: interventional TreeSHAP (tahoe_forest_set_background), no covers needed
+CREATE_VECTOR_INTERACTIONS = 0x100  # tahoe_vector_forest_create_ex, with CREATE_CONTRIBS: tahoe_forest_predict_interactions
 STRATEGY_NAMES = {1: "direct", 2: "rowtile", 3: "tileblock", 4: "tilering", 5: "qring"}
 STATUS_NAMES = {
     0: "TAHOE_OK",
@@ -589,7 +590,7 @@ class Forest:
     def predict_interactions(self, data, out=None, stream=None):
         """SHAP interaction values (tahoe_forest_predict_interactions): [rows, num_cols + 1, num_cols + 1] float32, or
         [rows, num_classes, num_cols + 1, num_cols + 1] on a multi-class handle; index num_cols is the bias.  Needs
-        contribs=True (an ObliviousForest: interactions=True)."""
+        contribs=True (an ObliviousForest or a VectorForest: interactions=True)."""
         return self._shap_out("tahoe_forest_predict_interactions", data, 2, out, stream)
 
     def predict_contribs_approx(self, data, out=None, stream=None):
@@ -851,11 +852,12 @@ class VectorForest(Forest):
     tree_.weighted_n_node_samples) and contribs=True go through tahoe_vector_forest_create_ex: predict_contribs then gives the
     TreeSHAP values of every output, [rows, K, num_cols + 1] ([rows, num_cols + 1] for K == 1).  interventional=True
     (TAHOE_CREATE_INTERVENTIONAL) serves set_background and predict_contribs_interventional in the same shape; alone it needs no
-    covers."""
+    covers.  interactions=True (TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_VECTOR_INTERACTIONS; needs covers) serves predict_contribs and
+    predict_interactions, [rows, K, num_cols + 1, num_cols + 1] ([rows, num_cols + 1, num_cols + 1] for K == 1)."""
 
     def __init__(self, nodes: np.ndarray, trees: np.ndarray, leaf_values, num_cols: int, leaf_dim: int = None,
                  missing: float = 0.0, output: int = OUT_RAW, threshold: float = 0.5, global_bias: float = 0.0, covers=None,
-                 contribs: bool = False, interventional: bool = False):
+                 contribs: bool = False, interventional: bool = False, interactions: bool = False):
         nodes = np.ascontiguousarray(nodes, dtype=SPARSE_NODE_DTYPE)
         trees = np.ascontiguousarray(trees, dtype=np.int32).reshape(-1)
         lv = np.asarray(leaf_values, dtype=np.float32)
@@ -873,7 +875,8 @@ class VectorForest(Forest):
         num_vectors = leaves.size // leaf_dim if leaf_dim >= 1 else 0
         self.params = ForestParams(int(nodes.size), 0, int(trees.size), num_cols, 0, output, threshold, global_bias, 0, missing)
         self._h = _vp()
-        flags = (CREATE_CONTRIBS if contribs else 0) | (CREATE_INTERVENTIONAL if interventional else 0)
+        flags = ((CREATE_CONTRIBS if contribs else 0) | (CREATE_INTERVENTIONAL if interventional else 0)
+                 | (CREATE_CONTRIBS | CREATE_VECTOR_INTERACTIONS if interactions else 0))
         if covers is not None or flags:
             cv = None if covers is None else np.ascontiguousarray(covers, dtype=np.float32).reshape(-1)
             if cv is not None and cv.size != nodes.size:

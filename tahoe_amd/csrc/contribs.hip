@@ -991,6 +991,8 @@ extern "C" tahoe_status tahoe_forest_predict_interactions(tahoe_forest *f, float
     if (!f) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_interactions: null forest");
     if (oblivious_serves(f, TAHOE_CREATE_INTERACTIONS))
         return oblivious_predict_interactions(f, out_dev, data_dev, rows, (hipStream_t)stream, "tahoe_forest_predict_interactions");
+    if (vector_serves_interactions(f))
+        return vector_predict_interactions(f, out_dev, data_dev, rows, (hipStream_t)stream, "tahoe_forest_predict_interactions");
     if (tahoe_status st = need_path_tables(f, "tahoe_forest_predict_interactions")) return st;
     if (rows == 0) return TAHOE_OK;
     if (!out_dev || !data_dev) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_interactions: null argument");

@@ -554,6 +554,12 @@ bool vector_serves_interventional(const tahoe_forest *f);
 tahoe_status vector_predict_interventional(tahoe_forest *f, float *phi_dev, const float *data_dev, size_t rows, hipStream_t stream,
                                            const char *fn);
 hipError_t vector_iv_allow_lds(const tahoe_forest *f);
+// ... its SHAP interaction values (vector_inter.hip).  vector_serves_interactions: was the handle created with
+// TAHOE_CREATE_VECTOR_INTERACTIONS?  vector_predict_interactions: tahoe_forest_predict_interactions on such a handle, entry checks
+// included (fn: the call's name)
+bool vector_serves_interactions(const tahoe_forest *f);
+tahoe_status vector_predict_interactions(tahoe_forest *f, float *out_dev, const float *data_dev, size_t rows, hipStream_t stream,
+                                         const char *fn);
 // The refusal of the entry points a vector-leaf handle does not serve (fn: the entry point's name); TAHOE_OK on every other handle
 inline tahoe_status refuse_vector(const tahoe_forest *f, const char *fn)
 {

@@ -271,11 +271,15 @@ extern "C" tahoe_status tahoe_vector_forest_create_ex(tahoe_forest **out, const 
     }
     // the checks of tahoe_sparse_forest_create_ex for the flags: covers (TAHOE_CREATE_CONTRIBS; TAHOE_CREATE_INTERVENTIONAL alone
     // reads none), and at most 31 distinct features on a leaf's path
-    constexpr unsigned kShapFlags = TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_INTERVENTIONAL;
+    constexpr unsigned kShapFlags = TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_INTERVENTIONAL | TAHOE_CREATE_VECTOR_INTERACTIONS;
     if ((flags & ~kShapFlags) != 0)
         return fail(TAHOE_ERR_INVALID_ARG,
-                    "unknown create flags 0x%x (a vector-leaf handle takes TAHOE_CREATE_CONTRIBS and TAHOE_CREATE_INTERVENTIONAL only)",
+                    "unknown create flags 0x%x (a vector-leaf handle takes TAHOE_CREATE_CONTRIBS, TAHOE_CREATE_INTERVENTIONAL and "
+                    "TAHOE_CREATE_VECTOR_INTERACTIONS only)",
                     flags & ~kShapFlags);
+    // interaction values take phi from the TreeSHAP pass and the covers' zero fractions: no meaning without TAHOE_CREATE_CONTRIBS
+    if ((flags & TAHOE_CREATE_VECTOR_INTERACTIONS) != 0 && (flags & TAHOE_CREATE_CONTRIBS) == 0)
+        return fail(TAHOE_ERR_INVALID_ARG, "TAHOE_CREATE_VECTOR_INTERACTIONS needs TAHOE_CREATE_CONTRIBS (and covers) in the same call");
     const bool with_covers = (flags & TAHOE_CREATE_CONTRIBS) != 0;
     if (with_covers && !covers) return fail(TAHOE_ERR_INVALID_ARG, "TAHOE_CREATE_CONTRIBS needs covers (one per node)");
     if (flags & kShapFlags)

@@ -1,5 +1,6 @@
-// The device state of a vector-leaf handle (tahoe_vector_forest_create), shared by vector.hip (create, the walk kernels) and
-// vector_shap.hip (TreeSHAP on such a handle).  Internal: not part of the ABI.
+// The device state of a vector-leaf handle (tahoe_vector_forest_create), shared by vector.hip (create, the walk kernels),
+// vector_shap.hip (TreeSHAP on such a handle), vector_iv.hip (interventional TreeSHAP) and vector_inter.hip (interaction values).
+// Internal: not part of the ABI.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -42,6 +43,15 @@ struct VectorShap {
     int iv_rows = 0;
     bool iv_wlds = true;
     size_t iv_lds_bytes = 0;
+    // TAHOE_CREATE_VECTOR_INTERACTIONS (with contribs): tahoe_forest_predict_interactions is served by
+    // vector_interactions_kernel<KB, SLABS> (vector_inter.hip) -- its form (triangle slabs in LDS, or in place in the output; by
+    // num_cols alone, as the sparse handle's), class block, rows of a tile (slabs; in place a wave owns one row) and LDS bytes
+    // (slabs: (num_cols + 4 KB num_cols (num_cols - 1) / 2) R floats; in place: 4 num_cols floats)
+    bool interactions = false;
+    bool inter_slabs = true;
+    int inter_class_block = 1;
+    int inter_rows = 1;
+    size_t inter_lds_bytes = 0;
 };
 
 }  // namespace tahoe
@@ -63,5 +73,11 @@ tahoe_status vector_shap_build(tahoe_forest *f, const int32_t *trees, const taho
 void vector_shap_destroy(tahoe_forest *f);
 // vector_iv.hip: class block, tile rows and LDS form of vector_interventional_kernel on f (sh->iv_*), from num_cols, K and the knobs
 void vector_iv_shape(const tahoe_forest *f, VectorShap *sh);
+// vector_shap.hip: the first kernel of tahoe_forest_predict_interactions on a handle with sh->interactions -- phi, with
+// vector_contribs_kernel's bits, into row num_cols of each (row, k) matrix of out_dev
+tahoe_status vector_launch_contribs_spare(tahoe_forest *f, float *out_dev, const float *data_dev, size_t rows, hipStream_t stream);
+// vector_inter.hip: form, class block, tile rows and LDS bytes of vector_interactions_kernel on f (sh->inter_*), from num_cols, K
+// and the knobs, and the LDS limit of the instantiation the handle uses
+tahoe_status vector_inter_build(const tahoe_forest *f, VectorShap *sh);
 
 }  // namespace tahoe

@@ -28,15 +28,18 @@ constexpr int kVecShapMinRows = 4;               // a class block wider than 1 m
 // evaluates bins w, w + 4, ... into its own KB slabs [R][F] of LDS, one per class of the block; per class the four wave slabs are
 // summed in wave order and written out.  LDS: tile [R][F] | slabs [4][KB][R][F].  The recursion of a (bin, row) is contribs_tile's,
 // statement for statement (restated here, not shared as a function: the kernels of contribs.hip must stay the code they are).
-template <int KB>
-__global__ __launch_bounds__(256) void vector_contribs_kernel(float *__restrict__ phi, const float *__restrict__ data, size_t rows,
-                                                              int F, int K, int R, const uint4 *__restrict__ elems,
-                                                              const float *__restrict__ one_minus_z,
-                                                              const uint32_t *__restrict__ bin_info, int bins,
-                                                              const float *__restrict__ leaves, const float *__restrict__ bias,
-                                                              float div, float missing)
+// SPARE = false: phi[rows][K][F + 1] (vector_contribs_kernel).  SPARE = true: the same values into row F of each (row, k) matrix of
+// out[rows][K][F + 1][F + 1] (tahoe_forest_predict_interactions on a handle with TAHOE_CREATE_VECTOR_INTERACTIONS,
+// vector_contribs_spare_kernel).
+template <int KB, bool SPARE>
+__device__ __forceinline__ void vector_contribs_tile(float *__restrict__ phi, const float *__restrict__ data, size_t rows, int F, int K,
+                                                     int R, const uint4 *__restrict__ elems, const float *__restrict__ one_minus_z,
+                                                     const uint32_t *__restrict__ bin_info, int bins,
+                                                     const float *__restrict__ leaves, const float *__restrict__ bias, float div,
+                                                     float missing)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
+    if (SPARE) phi += (size_t)F * (F + 1);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const size_t row0 = (size_t)blockIdx.x * R;
@@ -47,7 +50,8 @@ __global__ __launch_bounds__(256) void vector_contribs_kernel(float *__restrict_
     float *slab = smem + slab_n * (1 + (size_t)wave * KB);  // this wave's KB slabs, class j of the block at slab + j slab_n
     const float *src = data + row0 * F;
     for (int i = tid; i < tile_n; i += 256) tile[i] = src[i];
-    const size_t out_row = (size_t)K * (F + 1);
+    const size_t mat = (size_t)(F + 1) * (F + 1);
+    const size_t out_row = SPARE ? (size_t)K * mat : (size_t)K * (F + 1);
 
     for (int k0 = (int)blockIdx.y * KB; k0 < K; k0 += (int)gridDim.y * KB) {
         const int nk = min(KB, K - k0);  // classes of this block
@@ -137,7 +141,7 @@ __global__ __launch_bounds__(256) void vector_contribs_kernel(float *__restrict_
         for (int j = 0; j < KB; ++j) {
             if (j >= nk) continue;
             const float *s0 = smem + slab_n * (1 + j), *s1 = s0 + KB * slab_n, *s2 = s1 + KB * slab_n, *s3 = s2 + KB * slab_n;
-            float *out = phi + row0 * out_row + (size_t)(k0 + j) * (F + 1);
+            float *out = phi + row0 * out_row + (size_t)(k0 + j) * (SPARE ? mat : (F + 1));
             for (int i = tid; i < tile_n; i += 256) {
                 const int r = i / F, col = i - r * F;
                 const float v = ((s0[i] + s1[i]) + s2[i]) + s3[i];
@@ -148,6 +152,22 @@ __global__ __launch_bounds__(256) void vector_contribs_kernel(float *__restrict_
         __syncthreads();
     }
 }
+
+#define TAHOE_VECTOR_SHAP_PARAMS                                                                                                  \
+    float *__restrict__ phi, const float *__restrict__ data, size_t rows, int F, int K, int R, const uint4 *__restrict__ elems,  \
+        const float *__restrict__ one_minus_z, const uint32_t *__restrict__ bin_info, int bins,                                   \
+        const float *__restrict__ leaves, const float *__restrict__ bias, float div, float missing
+template <int KB>
+__global__ __launch_bounds__(256) void vector_contribs_kernel(TAHOE_VECTOR_SHAP_PARAMS)
+{
+    vector_contribs_tile<KB, false>(phi, data, rows, F, K, R, elems, one_minus_z, bin_info, bins, leaves, bias, div, missing);
+}
+template <int KB>
+__global__ __launch_bounds__(256) void vector_contribs_spare_kernel(TAHOE_VECTOR_SHAP_PARAMS)
+{
+    vector_contribs_tile<KB, true>(phi, data, rows, F, K, R, elems, one_minus_z, bin_info, bins, leaves, bias, div, missing);
+}
+#undef TAHOE_VECTOR_SHAP_PARAMS
 
 // kernel(kb) for the runtime class block
 template <class Fn>
@@ -181,6 +201,7 @@ tahoe_status vector_shap_build(tahoe_forest *f, const int32_t *trees, const taho
     f->vl->shap = sh;
     sh->contribs = (flags & TAHOE_CREATE_CONTRIBS) != 0;
     sh->interventional = (flags & TAHOE_CREATE_INTERVENTIONAL) != 0;
+    sh->interactions = (flags & TAHOE_CREATE_VECTOR_INTERACTIONS) != 0;
     const int F = f->p.num_cols, K = f->num_classes;
     sh->bins = (int)h.bin_info.size();
     sh->paths = h.paths;
@@ -215,7 +236,13 @@ tahoe_status vector_shap_build(tahoe_forest *f, const int32_t *trees, const taho
     with_class_block(kb, [&](auto c) {
         e = allow_max_lds(reinterpret_cast<const void *>(&vector_contribs_kernel<decltype(c)::value>), f->lds_limit);
     });
-    return hip_status(e, "hipFuncSetAttribute(vector_contribs)");
+    if (e != hipSuccess || !sh->interactions) return hip_status(e, "hipFuncSetAttribute(vector_contribs)");
+    // TAHOE_CREATE_VECTOR_INTERACTIONS: no table of its own, the shape of vector_interactions_kernel and the LDS of the two kernels
+    with_class_block(kb, [&](auto c) {
+        e = allow_max_lds(reinterpret_cast<const void *>(&vector_contribs_spare_kernel<decltype(c)::value>), f->lds_limit);
+    });
+    if (e != hipSuccess) return hip_status(e, "hipFuncSetAttribute(vector_contribs_spare)");
+    return vector_inter_build(f, sh);
 }
 
 void vector_shap_destroy(tahoe_forest *f)
@@ -246,6 +273,21 @@ tahoe_status vector_predict_contribs(tahoe_forest *f, float *phi_dev, const floa
     with_class_block(kb, [&](auto c) {
         hipLaunchKernelGGL(vector_contribs_kernel<decltype(c)::value>, grid, dim3(256), sh->lds_bytes, stream, phi_dev, data_dev, rows,
                            f->p.num_cols, K, (int)R, sh->elems, sh->one_minus_z, sh->bin_info, sh->bins, f->vl->leaves, sh->bias,
+                           sh->div, f->p.missing);
+    });
+    TAHOE_HIP_TRY(hipGetLastError());
+    return TAHOE_OK;
+}
+
+tahoe_status vector_launch_contribs_spare(tahoe_forest *f, float *out_dev, const float *data_dev, size_t rows, hipStream_t stream)
+{
+    const VectorShap *sh = f->vl->shap;
+    const int K = f->num_classes, kb = sh->class_block;
+    const size_t R = (size_t)sh->rows_per_tile;
+    const dim3 grid((unsigned)((rows + R - 1) / R), sh->grid_blocks ? (unsigned)((K + kb - 1) / kb) : 1u);
+    with_class_block(kb, [&](auto c) {
+        hipLaunchKernelGGL(vector_contribs_spare_kernel<decltype(c)::value>, grid, dim3(256), sh->lds_bytes, stream, out_dev, data_dev,
+                           rows, f->p.num_cols, K, (int)R, sh->elems, sh->one_minus_z, sh->bin_info, sh->bins, f->vl->leaves, sh->bias,
                            sh->div, f->p.missing);
     });
     TAHOE_HIP_TRY(hipGetLastError());
