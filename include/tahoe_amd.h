@@ -326,7 +326,9 @@ tahoe_status tahoe_forest_predict_contribs_interventional(tahoe_forest *f, float
  * TAHOE_ERR_INVALID_ARG; a handle created without TAHOE_CREATE_APPROX_CONTRIBS: TAHOE_ERR_UNSUPPORTED; then rows == 0: TAHOE_OK;
  * NULL phi_dev / data_dev with rows > 0, or rows x C x (num_cols + 1) x 4 overflowing size_t: TAHOE_ERR_INVALID_ARG.  On a handle
  * with categorical splits (TAHOE_CREATE_CAT_CONTRIBS) the row follows tahoe_sparse_forest_create_cat's path; the deltas are per
- * child whatever the kind of the split. */
+ * child whatever the kind of the split.  A vector-leaf handle serves the call with TAHOE_CREATE_VECTOR_APPROX
+ * (tahoe_vector_forest_create_ex, which states the definition per output): C = K there, and phi[row][k] carries the bits of class
+ * k of the handle's K-fold expansion under TAHOE_CREATE_APPROX_CONTRIBS; without that flag: TAHOE_ERR_UNSUPPORTED. */
 tahoe_status tahoe_forest_predict_contribs_approx(tahoe_forest *f, float *phi_dev, const float *data_dev, size_t rows, void *stream);
 
 /* TreeSHAP and Saabas contributions on a handle with categorical splits.  A create flag for tahoe_sparse_forest_create_cat only
@@ -534,8 +536,9 @@ tahoe_status tahoe_oblivious_forest_create_ex(tahoe_forest **out, const int32_t 
  * AUTO = ROWTILE when the tile fits, else DIRECT; TILEBLOCK, TILERING and QRING are TAHOE_ERR_UNSUPPORTED.
  * Out of scope, TAHOE_ERR_UNSUPPORTED with nothing launched and a text that names the call and says "vector-leaf":
  * tahoe_forest_predict_accumulate, _predict_host, _predict_csr, _reserve_csr (and _get_csr_plan: form TAHOE_FORM_NONE),
- * _set_stages, _predict_staged (_get_staged_strategy: 0), _predict_contribs_approx; _predict_contribs unless the handle comes
- * from tahoe_vector_forest_create_ex with TAHOE_CREATE_CONTRIBS; _set_background and _predict_contribs_interventional unless it
+ * _set_stages, _predict_staged (_get_staged_strategy: 0); _predict_contribs_approx unless the handle comes from _create_ex with
+ * TAHOE_CREATE_VECTOR_APPROX; _predict_contribs unless the handle comes from tahoe_vector_forest_create_ex with
+ * TAHOE_CREATE_CONTRIBS; _set_background and _predict_contribs_interventional unless it
  * comes from there with TAHOE_CREATE_INTERVENTIONAL; _predict_interactions unless it comes from there with
  * TAHOE_CREATE_VECTOR_INTERACTIONS.  Categorical splits are not represented. */
 tahoe_status tahoe_vector_forest_create(tahoe_forest **out, const int32_t *trees, const tahoe_sparse_node *nodes,
@@ -547,8 +550,12 @@ tahoe_status tahoe_vector_forest_create(tahoe_forest **out, const int32_t *trees
 /* SHAP interaction values on a vector-leaf handle: a create flag that tahoe_vector_forest_create_ex alone accepts (every other
  * create: its refusal of an unknown flag), and only together with TAHOE_CREATE_CONTRIBS; TAHOE_CREATE_INTERVENTIONAL may join. */
 #define TAHOE_CREATE_VECTOR_INTERACTIONS 0x100u
+/* Saabas contributions on a vector-leaf handle: a create flag that tahoe_vector_forest_create_ex alone accepts (every other
+ * create: TAHOE_ERR_INVALID_ARG, its refusal of an unknown flag), alone or with any of the three flags above.  It is not
+ * TAHOE_CREATE_APPROX_CONTRIBS (0x10), which stays an unknown flag on that create, as does 0x200. */
+#define TAHOE_CREATE_VECTOR_APPROX 0x400u
 /* The same handle with explanations.  flags: a subset of TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_INTERVENTIONAL |
- * TAHOE_CREATE_VECTOR_INTERACTIONS; with flags == 0 covers is ignored and the call is tahoe_vector_forest_create (which is this
+ * TAHOE_CREATE_VECTOR_INTERACTIONS | TAHOE_CREATE_VECTOR_APPROX; with flags == 0 covers is ignored and the call is tahoe_vector_forest_create (which is this
  * call with NULL, 0), bit for bit; a handle created without TAHOE_CREATE_INTERVENTIONAL or without
  * TAHOE_CREATE_VECTOR_INTERACTIONS is bit for bit and byte for byte what it was before that flag existed.  With
  * TAHOE_CREATE_CONTRIBS covers[i] is the cover of nodes[i] (num_nodes floats; scikit-learn's tree_.weighted_n_node_samples).
@@ -586,7 +593,26 @@ tahoe_status tahoe_vector_forest_create(tahoe_forest **out, const int32_t *trees
  * off-diagonal sum ascending from 0.0f, row and column num_cols are +0.0f but the corner, which is the bias.  The conditioned
  * recursion of a (row, path, conditioning element) runs once for a block of up to 8 outputs; results do not depend on the block,
  * the batch or the strategy.
- * tahoe_forest_predict_contribs_approx stays TAHOE_ERR_UNSUPPORTED as above on every vector-leaf handle, _predict_interactions on
+ * TAHOE_CREATE_VECTOR_APPROX serves tahoe_forest_predict_contribs_approx: Saabas contributions of every output, phi_dev rows x K x
+ * (num_cols + 1), bias last.  It needs covers (NULL: TAHOE_ERR_INVALID_ARG, "TAHOE_CREATE_VECTOR_APPROX needs covers"), checked as
+ * tahoe_sparse_forest_create_ex checks them for TAHOE_CREATE_APPROX_CONTRIBS, with its codes and texts: the sibling covers at
+ * every reachable internal node finite, >= 0 and of positive sum.  Path lengths are not checked: alone, the flag knows neither the
+ * 31-distinct-features limit nor the 20-B-per-column limit and builds no path bins; with other flags each flag keeps its own
+ * checks.  Definition: node means per output k in float64, E_k(n) = (wl * E_k(l) + wr * E_k(r)) / (wl + wr) with wl, wr the
+ * children's covers, and E_k = (double)leaf_values[left_idx * K + k] at a leaf; each child of a reachable internal node carries
+ * d_k = (float)(E_k(child) - E_k(n)).  The row follows predict's path, and every internal node on it adds the taken child's d_k to
+ * phi[k][fid]: per (row, k, feature) one float32 sum from +0.0f, trees 0..T-1 in order, root to leaf, then with AVG one division
+ * by (float)num_trees.  Bias column k is bit for bit the bias of tahoe_forest_predict_contribs on a vector-leaf handle (above).
+ * phi[row][k] is bit for bit what tahoe_sparse_forest_create_ex(num_classes = K, TAHOE_CREATE_APPROX_CONTRIBS) gives for class k on
+ * the T x K-tree expansion with tree t's covers on every copy; with K == 1 the bits of the sparse handle on the same trees.  One
+ * walk per (row, tree) feeds a block of up to 8 outputs; results do not depend on the batch, on the block, on where the sums are
+ * accumulated (LDS or phi_dev) or on the strategy, which the call does not use.  rows == 0 is TAHOE_OK, then NULL pointers
+ * ("null argument") and an output that overflows size_t are TAHOE_ERR_INVALID_ARG.  The call is asynchronous, allocates nothing
+ * and can be captured.  device_bytes grows by exactly the new tables: 4 Kp max(num_nodes, 1) bytes of deltas, Kp = K rounded up
+ * to a multiple of the handle's class block (1, 2, 4 or 8; DESIGN.md section 29 has the rule), and 4 K bytes of bias.  Every other
+ * call on a handle with the flag gives the bits it gives without it.
+ * On a handle created without TAHOE_CREATE_VECTOR_APPROX tahoe_forest_predict_contribs_approx stays TAHOE_ERR_UNSUPPORTED as
+ * above, _predict_interactions on
  * one created without TAHOE_CREATE_VECTOR_INTERACTIONS, _set_background and _predict_contribs_interventional on one created
  * without TAHOE_CREATE_INTERVENTIONAL. */
 tahoe_status tahoe_vector_forest_create_ex(tahoe_forest **out, const int32_t *trees, const tahoe_sparse_node *nodes,

@@ -41,6 +41,7 @@ CREATE_CAT_CONTRIBS = 0x20  # tahoe_sparse_forest_create_cat: the two flags abov
 CREATE_INTERACTIONS = 0x40  # tahoe_oblivious_forest_create_ex: SHAP interaction values (tahoe_forest_predict_interactions)
 CREATE_INTERVENTIONAL = 0x80  # tahoe_vector_forest_create_ex: interventional TreeSHAP (tahoe_forest_set_background), no covers needed
 CREATE_VECTOR_INTERACTIONS = 0x100  # tahoe_vector_forest_create_ex, with CREATE_CONTRIBS: tahoe_forest_predict_interactions
+CREATE_VECTOR_APPROX = 0x400  # tahoe_vector_forest_create_ex: Saabas contributions (tahoe_forest_predict_contribs_approx); needs covers
 STRATEGY_NAMES = {1: "direct", 2: "rowtile", 3: "tileblock", 4: "tilering", 5: "qring"}
 STATUS_NAMES = {
     0: "TAHOE_OK",
@@ -595,7 +596,8 @@ class Forest:
 
     def predict_contribs_approx(self, data, out=None, stream=None):
         """Saabas contributions (XGBoost approx_contribs, tahoe_forest_predict_contribs_approx): [rows, num_cols + 1] float32, or
-        [rows, num_classes, num_cols + 1] on a multi-class handle; the bias is the last column.  Needs approx_contribs=True."""
+        [rows, num_classes, num_cols + 1] on a multi-class handle ([rows, K, num_cols + 1] on a VectorForest with K > 1); the
+        bias is the last column.  Needs approx_contribs=True."""
         return self._shap_out("tahoe_forest_predict_contribs_approx", data, 1, out, stream)
 
     def set_background(self, bg, stream=None) -> None:
@@ -853,11 +855,14 @@ class VectorForest(Forest):
     TreeSHAP values of every output, [rows, K, num_cols + 1] ([rows, num_cols + 1] for K == 1).  interventional=True
     (TAHOE_CREATE_INTERVENTIONAL) serves set_background and predict_contribs_interventional in the same shape; alone it needs no
     covers.  interactions=True (TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_VECTOR_INTERACTIONS; needs covers) serves predict_contribs and
-    predict_interactions, [rows, K, num_cols + 1, num_cols + 1] ([rows, num_cols + 1, num_cols + 1] for K == 1)."""
+    predict_interactions, [rows, K, num_cols + 1, num_cols + 1] ([rows, num_cols + 1, num_cols + 1] for K == 1).
+    approx_contribs=True (TAHOE_CREATE_VECTOR_APPROX; needs covers, checks no path length) serves predict_contribs_approx: the
+    Saabas contributions of every output, what treeinterpreter computes for a scikit-learn forest, in predict_contribs' shape."""
 
     def __init__(self, nodes: np.ndarray, trees: np.ndarray, leaf_values, num_cols: int, leaf_dim: int = None,
                  missing: float = 0.0, output: int = OUT_RAW, threshold: float = 0.5, global_bias: float = 0.0, covers=None,
-                 contribs: bool = False, interventional: bool = False, interactions: bool = False):
+                 contribs: bool = False, interventional: bool = False, interactions: bool = False,
+                 approx_contribs: bool = False):
         nodes = np.ascontiguousarray(nodes, dtype=SPARSE_NODE_DTYPE)
         trees = np.ascontiguousarray(trees, dtype=np.int32).reshape(-1)
         lv = np.asarray(leaf_values, dtype=np.float32)
@@ -876,7 +881,8 @@ class VectorForest(Forest):
         self.params = ForestParams(int(nodes.size), 0, int(trees.size), num_cols, 0, output, threshold, global_bias, 0, missing)
         self._h = _vp()
         flags = ((CREATE_CONTRIBS if contribs else 0) | (CREATE_INTERVENTIONAL if interventional else 0)
-                 | (CREATE_CONTRIBS | CREATE_VECTOR_INTERACTIONS if interactions else 0))
+                 | (CREATE_CONTRIBS | CREATE_VECTOR_INTERACTIONS if interactions else 0)
+                 | (CREATE_VECTOR_APPROX if approx_contribs else 0))
         if covers is not None or flags:
             cv = None if covers is None else np.ascontiguousarray(covers, dtype=np.float32).reshape(-1)
             if cv is not None and cv.size != nodes.size:

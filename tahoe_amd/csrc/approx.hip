@@ -228,16 +228,11 @@ tahoe_status approx_build_sparse(tahoe_forest *f, const int32_t *trees, const ta
             const size_t a = (size_t)trees[t], b = t + 1 < (size_t)T ? (size_t)trees[t + 1] : N;
             const tahoe_sparse_node *tn = nodes + a;
             const float *tc = covers + a;
-            E.assign(b - a, 0.0);
-            for (size_t i = b - a; i-- > 0;) {
-                if (tn[i].bits < 0) {
-                    E[i] = (double)tn[i].val;
-                    continue;
-                }
+            saabas_means(tn, tc, b - a, E, [&](size_t i) { return tn[i].val; });
+            for (size_t i = 0; i < b - a; ++i) {
+                if (tn[i].bits < 0) continue;
                 const size_t l = (size_t)tn[i].left_idx;
-                const double wl = tc[l], wr = tc[l + 1];
-                E[i] = (wl * E[l] + wr * E[l + 1]) / (wl + wr);
-                dd[a + i] = make_float2((float)(E[l] - E[i]), (float)(E[l + 1] - E[i]));
+                dd[a + i] = make_float2(saabas_delta(E, l, i), saabas_delta(E, l + 1, i));
             }
         }
     });
@@ -282,6 +277,8 @@ extern "C" tahoe_status tahoe_forest_predict_contribs_approx(tahoe_forest *f, fl
     if (oblivious_serves(f, TAHOE_CREATE_APPROX_CONTRIBS))
         return oblivious_predict_shap(f, TAHOE_CREATE_APPROX_CONTRIBS, phi_dev, data_dev, rows, (hipStream_t)stream,
                                       "tahoe_forest_predict_contribs_approx");
+    if (vector_serves_approx(f))
+        return vector_predict_approx(f, phi_dev, data_dev, rows, (hipStream_t)stream, "tahoe_forest_predict_contribs_approx");
     if (const tahoe_status st = refuse_oblivious(f, "tahoe_forest_predict_contribs_approx")) return st;
     if (const tahoe_status st = refuse_vector(f, "tahoe_forest_predict_contribs_approx")) return st;
     if (!f->ap)

@@ -907,25 +907,36 @@ tahoe_status contribs_build_sparse(tahoe_forest *f, const int32_t *tree_roots, c
     return build_tables(f, trees);
 }
 
+void contribs_bias_vector(const tahoe_forest *f, const int32_t *tree_roots, const tahoe_sparse_node *nodes, const float *leaf_values,
+                          const float *covers, std::vector<float> &bias, std::vector<float> &div)
+{
+    const size_t T = (size_t)f->p.num_trees, K = (size_t)f->num_classes;
+    std::vector<double> expect(T * K);  // [tree][k]: what class_bias reads on the expansion's tree t * K + k
+    parallel_for(T, 4, [&](size_t lo, size_t hi) {
+        for (size_t t = lo; t < hi; ++t) {
+            const SparseTree tree{nodes + tree_roots[t], covers + tree_roots[t]};
+            for (size_t k = 0; k < K; ++k) expect[t * K + k] = tree_expect(VectorTreeK{tree, leaf_values, K, k});
+        }
+    });
+    class_bias(f, expect, bias, div);
+}
+
 tahoe_status contribs_tables_vector(const tahoe_forest *f, const int32_t *tree_roots, const tahoe_sparse_node *nodes,
                                     const float *leaf_values, const float *covers, VectorPathTables &out)
 {
     if (const tahoe_status s = check_contrib_cols(f)) return s;
-    const size_t T = (size_t)f->p.num_trees, K = (size_t)f->num_classes;
+    const size_t T = (size_t)f->p.num_trees;
     std::vector<TreePaths> trees(T);
-    std::vector<double> expect(covers ? T * K : 0);  // [tree][k]: what class_bias reads on the expansion's tree t * K + k
     parallel_for(T, 4, [&](size_t lo, size_t hi) {
         for (size_t t = lo; t < hi; ++t) {
             if (!covers) {
                 tree_paths(VectorTreeUnit{VectorTree{SparseTree{nodes + tree_roots[t], nullptr}}}, trees[t]);
                 continue;
             }
-            const SparseTree tree{nodes + tree_roots[t], covers + tree_roots[t]};
-            tree_paths(VectorTree{tree}, trees[t]);
-            for (size_t k = 0; k < K; ++k) expect[t * K + k] = tree_expect(VectorTreeK{tree, leaf_values, K, k});
+            tree_paths(VectorTree{SparseTree{nodes + tree_roots[t], covers + tree_roots[t]}}, trees[t]);
         }
     });
-    if (covers) class_bias(f, expect, out.bias, out.div);
+    if (covers) contribs_bias_vector(f, tree_roots, nodes, leaf_values, covers, out.bias, out.div);
     PathBins bins;
     pack_paths(trees, 1, T, bins);  // one set of bins: what the sparse handle builds for one class of the expansion
     out.elems.swap(bins.elems);

@@ -609,5 +609,33 @@ tahoe_status approx_build(tahoe_forest *f, const tahoe_dense_node *nodes, const 
                           const std::vector<unsigned char> &h_real);
 tahoe_status approx_build_sparse(tahoe_forest *f, const int32_t *trees, const tahoe_sparse_node *nodes, const float *covers);
 void approx_destroy(tahoe_forest *f);
+// The node means of one sparse-layout tree of n nodes (tn, with its covers tc), bottom-up in float64: children lie after their
+// parent; leaf(i) is the value of leaf i.  The one definition behind the deltas of approx_build_sparse and of a vector-leaf
+// handle (vector_approx.hip), which must agree in every bit.
+template <class Leaf>
+inline void saabas_means(const tahoe_sparse_node *tn, const float *tc, size_t n, std::vector<double> &E, Leaf &&leaf)
+{
+    E.assign(n, 0.0);
+    for (size_t i = n; i-- > 0;) {
+        if (tn[i].bits < 0) {
+            E[i] = (double)leaf(i);
+            continue;
+        }
+        const size_t l = (size_t)tn[i].left_idx;
+        const double wl = tc[l], wr = tc[l + 1];
+        E[i] = (wl * E[l] + wr * E[l + 1]) / (wl + wr);
+    }
+}
+// ... and the delta a child c of node i carries
+inline float saabas_delta(const std::vector<double> &E, size_t c, size_t i) { return (float)(E[c] - E[i]); }
+// Saabas contributions on a vector-leaf handle (vector_approx.hip).  vector_serves_approx: was the handle created with
+// TAHOE_CREATE_VECTOR_APPROX?  vector_predict_approx: tahoe_forest_predict_contribs_approx on such a handle, entry checks included
+bool vector_serves_approx(const tahoe_forest *f);
+tahoe_status vector_predict_approx(tahoe_forest *f, float *phi_dev, const float *data_dev, size_t rows, hipStream_t stream,
+                                   const char *fn);
+// The bias column of a vector-leaf handle (bias[k]; contribs.hip): what tahoe_forest_predict_contribs and _predict_contribs_approx
+// both write, from the caller's validated trees and covers; div[k] as contribs_bias's
+void contribs_bias_vector(const tahoe_forest *f, const int32_t *trees, const tahoe_sparse_node *nodes, const float *leaf_values,
+                          const float *covers, std::vector<float> &bias, std::vector<float> &div);
 
 }  // namespace tahoe

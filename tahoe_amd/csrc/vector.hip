@@ -25,9 +25,6 @@ namespace tahoe {
 
 constexpr int kVecTrees = 4;    // consecutive trees a lane walks at once; their leaf reads are in flight before they are added in order
 constexpr int kVecClasses = 8;  // accumulators a lane keeps: gridDim.y runs over blocks of 8 classes, each repeats the walk
-constexpr uint32_t kVFidMask = (1u << 30) - 1u;
-constexpr uint32_t kVDefLeft = 1u << 30;
-constexpr uint32_t kVIsLeaf = 1u << 31;
 
 // The walk of one row over all trees, for classes [blockIdx.y * KB, + KB).  feature(fid) reads the row's value of a feature.
 // KB == 1 is the single-output handle (K == 1), KB == kVecClasses a block of a vector leaf.  Leaf indices are written once, by
@@ -194,6 +191,7 @@ void vector_destroy(tahoe_forest *f)
     if (!v) return;
     interventional_destroy(f);  // the background of a handle created with TAHOE_CREATE_INTERVENTIONAL
     vector_shap_destroy(f);
+    vector_approx_destroy(f);
     if (v->nodes) (void)hipFree(v->nodes);
     if (v->roots) (void)hipFree(v->roots);
     if (v->leaves) (void)hipFree(v->leaves);
@@ -272,18 +270,24 @@ extern "C" tahoe_status tahoe_vector_forest_create_ex(tahoe_forest **out, const 
     // the checks of tahoe_sparse_forest_create_ex for the flags: covers (TAHOE_CREATE_CONTRIBS; TAHOE_CREATE_INTERVENTIONAL alone
     // reads none), and at most 31 distinct features on a leaf's path
     constexpr unsigned kShapFlags = TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_INTERVENTIONAL | TAHOE_CREATE_VECTOR_INTERACTIONS;
-    if ((flags & ~kShapFlags) != 0)
+    if ((flags & ~(kShapFlags | TAHOE_CREATE_VECTOR_APPROX)) != 0)
         return fail(TAHOE_ERR_INVALID_ARG,
-                    "unknown create flags 0x%x (a vector-leaf handle takes TAHOE_CREATE_CONTRIBS, TAHOE_CREATE_INTERVENTIONAL and "
-                    "TAHOE_CREATE_VECTOR_INTERACTIONS only)",
-                    flags & ~kShapFlags);
+                    "unknown create flags 0x%x (a vector-leaf handle takes TAHOE_CREATE_CONTRIBS, TAHOE_CREATE_INTERVENTIONAL, "
+                    "TAHOE_CREATE_VECTOR_INTERACTIONS and TAHOE_CREATE_VECTOR_APPROX only)",
+                    flags & ~(kShapFlags | TAHOE_CREATE_VECTOR_APPROX));
     // interaction values take phi from the TreeSHAP pass and the covers' zero fractions: no meaning without TAHOE_CREATE_CONTRIBS
     if ((flags & TAHOE_CREATE_VECTOR_INTERACTIONS) != 0 && (flags & TAHOE_CREATE_CONTRIBS) == 0)
         return fail(TAHOE_ERR_INVALID_ARG, "TAHOE_CREATE_VECTOR_INTERACTIONS needs TAHOE_CREATE_CONTRIBS (and covers) in the same call");
     const bool with_covers = (flags & TAHOE_CREATE_CONTRIBS) != 0;
     if (with_covers && !covers) return fail(TAHOE_ERR_INVALID_ARG, "TAHOE_CREATE_CONTRIBS needs covers (one per node)");
-    if (flags & kShapFlags)
-        if (const tahoe_status cs = contribs_validate_sparse(trees, nodes, covers, p, true, with_covers)) return cs;
+    // Saabas deltas (TAHOE_CREATE_VECTOR_APPROX) read the covers and no path: alone, the covers are checked and no length is
+    const bool approx = (flags & TAHOE_CREATE_VECTOR_APPROX) != 0;
+    if (approx && !covers) return fail(TAHOE_ERR_INVALID_ARG, "TAHOE_CREATE_VECTOR_APPROX needs covers (one per node)");
+    if (flags & kShapFlags) {
+        if (const tahoe_status cs = contribs_validate_sparse(trees, nodes, covers, p, true, with_covers || approx)) return cs;
+    } else if (approx) {
+        if (const tahoe_status cs = contribs_validate_sparse(trees, nodes, covers, p, false)) return cs;
+    }
 
     ForestPtr f;
     if (const tahoe_status s = open_handle(p, leaf_dim, f)) return s;
@@ -301,6 +305,7 @@ extern "C" tahoe_status tahoe_vector_forest_create_ex(tahoe_forest **out, const 
         return s;
     if ((flags & kShapFlags) && (s = vector_shap_build(f.get(), trees, nodes, leaf_values, with_covers ? covers : nullptr, flags)))
         return s;
+    if (approx && (s = vector_approx_build(f.get(), trees, nodes, leaf_values, covers))) return s;
     *out = f.release();
     return TAHOE_OK;
 }

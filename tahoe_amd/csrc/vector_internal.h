@@ -1,5 +1,6 @@
 // The device state of a vector-leaf handle (tahoe_vector_forest_create), shared by vector.hip (create, the walk kernels),
-// vector_shap.hip (TreeSHAP on such a handle), vector_iv.hip (interventional TreeSHAP) and vector_inter.hip (interaction values).
+// vector_shap.hip (TreeSHAP on such a handle), vector_iv.hip (interventional TreeSHAP), vector_inter.hip (interaction values) and
+// vector_approx.hip (Saabas contributions).
 // Internal: not part of the ABI.
 #pragma once
 #include <cstddef>
@@ -18,6 +19,9 @@ struct VNode {
     uint32_t pad;
 };
 static_assert(sizeof(VNode) == 16, "VNode must be 16 bytes");
+constexpr uint32_t kVFidMask = (1u << 30) - 1u;
+constexpr uint32_t kVDefLeft = 1u << 30;
+constexpr uint32_t kVIsLeaf = 1u << 31;
 
 // The TreeSHAP path tables of a handle created with TAHOE_CREATE_CONTRIBS and / or TAHOE_CREATE_INTERVENTIONAL (DESIGN.md
 // sections 26 and 27): one set of bins for the forest, laid out as tahoe_cstate's, except that a path's root element carries the
@@ -54,6 +58,22 @@ struct VectorShap {
     size_t inter_lds_bytes = 0;
 };
 
+// The tables and the launch shape of a handle created with TAHOE_CREATE_VECTOR_APPROX: the child deltas of
+// every output beside each other, the bias column, and what vector_approx_kernel<KB, SLAB> runs as -- fixed per handle by num_cols,
+// K, the device's LDS and the knobs
+struct VectorApprox {
+    float *dd = nullptr;      // [num_nodes][kp]: row i = the K deltas of node i as a child (a root's row and the padding are 0)
+    float *bias = nullptr;    // [K] the bias column of tahoe_forest_predict_contribs on this handle
+    float div = 1.0f;         // (float)num_trees with TAHOE_OUT_AVG, else 1.0f
+    int class_block = 1;      // KB: outputs that share one walk (1, 2, 4 or 8)
+    int kp = 1;               // floats per row of dd: K rounded up to a multiple of KB, so that a block's deltas are one aligned load
+    bool slab = false;        // accumulate in a lane-private LDS row (else in place in phi_dev)
+    int waves = 1;            // waves (64 rows each) per workgroup
+    int stride = 0;           // floats per slab row: KB (num_cols + 1) made odd
+    size_t lds_bytes = 0;     // per workgroup
+    bool grid_blocks = true;  // gridDim.y runs over the class blocks (else a workgroup loops over them)
+};
+
 }  // namespace tahoe
 
 struct tahoe_vstate {
@@ -61,6 +81,7 @@ struct tahoe_vstate {
     int32_t *roots = nullptr;
     float *leaves = nullptr;
     tahoe::VectorShap *shap = nullptr;  // non-null: created with TAHOE_CREATE_CONTRIBS and / or TAHOE_CREATE_INTERVENTIONAL
+    tahoe::VectorApprox *approx = nullptr;  // non-null: created with TAHOE_CREATE_VECTOR_APPROX
 };
 
 namespace tahoe {
@@ -79,5 +100,10 @@ tahoe_status vector_launch_contribs_spare(tahoe_forest *f, float *out_dev, const
 // vector_inter.hip: form, class block, tile rows and LDS bytes of vector_interactions_kernel on f (sh->inter_*), from num_cols, K
 // and the knobs, and the LDS limit of the instantiation the handle uses
 tahoe_status vector_inter_build(const tahoe_forest *f, VectorShap *sh);
+// vector_approx.hip: the tables of TAHOE_CREATE_VECTOR_APPROX from the caller's arrays, whose covers have passed
+// contribs_validate_sparse, and the form and LDS limit of the kernel the handle uses
+tahoe_status vector_approx_build(tahoe_forest *f, const int32_t *trees, const tahoe_sparse_node *nodes, const float *leaf_values,
+                                 const float *covers);
+void vector_approx_destroy(tahoe_forest *f);
 
 }  // namespace tahoe
