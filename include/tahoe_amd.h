@@ -259,7 +259,9 @@ tahoe_status tahoe_forest_predict_interactions(tahoe_forest *f, float *out_dev, 
  * dense, sparse and multi-class handles created with TAHOE_CREATE_CONTRIBS; it reads the path bins that flag builds.  The covers are
  * checked at create as for tahoe_forest_predict_contribs but this game does not use them.  A vector-leaf handle serves it with
  * TAHOE_CREATE_INTERVENTIONAL (tahoe_vector_forest_create_ex), which takes no covers; without that flag both calls below are
- * TAHOE_ERR_UNSUPPORTED on it, TAHOE_CREATE_CONTRIBS or not.
+ * TAHOE_ERR_UNSUPPORTED on it, TAHOE_CREATE_CONTRIBS or not.  An oblivious handle serves it with
+ * TAHOE_CREATE_OBLIVIOUS_INTERVENTIONAL (tahoe_oblivious_forest_create_ex), which takes no covers either; without that flag both
+ * calls are TAHOE_ERR_UNSUPPORTED on it, whatever other flag it carries.
  *
  * tahoe_forest_set_background: bg_dev is row-major bg_rows x num_cols float32 on the handle's device; the handle keeps what it
  * needs (per path bin and background row, the 64-bit ballot of the bin's lanes whose element the row follows: bins x bg_rows x
@@ -272,7 +274,13 @@ tahoe_status tahoe_forest_predict_interactions(tahoe_forest *f, float *out_dev, 
  * created without TAHOE_CREATE_CONTRIBS: TAHOE_ERR_UNSUPPORTED; an allocation that fails: TAHOE_ERR_NO_MEMORY.  On any refusal
  * the previous background is kept.  On a vector-leaf handle: the same contract with C = K and div = num_trees; the masks are
  * stored once for the forest (bins x bg_rows x 8 bytes, not K times as on the T x K-tree expansion), raw_k(r) are the bits of
- * tahoe_forest_predict_raw on that handle, and device_bytes grows by bins x bg_rows x 8 + (1024 + K) x 4. */
+ * tahoe_forest_predict_raw on that handle, and device_bytes grows by bins x bg_rows x 8 + (1024 + K) x 4.
+ * On an oblivious handle created with TAHOE_CREATE_OBLIVIOUS_INTERVENTIONAL: the same contract with C = K and div = num_trees,
+ * raw_k(r) the bits of tahoe_forest_predict_raw on that handle.  A background row enters a tree only through its leaf index there,
+ * so the handle keeps no row: per tree it keeps the occupied leaves -- R(r, t) exactly what tahoe_forest_predict_leaf_idx reports --
+ * in ascending order with their integer counts (the histogram is made on the host; the order of the background rows cannot
+ * affect it).  device_bytes grows by 8 x (occupied (tree, leaf) pairs; at most min(bg_rows, 2^depth) per tree) + 4 x (num_trees
+ * + 1) + 4 x K. */
 tahoe_status tahoe_forest_set_background(tahoe_forest *f, const float *bg_dev, size_t bg_rows, void *stream);
 /* phi_dev[rows][num_classes][num_cols + 1] <- phi_i(x) = (1 / B) sum_r phi_i(x, r), B = background rows, phi_i(x, r) the exact
  * Shapley value of v_r(S) = f(x_S, r_{N \ S}) summed over class c's trees c, c + C, ... and divided by (float)Tc with
@@ -295,7 +303,20 @@ tahoe_status tahoe_forest_set_background(tahoe_forest *f, const float *bg_dev, s
  * tahoe_vector_forest_create with the same background under any valid covers, bias column included (K == 1: the bits of the sparse
  * handle on the same trees).  The K outputs of a leaf share one pass over the background per (row, path bin); the result does not
  * depend on the batch, on how many outputs share a pass, on the strategy or on whether TAHOE_CREATE_CONTRIBS is also set.  The
- * same refusals in the same order, the missing flag first (text: "vector-leaf" and the call's name). */
+ * same refusals in the same order, the missing flag first (text: "vector-leaf" and the call's name).
+ * On an oblivious handle created with TAHOE_CREATE_OBLIVIOUS_INTERVENTIONAL: phi_dev[rows][K][num_cols + 1], bias last.  Per tree,
+ * with X the row's leaf index, the elements e = the tree's distinct features in order of first appearance from level 0 and
+ * mask_e their levels: per occupied background leaf {R, count}, diff = X ^ R, the players are U = {e : diff & mask_e != 0}, u =
+ * |U| (u == 0: no term); the submasks S of U are taken in descending numeric order of their bit mask over the elements, from U
+ * itself down to the empty set; the live leaf is j = R ^ (diff & OR_{e in S} mask_e), s = |S|, and each e in U, e ascending, takes
+ * the term w x (float)count x leaf[j][k], w = +(s - 1)! (u - s)! / u! for e in S and -s! (u - s - 1)! / u! otherwise (float64
+ * quotients rounded once to float32; the count enters as one multiplication).  Per (row, k, feature): one float32 sum from +0.0f
+ * over the trees in order, within a tree over its occupied leaves in ascending order, within one over the submasks in that order;
+ * then one division by (float)B, then by (float)num_trees with AVG.  A feature no tree uses gives +0.0f.  The bits do not depend
+ * on the batch, on the kernel form, on how many outputs share a pass, on the strategy (not used) or on the handle's other flags,
+ * and in the feature columns not on the order of the background rows.  No atomics; asynchronous, allocates nothing,
+ * graph-capturable after set_background.  The same refusals in the same order: the missing flag first (text: "oblivious" and the
+ * call's name), no background, then rows == 0: TAHOE_OK, NULL pointers, the size overflow. */
 tahoe_status tahoe_forest_predict_contribs_interventional(tahoe_forest *f, float *phi_dev, const float *data_dev, size_t rows,
                                                           void *stream);
 
@@ -459,21 +480,28 @@ typedef struct {
  * TILERING and QRING are TAHOE_ERR_UNSUPPORTED.
  * Out of scope, TAHOE_ERR_UNSUPPORTED with nothing launched and a text that says "oblivious": tahoe_forest_predict_csr,
  * _reserve_csr (and _get_csr_plan: form TAHOE_FORM_NONE), _predict_host, _set_stages, _predict_staged (_get_staged_strategy: 0),
- * _predict_contribs_interventional and _set_background; _predict_contribs, _predict_contribs_approx and _predict_interactions
- * unless the handle comes from tahoe_oblivious_forest_create_ex with that call's flag.  CatBoost's one-hot and CTR splits are not
+ * _predict_contribs, _predict_contribs_approx, _predict_interactions, and _set_background with
+ * _predict_contribs_interventional, unless the handle comes from tahoe_oblivious_forest_create_ex with that call's flag.  CatBoost's one-hot and CTR splits are not
  * represented. */
 tahoe_status tahoe_oblivious_forest_create(tahoe_forest **out, const int32_t *depths, const tahoe_oblivious_split *splits,
                                            const float *leaf_values, const tahoe_forest_params *params, int leaf_dim);
 /* SHAP interaction values on an oblivious handle: accepted by tahoe_oblivious_forest_create_ex alone (every other create:
  * TAHOE_ERR_INVALID_ARG), alone or with TAHOE_CREATE_CONTRIBS and / or TAHOE_CREATE_APPROX_CONTRIBS. */
 #define TAHOE_CREATE_INTERACTIONS 0x40u
+/* Interventional TreeSHAP on an oblivious handle (tahoe_forest_set_background, tahoe_forest_predict_contribs_interventional):
+ * accepted by tahoe_oblivious_forest_create_ex alone (every other create refuses it as an unknown flag; it is not
+ * TAHOE_CREATE_INTERVENTIONAL, 0x80, which stays an unknown flag on this create), alone -- it needs no covers -- or with any of the
+ * three flags above. */
+#define TAHOE_CREATE_OBLIVIOUS_INTERVENTIONAL 0x200u
 /* The same handle with explanations.  flags: a subset of TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS |
- * TAHOE_CREATE_INTERACTIONS, each serving its own call and no other; with flags == 0
+ * TAHOE_CREATE_INTERACTIONS | TAHOE_CREATE_OBLIVIOUS_INTERVENTIONAL, each serving its own call(s) and no other; with flags == 0
  * leaf_covers is ignored and the call is tahoe_oblivious_forest_create (which is this call with NULL, 0).  leaf_covers holds
  * sum_t 2^depths[t] floats, one per leaf in the order of the leaves: the training weight that reached the leaf (CatBoost's
- * leaf_weights).  Checks, before a device is touched and after those of tahoe_oblivious_forest_create: another flag bit, or a flag
- * with leaf_covers == NULL: TAHOE_ERR_INVALID_ARG; a cover that is negative, NaN or infinite: TAHOE_ERR_INVALID_FOREST naming the
- * tree and the leaf.
+ * leaf_weights).  Checks, before a device is touched and after those of tahoe_oblivious_forest_create: another flag bit, or one of
+ * the first three flags with leaf_covers == NULL: TAHOE_ERR_INVALID_ARG; with one of the first three flags a cover that is
+ * negative, NaN or infinite: TAHOE_ERR_INVALID_FOREST naming the tree and the leaf.  TAHOE_CREATE_OBLIVIOUS_INTERVENTIONAL alone
+ * reads no cover (leaf_covers may be NULL); a handle created without it is bit for bit and byte for byte what it was before that
+ * flag existed.
  * Covers of the implicit nodes: the float64 sum of the leaf covers below.  A node of positive cover mixes its children by
  * w_child / (w_l + w_r); a node of cover 0 mixes them 1/2 and 1/2 (the limit of adding one epsilon to every leaf cover).  Leaves
  * and whole subtrees of cover 0 are therefore accepted -- CatBoost models have them -- where TAHOE_CREATE_CONTRIBS on a dense or
@@ -500,7 +528,14 @@ tahoe_status tahoe_oblivious_forest_create(tahoe_forest **out, const int32_t *de
  * The calls allocate nothing and can be captured.  The tables count in device_bytes: 8 bytes per (leaf, distinct feature of its
  * tree) and 4 per leaf (TreeSHAP and the interaction values, which share them), 4 K bytes per implicit child (Saabas), 8 bytes per
  * split and per (tree, distinct feature) more for the interaction values.  A call whose flag the handle lacks stays
- * TAHOE_ERR_UNSUPPORTED as above. */
+ * TAHOE_ERR_UNSUPPORTED as above.
+ * TAHOE_CREATE_OBLIVIOUS_INTERVENTIONAL: tahoe_forest_set_background and tahoe_forest_predict_contribs_interventional are served as
+ * defined there.  At create it adds to device_bytes 2312 bytes (two 17 x 17 float32 weight tables) beside TAHOE_CREATE_CONTRIBS or
+ * TAHOE_CREATE_INTERACTIONS, whose splits and elements it shares; alone, on a forest with at least one split, 8 bytes per split
+ * + 4 per feature the forest uses + 8 per (tree, distinct feature) + 12 num_trees + 4 K + 20 (offsets, a bias column and the
+ * one-element placeholders of the tables it does not build) + 2312.  One kernel form (LDS or in place) serves all the handle's
+ * explanation calls; with this flag the weight tables count in the LDS the LDS form needs.  What a background adds is stated at
+ * tahoe_forest_set_background. */
 tahoe_status tahoe_oblivious_forest_create_ex(tahoe_forest **out, const int32_t *depths, const tahoe_oblivious_split *splits,
                                               const float *leaf_values, const float *leaf_covers,
                                               const tahoe_forest_params *params, int leaf_dim, unsigned flags);

@@ -41,6 +41,7 @@ CREATE_CAT_CONTRIBS = 0x20  # tahoe_sparse_forest_create_cat: the two flags abov
 CREATE_INTERACTIONS = 0x40  # tahoe_oblivious_forest_create_ex: SHAP interaction values (tahoe_forest_predict_interactions)
 CREATE_INTERVENTIONAL = 0x80  # tahoe_vector_forest_create_ex: interventional TreeSHAP (tahoe_forest_set_background), no covers needed
 CREATE_VECTOR_INTERACTIONS = 0x100  # tahoe_vector_forest_create_ex, with CREATE_CONTRIBS: tahoe_forest_predict_interactions
+CREATE_OBLIVIOUS_INTERVENTIONAL = 0x200  # tahoe_oblivious_forest_create_ex: interventional TreeSHAP (tahoe_forest_set_background), no covers needed
 CREATE_VECTOR_APPROX = 0x400  # tahoe_vector_forest_create_ex: Saabas contributions (tahoe_forest_predict_contribs_approx); needs covers
 STRATEGY_NAMES = {1: "direct", 2: "rowtile", 3: "tileblock", 4: "tilering", 5: "qring"}
 STATUS_NAMES = {
@@ -603,7 +604,7 @@ class Forest:
     def set_background(self, bg, stream=None) -> None:
         """Background data set of interventional TreeSHAP (tahoe_forest_set_background): float32 [B, num_cols], contiguous, on
         the handle's device; None clears it.  Synchronous; the handle keeps what it needs, so `bg` may be freed afterwards.
-        Needs contribs=True (a VectorForest: interventional=True)."""
+        Needs contribs=True (a VectorForest or an ObliviousForest: interventional=True)."""
         if bg is None:
             _check(lib.tahoe_forest_set_background(self._h, None, 0, None), "tahoe_forest_set_background")
             return
@@ -612,8 +613,9 @@ class Forest:
 
     def predict_contribs_interventional(self, data, out=None, stream=None):
         """Interventional TreeSHAP against the background of set_background (tahoe_forest_predict_contribs_interventional):
-        [rows, num_cols + 1] float32, or [rows, num_classes, num_cols + 1] on a multi-class handle; the bias is the last
-        column.  Needs contribs=True (a VectorForest: interventional=True) and a background."""
+        [rows, num_cols + 1] float32, or [rows, num_classes, num_cols + 1] on a multi-class handle ([rows, K, num_cols + 1] on a
+        VectorForest or an ObliviousForest with leaf_dim K > 1); the bias is the last column.  Needs contribs=True (a VectorForest
+        or an ObliviousForest: interventional=True) and a background."""
         return self._shap_out("tahoe_forest_predict_contribs_interventional", data, 1, out, stream)
 
     def set_strategy(self, strategy: int) -> None:
@@ -803,11 +805,12 @@ class ObliviousForest(Forest):
     shapes of a multi-class handle ([rows, leaf_dim]); AVG divides by the number of trees.  contribs=True / approx_contribs=True /
     interactions=True (tahoe_oblivious_forest_create_ex) serve predict_contribs / predict_contribs_approx / predict_interactions,
     each its own call only, and need leaf_covers: sum(2 ** depths) floats, the training weight of every leaf (CatBoost's
-    leaf_weights); zeros are allowed."""
+    leaf_weights); zeros are allowed.  interventional=True (TAHOE_CREATE_OBLIVIOUS_INTERVENTIONAL) serves set_background and
+    predict_contribs_interventional; alone it needs no leaf_covers."""
 
     def __init__(self, depths, fids, thresholds, def_left, leaf_values, num_cols: int, leaf_dim: int = 1, missing: float = 0.0,
                  output: int = OUT_RAW, threshold: float = 0.5, global_bias: float = 0.0, leaf_covers=None, contribs: bool = False,
-                 approx_contribs: bool = False, interactions: bool = False):
+                 approx_contribs: bool = False, interactions: bool = False, interventional: bool = False):
         depths = np.ascontiguousarray(depths, dtype=np.int32).reshape(-1)
         fids = np.asarray(fids, dtype=np.int64).reshape(-1)
         nsplits = int(depths.astype(np.int64).sum())
@@ -828,15 +831,19 @@ class ObliviousForest(Forest):
         self._h = _vp()
         flags = ((CREATE_CONTRIBS if contribs else 0) | (CREATE_APPROX_CONTRIBS if approx_contribs else 0)
                  | (CREATE_INTERACTIONS if interactions else 0))
-        if flags:
-            if leaf_covers is None:
-                raise ValueError("contribs / approx_contribs / interactions need leaf_covers")
-            covers = np.ascontiguousarray(leaf_covers, dtype=np.float32).reshape(-1)
-            if covers.size * leaf_dim != leaves.size:
-                raise ValueError("leaf_covers.size != sum(2 ** depths)")
-            cv = covers if covers.size else np.zeros(1, np.float32)
+        if flags or interventional:
+            cv = None
+            if flags:
+                if leaf_covers is None:
+                    raise ValueError("contribs / approx_contribs / interactions need leaf_covers")
+                covers = np.ascontiguousarray(leaf_covers, dtype=np.float32).reshape(-1)
+                if covers.size * leaf_dim != leaves.size:
+                    raise ValueError("leaf_covers.size != sum(2 ** depths)")
+                cv = covers if covers.size else np.zeros(1, np.float32)
+            flags |= CREATE_OBLIVIOUS_INTERVENTIONAL if interventional else 0
             _check(lib.tahoe_oblivious_forest_create_ex(C.byref(self._h), dp.ctypes.data, splits.ctypes.data if nsplits else None,
-                                                        lv.ctypes.data, cv.ctypes.data, C.byref(self.params), leaf_dim, flags),
+                                                        lv.ctypes.data, None if cv is None else cv.ctypes.data, C.byref(self.params),
+                                                        leaf_dim, flags),
                    "tahoe_oblivious_forest_create_ex")
         else:
             _check(lib.tahoe_oblivious_forest_create(C.byref(self._h), dp.ctypes.data, splits.ctypes.data if nsplits else None,

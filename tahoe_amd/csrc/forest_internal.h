@@ -531,6 +531,12 @@ tahoe_status oblivious_predict_shap(tahoe_forest *f, unsigned flag, float *phi_d
                                     hipStream_t stream, const char *fn);
 tahoe_status oblivious_predict_interactions(tahoe_forest *f, float *out_dev, const float *data_dev, size_t rows, hipStream_t stream,
                                             const char *fn);
+// ... its interventional TreeSHAP (TAHOE_CREATE_OBLIVIOUS_INTERVENTIONAL, which oblivious_serves answers too): the bodies of
+// tahoe_forest_set_background and tahoe_forest_predict_contribs_interventional on such a handle, after the refusals of a NULL handle,
+// a missing flag and (set_background) a NULL background
+tahoe_status oblivious_set_background(tahoe_forest *f, const float *bg_dev, size_t bg_rows, hipStream_t stream);
+tahoe_status oblivious_predict_interventional(tahoe_forest *f, float *phi_dev, const float *data_dev, size_t rows, hipStream_t stream,
+                                              const char *fn);
 // The refusal of the entry points an oblivious handle does not serve (fn: the entry point's name); TAHOE_OK on every other handle
 inline tahoe_status refuse_oblivious(const tahoe_forest *f, const char *fn)
 {
@@ -577,10 +583,12 @@ inline tahoe_status need_path_tables(const tahoe_forest *f, const char *fn)
                                            "tables (tahoe_sparse_forest_create_ex)", fn);
     return fail(TAHOE_ERR_UNSUPPORTED, "%s: the handle was created without TAHOE_CREATE_CONTRIBS and has no path tables", fn);
 }
-// ... of the two interventional entry points: the path tables, or a vector-leaf handle's bins of TAHOE_CREATE_INTERVENTIONAL
+// ... of the two interventional entry points: the path tables, a vector-leaf handle's bins of TAHOE_CREATE_INTERVENTIONAL, or an
+// oblivious handle's tables of TAHOE_CREATE_OBLIVIOUS_INTERVENTIONAL
 inline tahoe_status need_background_tables(const tahoe_forest *f, const char *fn)
 {
-    return vector_serves_interventional(f) ? TAHOE_OK : need_path_tables(f, fn);
+    if (vector_serves_interventional(f) || oblivious_serves(f, TAHOE_CREATE_OBLIVIOUS_INTERVENTIONAL)) return TAHOE_OK;
+    return need_path_tables(f, fn);
 }
 // TAHOE_ERR_INVALID_ARG unless the output of a SHAP entry point, rows x classes x (num_cols + 1)^k floats, fits in size_t
 inline tahoe_status check_shap_out(const tahoe_forest *f, size_t rows, int k, const char *fn)

@@ -250,6 +250,7 @@ extern "C" tahoe_status tahoe_forest_set_background(tahoe_forest *f, const float
     if (!f) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_set_background: null forest");
     if (tahoe_status st = need_background_tables(f, "tahoe_forest_set_background")) return st;
     if (bg_rows > 0 && !bg_dev) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_set_background: null background");
+    if (f->ob) return oblivious_set_background(f, bg_dev, bg_rows, (hipStream_t)stream);  // no path bins: a histogram of leaf indices
     // one body for both kinds of handle: a vector-leaf handle has num_classes = K, class_trees = num_trees and one set of bins
     const IvBins pb = iv_bins(f);
     const size_t F = (size_t)f->p.num_cols, C = (size_t)f->num_classes, bins = pb.bins;
@@ -344,6 +345,9 @@ extern "C" tahoe_status tahoe_forest_predict_contribs_interventional(tahoe_fores
 {
     if (!f) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_contribs_interventional: null forest");
     if (tahoe_status st = need_background_tables(f, "tahoe_forest_predict_contribs_interventional")) return st;
+    if (f->ob)
+        return oblivious_predict_interventional(f, phi_dev, data_dev, rows, (hipStream_t)stream,
+                                                "tahoe_forest_predict_contribs_interventional");
     if (!f->iv)
         return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_contribs_interventional: no background set "
                                            "(tahoe_forest_set_background)");

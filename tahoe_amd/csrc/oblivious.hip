@@ -239,12 +239,15 @@ extern "C" tahoe_status tahoe_oblivious_forest_create_ex(tahoe_forest **out, con
     }
 
     // ... and the checks of the explanation flags, after those every create makes
-    if (flags & ~(unsigned)(TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS | TAHOE_CREATE_INTERACTIONS))
+    if (flags & ~(unsigned)(TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS | TAHOE_CREATE_INTERACTIONS |
+                            TAHOE_CREATE_OBLIVIOUS_INTERVENTIONAL))
         return fail(TAHOE_ERR_INVALID_ARG, "tahoe_oblivious_forest_create_ex: flags 0x%x: only TAHOE_CREATE_CONTRIBS, "
-                                           "TAHOE_CREATE_APPROX_CONTRIBS and TAHOE_CREATE_INTERACTIONS are served", flags);
-    if (flags && !leaf_covers)
+                                           "TAHOE_CREATE_APPROX_CONTRIBS, TAHOE_CREATE_INTERACTIONS and "
+                                           "TAHOE_CREATE_OBLIVIOUS_INTERVENTIONAL are served", flags);
+    const unsigned cover_flags = flags & ~(unsigned)TAHOE_CREATE_OBLIVIOUS_INTERVENTIONAL;  // (the interventional game reads no cover)
+    if (cover_flags && !leaf_covers)
         return fail(TAHOE_ERR_INVALID_ARG, "tahoe_oblivious_forest_create_ex: leaf_covers is null, and the flags need the covers");
-    if (flags)
+    if (cover_flags)
         if (const tahoe_status s = oblivious_shap_validate(depths, T, leaf_covers)) return s;
 
     ForestPtr f;

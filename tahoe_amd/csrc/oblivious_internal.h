@@ -30,8 +30,8 @@ struct ObliviousSource {
 
 // TAHOE_ERR_INVALID_FOREST unless every leaf cover is finite and >= 0 (no device touched)
 tahoe_status oblivious_shap_validate(const int32_t *depths, int num_trees, const float *leaf_covers);
-// The tables `flags` (TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS | TAHOE_CREATE_INTERACTIONS) ask for, on the handle's
-// device
+// The tables `flags` (TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS | TAHOE_CREATE_INTERACTIONS |
+// TAHOE_CREATE_OBLIVIOUS_INTERVENTIONAL) ask for, on the handle's device; src.leaf_covers is read only with one of the first three
 tahoe_status oblivious_shap_build(tahoe_forest *f, const ObliviousSource &src, unsigned flags);
 void oblivious_shap_destroy(tahoe_forest *f);
 

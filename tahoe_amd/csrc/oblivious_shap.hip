@@ -44,6 +44,20 @@
 //   end     per lane and class, over the used columns u[0] < u[1] < ...: M[a][b] = M[b][a] = M[a][b] / div for a < b; then per
 //           used column a: S = +0.0f + M[a][b] for b != a ascending, M[a][a] = M[F][a] / div - S; then row F becomes +0.0f and
 //           M[F][F] = bias[k].  Everything else keeps the +0.0f of the begin.
+//
+// Interventional TreeSHAP (TAHOE_CREATE_OBLIVIOUS_INTERVENTIONAL): oblivious_iv_kernel, lane = row, the
+// accumulators and the begin / end of oblivious_shap_kernel.  A background row r enters tree t only through its leaf index R, so
+// tahoe_forest_set_background keeps per tree the occupied leaves, ascending, with their integer counts (occ, occ_off) -- not the rows.
+//   tree    of m distinct features (m == 0: nothing), X the row's leaf index; per occupied leaf {R, count}, in order:
+//             diff = X ^ R;  dU = the elements e with diff & mask_e != 0 (the players), u = popcount(dU);  u == 0: no term
+//             cf = (float)count
+//             per submask sub of dU, in descending numeric order from dU itself down to 0 (sub = (sub - 1) & dU), s = popcount(sub):
+//               j = R ^ (diff & OR_{e in sub} mask_e)            the live leaf: x's bits on the levels of sub, r's elsewhere
+//               per e in dU, e ascending:  w = e in sub ? W+[u][s] : -W-[u][s]
+//                 per class: sum = sum + (w * cf) * leaf[j][k]
+//           W+[u][s] = (s - 1)! (u - s)! / u!, W-[u][s] = s! (u - s - 1)! / u!: float64 quotients rounded once, 17 x 17 each, in LDS.
+//           The lanes of a wave differ in dU; the submask loop runs until the wave's last lane is through.
+//   end     every used column / (float)B, then ob_shap_end: / div and the bias column of the background.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -76,6 +90,17 @@ struct ObShapView {
     int F, K, T, U, S;  // columns, leaf dimension, trees, used features, floats per slab row (odd)
 };
 
+constexpr int kObIvW = 17;                        // u and s run over 0 .. 16
+constexpr int kObIvTable = 2 * kObIvW * kObIvW;   // floats of W+ | W-
+
+// What oblivious_iv_kernel reads beside the view: the background of tahoe_forest_set_background and the weight tables
+struct ObIvView {
+    const uint2 *occ;         // {leaf, count} of every occupied (tree, leaf), tree-major, leaves ascending
+    const int32_t *occ_off;   // [T + 1]
+    const float *wtab;        // [kObIvTable]
+    float fB;                 // (float)background rows
+};
+
 }  // namespace tahoe
 
 struct tahoe_oshap {
@@ -95,6 +120,16 @@ struct tahoe_oshap {
     size_t lds_bytes = 0;
     tahoe::ObShapView view{};
     tahoe::ObShapView inter_view{};  // view with splits_col and elems_col
+    // TAHOE_CREATE_OBLIVIOUS_INTERVENTIONAL: the weight tables (create); the background (tahoe_forest_set_background): occupied
+    // leaves, per-tree offsets, bias column
+    bool iv = false;
+    size_t iv_lds_bytes = 0;  // oblivious_iv_kernel: lds_bytes, then the weight tables
+    float *wtab = nullptr;
+    uint2 *occ = nullptr;
+    int32_t *occ_off = nullptr;
+    float *iv_bias = nullptr;
+    size_t bg_rows = 0;   // 0: no background
+    size_t bg_bytes = 0;  // device bytes of the three background buffers (counted in tahoe_forest::device_bytes)
 };
 
 namespace tahoe {
@@ -480,6 +515,105 @@ __global__ void __launch_bounds__(64) oblivious_inter_kernel(const ObShapView vi
     }
 }
 
+// Interventional TreeSHAP, one tree of M distinct features (the file's header: "tree").  a, id and mask as in ob_shap_tree; W is
+// the LDS copy of the weight tables.  The occupancy entries sit at wave-uniform addresses; the leaf gather is per lane.
+template <int M, int KB, bool INPLACE>
+__device__ __forceinline__ void ob_iv_tree(const ObShapRows<KB, INPLACE> &r, const uint2 *__restrict__ el,
+                                           const uint2 *__restrict__ occ, int nocc, const float *__restrict__ lv, uint32_t X, int K,
+                                           const float *W)
+{
+    uint32_t id[M], mask[M];
+    float a[M][KB];
+#pragma unroll
+    for (int e = 0; e < M; ++e) {
+        id[e] = el[e].x;
+        mask[e] = el[e].y;
+#pragma unroll
+        for (int k = 0; k < KB; ++k) a[e][k] = (KB == 1 || k < r.kb) ? r.load(k, id[e]) : 0.0f;
+    }
+    for (int q = 0; q < nocc; ++q) {
+        const uint2 oc = occ[q];
+        const uint32_t R = oc.x;
+        const float cf = (float)oc.y;
+        const uint32_t diff = X ^ R;
+        uint32_t dU = 0u;
+#pragma unroll
+        for (int e = 0; e < M; ++e) dU |= (diff & mask[e]) != 0u ? 1u << e : 0u;
+        const int u = __popc(dU);
+        uint32_t sub = dU;
+        bool act = dU != 0u;
+        while (__ballot(act) != 0ull) {
+            const int s = __popc(sub);
+            uint32_t lm = 0u;
+#pragma unroll
+            for (int e = 0; e < M; ++e) lm |= (sub >> e & 1u) != 0u ? mask[e] : 0u;
+            const uint32_t j = R ^ (diff & lm);  // < 2^D: R, diff and lm are
+            const float wp = W[u * kObIvW + s] * cf;
+            const float wm = -(W[kObIvW * kObIvW + u * kObIvW + s] * cf);
+            const float *lj = lv + (size_t)j * (size_t)K;
+            float leaf[KB];
+#pragma unroll
+            for (int k = 0; k < KB; ++k) leaf[k] = (KB == 1 || k < r.kb) ? lj[k] : 0.0f;
+#pragma unroll
+            for (int e = 0; e < M; ++e) {
+                const float w = (sub >> e & 1u) != 0u ? wp : wm;
+                const bool on = act && (dU >> e & 1u) != 0u;
+#pragma unroll
+                for (int k = 0; k < KB; ++k) {
+                    const float sum = a[e][k] + w * leaf[k];
+                    a[e][k] = on ? sum : a[e][k];
+                }
+            }
+            act = act && sub != 0u;
+            sub = (sub - 1u) & dU;
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < M; ++e)
+#pragma unroll
+        for (int k = 0; k < KB; ++k)
+            if (KB == 1 || k < r.kb) r.store(k, id[e], a[e][k]);
+}
+
+// Interventional TreeSHAP: grid (row tiles, class blocks), one wave per workgroup.  Dynamic LDS: (not INPLACE) [U][64] tile |
+// [64][S] slab, then [kObIvTable] weights.  v.bias is the bias column of the background.
+template <int KB, bool INPLACE>
+__global__ void __launch_bounds__(64) oblivious_iv_kernel(const ObShapView v, const ObIvView b, float *__restrict__ phi,
+                                                          const float *__restrict__ data, size_t rows)
+{
+    extern __shared__ __attribute__((aligned(16))) float ob_shap_smem[];
+    float *W = ob_shap_smem + (INPLACE ? 0 : (v.U + v.S) * 64);
+    for (int i = (int)threadIdx.x; i < kObIvTable; i += 64) W[i] = b.wtab[i];
+    const ObShapRows<KB, INPLACE> r = ob_shap_begin<KB, INPLACE>(v, phi, data, rows, ob_shap_smem);  // (its barrier)
+    for (int t = 0; t < v.T; ++t) {
+        const int e0 = v.elem_off[t];
+        const int m = v.elem_off[t + 1] - e0;  // wave-uniform, as everything read below but the leaves
+        if (m == 0) continue;                  // a single leaf: all of it is bias
+        const uint32_t idx = ob_shap_leaf_index(v, r, t, [](int, uint32_t, uint32_t) {});
+        const uint2 *el = v.elems + e0;
+        const int o0 = b.occ_off[t];
+        const int nocc = b.occ_off[t + 1] - o0;
+        const uint2 *oc = b.occ + o0;
+        const float *lv = v.leaves + (size_t)v.leaf_off[t] * (size_t)v.K + r.k0;
+        switch (m) {
+#define TAHOE_OB_IV_CASE(M) \
+    case M: ob_iv_tree<M, KB, INPLACE>(r, el, oc, nocc, lv, idx, v.K, W); break;
+            TAHOE_OB_IV_CASE(1) TAHOE_OB_IV_CASE(2) TAHOE_OB_IV_CASE(3) TAHOE_OB_IV_CASE(4)
+            TAHOE_OB_IV_CASE(5) TAHOE_OB_IV_CASE(6) TAHOE_OB_IV_CASE(7) TAHOE_OB_IV_CASE(8)
+            TAHOE_OB_IV_CASE(9) TAHOE_OB_IV_CASE(10) TAHOE_OB_IV_CASE(11) TAHOE_OB_IV_CASE(12)
+            TAHOE_OB_IV_CASE(13) TAHOE_OB_IV_CASE(14) TAHOE_OB_IV_CASE(15) TAHOE_OB_IV_CASE(16)
+#undef TAHOE_OB_IV_CASE
+        default: break;
+        }
+    }
+    // the mean over the background: the lane's own sums of the used columns, before ob_shap_end's division by div
+    for (int c = 0; c < v.U; ++c) {
+        const uint32_t id = INPLACE ? (uint32_t)v.used[c] : (uint32_t)c;
+        for (int k = 0; k < r.kb; ++k) r.store(k, id, r.load(k, id) / b.fB);
+    }
+    ob_shap_end<KB, INPLACE>(v, r, phi);
+}
+
 tahoe_status oblivious_shap_validate(const int32_t *depths, int num_trees, const float *leaf_covers)
 {
     size_t at = 0;
@@ -524,6 +658,23 @@ struct ObHeap {
     }
 };
 
+// The distinct features of a tree's D levels in order of first appearance from level 0, with their level masks; returns their number
+int tree_elements(const InnerNode *ts, int D, uint32_t *fid, uint32_t *mask)
+{
+    int m = 0;
+    for (int l = 0; l < D; ++l) {
+        const uint32_t fl = ts[l].meta & kMetaFidMask;
+        int e = 0;
+        while (e < m && fid[e] != fl) ++e;
+        if (e == m) {
+            fid[m] = fl;
+            mask[m++] = 0u;
+        }
+        mask[e] |= 1u << l;
+    }
+    return m;
+}
+
 uint32_t bit_reverse(uint32_t p, int d)
 {
     uint32_t r = 0;
@@ -542,7 +693,9 @@ tahoe_status oblivious_shap_build(tahoe_forest *f, const ObliviousSource &src, u
     sh->contribs = (flags & TAHOE_CREATE_CONTRIBS) != 0;
     sh->approx = (flags & TAHOE_CREATE_APPROX_CONTRIBS) != 0;
     sh->inter = (flags & TAHOE_CREATE_INTERACTIONS) != 0;
+    sh->iv = (flags & TAHOE_CREATE_OBLIVIOUS_INTERVENTIONAL) != 0;
     const bool paths = sh->contribs || sh->inter;  // elems, zz and zmask serve both
+    const bool cover_tables = sh->contribs || sh->inter || sh->approx;  // (src.leaf_covers may be null without them)
     const int T = f->p.num_trees, K = f->num_classes, F = f->p.num_cols;
     const std::vector<InnerNode> &splits = *src.h_splits;
     const std::vector<int32_t> &split_off = *src.h_split_off;
@@ -557,7 +710,9 @@ tahoe_status oblivious_shap_build(tahoe_forest *f, const ObliviousSource &src, u
     const int U = (int)used.size();
     const int S = (std::min(K, kObShapClasses) * U) | 1;
     sh->lds_bytes = ((size_t)U + (size_t)S) * 64 * sizeof(float);
-    sh->inplace = sh->lds_bytes > (size_t)f->lds_limit || f->knobs.oblivious_shap_inplace;  // TAHOE_OBLIVIOUS_SHAP_INPLACE
+    // One form per handle (the ids of splits and elems follow it): with the interventional flag its weight tables must fit as well
+    const size_t iv_table_bytes = sh->iv ? kObIvTable * sizeof(float) : 0;
+    sh->inplace = sh->lds_bytes + iv_table_bytes > (size_t)f->lds_limit || f->knobs.oblivious_shap_inplace;  // TAHOE_OBLIVIOUS_SHAP_INPLACE
     if (sh->inplace) sh->lds_bytes = 0;
     auto id_of = [&](uint32_t fid) {
         return sh->inplace ? fid : (uint32_t)(std::lower_bound(used.begin(), used.end(), (int32_t)fid) - used.begin());
@@ -582,6 +737,13 @@ tahoe_status oblivious_shap_build(tahoe_forest *f, const ObliviousSource &src, u
         const int D = src.depths[t];
         const size_t nleaf = (size_t)1 << D, lo = (size_t)leaf_off[(size_t)t];
         const InnerNode *ts = splits.data() + split_off[(size_t)t];
+        if (!cover_tables) {  // TAHOE_CREATE_OBLIVIOUS_INTERVENTIONAL alone: the elements, and nothing that reads a cover
+            uint32_t fid[kObMaxDepth], mask[kObMaxDepth];
+            const int m = tree_elements(ts, D, fid, mask);
+            for (int e = 0; e < m; ++e) h_elems.push_back(make_uint2(id_of(fid[e]), mask[e]));
+            h_elem_off[(size_t)t + 1] = (int32_t)h_elems.size();
+            continue;
+        }
         heap.build(D, src.leaf_covers + lo);
         // E_t[k]: the leaves in heap order left to right (the leaf at heap position h is leaf bit_reverse(h)), each times the
         // product of its path's ratios multiplied root first -- tree_expect's sum on the heap expansion, operation for operation
@@ -619,20 +781,14 @@ tahoe_status oblivious_shap_build(tahoe_forest *f, const ObliviousSource &src, u
                 }
             }
         }
-        if (paths) {
+        if (paths || sh->iv) {
             uint32_t fid[kObMaxDepth], mask[kObMaxDepth];
-            int m = 0;
-            for (int l = 0; l < D; ++l) {
-                const uint32_t fl = ts[l].meta & kMetaFidMask;
-                int e = 0;
-                while (e < m && fid[e] != fl) ++e;
-                if (e == m) {
-                    fid[m] = fl;
-                    mask[m++] = 0u;
-                }
-                mask[e] |= 1u << l;
-            }
+            const int m = tree_elements(ts, D, fid, mask);
             for (int e = 0; e < m; ++e) h_elems.push_back(make_uint2(id_of(fid[e]), mask[e]));
+            if (!paths) {
+                h_elem_off[(size_t)t + 1] = (int32_t)h_elems.size();
+                continue;
+            }
             if (sh->inter)
                 for (int e = 0; e < m; ++e) h_elems_col.push_back(make_uint2(fid[e], mask[e]));
             h_zz_off[(size_t)t] = (int64_t)h_zz.size();
@@ -676,6 +832,27 @@ tahoe_status oblivious_shap_build(tahoe_forest *f, const ObliviousSource &src, u
     sh->inter_view = sh->view;
     sh->inter_view.splits = sh->splits_col;
     sh->inter_view.elems = sh->elems_col;
+    if (sh->iv) {
+        // W+[u][s] = (s - 1)! (u - s)! / u! = 1 / (s C(u, s)) for 1 <= s <= u, W-[u][s] = s! (u - s - 1)! / u! = 1 / ((u - s) C(u, s))
+        // for 0 <= s < u; C(u, s) is exact in float64 (<= C(16, 8)); 0 elsewhere
+        std::vector<float> h_w((size_t)kObIvTable, 0.0f);
+        for (int u = 1; u < kObIvW; ++u) {
+            double binom = 1.0;  // C(u, s)
+            for (int s = 0; s <= u; ++s) {
+                if (s > 0) binom = binom * (double)(u - s + 1) / (double)s;
+                if (s >= 1) h_w[(size_t)(u * kObIvW + s)] = (float)(1.0 / ((double)s * binom));
+                if (s < u) h_w[(size_t)(kObIvW * kObIvW + u * kObIvW + s)] = (float)(1.0 / ((double)(u - s) * binom));
+            }
+        }
+        if ((s = hip_status(upload(&sh->wtab, h_w, &f->device_bytes), "upload(interventional weights)"))) return s;
+        sh->iv_lds_bytes = sh->lds_bytes + kObIvTable * sizeof(float);  // the tile and slab of the handle's form, then the tables
+        if (!sh->inplace) {
+            hipError_t e = hipSuccess;
+            if ((e = allow_max_lds(reinterpret_cast<const void *>(&oblivious_iv_kernel<1, false>), f->lds_limit)) != hipSuccess ||
+                (e = allow_max_lds(reinterpret_cast<const void *>(&oblivious_iv_kernel<kObShapClasses, false>), f->lds_limit)) != hipSuccess)
+                return hip_status(e, "hipFuncSetAttribute(oblivious_iv)");
+        }
+    }
     if (!sh->inplace) {  // the LDS forms may need more than the default 64 KiB
         hipError_t e = hipSuccess;
         if ((e = allow_max_lds(reinterpret_cast<const void *>(&oblivious_shap_kernel<1, false>), f->lds_limit)) != hipSuccess ||
@@ -692,7 +869,8 @@ void oblivious_shap_destroy(tahoe_forest *f)
     tahoe_oshap *sh = f->ob ? f->ob->shap : nullptr;
     if (!sh) return;
     for (void *p : {(void *)sh->splits, (void *)sh->used, (void *)sh->elems, (void *)sh->elem_off, (void *)sh->zz, (void *)sh->zz_off,
-                    (void *)sh->zmask, (void *)sh->delta, (void *)sh->bias, (void *)sh->splits_col, (void *)sh->elems_col})
+                    (void *)sh->zmask, (void *)sh->delta, (void *)sh->bias, (void *)sh->splits_col, (void *)sh->elems_col,
+                    (void *)sh->wtab, (void *)sh->occ, (void *)sh->occ_off, (void *)sh->iv_bias})
         if (p) (void)hipFree(p);
     delete sh;
     f->ob->shap = nullptr;
@@ -702,6 +880,7 @@ bool oblivious_serves(const tahoe_forest *f, unsigned flag)
 {
     const tahoe_oshap *sh = f->ob ? f->ob->shap : nullptr;
     if (!sh) return false;
+    if (flag == TAHOE_CREATE_OBLIVIOUS_INTERVENTIONAL) return sh->iv;
     return flag == TAHOE_CREATE_CONTRIBS ? sh->contribs : flag == TAHOE_CREATE_INTERACTIONS ? sh->inter : sh->approx;
 }
 
@@ -746,6 +925,141 @@ tahoe_status oblivious_predict_interactions(tahoe_forest *f, float *out_dev, con
     const dim3 grid((unsigned)((rows + 63) / 64), (unsigned)((K + kObShapClasses - 1) / kObShapClasses));
     if (K == 1) hipLaunchKernelGGL((oblivious_inter_kernel<1>), grid, dim3(64), 0, stream, sh->inter_view, out_dev, data_dev, rows);
     else hipLaunchKernelGGL((oblivious_inter_kernel<kObShapClasses>), grid, dim3(64), 0, stream, sh->inter_view, out_dev, data_dev, rows);
+    TAHOE_HIP_TRY(hipGetLastError());
+    return TAHOE_OK;
+}
+
+namespace {
+
+void ob_background_free(tahoe_forest *f, tahoe_oshap *sh)
+{
+    for (void *p : {(void *)sh->occ, (void *)sh->occ_off, (void *)sh->iv_bias})
+        if (p) (void)hipFree(p);
+    sh->occ = nullptr;
+    sh->occ_off = nullptr;
+    sh->iv_bias = nullptr;
+    f->device_bytes -= sh->bg_bytes;
+    sh->bg_rows = sh->bg_bytes = 0;
+}
+
+}  // namespace
+
+// tahoe_forest_set_background on a handle with TAHOE_CREATE_OBLIVIOUS_INTERVENTIONAL, after the refusals of a NULL handle, a missing
+// flag and a NULL background.  The old background stays until the new one is complete.
+tahoe_status oblivious_set_background(tahoe_forest *f, const float *bg_dev, size_t bg_rows, hipStream_t stream)
+{
+    tahoe_oshap *sh = f->ob->shap;
+    const size_t F = (size_t)f->p.num_cols, K = (size_t)f->num_classes, T = (size_t)f->p.num_trees;
+    if (F > 0 && bg_rows > SIZE_MAX / sizeof(float) / F)
+        return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_set_background: rows x num_cols floats overflow size_t (rows %zu)", bg_rows);
+    if (bg_rows > (size_t)INT32_MAX)
+        return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_set_background: %zu background rows (at most 2^31 - 1)", bg_rows);
+    DeviceGuard on_device(f->device);
+    if (bg_rows == 0) {
+        ob_background_free(f, sh);
+        return TAHOE_OK;
+    }
+    if (bg_rows > SIZE_MAX / sizeof(uint32_t) / std::max<size_t>(T, K))
+        return fail(TAHOE_ERR_NO_MEMORY, "tahoe_forest_set_background: %zu rows x %zu trees of leaf indices overflow size_t", bg_rows, T);
+    uint32_t *leaf = nullptr;
+    float *sums = nullptr;
+    uint2 *occ = nullptr;
+    int32_t *occ_off = nullptr;
+    float *bias = nullptr;
+    auto bail = [&](tahoe_status st) {
+        for (void *p : {(void *)leaf, (void *)sums, (void *)occ, (void *)occ_off, (void *)bias})
+            if (p) (void)hipFree(p);
+        (void)hipGetLastError();  // a failed allocation is not the caller's next error
+        return st;
+    };
+    if (hipMalloc(reinterpret_cast<void **>(&leaf), std::max<size_t>(bg_rows * T, 1) * sizeof(uint32_t)) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void **>(&sums), bg_rows * K * sizeof(float)) != hipSuccess)
+        return bail(fail(TAHOE_ERR_NO_MEMORY, "tahoe_forest_set_background: the leaf indices of %zu background rows x %zu trees do not "
+                                              "fit on the device; the previous background is kept", bg_rows, T));
+    // R(r, t): tahoe_forest_predict_leaf_idx's words; raw_k(r): tahoe_forest_predict_raw's bits.  DIRECT serves every shape and
+    // allocates nothing; the caller's strategy setting is restored.
+    const int saved = f->strategy;
+    f->strategy = TAHOE_STRATEGY_DIRECT;
+    tahoe_status st = tahoe_forest_predict_leaf_idx(f, leaf, nullptr, bg_dev, bg_rows, stream);
+    if (st == TAHOE_OK) st = tahoe_forest_predict_raw(f, sums, bg_dev, bg_rows, stream);
+    f->strategy = saved;
+    if (st != TAHOE_OK) return bail(st);
+    std::vector<uint32_t> h_leaf(bg_rows * T);
+    std::vector<float> raw(bg_rows * K);
+    hipError_t e = hipMemcpyAsync(h_leaf.data(), leaf, h_leaf.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(raw.data(), sums, raw.size() * sizeof(float), hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return bail(fail(TAHOE_ERR_HIP, "tahoe_forest_set_background: %s", hipGetErrorString(e)));
+
+    // per tree the occupied leaves, ascending, with their counts
+    std::vector<uint2> h_occ;
+    std::vector<int32_t> h_off(T + 1, 0);
+    std::vector<uint32_t> col(bg_rows);
+    for (size_t t = 0; t < T; ++t) {
+        for (size_t r = 0; r < bg_rows; ++r) col[r] = h_leaf[r * T + t];
+        std::sort(col.begin(), col.end());
+        for (size_t r = 0; r < bg_rows;) {
+            size_t n = r;
+            while (n < bg_rows && col[n] == col[r]) ++n;
+            h_occ.push_back(make_uint2(col[r], (uint32_t)(n - r)));
+            r = n;
+        }
+        if (h_occ.size() > (size_t)INT32_MAX)
+            return bail(fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_set_background: more than 2^31 - 1 occupied (tree, leaf) pairs"));
+        h_off[t + 1] = (int32_t)h_occ.size();
+    }
+    const bool avg = (f->p.output & TAHOE_OUT_AVG) != 0 && T > 0;
+    std::vector<float> h_bias(K);
+    for (size_t k = 0; k < K; ++k) {
+        double sum = 0.0;
+        for (size_t r = 0; r < bg_rows; ++r) sum += (double)raw[r * K + k];
+        double m = sum / (double)bg_rows;
+        if (avg) m /= (double)T;
+        h_bias[k] = (float)(m + (double)f->p.global_bias);
+    }
+    size_t bytes = 0;
+    if ((e = upload(&occ, h_occ, &bytes)) != hipSuccess || (e = upload(&occ_off, h_off, &bytes)) != hipSuccess ||
+        (e = upload(&bias, h_bias, &bytes)) != hipSuccess)
+        return bail(fail(e == hipErrorOutOfMemory ? TAHOE_ERR_NO_MEMORY : TAHOE_ERR_HIP,
+                         "tahoe_forest_set_background: %s; the previous background is kept", hipGetErrorString(e)));
+    (void)hipFree(leaf);
+    (void)hipFree(sums);
+    ob_background_free(f, sh);
+    sh->occ = occ;
+    sh->occ_off = occ_off;
+    sh->iv_bias = bias;
+    sh->bg_rows = bg_rows;
+    sh->bg_bytes = bytes;
+    f->device_bytes += bytes;
+    return TAHOE_OK;
+}
+
+// tahoe_forest_predict_contribs_interventional on such a handle, after the refusals of a NULL handle and a missing flag
+tahoe_status oblivious_predict_interventional(tahoe_forest *f, float *phi_dev, const float *data_dev, size_t rows, hipStream_t stream,
+                                              const char *fn)
+{
+    const tahoe_oshap *sh = f->ob->shap;
+    if (sh->bg_rows == 0) return fail(TAHOE_ERR_UNSUPPORTED, "%s: no background set (tahoe_forest_set_background)", fn);
+    if (rows == 0) return TAHOE_OK;
+    if (!phi_dev || !data_dev) return fail(TAHOE_ERR_INVALID_ARG, "%s: null argument", fn);
+    if (const tahoe_status st = check_shap_out(f, rows, 1, fn)) return st;
+    if ((rows + 63) / 64 > 0x7fffffffu) return fail(TAHOE_ERR_INVALID_ARG, "%s: too many rows for one launch: %zu", fn, rows);
+    DeviceGuard on_device(f->device);
+    const int K = f->num_classes;
+    ObShapView v = sh->view;
+    v.bias = sh->iv_bias;
+    const ObIvView b{sh->occ, sh->occ_off, sh->wtab, (float)sh->bg_rows};
+    const dim3 grid((unsigned)((rows + 63) / 64), (unsigned)((K + kObShapClasses - 1) / kObShapClasses));
+    auto launch = [&](auto kb, auto inplace) {
+        hipLaunchKernelGGL((oblivious_iv_kernel<decltype(kb)::value, decltype(inplace)::value>), grid, dim3(64), sh->iv_lds_bytes, stream,
+                           v, b, phi_dev, data_dev, rows);
+    };
+    auto with_form = [&](auto kb) {
+        if (sh->inplace) launch(kb, std::true_type{});
+        else launch(kb, std::false_type{});
+    };
+    if (K == 1) with_form(std::integral_constant<int, 1>{});
+    else with_form(std::integral_constant<int, kObShapClasses>{});
     TAHOE_HIP_TRY(hipGetLastError());
     return TAHOE_OK;
 }
