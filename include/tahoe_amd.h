@@ -481,8 +481,8 @@ typedef struct {
  * Out of scope, TAHOE_ERR_UNSUPPORTED with nothing launched and a text that says "oblivious": tahoe_forest_predict_csr,
  * _reserve_csr (and _get_csr_plan: form TAHOE_FORM_NONE), _predict_host, _set_stages, _predict_staged (_get_staged_strategy: 0),
  * _predict_contribs, _predict_contribs_approx, _predict_interactions, and _set_background with
- * _predict_contribs_interventional, unless the handle comes from tahoe_oblivious_forest_create_ex with that call's flag.  CatBoost's one-hot and CTR splits are not
- * represented. */
+ * _predict_contribs_interventional, unless the handle comes from tahoe_oblivious_forest_create_ex with that call's flag.  CatBoost's one-hot splits are
+ * category sets (tahoe_oblivious_forest_create_cat); a CTR split is a border on a column the caller computes. */
 tahoe_status tahoe_oblivious_forest_create(tahoe_forest **out, const int32_t *depths, const tahoe_oblivious_split *splits,
                                            const float *leaf_values, const tahoe_forest_params *params, int leaf_dim);
 /* SHAP interaction values on an oblivious handle: accepted by tahoe_oblivious_forest_create_ex alone (every other create:
@@ -539,6 +539,37 @@ tahoe_status tahoe_oblivious_forest_create(tahoe_forest **out, const int32_t *de
 tahoe_status tahoe_oblivious_forest_create_ex(tahoe_forest **out, const int32_t *depths, const tahoe_oblivious_split *splits,
                                               const float *leaf_values, const float *leaf_covers,
                                               const tahoe_forest_params *params, int leaf_dim, unsigned flags);
+/* tahoe_oblivious_forest_create_ex with category-set splits (CatBoost's one-hot splits; a set of any size).  Everything but cats
+ * is as there: the same four flags, each serving its own call(s); TAHOE_CREATE_CAT_CONTRIBS stays an unknown flag here, because
+ * no explanation table of an oblivious handle holds a threshold or an interval -- every explanation follows the sets as it stands.
+ * cats is the struct of tahoe_sparse_forest_create_cat in the same word layout; cats->node[k] is an index into splits[], the record
+ * of one (tree, level), strictly ascending in [0, sum_t depths[t]).  At such a level thr is ignored, fid and def_left keep their
+ * meaning, and the level's bit is steps 1-3 of tahoe_sparse_forest_create_cat, word for word: the missing sentinel takes the
+ * default branch (right iff !def_left); otherwise member = (x >= 0.0f && x < 32 * nwords) && bit((uint32_t)x) -- the cast
+ * truncates; NaN, negative values, values past the words and values >= 2^24 are never members -- and right = member !=
+ * members_left[k].  Level l still sets bit l of the leaf index; the order of the sums and the output bits are those of
+ * tahoe_oblivious_forest_create.  A CatBoost one-hot split "hash == value goes right" is the set {id of value} with members_left
+ * NULL; a CTR split is an ordinary border on a column the caller computes.
+ * cats == NULL or num_splits == 0 gives the handle of tahoe_oblivious_forest_create_ex, bit for bit and byte for byte (that call
+ * is this one with NULL).
+ * Checks, all before a device is touched, in this order: those of tahoe_oblivious_forest_create_ex, in its order; then the cats
+ * checks of tahoe_sparse_forest_create_cat with its codes and texts (TAHOE_ERR_INVALID_ARG), the bound on num_splits and node[]
+ * being sum_t depths[t], a split wider than 2^19 words refused; then, with num_splits > 0, num_cols > 2^28: TAHOE_ERR_UNSUPPORTED
+ * (the split record keeps bits 28 to 30 of its fid word for the kind of split).
+ * device_bytes: a set of at most one word (categories < 32; the one-hot case) rides in its 8-byte split record and adds nothing.
+ * A set of nwords >= 2 words adds 4 * (1 + nwords) bytes, a header word and its words in one pool:
+ *   device_bytes(cats) = device_bytes(NULL) + 4 * sum over the splits k with nwords_k >= 2 of (1 + nwords_k).
+ * The explanation tables share that pool and grow by nothing.
+ * Served, under the same flags and with the same kernel forms, strategies (DIRECT, ROWTILE, AUTO) and graph capture: everything
+ * tahoe_oblivious_forest_create_ex serves -- tahoe_forest_predict, _predict_raw, _predict_leaf_idx, _predict_accumulate (K == 1),
+ * _reserve, _predict_contribs, _predict_contribs_approx, _predict_interactions, _set_background and
+ * _predict_contribs_interventional, their definitions unchanged except that "the row's bit at a level" is the rule above.  The
+ * elements of a tree are still its distinct features in order of first appearance, whether a feature appears numeric,
+ * categorical, or both.  What that handle refuses stays refused with the same texts. */
+tahoe_status tahoe_oblivious_forest_create_cat(tahoe_forest **out, const int32_t *depths, const tahoe_oblivious_split *splits,
+                                               const float *leaf_values, const float *leaf_covers,
+                                               const tahoe_forest_params *params, int leaf_dim, unsigned flags,
+                                               const tahoe_categorical_splits *cats);
 
 /* ---- vector-leaf forests: irregular trees whose leaves hold K = leaf_dim values (scikit-learn's RandomForestClassifier,
  * ExtraTreesClassifier, DecisionTreeClassifier and multi-output regressors; XGBoost multi_strategy = "multi_output_tree"); no

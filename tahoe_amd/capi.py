@@ -152,6 +152,8 @@ _PROTOS = {
                                             C.POINTER(CategoricalSplits)]),
     "tahoe_oblivious_forest_create": (_i, [C.POINTER(_vp), _vp, _vp, _vp, C.POINTER(ForestParams), _i]),
     "tahoe_oblivious_forest_create_ex": (_i, [C.POINTER(_vp), _vp, _vp, _vp, _vp, C.POINTER(ForestParams), _i, C.c_uint]),
+    "tahoe_oblivious_forest_create_cat": (_i, [C.POINTER(_vp), _vp, _vp, _vp, _vp, C.POINTER(ForestParams), _i, C.c_uint,
+                                               C.POINTER(CategoricalSplits)]),
     "tahoe_vector_forest_create": (_i, [C.POINTER(_vp), _vp, _vp, _vp, C.c_int64, C.POINTER(ForestParams), _i]),
     "tahoe_vector_forest_create_ex": (_i, [C.POINTER(_vp), _vp, _vp, _vp, C.c_int64, _vp, C.POINTER(ForestParams), _i, C.c_uint]),
     "tahoe_dense_to_sparse": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz)]),
@@ -806,11 +808,14 @@ class ObliviousForest(Forest):
     interactions=True (tahoe_oblivious_forest_create_ex) serve predict_contribs / predict_contribs_approx / predict_interactions,
     each its own call only, and need leaf_covers: sum(2 ** depths) floats, the training weight of every leaf (CatBoost's
     leaf_weights); zeros are allowed.  interventional=True (TAHOE_CREATE_OBLIVIOUS_INTERVENTIONAL) serves set_background and
-    predict_contribs_interventional; alone it needs no leaf_covers."""
+    predict_contribs_interventional; alone it needs no leaf_covers.  categories ({split index: category ids}, the index running
+    over the flattened (tree, level) records) makes those levels category-set splits, members going right unless the index is in
+    members_left (tahoe_oblivious_forest_create_cat; the level's threshold is then ignored); every call above follows the sets."""
 
     def __init__(self, depths, fids, thresholds, def_left, leaf_values, num_cols: int, leaf_dim: int = 1, missing: float = 0.0,
                  output: int = OUT_RAW, threshold: float = 0.5, global_bias: float = 0.0, leaf_covers=None, contribs: bool = False,
-                 approx_contribs: bool = False, interactions: bool = False, interventional: bool = False):
+                 approx_contribs: bool = False, interactions: bool = False, interventional: bool = False, categories=None,
+                 members_left=()):
         depths = np.ascontiguousarray(depths, dtype=np.int32).reshape(-1)
         fids = np.asarray(fids, dtype=np.int64).reshape(-1)
         nsplits = int(depths.astype(np.int64).sum())
@@ -831,7 +836,7 @@ class ObliviousForest(Forest):
         self._h = _vp()
         flags = ((CREATE_CONTRIBS if contribs else 0) | (CREATE_APPROX_CONTRIBS if approx_contribs else 0)
                  | (CREATE_INTERACTIONS if interactions else 0))
-        if flags or interventional:
+        if flags or interventional or categories:
             cv = None
             if flags:
                 if leaf_covers is None:
@@ -841,10 +846,17 @@ class ObliviousForest(Forest):
                     raise ValueError("leaf_covers.size != sum(2 ** depths)")
                 cv = covers if covers.size else np.zeros(1, np.float32)
             flags |= CREATE_OBLIVIOUS_INTERVENTIONAL if interventional else 0
-            _check(lib.tahoe_oblivious_forest_create_ex(C.byref(self._h), dp.ctypes.data, splits.ctypes.data if nsplits else None,
-                                                        lv.ctypes.data, None if cv is None else cv.ctypes.data, C.byref(self.params),
-                                                        leaf_dim, flags),
-                   "tahoe_oblivious_forest_create_ex")
+            if categories:
+                cats, _keep = pack_categorical(categories, members_left)
+                _check(lib.tahoe_oblivious_forest_create_cat(C.byref(self._h), dp.ctypes.data, splits.ctypes.data if nsplits else None,
+                                                             lv.ctypes.data, None if cv is None else cv.ctypes.data,
+                                                             C.byref(self.params), leaf_dim, flags, C.byref(cats)),
+                       "tahoe_oblivious_forest_create_cat")
+            else:
+                _check(lib.tahoe_oblivious_forest_create_ex(C.byref(self._h), dp.ctypes.data, splits.ctypes.data if nsplits else None,
+                                                            lv.ctypes.data, None if cv is None else cv.ctypes.data,
+                                                            C.byref(self.params), leaf_dim, flags),
+                       "tahoe_oblivious_forest_create_ex")
         else:
             _check(lib.tahoe_oblivious_forest_create(C.byref(self._h), dp.ctypes.data, splits.ctypes.data if nsplits else None,
                                                      lv.ctypes.data, C.byref(self.params), leaf_dim), "tahoe_oblivious_forest_create")

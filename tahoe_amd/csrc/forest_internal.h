@@ -443,6 +443,40 @@ __device__ __forceinline__ uint32_t go_right_meta(float x, float thr, uint32_t m
 {
     return go_right(x, thr, (meta >> 31) != 0, missing) ^ ((meta >> 30) & 1u);
 }
+// The argument checks of tahoe_categorical_splits, shared by the creates that take them (sparse.hip)
+tahoe_status check_cat_args(const tahoe_categorical_splits *c, int num_nodes);
+
+// The split record of an oblivious handle (oblivious.hip, oblivious_shap.hip): an InnerNode {thr, fid | def_left << 31} whose bit
+// 30 -- the exchange bit of a heap record, which no oblivious handle sets -- says "category set" (tahoe_oblivious_forest_create_cat).
+// Such a record has a 28-bit fid (num_cols <= 2^28 on a handle with sets) and one of two kinds:
+//   inline  (bit 29 clear): the set's only word sits where thr was (nwords <= 1; an empty set is the word 0), bit 28 = members_left
+//   pooled  (bit 29 set):   thr's bits are the index of the set's header in the handle's pool, laid out as go_right_cat reads it
+// The record sits at a wave-uniform address, so the kind is wave-uniform and the branch on it diverges nowhere.
+constexpr uint32_t kObCat = 1u << 30;
+constexpr uint32_t kObCatPooled = 1u << 29;
+constexpr uint32_t kObCatLeft = 1u << 28;
+constexpr uint32_t kObCatFidMask = (1u << 28) - 1u;
+__host__ __device__ __forceinline__ uint32_t ob_split_fid(uint32_t meta)
+{
+    return meta & ((meta & kObCat) ? kObCatFidMask : kMetaFidMask);
+}
+// The bit level l adds to the leaf index: the one definition of the branch rule of an oblivious level, for the walk and for every
+// explanation kernel.  CAT == false is a handle without sets: go_right_meta and nothing else.
+template <bool CAT>
+__device__ __forceinline__ uint32_t ob_split_bit(const InnerNode n, float x, float missing, const uint32_t *__restrict__ pool,
+                                                 uint32_t pool_words)
+{
+    if (!CAT || !(n.meta & kObCat)) return go_right_meta(x, n.thr, n.meta, missing);
+    const bool def_left = (n.meta >> 31) != 0u;
+    if (n.meta & kObCatPooled) return go_right_cat(x, pool, __float_as_uint(n.thr), pool_words, def_left, missing);
+    // go_right_cat on a set of one word held in a register: x < 32 <=> (uint32_t)x < 32 for the x >= 0 that pass
+    const bool is_missing = fabsf(x - missing) <= kMissingEps;
+    const bool in = x >= 0.0f && x < 32.0f;
+    const uint32_t c = in ? (uint32_t)x : 0u;
+    const bool member = in && ((__float_as_uint(n.thr) >> c) & 1u) != 0u;
+    const bool cond = is_missing ? !def_left : (member != ((n.meta & kObCatLeft) != 0u));
+    return cond ? 1u : 0u;
+}
 
 // Multi-class handles store the trees class-major: internal tree p (class p / class_trees) is original tree
 // (p % class_trees) * num_classes + p / class_trees.  Leaf indices are written in the original numbering.

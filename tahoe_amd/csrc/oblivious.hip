@@ -6,6 +6,8 @@
 //   split_off[T + 1]     first record of tree t; D_t = split_off[t + 1] - split_off[t]
 //   leaf_off[T]          first leaf of tree t, in leaves (64-bit: T x 2^16 leaves x K values passes 2^31)
 //   leaves[sum 2^D_t][K] as the caller gave them (CatBoost's layout)
+//   cat_pool[]           tahoe_oblivious_forest_create_cat only: header and words of every set wider than one word; a narrower set
+//                        rides in its split record (forest_internal.h: kObCat)
 // The walk has nothing to gather per lane: a level's split record sits at a wave-uniform address (scalar loads), its feature is one
 // 64-float row of the LDS tile, the leaf index is D compare bits (level 0 = bit 0), and one table read finishes the tree.
 //
@@ -14,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstring>
 #include <new>
 #include <type_traits>
 #include <vector>
@@ -28,11 +31,14 @@ constexpr int kObClasses = 8;  // accumulators a lane keeps: gridDim.y runs over
 // The walk of one row over all trees, for classes [blockIdx.y * KB, + KB).  feature(fid) reads the row's value of a feature.
 // KB == 1 is the single-output handle (K == 1; sums_in continues a running sum), KB == kObClasses a block of a vector leaf.
 // Leaf indices are written once, by class block 0.
-template <int KB, bool WRITE_LEAF, class Feature>
+// CAT: the handle has category sets (tahoe_oblivious_forest_create_cat); a level's record then says its kind (ob_split_bit).  An
+// inline set is tested in registers; a pooled one gathers its member word per lane, and the kObTrees trees in flight overlap it.
+template <int KB, bool WRITE_LEAF, bool CAT, class Feature>
 __device__ __forceinline__ void oblivious_walk(const InnerNode *__restrict__ splits, const int32_t *__restrict__ split_off,
                                                const int64_t *__restrict__ leaf_off, const float *__restrict__ leaves, float *sums,
                                                uint32_t *__restrict__ leaf_out, const float *sums_in, size_t row, bool row_ok,
-                                               int num_trees, int K, float missing, Feature &&feature)
+                                               int num_trees, int K, float missing, const uint32_t *__restrict__ cat_pool,
+                                               uint32_t cat_words, Feature &&feature)
 {
     const int k0 = (int)blockIdx.y * KB;
     float acc[KB];
@@ -49,7 +55,8 @@ __device__ __forceinline__ void oblivious_walk(const InnerNode *__restrict__ spl
 #pragma unroll 4
         for (int l = 0; l < d; ++l) {
             const InnerNode n = splits[s0 + l];
-            idx |= go_right_meta(feature(n.meta & kMetaFidMask), n.thr, n.meta, missing) << l;
+            const uint32_t fid = CAT ? ob_split_fid(n.meta) : n.meta & kMetaFidMask;
+            idx |= ob_split_bit<CAT>(n, feature(fid), missing, cat_pool, cat_words) << l;
         }
         if (write_leaf) leaf_out[row * (size_t)num_trees + t] = idx;
         const float *lv = leaves + ((size_t)leaf_off[t] + idx) * (size_t)K + k0;
@@ -84,14 +91,15 @@ __device__ __forceinline__ void oblivious_walk(const InnerNode *__restrict__ spl
 // rowtile_kernel; a level's feature is the row tile[fid][0..64): 64 consecutive floats, no bank conflict, no per-lane address
 // arithmetic.  A lane reads back only what it stored itself, so there is no barrier after staging, and nothing crosses waves.
 // Dynamic LDS: [cols][64] float.
-template <int KB, bool WRITE_LEAF>
+template <int KB, bool WRITE_LEAF, bool CAT>
 __global__ void __launch_bounds__(kTileRows) oblivious_tile_kernel(const InnerNode *__restrict__ splits,
                                                                    const int32_t *__restrict__ split_off,
                                                                    const int64_t *__restrict__ leaf_off,
                                                                    const float *__restrict__ leaves, const float *__restrict__ data,
                                                                    float *sums, uint32_t *__restrict__ leaf_out, const float *sums_in,
                                                                    size_t rows, int cols, int num_trees, int K, float missing,
-                                                                   int vec4_ok)
+                                                                   int vec4_ok, const uint32_t *__restrict__ cat_pool,
+                                                                   uint32_t cat_words)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float *tile = reinterpret_cast<float *>(smem);
@@ -115,24 +123,25 @@ __global__ void __launch_bounds__(kTileRows) oblivious_tile_kernel(const InnerNo
         for (int f = 0; f < cols; ++f) tile[f * kTileRows + lane] = row_ok ? src[f] : 0.0f;
     }
 
-    oblivious_walk<KB, WRITE_LEAF>(splits, split_off, leaf_off, leaves, sums, leaf_out, sums_in, row, row_ok, num_trees, K, missing,
-                                   [&](uint32_t fid) { return tile[fid * kTileRows + lane]; });
+    oblivious_walk<KB, WRITE_LEAF, CAT>(splits, split_off, leaf_off, leaves, sums, leaf_out, sums_in, row, row_ok, num_trees, K,
+                                        missing, cat_pool, cat_words, [&](uint32_t fid) { return tile[fid * kTileRows + lane]; });
 }
 
 // DIRECT: the same walk with the features read from global memory, for any num_cols.
-template <int KB, bool WRITE_LEAF>
+template <int KB, bool WRITE_LEAF, bool CAT>
 __global__ void __launch_bounds__(kBlock) oblivious_direct_kernel(const InnerNode *__restrict__ splits,
                                                                   const int32_t *__restrict__ split_off,
                                                                   const int64_t *__restrict__ leaf_off,
                                                                   const float *__restrict__ leaves, const float *__restrict__ data,
                                                                   float *sums, uint32_t *__restrict__ leaf_out, const float *sums_in,
-                                                                  size_t rows, int cols, int num_trees, int K, float missing)
+                                                                  size_t rows, int cols, int num_trees, int K, float missing,
+                                                                  const uint32_t *__restrict__ cat_pool, uint32_t cat_words)
 {
     const size_t row = (size_t)blockIdx.x * kBlock + threadIdx.x;
     const bool row_ok = row < rows;
     const float *x = data + (row_ok ? row : 0) * (size_t)cols;  // (a lane past the batch walks row 0 and stores nothing)
-    oblivious_walk<KB, WRITE_LEAF>(splits, split_off, leaf_off, leaves, sums, leaf_out, sums_in, row, row_ok, num_trees, K, missing,
-                                   [&](uint32_t fid) { return x[fid]; });
+    oblivious_walk<KB, WRITE_LEAF, CAT>(splits, split_off, leaf_off, leaves, sums, leaf_out, sums_in, row, row_ok, num_trees, K,
+                                        missing, cat_pool, cat_words, [&](uint32_t fid) { return x[fid]; });
 }
 
 static long long oblivious_tile_bytes(const tahoe_forest *f) { return (long long)f->p.num_cols * kTileRows * (long long)sizeof(float); }
@@ -146,21 +155,26 @@ tahoe_status oblivious_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, 
     const int K = f->num_classes, T = f->p.num_trees, cols = f->p.num_cols;
     const unsigned blocks_y = (unsigned)((K + kObClasses - 1) / kObClasses);  // 1 when K == 1
     const int vec4_ok = (cols % 4 == 0) && ((reinterpret_cast<uintptr_t>(data) & 15u) == 0);
-    auto launch = [&](auto kb, auto wl) {
+    auto launch = [&](auto kb, auto wl, auto cat) {
         constexpr int KB = decltype(kb)::value;
         constexpr bool WL = decltype(wl)::value;
+        constexpr bool CAT = decltype(cat)::value;
         if (strategy == TAHOE_STRATEGY_ROWTILE)
-            hipLaunchKernelGGL((oblivious_tile_kernel<KB, WL>), dim3((unsigned)((rows + kTileRows - 1) / kTileRows), blocks_y),
+            hipLaunchKernelGGL((oblivious_tile_kernel<KB, WL, CAT>), dim3((unsigned)((rows + kTileRows - 1) / kTileRows), blocks_y),
                                dim3(kTileRows), (size_t)oblivious_tile_bytes(f), stream, o->splits, o->split_off, o->leaf_off, o->leaves,
-                               data, sums, leaf_out, sums_in, rows, cols, T, K, f->p.missing, vec4_ok);
+                               data, sums, leaf_out, sums_in, rows, cols, T, K, f->p.missing, vec4_ok, o->cat_pool, o->cat_words);
         else
-            hipLaunchKernelGGL((oblivious_direct_kernel<KB, WL>), dim3((unsigned)((rows + kBlock - 1) / kBlock), blocks_y), dim3(kBlock),
-                               0, stream, o->splits, o->split_off, o->leaf_off, o->leaves, data, sums, leaf_out, sums_in, rows, cols, T, K,
-                               f->p.missing);
+            hipLaunchKernelGGL((oblivious_direct_kernel<KB, WL, CAT>), dim3((unsigned)((rows + kBlock - 1) / kBlock), blocks_y),
+                               dim3(kBlock), 0, stream, o->splits, o->split_off, o->leaf_off, o->leaves, data, sums, leaf_out, sums_in,
+                               rows, cols, T, K, f->p.missing, o->cat_pool, o->cat_words);
     };
-    with_leaf(leaf_out != nullptr, [&](auto wl) {
-        if (K == 1) launch(std::integral_constant<int, 1>{}, wl);
-        else launch(std::integral_constant<int, kObClasses>{}, wl);
+    with_leaf(leaf_out != nullptr, [&](auto wl) {  // a handle without sets launches the instantiation without the kind test
+        auto with_classes = [&](auto cat) {
+            if (K == 1) launch(std::integral_constant<int, 1>{}, wl, cat);
+            else launch(std::integral_constant<int, kObClasses>{}, wl, cat);
+        };
+        if (o->cats) with_classes(std::true_type{});
+        else with_classes(std::false_type{});
     });
     TAHOE_HIP_TRY(hipGetLastError());
     return TAHOE_OK;
@@ -175,6 +189,7 @@ void oblivious_destroy(tahoe_forest *f)
     if (o->split_off) (void)hipFree(o->split_off);
     if (o->leaf_off) (void)hipFree(o->leaf_off);
     if (o->leaves) (void)hipFree(o->leaves);
+    if (o->cat_pool) (void)hipFree(o->cat_pool);
     delete o;
     f->ob = nullptr;
 }
@@ -183,9 +198,12 @@ void oblivious_destroy(tahoe_forest *f)
 static tahoe_status oblivious_allow_lds(const tahoe_forest *f)
 {
     hipError_t e = hipSuccess;
-    if (oblivious_tile_fits(f) &&
-        ((e = allow_max_lds_leaf([](auto wl) { return &oblivious_tile_kernel<1, decltype(wl)::value>; }, f->lds_limit)) != hipSuccess ||
-         (e = allow_max_lds_leaf([](auto wl) { return &oblivious_tile_kernel<kObClasses, decltype(wl)::value>; }, f->lds_limit)) != hipSuccess))
+    if (!oblivious_tile_fits(f)) return TAHOE_OK;
+    if (f->ob->cats
+            ? ((e = allow_max_lds_leaf([](auto wl) { return &oblivious_tile_kernel<1, decltype(wl)::value, true>; }, f->lds_limit)) != hipSuccess ||
+               (e = allow_max_lds_leaf([](auto wl) { return &oblivious_tile_kernel<kObClasses, decltype(wl)::value, true>; }, f->lds_limit)) != hipSuccess)
+            : ((e = allow_max_lds_leaf([](auto wl) { return &oblivious_tile_kernel<1, decltype(wl)::value, false>; }, f->lds_limit)) != hipSuccess ||
+               (e = allow_max_lds_leaf([](auto wl) { return &oblivious_tile_kernel<kObClasses, decltype(wl)::value, false>; }, f->lds_limit)) != hipSuccess))
         return hip_status(e, "hipFuncSetAttribute(oblivious_tile)");
     return TAHOE_OK;
 }
@@ -194,10 +212,10 @@ static tahoe_status oblivious_allow_lds(const tahoe_forest *f)
 
 using namespace tahoe;
 
-extern "C" tahoe_status tahoe_oblivious_forest_create_ex(tahoe_forest **out, const int32_t *depths,
-                                                         const tahoe_oblivious_split *splits, const float *leaf_values,
-                                                         const float *leaf_covers, const tahoe_forest_params *p, int leaf_dim,
-                                                         unsigned flags)
+extern "C" tahoe_status tahoe_oblivious_forest_create_cat(tahoe_forest **out, const int32_t *depths,
+                                                          const tahoe_oblivious_split *splits, const float *leaf_values,
+                                                          const float *leaf_covers, const tahoe_forest_params *p, int leaf_dim,
+                                                          unsigned flags, const tahoe_categorical_splits *cats)
 {
     // every check here runs before a device is touched
     if (!out || !depths || !leaf_values || !p) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_oblivious_forest_create: null argument");
@@ -250,6 +268,35 @@ extern "C" tahoe_status tahoe_oblivious_forest_create_ex(tahoe_forest **out, con
     if (cover_flags)
         if (const tahoe_status s = oblivious_shap_validate(depths, T, leaf_covers)) return s;
 
+    // ... and those of the category sets (tahoe_oblivious_forest_create_cat), which name (tree, level) records
+    std::vector<uint32_t> h_pool;
+    if (cats) {
+        if (const tahoe_status s = check_cat_args(cats, (int)total_depth)) return s;
+        if (cats->num_splits == 0) cats = nullptr;  // the handle of tahoe_oblivious_forest_create_ex
+    }
+    if (cats) {
+        if (p->num_cols > (1 << 28))
+            return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_oblivious_forest_create_cat: categorical splits need num_cols <= 2^28 (the "
+                                               "split record keeps bits 28 to 30 for the kind of split); num_cols = %d", p->num_cols);
+        // a set of at most one word rides in its record, where thr was; a wider one goes to the pool: header, then its words
+        for (int k = 0; k < cats->num_splits; ++k) {
+            InnerNode &n = h_splits[(size_t)cats->node[k]];
+            const uint32_t nw = (uint32_t)(cats->offset[k + 1] - cats->offset[k]);
+            const bool ml = cats->members_left && cats->members_left[k];
+            uint32_t word = nw ? cats->words[cats->offset[k]] : 0u;
+            n.meta |= kObCat;
+            if (nw <= 1) {
+                n.meta |= ml ? kObCatLeft : 0u;
+            } else {
+                n.meta |= kObCatPooled;
+                word = (uint32_t)h_pool.size();
+                h_pool.push_back((ml ? 0x80000000u : 0u) | nw);
+                h_pool.insert(h_pool.end(), cats->words + cats->offset[k], cats->words + cats->offset[k + 1]);
+            }
+            memcpy(&n.thr, &word, sizeof word);
+        }
+    }
+
     ForestPtr f;
     if (const tahoe_status s = open_handle(p, leaf_dim, f)) return s;
     f->class_trees = T;  // AVG divides by (float)num_trees whatever K is
@@ -257,7 +304,12 @@ extern "C" tahoe_status tahoe_oblivious_forest_create_ex(tahoe_forest **out, con
     f->ob = new (std::nothrow) tahoe_ostate();
     if (!f->ob) return fail(TAHOE_ERR_NO_MEMORY, "tahoe_oblivious_forest_create");
     tahoe_ostate *o = f->ob;
+    o->cats = cats != nullptr;
     tahoe_status s = TAHOE_OK;
+    if (!h_pool.empty()) {
+        o->cat_words = (uint32_t)h_pool.size();
+        if ((s = hip_status(upload(&o->cat_pool, h_pool, &f->device_bytes), "upload(categorical splits)"))) return s;
+    }
     if ((s = hip_status(upload(&o->splits, h_splits, &f->device_bytes), "upload(splits)")) ||
         (s = hip_status(upload(&o->split_off, h_split_off, &f->device_bytes), "upload(split_off)")) ||
         (s = hip_status(upload(&o->leaf_off, h_leaf_off, &f->device_bytes), "upload(leaf_off)")) ||
@@ -270,6 +322,14 @@ extern "C" tahoe_status tahoe_oblivious_forest_create_ex(tahoe_forest **out, con
     }
     *out = f.release();
     return TAHOE_OK;
+}
+
+extern "C" tahoe_status tahoe_oblivious_forest_create_ex(tahoe_forest **out, const int32_t *depths,
+                                                         const tahoe_oblivious_split *splits, const float *leaf_values,
+                                                         const float *leaf_covers, const tahoe_forest_params *p, int leaf_dim,
+                                                         unsigned flags)
+{
+    return tahoe_oblivious_forest_create_cat(out, depths, splits, leaf_values, leaf_covers, p, leaf_dim, flags, nullptr);
 }
 
 extern "C" tahoe_status tahoe_oblivious_forest_create(tahoe_forest **out, const int32_t *depths, const tahoe_oblivious_split *splits,

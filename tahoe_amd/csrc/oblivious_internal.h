@@ -1,5 +1,6 @@
 // What the translation units of an oblivious handle share (oblivious.hip: create and the walk; oblivious_shap.hip: the TreeSHAP,
-// Saabas and interaction tables and kernels).  Internal: not part of the ABI.
+// Saabas and interaction tables and kernels; oblivious_shap_cat.hip: those kernels for handles with category sets).  Internal: not
+// part of the ABI.
 #pragma once
 #include "forest_internal.h"
 
@@ -10,6 +11,11 @@ struct tahoe_ostate {
     int32_t *split_off = nullptr;
     int64_t *leaf_off = nullptr;
     float *leaves = nullptr;
+    // tahoe_oblivious_forest_create_cat with splits: cats says that some record is a category set (forest_internal.h: kObCat);
+    // cat_pool holds the sets wider than one word (null when there is none), cat_words its length in words
+    bool cats = false;
+    uint32_t *cat_pool = nullptr;
+    uint32_t cat_words = 0;
     tahoe_oshap *shap = nullptr;
 };
 
@@ -17,7 +23,8 @@ namespace tahoe {
 
 constexpr int kObMaxDepth = 16;
 
-// The caller's forest as the creates have checked it, for the table builds: h_splits holds {thr, fid | def_left << 31}
+// The caller's forest as the creates have checked it, for the table builds: h_splits holds the device records ({thr, fid |
+// def_left << 31}; a category set as forest_internal.h describes it)
 struct ObliviousSource {
     const int32_t *depths;
     const std::vector<InnerNode> *h_splits;

@@ -1,5 +1,6 @@
 // TreeSHAP and Saabas contributions on an oblivious handle (tahoe_oblivious_forest_create_ex with TAHOE_CREATE_CONTRIBS /
-// TAHOE_CREATE_APPROX_CONTRIBS).
+// TAHOE_CREATE_APPROX_CONTRIBS).  Handles with category sets run the CAT == true
+// instantiations of the kernels below, which oblivious_shap_cat.hip compiles from this file's device code.
 //
 // Every leaf of an oblivious tree tests the same m <= D distinct features in the same order, the cover ratios of a leaf's path
 // depend on (tree, leaf) alone, and a row follows the path's element of feature e exactly when its leaf index idx and the leaf j
@@ -8,7 +9,8 @@
 //
 // Tables, built once at create from the leaf covers (float64 on the host):
 //   splits[sum D_t]       {thr, id | def_left << 31}; id = the feature's compact id over the features the forest uses (LDS form)
-//                         or its column (in-place form)
+//                         or its column (in-place form).  A category set (tahoe_oblivious_forest_create_cat) keeps its kind bits
+//                         and its word or pool index as the walk's record has them; the pool itself is the walk's, not a copy
 //   used[U]               column of compact id c, ascending
 //   elems[sum m_t]        {id, level mask} of tree t's distinct features in order of first appearance from level 0
 //   zz[sum 2^D_t m_t]     {z, 1 - z} of (tree, leaf, element): z = the product of the cover ratios on the leaf's path over the
@@ -63,6 +65,7 @@
 #include <algorithm>
 #include <cmath>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "contribs_internal.h"
@@ -89,6 +92,25 @@ struct ObShapView {
     float div, missing;
     int F, K, T, U, S;  // columns, leaf dimension, trees, used features, floats per slab row (odd)
 };
+// ... as a kernel argument: on a handle with category sets the walk's pool (shared, not copied; null: no pooled set) and its length
+// in words ride behind it, and a handle without sets passes what it always passed
+struct ObShapCatView : ObShapView {
+    const uint32_t *cat_pool;
+    uint32_t cat_words;
+};
+template <bool CAT>
+using ObCatView = std::conditional_t<CAT, ObShapCatView, ObShapView>;
+template <bool CAT>
+inline ObCatView<CAT> ob_cat_view(const ObShapView &v, const uint32_t *cat_pool, uint32_t cat_words)
+{
+    ObCatView<CAT> c;
+    static_cast<ObShapView &>(c) = v;
+    if constexpr (CAT) {
+        c.cat_pool = cat_pool;
+        c.cat_words = cat_words;
+    }
+    return c;
+}
 
 constexpr int kObIvW = 17;                        // u and s run over 0 .. 16
 constexpr int kObIvTable = 2 * kObIvW * kObIvW;   // floats of W+ | W-
@@ -101,38 +123,7 @@ struct ObIvView {
     float fB;                 // (float)background rows
 };
 
-}  // namespace tahoe
 
-struct tahoe_oshap {
-    tahoe::InnerNode *splits = nullptr;
-    int32_t *used = nullptr;
-    uint2 *elems = nullptr;
-    int32_t *elem_off = nullptr;
-    float2 *zz = nullptr;
-    int64_t *zz_off = nullptr;
-    uint32_t *zmask = nullptr;
-    float *delta = nullptr;
-    float *bias = nullptr;
-    tahoe::InnerNode *splits_col = nullptr;  // TAHOE_CREATE_INTERACTIONS: splits and elems with id = the column in either form
-    uint2 *elems_col = nullptr;
-    bool contribs = false, approx = false, inter = false;
-    bool inplace = false;  // accumulate in phi_dev (else in LDS)
-    size_t lds_bytes = 0;
-    tahoe::ObShapView view{};
-    tahoe::ObShapView inter_view{};  // view with splits_col and elems_col
-    // TAHOE_CREATE_OBLIVIOUS_INTERVENTIONAL: the weight tables (create); the background (tahoe_forest_set_background): occupied
-    // leaves, per-tree offsets, bias column
-    bool iv = false;
-    size_t iv_lds_bytes = 0;  // oblivious_iv_kernel: lds_bytes, then the weight tables
-    float *wtab = nullptr;
-    uint2 *occ = nullptr;
-    int32_t *occ_off = nullptr;
-    float *iv_bias = nullptr;
-    size_t bg_rows = 0;   // 0: no background
-    size_t bg_bytes = 0;  // device bytes of the three background buffers (counted in tahoe_forest::device_bytes)
-};
-
-namespace tahoe {
 
 // One wave's 64 rows and their accumulators for the classes [k0, k0 + kb) of this grid.y block
 template <int KB, bool INPLACE>
@@ -212,17 +203,27 @@ __device__ __forceinline__ void ob_shap_end(const ObShapView &v, const ObShapRow
         }
 }
 
-// The row's leaf index of tree t (level 0 = bit 0), as oblivious_walk computes it; each(l, id, idx) after level l's bit is in
-template <class Rows, class Each>
-__device__ __forceinline__ uint32_t ob_shap_leaf_index(const ObShapView &v, const Rows &r, int t, Each &&each)
+// The row's leaf index of tree t (level 0 = bit 0), as oblivious_walk computes it; each(l, id, idx) after level l's bit is in.
+// This is the only place where an explanation kernel sees the row, so a category set (a record with kObCat, a wave-uniform
+// branch in ob_split_bit) changes nothing else: no table holds a threshold.  CAT == false is the code of a handle without sets:
+// every kernel is instantiated for both, because the branch taken at run time on every handle cost a numeric handle up to a
+// quarter of its Saabas time.
+template <bool CAT, class Rows, class Each>
+__device__ __forceinline__ uint32_t ob_shap_leaf_index(const ObCatView<CAT> &v, const Rows &r, int t, Each &&each)
 {
+    const uint32_t *cat_pool = nullptr;
+    uint32_t cat_words = 0;
+    if constexpr (CAT) {
+        cat_pool = v.cat_pool;
+        cat_words = v.cat_words;
+    }
     const int s0 = v.split_off[t];
     const int d = v.split_off[t + 1] - s0;
     uint32_t idx = 0;
     for (int l = 0; l < d; ++l) {
         const InnerNode n = v.splits[s0 + l];
-        const uint32_t id = n.meta & kMetaFidMask;
-        idx |= go_right_meta(r.feature(id), n.thr, n.meta, v.missing) << l;
+        const uint32_t id = CAT ? ob_split_fid(n.meta) : n.meta & kMetaFidMask;
+        idx |= ob_split_bit<CAT>(n, r.feature(id), v.missing, cat_pool, cat_words) << l;
         each(l, id, idx);
     }
     return idx;
@@ -302,8 +303,8 @@ __device__ __forceinline__ void ob_shap_tree(const ObShapRows<KB, INPLACE> &r, c
 }
 
 // TreeSHAP: grid (row tiles, class blocks), one wave per workgroup.  Dynamic LDS (not INPLACE): [U][64] tile | [64][S] slab.
-template <int KB, bool INPLACE>
-__global__ void __launch_bounds__(64) oblivious_shap_kernel(const ObShapView v, float *__restrict__ phi,
+template <int KB, bool INPLACE, bool CAT = false>
+__global__ void __launch_bounds__(64) oblivious_shap_kernel(const ObCatView<CAT> v, float *__restrict__ phi,
                                                             const float *__restrict__ data, size_t rows)
 {
     extern __shared__ __attribute__((aligned(16))) float ob_shap_smem[];
@@ -312,7 +313,7 @@ __global__ void __launch_bounds__(64) oblivious_shap_kernel(const ObShapView v, 
         const int e0 = v.elem_off[t];
         const int m = v.elem_off[t + 1] - e0;  // wave-uniform, as everything read below
         if (m == 0) continue;                  // a single leaf: all of it is bias
-        const uint32_t idx = ob_shap_leaf_index(v, r, t, [](int, uint32_t, uint32_t) {});
+        const uint32_t idx = ob_shap_leaf_index<CAT>(v, r, t, [](int, uint32_t, uint32_t) {});
         const int nleaf = 1 << (v.split_off[t + 1] - v.split_off[t]);
         const uint2 *el = v.elems + e0;
         const float2 *zz = v.zz + v.zz_off[t];
@@ -333,8 +334,8 @@ __global__ void __launch_bounds__(64) oblivious_shap_kernel(const ObShapView v, 
 }
 
 // Saabas: the walk of oblivious_walk with one add per level -- the taken child's delta to the level's feature
-template <int KB, bool INPLACE>
-__global__ void __launch_bounds__(64) oblivious_approx_kernel(const ObShapView v, float *__restrict__ phi,
+template <int KB, bool INPLACE, bool CAT = false>
+__global__ void __launch_bounds__(64) oblivious_approx_kernel(const ObCatView<CAT> v, float *__restrict__ phi,
                                                               const float *__restrict__ data, size_t rows)
 {
     extern __shared__ __attribute__((aligned(16))) float ob_shap_smem[];
@@ -342,7 +343,7 @@ __global__ void __launch_bounds__(64) oblivious_approx_kernel(const ObShapView v
     for (int t = 0; t < v.T; ++t) {
         // children of level l start at 2^(l + 1) - 2 of the tree's deltas; the child's index is the leaf index so far
         const float *dt = v.delta + (size_t)(2 * (v.leaf_off[t] - t)) * (size_t)v.K + r.k0;
-        ob_shap_leaf_index(v, r, t, [&](int l, uint32_t id, uint32_t idx) {
+        ob_shap_leaf_index<CAT>(v, r, t, [&](int l, uint32_t id, uint32_t idx) {
             const float *d = dt + (size_t)((2u << l) - 2u + idx) * (size_t)v.K;
 #pragma unroll
             for (int k = 0; k < KB; ++k)
@@ -435,16 +436,17 @@ __device__ __forceinline__ void ob_inter_tree(const ObShapRows<KB, true> &r, flo
 }
 
 // SHAP interaction values: grid (row tiles, class blocks), one wave per workgroup, no LDS.  v holds columns in splits and elems.
-template <int KB>
-__global__ void __launch_bounds__(64) oblivious_inter_kernel(const ObShapView vin, float *__restrict__ out,
+template <int KB, bool CAT = false>
+__global__ void __launch_bounds__(64) oblivious_inter_kernel(const ObCatView<CAT> vin, float *__restrict__ out,
                                                              const float *__restrict__ data, size_t rows)
 {
     // The view's pointers pass through an empty asm and are ordinary scalar values from here on.  As kernel-argument loads, which
     // the register allocator may repeat instead of spilling, a 16-dword group of them left a spill slot behind that no
     // instruction uses: 68 bytes of stack per lane in the resource table.  So: ScratchSize 0.
-    ObShapView v = vin;
+    ObCatView<CAT> v = vin;
     asm volatile("" : "+s"(v.splits), "+s"(v.split_off), "+s"(v.leaf_off), "+s"(v.leaves), "+s"(v.used), "+s"(v.elems), "+s"(v.elem_off),
                  "+s"(v.zz), "+s"(v.zz_off), "+s"(v.zmask), "+s"(v.bias));
+    if constexpr (CAT) asm volatile("" : "+s"(v.cat_pool));
     ObShapRows<KB, true> r;
     r.lane = (int)threadIdx.x;
     r.row0 = (size_t)blockIdx.x * 64;
@@ -471,7 +473,7 @@ __global__ void __launch_bounds__(64) oblivious_inter_kernel(const ObShapView vi
         const int e0 = v.elem_off[t];
         const int m = v.elem_off[t + 1] - e0;  // wave-uniform, as everything read below
         if (m == 0) continue;
-        const uint32_t idx = ob_shap_leaf_index(v, r, t, [](int, uint32_t, uint32_t) {});
+        const uint32_t idx = ob_shap_leaf_index<CAT>(v, r, t, [](int, uint32_t, uint32_t) {});
         const int nleaf = 1 << (v.split_off[t + 1] - v.split_off[t]);
         const uint2 *el = v.elems + e0;
         const float2 *zz = v.zz + v.zz_off[t];
@@ -577,8 +579,8 @@ __device__ __forceinline__ void ob_iv_tree(const ObShapRows<KB, INPLACE> &r, con
 
 // Interventional TreeSHAP: grid (row tiles, class blocks), one wave per workgroup.  Dynamic LDS: (not INPLACE) [U][64] tile |
 // [64][S] slab, then [kObIvTable] weights.  v.bias is the bias column of the background.
-template <int KB, bool INPLACE>
-__global__ void __launch_bounds__(64) oblivious_iv_kernel(const ObShapView v, const ObIvView b, float *__restrict__ phi,
+template <int KB, bool INPLACE, bool CAT = false>
+__global__ void __launch_bounds__(64) oblivious_iv_kernel(const ObCatView<CAT> v, const ObIvView b, float *__restrict__ phi,
                                                           const float *__restrict__ data, size_t rows)
 {
     extern __shared__ __attribute__((aligned(16))) float ob_shap_smem[];
@@ -589,7 +591,7 @@ __global__ void __launch_bounds__(64) oblivious_iv_kernel(const ObShapView v, co
         const int e0 = v.elem_off[t];
         const int m = v.elem_off[t + 1] - e0;  // wave-uniform, as everything read below but the leaves
         if (m == 0) continue;                  // a single leaf: all of it is bias
-        const uint32_t idx = ob_shap_leaf_index(v, r, t, [](int, uint32_t, uint32_t) {});
+        const uint32_t idx = ob_shap_leaf_index<CAT>(v, r, t, [](int, uint32_t, uint32_t) {});
         const uint2 *el = v.elems + e0;
         const int o0 = b.occ_off[t];
         const int nocc = b.occ_off[t + 1] - o0;
@@ -613,6 +615,122 @@ __global__ void __launch_bounds__(64) oblivious_iv_kernel(const ObShapView v, co
     }
     ob_shap_end<KB, INPLACE>(v, r, phi);
 }
+
+// ---- launches.  Each translation unit instantiates its own CAT; K == 1 takes the single-class kernels. ----
+template <class Fn>
+inline void ob_with_classes_and_form(int K, bool inplace, Fn &&fn)
+{
+    auto with_form = [&](auto kb) {
+        if (inplace) fn(kb, std::true_type{});
+        else fn(kb, std::false_type{});
+    };
+    if (K == 1) with_form(std::integral_constant<int, 1>{});
+    else with_form(std::integral_constant<int, kObShapClasses>{});
+}
+
+// TreeSHAP (flag == TAHOE_CREATE_CONTRIBS) or Saabas
+template <bool CAT>
+void ob_launch_shap(unsigned flag, int K, bool inplace, dim3 grid, size_t lds_bytes, hipStream_t stream, const ObShapView &view,
+                    const uint32_t *cat_pool, uint32_t cat_words, float *phi_dev, const float *data_dev, size_t rows)
+{
+    const ObCatView<CAT> v = ob_cat_view<CAT>(view, cat_pool, cat_words);
+    ob_with_classes_and_form(K, inplace, [&](auto kb, auto ip) {
+        constexpr int KB = decltype(kb)::value;
+        constexpr bool IP = decltype(ip)::value;
+        if (flag == TAHOE_CREATE_CONTRIBS)
+            hipLaunchKernelGGL((oblivious_shap_kernel<KB, IP, CAT>), grid, dim3(64), lds_bytes, stream, v, phi_dev, data_dev, rows);
+        else
+            hipLaunchKernelGGL((oblivious_approx_kernel<KB, IP, CAT>), grid, dim3(64), lds_bytes, stream, v, phi_dev, data_dev, rows);
+    });
+}
+
+template <bool CAT>
+void ob_launch_iv(int K, bool inplace, dim3 grid, size_t lds_bytes, hipStream_t stream, const ObShapView &view,
+                  const uint32_t *cat_pool, uint32_t cat_words, const ObIvView &b, float *phi_dev, const float *data_dev, size_t rows)
+{
+    const ObCatView<CAT> v = ob_cat_view<CAT>(view, cat_pool, cat_words);
+    ob_with_classes_and_form(K, inplace, [&](auto kb, auto ip) {
+        hipLaunchKernelGGL((oblivious_iv_kernel<decltype(kb)::value, decltype(ip)::value, CAT>), grid, dim3(64), lds_bytes, stream, v, b,
+                           phi_dev, data_dev, rows);
+    });
+}
+
+// The LDS forms may need more than the default 64 KiB: those of TreeSHAP and Saabas, or (iv) of the interventional kernel
+template <bool CAT>
+hipError_t ob_allow_lds(bool iv, int limit)
+{
+    hipError_t e = hipSuccess;
+    if (iv) {
+        if ((e = allow_max_lds(reinterpret_cast<const void *>(&oblivious_iv_kernel<1, false, CAT>), limit)) != hipSuccess) return e;
+        return allow_max_lds(reinterpret_cast<const void *>(&oblivious_iv_kernel<kObShapClasses, false, CAT>), limit);
+    }
+    if ((e = allow_max_lds(reinterpret_cast<const void *>(&oblivious_shap_kernel<1, false, CAT>), limit)) != hipSuccess ||
+        (e = allow_max_lds(reinterpret_cast<const void *>(&oblivious_shap_kernel<kObShapClasses, false, CAT>), limit)) != hipSuccess ||
+        (e = allow_max_lds(reinterpret_cast<const void *>(&oblivious_approx_kernel<1, false, CAT>), limit)) != hipSuccess)
+        return e;
+    return allow_max_lds(reinterpret_cast<const void *>(&oblivious_approx_kernel<kObShapClasses, false, CAT>), limit);
+}
+
+// CAT == true lives in oblivious_shap_cat.hip, which compiles this file's device code with TAHOE_OBLIVIOUS_SHAP_CAT_UNIT defined, so
+// that the two halves of the kernels build side by side
+extern template void ob_launch_shap<true>(unsigned, int, bool, dim3, size_t, hipStream_t, const ObShapView &, const uint32_t *, uint32_t,
+                                          float *, const float *, size_t);
+void ob_launch_inter_cat(int K, dim3 grid, hipStream_t stream, const ObShapView &view, const uint32_t *cat_pool, uint32_t cat_words,
+                         float *out_dev, const float *data_dev, size_t rows);
+extern template void ob_launch_iv<true>(int, bool, dim3, size_t, hipStream_t, const ObShapView &, const uint32_t *, uint32_t,
+                                        const ObIvView &, float *, const float *, size_t);
+extern template hipError_t ob_allow_lds<true>(bool, int);
+
+#ifdef TAHOE_OBLIVIOUS_SHAP_CAT_UNIT
+template void ob_launch_shap<true>(unsigned, int, bool, dim3, size_t, hipStream_t, const ObShapView &, const uint32_t *, uint32_t,
+                                   float *, const float *, size_t);
+template void ob_launch_iv<true>(int, bool, dim3, size_t, hipStream_t, const ObShapView &, const uint32_t *, uint32_t, const ObIvView &,
+                                 float *, const float *, size_t);
+template hipError_t ob_allow_lds<true>(bool, int);
+
+void ob_launch_inter_cat(int K, dim3 grid, hipStream_t stream, const ObShapView &view, const uint32_t *cat_pool, uint32_t cat_words,
+                         float *out_dev, const float *data_dev, size_t rows)
+{
+    const ObCatView<true> v = ob_cat_view<true>(view, cat_pool, cat_words);
+    if (K == 1) hipLaunchKernelGGL((oblivious_inter_kernel<1, true>), grid, dim3(64), 0, stream, v, out_dev, data_dev, rows);
+    else hipLaunchKernelGGL((oblivious_inter_kernel<kObShapClasses, true>), grid, dim3(64), 0, stream, v, out_dev, data_dev, rows);
+}
+#endif
+
+}  // namespace tahoe
+
+#ifndef TAHOE_OBLIVIOUS_SHAP_CAT_UNIT  // from here on: the tables and the entry points
+
+struct tahoe_oshap {
+    tahoe::InnerNode *splits = nullptr;
+    int32_t *used = nullptr;
+    uint2 *elems = nullptr;
+    int32_t *elem_off = nullptr;
+    float2 *zz = nullptr;
+    int64_t *zz_off = nullptr;
+    uint32_t *zmask = nullptr;
+    float *delta = nullptr;
+    float *bias = nullptr;
+    tahoe::InnerNode *splits_col = nullptr;  // TAHOE_CREATE_INTERACTIONS: splits and elems with id = the column in either form
+    uint2 *elems_col = nullptr;
+    bool contribs = false, approx = false, inter = false;
+    bool inplace = false;  // accumulate in phi_dev (else in LDS)
+    size_t lds_bytes = 0;
+    tahoe::ObShapView view{};
+    tahoe::ObShapView inter_view{};  // view with splits_col and elems_col
+    // TAHOE_CREATE_OBLIVIOUS_INTERVENTIONAL: the weight tables (create); the background (tahoe_forest_set_background): occupied
+    // leaves, per-tree offsets, bias column
+    bool iv = false;
+    size_t iv_lds_bytes = 0;  // oblivious_iv_kernel: lds_bytes, then the weight tables
+    float *wtab = nullptr;
+    uint2 *occ = nullptr;
+    int32_t *occ_off = nullptr;
+    float *iv_bias = nullptr;
+    size_t bg_rows = 0;   // 0: no background
+    size_t bg_bytes = 0;  // device bytes of the three background buffers (counted in tahoe_forest::device_bytes)
+};
+
+namespace tahoe {
 
 tahoe_status oblivious_shap_validate(const int32_t *depths, int num_trees, const float *leaf_covers)
 {
@@ -663,7 +781,7 @@ int tree_elements(const InnerNode *ts, int D, uint32_t *fid, uint32_t *mask)
 {
     int m = 0;
     for (int l = 0; l < D; ++l) {
-        const uint32_t fl = ts[l].meta & kMetaFidMask;
+        const uint32_t fl = ob_split_fid(ts[l].meta);
         int e = 0;
         while (e < m && fid[e] != fl) ++e;
         if (e == m) {
@@ -704,7 +822,7 @@ tahoe_status oblivious_shap_build(tahoe_forest *f, const ObliviousSource &src, u
     // ---- the features the forest uses, and the form ----
     std::vector<int32_t> used;
     used.reserve(splits.size());
-    for (const InnerNode &n : splits) used.push_back((int32_t)(n.meta & kMetaFidMask));
+    for (const InnerNode &n : splits) used.push_back((int32_t)ob_split_fid(n.meta));
     std::sort(used.begin(), used.end());
     used.erase(std::unique(used.begin(), used.end()), used.end());
     const int U = (int)used.size();
@@ -718,8 +836,10 @@ tahoe_status oblivious_shap_build(tahoe_forest *f, const ObliviousSource &src, u
         return sh->inplace ? fid : (uint32_t)(std::lower_bound(used.begin(), used.end(), (int32_t)fid) - used.begin());
     };
     std::vector<InnerNode> h_splits(splits.size());
-    for (size_t s = 0; s < splits.size(); ++s)
-        h_splits[s] = InnerNode{splits[s].thr, id_of(splits[s].meta & kMetaFidMask) | (splits[s].meta & (1u << 31))};
+    for (size_t s = 0; s < splits.size(); ++s) {  // the id takes the fid's place; def_left, the kind bits and the set word / pool index stay
+        const uint32_t fid = ob_split_fid(splits[s].meta);
+        h_splits[s] = InnerNode{splits[s].thr, id_of(fid) | (splits[s].meta & ~fid)};
+    }
 
     // ---- per tree: elements, zero fractions, deltas, E_t ----
     std::vector<uint2> h_elems;
@@ -847,19 +967,13 @@ tahoe_status oblivious_shap_build(tahoe_forest *f, const ObliviousSource &src, u
         if ((s = hip_status(upload(&sh->wtab, h_w, &f->device_bytes), "upload(interventional weights)"))) return s;
         sh->iv_lds_bytes = sh->lds_bytes + kObIvTable * sizeof(float);  // the tile and slab of the handle's form, then the tables
         if (!sh->inplace) {
-            hipError_t e = hipSuccess;
-            if ((e = allow_max_lds(reinterpret_cast<const void *>(&oblivious_iv_kernel<1, false>), f->lds_limit)) != hipSuccess ||
-                (e = allow_max_lds(reinterpret_cast<const void *>(&oblivious_iv_kernel<kObShapClasses, false>), f->lds_limit)) != hipSuccess)
-                return hip_status(e, "hipFuncSetAttribute(oblivious_iv)");
+            const hipError_t e = o->cats ? ob_allow_lds<true>(true, f->lds_limit) : ob_allow_lds<false>(true, f->lds_limit);
+            if (e != hipSuccess) return hip_status(e, "hipFuncSetAttribute(oblivious_iv)");
         }
     }
     if (!sh->inplace) {  // the LDS forms may need more than the default 64 KiB
-        hipError_t e = hipSuccess;
-        if ((e = allow_max_lds(reinterpret_cast<const void *>(&oblivious_shap_kernel<1, false>), f->lds_limit)) != hipSuccess ||
-            (e = allow_max_lds(reinterpret_cast<const void *>(&oblivious_shap_kernel<kObShapClasses, false>), f->lds_limit)) != hipSuccess ||
-            (e = allow_max_lds(reinterpret_cast<const void *>(&oblivious_approx_kernel<1, false>), f->lds_limit)) != hipSuccess ||
-            (e = allow_max_lds(reinterpret_cast<const void *>(&oblivious_approx_kernel<kObShapClasses, false>), f->lds_limit)) != hipSuccess)
-            return hip_status(e, "hipFuncSetAttribute(oblivious_shap)");
+        const hipError_t e = o->cats ? ob_allow_lds<true>(false, f->lds_limit) : ob_allow_lds<false>(false, f->lds_limit);
+        if (e != hipSuccess) return hip_status(e, "hipFuncSetAttribute(oblivious_shap)");
     }
     return TAHOE_OK;
 }
@@ -894,21 +1008,13 @@ tahoe_status oblivious_predict_shap(tahoe_forest *f, unsigned flag, float *phi_d
     DeviceGuard on_device(f->device);
     const int K = f->num_classes;
     const dim3 grid((unsigned)((rows + 63) / 64), (unsigned)((K + kObShapClasses - 1) / kObShapClasses));
-    auto launch = [&](auto kb, auto inplace) {
-        constexpr int KB = decltype(kb)::value;
-        constexpr bool IP = decltype(inplace)::value;
-        if (flag == TAHOE_CREATE_CONTRIBS)
-            hipLaunchKernelGGL((oblivious_shap_kernel<KB, IP>), grid, dim3(64), sh->lds_bytes, stream, sh->view, phi_dev, data_dev, rows);
-        else
-            hipLaunchKernelGGL((oblivious_approx_kernel<KB, IP>), grid, dim3(64), sh->lds_bytes, stream, sh->view, phi_dev, data_dev,
-                               rows);
-    };
-    auto with_form = [&](auto kb) {
-        if (sh->inplace) launch(kb, std::true_type{});
-        else launch(kb, std::false_type{});
-    };
-    if (K == 1) with_form(std::integral_constant<int, 1>{});
-    else with_form(std::integral_constant<int, kObShapClasses>{});
+    // a handle without sets launches the instantiations without the kind test
+    const tahoe_ostate *o = f->ob;
+    if (o->cats)
+        ob_launch_shap<true>(flag, K, sh->inplace, grid, sh->lds_bytes, stream, sh->view, o->cat_pool, o->cat_words, phi_dev, data_dev,
+                             rows);
+    else
+        ob_launch_shap<false>(flag, K, sh->inplace, grid, sh->lds_bytes, stream, sh->view, nullptr, 0u, phi_dev, data_dev, rows);
     TAHOE_HIP_TRY(hipGetLastError());
     return TAHOE_OK;
 }
@@ -923,7 +1029,9 @@ tahoe_status oblivious_predict_interactions(tahoe_forest *f, float *out_dev, con
     DeviceGuard on_device(f->device);
     const int K = f->num_classes;
     const dim3 grid((unsigned)((rows + 63) / 64), (unsigned)((K + kObShapClasses - 1) / kObShapClasses));
-    if (K == 1) hipLaunchKernelGGL((oblivious_inter_kernel<1>), grid, dim3(64), 0, stream, sh->inter_view, out_dev, data_dev, rows);
+    const tahoe_ostate *o = f->ob;
+    if (o->cats) ob_launch_inter_cat(K, grid, stream, sh->inter_view, o->cat_pool, o->cat_words, out_dev, data_dev, rows);
+    else if (K == 1) hipLaunchKernelGGL((oblivious_inter_kernel<1>), grid, dim3(64), 0, stream, sh->inter_view, out_dev, data_dev, rows);
     else hipLaunchKernelGGL((oblivious_inter_kernel<kObShapClasses>), grid, dim3(64), 0, stream, sh->inter_view, out_dev, data_dev, rows);
     TAHOE_HIP_TRY(hipGetLastError());
     return TAHOE_OK;
@@ -1050,18 +1158,13 @@ tahoe_status oblivious_predict_interventional(tahoe_forest *f, float *phi_dev, c
     v.bias = sh->iv_bias;
     const ObIvView b{sh->occ, sh->occ_off, sh->wtab, (float)sh->bg_rows};
     const dim3 grid((unsigned)((rows + 63) / 64), (unsigned)((K + kObShapClasses - 1) / kObShapClasses));
-    auto launch = [&](auto kb, auto inplace) {
-        hipLaunchKernelGGL((oblivious_iv_kernel<decltype(kb)::value, decltype(inplace)::value>), grid, dim3(64), sh->iv_lds_bytes, stream,
-                           v, b, phi_dev, data_dev, rows);
-    };
-    auto with_form = [&](auto kb) {
-        if (sh->inplace) launch(kb, std::true_type{});
-        else launch(kb, std::false_type{});
-    };
-    if (K == 1) with_form(std::integral_constant<int, 1>{});
-    else with_form(std::integral_constant<int, kObShapClasses>{});
+    const tahoe_ostate *o = f->ob;
+    if (o->cats) ob_launch_iv<true>(K, sh->inplace, grid, sh->iv_lds_bytes, stream, v, o->cat_pool, o->cat_words, b, phi_dev, data_dev, rows);
+    else ob_launch_iv<false>(K, sh->inplace, grid, sh->iv_lds_bytes, stream, v, nullptr, 0u, b, phi_dev, data_dev, rows);
     TAHOE_HIP_TRY(hipGetLastError());
     return TAHOE_OK;
 }
 
 }  // namespace tahoe
+
+#endif  // TAHOE_OBLIVIOUS_SHAP_CAT_UNIT

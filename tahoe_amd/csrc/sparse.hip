@@ -1229,8 +1229,9 @@ void sparse_cat_view(const tahoe_forest *f, const uint32_t **pool, uint32_t *poo
     *pool_words = f->sp->cat_words;
 }
 
-// The argument checks of the categorical splits (TAHOE_ERR_INVALID_ARG), in the header's order.
-static tahoe_status check_cat_args(const tahoe_categorical_splits *c, int num_nodes)
+// The argument checks of the categorical splits (TAHOE_ERR_INVALID_ARG), in the header's order; num_nodes: the records a split may
+// name (the nodes of a sparse forest, the (tree, level) records of an oblivious one).
+tahoe_status check_cat_args(const tahoe_categorical_splits *c, int num_nodes)
 {
     const int ns = c->num_splits;
     if (ns < 0 || ns > num_nodes)

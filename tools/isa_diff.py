@@ -20,7 +20,9 @@ import sys
 FLAGGED = ("direct_kernel", "rowtile_kernel", "qring_kernel", "qwide_kernel",  # kernels that carry the appended flag
            "sparse_kernel", "sparse_top_kernel", "sparse_q_kernel",
            "contribs_kernel", "contribs_spare_kernel", "interactions_kernel", "background_mask_kernel",  # SETS / CAT
-           "interventional_kernel", "approx_kernel")
+           "interventional_kernel", "approx_kernel",
+           "oblivious_tile_kernel", "oblivious_direct_kernel", "oblivious_shap_kernel", "oblivious_inter_kernel",
+           "oblivious_iv_kernel")  # CAT
 
 
 def functions(path):
