@@ -386,7 +386,8 @@ tahoe_status tahoe_sparse_forest_create(tahoe_forest **out, const int32_t *trees
  *    node the covers of nodes left_idx and left_idx + 1 must be finite and >= 0 with a positive sum (TAHOE_ERR_INVALID_FOREST
  *    naming the tree and node), and no reachable leaf's path may have more than 31 distinct features (TAHOE_ERR_UNSUPPORTED
  *    naming the tree; a deep path that repeats features is fine).  The handle then serves the four TreeSHAP calls.  Without
- *    the flag covers is ignored and may be NULL.
+ *    the flag covers is ignored and may be NULL.  TAHOE_CREATE_PARTIAL_DEPENDENCE (below) is accepted too, alone or beside them:
+ *    it needs covers, checks them and the depth as stated there, and serves tahoe_forest_predict_partial_dependence.
  * num_classes == 1 with flags == 0 gives a handle that behaves exactly like tahoe_sparse_forest_create. */
 tahoe_status tahoe_sparse_forest_create_ex(tahoe_forest **out, const int32_t *trees, const tahoe_sparse_node *nodes,
                                            const float *covers, const tahoe_forest_params *params, int num_classes,
@@ -449,6 +450,46 @@ typedef struct {
 tahoe_status tahoe_sparse_forest_create_cat(tahoe_forest **out, const int32_t *trees, const tahoe_sparse_node *nodes,
                                             const float *covers, const tahoe_forest_params *params, int num_classes,
                                             unsigned flags, const tahoe_categorical_splits *cats);
+
+/* ---- partial dependence: the model as a function of a few target features, the others averaged out by the node covers.  What
+ * scikit-learn's partial_dependence(method="recursion") computes for gradient boosting, random forests and single trees. ----
+ * A create flag for tahoe_sparse_forest_create_ex and tahoe_sparse_forest_create_cat (every other create keeps its refusal of an
+ * unknown flag), alone or with any flag they accept; a dense model takes it through tahoe_dense_to_sparse_ex, which keeps the
+ * covers of dense_node_t.weight.  It needs covers (NULL: TAHOE_ERR_INVALID_ARG) and goes with categorical splits without
+ * TAHOE_CREATE_CAT_CONTRIBS (nothing here is a path element).  Checked, before a device is touched, after the checks the other
+ * flags make: at every reachable internal node the covers of both children finite and >= 0 with a positive sum, and their float32
+ * sum finite (TAHOE_ERR_INVALID_FOREST naming the tree and node); no reachable leaf more than 32 edges below its root
+ * (TAHOE_ERR_UNSUPPORTED naming the tree: the stack depth of the walk).  No limit on the features of a path or on num_cols.
+ * The handle keeps, counted in tahoe_forest_info.device_bytes: 8 bytes per node (the fractions below; max(num_nodes, 1) nodes)
+ * and a workspace of 4 x num_trees x chunk bytes, chunk = the grid points one pass takes: a multiple of 64, at least 64, by
+ * default what keeps the workspace near 32 MiB; the environment variable TAHOE_PD_CHUNK_ROWS, read at create, sets it (rounded
+ * up to a multiple of 64).  A handle created without the flag is byte for byte what it was. */
+#define TAHOE_CREATE_PARTIAL_DEPENDENCE 0x800u
+/* pd_dev[g * C + c] (grid_rows x C floats, C = the handle's classes) = the partial dependence of class c at grid point g.
+ * targets: host memory, num_targets distinct column ids, num_targets in [0, 32]; grid_dev: device memory, row-major grid_rows x
+ * num_targets float32, column j the value of feature targets[j] (num_targets == 0: ignored, may be NULL).
+ * The bits.  At create, per internal node with child covers cl, cr: tot = cl + cr, fl = cl / tot, fr = cr / tot, three IEEE float32
+ * operations.  For grid point g and tree t, start at the root with w = 1.0f and acc = +0.0f.  At an internal node whose feature is
+ * a target take the branch tahoe_forest_predict takes for the grid value of that feature (the missing sentinel's default branch,
+ * NaN left, x >= val right, the set rule of tahoe_sparse_forest_create_cat at a categorical node), w unchanged.  At any other
+ * internal node visit the left subtree with w * fl, then the right subtree with w * fr (one float32 multiply each); a child whose
+ * fraction is exactly 0.0f is not visited.  At a leaf acc = acc + (w * val), the product rounded to float32 before the add (no
+ * fused multiply-add).  Leaves are added in depth-first order, left before right.  pd[g][c] is the float32 sum from +0.0f of acc
+ * over the trees of class c (t % C == c) in increasing t.  So: where every feature a tree splits on is a target, pd equals
+ * tahoe_forest_predict_raw of that row bit for bit; a grid point's value does not depend on grid_rows, on its position in the
+ * grid, on the chunk or on the call; with no targets every row gets the forest's cover-weighted mean.
+ * The values are raw sums as tahoe_forest_predict_raw gives them: no AVG division, no global_bias, no output transform
+ * (tahoe_transform_preds applies those).  Asynchronous on `stream`; the call allocates nothing, the targets travel as kernel
+ * arguments, and a grid larger than the chunk runs chunk after chunk on the stream.
+ * Refusals, in this order, nothing launched: f NULL: TAHOE_ERR_INVALID_ARG; a dense, multi-class dense, oblivious or vector-leaf
+ * handle: TAHOE_ERR_UNSUPPORTED naming the call and the handle kind; a sparse handle created without
+ * TAHOE_CREATE_PARTIAL_DEPENDENCE: TAHOE_ERR_UNSUPPORTED naming the flag; num_targets outside [0, 32], targets NULL with
+ * num_targets > 0, a target outside [0, num_cols) or a repeated one: TAHOE_ERR_INVALID_ARG naming the index; then grid_rows == 0:
+ * TAHOE_OK; pd_dev NULL, or grid_dev NULL with num_targets > 0: TAHOE_ERR_INVALID_ARG; grid_rows x num_targets or grid_rows x C
+ * floats past size_t: TAHOE_ERR_INVALID_ARG. */
+tahoe_status tahoe_forest_predict_partial_dependence(tahoe_forest *f, float *pd_dev, const int32_t *targets, int num_targets,
+                                                     const float *grid_dev, size_t grid_rows, void *stream);
+
 /* ---- oblivious (symmetric) forests: CatBoost models.  Every node of a level shares one split, so a tree of depth D is D
  * (feature, border) records and a table of 2^D leaves; no counterpart in the reference. ---- */
 typedef struct {

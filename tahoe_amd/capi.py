@@ -42,6 +42,7 @@ CREATE_INTERACTIONS = 0x40  # tahoe_oblivious_forest_create_ex: SHAP interaction
 CREATE_INTERVENTIONAL = 0x80  # tahoe_vector_forest_create_ex: interventional TreeSHAP (tahoe_forest_set_background), no covers needed
 CREATE_VECTOR_INTERACTIONS = 0x100  # tahoe_vector_forest_create_ex, with CREATE_CONTRIBS: tahoe_forest_predict_interactions
 CREATE_OBLIVIOUS_INTERVENTIONAL = 0x200  # tahoe_oblivious_forest_create_ex: interventional TreeSHAP (tahoe_forest_set_background), no covers needed
+CREATE_PARTIAL_DEPENDENCE = 0x800  # tahoe_sparse_forest_create_ex / _cat: partial dependence (tahoe_forest_predict_partial_dependence); needs covers
 CREATE_VECTOR_APPROX = 0x400  # tahoe_vector_forest_create_ex: Saabas contributions (tahoe_forest_predict_contribs_approx); needs covers
 STRATEGY_NAMES = {1: "direct", 2: "rowtile", 3: "tileblock", 4: "tilering", 5: "qring"}
 STATUS_NAMES = {
@@ -146,6 +147,7 @@ _PROTOS = {
     "tahoe_forest_set_background": (_i, [_vp, _vp, _sz, _vp]),
     "tahoe_forest_predict_contribs_interventional": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "tahoe_forest_predict_contribs_approx": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "tahoe_forest_predict_partial_dependence": (_i, [_vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "tahoe_sparse_forest_create": (_i, [C.POINTER(_vp), _vp, _vp, C.POINTER(ForestParams)]),
     "tahoe_sparse_forest_create_ex": (_i, [C.POINTER(_vp), _vp, _vp, _vp, C.POINTER(ForestParams), _i, C.c_uint]),
     "tahoe_sparse_forest_create_cat": (_i, [C.POINTER(_vp), _vp, _vp, _vp, C.POINTER(ForestParams), _i, C.c_uint,
@@ -603,6 +605,37 @@ class Forest:
         bias is the last column.  Needs approx_contribs=True."""
         return self._shap_out("tahoe_forest_predict_contribs_approx", data, 1, out, stream)
 
+    def partial_dependence(self, features, grid, out=None, stream=None):
+        """Partial dependence on the target columns `features` (tahoe_forest_predict_partial_dependence; scikit-learn's
+        partial_dependence(method="recursion")): raw sums, float32 [G], or [G, num_classes] on a multi-class handle.  grid: a
+        float32 CUDA tensor [G, len(features)], column j the value of features[j]; or a sequence of 1-D axes (tensors or arrays),
+        one per feature, whose Cartesian product (first axis slowest) is the grid -- the result then has the shape axes...
+        (, num_classes), scikit-learn's layout.  Needs a SparseForest with partial_dependence=True."""
+        import torch
+
+        feats = np.ascontiguousarray(np.asarray(features, dtype=np.int32).reshape(-1))
+        nt = int(feats.size)
+        axes_shape = None
+        if not (torch.is_tensor(grid) and grid.dim() == 2) and not (isinstance(grid, np.ndarray) and grid.ndim == 2):
+            axes = [torch.as_tensor(a, dtype=torch.float32).reshape(-1).cuda() for a in grid]
+            assert len(axes) == nt, (len(axes), nt)
+            axes_shape = tuple(int(a.numel()) for a in axes)
+            grid = (torch.cartesian_prod(*axes).reshape(-1, nt) if nt else torch.empty((1, 0), dtype=torch.float32, device="cuda"))
+        grid = torch.as_tensor(grid, dtype=torch.float32)
+        grid = grid.cuda().contiguous() if not grid.is_cuda else grid.contiguous()
+        assert grid.dim() == 2 and grid.shape[1] == nt, (tuple(grid.shape), nt)
+        rows = grid.shape[0]
+        shape = self._out_shape(rows)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=grid.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.numel() == int(np.prod(shape))
+        _check(lib.tahoe_forest_predict_partial_dependence(self._h, _ptr(out), feats.ctypes.data if nt else None, nt,
+                                                           _ptr(grid) if nt and rows else None, rows, _stream(stream)),
+               "tahoe_forest_predict_partial_dependence")
+        if axes_shape is not None:
+            return out.reshape(axes_shape + ((self.num_classes,) if self.num_classes > 1 else ()))
+        return out
+
     def set_background(self, bg, stream=None) -> None:
         """Background data set of interventional TreeSHAP (tahoe_forest_set_background): float32 [B, num_cols], contiguous, on
         the handle's device; None clears it.  Synchronous; the handle keeps what it needs, so `bg` may be freed afterwards.
@@ -749,23 +782,27 @@ class SparseForest(Forest):
     t % num_classes, contribs=True builds the TreeSHAP path tables from the covers and approx_contribs=True the Saabas node
     deltas.  categories ({node index: category ids}) makes those nodes categorical splits, members going right unless the
     node is in members_left (tahoe_sparse_forest_create_cat; the node's val is then ignored).  categories together with
-    contribs / approx_contribs sets TAHOE_CREATE_CAT_CONTRIBS: the four explanation calls then follow the category sets."""
+    contribs / approx_contribs sets TAHOE_CREATE_CAT_CONTRIBS: the four explanation calls then follow the category sets.
+    partial_dependence=True (TAHOE_CREATE_PARTIAL_DEPENDENCE; needs covers) serves Forest.partial_dependence."""
 
     def __init__(self, nodes: np.ndarray, trees: np.ndarray, num_cols: int, missing: float = 0.0, output: int = OUT_RAW,
                  threshold: float = 0.0, global_bias: float = 0.0, covers=None, num_classes: int = 1,
-                 contribs: bool = False, approx_contribs: bool = False, categories=None, members_left=()):
+                 contribs: bool = False, approx_contribs: bool = False, categories=None, members_left=(),
+                 partial_dependence: bool = False):
         nodes = np.ascontiguousarray(nodes, dtype=SPARSE_NODE_DTYPE)
         trees = np.ascontiguousarray(trees, dtype=np.int32)
         self.params = ForestParams(int(nodes.size), 0, int(trees.size), num_cols, 0, output, threshold, global_bias, 0,
                                    missing)
         self._h = _vp()
         flags = (CREATE_CONTRIBS if contribs else 0) | (CREATE_APPROX_CONTRIBS if approx_contribs else 0)
+        shap_flags = flags
+        flags |= CREATE_PARTIAL_DEPENDENCE if partial_dependence else 0
         if categories:
             cv = None if covers is None else np.ascontiguousarray(covers, dtype=np.float32)
             if cv is not None and cv.size != nodes.size:
                 raise ValueError("covers.size != nodes.size")
             cats, _keep = pack_categorical(categories, members_left)
-            if flags:  # the path elements / the Saabas walk then test category sets
+            if shap_flags:  # the path elements / the Saabas walk then test category sets
                 flags |= CREATE_CAT_CONTRIBS
             _check(lib.tahoe_sparse_forest_create_cat(C.byref(self._h), trees.ctypes.data if trees.size else None,
                                                       nodes.ctypes.data if nodes.size else None,

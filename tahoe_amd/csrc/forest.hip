@@ -1118,6 +1118,7 @@ static tahoe_knobs read_knobs()
     k.oblivious_shap_inplace = num("TAHOE_OBLIVIOUS_SHAP_INPLACE", 0) != 0;
     k.vector_shap_kb = num("TAHOE_VECTOR_SHAP_KB", k.vector_shap_kb);
     k.vector_shap_grid = num("TAHOE_VECTOR_SHAP_GRID", k.vector_shap_grid);
+    k.pd_chunk_rows = num("TAHOE_PD_CHUNK_ROWS", k.pd_chunk_rows);
     return k;
 }
 
@@ -1515,6 +1516,7 @@ void tahoe_forest_destroy(tahoe_forest *f)
     interventional_destroy(f);
     contribs_destroy(f);
     approx_destroy(f);
+    pd_destroy(f);
     for (hipEvent_t e : f->ev_start) (void)hipEventDestroy(e);
     for (hipEvent_t e : f->ev_mid) (void)hipEventDestroy(e);
     for (hipEvent_t e : f->ev_stop) (void)hipEventDestroy(e);

@@ -21,6 +21,7 @@ struct tahoe_istate;  // background of interventional TreeSHAP (tahoe_forest_set
 struct tahoe_astate;  // Saabas node deltas (TAHOE_CREATE_APPROX_CONTRIBS), owned by approx.hip
 struct tahoe_ostate;  // oblivious (symmetric) forest, owned by oblivious.hip
 struct tahoe_vstate;  // vector-leaf forest, owned by vector.hip (its TreeSHAP tables by vector_shap.hip)
+struct tahoe_pdstate; // cover fractions + workspace of TAHOE_CREATE_PARTIAL_DEPENDENCE, owned by partial_dependence.hip
 
 namespace tahoe {
 
@@ -83,6 +84,7 @@ struct tahoe_knobs {
     int csr_fused = -1;           // TAHOE_CSR_FUSED: under AUTO, 0 = never the fused CSR tile kernels, 1 = wherever one exists, -1 = the rule
     bool oblivious_shap_inplace = false;  // TAHOE_OBLIVIOUS_SHAP_INPLACE = 1: an oblivious handle's explanations accumulate in phi_dev
     int vector_shap_kb = 0;       // TAHOE_VECTOR_SHAP_KB = 1 / 2 / 4 / 8: force the class block of a vector-leaf handle's TreeSHAP kernels
+    int pd_chunk_rows = 0;        // TAHOE_PD_CHUNK_ROWS >= 1: grid points per chunk of tahoe_forest_predict_partial_dependence (rounded up to 64s)
     int vector_shap_grid = -1;    // TAHOE_VECTOR_SHAP_GRID: ... 0 = a workgroup loops over its class blocks, 1 = gridDim.y runs over them, -1 = the rule
 };
 
@@ -118,6 +120,7 @@ struct tahoe_forest {
     tahoe_ostate *ob = nullptr;    // non-null: this handle is an oblivious forest (oblivious.hip); the dense views are unused,
                                    // num_classes is the leaf dimension K and class_trees = num_trees (every tree feeds every class)
     tahoe_vstate *vl = nullptr;    // non-null: this handle is a vector-leaf forest (vector.hip); num_classes and class_trees as with ob
+    tahoe_pdstate *pd = nullptr;   // non-null: a sparse handle created with TAHOE_CREATE_PARTIAL_DEPENDENCE (partial_dependence.hip)
     size_t device_bytes = 0;
     // Multi-class handle (tahoe_forest_create_multiclass): the trees are stored class-major -- internal tree p belongs to class
     // p / class_trees and is original tree (p % class_trees) * num_classes + p / class_trees -- and every consumer writes
@@ -651,6 +654,12 @@ tahoe_status approx_build(tahoe_forest *f, const tahoe_dense_node *nodes, const 
                           const std::vector<unsigned char> &h_real);
 tahoe_status approx_build_sparse(tahoe_forest *f, const int32_t *trees, const tahoe_sparse_node *nodes, const float *covers);
 void approx_destroy(tahoe_forest *f);
+// partial dependence (partial_dependence.hip).  pd_validate_sparse: the checks of TAHOE_CREATE_PARTIAL_DEPENDENCE on the caller's
+// structure-checked trees -- covers, their float32 sums, no leaf deeper than 32 edges -- before a device is touched;
+// pd_build_sparse: the per-node cover fractions in the stored node order and the workspace, both counted in device_bytes
+tahoe_status pd_validate_sparse(const int32_t *trees, const tahoe_sparse_node *nodes, const float *covers, const tahoe_forest_params *p);
+tahoe_status pd_build_sparse(tahoe_forest *f, const int32_t *trees, const tahoe_sparse_node *nodes, const float *covers);
+void pd_destroy(tahoe_forest *f);
 // The node means of one sparse-layout tree of n nodes (tn, with its covers tc), bottom-up in float64: children lie after their
 // parent; leaf(i) is the value of leaf i.  The one definition behind the deltas of approx_build_sparse and of a vector-leaf
 // handle (vector_approx.hip), which must agree in every bit.

@@ -1319,6 +1319,9 @@ static tahoe_status create_sparse(tahoe_forest **out, const int32_t *trees, cons
         const tahoe_status cs = contribs_validate_sparse(trees, nodes, covers, p, (flags & TAHOE_CREATE_CONTRIBS) != 0);
         if (cs != TAHOE_OK) return cs;
     }
+    if (flags & TAHOE_CREATE_PARTIAL_DEPENDENCE) {  // its covers and its depth limit, on the caller's nodes (no path-feature limit)
+        if (const tahoe_status ps = pd_validate_sparse(trees, nodes, covers, p)) return ps;
+    }
     ForestPtr f;
     if (const tahoe_status s = open_handle(p, num_classes, f)) return s;
     tahoe_sstate *sp = new (std::nothrow) tahoe_sstate();
@@ -1383,6 +1386,7 @@ static tahoe_status create_sparse(tahoe_forest **out, const int32_t *trees, cons
         if ((e = allow_max_lds(k, f->lds_limit)) != hipSuccess) return hip_status(e, "hipFuncSetAttribute(sparse, csr)");
     }
     if (p->num_cols <= 32767 && p->num_trees > 0 && (s = sparse_top_build(f.get(), trees, nodes))) return s;
+    if ((flags & TAHOE_CREATE_PARTIAL_DEPENDENCE) && (s = pd_build_sparse(f.get(), caller_trees, caller_nodes, covers))) return s;
     // contributions from the caller's trees, in the caller's numbering (contribs_build's order); Saabas deltas in the stored
     // (class-major) order
     return finish_create(f, flags, out, [&] { return contribs_build_sparse(f.get(), caller_trees, caller_nodes, covers, cats); },
@@ -1411,14 +1415,17 @@ static tahoe_status create_sparse_checked(tahoe_forest **out, const int32_t *tre
     *out = nullptr;
     if (const tahoe_status s = check_classes(p, num_classes)) return s;
     // tahoe_sparse_forest_create_ex comes here with cats == NULL and keeps its "any other bit" rule
-    const unsigned known = TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS | (from_create_cat ? TAHOE_CREATE_CAT_CONTRIBS : 0u);
+    const unsigned known = TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS | TAHOE_CREATE_PARTIAL_DEPENDENCE |
+                           (from_create_cat ? TAHOE_CREATE_CAT_CONTRIBS : 0u);
     if ((flags & ~known) != 0)
-        return fail(TAHOE_ERR_INVALID_ARG, "unknown create flags 0x%x (a sparse handle takes TAHOE_CREATE_CONTRIBS and "
-                                           "TAHOE_CREATE_APPROX_CONTRIBS only)", flags);
+        return fail(TAHOE_ERR_INVALID_ARG, "unknown create flags 0x%x (a sparse handle takes TAHOE_CREATE_CONTRIBS, "
+                                           "TAHOE_CREATE_APPROX_CONTRIBS and TAHOE_CREATE_PARTIAL_DEPENDENCE only)", flags);
     if ((flags & TAHOE_CREATE_CONTRIBS) && !covers)
         return fail(TAHOE_ERR_INVALID_ARG, "TAHOE_CREATE_CONTRIBS needs covers (one per node)");
     if ((flags & TAHOE_CREATE_APPROX_CONTRIBS) && !covers)
         return fail(TAHOE_ERR_INVALID_ARG, "TAHOE_CREATE_APPROX_CONTRIBS needs covers (one per node)");
+    if ((flags & TAHOE_CREATE_PARTIAL_DEPENDENCE) && !covers)
+        return fail(TAHOE_ERR_INVALID_ARG, "TAHOE_CREATE_PARTIAL_DEPENDENCE needs covers (one per node)");
     return create_sparse(out, trees, nodes, covers, p, num_classes, flags, cats);
 }
 
