@@ -286,7 +286,9 @@ extern "C" tahoe_status tahoe_forest_predict_partial_dependence(tahoe_forest *f,
         const unsigned tiles = (unsigned)((n + 63) / 64);
         const float *g = num_targets > 0 ? grid_dev + row0 * (size_t)num_targets : nullptr;
         const dim3 wgrid(tiles * tree_blocks), wblock(kPdWaves * 64);
-        if (cat_pool)
+        if (T == 0)
+            ;  // no trees, no walk (HIP refuses a grid of 0 workgroups): the sum over no trees below writes +0.0f
+        else if (cat_pool)
             hipLaunchKernelGGL((pd_walk_kernel<true>), wgrid, wblock, 0, s, sn, st, pd->frac, cat_pool, cat_words, g, n, tiles, T,
                                f->p.missing, tg, pd->ws, pd->chunk);
         else
