@@ -271,12 +271,30 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
             for (int k = 0; k < K; ++k) ring.vals[e * TR + k * 64 + lane] = v[k];
             TAHOE_RING_PUBLISH(ring, RING, t, lane == 0);
         };
-        int t_p = -1;  // tree whose bottom blocks are in flight
-        uint4 na_p[K] = {}, nb_p[K] = {};
+        // the bottom-block gathers of tree t from the block selectors bs: the tree's blocks from SGPRs, the block's byte offset
+        // (32 bits) from a VGPR
+        auto gather = [&](int t, const uint32_t (&bs)[K], uint4 (&na)[K], uint4 (&nb)[K]) {
+            const unsigned char *tb = reinterpret_cast<const unsigned char *>(blocks + (size_t)t * n_blocks * 2);
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                const uint4 *bp = reinterpret_cast<const uint4 *>(tb + 32u * bs[k]);
+                na[k] = bp[0];  // node0, node1, node2, 0
+                nb[k] = bp[1];  // four leaf values
+            }
+        };
+        // ---- software pipeline.  Only the block selectors of the previous tree cross the back edge; its gathers are issued
+        // at the HEAD of the iteration, fly under this tree's top walk and die in finish().  No load and no commit stands
+        // under a condition, and no load result is live across the latch, so the compiler's wait counts are exact: nothing
+        // waits for a load it has only just issued (profiles/qring_loop/loop_waits.txt).
+        // First tree of a walker: the gathers read block 0 of its own tree (in bounds, unused) and only finish() is skipped.
+        // Last tree: the prefetch is clamped to the walker's own tree and the commit rewrites the slot with the data it
+        // already holds, after this wave's reads of it (in-order LDS). ----
+        int t_p = -1;  // tree whose block selectors are in bsel_p
         uint32_t bsel_p[K] = {};
         for (int t = t_begin + wave; t < t_end && !dead; t += NWALK) {
-            const bool more = t + NWALK < t_end;
-            if (more) prefetch_top(t + NWALK);
+            uint4 na[K], nb[K];
+            gather(t_p >= 0 ? t_p : t, bsel_p, na, nb);
+            prefetch_top(t + NWALK < t_end ? t + NWALK : t);
             uint32_t i[K];
     #pragma unroll
             for (int k = 0; k < K; ++k) i[k] = 1;
@@ -355,23 +373,17 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
                 }
                 bsel[k] = idx - first_block_node;
             }
-            // ---- software pipeline: finish the PREVIOUS tree (its bottom-block gathers were issued one
-            // iteration ago and have been flying under this top walk), then issue this tree's gathers
-            // into the same registers ----
-            if (t_p >= 0) finish(t_p, na_p, nb_p, bsel_p);
+            if (t_p >= 0) finish(t_p, na, nb, bsel_p);  // the previous tree: its gathers have been flying under this top walk
             t_p = t;
 #pragma unroll
-            for (int k = 0; k < K; ++k) {
-                // the tree's blocks from SGPRs, the block's byte offset (32 bits) from a VGPR
-                const unsigned char *tb = reinterpret_cast<const unsigned char *>(blocks + (size_t)t * n_blocks * 2);
-                const uint4 *bp = reinterpret_cast<const uint4 *>(tb + 32u * bsel[k]);
-                na_p[k] = bp[0];  // node0, node1, node2, 0
-                nb_p[k] = bp[1];  // four leaf values
-                bsel_p[k] = bsel[k];
-            }
-            if (more) commit_top();  // this wave's reads of its slot are done (in-order LDS)
+            for (int k = 0; k < K; ++k) bsel_p[k] = bsel[k];
+            commit_top();  // this wave's reads of its slot are done (in-order LDS)
         }
-        if (t_p >= 0 && !dead) finish(t_p, na_p, nb_p, bsel_p);
+        if (t_p >= 0 && !dead) {  // the last tree
+            uint4 na[K], nb[K];
+            gather(t_p, bsel_p, na, nb);
+            finish(t_p, na, nb, bsel_p);
+        }
     };
     // chunk_flags[c] != 0 <=> the quantise pass met a missing value in rows [c, c+1) << cshift; a 192-row tile can
     // straddle two chunks (a chunk is at least 512 rows)
@@ -560,12 +572,23 @@ __global__ void __launch_bounds__(16 * 64)
                 if (r == 0 && t < num_trees) lds_flag_store(&ring.ready[t % RE], (uint32_t)(t + 1));
             }
         };
-        int g_p = -1;  // iteration whose bottom blocks are in flight
-        uint4 na_p[KG] = {}, nb_p[KG] = {};
+        auto gather = [&](int g, const uint32_t (&bs)[KG], uint4 (&na)[KG], uint4 (&nb)[KG]) {  // iteration g's bottom blocks
+#pragma unroll
+            for (int k = 0; k < KG; ++k) {
+                const int t = min(g * TPG + k * TPW + j, num_trees - 1);
+                const uint4 *bp = blocks + ((size_t)t * n_blocks + bs[k]) * 2;
+                na[k] = bp[0];
+                nb[k] = bp[1];
+            }
+        };
+        // the software pipeline of qring_kernel's walkers: the previous iteration's gathers at the head (block 0 of its own trees in a
+        // walker's first iteration, unused), prefetch and commit unconditional (the last iteration stages its own tops again)
+        int g_p = -1;  // iteration whose block selectors are in bsel_p
         uint32_t bsel_p[KG] = {};
         for (int g = wave; g < n_groups && !dead; g += NWALK) {
-            const bool more = g + NWALK < n_groups;
-            if (more) prefetch_tops(g + NWALK);
+            uint4 na[KG], nb[KG];
+            gather(g_p >= 0 ? g_p : g, bsel_p, na, nb);
+            prefetch_tops(g + NWALK < n_groups ? g + NWALK : g);
             int t[KG];  // lanes of a missing tree repeat the last one, unused
             uint32_t i[KG];
 #pragma unroll
@@ -612,18 +635,17 @@ __global__ void __launch_bounds__(16 * 64)
                 }
                 bsel[k] = idx - first_block_node;
             }
-            if (g_p >= 0) finish(g_p, na_p, nb_p, bsel_p);
+            if (g_p >= 0) finish(g_p, na, nb, bsel_p);
             g_p = g;
 #pragma unroll
-            for (int k = 0; k < KG; ++k) {
-                const uint4 *bp = blocks + ((size_t)t[k] * n_blocks + bsel[k]) * 2;
-                na_p[k] = bp[0];
-                nb_p[k] = bp[1];
-                bsel_p[k] = bsel[k];
-            }
-            if (more) commit_tops();
+            for (int k = 0; k < KG; ++k) bsel_p[k] = bsel[k];
+            commit_tops();
         }
-        if (g_p >= 0 && !dead) finish(g_p, na_p, nb_p, bsel_p);
+        if (g_p >= 0 && !dead) {  // the last iteration
+            uint4 na[KG], nb[KG];
+            gather(g_p, bsel_p, na, nb);
+            finish(g_p, na, nb, bsel_p);
+        }
     };
     if (chunk_flags[row0 >> cshift] != 0)
         run(std::true_type{});
