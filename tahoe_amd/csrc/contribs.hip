@@ -15,11 +15,9 @@
 
 #include "forest_internal.h"
 #include "contribs_internal.h"
+#include "treeshap_lanes.h"
 
 namespace tahoe {
-
-// 1 / k, correctly rounded (constant folding), for the uniform factors of the recursions
-__constant__ float c_inv[34] = TAHOE_CONTRIB_INV_TABLE;
 
 // One workgroup = a tile of R rows (staged in LDS) x all bins; wave w evaluates bins w, w + 4, ... of each class into its own
 // slab [R][F] of LDS; the four slabs are then summed in wave order and written out.  Every row sees the same operations in the
@@ -104,7 +102,7 @@ __device__ __forceinline__ void contribs_tile(float *__restrict__ phi, const flo
                         next = o ? n_one : next;
                     }
                 }
-                // a followed element's weights below `split` come from the other end (unwind_split, contribs_internal.h)
+                // a followed element's weights below `split` come from the other end (unwind_split, treeshap_lanes.h)
                 if (__any(o && split > 0)) {
                     float prev = 0.0f;
                     for (int i = 0; i < steps - 1; ++i) {
@@ -179,8 +177,6 @@ __global__ __launch_bounds__(256) void contribs_spare_kernel(float *__restrict__
     contribs_tile<true, SETS>(out, data, rows, F, C, R, elems, one_minus_z, bin_info, class_bins, bias, class_div, missing, elem_set,
                               set_pool, set_words);
 }
-
-__device__ __forceinline__ void vm_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // The off-diagonal terms of bins b_first, b_first + b_step, ... < b_end for the nr rows of `tile` (row r at tile + r F), added
 // into acc + r acc_row + a ld + b for the pair (a, b).

@@ -130,41 +130,13 @@ __device__ __forceinline__ bool follows_set(float x, float lower, float upper, b
     return is_missing ? missing_ok : (num_ok && set_ok);
 }
 
-// 1 / k for k = 0 .. 33 (entry 0 unused), correctly rounded by constant folding: the uniform factors of the recursions.  Every
-// translation unit with a TreeSHAP kernel defines its own __constant__ table from this list.
+// 1 / k for k = 0 .. 33 (entry 0 unused), correctly rounded by constant folding: the uniform factors of the recursions
+// (treeshap_lanes.h defines the __constant__ table of a unit from this list).
 #define TAHOE_CONTRIB_INV_TABLE                                                                                                   \
     {0.0f,         1.0f,         1.0f / 2.0f,  1.0f / 3.0f,  1.0f / 4.0f,  1.0f / 5.0f,  1.0f / 6.0f,  1.0f / 7.0f,  1.0f / 8.0f,    \
      1.0f / 9.0f,  1.0f / 10.0f, 1.0f / 11.0f, 1.0f / 12.0f, 1.0f / 13.0f, 1.0f / 14.0f, 1.0f / 15.0f, 1.0f / 16.0f, 1.0f / 17.0f,   \
      1.0f / 18.0f, 1.0f / 19.0f, 1.0f / 20.0f, 1.0f / 21.0f, 1.0f / 22.0f, 1.0f / 23.0f, 1.0f / 24.0f, 1.0f / 25.0f, 1.0f / 26.0f,   \
      1.0f / 27.0f, 1.0f / 28.0f, 1.0f / 29.0f, 1.0f / 30.0f, 1.0f / 31.0f, 1.0f / 32.0f, 1.0f / 33.0f}
-
-// Where the unwound sum of a followed element (one fraction 1, zero fraction z) of a path of ud + 1 elements changes direction.
-// The weights q_i of the path without the element satisfy pw_i = q_i z (ud - i) / (ud + 1) + q_(i-1) i / (ud + 1).  Solved from
-// the top (q_(ud-1) first) an error grows by z (ud - i) / (i + 1) per step, from the bottom (q_0 first) by i / (z (ud - i)):
-// either alone loses 5 to 6 digits on a 32-element path whose z is near 1.  Both factors stay <= 1 when the top-down recurrence
-// runs for i >= split and the bottom-up one for i < split, split = floor((z ud - 1) / (1 + z)) + 1 clamped to [0, ud].  z < 1 / ud
-// (a cut z = 0 among them) gives 0: all from the top, and no division by a small z.
-__device__ __forceinline__ int unwind_split(float z, int ud)
-{
-    const float s = floorf((z * (float)ud - 1.0f) / (1.0f + z)) + 1.0f;
-    return (int)fminf(fmaxf(s, 0.0f), (float)ud);
-}
-
-// value of lane - 1 (0 in lane 0): DPP wave_shr:1
-__device__ __forceinline__ float from_left_lane(float v)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138, 0xf, 0xf, false));
-}
-
-// v of lane src_lane (ds_bpermute)
-__device__ __forceinline__ float lane_read(float v, int src_lane)
-{
-    return __int_as_float(__builtin_amdgcn_ds_bpermute(src_lane << 2, __float_as_int(v)));
-}
-__device__ __forceinline__ uint32_t lane_read_u(uint32_t v, int src_lane)
-{
-    return (uint32_t)__builtin_amdgcn_ds_bpermute(src_lane << 2, (int)v);
-}
 
 // The path tables of a vector-leaf handle (tahoe_vector_forest_create_ex with TAHOE_CREATE_CONTRIBS), on the host: one set of
 // bins for the forest -- the bins tahoe_sparse_forest_create_ex builds for one class of the K-fold expansion -- whose root

@@ -19,6 +19,7 @@
 
 #include "forest_internal.h"
 #include "contribs_internal.h"
+#include "treeshap_lanes.h"
 #include "vector_internal.h"
 
 namespace tahoe {
@@ -114,34 +115,9 @@ __global__ __launch_bounds__(256) void interventional_kernel(float *__restrict__
                 bool o;
                 if constexpr (SETS) o = rank != 0 && follows_set(tile[r * F + fid], lower, upper, missing_ok, nan_ok, missing, es, set_pool, set_words, gather);
                 else o = rank != 0 && follows(tile[r * F + fid], lower, upper, missing_ok, nan_ok, missing);
-                const unsigned long long mx = __ballot(o);
-                const unsigned long long pa = pm & mx, pb = pm & ~mx;
-                const int nb = __popcll(pb);
-                // A lane that x follows is in A when r does not (weight W[a][b]), one that x does not follow is in B when r
-                // does (W[b][a]): the sign is fixed for the row and applied after the sum
-                const int sha = o ? 7 : 2, shb = o ? 2 : 7;  // byte offset of W[p][q]: (p << 7) + (q << 2)
-                const char *wb = reinterpret_cast<const char *>(w);
-                // this lane's weight for background row k, 0 where its element is in neither A nor B or the path is dead
-                auto weight = [&](int k) {
-                    const unsigned long long d = mx ^ mb[k];
-                    const int na = __popcll(d & pa), nd = __popcll(d & pb);
-                    const bool active = nd == nb && ((d >> lane) & 1ull) != 0;
-                    const float wv = *reinterpret_cast<const float *>(wb + ((na << sha) + (nd << shb)));
-                    return active ? wv : 0.0f;
-                };
-                float acc = 0.0f;
-                int k = 0;
-                for (; k + kIvUnroll <= B; k += kIvUnroll) {  // the loads of kIvUnroll rows in flight together; adds in order
-                    float wk[kIvUnroll];
-#pragma unroll
-                    for (int u = 0; u < kIvUnroll; ++u) wk[u] = weight(k + u);
-#pragma unroll
-                    for (int u = 0; u < kIvUnroll; ++u) acc += wk[u];
-                }
-                for (; k < B; ++k) acc += weight(k);
+                const float acc = background_weight_sum(o, pm, mb, B, w, lane);
                 const float term = (o ? acc : -acc) * leaf;
-                // the round-ordered add and the epilogue below are contribs_tile's, written out again: as shared helpers
-                // they change both kernels' instruction streams
+                // two lanes of a bin on one feature add in lane order, as in contribs_tile
                 for (int k = 0; k < rounds; ++k)
                     if (rank != 0 && round == k) slab[r * F + fid] += term;
             }

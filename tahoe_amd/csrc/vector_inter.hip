@@ -9,8 +9,8 @@
 // Bits: out[row][k] is what interactions_kernel gives for class k of the expansion.  The form is chosen as there, by F alone.
 // Slabs: bin b goes to wave b % 4, the terms of a pair add in the row-independent round order of the bin, the four partial sums
 // combine as ((s0 + s1) + s2) + s3 and are divided by div.  In place: every bin in order, straight into the output, then / div.
-// Both: diagonal = phi_i - (off-diagonal sum of row i, ascending from 0.0f).  The conditioned unwound sum is interaction_bins'
-// one-sided recurrence, statement for statement (restated, not shared: the kernels of contribs.hip must stay the code they are).
+// Both: diagonal = phi_i - (off-diagonal sum of row i, ascending from 0.0f).  The pair rounds and the conditioned unwound sum are
+// interaction_bins' statements (contribs.hip), kept in step by hand: treeshap_lanes.h says why they are not one function.
 // Neither KB, the rows of a tile nor the placement of the class blocks takes part in any sum.
 #include <hip/hip_runtime.h>
 
@@ -18,16 +18,13 @@
 
 #include "forest_internal.h"
 #include "contribs_internal.h"
+#include "treeshap_lanes.h"
 #include "vector_internal.h"
 
 namespace tahoe {
 
-static __constant__ float c_inv[34] = TAHOE_CONTRIB_INV_TABLE;
-
 constexpr size_t kVecInterLdsBudget = 80 * 1024;  // interactions_kernel's: two workgroups per CU
 constexpr int kVecInterMaxRows = 32;              // rows of a tile: one bit each in the per-lane one-fraction mask
-
-__device__ __forceinline__ void vm_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // Both entries of a pair receive the same adds in the same order, so the slab form keeps each unordered pair once: the strict
 // upper triangle of an F x F matrix, row-major.  (a, b) with a < b < F -> [0, F (F - 1) / 2)
@@ -54,15 +51,8 @@ __device__ __forceinline__ void vector_interaction_bins(float *acc, size_t acc_r
         const int fid = elem_fid(e.w), rank = elem_rank(e.w), ud = elem_ud(e.w);
         const bool missing_ok = elem_missing_ok(e.w), nan_ok = elem_nan_ok(e.w);
         const int gs = lane - rank;  // lane of the path's root element
-        // the block's leaf values: a root lane reads them (.x is its vector's index; a padding lane names vector 0, which exists
-        // where a bin does), the other lanes of the path take them from it
-        float leaf[KB];
-#pragma unroll
-        for (int j = 0; j < KB; ++j) {
-            float own = 0.0f;
-            if (rank == 0 && j < nk) own = leaves[(size_t)e.x * (size_t)K + (size_t)(k0 + j)];
-            leaf[j] = lane_read(own, gs);
-        }
+        float leaf[KB];  // the block's leaf values
+        load_leaf_block<KB>(leaf, leaves, e.x, K, k0, nk, rank, gs);
         // one-fractions of this lane's element, bit r for row r (a root lane's bounds are not bounds: its bit is never read)
         uint32_t omask = 0;
         for (int r = 0; r < nr; ++r) omask |= (follows(tile[r * F + fid], lower, upper, missing_ok, nan_ok, missing) ? 1u : 0u) << r;
@@ -129,13 +119,7 @@ __device__ __forceinline__ void vector_interaction_bins(float *acc, size_t acc_r
                 for (int q = 0; q < rounds; ++q) {
                     if (pair && round == q) {
                         if (SLABS) {
-                            float v[KB];
-#pragma unroll
-                            for (int j = 0; j < KB; ++j)
-                                if (j < nk) v[j] = pa[j * acc_class];
-#pragma unroll
-                            for (int j = 0; j < KB; ++j)
-                                if (j < nk) pa[j * acc_class] = v[j] + tw * leaf[j] * h;
+                            add_leaf_block<KB>(pa, acc_class, nk, [&](int j) { return tw * leaf[j] * h; });
                         } else {
                             float va[KB], vb[KB];
 #pragma unroll
@@ -282,14 +266,10 @@ __global__ __launch_bounds__(256) void vector_interactions_kernel(float *out, co
 template <class Fn>
 static inline void with_inter_shape(int kb, bool slabs, Fn &&fn)
 {
-    auto form = [&](auto c) {
+    with_class_block(kb, [&](auto c) {
         if (slabs) fn(c, std::true_type{});
         else fn(c, std::false_type{});
-    };
-    if (kb == 8) form(std::integral_constant<int, 8>{});
-    else if (kb == 4) form(std::integral_constant<int, 4>{});
-    else if (kb == 2) form(std::integral_constant<int, 2>{});
-    else form(std::integral_constant<int, 1>{});
+    });
 }
 
 // LDS bytes of one row of the slab form with class block kb
@@ -309,15 +289,8 @@ tahoe_status vector_inter_build(const tahoe_forest *f, VectorShap *sh)
     // The class block: the largest of 8, 4, 2 -- not above K rounded up to one of them -- of which one row fits the budget (in
     // place: no LDS per class, so the largest), else 1; TAHOE_VECTOR_SHAP_KB forces one that leaves a row.  Then the rows of a
     // slab tile: the largest power of two <= 32 that fits.  Neither changes a bit of the result.
-    auto fits = [&](int c) { return !sh->inter_slabs || slab_row_bytes(F, c) <= budget; };
-    int kb = 1;
-    const int forced = f->knobs.vector_shap_kb;
-    if (forced == 1 || forced == 2 || forced == 4 || forced == 8) {
-        kb = fits(forced) ? forced : 1;
-    } else {
-        for (int c = 8; c > 1 && kb == 1; c /= 2)
-            if (c < 2 * K && fits(c)) kb = c;
-    }
+    const int kb = pick_class_block(f->knobs.vector_shap_kb, K,
+                                    [&](int c, bool) { return !sh->inter_slabs || slab_row_bytes(F, c) <= budget; });
     sh->inter_class_block = kb;
     size_t R = 1;
     if (sh->inter_slabs)

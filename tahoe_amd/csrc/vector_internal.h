@@ -5,6 +5,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <type_traits>
 
 #include <hip/hip_runtime.h>
 
@@ -73,6 +74,28 @@ struct VectorApprox {
     size_t lds_bytes = 0;     // per workgroup
     bool grid_blocks = true;  // gridDim.y runs over the class blocks (else a workgroup loops over them)
 };
+
+// The class block KB of a vector-leaf TreeSHAP kernel, the classes that share one recursion: a forced value (TAHOE_VECTOR_SHAP_KB)
+// of 1, 2, 4 or 8 if it fits, else 1; without one the largest of 8, 4, 2 -- not above K rounded up to one of them -- that fits,
+// else 1.  fits(c, forced): does the kernel's shape hold a block of c?  No choice changes a bit of the result.
+template <class Fits>
+inline int pick_class_block(int forced, int K, Fits fits)
+{
+    if (forced == 1 || forced == 2 || forced == 4 || forced == 8) return fits(forced, true) ? forced : 1;
+    for (int c = 8; c > 1; c /= 2)
+        if (c < 2 * K && fits(c, false)) return c;
+    return 1;
+}
+
+// fn(std::integral_constant<int, KB>) for the runtime class block
+template <class Fn>
+inline void with_class_block(int kb, Fn &&fn)
+{
+    if (kb == 8) fn(std::integral_constant<int, 8>{});
+    else if (kb == 4) fn(std::integral_constant<int, 4>{});
+    else if (kb == 2) fn(std::integral_constant<int, 2>{});
+    else fn(std::integral_constant<int, 1>{});
+}
 
 }  // namespace tahoe
 

@@ -14,6 +14,7 @@
 
 #include "forest_internal.h"
 #include "contribs_internal.h"
+#include "treeshap_lanes.h"
 #include "vector_internal.h"
 
 namespace tahoe {
@@ -21,8 +22,8 @@ namespace tahoe {
 // One workgroup = a tile of R rows (staged in LDS) x all bins x the class blocks k0 = blockIdx.y KB, + gridDim.y KB, ...; wave w
 // evaluates bins w, w + 4, ... into its own KB slabs [R][F] of LDS, one per class of the block; per class the four wave slabs are
 // summed in wave order and written out.  LDS: tile [R][F] | slabs [4][KB][R][F] | W [32 x 32] (WLDS; else the weight table is
-// read from global memory).  The body of a (bin, row) is interventional_kernel's, statement for statement (restated here, not
-// shared as a function: the kernels of interventional.hip must stay the code they are).
+// read from global memory).  The body of a (bin, row) is interventional_kernel's: background_weight_sum
+// (treeshap_lanes.h).
 template <int KB, bool WLDS>
 __global__ __launch_bounds__(256) void vector_interventional_kernel(float *__restrict__ phi, const float *__restrict__ data,
                                                                     size_t rows, int F, int K, int R,
@@ -64,58 +65,19 @@ __global__ __launch_bounds__(256) void vector_interventional_kernel(float *__res
             const int fid = elem_fid(e.w), rank = elem_rank(e.w), ud = elem_ud(e.w), round = elem_round(e.w);
             const bool missing_ok = elem_missing_ok(e.w), nan_ok = elem_nan_ok(e.w);
             const int gs = lane - rank;  // lane of the path's root element
-            // the block's leaf values: a root lane reads them (.x is its vector's index; a padding lane names vector 0, which
-            // exists where a bin does), the other lanes of the path take them from it
-            float leaf[KB];
-#pragma unroll
-            for (int j = 0; j < KB; ++j) {
-                float own = 0.0f;
-                if (rank == 0 && j < nk) own = leaves[(size_t)e.x * (size_t)K + (size_t)(k0 + j)];
-                leaf[j] = lane_read(own, gs);
-            }
+            float leaf[KB];  // the block's leaf values
+            load_leaf_block<KB>(leaf, leaves, e.x, K, k0, nk, rank, gs);
             // the lanes of this lane's path but its root: gs + 1 .. gs + ud (a path never leaves its bin)
             const unsigned long long pm = ud == 0 ? 0ull : ((1ull << ud) - 1ull) << (gs + 1);
             const unsigned long long *mb = masks + (size_t)b * B;
             for (int r = 0; r < nr; ++r) {
                 const bool o = rank != 0 && follows(tile[r * F + fid], lower, upper, missing_ok, nan_ok, missing);
-                const unsigned long long mx = __ballot(o);
-                const unsigned long long pa = pm & mx, pb = pm & ~mx;
-                const int nb = __popcll(pb);
-                // A lane that x follows is in A when r does not (weight W[a][b]), one that x does not follow is in B when r
-                // does (W[b][a]): the sign is fixed for the row and applied after the sum
-                const int sha = o ? 7 : 2, shb = o ? 2 : 7;  // byte offset of W[p][q]: (p << 7) + (q << 2)
-                const char *wb = reinterpret_cast<const char *>(w);
-                // this lane's weight for background row k, 0 where its element is in neither A nor B or the path is dead
-                auto weight = [&](int k) {
-                    const unsigned long long d = mx ^ mb[k];
-                    const int na = __popcll(d & pa), nd = __popcll(d & pb);
-                    const bool active = nd == nb && ((d >> lane) & 1ull) != 0;
-                    const float wv = *reinterpret_cast<const float *>(wb + ((na << sha) + (nd << shb)));
-                    return active ? wv : 0.0f;
-                };
-                float acc = 0.0f;
-                int k = 0;
-                for (; k + kIvUnroll <= B; k += kIvUnroll) {  // the loads of kIvUnroll rows in flight together; adds in order
-                    float wk[kIvUnroll];
-#pragma unroll
-                    for (int u = 0; u < kIvUnroll; ++u) wk[u] = weight(k + u);
-#pragma unroll
-                    for (int u = 0; u < kIvUnroll; ++u) acc += wk[u];
-                }
-                for (; k < B; ++k) acc += weight(k);
+                const float acc = background_weight_sum(o, pm, mb, B, w, lane);
                 const float s = o ? acc : -acc;  // shared by the block's classes
                 // two lanes of a bin on one feature add in lane order (round = earlier lanes of the bin on that feature)
                 float *cell = slab + r * F + fid;
                 for (int q = 0; q < rounds; ++q)
-                    if (rank != 0 && round == q) {
-                        float v[KB];
-#pragma unroll
-                        for (int j = 0; j < KB; ++j)
-                            if (j < nk) v[j] = cell[j * slab_n];
-#pragma unroll
-                        for (int j = 0; j < KB; ++j)
-                            if (j < nk) cell[j * slab_n] = v[j] + s * leaf[j];
-                    }
+                    if (rank != 0 && round == q) add_leaf_block<KB>(cell, slab_n, nk, [&](int j) { return s * leaf[j]; });
             }
         }
         __syncthreads();
@@ -139,11 +101,11 @@ __global__ __launch_bounds__(256) void vector_interventional_kernel(float *__res
 template <class Fn>
 static inline void with_iv_form(int kb, bool wlds, Fn &&fn)
 {
-    if (kb == 8) fn(std::integral_constant<int, 8>{}, std::true_type{});
-    else if (kb == 4) fn(std::integral_constant<int, 4>{}, std::true_type{});
-    else if (kb == 2) fn(std::integral_constant<int, 2>{}, std::true_type{});
-    else if (wlds) fn(std::integral_constant<int, 1>{}, std::true_type{});
-    else fn(std::integral_constant<int, 1>{}, std::false_type{});
+    with_class_block(kb, [&](auto c) {
+        if constexpr (decltype(c)::value > 1) fn(c, std::true_type{});
+        else if (wlds) fn(c, std::true_type{});
+        else fn(c, std::false_type{});
+    });
 }
 
 // Rows of a tile for class block kb: the largest power of two <= kIvMaxTileRows whose tile, 4 kb slabs and the weight table fit
@@ -164,14 +126,7 @@ static size_t iv_tile_rows(int F, int kb)
 void vector_iv_shape(const tahoe_forest *f, VectorShap *sh)
 {
     const int F = f->p.num_cols, K = f->num_classes;
-    int kb = 1;
-    const int forced = f->knobs.vector_shap_kb;
-    if (forced == 1 || forced == 2 || forced == 4 || forced == 8) {
-        kb = iv_tile_rows(F, forced) ? forced : 1;
-    } else {
-        for (int c = 8; c > 1 && kb == 1; c /= 2)
-            if (c < 2 * K && iv_tile_rows(F, c)) kb = c;
-    }
+    const int kb = pick_class_block(f->knobs.vector_shap_kb, K, [&](int c, bool) { return iv_tile_rows(F, c) != 0; });
     const size_t per_row = (1 + 4 * (size_t)kb) * (size_t)F * sizeof(float), table = kIvTable * sizeof(float);
     const size_t R = std::max<size_t>(iv_tile_rows(F, kb), 1);  // (kb == 1: check_contrib_cols has made sure that one row fits the device)
     sh->iv_class_block = kb;

@@ -15,19 +15,18 @@
 
 #include "forest_internal.h"
 #include "contribs_internal.h"
+#include "treeshap_lanes.h"
 #include "vector_internal.h"
 
 namespace tahoe {
-
-static __constant__ float c_inv[34] = TAHOE_CONTRIB_INV_TABLE;
 
 constexpr size_t kVecShapLdsBudget = 80 * 1024;  // two workgroups per CU, as contribs_kernel's tiles
 constexpr int kVecShapMinRows = 4;               // a class block wider than 1 must leave a tile of at least this many rows
 
 // One workgroup = a tile of R rows (staged in LDS) x all bins x the class blocks k0 = blockIdx.y KB, + gridDim.y KB, ...; wave w
 // evaluates bins w, w + 4, ... into its own KB slabs [R][F] of LDS, one per class of the block; per class the four wave slabs are
-// summed in wave order and written out.  LDS: tile [R][F] | slabs [4][KB][R][F].  The recursion of a (bin, row) is contribs_tile's,
-// statement for statement (restated here, not shared as a function: the kernels of contribs.hip must stay the code they are).
+// summed in wave order and written out.  LDS: tile [R][F] | slabs [4][KB][R][F].  The recursion of a (bin, row) is contribs_tile's
+// statements (contribs.hip), kept in step by hand: treeshap_lanes.h says why they are not one function.
 // SPARE = false: phi[rows][K][F + 1] (vector_contribs_kernel).  SPARE = true: the same values into row F of each (row, k) matrix of
 // out[rows][K][F + 1][F + 1] (tahoe_forest_predict_interactions on a handle with TAHOE_CREATE_VECTOR_INTERACTIONS,
 // vector_contribs_spare_kernel).
@@ -109,7 +108,7 @@ __device__ __forceinline__ void vector_contribs_tile(float *__restrict__ phi, co
                         next = o ? n_one : next;
                     }
                 }
-                // a followed element's weights below `split` come from the other end (unwind_split, contribs_internal.h)
+                // a followed element's weights below `split` come from the other end (unwind_split, treeshap_lanes.h)
                 if (__any(o && split > 0)) {
                     float prev = 0.0f;
                     for (int i = 0; i < steps - 1; ++i) {
@@ -169,16 +168,6 @@ __global__ __launch_bounds__(256) void vector_contribs_spare_kernel(TAHOE_VECTOR
 }
 #undef TAHOE_VECTOR_SHAP_PARAMS
 
-// kernel(kb) for the runtime class block
-template <class Fn>
-static inline void with_class_block(int kb, Fn &&fn)
-{
-    if (kb == 8) fn(std::integral_constant<int, 8>{});
-    else if (kb == 4) fn(std::integral_constant<int, 4>{});
-    else if (kb == 2) fn(std::integral_constant<int, 2>{});
-    else fn(std::integral_constant<int, 1>{});
-}
-
 // Rows of a tile for class block kb: the largest power of two <= 64 whose tile and 4 kb slabs fit the budget; for kb == 1 at
 // least 1 (the column limit of contribs_tables_vector has made sure that one row fits the device), else 0 where fewer than
 // min_rows fit
@@ -210,14 +199,9 @@ tahoe_status vector_shap_build(tahoe_forest *f, const int32_t *trees, const taho
     sh->div = ((f->p.output & TAHOE_OUT_AVG) != 0 && f->class_trees > 0) ? (float)f->class_trees : 1.0f;
     // The class block: the largest of 8, 4, 2 -- not above K rounded up to one of them -- that leaves a tile of >= 4 rows, else 1.
     // TAHOE_VECTOR_SHAP_KB forces one that leaves a tile of >= 1 row.  Neither changes a bit of the result.
-    int kb = 1;
-    const int forced = f->knobs.vector_shap_kb;
-    if (forced == 1 || forced == 2 || forced == 4 || forced == 8) {
-        kb = tile_rows(F, forced, 1) ? forced : 1;
-    } else {
-        for (int c = 8; c > 1 && kb == 1; c /= 2)
-            if (c < 2 * K && tile_rows(F, c, kVecShapMinRows)) kb = c;
-    }
+    const int kb = pick_class_block(f->knobs.vector_shap_kb, K, [&](int c, bool forced) {
+        return tile_rows(F, c, forced ? 1 : kVecShapMinRows) != 0;
+    });
     sh->class_block = kb;
     sh->rows_per_tile = (int)tile_rows(F, kb, 1);
     sh->lds_bytes = (1 + 4 * (size_t)kb) * (size_t)sh->rows_per_tile * (size_t)F * sizeof(float);

@@ -11,7 +11,10 @@ A template flag appended with a default (`bool MC = false`) is matched by droppi
 instantiations with `, true` there are counted, not compared; a kernel that became a template for the flag is matched by dropping
 `<false>`.  A function whose full name exists in both builds is matched by
 that name first, so kernels of the list that did not get the flag in this change are compared as they are.  --exact: both builds have the same template parameters (no appended
-flag): functions are matched by their full names.  A translation unit that exists only in <new_dir> is listed as new."""
+flag): functions are matched by their full names.  A translation unit that exists only in <new_dir> is listed as new.
+--ops: for every changed kernel, the instruction count of both builds, the opcodes whose counts differ (old -> new) and both
+builds' VGPRs, scratch bytes and occupancy (the compiler's resource comments after each function)."""
+import collections
 import difflib
 import re
 import subprocess
@@ -49,6 +52,19 @@ def functions(path):
     return out
 
 
+def ops_report(path_old, k_old, body_old, path_new, k_new, body_new):
+    """--ops: what a changed kernel's two streams differ in, by opcode count and by resources"""
+    count = [collections.Counter(re.sub(r"_e(32|64)$", "", t.split()[0])  # (one opcode under either encoding)
+                                 for t in b if t[0] in " \t" and not t.strip().startswith(".")) for b in (body_old, body_new)]
+    diff = ", ".join(f"{op} {count[0][op]} -> {count[1][op]}" for op in sorted(set(count[0]) | set(count[1])) if count[0][op] != count[1][op])
+    res = []
+    for path, k in ((path_old, k_old), (path_new, k_new)):
+        tail = open(path).read().split(f"\n{k}:")[1]  # the first comments after the label are the function's own
+        res.append(" / ".join(re.search(rf"; {f}: (\d+)", tail).group(1) for f in ("NumVgprs", "ScratchSize", "Occupancy")))
+    print(f"    instructions {sum(count[0].values())} -> {sum(count[1].values())}; opcode counts that differ: {diff or 'none'}")
+    print(f"    VGPRs / scratch bytes / occupancy: {res[0]} -> {res[1]}")
+
+
 def demangle(names):
     res = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
     return dict(zip(names, res))
@@ -71,15 +87,17 @@ def key(name, new, old_names=()):
 def main(argv):
     verbose = "-v" in argv
     exact = "--exact" in argv
-    args = [a for a in argv if a not in ("-v", "--exact")]
+    ops = "--ops" in argv
+    args = [a for a in argv if a not in ("-v", "--exact", "--ops")]
     old_dir, new_dir, units = args[0], args[1], args[2:] or ["forest", "qring"]
     changed = 0
     for unit in units:
+        old_path, new_path = (f"{d}/{unit}-hip-amdgcn-amd-amdhsa-gfx950.s" for d in (old_dir, new_dir))
         try:
-            old = functions(f"{old_dir}/{unit}-hip-amdgcn-amd-amdhsa-gfx950.s")
+            old = functions(old_path)
         except FileNotFoundError:
             old = {}
-        new = functions(f"{new_dir}/{unit}-hip-amdgcn-amd-amdhsa-gfx950.s")
+        new = functions(new_path)
         od, nd = demangle(list(old)), demangle(list(new))
         old_by = {key(od[k], False): k for k in old}
         new_by = {}
@@ -97,6 +115,8 @@ def main(argv):
             else:
                 changed += 1
                 print(f"{unit}: CHANGED: {name}")
+                if ops:
+                    ops_report(old_path, k, old[k], new_path, new_by[name], new[new_by[name]])
                 if verbose:
                     print("\n".join(list(difflib.unified_diff(old[k], new[new_by[name]], lineterm=""))[:60]))
         added = [n for n in new_by if n not in old_by]
