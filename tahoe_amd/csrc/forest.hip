@@ -1106,6 +1106,7 @@ static tahoe_knobs read_knobs()
     k.qring_regions = on("TAHOE_QRING_REGIONS");
     k.qring_code8 = on("TAHOE_QRING_CODE8");
     k.qring_narrow128 = on("TAHOE_QRING_NARROW128");
+    k.qring_top24 = on("TAHOE_QRING_TOP24");
     k.quant_buckets = on("TAHOE_QUANT_BUCKETS");
     k.quant_multi = on("TAHOE_QUANT_MULTI");
     k.sparse_qring = on("TAHOE_SPARSE_QRING");

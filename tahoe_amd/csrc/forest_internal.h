@@ -73,6 +73,7 @@ struct tahoe_knobs {
     bool qring_regions = true;    // TAHOE_QRING_REGIONS = 0: the 128-slot column layout instead of the region form
     bool qring_code8 = true;      // TAHOE_QRING_CODE8 = 0: u16 codes where u8 codes would serve
     bool qring_narrow128 = true;  // TAHOE_QRING_NARROW128 = 0: the 32-KiB region stride for forests of <= 128 features
+    bool qring_top24 = true;      // TAHOE_QRING_TOP24 = 0: no packed tops (192-row u16 tiles stage the u32 tops always)
     bool quant_buckets = true;    // TAHOE_QUANT_BUCKETS = 0: no bucketed quantise kernel
     bool quant_multi = true;      // TAHOE_QUANT_MULTI = 0: the pair quantise kernels instead of the many-features ones
     bool sparse_qring = true;     // TAHOE_SPARSE_QRING = 0: a sparse handle keeps the float32 kernels only

@@ -10,6 +10,8 @@
 //   x code    u16: 0..n_f, or 0xFFFF when |x - missing| <= 1e-6 (float32)   (missing takes !def_left)
 //   node      u32: threshold code (1..n_f; 0xFFFF for a NaN threshold: never >=) | fid << 16 | def_left << 31
 //   top       [t][2^L] u32, 1-based heap positions (children of i = the aligned pair 2i, 2i+1), L <= 10
+//   top24     the same tops at 3 bytes per node, without def_left (192-row tiles on u16 codes without a missing value stage
+//             these and expand them to the u32 words on the way into LDS: qring_kernel, "packed tops")
 //   block     [t][2^(De-2)] 32 B = {node0, node1, node2, 0} {leaf0..3 f32}: last two levels + leaves
 // Requires num_cols <= 32767 and at most 32767 distinct thresholds per feature within a tree group (the
 // per-feature search tree must fit LDS in the quantise kernel; larger forests are cut into groups of
@@ -69,14 +71,14 @@ constexpr int kConsSleep8 = 1, kWalkSleep8 = 8;
 // inside a class leaves the partial sum there.  Leaf indices go to the original tree's column.
 template <int NWALK, bool WRITE_LEAF, bool LDSX, bool NARROW = false, bool EXCH = false, int K = 2, bool REG = false, int RING = kQRing,
           bool SPLIT = false, int BATCH = (RING >= 2 * kQBatch ? kQBatch : RING / 2), bool CODE8 = false, bool DEP = false,
-          int REGB = kRegBytes, bool MC = false>
+          int REGB = kRegBytes, bool MC = false, bool T24 = false>
 __global__ void __launch_bounds__((NWALK + 1) * 64)
     qring_kernel(const uint16_t *__restrict__ xq, const uint32_t *__restrict__ top, const uint4 *__restrict__ blocks,
                  const uint32_t *__restrict__ qinner, const uint32_t *__restrict__ leaf_orig, float *sums,
                  uint32_t *__restrict__ leaf_out, size_t rows, int cols, int num_trees, int depth, int top_levels,
                  int top_stride, const uint32_t *__restrict__ chunk_flags, int *__restrict__ error_flag,
                  const float *sums_in, int tree_base, int total_trees, int cshift, float *__restrict__ leafbuf, size_t leaf_stride,
-                 int slices, size_t row_begin, int num_classes)
+                 int slices, size_t row_begin, int num_classes, const uint4 *__restrict__ top24, int top24_chunks)
 {
     // `rows` is the END of the rows this launch walks and row_begin (region form only; a multiple of 384) their start: a batch
     // may be walked as whole waves of 192-row tiles followed by a remainder of 128-row tiles (qring_launch).
@@ -109,6 +111,13 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
     const LdsRing<RING, TR> ring(slots + (size_t)NWALK * slot_bytes);
 
     const size_t row0 = row_begin + (size_t)tile_id * TR;
+    // T24: the instantiation that stages its tops from the packed array `top24` on tiles without a missing value (below, "packed
+    // tops"); launched only for handles that have the array.  It needs to know which top to load before the first one: the
+    // tile's "missing seen" flags are read here, as scalar loads that fly under the tile copy.  Every other instantiation is,
+    // instruction for instruction, what it was before packed tops: it reads the flags where it branches on them.
+    static_assert(!T24 || (REG && DEP && !CODE8 && REGB == kRegBytes && K == 3 && !SPLIT), "packed tops: the 192-row tile on u16 codes");
+    uint32_t ms_flags = 0;  // (uniform: two scalar loads; the consumer wave issues them too and does not use them)
+    if (T24) ms_flags = chunk_flags[row0 >> cshift] | chunk_flags[(min(rows, row0 + TR) - 1) >> cshift];
     if (LDSX && NARROW && (uint32_t)reinterpret_cast<uintptr_t>(tile) != 0u) {
         // q_xread's v_bfi needs the tile at LDS address 0 (true while the kernel has no static LDS)
         if (tid == 0) atomicOr(error_flag, 2);
@@ -202,32 +211,68 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
     const uint32_t last_chunk = (uint32_t)(n_chunks - 1);
     const uint32_t po0 = 16u * min((uint32_t)(0 * 64 + lane), last_chunk), po1 = 16u * min((uint32_t)(1 * 64 + lane), last_chunk);
     const uint32_t po2 = 16u * min((uint32_t)(2 * 64 + lane), last_chunk), po3 = 16u * min((uint32_t)(3 * 64 + lane), last_chunk);
-    auto prefetch_top = [&](int t) {
-        const unsigned char *g = reinterpret_cast<const unsigned char *>(top + (size_t)t * top_stride);
-        pf0 = *reinterpret_cast<const uint4 *>(g + po0);
-        pf1 = *reinterpret_cast<const uint4 *>(g + po1);
-        pf2 = *reinterpret_cast<const uint4 *>(g + po2);
-        pf3 = *reinterpret_cast<const uint4 *>(g + po3);
+    // Packed tops (T24, tiles without a missing value).  The level loop of such a tile reads a node's code (bits 31:16) and fid
+    // (bits 14:7) only, 24 of the 32 bits, so its tops come from `top24`: 12 bytes per four nodes, a 10-level top in three
+    // 1-KiB wave-loads instead of four.  Lane l holds the 16-byte chunks l, 64 + l, 128 + l of a tree, 12 dwords that carry its
+    // four node groups 64 c + l (c = 0 .. 3; a group = nodes 4 g .. 4 g + 3, the 16 bytes the lane commits to slot chunk g): group
+    // c is dwords 3 c .. 3 c + 2 = A, B, F with A = code0 << 16 | code1, B = code2 << 16 | code3 and F the four fids, placed so
+    // that ONE v_perm_b32 per node builds code << 16 | fid << 7 (pack_top24 below); bits 15 and 6:0 of the word come out
+    // arbitrary.  The slot then holds u32 nodes as ever and the level loop is unchanged.  Tiles with a missing value need
+    // def_left (bit 15) and stage the u32 top.  PK selects the source at compile time: one kind per tile (run<MS, PK>).
+    const uint32_t last24 = (uint32_t)(top24_chunks - 1);  // (T24 only: top24_chunks >= 1 there; the offsets are dead code elsewhere)
+    const uint32_t qo0 = 16u * min((uint32_t)(0 * 64 + lane), last24), qo1 = 16u * min((uint32_t)(1 * 64 + lane), last24);
+    const uint32_t qo2 = 16u * min((uint32_t)(2 * 64 + lane), last24);
+    auto prefetch_top = [&](auto pk_tag, int t) {
+        if constexpr (decltype(pk_tag)::value) {
+            const unsigned char *g = reinterpret_cast<const unsigned char *>(top24 + (size_t)t * top24_chunks);
+            pf0 = *reinterpret_cast<const uint4 *>(g + qo0);
+            pf1 = *reinterpret_cast<const uint4 *>(g + qo1);
+            pf2 = *reinterpret_cast<const uint4 *>(g + qo2);
+        } else {
+            const unsigned char *g = reinterpret_cast<const unsigned char *>(top + (size_t)t * top_stride);
+            pf0 = *reinterpret_cast<const uint4 *>(g + po0);
+            pf1 = *reinterpret_cast<const uint4 *>(g + po1);
+            pf2 = *reinterpret_cast<const uint4 *>(g + po2);
+            pf3 = *reinterpret_cast<const uint4 *>(g + po3);
+        }
     };
     // Unconditional stores (a smaller top just rewrites its last chunk into unused slot space): with
     // per-lane conditions hipcc branches around each store AND its s_waitcnt, leaves the load "pending" on
     // the skipped path and then waits for the newest gathers at the loop latch.
-    auto commit_top = [&]() {
+    auto commit_top = [&](auto pk_tag) {
         uint4 *s = reinterpret_cast<uint4 *>(slot);
-        s[0 * 64 + lane] = pf0;
-        s[1 * 64 + lane] = pf1;
-        s[2 * 64 + lane] = pf2;
-        s[3 * 64 + lane] = pf3;
+        if constexpr (decltype(pk_tag)::value) {
+            auto expand = [](uint32_t a, uint32_t b, uint32_t f) {  // v_perm_b32: selector bytes 4 .. 7 = the code word's, 0 .. 3 = F's
+                return make_uint4(__builtin_amdgcn_perm(a, f, 0x07060100u), __builtin_amdgcn_perm(a, f, 0x05040302u),
+                                  __builtin_amdgcn_perm(b, f, 0x07060001u), __builtin_amdgcn_perm(b, f, 0x05040203u));
+            };
+            s[0 * 64 + lane] = expand(pf0.x, pf0.y, pf0.z);
+            s[1 * 64 + lane] = expand(pf0.w, pf1.x, pf1.y);
+            s[2 * 64 + lane] = expand(pf1.z, pf1.w, pf2.x);
+            s[3 * 64 + lane] = expand(pf2.y, pf2.z, pf2.w);
+        } else {
+            s[0 * 64 + lane] = pf0;
+            s[1 * 64 + lane] = pf1;
+            s[2 * 64 + lane] = pf2;
+            s[3 * 64 + lane] = pf3;
+        }
     };
+    const bool packed = T24 && ms_flags == 0;  // (uniform)
     if (t_begin + wave < t_end) {
-        prefetch_top(t_begin + wave);
-        commit_top();
+        if (packed) {
+            prefetch_top(std::true_type{}, t_begin + wave);
+            commit_top(std::true_type{});
+        } else {
+            prefetch_top(std::false_type{}, t_begin + wave);
+            commit_top(std::false_type{});
+        }
     }
     __syncthreads();  // the tile, the ring state and (own wave) the first top are in LDS
 
     bool dead = false;
-    auto run = [&](auto ms_tag) {
+    auto run = [&](auto ms_tag, auto pk_tag) {
         constexpr bool MS = decltype(ms_tag)::value;
+        static_assert(!(MS && decltype(pk_tag)::value), "a packed top has no def_left bits");
         uint32_t pos[K];  // byte position of this lane's row inside a 256-byte feature column, per chain
     #pragma unroll
         for (int k = 0; k < K; ++k)  // low 32 bits of a generic LDS pointer = the LDS byte address
@@ -294,7 +339,7 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
         for (int t = t_begin + wave; t < t_end && !dead; t += NWALK) {
             uint4 na[K], nb[K];
             gather(t_p >= 0 ? t_p : t, bsel_p, na, nb);
-            prefetch_top(t + NWALK < t_end ? t + NWALK : t);
+            prefetch_top(pk_tag, t + NWALK < t_end ? t + NWALK : t);
             uint32_t i[K];
     #pragma unroll
             for (int k = 0; k < K; ++k) i[k] = 1;
@@ -353,10 +398,22 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
                     }
                 }
                 }
+                if constexpr (T24) {
+                    // the last top level as the levels above it: the K feature reads first, then the compares.  (Written as one
+                    // loop, below, this instantiation's MS = true body came out with each chain's compares ahead of the next
+                    // chain's read -- the reads' latencies in a row -- and tiles with missing values walked 0.9 % slower.)
+                    uint32_t xc[K];
+    #pragma unroll
+                    for (int k = 0; k < K; ++k) xc[k] = q_xread<LDSX, NARROW, CS, CODE8, FB>(gx, node[k], pos[k]);
+                    __builtin_amdgcn_sched_barrier(0);  // (the scheduler keeps to that order)
+    #pragma unroll
+                    for (int k = 0; k < K; ++k) i[k] = q_descend(i[k], q_right_mask<MS, NARROW, EXCH, MISSC, DLB>(xc[k], node[k]));
+                } else {
     #pragma unroll
                 for (int k = 0; k < K; ++k) {
                     const uint32_t xc = q_xread<LDSX, NARROW, CS, CODE8, FB>(gx, node[k], pos[k]);
                     i[k] = q_descend(i[k], q_right_mask<MS, NARROW, EXCH, MISSC, DLB>(xc, node[k]));
+                }
                 }
             }
             uint32_t bsel[K];
@@ -377,7 +434,7 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
             t_p = t;
 #pragma unroll
             for (int k = 0; k < K; ++k) bsel_p[k] = bsel[k];
-            commit_top();  // this wave's reads of its slot are done (in-order LDS)
+            commit_top(pk_tag);  // this wave's reads of its slot are done (in-order LDS)
         }
         if (t_p >= 0 && !dead) {  // the last tree
             uint4 na[K], nb[K];
@@ -387,10 +444,17 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
     };
     // chunk_flags[c] != 0 <=> the quantise pass met a missing value in rows [c, c+1) << cshift; a 192-row tile can
     // straddle two chunks (a chunk is at least 512 rows)
-    if ((chunk_flags[row0 >> cshift] | chunk_flags[(min(rows, row0 + TR) - 1) >> cshift]) != 0)
-        run(std::true_type{});
-    else
-        run(std::false_type{});
+    if constexpr (T24) {  // (the flags were read at the top)
+        if (ms_flags != 0)
+            run(std::true_type{}, std::false_type{});
+        else
+            run(std::false_type{}, std::true_type{});
+    } else {
+        if ((chunk_flags[row0 >> cshift] | chunk_flags[(min(rows, row0 + TR) - 1) >> cshift]) != 0)
+            run(std::true_type{}, std::false_type{});
+        else
+            run(std::false_type{}, std::false_type{});
+    }
     ring_dead(dead, lane, error_flag);
 }
 
@@ -784,7 +848,7 @@ long long qring_lds_bytes(const tahoe_forest *f)
 // of u16 codes, 15 walkers); each form states only what it changes.  q_kernel<F, WL, MC> is the kernel of form F.
 struct QForm {
     static constexpr int nwalk = 15, k = 2, ring = kQRing, batch = kQBatch, regb = kRegBytes;
-    static constexpr bool ldsx = true, narrow = false, exch = false, reg = false, split = false, code8 = false, dep = false;
+    static constexpr bool ldsx = true, narrow = false, exch = false, reg = false, split = false, code8 = false, dep = false, top24 = false;
 };
 template <int N> struct QColumns : QForm { static constexpr int nwalk = N; };  // 15 / 12 / 8 / 4 walkers
 struct QNarrow : QForm { static constexpr bool narrow = true; };                // NARROW node words (num_cols <= 256)
@@ -802,6 +866,7 @@ struct QReg3 : QReg2 {  // the 192-row u16 tile
     static constexpr int nwalk = kReg3Walkers, k = 3, ring = kReg3Ring, batch = kReg3Batch;
     static constexpr bool dep = kReg3Dep;
 };
+struct QReg3P : QReg3 { static constexpr bool top24 = true; };  // ... of handles with packed tops (q->top24_chunks > 0)
 struct QReg8 : QReg2 {  // the 384-row u8 tile (32-KiB region stride)
     static constexpr int nwalk = kReg8Walkers, k = 6, ring = kReg8Ring, batch = kReg8Batch;
     static constexpr bool code8 = true, dep = kReg8Dep;
@@ -816,7 +881,7 @@ struct QSix16 : QReg8 {  // six 16-KiB regions of u16 codes (forests of <= 128 f
 };
 template <class F, bool WL, bool MC>
 constexpr auto q_kernel = &qring_kernel<F::nwalk, WL, F::ldsx, F::narrow, F::exch, F::k, F::reg, F::ring, F::split, F::batch, F::code8,
-                                        F::dep, F::regb, MC>;
+                                        F::dep, F::regb, MC, F::top24>;
 
 // Raises the dynamic-LDS limit of each form's two leaf-index instantiations (the multi-class ones with MC).
 template <bool MC, class... F>
@@ -835,6 +900,7 @@ static auto with_qreg_forms(const tahoe_qstate *q, Fn &&fn)
     if (q->code8 && q->narrow128) return fn(QReg8N{}, QReg2U8{}, QReg2U8Split{});
     if (q->code8) return fn(QReg8{}, QReg2U8{}, QReg2U8Split{});
     if (q->narrow128) return fn(QSix16{}, QReg2{}, QReg2Split{});
+    if (q->top24_chunks > 0) return fn(QReg3P{}, QReg2{}, QReg2Split{});
     return fn(QReg3{}, QReg2{}, QReg2Split{});
 }
 
@@ -846,6 +912,39 @@ static hipError_t qwide_allow(int limit)
 
 // Builds one tree group [lo, hi).  Returns TAHOE_OK with *too_many = the largest per-feature count when that
 // exceeds the limit (nothing is allocated then).
+// The packed tops of the 192-row u16 region form (qring_kernel, "packed tops"): per tree `chunks` 16-byte chunks; lane l of a
+// walker loads chunks l, 64 + l and 128 + l, whose 12 dwords are its node groups 64 c + l as A, B, F: the codes of nodes 4 g and
+// 4 g + 1, of 4 g + 2 and 4 g + 3, and the four fids -- fid0 in bits 14:7 and fid1 in bits 30:23 (where the node word has
+// them, under either code half), fid2 as bits 6:0 + 15 and fid3 as bits 22:16 + 31 (the same field after the kernel's v_perm
+// swaps the two bytes of that half).  def_left is dropped.
+static int top24_chunks_for(int top_levels)
+{
+    const int groups = std::max(1, (1 << top_levels) / 4);  // <= 64 groups: lane l needs dwords 0 .. 2 of chunk l only
+    return groups <= 64 ? groups : (groups / 64 * 3 + 3) / 4 * 64;
+}
+static std::vector<uint4> pack_top24(const std::vector<uint32_t> &h_top, size_t trees, size_t top_stride, size_t chunks)
+{
+    std::vector<uint4> out(trees * chunks, uint4{0u, 0u, 0u, 0u});
+    const size_t groups = top_stride / 4;
+    for (size_t t = 0; t < trees; ++t) {
+        uint32_t *d = reinterpret_cast<uint32_t *>(&out[t * chunks]);
+        for (size_t g = 0; g < groups; ++g) {
+            const uint32_t *n = &h_top[t * top_stride + 4 * g];
+            const size_t lane = g % 64, c = g / 64;
+            const uint32_t fid[4] = {(n[0] >> 7) & 0xFFu, (n[1] >> 7) & 0xFFu, (n[2] >> 7) & 0xFFu, (n[3] >> 7) & 0xFFu};
+            const uint32_t w[3] = {(n[0] & 0xFFFF0000u) | (n[1] >> 16), (n[2] & 0xFFFF0000u) | (n[3] >> 16),
+                                   (fid[0] << 7) | (fid[1] << 23) | (fid[2] >> 1) | ((fid[2] & 1u) << 15) | ((fid[3] >> 1) << 16) |
+                                       ((fid[3] & 1u) << 31)};
+            for (size_t j = 0; j < 3; ++j) {
+                const size_t k = 3 * c + j;  // of the lane's 12 dwords: dword k % 4 of its chunk k / 4
+                const size_t chunk = (k / 4) * 64 + lane;
+                if (chunk < chunks) d[chunk * 4 + k % 4] = w[j];
+            }
+        }
+    }
+    return out;
+}
+
 static tahoe_status build_group(tahoe_forest *f, const std::vector<InnerNode> &h_inner, const std::vector<unsigned char> &h_real,
                                 const std::vector<float> &h_leaf, size_t lo, size_t hi, tahoe_qgroup &g, int *too_many)
 {
@@ -931,6 +1030,10 @@ static tahoe_status build_group(tahoe_forest *f, const std::vector<InnerNode> &h
     hipError_t e;
     auto bad = [&](const char *what) { return fail(TAHOE_ERR_HIP, "qring_build: %s failed: %s", what, hipGetErrorString(e)); };
     if ((e = upload(&g.top, h_top, &f->device_bytes)) != hipSuccess) return bad("top");
+    if (q->top24_chunks > 0) {
+        const std::vector<uint4> h_top24 = pack_top24(h_top, Tg, top_stride, (size_t)q->top24_chunks);
+        if ((e = upload(&g.top24, h_top24, &f->device_bytes)) != hipSuccess) return bad("top24");
+    }
     if ((e = upload(&g.blocks, h_blocks, &f->device_bytes)) != hipSuccess) return bad("blocks");
     if (q->have_mid && (e = upload(&g.qinner, h_qinner, &f->device_bytes)) != hipSuccess)
         return bad("qinner");
@@ -940,7 +1043,7 @@ static tahoe_status build_group(tahoe_forest *f, const std::vector<InnerNode> &h
 static void free_group(tahoe_qgroup &g)
 {
     quantize_free_tables(g);
-    for (void *p : {(void *)g.top, (void *)g.blocks, (void *)g.qinner})
+    for (void *p : {(void *)g.top, (void *)g.top24, (void *)g.blocks, (void *)g.qinner})
         if (p) (void)hipFree(p);
     g = tahoe_qgroup();
 }
@@ -966,6 +1069,9 @@ tahoe_status qring_build(tahoe_forest *f, const std::vector<InnerNode> &h_inner,
         qring_destroy(f);
         return TAHOE_OK;
     }
+    // <= 128 features: regions at a 16-KiB LDS stride (q->narrow128, set once the groups are built)
+    const bool narrow128 = q->reg && cols <= 128 && qreg_lds_for(6, kReg8Walkers, kReg8Ring, false, kRegBytes / 2) <= f->lds_limit &&
+                           qreg_lds_for(6, 15, kQRing, true, kRegBytes / 2) <= f->lds_limit && f->knobs.qring_narrow128;
     // ---- cut the forest into tree groups whose features each see <= kQMaxTable distinct thresholds ----
     // G groups of (nearly) equal size, G as small as the busiest feature allows.  First guess from the distinct thresholds
     // per feature of the whole forest (a group of T / G trees sees at most that many, usually ~1 / G of them), then G grows
@@ -994,6 +1100,8 @@ tahoe_status qring_build(tahoe_forest *f, const std::vector<InnerNode> &h_inner,
         // such a handle has its own node encoding and only ever quantises to u8 (large batches, remainders and tree slices alike)
         q->code8 = q->reg && most <= (size_t)kQMaxTable8 && qreg_lds_for(6, kReg8Walkers, kReg8Ring, true) <= f->lds_limit &&
                    f->knobs.qring_code8;
+        // packed tops for the handles whose large tile is the 192-row tile on u16 codes (TAHOE_QRING_TOP24 = 0: none)
+        q->top24_chunks = q->reg && !q->code8 && !narrow128 && f->knobs.qring_top24 ? top24_chunks_for(q->top_levels) : 0;
         // TAHOE_QRING_GROUPS: at least this many groups (K4: 8 groups of 1000 trees take the bucketed quantise kernel, 4 of 2000
         // the two-pass one)
         G = std::max(G, (size_t)std::max(f->knobs.qring_groups, 1));
@@ -1029,9 +1137,7 @@ tahoe_status qring_build(tahoe_forest *f, const std::vector<InnerNode> &h_inner,
         }
         G = std::max(G + 1, (size_t)((double)G * worst / kQMaxTable + 0.999));
     }
-    // <= 128 features: regions at a 16-KiB LDS stride
-    q->narrow128 = q->reg && cols <= 128 && qreg_lds_for(6, kReg8Walkers, kReg8Ring, false, kRegBytes / 2) <= f->lds_limit &&
-                   qreg_lds_for(6, 15, kQRing, true, kRegBytes / 2) <= f->lds_limit && f->knobs.qring_narrow128;
+    q->narrow128 = narrow128;
     // kernels that need more than 64 KiB of dynamic LDS
     hipError_t e;
     auto bad = [&](const char *what) { return fail(TAHOE_ERR_HIP, "qring_build: %s failed: %s", what, hipGetErrorString(e)); };
@@ -1174,7 +1280,7 @@ static void q_launch(tahoe_forest *f, const tahoe_qgroup &g, float *sums, const 
         hipLaunchKernelGGL((q_kernel<F, decltype(wl)::value, decltype(mc)::value>), dim3(grid), dim3((F::nwalk + 1) * 64), lds, stream,
                            q->xq, g.top, g.blocks, g.qinner, leaf_orig, sums, leaf_out, rows, f->p.num_cols, g.num_trees, f->depth,
                            q->top_levels, q->top_stride, q->chunk_flags, f->error_flag, sums_in, g.tree_lo, f->p.num_trees, cshift,
-                           leafbuf, leaf_stride, slices, row_begin, nc);
+                           leafbuf, leaf_stride, slices, row_begin, nc, g.top24, q->top24_chunks);
     });
     const unsigned sum_blocks = (unsigned)((rows - row_begin + kOrderedSumThreads - 1) / kOrderedSumThreads);
     if (F::split && sums && nc > 1) {

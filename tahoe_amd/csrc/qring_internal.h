@@ -33,6 +33,7 @@ struct tahoe_qgroup {
     uint16_t *bstarts = nullptr;  // [cols][B + 2]: first sorted index of each bucket (entry B = n_f)
     float4 *bparams = nullptr;    // [cols]: lo, scale, steps (int bits), unused
     uint32_t *top = nullptr;      // [T_g][top_stride]
+    uint4 *top24 = nullptr;       // [T_g][top24_chunks]: the same tops without def_left, 3 bytes per node (qring.hip, "packed tops")
     uint4 *blocks = nullptr;      // [T_g][2^(De-2)][2]
     uint32_t *qinner = nullptr;   // [T_g][2^De - 1] (only when have_mid)
 };
@@ -41,6 +42,7 @@ struct tahoe_qstate {
     int top_levels = 0;
     bool have_mid = false;        // De - 2 > top_levels: heap of quantised nodes for the middle levels
     int top_stride = 0;           // u32 entries per tree in `top` (>= 4)
+    int top24_chunks = 0;         // 16-byte chunks per tree in the groups' `top24`; 0 = no packed tops on this handle
     bool narrow = false;          // node words in the NARROW layout (num_cols <= 256, 15 walkers, LDS tile)
     bool reg = false;             // ... in its region form: fid << 7, tiles of two or three 64-row regions (qring.hip)
     bool sparse = false;          // the handle is a sparse forest: tables, workspace and region tiles only (sparse.hip walks)

@@ -2,7 +2,8 @@
 // [256 cols][64*K rows] and one 10-level quantised top (4 KiB, u32 nodes, child pairs by ds_read_b64) per walker wave
 // in LDS; every wave repeats the 10-level walk with K independent 64-row chains.  No global-memory traffic in the
 // loop: prices the walk proper as a function of walker waves, chains per lane and loop form, and separates the LDS
-// and VALU ceilings (MODE 1: the LDS reads only, MODE 2: the VALU only).
+// and VALU ceilings (MODE 1: the LDS reads only, MODE 2: the VALU only).  --top-forms: the same loop by how the top is held
+// (u32 nodes, two 3-KiB forms in LDS, a packed top expanded at the commit; profiles/top24/ubench_levels.txt).
 // Build: hipcc --offload-arch=gfx950 -O3 -o tools/ubench_qwalk tools/ubench_qwalk.hip
 #include <hip/hip_runtime.h>
 
@@ -51,7 +52,23 @@ __device__ __forceinline__ uint32_t xaddr(uint32_t node, uint32_t posb)
     return a;
 }
 
-template <int NW, int K, int MODE, bool UNROLL, int COLB, bool DEP>
+// TOP (DEP, COLB = 128 only): how the top lies in its 4-KiB slot.
+//   0  u32 nodes, code << 16 | fid << 7 (what the product stages): v_bfi, cmp (SDWA WORD_1), addc, lshl_add + 2 LDS.
+//   1  byte-packed, 3 B per node: node i (1-based) = bytes 3i .. 3i+2 = fid | code_lo | code_hi, read with ONE dword read at byte
+//      3i - 1 (code in bits 31:16 as in form 0, fid in bits 15:8, the low byte is the previous node's): bfe, lshl_add, cmp, addc,
+//      mad_u24 + 2 LDS.  Three of four of those reads straddle two LDS dwords.
+//   2  two arrays, code[1024] u16 at the slot's start and fid[1024] u8 at byte 2048: lshl_add, cmp, addc, lshl_add, add + 3 LDS
+//      (aligned reads).
+//   3  form 0 whose slot every iteration rewrites from 16 dwords the lane holds (4 ds_write_b128): the commit of a prefetched top
+//      as the product does it once per tree; the base line of form 4.
+//   4  form 3 with the top held PACKED in 12 dwords per lane (what three 16-byte loads of a 3-KiB top in global memory bring) and
+//      expanded to u32 node words on the way to the slot: per four nodes A = code0 << 16 | code1, B = code2 << 16 | code3 and C =
+//      the four fids, placed so that ONE v_perm_b32 per node puts a fid into bits 14:7 under its code (bits 15 and 6:0 of a node
+//      word are then arbitrary; the level loop reads neither): 16 v_perm + 4 ds_write_b128 per iteration, the level loop is form 0's.
+// Forms 1, 2 and 4 hold a 10-level top in 3 KiB.  All walk the same tops to the same leaves (the host compares the sums).
+typedef uint32_t __attribute__((aligned(1))) u32_a1;
+
+template <int NW, int K, int MODE, bool UNROLL, int COLB, bool DEP, int TOP = 0>
 __global__ void __launch_bounds__(NW * 64) qwalk(const uint16_t *__restrict__ tile_src, const uint32_t *__restrict__ top_src, int iters,
                                                  uint32_t *__restrict__ out)
 {
@@ -63,7 +80,22 @@ __global__ void __launch_bounds__(NW * 64) qwalk(const uint16_t *__restrict__ ti
     for (int e = tid; e < TILEB / 2; e += NW * 64) tile[e] = tile_src[e % (COLS * 128)];
     uint32_t *slot = reinterpret_cast<uint32_t *>(smem + TILEB + wave * 4096);
     const uint32_t *src = top_src + (size_t)((blockIdx.x * NW + wave) % 64) * 1024;
-    for (int i = lane; i < 1024; i += 64) slot[i] = src[i];
+    static_assert(TOP == 0 || (DEP && COLB == 128), "packed tops: the chosen-child form on 64-row regions");
+    static_assert(TOP >= 0 && TOP <= 4, "top form");
+    for (int i = lane; i < 1024; i += 64) {
+        const uint32_t n = src[i];
+        if (TOP == 0 || TOP >= 3) {
+            slot[i] = n;
+        } else if (TOP == 1) {
+            unsigned char *b = reinterpret_cast<unsigned char *>(slot) + 3 * i;
+            b[0] = (unsigned char)(n >> 7);
+            b[1] = (unsigned char)(n >> 16);
+            b[2] = (unsigned char)(n >> 24);
+        } else {
+            reinterpret_cast<uint16_t *>(slot)[i] = (uint16_t)(n >> 16);
+            reinterpret_cast<unsigned char *>(slot)[2048 + i] = (unsigned char)(n >> 7);
+        }
+    }
     __syncthreads();
     const uint32_t slot_a = (uint32_t)reinterpret_cast<uintptr_t>(slot);
     uint32_t pos[K];
@@ -72,8 +104,99 @@ __global__ void __launch_bounds__(NW * 64) qwalk(const uint16_t *__restrict__ ti
         pos[k] = COLB == 128 ? (uint32_t)(k * COLS * 128) + (uint32_t)(((lane & 31) << 2) | ((lane >> 5) << 1))
                          : 2u * (uint32_t)(k * 64 + lane);
     uint32_t acc = 0;
+    if (TOP == 1 || TOP == 2) {  // (the same data-dependent start as form 0: bits 14:8 of its node word are bits 7:1 of the fid)
+        typedef const u32_a1 __attribute__((address_space(3))) *lds_u32a1_ptr;
+        typedef const unsigned char __attribute__((address_space(3))) *lds_u8_ptr;
+        const uint32_t slot_m1 = slot_a - 1u;
+        for (int it = 0; it < iters; ++it) {
+            uint32_t i[K], node[K], fid[K];
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                i[k] = 1;
+                if (TOP == 1) {
+                    node[k] = *reinterpret_cast<lds_u32a1_ptr>(slot_m1 + 3u) ^ ((acc & 0x7fu) << 9);
+                } else {
+                    node[k] = *reinterpret_cast<lds_u16_ptr>(slot_a + 2u);
+                    fid[k] = *reinterpret_cast<lds_u8_ptr>(slot_a + 2048u + 1u) ^ ((acc & 0x7fu) << 1);
+                }
+            }
+            auto xa = [&](int k) {
+                uint32_t a;
+                if (TOP == 1)
+                    asm("v_bfe_u32 %0, %1, 8, 8\n\tv_lshl_add_u32 %0, %0, 7, %2" : "=&v"(a) : "v"(node[k]), "v"(pos[k]));
+                else
+                    asm("v_lshl_add_u32 %0, %1, 7, %2" : "=v"(a) : "v"(fid[k]), "v"(pos[k]));
+                return a;
+            };
+            auto right = [&](int k, uint32_t xc) { return __builtin_amdgcn_uicmp(xc, TOP == 1 ? node[k] >> 16 : node[k], 35); };
+            auto level = [&]() {
+                uint32_t xc[K];
+#pragma unroll
+                for (int k = 0; k < K; ++k) xc[k] = *reinterpret_cast<lds_u16_ptr>(xa(k));
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    i[k] = descend(i[k], right(k, xc[k]));
+                    if (TOP == 1) {
+                        uint32_t a;
+                        asm("v_mad_u32_u24 %0, %1, 3, %2" : "=v"(a) : "v"(i[k]), "v"(slot_m1));
+                        node[k] = *reinterpret_cast<lds_u32a1_ptr>(a);
+                    } else {
+                        node[k] = *reinterpret_cast<lds_u16_ptr>(slot_a + 2u * i[k]);
+                        fid[k] = *reinterpret_cast<lds_u8_ptr>(slot_a + 2048u + i[k]);
+                    }
+                }
+            };
+            if (UNROLL) {
+#pragma unroll
+                for (int l = 0; l < LEVELS - 1; ++l) level();
+            } else {
+#pragma unroll 1
+                for (int l = 0; l < LEVELS - 1; ++l) level();
+            }
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                i[k] = descend(i[k], right(k, *reinterpret_cast<lds_u16_ptr>(xa(k))));
+                acc += i[k];
+            }
+        }
+        out[(size_t)blockIdx.x * NW * 64 + tid] = acc;
+        return;
+    }
+    uint32_t held[16] = {};  // forms 3 and 4: this lane's 16 nodes (groups of four at slot words 4 * (64 c + lane)), form 4: packed into 12
+    if (TOP >= 3) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            uint32_t n[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) n[j] = slot[4 * (64 * c + lane) + j];
+            if (TOP == 3) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) held[4 * c + j] = n[j];
+            } else {
+                const uint32_t f2 = (n[2] >> 7) & 0xffu, f3 = (n[3] >> 7) & 0xffu;
+                held[3 * c + 0] = (n[0] & 0xffff0000u) | (n[1] >> 16);
+                held[3 * c + 1] = (n[2] & 0xffff0000u) | (n[3] >> 16);
+                held[3 * c + 2] = (n[0] & 0x7f80u) | ((n[1] & 0x7f80u) << 16) | (f2 >> 1) | ((f2 & 1u) << 15) | ((f3 >> 1) << 16) | ((f3 & 1u) << 31);
+            }
+        }
+    }
     for (int it = 0; it < iters; ++it) {
         uint32_t i[K], node[K];
+        if (TOP >= 3) {  // the commit (the registers are made opaque: the expansion is paid every iteration, as per tree)
+#pragma unroll
+            for (int q = 0; q < (TOP == 3 ? 16 : 12); ++q) asm volatile("" : "+v"(held[q]));
+            uint4 *s4 = reinterpret_cast<uint4 *>(slot);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                if (TOP == 3) {
+                    s4[64 * c + lane] = make_uint4(held[4 * c], held[4 * c + 1], held[4 * c + 2], held[4 * c + 3]);
+                } else {
+                    const uint32_t a = held[3 * c], b = held[3 * c + 1], f = held[3 * c + 2];
+                    s4[64 * c + lane] = make_uint4(__builtin_amdgcn_perm(a, f, 0x07060100u), __builtin_amdgcn_perm(a, f, 0x05040302u),
+                                                   __builtin_amdgcn_perm(b, f, 0x07060001u), __builtin_amdgcn_perm(b, f, 0x05040203u));
+                }
+            }
+        }
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             i[k] = 1;
@@ -171,11 +294,11 @@ static void run(const uint16_t *tile, const uint32_t *tops, uint32_t *out)
 
 // --kernel-shape: only the shape the product's K3 walk runs (14 walker waves x 3 chains on 64-row regions, child pairs,
 // unrolled), best of 5 launches, as one JSON line: bench.py runs this as a child process for roofline.physical.walk.lds_walk_ceiling.
-template <int NW, int K, bool DEP>
+template <int NW, int K, bool DEP, bool UNROLL = true, int TOP = 0>
 static float best_ms(const uint16_t *tile, const uint32_t *tops, uint32_t *out, int cus, int iters)
 {
     const int lds = COLS * 128 * K + NW * 4096;
-    CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&qwalk<NW, K, 0, true, 128, DEP>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&qwalk<NW, K, 0, UNROLL, 128, DEP, TOP>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     hipEvent_t e0, e1;
     CHECK(hipEventCreate(&e0));
     CHECK(hipEventCreate(&e1));
@@ -183,7 +306,7 @@ static float best_ms(const uint16_t *tile, const uint32_t *tops, uint32_t *out, 
     for (int rep = 0; rep < 6; ++rep) {
         float ms = 0;
         CHECK(hipEventRecord(e0));
-        hipLaunchKernelGGL((qwalk<NW, K, 0, true, 128, DEP>), dim3(cus), dim3(NW * 64), lds, 0, tile, tops, iters, out);
+        hipLaunchKernelGGL((qwalk<NW, K, 0, UNROLL, 128, DEP, TOP>), dim3(cus), dim3(NW * 64), lds, 0, tile, tops, iters, out);
         CHECK(hipEventRecord(e1));
         CHECK(hipEventSynchronize(e1));
         CHECK(hipEventElapsedTime(&ms, e0, e1));
@@ -210,6 +333,44 @@ static void run_json(const uint16_t *tile, const uint32_t *tops, uint32_t *out)
            best * 1e6 / wave_levels_per_cu, prop.clockRate / 1000);
 }
 
+// --top-forms: the level loop in the product's K3 shape (14 walker waves x 3 chains, 64-row regions) for the four ways to hold and
+// read a top -- child pairs and the chosen child on u32 nodes, the byte-packed and the two-array 3-KiB tops -- as the loop the
+// kernel runs (levels not unrolled: top_levels is a run-time value) and unrolled.  Best of 5 launches; `sum` is the sum of all
+// lanes' leaf positions, equal for forms that walked the same paths (the pair form perturbs its start differently: not compared).
+template <int NW, int K, bool DEP, bool UNROLL, int TOP>
+static void run_top(const char *name, const uint16_t *tile, const uint32_t *tops, uint32_t *out, int cus)
+{
+    const int iters = 2400 / K;
+    const float ms = best_ms<NW, K, DEP, UNROLL, TOP>(tile, tops, out, cus, iters);
+    std::vector<uint32_t> h((size_t)cus * NW * 64);
+    CHECK(hipMemcpy(h.data(), out, h.size() * 4, hipMemcpyDeviceToHost));
+    uint64_t sum = 0;
+    for (uint32_t v : h) sum += v;
+    const double wave_levels_per_cu = (double)NW * iters * K * LEVELS;
+    printf("NW %2d K %d %-34s %s : %7.3f ms  %6.3f clk per wave-level per CU at 2.4 GHz  sum %016llx\n", NW, K, name,
+           UNROLL ? "unrolled" : "loop    ", ms, ms * 1e-3 * 2.4e9 / wave_levels_per_cu, (unsigned long long)sum);
+}
+template <int NW, int K>
+static void run_top_forms(const uint16_t *tile, const uint32_t *tops, uint32_t *out)
+{
+    hipDeviceProp_t prop;
+    CHECK(hipGetDeviceProperties(&prop, 0));
+    const int cus = prop.multiProcessorCount < 256 ? prop.multiProcessorCount : 256;
+    printf("%d CUs, clock %d MHz\n", cus, prop.clockRate / 1000);
+    run_top<NW, K, false, false, 0>("u32 nodes, child pairs (5+2)", tile, tops, out, cus);
+    run_top<NW, K, true, false, 0>("u32 nodes, chosen child (4+2)", tile, tops, out, cus);
+    run_top<NW, K, true, false, 1>("3-B nodes, straddling dword (5+2)", tile, tops, out, cus);
+    run_top<NW, K, true, false, 2>("u16 code + u8 fid arrays (5+3)", tile, tops, out, cus);
+    run_top<NW, K, true, false, 3>("u32 nodes, commit per iteration", tile, tops, out, cus);
+    run_top<NW, K, true, false, 4>("... from 12 packed dwords, 16 perm", tile, tops, out, cus);
+    run_top<NW, K, false, true, 0>("u32 nodes, child pairs (5+2)", tile, tops, out, cus);
+    run_top<NW, K, true, true, 0>("u32 nodes, chosen child (4+2)", tile, tops, out, cus);
+    run_top<NW, K, true, true, 1>("3-B nodes, straddling dword (5+2)", tile, tops, out, cus);
+    run_top<NW, K, true, true, 2>("u16 code + u8 fid arrays (5+3)", tile, tops, out, cus);
+    run_top<NW, K, true, true, 3>("u32 nodes, commit per iteration", tile, tops, out, cus);
+    run_top<NW, K, true, true, 4>("... from 12 packed dwords, 16 perm", tile, tops, out, cus);
+}
+
 int main(int argc, char **argv)
 {
     uint64_t s = 99;
@@ -230,6 +391,10 @@ int main(int argc, char **argv)
     CHECK(hipMemcpy(d_tops, h_tops.data(), h_tops.size() * 4, hipMemcpyHostToDevice));
     if (argc > 1 && std::string(argv[1]) == "--kernel-shape") {
         run_json<14, 3>(d_tile, d_tops, d_out);
+        return 0;
+    }
+    if (argc > 1 && std::string(argv[1]) == "--top-forms") {
+        run_top_forms<14, 3>(d_tile, d_tops, d_out);
         return 0;
     }
 
