@@ -522,7 +522,8 @@ typedef struct {
  * Out of scope, TAHOE_ERR_UNSUPPORTED with nothing launched and a text that says "oblivious": tahoe_forest_predict_csr,
  * _reserve_csr (and _get_csr_plan: form TAHOE_FORM_NONE), _predict_host, _set_stages, _predict_staged (_get_staged_strategy: 0),
  * _predict_contribs, _predict_contribs_approx, _predict_interactions, and _set_background with
- * _predict_contribs_interventional, unless the handle comes from tahoe_oblivious_forest_create_ex with that call's flag.  CatBoost's one-hot splits are
+ * _predict_contribs_interventional, unless the handle comes from tahoe_oblivious_forest_create_ex with that call's flag
+ * (TAHOE_CREATE_STAGED for the three staged calls).  CatBoost's one-hot splits are
  * category sets (tahoe_oblivious_forest_create_cat); a CTR split is a border on a column the caller computes. */
 tahoe_status tahoe_oblivious_forest_create(tahoe_forest **out, const int32_t *depths, const tahoe_oblivious_split *splits,
                                            const float *leaf_values, const tahoe_forest_params *params, int leaf_dim);
@@ -534,8 +535,17 @@ tahoe_status tahoe_oblivious_forest_create(tahoe_forest **out, const int32_t *de
  * TAHOE_CREATE_INTERVENTIONAL, 0x80, which stays an unknown flag on this create), alone -- it needs no covers -- or with any of the
  * three flags above. */
 #define TAHOE_CREATE_OBLIVIOUS_INTERVENTIONAL 0x200u
+/* Staged prediction on an oblivious or a vector-leaf handle (tahoe_forest_set_stages, tahoe_forest_predict_staged,
+ * tahoe_forest_get_staged_strategy; CatBoost's staged_predict / ntree_end, XGBoost's iteration_range on multi_output_tree models, a
+ * random forest's output against n_estimators): accepted by tahoe_oblivious_forest_create_ex, tahoe_oblivious_forest_create_cat
+ * and tahoe_vector_forest_create_ex, alone -- it reads no cover: leaf_covers / covers may be NULL -- or beside any of their other
+ * flags; every other create refuses it as an unknown flag.  It builds no table: device_bytes is that of the handle without it until
+ * stages are set, and everything else the handle serves is bit for bit what the handle without the flag gives.  A handle created
+ * without it keeps refusing the three calls, with the same codes and texts as before the flag existed. */
+#define TAHOE_CREATE_STAGED 0x2000u
 /* The same handle with explanations.  flags: a subset of TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS |
- * TAHOE_CREATE_INTERACTIONS | TAHOE_CREATE_OBLIVIOUS_INTERVENTIONAL, each serving its own call(s) and no other; with flags == 0
+ * TAHOE_CREATE_INTERACTIONS | TAHOE_CREATE_OBLIVIOUS_INTERVENTIONAL | TAHOE_CREATE_STAGED (staged prediction, stated at the flag
+ * and at tahoe_forest_set_stages; Tc = num_trees, C = K), each serving its own call(s) and no other; with flags == 0
  * leaf_covers is ignored and the call is tahoe_oblivious_forest_create (which is this call with NULL, 0).  leaf_covers holds
  * sum_t 2^depths[t] floats, one per leaf in the order of the leaves: the training weight that reached the leaf (CatBoost's
  * leaf_weights).  Checks, before a device is touched and after those of tahoe_oblivious_forest_create: another flag bit, or one of
@@ -581,7 +591,7 @@ tahoe_status tahoe_oblivious_forest_create_ex(tahoe_forest **out, const int32_t 
                                               const float *leaf_values, const float *leaf_covers,
                                               const tahoe_forest_params *params, int leaf_dim, unsigned flags);
 /* tahoe_oblivious_forest_create_ex with category-set splits (CatBoost's one-hot splits; a set of any size).  Everything but cats
- * is as there: the same four flags, each serving its own call(s); TAHOE_CREATE_CAT_CONTRIBS stays an unknown flag here, because
+ * is as there: the same four flags and TAHOE_CREATE_STAGED, each serving its own call(s); TAHOE_CREATE_CAT_CONTRIBS stays an unknown flag here, because
  * no explanation table of an oblivious handle holds a threshold or an interval -- every explanation follows the sets as it stands.
  * cats is the struct of tahoe_sparse_forest_create_cat in the same word layout; cats->node[k] is an index into splits[], the record
  * of one (tree, level), strictly ascending in [0, sum_t depths[t]).  At such a level thr is ignored, fid and def_left keep their
@@ -603,8 +613,8 @@ tahoe_status tahoe_oblivious_forest_create_ex(tahoe_forest **out, const int32_t 
  * The explanation tables share that pool and grow by nothing.
  * Served, under the same flags and with the same kernel forms, strategies (DIRECT, ROWTILE, AUTO) and graph capture: everything
  * tahoe_oblivious_forest_create_ex serves -- tahoe_forest_predict, _predict_raw, _predict_leaf_idx, _predict_accumulate (K == 1),
- * _reserve, _predict_contribs, _predict_contribs_approx, _predict_interactions, _set_background and
- * _predict_contribs_interventional, their definitions unchanged except that "the row's bit at a level" is the rule above.  The
+ * _reserve, _predict_contribs, _predict_contribs_approx, _predict_interactions, _set_background,
+ * _predict_contribs_interventional, and _set_stages / _predict_staged / _get_staged_strategy, their definitions unchanged except that "the row's bit at a level" is the rule above.  The
  * elements of a tree are still its distinct features in order of first appearance, whether a feature appears numeric,
  * categorical, or both.  What that handle refuses stays refused with the same texts. */
 tahoe_status tahoe_oblivious_forest_create_cat(tahoe_forest **out, const int32_t *depths, const tahoe_oblivious_split *splits,
@@ -643,7 +653,8 @@ tahoe_status tahoe_oblivious_forest_create_cat(tahoe_forest **out, const int32_t
  * AUTO = ROWTILE when the tile fits, else DIRECT; TILEBLOCK, TILERING and QRING are TAHOE_ERR_UNSUPPORTED.
  * Out of scope, TAHOE_ERR_UNSUPPORTED with nothing launched and a text that names the call and says "vector-leaf":
  * tahoe_forest_predict_accumulate, _predict_host, _predict_csr, _reserve_csr (and _get_csr_plan: form TAHOE_FORM_NONE),
- * _set_stages, _predict_staged (_get_staged_strategy: 0); _predict_contribs_approx unless the handle comes from _create_ex with
+ * _set_stages, _predict_staged (_get_staged_strategy: 0) unless the handle comes from _create_ex with TAHOE_CREATE_STAGED;
+ * _predict_contribs_approx unless the handle comes from _create_ex with
  * TAHOE_CREATE_VECTOR_APPROX; _predict_contribs unless the handle comes from tahoe_vector_forest_create_ex with
  * TAHOE_CREATE_CONTRIBS; _set_background and _predict_contribs_interventional unless it
  * comes from there with TAHOE_CREATE_INTERVENTIONAL; _predict_interactions unless it comes from there with
@@ -662,7 +673,8 @@ tahoe_status tahoe_vector_forest_create(tahoe_forest **out, const int32_t *trees
  * TAHOE_CREATE_APPROX_CONTRIBS (0x10), which stays an unknown flag on that create, as does 0x200. */
 #define TAHOE_CREATE_VECTOR_APPROX 0x400u
 /* The same handle with explanations.  flags: a subset of TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_INTERVENTIONAL |
- * TAHOE_CREATE_VECTOR_INTERACTIONS | TAHOE_CREATE_VECTOR_APPROX; with flags == 0 covers is ignored and the call is tahoe_vector_forest_create (which is this
+ * TAHOE_CREATE_VECTOR_INTERACTIONS | TAHOE_CREATE_VECTOR_APPROX | TAHOE_CREATE_STAGED (staged prediction, stated at the flag and
+ * at tahoe_forest_set_stages; Tc = num_trees, C = K; it reads no covers and joins none of the checks below); with flags == 0 covers is ignored and the call is tahoe_vector_forest_create (which is this
  * call with NULL, 0), bit for bit; a handle created without TAHOE_CREATE_INTERVENTIONAL or without
  * TAHOE_CREATE_VECTOR_INTERACTIONS is bit for bit and byte for byte what it was before that flag existed.  With
  * TAHOE_CREATE_CONTRIBS covers[i] is the cover of nodes[i] (num_nodes floats; scikit-learn's tree_.weighted_n_node_samples).
@@ -803,7 +815,9 @@ tahoe_status tahoe_forest_predict_accumulate(tahoe_forest *f, float *sums_dev, c
  * (NULL, 0) clears them.  Refusals, TAHOE_ERR_INVALID_ARG with a text that names the offending index, checked before a device is
  * touched: a NULL handle, num_stages < 0, NULL rounds with num_stages > 0, a value outside [1, Tc], a value not above its
  * predecessor.  On any refusal the previous stages stay.  Served on dense, multi-class, sparse, multi-class sparse and
- * categorical handles. */
+ * categorical handles, and on oblivious and vector-leaf handles created with TAHOE_CREATE_STAGED (without the flag:
+ * TAHOE_ERR_UNSUPPORTED, as stated at their creates).  There every tree feeds every class: Tc = num_trees, C = K = leaf_dim, and
+ * stage s is the forest of trees 0 .. rounds[s] - 1; a forest without trees has no valid stage. */
 tahoe_status tahoe_forest_set_stages(tahoe_forest *f, const int32_t *rounds, int num_stages);
 /* out_dev[(row * S + s) * C + c], S = num_stages <- bit for bit what tahoe_forest_predict writes for that row and class on a
  * handle created with the same parameters from the trees of stage s, output bits included, applied as that handle applies
@@ -813,15 +827,19 @@ tahoe_status tahoe_forest_set_stages(tahoe_forest *f, const int32_t *rounds, int
  * Strategies with a staged form: DIRECT and ROWTILE on dense and multi-class handles; DIRECT, ROWTILE and TILEBLOCK on sparse,
  * multi-class sparse and categorical handles.  A forced strategy of that set is honoured.  Under AUTO a dense handle takes
  * ROWTILE when its tile fits LDS, else DIRECT; a sparse handle TILEBLOCK when available, else ROWTILE, else DIRECT -- whatever
- * AUTO picks for tahoe_forest_predict.  QRING, TILERING and dense TILEBLOCK have no staged form.
+ * AUTO picks for tahoe_forest_predict.  QRING, TILERING and dense TILEBLOCK have no staged form.  An oblivious or vector-leaf
+ * handle created with TAHOE_CREATE_STAGED runs DIRECT or ROWTILE, whichever tahoe_forest_predict resolves for its strategy
+ * setting (AUTO: ROWTILE when the 256 x num_cols-byte tile fits LDS, else DIRECT); "the same parameters" then means the same create
+ * call, parameters and category sets on trees 0 .. rounds[s] - 1, and AVG divides by (float)rounds[s] whatever K is.
  * Refusals, in this order, nothing launched: a NULL handle: TAHOE_ERR_INVALID_ARG; no stages set: TAHOE_ERR_UNSUPPORTED
  * (tahoe_last_error says so); a forced strategy without a staged form: TAHOE_ERR_UNSUPPORTED; then rows == 0: TAHOE_OK; NULL
  * out_dev / data_dev with rows > 0: TAHOE_ERR_INVALID_ARG; rows * S * C * 4 overflowing size_t: TAHOE_ERR_INVALID_ARG.
- * Out of scope: CSR rows (densify, or use tahoe_forest_predict_csr per truncated handle), a staged
+ * Out of scope, on every handle kind: CSR rows (densify, or use tahoe_forest_predict_csr per truncated handle), a staged
  * tahoe_forest_predict_accumulate, staged leaf indices, and a start round other than 0. */
 tahoe_status tahoe_forest_predict_staged(tahoe_forest *f, float *out_dev, const float *data_dev, size_t rows, void *stream);
 /* The strategy tahoe_forest_predict_staged runs for `rows` rows (TAHOE_STRATEGY_DIRECT, _ROWTILE or _TILEBLOCK); 0 when the call
- * would be refused (no stages set, or a forced strategy without a staged form); -1 for a NULL handle. */
+ * would be refused (no stages set, or a forced strategy without a staged form); -1 for a NULL handle.  Served on the handles
+ * tahoe_forest_set_stages serves; an oblivious or vector-leaf handle gives DIRECT or ROWTILE. */
 int tahoe_forest_get_staged_strategy(const tahoe_forest *f, size_t rows);
 
 /* leaf_dev[row * num_trees + tree] <- index of the leaf the row ends in, in the tree's original heap

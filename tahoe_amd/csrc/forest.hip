@@ -1184,10 +1184,12 @@ tahoe_status predict_rows(tahoe_forest *f, float *preds, const float *data, size
 
 // The strategy of tahoe_forest_predict_staged: a forced one that has a staged form, or AUTO's -- the tile kernel that needs no
 // pre-pass (a sparse handle: TILEBLOCK, else ROWTILE, else DIRECT; a dense one: ROWTILE when its tile fits LDS, else DIRECT).
+// An oblivious or vector-leaf handle (TAHOE_CREATE_STAGED) walks as tahoe_forest_predict does: DIRECT or ROWTILE, AUTO by its tile.
 // 0: no stages are set, or the forced strategy (QRING, TILERING, dense TILEBLOCK) has no staged form.
 static int staged_strategy(const tahoe_forest *f)
 {
-    if (!f->stages_dev) return 0;  // (an oblivious or vector-leaf handle never has stages)
+    if (!f->stages_dev) return 0;  // (an oblivious or vector-leaf handle without TAHOE_CREATE_STAGED never has stages)
+    if (f->ob || f->vl) return resolve_strategy(f, 0);  // (never a third strategy: strategy_available)
     const int forced = f->strategy;  // (tahoe_forest_set_strategy has checked that the handle can run it)
     if (forced == TAHOE_STRATEGY_DIRECT || forced == TAHOE_STRATEGY_ROWTILE) return forced;
     if (f->sp) {
@@ -1554,8 +1556,7 @@ tahoe_status tahoe_forest_set_stages(tahoe_forest *f, const int32_t *rounds, int
 {
     // every check here runs before a device is touched
     if (!f) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_set_stages: null forest");
-    if (const tahoe_status s = refuse_oblivious(f, "tahoe_forest_set_stages")) return s;
-    if (const tahoe_status s = refuse_vector(f, "tahoe_forest_set_stages")) return s;
+    if (const tahoe_status s = refuse_unstaged(f, "tahoe_forest_set_stages")) return s;
     if (num_stages < 0) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_set_stages: num_stages must be non-negative, got %d", num_stages);
     if (num_stages > 0 && !rounds) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_set_stages: rounds is null with num_stages %d", num_stages);
     for (int s = 0; s < num_stages; ++s) {
@@ -1571,7 +1572,11 @@ tahoe_status tahoe_forest_set_stages(tahoe_forest *f, const int32_t *rounds, int
     if (num_stages > 0) {
         // the staged tile kernels of this handle's kind may need more than the default 64 KiB of dynamic LDS
         hipError_t e = hipSuccess;
-        if (f->sp) {
+        if (f->ob) {
+            if (const tahoe_status s = oblivious_allow_staged_lds(f)) return s;
+        } else if (f->vl) {
+            if (const tahoe_status s = vector_allow_staged_lds(f)) return s;
+        } else if (f->sp) {
             if (const tahoe_status s = sparse_allow_staged_lds(f)) return s;
         } else if (rowtile_fits(f) &&
                    (e = allow_max_lds(f->num_classes > 1 ? reinterpret_cast<const void *>(&rowtile_kernel<false, true, false, true>)
@@ -1603,8 +1608,7 @@ int tahoe_forest_get_staged_strategy(const tahoe_forest *f, size_t rows) { retur
 tahoe_status tahoe_forest_predict_staged(tahoe_forest *f, float *out_dev, const float *data_dev, size_t rows, void *stream)
 {
     if (!f) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_staged: null forest");
-    if (const tahoe_status s = refuse_oblivious(f, "tahoe_forest_predict_staged")) return s;
-    if (const tahoe_status s = refuse_vector(f, "tahoe_forest_predict_staged")) return s;
+    if (const tahoe_status s = refuse_unstaged(f, "tahoe_forest_predict_staged")) return s;
     if (!f->stages_dev)
         return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_staged: no stages are set (tahoe_forest_set_stages)");
     const int strategy = staged_strategy(f);
@@ -1620,8 +1624,10 @@ tahoe_status tahoe_forest_predict_staged(tahoe_forest *f, float *out_dev, const 
     if ((rows + 63) / 64 > 0x7fffffffu) return fail(TAHOE_ERR_INVALID_ARG, "too many rows for one launch: %zu", rows);
     DeviceGuard on_device(f->device);
     hipStream_t st = (hipStream_t)stream;
-    const tahoe_status ws = f->sp ? sparse_launch_staged(f, out_dev, data_dev, rows, st, strategy)
-                                  : launch_staged_dense(f, out_dev, data_dev, rows, st, strategy);
+    const tahoe_status ws = f->ob   ? oblivious_launch_staged(f, out_dev, data_dev, rows, st, strategy)
+                            : f->vl ? vector_launch_staged(f, out_dev, data_dev, rows, st, strategy)
+                            : f->sp ? sparse_launch_staged(f, out_dev, data_dev, rows, st, strategy)
+                                    : launch_staged_dense(f, out_dev, data_dev, rows, st, strategy);
     if (ws != TAHOE_OK) return ws;
     // (as predict_rows: the transform runs only when it changes something)
     if (f->p.output == TAHOE_OUT_RAW && f->p.global_bias == 0.0f) return TAHOE_OK;

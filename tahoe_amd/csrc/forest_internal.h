@@ -141,6 +141,9 @@ struct tahoe_forest {
     // (trees per class), on the device; null = none set
     int32_t *stages_dev = nullptr;
     size_t num_stages = 0;
+    // An oblivious or vector-leaf handle created with TAHOE_CREATE_STAGED: the three staged calls are served (every other handle
+    // kind serves them without a flag)
+    bool staged = false;
 };
 
 namespace tahoe {
@@ -560,6 +563,10 @@ void contribs_destroy(tahoe_forest *f);
 bool oblivious_tile_fits(const tahoe_forest *f);
 tahoe_status oblivious_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data, size_t rows, hipStream_t stream,
                               int strategy, const float *sums_in);
+// tahoe_forest_predict_staged on a handle created with TAHOE_CREATE_STAGED: the same walk (DIRECT or ROWTILE) with the stage stores
+// to out[rows][num_stages][K]; oblivious_allow_staged_lds lets its tile kernel take the device's LDS (set_stages calls it)
+tahoe_status oblivious_launch_staged(tahoe_forest *f, float *out, const float *data, size_t rows, hipStream_t stream, int strategy);
+tahoe_status oblivious_allow_staged_lds(const tahoe_forest *f);
 void oblivious_destroy(tahoe_forest *f);
 // ... its explanations (oblivious_shap.hip).  oblivious_serves: was the handle created with `flag` (TAHOE_CREATE_CONTRIBS,
 // TAHOE_CREATE_APPROX_CONTRIBS or TAHOE_CREATE_INTERACTIONS)?  oblivious_predict_shap: the call of one of the first two flags on
@@ -585,6 +592,9 @@ inline tahoe_status refuse_oblivious(const tahoe_forest *f, const char *fn)
 bool vector_tile_fits(const tahoe_forest *f);
 tahoe_status vector_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data, size_t rows, hipStream_t stream,
                            int strategy);
+// ... and the same pair for a vector-leaf handle created with TAHOE_CREATE_STAGED
+tahoe_status vector_launch_staged(tahoe_forest *f, float *out, const float *data, size_t rows, hipStream_t stream, int strategy);
+tahoe_status vector_allow_staged_lds(const tahoe_forest *f);
 void vector_destroy(tahoe_forest *f);
 // ... its TreeSHAP (vector_shap.hip).  vector_serves_contribs: was the handle created with TAHOE_CREATE_CONTRIBS?
 // vector_predict_contribs: tahoe_forest_predict_contribs on such a handle, entry checks included (fn: the call's name)
@@ -609,6 +619,13 @@ inline tahoe_status refuse_vector(const tahoe_forest *f, const char *fn)
 {
     if (!f->vl) return TAHOE_OK;
     return fail(TAHOE_ERR_UNSUPPORTED, "%s: not served on a vector-leaf handle (tahoe_vector_forest_create)", fn);
+}
+// ... of the three staged entry points: both refusals give way on a handle created with TAHOE_CREATE_STAGED
+inline tahoe_status refuse_unstaged(const tahoe_forest *f, const char *fn)
+{
+    if (f->staged) return TAHOE_OK;
+    if (const tahoe_status s = refuse_oblivious(f, fn)) return s;
+    return refuse_vector(f, fn);
 }
 // The first refusal of every TreeSHAP entry point (fn: its name): TAHOE_ERR_UNSUPPORTED unless the handle has path tables
 inline tahoe_status need_path_tables(const tahoe_forest *f, const char *fn)

@@ -33,13 +33,20 @@ constexpr int kObClasses = 8;  // accumulators a lane keeps: gridDim.y runs over
 // Leaf indices are written once, by class block 0.
 // CAT: the handle has category sets (tahoe_oblivious_forest_create_cat); a level's record then says its kind (ob_split_bit).  An
 // inline set is tested in registers; a pooled one gathers its member word per lane, and the kObTrees trees in flight overlap it.
-template <int KB, bool WRITE_LEAF, bool CAT, class Feature>
+// STAGED (tahoe_forest_predict_staged on a handle of TAHOE_CREATE_STAGED): `sums` is out[rows][S][K] and
+// stages[0 .. S) the strictly ascending tree counts.  The running sums are stored wherever the tree just added ends a stage, by a
+// cursor si that every class block runs for itself; the sums go on untouched, and the final store is not done (a stage equal
+// to num_trees is that store).  first_end is stages[0], which a kernel reads before it stages its tile: read here, the load's
+// latency stands between the tile and the first tree of every wave.
+template <int KB, bool WRITE_LEAF, bool CAT, bool STAGED = false, class Feature>
 __device__ __forceinline__ void oblivious_walk(const InnerNode *__restrict__ splits, const int32_t *__restrict__ split_off,
                                                const int64_t *__restrict__ leaf_off, const float *__restrict__ leaves, float *sums,
                                                uint32_t *__restrict__ leaf_out, const float *sums_in, size_t row, bool row_ok,
                                                int num_trees, int K, float missing, const uint32_t *__restrict__ cat_pool,
-                                               uint32_t cat_words, Feature &&feature)
+                                               uint32_t cat_words, const int32_t *__restrict__ stages, int S, int first_end,
+                                               Feature &&feature)
 {
+    static_assert(!STAGED || !WRITE_LEAF, "no staged leaf indices");
     const int k0 = (int)blockIdx.y * KB;
     float acc[KB];
 #pragma unroll
@@ -64,8 +71,46 @@ __device__ __forceinline__ void oblivious_walk(const InnerNode *__restrict__ spl
         for (int j = 0; j < KB; ++j) v[j] = (KB == 1 || k0 + j < K) ? lv[j] : 0.0f;
     };
 
+    // STAGED: the cursor and the tree count that ends its stage (wave-uniform; one load when the cursor moves); -1 after the last
+    int si = 0, send = first_end;
+    auto stage_end = [&](int trees_done) {  // after the adds of tree trees_done - 1
+        if (trees_done != send) return;
+        if (row_ok) {
+#pragma unroll
+            for (int j = 0; j < KB; ++j)
+                if (KB == 1 || k0 + j < K) sums[(row * (size_t)S + (size_t)si) * (size_t)K + k0 + j] = acc[j];
+        }
+        ++si;
+        send = si < S ? stages[si] : -1;
+    };
+
     int t = 0;
-    for (; t + kObTrees <= num_trees; t += kObTrees) {
+    if constexpr (STAGED) {
+        // A loop of its own (the plain one below keeps its statements, and so its instruction stream).  ends: a stage may end in
+        // this window, at any of the four trees
+        auto window = [&](int t0, auto ends) {
+            float v[kObTrees][KB];
+#pragma unroll
+            for (int u = 0; u < kObTrees; ++u) walk_tree(t0 + u, v[u]);
+#pragma unroll
+            for (int u = 0; u < kObTrees; ++u) {  // tree order
+#pragma unroll
+                for (int j = 0; j < KB; ++j) acc[j] += v[u][j];
+                if constexpr (decltype(ends)::value) stage_end(t0 + u + 1);
+            }
+        };
+        // The windows that lie before the cursor's stage end run the plain loop, bounded by that end instead of num_trees, so the
+        // compare is paid per stage and not per tree (on a K == 1 tree of depth 6 a compare per tree was 2.4 % of the walk); the
+        // window a stage ends in takes the compares.  Every end <= t is behind the cursor: send > t or send == -1.
+        for (;;) {
+            const int before = send < 0 ? num_trees : min(num_trees, send - 1);
+            for (; t + kObTrees <= before; t += kObTrees) window(t, std::false_type{});
+            if (t + kObTrees > num_trees) break;
+            window(t, std::true_type{});
+            t += kObTrees;
+        }
+    }
+    for (; !STAGED && t + kObTrees <= num_trees; t += kObTrees) {
         float v[kObTrees][KB];
 #pragma unroll
         for (int u = 0; u < kObTrees; ++u) walk_tree(t + u, v[u]);
@@ -79,8 +124,9 @@ __device__ __forceinline__ void oblivious_walk(const InnerNode *__restrict__ spl
         walk_tree(t, v);
 #pragma unroll
         for (int j = 0; j < KB; ++j) acc[j] += v[j];
+        if constexpr (STAGED) stage_end(t + 1);
     }
-    if (sums && row_ok) {
+    if (!STAGED && sums && row_ok) {
 #pragma unroll
         for (int j = 0; j < KB; ++j)
             if (KB == 1 || k0 + j < K) sums[row * (size_t)K + k0 + j] = acc[j];
@@ -91,7 +137,7 @@ __device__ __forceinline__ void oblivious_walk(const InnerNode *__restrict__ spl
 // rowtile_kernel; a level's feature is the row tile[fid][0..64): 64 consecutive floats, no bank conflict, no per-lane address
 // arithmetic.  A lane reads back only what it stored itself, so there is no barrier after staging, and nothing crosses waves.
 // Dynamic LDS: [cols][64] float.
-template <int KB, bool WRITE_LEAF, bool CAT>
+template <int KB, bool WRITE_LEAF, bool CAT, bool STAGED = false>
 __global__ void __launch_bounds__(kTileRows) oblivious_tile_kernel(const InnerNode *__restrict__ splits,
                                                                    const int32_t *__restrict__ split_off,
                                                                    const int64_t *__restrict__ leaf_off,
@@ -99,7 +145,7 @@ __global__ void __launch_bounds__(kTileRows) oblivious_tile_kernel(const InnerNo
                                                                    float *sums, uint32_t *__restrict__ leaf_out, const float *sums_in,
                                                                    size_t rows, int cols, int num_trees, int K, float missing,
                                                                    int vec4_ok, const uint32_t *__restrict__ cat_pool,
-                                                                   uint32_t cat_words)
+                                                                   uint32_t cat_words, const int32_t *__restrict__ stages, int S)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float *tile = reinterpret_cast<float *>(smem);
@@ -107,6 +153,7 @@ __global__ void __launch_bounds__(kTileRows) oblivious_tile_kernel(const InnerNo
     const size_t row0 = (size_t)blockIdx.x * kTileRows;
     const size_t row = row0 + lane;
     const bool row_ok = row < rows;
+    const int first_end = STAGED ? stages[0] : 0;
 
     // ---- stage the row tile, transposed to feature-major ----
     const float *src = data + (row_ok ? row : row0) * (size_t)cols;
@@ -123,50 +170,58 @@ __global__ void __launch_bounds__(kTileRows) oblivious_tile_kernel(const InnerNo
         for (int f = 0; f < cols; ++f) tile[f * kTileRows + lane] = row_ok ? src[f] : 0.0f;
     }
 
-    oblivious_walk<KB, WRITE_LEAF, CAT>(splits, split_off, leaf_off, leaves, sums, leaf_out, sums_in, row, row_ok, num_trees, K,
-                                        missing, cat_pool, cat_words, [&](uint32_t fid) { return tile[fid * kTileRows + lane]; });
+    oblivious_walk<KB, WRITE_LEAF, CAT, STAGED>(splits, split_off, leaf_off, leaves, sums, leaf_out, sums_in, row, row_ok, num_trees,
+                                                K, missing, cat_pool, cat_words, stages, S, first_end,
+                                                [&](uint32_t fid) { return tile[fid * kTileRows + lane]; });
 }
 
 // DIRECT: the same walk with the features read from global memory, for any num_cols.
-template <int KB, bool WRITE_LEAF, bool CAT>
+template <int KB, bool WRITE_LEAF, bool CAT, bool STAGED = false>
 __global__ void __launch_bounds__(kBlock) oblivious_direct_kernel(const InnerNode *__restrict__ splits,
                                                                   const int32_t *__restrict__ split_off,
                                                                   const int64_t *__restrict__ leaf_off,
                                                                   const float *__restrict__ leaves, const float *__restrict__ data,
                                                                   float *sums, uint32_t *__restrict__ leaf_out, const float *sums_in,
                                                                   size_t rows, int cols, int num_trees, int K, float missing,
-                                                                  const uint32_t *__restrict__ cat_pool, uint32_t cat_words)
+                                                                  const uint32_t *__restrict__ cat_pool, uint32_t cat_words,
+                                                                  const int32_t *__restrict__ stages, int S)
 {
     const size_t row = (size_t)blockIdx.x * kBlock + threadIdx.x;
     const bool row_ok = row < rows;
     const float *x = data + (row_ok ? row : 0) * (size_t)cols;  // (a lane past the batch walks row 0 and stores nothing)
-    oblivious_walk<KB, WRITE_LEAF, CAT>(splits, split_off, leaf_off, leaves, sums, leaf_out, sums_in, row, row_ok, num_trees, K,
-                                        missing, cat_pool, cat_words, [&](uint32_t fid) { return x[fid]; });
+    oblivious_walk<KB, WRITE_LEAF, CAT, STAGED>(splits, split_off, leaf_off, leaves, sums, leaf_out, sums_in, row, row_ok, num_trees,
+                                                K, missing, cat_pool, cat_words, stages, S, STAGED ? stages[0] : 0,
+                                                [&](uint32_t fid) { return x[fid]; });
 }
 
 static long long oblivious_tile_bytes(const tahoe_forest *f) { return (long long)f->p.num_cols * kTileRows * (long long)sizeof(float); }
 
 bool oblivious_tile_fits(const tahoe_forest *f) { return f->p.num_cols >= 1 && oblivious_tile_bytes(f) <= f->lds_limit; }
 
-tahoe_status oblivious_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data, size_t rows, hipStream_t stream,
-                              int strategy, const float *sums_in)
+// The launch of both forms.  STAGED: sums is out[rows][num_stages][K], leaf_out and sums_in are null
+template <bool STAGED>
+static tahoe_status oblivious_launch_as(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data, size_t rows,
+                                        hipStream_t stream, int strategy, const float *sums_in)
 {
     const tahoe_ostate *o = f->ob;
+    const int32_t *stages = STAGED ? f->stages_dev : nullptr;
+    const int S = STAGED ? (int)f->num_stages : 0;
     const int K = f->num_classes, T = f->p.num_trees, cols = f->p.num_cols;
     const unsigned blocks_y = (unsigned)((K + kObClasses - 1) / kObClasses);  // 1 when K == 1
     const int vec4_ok = (cols % 4 == 0) && ((reinterpret_cast<uintptr_t>(data) & 15u) == 0);
     auto launch = [&](auto kb, auto wl, auto cat) {
         constexpr int KB = decltype(kb)::value;
-        constexpr bool WL = decltype(wl)::value;
+        constexpr bool WL = decltype(wl)::value && !STAGED;
         constexpr bool CAT = decltype(cat)::value;
         if (strategy == TAHOE_STRATEGY_ROWTILE)
-            hipLaunchKernelGGL((oblivious_tile_kernel<KB, WL, CAT>), dim3((unsigned)((rows + kTileRows - 1) / kTileRows), blocks_y),
-                               dim3(kTileRows), (size_t)oblivious_tile_bytes(f), stream, o->splits, o->split_off, o->leaf_off, o->leaves,
-                               data, sums, leaf_out, sums_in, rows, cols, T, K, f->p.missing, vec4_ok, o->cat_pool, o->cat_words);
+            hipLaunchKernelGGL((oblivious_tile_kernel<KB, WL, CAT, STAGED>),
+                               dim3((unsigned)((rows + kTileRows - 1) / kTileRows), blocks_y), dim3(kTileRows),
+                               (size_t)oblivious_tile_bytes(f), stream, o->splits, o->split_off, o->leaf_off, o->leaves, data, sums,
+                               leaf_out, sums_in, rows, cols, T, K, f->p.missing, vec4_ok, o->cat_pool, o->cat_words, stages, S);
         else
-            hipLaunchKernelGGL((oblivious_direct_kernel<KB, WL, CAT>), dim3((unsigned)((rows + kBlock - 1) / kBlock), blocks_y),
+            hipLaunchKernelGGL((oblivious_direct_kernel<KB, WL, CAT, STAGED>), dim3((unsigned)((rows + kBlock - 1) / kBlock), blocks_y),
                                dim3(kBlock), 0, stream, o->splits, o->split_off, o->leaf_off, o->leaves, data, sums, leaf_out, sums_in,
-                               rows, cols, T, K, f->p.missing, o->cat_pool, o->cat_words);
+                               rows, cols, T, K, f->p.missing, o->cat_pool, o->cat_words, stages, S);
     };
     with_leaf(leaf_out != nullptr, [&](auto wl) {  // a handle without sets launches the instantiation without the kind test
         auto with_classes = [&](auto cat) {
@@ -178,6 +233,17 @@ tahoe_status oblivious_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, 
     });
     TAHOE_HIP_TRY(hipGetLastError());
     return TAHOE_OK;
+}
+
+tahoe_status oblivious_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data, size_t rows, hipStream_t stream,
+                              int strategy, const float *sums_in)
+{
+    return oblivious_launch_as<false>(f, sums, leaf_out, data, rows, stream, strategy, sums_in);
+}
+
+tahoe_status oblivious_launch_staged(tahoe_forest *f, float *out, const float *data, size_t rows, hipStream_t stream, int strategy)
+{
+    return oblivious_launch_as<true>(f, out, nullptr, data, rows, stream, strategy, nullptr);
 }
 
 void oblivious_destroy(tahoe_forest *f)
@@ -206,6 +272,18 @@ static tahoe_status oblivious_allow_lds(const tahoe_forest *f)
                (e = allow_max_lds_leaf([](auto wl) { return &oblivious_tile_kernel<kObClasses, decltype(wl)::value, false>; }, f->lds_limit)) != hipSuccess))
         return hip_status(e, "hipFuncSetAttribute(oblivious_tile)");
     return TAHOE_OK;
+}
+
+// ... and so may the staged ones of this handle (tahoe_forest_set_stages calls it)
+tahoe_status oblivious_allow_staged_lds(const tahoe_forest *f)
+{
+    if (!oblivious_tile_fits(f)) return TAHOE_OK;
+    const bool one = f->num_classes == 1;
+    const void *fn = f->ob->cats ? (one ? reinterpret_cast<const void *>(&oblivious_tile_kernel<1, false, true, true>)
+                                        : reinterpret_cast<const void *>(&oblivious_tile_kernel<kObClasses, false, true, true>))
+                                 : (one ? reinterpret_cast<const void *>(&oblivious_tile_kernel<1, false, false, true>)
+                                        : reinterpret_cast<const void *>(&oblivious_tile_kernel<kObClasses, false, false, true>));
+    return hip_status(allow_max_lds(fn, f->lds_limit), "hipFuncSetAttribute(oblivious_tile, staged)");
 }
 
 }  // namespace tahoe
@@ -257,6 +335,9 @@ extern "C" tahoe_status tahoe_oblivious_forest_create_cat(tahoe_forest **out, co
     }
 
     // ... and the checks of the explanation flags, after those every create makes
+    // (TAHOE_CREATE_STAGED opens tahoe_forest_set_stages / _predict_staged, reads no cover and builds no table)
+    const bool staged = (flags & TAHOE_CREATE_STAGED) != 0;
+    flags &= ~(unsigned)TAHOE_CREATE_STAGED;
     if (flags & ~(unsigned)(TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS | TAHOE_CREATE_INTERACTIONS |
                             TAHOE_CREATE_OBLIVIOUS_INTERVENTIONAL))
         return fail(TAHOE_ERR_INVALID_ARG, "tahoe_oblivious_forest_create_ex: flags 0x%x: only TAHOE_CREATE_CONTRIBS, "
@@ -301,6 +382,7 @@ extern "C" tahoe_status tahoe_oblivious_forest_create_cat(tahoe_forest **out, co
     if (const tahoe_status s = open_handle(p, leaf_dim, f)) return s;
     f->class_trees = T;  // AVG divides by (float)num_trees whatever K is
     f->p.depth = f->depth = max_depth;
+    f->staged = staged;
     f->ob = new (std::nothrow) tahoe_ostate();
     if (!f->ob) return fail(TAHOE_ERR_NO_MEMORY, "tahoe_oblivious_forest_create");
     tahoe_ostate *o = f->ob;

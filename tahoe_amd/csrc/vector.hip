@@ -29,16 +29,37 @@ constexpr int kVecClasses = 8;  // accumulators a lane keeps: gridDim.y runs ove
 // The walk of one row over all trees, for classes [blockIdx.y * KB, + KB).  feature(fid) reads the row's value of a feature.
 // KB == 1 is the single-output handle (K == 1), KB == kVecClasses a block of a vector leaf.  Leaf indices are written once, by
 // class block 0.
-template <int KB, bool WRITE_LEAF, class Feature>
+// STAGED (tahoe_forest_predict_staged on a handle of TAHOE_CREATE_STAGED): `sums` is out[rows][S][K] and
+// stages[0 .. S) the strictly ascending tree counts.  The running sums are stored wherever the tree just added ends a stage, by a
+// cursor si that every class block runs for itself; the sums go on untouched, and the final store is not done (a stage equal
+// to num_trees is that store).  first_end is stages[0], which a kernel reads before it stages its tile.  The compare sits after
+// every tree's adds: next to the gathers of an irregular tree it does not show, so this walk has no second loop as
+// oblivious_walk's has.
+template <int KB, bool WRITE_LEAF, bool STAGED = false, class Feature>
 __device__ __forceinline__ void vector_walk(const VNode *__restrict__ nodes, const int32_t *__restrict__ roots,
                                             const float *__restrict__ leaves, float *sums, uint32_t *__restrict__ leaf_out, size_t row,
-                                            bool row_ok, int num_trees, int K, float missing, Feature &&feature)
+                                            bool row_ok, int num_trees, int K, float missing, const int32_t *__restrict__ stages, int S,
+                                            int first_end, Feature &&feature)
 {
+    static_assert(!STAGED || !WRITE_LEAF, "no staged leaf indices");
     const int k0 = (int)blockIdx.y * KB;
     float acc[KB];
 #pragma unroll
     for (int j = 0; j < KB; ++j) acc[j] = 0.0f;
     const bool write_leaf = WRITE_LEAF && row_ok && blockIdx.y == 0;
+
+    // STAGED: the cursor and the tree count that ends its stage (wave-uniform; one load when the cursor moves); -1 after the last
+    int si = 0, send = first_end;
+    auto stage_end = [&](int trees_done) {  // after the adds of tree trees_done - 1
+        if (trees_done != send) return;
+        if (row_ok) {
+#pragma unroll
+            for (int j = 0; j < KB; ++j)
+                if (KB == 1 || k0 + j < K) sums[(row * (size_t)S + (size_t)si) * (size_t)K + k0 + j] = acc[j];
+        }
+        ++si;
+        send = si < S ? stages[si] : -1;
+    };
 
     // Trees t .. t + W - 1 at once.  A step of tree u is a per-lane gather of one node, so the W gathers of a round are issued
     // together, unconditionally -- a lane that has reached its leaf in tree u re-reads the root, one cache line for all such
@@ -89,15 +110,17 @@ __device__ __forceinline__ void vector_walk(const VNode *__restrict__ nodes, con
             if (write_leaf) leaf_out[row * (size_t)num_trees + (size_t)(t + u)] = curr[u];
         }
 #pragma unroll
-        for (int u = 0; u < W; ++u)  // tree order
+        for (int u = 0; u < W; ++u) {  // tree order
 #pragma unroll
             for (int j = 0; j < KB; ++j) acc[j] += v[u][j];
+            if constexpr (STAGED) stage_end(t + u + 1);  // (a stage can end at any tree of the window)
+        }
     };
 
     int t = 0;
     for (; t + kVecTrees <= num_trees; t += kVecTrees) window(t, std::integral_constant<int, kVecTrees>{});
     for (; t < num_trees; ++t) window(t, std::integral_constant<int, 1>{});
-    if (sums && row_ok) {
+    if (!STAGED && sums && row_ok) {
 #pragma unroll
         for (int j = 0; j < KB; ++j)
             if (KB == 1 || k0 + j < K) sums[row * (size_t)K + k0 + j] = acc[j];
@@ -108,11 +131,12 @@ __device__ __forceinline__ void vector_walk(const VNode *__restrict__ nodes, con
 // of oblivious_tile_kernel.  A node's feature is tile[fid * 64 + lane] with a per-lane fid: the bank is the lane's whatever fid
 // is, so the read is conflict-free.  A lane reads back only what it stored itself, so there is no barrier after staging, and
 // nothing crosses waves.  Dynamic LDS: [cols][64] float.
-template <int KB, bool WRITE_LEAF>
+template <int KB, bool WRITE_LEAF, bool STAGED = false>
 __global__ void __launch_bounds__(kTileRows) vector_tile_kernel(const VNode *__restrict__ nodes, const int32_t *__restrict__ roots,
                                                                 const float *__restrict__ leaves, const float *__restrict__ data,
                                                                 float *sums, uint32_t *__restrict__ leaf_out, size_t rows, int cols,
-                                                                int num_trees, int K, float missing, int vec4_ok)
+                                                                int num_trees, int K, float missing, int vec4_ok,
+                                                                const int32_t *__restrict__ stages, int S)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float *tile = reinterpret_cast<float *>(smem);
@@ -120,6 +144,7 @@ __global__ void __launch_bounds__(kTileRows) vector_tile_kernel(const VNode *__r
     const size_t row0 = (size_t)blockIdx.x * kTileRows;
     const size_t row = row0 + lane;
     const bool row_ok = row < rows;
+    const int first_end = STAGED ? stages[0] : 0;
 
     // ---- stage the row tile, transposed to feature-major (a lane past the batch stages and walks a row of zeros) ----
     const float *src = data + (row_ok ? row : row0) * (size_t)cols;
@@ -136,46 +161,52 @@ __global__ void __launch_bounds__(kTileRows) vector_tile_kernel(const VNode *__r
         for (int f = 0; f < cols; ++f) tile[f * kTileRows + lane] = row_ok ? src[f] : 0.0f;
     }
 
-    vector_walk<KB, WRITE_LEAF>(nodes, roots, leaves, sums, leaf_out, row, row_ok, num_trees, K, missing,
-                                [&](uint32_t fid) { return tile[fid * kTileRows + lane]; });
+    vector_walk<KB, WRITE_LEAF, STAGED>(nodes, roots, leaves, sums, leaf_out, row, row_ok, num_trees, K, missing, stages, S,
+                                        first_end, [&](uint32_t fid) { return tile[fid * kTileRows + lane]; });
 }
 
 // DIRECT: the same walk with the features read from global memory, for any num_cols.
-template <int KB, bool WRITE_LEAF>
+template <int KB, bool WRITE_LEAF, bool STAGED = false>
 __global__ void __launch_bounds__(kBlock) vector_direct_kernel(const VNode *__restrict__ nodes, const int32_t *__restrict__ roots,
                                                                const float *__restrict__ leaves, const float *__restrict__ data,
                                                                float *sums, uint32_t *__restrict__ leaf_out, size_t rows, int cols,
-                                                               int num_trees, int K, float missing)
+                                                               int num_trees, int K, float missing,
+                                                               const int32_t *__restrict__ stages, int S)
 {
     const size_t row = (size_t)blockIdx.x * kBlock + threadIdx.x;
     const bool row_ok = row < rows;
     const float *x = data + (row_ok ? row : 0) * (size_t)cols;  // (a lane past the batch walks row 0 and stores nothing)
-    vector_walk<KB, WRITE_LEAF>(nodes, roots, leaves, sums, leaf_out, row, row_ok, num_trees, K, missing,
-                                [&](uint32_t fid) { return x[fid]; });
+    vector_walk<KB, WRITE_LEAF, STAGED>(nodes, roots, leaves, sums, leaf_out, row, row_ok, num_trees, K, missing, stages, S,
+                                        STAGED ? stages[0] : 0, [&](uint32_t fid) { return x[fid]; });
 }
 
 static long long vector_tile_bytes(const tahoe_forest *f) { return (long long)f->p.num_cols * kTileRows * (long long)sizeof(float); }
 
 bool vector_tile_fits(const tahoe_forest *f) { return f->p.num_cols >= 1 && vector_tile_bytes(f) <= f->lds_limit; }
 
-tahoe_status vector_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data, size_t rows, hipStream_t stream,
-                           int strategy)
+// The launch of both forms.  STAGED: sums is out[rows][num_stages][K] and leaf_out is null
+template <bool STAGED>
+static tahoe_status vector_launch_as(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data, size_t rows,
+                                     hipStream_t stream, int strategy)
 {
     const tahoe_vstate *v = f->vl;
+    const int32_t *stages = STAGED ? f->stages_dev : nullptr;
+    const int S = STAGED ? (int)f->num_stages : 0;
     const int K = f->num_classes, T = f->p.num_trees, cols = f->p.num_cols;
     const unsigned blocks_y = (unsigned)((K + kVecClasses - 1) / kVecClasses);  // 1 when K == 1
     if (cols == 0) data = v->leaves;  // every tree is a single leaf: the walk's idle feature read needs one readable float
     const int vec4_ok = (cols % 4 == 0) && ((reinterpret_cast<uintptr_t>(data) & 15u) == 0);
     auto launch = [&](auto kb, auto wl) {
         constexpr int KB = decltype(kb)::value;
-        constexpr bool WL = decltype(wl)::value;
+        constexpr bool WL = decltype(wl)::value && !STAGED;
         if (strategy == TAHOE_STRATEGY_ROWTILE)
-            hipLaunchKernelGGL((vector_tile_kernel<KB, WL>), dim3((unsigned)((rows + kTileRows - 1) / kTileRows), blocks_y),
+            hipLaunchKernelGGL((vector_tile_kernel<KB, WL, STAGED>), dim3((unsigned)((rows + kTileRows - 1) / kTileRows), blocks_y),
                                dim3(kTileRows), (size_t)vector_tile_bytes(f), stream, v->nodes, v->roots, v->leaves, data, sums,
-                               leaf_out, rows, cols, T, K, f->p.missing, vec4_ok);
+                               leaf_out, rows, cols, T, K, f->p.missing, vec4_ok, stages, S);
         else
-            hipLaunchKernelGGL((vector_direct_kernel<KB, WL>), dim3((unsigned)((rows + kBlock - 1) / kBlock), blocks_y), dim3(kBlock), 0,
-                               stream, v->nodes, v->roots, v->leaves, data, sums, leaf_out, rows, cols, T, K, f->p.missing);
+            hipLaunchKernelGGL((vector_direct_kernel<KB, WL, STAGED>), dim3((unsigned)((rows + kBlock - 1) / kBlock), blocks_y),
+                               dim3(kBlock), 0, stream, v->nodes, v->roots, v->leaves, data, sums, leaf_out, rows, cols, T, K,
+                               f->p.missing, stages, S);
     };
     with_leaf(leaf_out != nullptr, [&](auto wl) {
         if (K == 1) launch(std::integral_constant<int, 1>{}, wl);
@@ -183,6 +214,17 @@ tahoe_status vector_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, con
     });
     TAHOE_HIP_TRY(hipGetLastError());
     return TAHOE_OK;
+}
+
+tahoe_status vector_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data, size_t rows, hipStream_t stream,
+                           int strategy)
+{
+    return vector_launch_as<false>(f, sums, leaf_out, data, rows, stream, strategy);
+}
+
+tahoe_status vector_launch_staged(tahoe_forest *f, float *out, const float *data, size_t rows, hipStream_t stream, int strategy)
+{
+    return vector_launch_as<true>(f, out, nullptr, data, rows, stream, strategy);
 }
 
 void vector_destroy(tahoe_forest *f)
@@ -208,6 +250,15 @@ static tahoe_status vector_allow_lds(const tahoe_forest *f)
          (e = allow_max_lds_leaf([](auto wl) { return &vector_tile_kernel<kVecClasses, decltype(wl)::value>; }, f->lds_limit)) != hipSuccess))
         return hip_status(e, "hipFuncSetAttribute(vector_tile)");
     return TAHOE_OK;
+}
+
+// ... and so may the staged ones of this handle (tahoe_forest_set_stages calls it)
+tahoe_status vector_allow_staged_lds(const tahoe_forest *f)
+{
+    if (!vector_tile_fits(f)) return TAHOE_OK;
+    const void *fn = f->num_classes == 1 ? reinterpret_cast<const void *>(&vector_tile_kernel<1, false, true>)
+                                         : reinterpret_cast<const void *>(&vector_tile_kernel<kVecClasses, false, true>);
+    return hip_status(allow_max_lds(fn, f->lds_limit), "hipFuncSetAttribute(vector_tile, staged)");
 }
 
 }  // namespace tahoe
@@ -269,6 +320,9 @@ extern "C" tahoe_status tahoe_vector_forest_create_ex(tahoe_forest **out, const 
     }
     // the checks of tahoe_sparse_forest_create_ex for the flags: covers (TAHOE_CREATE_CONTRIBS; TAHOE_CREATE_INTERVENTIONAL alone
     // reads none), and at most 31 distinct features on a leaf's path
+    // (TAHOE_CREATE_STAGED opens tahoe_forest_set_stages / _predict_staged, reads no cover and builds no table)
+    const bool staged = (flags & TAHOE_CREATE_STAGED) != 0;
+    flags &= ~(unsigned)TAHOE_CREATE_STAGED;
     constexpr unsigned kShapFlags = TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_INTERVENTIONAL | TAHOE_CREATE_VECTOR_INTERACTIONS;
     if ((flags & ~(kShapFlags | TAHOE_CREATE_VECTOR_APPROX)) != 0)
         return fail(TAHOE_ERR_INVALID_ARG,
@@ -294,6 +348,7 @@ extern "C" tahoe_status tahoe_vector_forest_create_ex(tahoe_forest **out, const 
     f->class_trees = T;  // AVG divides by (float)num_trees whatever K is
     f->p.depth = f->depth = max_depth;
     f->bits_bytes = 4;
+    f->staged = staged;
     f->vl = new (std::nothrow) tahoe_vstate();
     if (!f->vl) return fail(TAHOE_ERR_NO_MEMORY, "tahoe_vector_forest_create");
     tahoe_vstate *v = f->vl;

@@ -25,7 +25,8 @@ FLAGGED = ("direct_kernel", "rowtile_kernel", "qring_kernel", "qwide_kernel",  #
            "contribs_kernel", "contribs_spare_kernel", "interactions_kernel", "background_mask_kernel",  # SETS / CAT
            "interventional_kernel", "approx_kernel",
            "oblivious_tile_kernel", "oblivious_direct_kernel", "oblivious_shap_kernel", "oblivious_inter_kernel",
-           "oblivious_iv_kernel")  # CAT
+           "oblivious_iv_kernel",  # CAT
+           "vector_tile_kernel", "vector_direct_kernel")  # STAGED (the two oblivious walk kernels carry it too)
 
 
 def functions(path):
