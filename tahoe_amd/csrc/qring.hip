@@ -37,6 +37,7 @@
 // layout build of Struct.h:1756-1986 (whose char/short/int "adaptive" widths compress only the
 // fid/flag word; here the threshold is compressed too, losslessly).
 #include "qring_internal.h"
+#include "stage_burst.h"
 
 namespace tahoe {
 
@@ -124,26 +125,39 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
         return;
     }
 
-    // ---- stage the quantised tile (already in LDS order): straight 16-byte copies ----
-    if (REG) {  // consecutive regions of the workspace (cols x 128 bytes each: 64 rows of u16 or 128 rows of u8 codes), each to
-                // its 32-KiB-aligned place
-        const int n16 = cols * kRegRows * 2 / 16;  // 16-byte pieces of a region
-        const size_t first_region = CODE8 ? row0 >> 7 : row0 >> 6;
-        for (int k = 0; k < NREG; ++k) {
-            const uint4 *src = reinterpret_cast<const uint4 *>(xq + (first_region + (size_t)k) * ((size_t)cols * kRegRows));
-            uint4 *dst = reinterpret_cast<uint4 *>(smem + (size_t)k * REGB);
-            for (int e = tid; e < n16; e += NT) dst[e] = src[e];
+    // ---- stage the quantised tile (already in LDS order) as one burst of 16-byte loads (stage_burst.h) ----
+    // REG: consecutive regions of the workspace (cols x 128 bytes each: 64 rows of u16 or 128 rows of u8 codes), each to its
+    // REGB-aligned place; every load of every region is issued before the first one is committed.  A walker puts the loads of
+    // its first top at the head of the same burst (top_loads; they hit L2 and vmcnt retires in order) and commits that top
+    // (top_commit) while the tile is still in flight.  The 128-slot column form copies its tile in bursts of eight loads per lane.
+    auto stage_tile = [&](auto &&top_loads, auto &&top_commit) __attribute__((always_inline)) {
+        if constexpr (REG) {
+            constexpr int PMAX = (REGB / 16 + NT - 1) / NT;  // 16-byte pieces of a region per thread, at most
+            const uint32_t n16 = (uint32_t)cols * (kRegRows * 2 / 16);
+            const uint32_t wrap = stage_wrap(n16);
+            const size_t first_region = CODE8 ? row0 >> 7 : row0 >> 6;
+            const uint4 *src = reinterpret_cast<const uint4 *>(xq + first_region * ((size_t)cols * kRegRows));
+            top_loads();  // ahead of the scalar branch on the piece count, once
+            __builtin_amdgcn_sched_barrier(0);  // (the scheduler would put the tile's loads first)
+            stage_dispatch<PMAX>((int)((n16 + NT - 1) / NT), [&](auto p_tag) __attribute__((always_inline)) {
+                constexpr int P = decltype(p_tag)::value;
+                StageRegs<NREG * P> v;
+                stage_issue<NT, P, NREG>(v, src, n16, tid, n16, wrap);
+                top_commit();
+                stage_commit<NT, P, NREG>(v, reinterpret_cast<uint4 *>(smem), REGB / 16, tid, n16, wrap);
+            });
+        } else {
+            top_loads();
+            if constexpr (LDSX)
+                stage_copy<NT, 8>(xq + (size_t)tile_id * ((size_t)cols * TR), tile, (size_t)cols * TR * sizeof(uint16_t), tid);
+            top_commit();
         }
-    } else if (LDSX) {
-        const uint4 *src = reinterpret_cast<const uint4 *>(xq + (size_t)tile_id * ((size_t)cols * TR));
-        uint4 *dst = reinterpret_cast<uint4 *>(tile);
-        const int n16 = cols * TR * 2 / 16;
-        for (int e = tid; e < n16; e += NT) dst[e] = src[e];
-    }
+    };
     TAHOE_RING_RESET(ring, RING, tid);
 
     if (wave == NWALK) {
         // ================= consumer: ordered accumulation =================
+        stage_tile([] {}, [] {});
         __syncthreads();
         if (SPLIT) return;  // the leaf values go to leafbuf; ordered_sum_kernel adds them
         float sum[K];  // continues the running sums of the previous tree group (sums_in may alias sums)
@@ -258,15 +272,17 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
         }
     };
     const bool packed = T24 && ms_flags == 0;  // (uniform)
-    if (t_begin + wave < t_end) {
-        if (packed) {
-            prefetch_top(std::true_type{}, t_begin + wave);
-            commit_top(std::true_type{});
-        } else {
-            prefetch_top(std::false_type{}, t_begin + wave);
-            commit_top(std::false_type{});
-        }
-    }
+    // The first top rides in the tile's burst.  No branch stands around its loads (they would be sunk behind the tile's): a walker
+    // without a tree (fewer trees than walkers) stages its slice's last tree, or the group's first, into its unused slot.
+    // Precondition: the launch's tree group holds at least one tree, so tree 0 exists (a forest without trees never reaches a walk:
+    // tahoe_forest_predict answers it with zeros, forest.hip).
+    const int t_first = max(min(t_begin + wave, t_end - 1), 0);
+    if (packed)
+        stage_tile([&]() __attribute__((always_inline)) { prefetch_top(std::true_type{}, t_first); },
+                   [&]() __attribute__((always_inline)) { commit_top(std::true_type{}); });
+    else
+        stage_tile([&]() __attribute__((always_inline)) { prefetch_top(std::false_type{}, t_first); },
+                   [&]() __attribute__((always_inline)) { commit_top(std::false_type{}); });
     __syncthreads();  // the tile, the ring state and (own wave) the first top are in LDS
 
     bool dead = false;

@@ -28,9 +28,10 @@ struct tahoe_qgroup {
     // bucketed form (quantize_bucket_pair_kernel): sorted thresholds + a direct-index table per feature
     int buckets = 0;              // B (power of two); 0 = form unavailable for this group
     int bucket_lds_bytes = 0;     // LDS of the largest feature pair
-    float *bsorted = nullptr;     // per feature: n_f sorted thresholds + (2^steps_f - 1) NaN pads
-    int *boffsets = nullptr;      // [cols + 1] into bsorted
-    uint16_t *bstarts = nullptr;  // [cols][B + 2]: first sorted index of each bucket (entry B = n_f)
+    float *bimage = nullptr;      // per feature pair one 16-byte-aligned image in the kernel's LDS order: per feature n_f sorted thresholds +
+                                  // (2^steps_f - 1) NaN pads (the second run padded to 16 bytes), then both start tables, (B + 2) u16
+                                  // each: first sorted index of each bucket (entry B = n_f), padded to 16 bytes
+    int *boffsets = nullptr;      // [cols + 1] floats into bimage: where each feature's sorted run starts (an even feature's = its pair's image)
     float4 *bparams = nullptr;    // [cols]: lo, scale, steps (int bits), unused
     uint32_t *top = nullptr;      // [T_g][top_stride]
     uint4 *top24 = nullptr;       // [T_g][top24_chunks]: the same tops without def_left, 3 bytes per node (qring.hip, "packed tops")

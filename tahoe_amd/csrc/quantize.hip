@@ -7,12 +7,13 @@
 // Replaces nothing in the reference (its kernels compare float32 features, Struct.h:359-407); it is the pre-pass
 // that lets the walk run on 16-bit integers without changing a single branch.
 #include "qring_internal.h"
+#include "stage_burst.h"
 
 namespace tahoe {
 
 // ------------------------------------------------------------------------------------------------
 // (1) float32 rows -> u16 codes.  One workgroup = F adjacent features x 2^cshift rows (quantize_launch), the F
-// search trees in LDS (stride `tab_stride` floats).  A thread reads the F values of a row with one
+// search trees in LDS (one after the other, as in global memory).  A thread reads the F values of a row with one
 // F*4-byte load: the row-major input is fetched in 64-byte lines of 16 features, and a workgroup uses
 // F*4 bytes of each line it pulls through L2 -> L1, so F = 2 halves and F = 4 quarters that traffic
 // (the kernel was bound by it at F = 1: 16 GB of line traffic for a 1 GB batch).
@@ -48,13 +49,16 @@ __global__ void __launch_bounds__(kQuantThreads) quantize_kernel(const float *__
     // size = 2^p entries.  A probe sequence touches one entry per level and a level is contiguous, so the 64
     // lanes of a probe spread over the LDS banks (a sorted array probed at power-of-two strides puts every
     // lane in the same bank: 32-way conflicts, measured).
-    int size[F];
+    // The F tables are adjacent in global memory and 16-byte aligned (every table has 2^p >= 4 entries, quantize_build_tables):
+    // one linear image, staged in bursts of 16-byte loads (stage_burst.h).
+    int size[F], toff[F];
+    const int base0 = offsets[f0];
 #pragma unroll
     for (int j = 0; j < F; ++j) {
-        const int base = offsets[f0 + j];
-        size[j] = offsets[f0 + j + 1] - base;  // 2^p, p >= 0 (size 1 = no thresholds)
-        for (int i = threadIdx.x; i < size[j]; i += blockDim.x) tab[j * tab_stride + i] = tables[base + i];
+        toff[j] = offsets[f0 + j] - base0;
+        size[j] = offsets[f0 + j + 1] - offsets[f0 + j];  // 2^p, p >= 2 (size 4 with NaN pads only = no thresholds)
     }
+    stage_copy<kQuantThreads, 8>(tables + base0, tab, (size_t)(offsets[f0 + F] - base0) * sizeof(float), (int)threadIdx.x);
     __syncthreads();
     const size_t r0 = chunk << cshift;
     const size_t r1 = min(rows, r0 + ((size_t)1 << cshift));
@@ -70,7 +74,7 @@ __global__ void __launch_bounds__(kQuantThreads) quantize_kernel(const float *__
         }
 #pragma unroll
         for (int j = 0; j < F; ++j) {
-            const float *tj = tab + j * tab_stride;
+            const float *tj = tab + toff[j];
             float x[U];
             int cnt[U];
 #pragma unroll
@@ -127,10 +131,9 @@ __global__ void __launch_bounds__(kQuantPairThreads)
         const bool do0 = together || pass == 0, do1 = together || pass == 1;
         const float *t0 = tab;
         const float *t1 = together ? tab + size0 : tab;
-        if (do0)
-            for (int i = threadIdx.x; i < size0; i += blockDim.x) tab[i] = tables[base0 + i];
-        if (do1)
-            for (int i = threadIdx.x; i < size1; i += blockDim.x) tab[(together ? size0 : 0) + i] = tables[base1 + i];
+        // both trees (adjacent in global memory as in LDS), or this pass's, as one burst of 16-byte loads (stage_burst.h)
+        stage_copy_once<kQuantPairThreads, 10>(tables + (pass ? base1 : base0), tab,
+                                               (size_t)(together ? size0 + size1 : pass ? size1 : size0) * sizeof(float), (int)threadIdx.x);
         __syncthreads();
         float2 nx[U];  // next iteration's rows, loaded one iteration ahead (see quantize_bucket_pair_kernel)
 #pragma unroll
@@ -211,9 +214,12 @@ __global__ void bucket_index_kernel(const float *__restrict__ vals, const int *_
     out[i] = q_bucket(vals[i], p.x, p.y, bm1);
 }
 
+// floats of a pair's image behind its two sorted runs: both start tables ((B + 2) u16 each), padded to 16 bytes
+__host__ __device__ __forceinline__ int q_bucket_tail_floats(int B) { return (B + 2 + 3) & ~3; }
+
 __global__ void __launch_bounds__(kQuantPairThreads)
-    quantize_bucket_pair_kernel(const float *__restrict__ data, const float *__restrict__ bsorted, const int *__restrict__ boffsets,
-                                const uint16_t *__restrict__ bstarts, const float4 *__restrict__ bparams,
+    quantize_bucket_pair_kernel(const float *__restrict__ data, const float *__restrict__ bimage, const int *__restrict__ boffsets,
+                                const float4 *__restrict__ bparams,
                                 uint16_t *__restrict__ xq, uint32_t *__restrict__ chunk_flags, size_t rows, int cols, float missing,
                                 int B, int trs, int cshift, int perm)
 {
@@ -223,19 +229,15 @@ __global__ void __launch_bounds__(kQuantPairThreads)
     const int groups = cols / 2;
     const int f0 = (int)(vid % groups) * 2;
     const size_t chunk = vid / groups;
-    const int base0 = boffsets[f0], base1 = boffsets[f0 + 1];
-    const int len0 = base1 - base0, len1 = boffsets[f0 + 2] - base1;
+    // The pair's tables are one 16-byte-aligned image in global memory, in LDS order (build_buckets): [sorted f0 | sorted f0 + 1 |
+    // starts f0 | starts f0 + 1 | pad], staged as one burst of 16-byte loads (stage_burst.h; 144 KiB at K3 = nine loads per lane).
+    const int base0 = boffsets[f0], base1 = boffsets[f0 + 1], end = boffsets[f0 + 2];
+    const int len0 = base1 - base0, len1 = end - base1 - q_bucket_tail_floats(B);
     float *s0 = reinterpret_cast<float *>(smem);
     float *s1 = s0 + len0;
     uint16_t *st0 = reinterpret_cast<uint16_t *>(s1 + len1);
     uint16_t *st1 = st0 + (B + 2);
-    for (int i = threadIdx.x; i < len0; i += blockDim.x) s0[i] = bsorted[base0 + i];
-    for (int i = threadIdx.x; i < len1; i += blockDim.x) s1[i] = bsorted[base1 + i];
-    {   // both start tables are adjacent in global memory too: (B + 2) u16 each, copied as dwords
-        const uint32_t *src = reinterpret_cast<const uint32_t *>(bstarts + (size_t)f0 * (B + 2));
-        uint32_t *dst = reinterpret_cast<uint32_t *>(st0);
-        for (int i = threadIdx.x; i < B + 2; i += blockDim.x) dst[i] = src[i];
-    }
+    stage_copy_once<kQuantPairThreads, 10>(bimage + base0, smem, (size_t)(end - base0) * sizeof(float), (int)threadIdx.x);
     const float4 p0 = bparams[f0], p1 = bparams[f0 + 1];
     const int steps0 = __float_as_int(p0.z), steps1 = __float_as_int(p1.z);
     const float bm1 = (float)(B - 1);
@@ -331,15 +333,17 @@ __global__ void __launch_bounds__(kQuantPairThreads)
     const int groups = cols / F;
     const int f0 = (int)(vid % groups) * F;
     const size_t chunk = vid / groups;
-    for (int j = 0; j < F; ++j) {
-        const int base = offsets[f0 + j], size = offsets[f0 + j + 1] - base;
-        for (int i = threadIdx.x; i < size; i += blockDim.x) tab[j * tab_stride + i] = tables[base + i];
-    }
+    // the F tables, adjacent and 16-byte aligned in global memory, as one linear image in one burst (stage_burst.h)
+    const int base0 = offsets[f0];
+    stage_copy_once<kQuantPairThreads, 10>(tables + base0, tab, (size_t)(offsets[f0 + F] - base0) * sizeof(float), (int)threadIdx.x);
     const int quad = threadIdx.x % Q, rsub = threadIdx.x / Q;
     const int fq = f0 + 4 * quad;  // this thread's four features
-    int size[4];
+    int size[4], toff[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) size[j] = offsets[fq + j + 1] - offsets[fq + j];
+    for (int j = 0; j < 4; ++j) {
+        toff[j] = offsets[fq + j] - base0;
+        size[j] = offsets[fq + j + 1] - offsets[fq + j];
+    }
     __syncthreads();
     const size_t r0 = chunk << cshift;
     const size_t r1 = min(rows, r0 + ((size_t)1 << cshift));
@@ -361,7 +365,7 @@ __global__ void __launch_bounds__(kQuantPairThreads)
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const float *tj = tab + (4 * quad + j) * tab_stride;
+            const float *tj = tab + toff[j];
             float x[U];
             int cnt[U];
 #pragma unroll
@@ -481,25 +485,28 @@ static tahoe_status build_buckets(tahoe_forest *f, const std::vector<std::vector
             int sp = 0;
             while ((1 << sp) - 1 < longest) ++sp;
             steps[c] = sp;
+            // One image per feature pair, in the kernel's LDS order and a multiple of 16 bytes: the second run is padded (with
+            // the NaN pads the probes tolerate) until both runs end on 16 bytes, then come the pair's start tables.
             boffsets[c] = len_total;
             len_total += n + (1 << sp) - 1;
+            if (c % 2 == 1) len_total = ((len_total + 3) & ~3) + q_bucket_tail_floats(B);
             memcpy(&params[c].z, &sp, 4);
             at += (size_t)n;
         }
         boffsets[cols] = len_total;
         if (!monotone) break;  // cannot happen with a monotone q_bucket; be safe and keep the search-tree form
         int lds = 0;
-        for (int c = 0; c < cols; c += 2) lds = std::max(lds, (boffsets[c + 2] - boffsets[c]) * 4 + 2 * (B + 2) * 2);
+        for (int c = 0; c < cols; c += 2) lds = std::max(lds, (boffsets[c + 2] - boffsets[c]) * 4);
         if (lds > f->lds_limit - 256) continue;  // try fewer buckets (smaller start tables)
-        std::vector<float> bsorted((size_t)len_total, std::nanf(""));
-        at = 0;
+        std::vector<float> bimage((size_t)len_total, std::nanf(""));
         for (int c = 0; c < cols; ++c) {
-            std::copy(tab[c].begin(), tab[c].end(), bsorted.begin() + boffsets[c]);
-            at += tab[c].size();
+            std::copy(tab[c].begin(), tab[c].end(), bimage.begin() + boffsets[c]);
+            if (c % 2 == 1)  // both start tables, adjacent in `starts` too
+                memcpy(&bimage[(size_t)boffsets[c + 1] - q_bucket_tail_floats(B)], &starts[(size_t)(c - 1) * (B + 2)],
+                       (size_t)2 * (B + 2) * sizeof(uint16_t));
         }
-        if ((e = upload(&g.bsorted, bsorted, &f->device_bytes)) != hipSuccess) return bad("bsorted");
+        if ((e = upload(&g.bimage, bimage, &f->device_bytes)) != hipSuccess) return bad("bimage");
         if ((e = upload(&g.boffsets, boffsets, &f->device_bytes)) != hipSuccess) return bad("boffsets");
-        if ((e = upload(&g.bstarts, starts, &f->device_bytes)) != hipSuccess) return bad("bstarts");
         if ((e = upload(&g.bparams, params, &f->device_bytes)) != hipSuccess) return bad("bparams");
         g.buckets = B;
         g.bucket_lds_bytes = lds;
@@ -516,10 +523,10 @@ tahoe_status quantize_build_tables(tahoe_forest *f, const std::vector<std::vecto
     // false, i.e. "greater than every x"); entry 0 unused
     std::vector<int> offsets((size_t)cols + 1, 0);
     std::vector<float> tables;
-    int max_size = 1;
+    int max_size = 4;
     for (int c = 0; c < cols; ++c) {
         const auto &v = tab[c];
-        int size = 1;
+        int size = 4;  // (at least 16 bytes: every table starts 16-byte aligned, the kernels stage them with 16-byte loads)
         while (size - 1 < (int)v.size()) size *= 2;  // 2^p with 2^p - 1 >= n
         max_size = std::max(max_size, size);
         offsets[c] = (int)tables.size();
@@ -573,13 +580,12 @@ tahoe_status quantize_build_tables(tahoe_forest *f, const std::vector<std::vecto
 
 void quantize_free_tables(tahoe_qgroup &g)
 {
-    for (void *p : {(void *)g.tables, (void *)g.offsets, (void *)g.bsorted, (void *)g.boffsets, (void *)g.bstarts, (void *)g.bparams})
+    for (void *p : {(void *)g.tables, (void *)g.offsets, (void *)g.bimage, (void *)g.boffsets, (void *)g.bparams})
         if (p) (void)hipFree(p);
     g.tables = nullptr;
     g.offsets = nullptr;
-    g.bsorted = nullptr;
+    g.bimage = nullptr;
     g.boffsets = nullptr;
-    g.bstarts = nullptr;
     g.bparams = nullptr;
 }
 
@@ -629,7 +635,7 @@ tahoe_status quantize_launch(tahoe_forest *f, const tahoe_qgroup &g, const float
                            rows, f->p.num_cols, f->p.missing, std::max(g.max_table, 1), trs, cshift, perm);
     else if (pair_ok && g.buckets > 0)
         hipLaunchKernelGGL(quantize_bucket_pair_kernel, dim3((unsigned)qgrid), dim3(kQuantPairThreads),
-                           (size_t)g.bucket_lds_bytes, stream, data, g.bsorted, g.boffsets, g.bstarts, g.bparams, q->xq,
+                           (size_t)g.bucket_lds_bytes, stream, data, g.bimage, g.boffsets, g.bparams, q->xq,
                            q->chunk_flags, rows, f->p.num_cols, f->p.missing, g.buckets, trs, cshift, perm);
     else if (pair_ok)
         hipLaunchKernelGGL(quantize_pair_kernel, dim3((unsigned)qgrid), dim3(kQuantPairThreads),

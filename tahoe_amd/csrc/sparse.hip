@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "qring_internal.h"
+#include "stage_burst.h"
 
 struct tahoe_sstate {
     tahoe_sparse_node *nodes = nullptr;  // device copy, as given
@@ -439,18 +440,28 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
         if (tid == 0) atomicOr(error_flag, 2);
         return;
     }
-    {   // K consecutive regions of the workspace, each to its 32-KiB-aligned place
-        const int n16 = cols * kRegRows * 2 / 16;
-        for (int k = 0; k < K; ++k) {
-            const uint4 *src = reinterpret_cast<const uint4 *>(xq + ((row0 >> 6) + (size_t)k) * ((size_t)cols * kRegRows));
-            uint4 *dst = reinterpret_cast<uint4 *>(smem + (size_t)k * kRegBytes);
-            for (int e = tid; e < n16; e += NT) dst[e] = src[e];
-        }
-    }
+    // K consecutive regions of the workspace, each to its 32-KiB-aligned place, as one burst of 16-byte loads (stage_burst.h); a
+    // walker's first top rides at the head of the burst and is committed while the regions are in flight (qring_kernel's prologue)
+    auto stage_tile = [&](auto &&top_loads, auto &&top_commit) __attribute__((always_inline)) {
+        constexpr int PMAX = (kRegBytes / 16 + NT - 1) / NT;
+        const uint32_t n16 = (uint32_t)cols * (kRegRows * 2 / 16);
+        const uint32_t wrap = stage_wrap(n16);
+        const uint4 *src = reinterpret_cast<const uint4 *>(xq + (row0 >> 6) * ((size_t)cols * kRegRows));
+        top_loads();  // ahead of the scalar branch on the piece count, once
+        __builtin_amdgcn_sched_barrier(0);  // (the scheduler would put the tile's loads first)
+        stage_dispatch<PMAX>((int)((n16 + NT - 1) / NT), [&](auto p_tag) __attribute__((always_inline)) {
+            constexpr int P = decltype(p_tag)::value;
+            StageRegs<K * P> v;
+            stage_issue<NT, P, K>(v, src, n16, tid, n16, wrap);
+            top_commit();
+            stage_commit<NT, P, K>(v, reinterpret_cast<uint4 *>(smem), kRegBytes / 16, tid, n16, wrap);
+        });
+    };
     TAHOE_RING_RESET(ring, RING, tid);
 
     if (wave == NWALK) {
         // ================= consumer: ordered accumulation =================
+        stage_tile([] {}, [] {});
         __syncthreads();
         float sum[K];  // continues the running sums of the previous tree group (sums_in may alias sums)
         // MC: class cls of the group's first tree; its trees end after local tree cend - 1
@@ -525,10 +536,10 @@ __global__ void __launch_bounds__((NWALK + 1) * 64)
         s[2 * 64 + lane] = pf2;
         s[3 * 64 + lane] = pf3;
     };
-    if (wave < num_trees) {
-        prefetch_top(wave);
-        commit_top();
-    }
+    // (no branch around the top's loads: a walker without a tree stages the group's last tree into its unused slot)
+    // Precondition: num_trees >= 1 (a forest without trees never reaches a walk: tahoe_forest_predict answers it with zeros).
+    stage_tile([&]() __attribute__((always_inline)) { prefetch_top(min(wave, num_trees - 1)); },
+               [&]() __attribute__((always_inline)) { commit_top(); });
     __syncthreads();  // the regions, the ring state and (own wave) the first top are in LDS
 
     bool dead = false;
