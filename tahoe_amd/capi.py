@@ -532,13 +532,22 @@ class Forest:
                "tahoe_forest_predict_accumulate")
         return sums
 
-    def predict_leaf_idx(self, data, want_sums: bool = True, stream=None):
+    def predict_leaf_idx(self, data, want_sums: bool = True, stream=None, leaf=None, sums=None):
+        """-> (leaf int32 [rows, num_trees], sums float32 like predict_raw's, or None without want_sums).  leaf= / sums=:
+        the caller's output tensors (sums= only with want_sums)."""
         import torch
 
         self._check_data(data)
         rows = data.shape[0]
-        leaf = torch.empty((rows, self.num_trees), dtype=torch.int32, device=data.device)
-        sums = torch.empty(self._out_shape(rows), dtype=torch.float32, device=data.device) if want_sums else None
+        if leaf is None:
+            leaf = torch.empty((rows, self.num_trees), dtype=torch.int32, device=data.device)
+        assert leaf.is_cuda and leaf.is_contiguous() and leaf.dtype == torch.int32 and tuple(leaf.shape) == (rows, self.num_trees)
+        assert sums is None or want_sums, "sums= given, but want_sums is False"
+        if want_sums and sums is None:
+            sums = torch.empty(self._out_shape(rows), dtype=torch.float32, device=data.device)
+        if want_sums:
+            assert sums.is_cuda and sums.is_contiguous() and sums.dtype == torch.float32
+            assert tuple(sums.shape) == self._out_shape(rows)
         _check(lib.tahoe_forest_predict_leaf_idx(self._h, _ptr(leaf), _ptr(sums) if want_sums else None,
                                                  _ptr(data), rows, _stream(stream)),
                "tahoe_forest_predict_leaf_idx")
