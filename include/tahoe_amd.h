@@ -520,7 +520,8 @@ typedef struct {
  * 64-row float32 tile in LDS; needs 256 x num_cols bytes of LDS), AUTO = ROWTILE when the tile fits, else DIRECT; TILEBLOCK,
  * TILERING and QRING are TAHOE_ERR_UNSUPPORTED.
  * Out of scope, TAHOE_ERR_UNSUPPORTED with nothing launched and a text that says "oblivious": tahoe_forest_predict_csr,
- * _reserve_csr (and _get_csr_plan: form TAHOE_FORM_NONE), _predict_host, _set_stages, _predict_staged (_get_staged_strategy: 0),
+ * _reserve_csr (and _get_csr_plan: form TAHOE_FORM_NONE) unless the handle comes from tahoe_oblivious_forest_create_ex or
+ * _create_cat with TAHOE_CREATE_CSR; _predict_host, _set_stages, _predict_staged (_get_staged_strategy: 0),
  * _predict_contribs, _predict_contribs_approx, _predict_interactions, and _set_background with
  * _predict_contribs_interventional, unless the handle comes from tahoe_oblivious_forest_create_ex with that call's flag
  * (TAHOE_CREATE_STAGED for the three staged calls).  CatBoost's one-hot splits are
@@ -543,9 +544,24 @@ tahoe_status tahoe_oblivious_forest_create(tahoe_forest **out, const int32_t *de
  * stages are set, and everything else the handle serves is bit for bit what the handle without the flag gives.  A handle created
  * without it keeps refusing the three calls, with the same codes and texts as before the flag existed. */
 #define TAHOE_CREATE_STAGED 0x2000u
+/* CSR rows on an oblivious or a vector-leaf handle (tahoe_forest_predict_csr, tahoe_forest_reserve_csr, tahoe_forest_get_csr_plan,
+ * with the contract stated at tahoe_forest_predict_csr and nothing new): accepted by tahoe_oblivious_forest_create_ex,
+ * tahoe_oblivious_forest_create_cat and tahoe_vector_forest_create_ex, alone -- it reads no cover: leaf_covers / covers may be
+ * NULL, and it joins no cover check -- or beside any of their other flags; every other create refuses it as an unknown flag.  It
+ * builds no table: device_bytes is that of the handle without it until the first chunked CSR call (or tahoe_forest_reserve_csr)
+ * allocates the chunk buffer, and everything else the handle serves is bit for bit what the handle without the flag gives.  A
+ * handle created without it keeps refusing the three calls, with the same codes and texts as before the flag existed.
+ * ROWTILE, and AUTO where the 64-row tile fits (256 x num_cols bytes of LDS) and nnz x ceil(K / 8) <= 96 x rows, stage the tile
+ * straight from the CSR arrays (kernel forms TAHOE_OBLIVIOUS_FORM_CSR_TILE / TAHOE_VECTOR_FORM_CSR_TILE; with K > 8 every block of
+ * 8 classes stages it again); DIRECT, a tile that does not fit, AUTO on rows that store more than that, and AUTO under
+ * TAHOE_CSR_FUSED=0 run the handle's own kernels on densified chunks (tahoe_forest_get_csr_plan tells).
+ * Still refused on these handles, flag or not, because they take dense rows only: leaf indices from CSR, staged output from CSR,
+ * predict_accumulate from CSR, every explanation call from CSR; and there is no DIRECT kernel that reads CSR without a dense
+ * chunk. */
+#define TAHOE_CREATE_CSR 0x4000u
 /* The same handle with explanations.  flags: a subset of TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS |
  * TAHOE_CREATE_INTERACTIONS | TAHOE_CREATE_OBLIVIOUS_INTERVENTIONAL | TAHOE_CREATE_STAGED (staged prediction, stated at the flag
- * and at tahoe_forest_set_stages; Tc = num_trees, C = K), each serving its own call(s) and no other; with flags == 0
+ * and at tahoe_forest_set_stages; Tc = num_trees, C = K) | TAHOE_CREATE_CSR (CSR rows, stated at the flag), each serving its own call(s) and no other; with flags == 0
  * leaf_covers is ignored and the call is tahoe_oblivious_forest_create (which is this call with NULL, 0).  leaf_covers holds
  * sum_t 2^depths[t] floats, one per leaf in the order of the leaves: the training weight that reached the leaf (CatBoost's
  * leaf_weights).  Checks, before a device is touched and after those of tahoe_oblivious_forest_create: another flag bit, or one of
@@ -652,7 +668,8 @@ tahoe_status tahoe_oblivious_forest_create_cat(tahoe_forest **out, const int32_t
  * any num_cols), ROWTILE (TAHOE_VECTOR_FORM_TILE: one wave per 64-row float32 tile in LDS; needs 256 x num_cols bytes of LDS),
  * AUTO = ROWTILE when the tile fits, else DIRECT; TILEBLOCK, TILERING and QRING are TAHOE_ERR_UNSUPPORTED.
  * Out of scope, TAHOE_ERR_UNSUPPORTED with nothing launched and a text that names the call and says "vector-leaf":
- * tahoe_forest_predict_accumulate, _predict_host, _predict_csr, _reserve_csr (and _get_csr_plan: form TAHOE_FORM_NONE),
+ * tahoe_forest_predict_accumulate, _predict_host; _predict_csr, _reserve_csr (and _get_csr_plan: form TAHOE_FORM_NONE) unless the
+ * handle comes from _create_ex with TAHOE_CREATE_CSR;
  * _set_stages, _predict_staged (_get_staged_strategy: 0) unless the handle comes from _create_ex with TAHOE_CREATE_STAGED;
  * _predict_contribs_approx unless the handle comes from _create_ex with
  * TAHOE_CREATE_VECTOR_APPROX; _predict_contribs unless the handle comes from tahoe_vector_forest_create_ex with
@@ -674,7 +691,8 @@ tahoe_status tahoe_vector_forest_create(tahoe_forest **out, const int32_t *trees
 #define TAHOE_CREATE_VECTOR_APPROX 0x400u
 /* The same handle with explanations.  flags: a subset of TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_INTERVENTIONAL |
  * TAHOE_CREATE_VECTOR_INTERACTIONS | TAHOE_CREATE_VECTOR_APPROX | TAHOE_CREATE_STAGED (staged prediction, stated at the flag and
- * at tahoe_forest_set_stages; Tc = num_trees, C = K; it reads no covers and joins none of the checks below); with flags == 0 covers is ignored and the call is tahoe_vector_forest_create (which is this
+ * at tahoe_forest_set_stages; Tc = num_trees, C = K; it reads no covers and joins none of the checks below) | TAHOE_CREATE_CSR
+ * (CSR rows, stated at the flag; no covers and no checks either); with flags == 0 covers is ignored and the call is tahoe_vector_forest_create (which is this
  * call with NULL, 0), bit for bit; a handle created without TAHOE_CREATE_INTERVENTIONAL or without
  * TAHOE_CREATE_VECTOR_INTERACTIONS is bit for bit and byte for byte what it was before that flag existed.  With
  * TAHOE_CREATE_CONTRIBS covers[i] is the cover of nodes[i] (num_nodes floats; scikit-learn's tree_.weighted_n_node_samples).
@@ -772,11 +790,14 @@ tahoe_status tahoe_forest_predict(tahoe_forest *f, float *preds_dev, const float
  *     indptr_dev holds: entry ranges are clamped to nnz.  An entry whose column id is outside [0, num_cols) is skipped (its row
  *     reads the sentinel there) and raises a flag of its own in the handle: the next tahoe_forest_check returns
  *     TAHOE_ERR_INVALID_ARG with a text that says "column" and clears that flag, so a later clean call checks TAHOE_OK.
- *   - Served on dense, multi-class, sparse, multi-class sparse and categorical handles.  rows == 0: TAHOE_OK, nothing launched;
+ *   - Served on dense, multi-class, sparse, multi-class sparse and categorical handles, and on oblivious and vector-leaf handles
+ *     created with TAHOE_CREATE_CSR (without the flag: TAHOE_ERR_UNSUPPORTED, as stated at their creates; on a handle with
+ *     category sets the level rule of tahoe_oblivious_forest_create_cat applies to the densified row).  rows == 0: TAHOE_OK, nothing launched;
  *     nnz == 0 with rows > 0 is valid (every value missing).  NULL preds_dev / indptr_dev with rows > 0, NULL indices_dev /
  *     values_dev with nnz > 0, or nnz > INT64_MAX: TAHOE_ERR_INVALID_ARG, checked before the handle or a device is touched.
  *   - Asynchronous on `stream`.  ROWTILE, and on sparse handles TILEBLOCK, stage their 64-row LDS tile straight from the CSR
- *     arrays (kernel forms TAHOE_FORM_CSR_*); every other kernel form gets the batch densified chunk by chunk into a buffer the
+ *     arrays (kernel forms TAHOE_FORM_CSR_*; ROWTILE on an oblivious or vector-leaf handle: TAHOE_OBLIVIOUS_FORM_CSR_TILE /
+ *     TAHOE_VECTOR_FORM_CSR_TILE); every other kernel form gets the batch densified chunk by chunk into a buffer the
  *     handle owns -- at most TAHOE_CSR_CHUNK_MB MiB (read at create, default 64; at least one 64-row tile), counted in
  *     device_bytes -- and runs on each chunk in turn.  Under AUTO the path is picked from num_cols, the trees and nnz / rows
  *     (tahoe_forest_get_csr_plan tells).  The buffer and the kernels' workspace grow on demand, which allocates and
@@ -958,6 +979,12 @@ enum {
 enum {
     TAHOE_VECTOR_FORM_DIRECT = 27,        /* vector_direct_kernel: features from global memory */
     TAHOE_VECTOR_FORM_TILE = 28           /* vector_tile_kernel: one wave per 64-row float32 tile */
+};
+/* The fused CSR forms of those two handle kinds (TAHOE_CREATE_CSR).  29 stays unassigned for the same reason: the first value past
+ * TAHOE_VECTOR_FORM_TILE has no name (tahoe_kernel_form_name(29) == "?"). */
+enum {
+    TAHOE_OBLIVIOUS_FORM_CSR_TILE = 30,   /* tahoe_forest_predict_csr only: oblivious_tile_kernel staging its tile from the CSR arrays */
+    TAHOE_VECTOR_FORM_CSR_TILE = 31       /* ... vector_tile_kernel */
 };
 int tahoe_forest_get_kernel_form(const tahoe_forest *f, size_t rows);
 const char *tahoe_kernel_form_name(int form);

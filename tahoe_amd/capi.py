@@ -44,6 +44,7 @@ CREATE_VECTOR_INTERACTIONS = 0x100  # tahoe_vector_forest_create_ex, with CREATE
 CREATE_OBLIVIOUS_INTERVENTIONAL = 0x200  # tahoe_oblivious_forest_create_ex: interventional TreeSHAP (tahoe_forest_set_background), no covers needed
 CREATE_PARTIAL_DEPENDENCE = 0x800  # tahoe_sparse_forest_create_ex / _cat: partial dependence (tahoe_forest_predict_partial_dependence); needs covers
 CREATE_STAGED = 0x2000  # tahoe_oblivious_forest_create_ex / _cat, tahoe_vector_forest_create_ex: set_stages / predict_staged; no covers needed
+CREATE_CSR = 0x4000  # the same three creates: predict_csr / reserve_csr / csr_plan; no covers needed
 CREATE_VECTOR_APPROX = 0x400  # tahoe_vector_forest_create_ex: Saabas contributions (tahoe_forest_predict_contribs_approx); needs covers
 STRATEGY_NAMES = {1: "direct", 2: "rowtile", 3: "tileblock", 4: "tilering", 5: "qring"}
 STATUS_NAMES = {
@@ -859,12 +860,13 @@ class ObliviousForest(Forest):
     over the flattened (tree, level) records) makes those levels category-set splits, members going right unless the index is in
     members_left (tahoe_oblivious_forest_create_cat; the level's threshold is then ignored); every call above follows the sets.
     staged=True (TAHOE_CREATE_STAGED; needs no leaf_covers) serves set_stages, predict_staged and staged_strategy: the outputs after
-    the first rounds[s] trees, [rows, S] for leaf_dim == 1 and [rows, S, leaf_dim] otherwise (CatBoost's staged_predict)."""
+    the first rounds[s] trees, [rows, S] for leaf_dim == 1 and [rows, S, leaf_dim] otherwise (CatBoost's staged_predict).
+    csr=True (TAHOE_CREATE_CSR; needs no leaf_covers) serves predict_csr, reserve_csr and csr_plan (a sparse Pool's rows)."""
 
     def __init__(self, depths, fids, thresholds, def_left, leaf_values, num_cols: int, leaf_dim: int = 1, missing: float = 0.0,
                  output: int = OUT_RAW, threshold: float = 0.5, global_bias: float = 0.0, leaf_covers=None, contribs: bool = False,
                  approx_contribs: bool = False, interactions: bool = False, interventional: bool = False, categories=None,
-                 members_left=(), staged: bool = False):
+                 members_left=(), staged: bool = False, csr: bool = False):
         depths = np.ascontiguousarray(depths, dtype=np.int32).reshape(-1)
         fids = np.asarray(fids, dtype=np.int64).reshape(-1)
         nsplits = int(depths.astype(np.int64).sum())
@@ -885,7 +887,7 @@ class ObliviousForest(Forest):
         self._h = _vp()
         flags = ((CREATE_CONTRIBS if contribs else 0) | (CREATE_APPROX_CONTRIBS if approx_contribs else 0)
                  | (CREATE_INTERACTIONS if interactions else 0))
-        if flags or interventional or categories or staged:
+        if flags or interventional or categories or staged or csr:
             cv = None
             if flags:
                 if leaf_covers is None:
@@ -894,7 +896,8 @@ class ObliviousForest(Forest):
                 if covers.size * leaf_dim != leaves.size:
                     raise ValueError("leaf_covers.size != sum(2 ** depths)")
                 cv = covers if covers.size else np.zeros(1, np.float32)
-            flags |= (CREATE_OBLIVIOUS_INTERVENTIONAL if interventional else 0) | (CREATE_STAGED if staged else 0)
+            flags |= ((CREATE_OBLIVIOUS_INTERVENTIONAL if interventional else 0) | (CREATE_STAGED if staged else 0)
+                      | (CREATE_CSR if csr else 0))
             if categories:
                 cats, _keep = pack_categorical(categories, members_left)
                 _check(lib.tahoe_oblivious_forest_create_cat(C.byref(self._h), dp.ctypes.data, splits.ctypes.data if nsplits else None,
@@ -927,12 +930,13 @@ class VectorForest(Forest):
     approx_contribs=True (TAHOE_CREATE_VECTOR_APPROX; needs covers, checks no path length) serves predict_contribs_approx: the
     Saabas contributions of every output, what treeinterpreter computes for a scikit-learn forest, in predict_contribs' shape.
     staged=True (TAHOE_CREATE_STAGED; needs no covers) serves set_stages, predict_staged and staged_strategy: the outputs after the
-    first rounds[s] trees, [rows, S] for K == 1 and [rows, S, K] otherwise (XGBoost's iteration_range, a forest's error curve)."""
+    first rounds[s] trees, [rows, S] for K == 1 and [rows, S, K] otherwise (XGBoost's iteration_range, a forest's error curve).
+    csr=True (TAHOE_CREATE_CSR; needs no covers) serves predict_csr, reserve_csr and csr_plan (a forest fit on a scipy CSR matrix)."""
 
     def __init__(self, nodes: np.ndarray, trees: np.ndarray, leaf_values, num_cols: int, leaf_dim: int = None,
                  missing: float = 0.0, output: int = OUT_RAW, threshold: float = 0.5, global_bias: float = 0.0, covers=None,
                  contribs: bool = False, interventional: bool = False, interactions: bool = False,
-                 approx_contribs: bool = False, staged: bool = False):
+                 approx_contribs: bool = False, staged: bool = False, csr: bool = False):
         nodes = np.ascontiguousarray(nodes, dtype=SPARSE_NODE_DTYPE)
         trees = np.ascontiguousarray(trees, dtype=np.int32).reshape(-1)
         lv = np.asarray(leaf_values, dtype=np.float32)
@@ -952,7 +956,8 @@ class VectorForest(Forest):
         self._h = _vp()
         flags = ((CREATE_CONTRIBS if contribs else 0) | (CREATE_INTERVENTIONAL if interventional else 0)
                  | (CREATE_CONTRIBS | CREATE_VECTOR_INTERACTIONS if interactions else 0)
-                 | (CREATE_VECTOR_APPROX if approx_contribs else 0) | (CREATE_STAGED if staged else 0))
+                 | (CREATE_VECTOR_APPROX if approx_contribs else 0) | (CREATE_STAGED if staged else 0)
+                 | (CREATE_CSR if csr else 0))
         if covers is not None or flags:
             cv = None if covers is None else np.ascontiguousarray(covers, dtype=np.float32).reshape(-1)
             if cv is not None and cv.size != nodes.size:

@@ -1,8 +1,9 @@
 // Predictions from CSR rows (tahoe_forest_predict_csr): an entry that is not stored is the missing value.
 //
 // Two paths, chosen per call by csr_fused_strategy (forest.hip; DESIGN.md, "CSR rows"):
-//   fused     the 64-row float32 tile kernels (rowtile_kernel, sparse_kernel<TILE>, sparse_top_kernel) stage their LDS tile
-//             straight from the CSR arrays (csr_stage_tile, forest_internal.h): no dense copy exists anywhere
+//   fused     the 64-row float32 tile kernels (rowtile_kernel, sparse_kernel<TILE>, sparse_top_kernel; oblivious_tile_kernel and
+//             vector_tile_kernel on a handle of TAHOE_CREATE_CSR) stage their LDS tile straight from the CSR arrays
+//             (csr_stage_tile, csr_stage_tile_wave; forest_internal.h): no dense copy exists anywhere
 //   fallback  csr_densify_kernel writes a chunk of rows as dense float32 into a buffer the handle owns (capped by
 //             TAHOE_CSR_CHUNK_MB, counted in device_bytes), the handle's own predict path runs on the chunk, and so on chunk
 //             after chunk on the caller's stream: every other kernel form is served, with extra memory independent of `rows`
@@ -86,6 +87,8 @@ void csr_destroy(tahoe_forest *f)
 
 static int csr_fused_form(const tahoe_forest *f, int strategy)
 {
+    if (f->ob) return TAHOE_OBLIVIOUS_FORM_CSR_TILE;
+    if (f->vl) return TAHOE_VECTOR_FORM_CSR_TILE;
     if (!f->sp) return TAHOE_FORM_CSR_ROWTILE;
     return strategy == TAHOE_STRATEGY_TILEBLOCK ? TAHOE_FORM_CSR_SPARSE_TOP : TAHOE_FORM_CSR_SPARSE_ROWTILE;
 }
@@ -112,8 +115,7 @@ tahoe_status tahoe_forest_predict_csr(tahoe_forest *f, float *preds_dev, const i
     if (rows && (!preds_dev || !indptr_dev)) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_csr: null preds_dev / indptr_dev");
     if (nnz && (!indices_dev || !values_dev)) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_csr: null indices_dev / values_dev");
     if (nnz > (size_t)INT64_MAX) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_predict_csr: nnz %zu does not fit indptr's int64", nnz);
-    if (const tahoe_status st = refuse_oblivious(f, "tahoe_forest_predict_csr")) return st;
-    if (const tahoe_status st = refuse_vector(f, "tahoe_forest_predict_csr")) return st;
+    if (const tahoe_status st = refuse_no_csr(f, "tahoe_forest_predict_csr")) return st;
     if (rows == 0) return TAHOE_OK;
     hipStream_t stream = (hipStream_t)stream_;
     DeviceGuard on_device(f->device);
@@ -152,8 +154,7 @@ tahoe_status tahoe_forest_predict_csr(tahoe_forest *f, float *preds_dev, const i
 tahoe_status tahoe_forest_reserve_csr(tahoe_forest *f, size_t rows, size_t nnz)
 {
     if (!f) return fail(TAHOE_ERR_INVALID_ARG, "null forest");
-    if (const tahoe_status st = refuse_oblivious(f, "tahoe_forest_reserve_csr")) return st;
-    if (const tahoe_status st = refuse_vector(f, "tahoe_forest_reserve_csr")) return st;
+    if (const tahoe_status st = refuse_no_csr(f, "tahoe_forest_reserve_csr")) return st;
     // Which path a later call takes depends on its own rows and nnz, so the fallback's workspace is sized whatever `nnz` says: the
     // chunk buffer, and what the handle's kernels need for a batch of one chunk.  The fused kernels need no workspace.
     (void)nnz;
@@ -165,10 +166,10 @@ tahoe_status tahoe_forest_reserve_csr(tahoe_forest *f, size_t rows, size_t nnz)
 tahoe_status tahoe_forest_get_csr_plan(const tahoe_forest *f, size_t rows, size_t nnz, int *form, size_t *chunk_rows)
 {
     if (!f || !form || !chunk_rows) return fail(TAHOE_ERR_INVALID_ARG, "null argument");
-    if (f->ob || f->vl) {  // no CSR path: nothing would be launched
+    if (const tahoe_status st = refuse_no_csr(f, "tahoe_forest_get_csr_plan")) {  // no CSR path: nothing would be launched
         *form = TAHOE_FORM_NONE;
         *chunk_rows = 0;
-        return f->ob ? refuse_oblivious(f, "tahoe_forest_get_csr_plan") : refuse_vector(f, "tahoe_forest_get_csr_plan");
+        return st;
     }
     const int fused = csr_fused_strategy(f, rows, nnz);
     *chunk_rows = fused >= 0 ? 0 : csr_chunk_cap(f);

@@ -969,10 +969,10 @@ static tahoe_status launch_traversal(tahoe_forest *f, float *sums, uint32_t *lea
         else if (sums && !sums_in)
             TAHOE_HIP_TRY(hipMemsetAsync(sums, 0, rows * (size_t)f->num_classes * sizeof(float), stream));
     } else if (f->ob) {
-        const tahoe_status os = oblivious_launch(f, sums, leaf_out, data, rows, stream, strategy, sums_in);
+        const tahoe_status os = oblivious_launch(f, sums, leaf_out, data, rows, stream, strategy, sums_in, csr);
         if (os != TAHOE_OK) return os;
     } else if (f->vl) {
-        const tahoe_status vs = vector_launch(f, sums, leaf_out, data, rows, stream, strategy);
+        const tahoe_status vs = vector_launch(f, sums, leaf_out, data, rows, stream, strategy, csr);
         if (vs != TAHOE_OK) return vs;
     } else if (f->sp) {
         const tahoe_status ss = sparse_launch(f, sums, leaf_out, data, rows, stream, strategy, sums_in, csr);
@@ -1234,7 +1234,7 @@ static tahoe_status launch_staged_dense(tahoe_forest *f, float *out, const float
 int csr_fused_strategy(const tahoe_forest *f, size_t rows, size_t nnz)
 {
     if (f->p.num_trees == 0) return -1;
-    const bool tile = f->sp ? sparse_tile_fits(f) : rowtile_fits(f);
+    const bool tile = f->ob ? oblivious_tile_fits(f) : f->vl ? vector_tile_fits(f) : f->sp ? sparse_tile_fits(f) : rowtile_fits(f);
     const bool top = f->sp && sparse_top_waves(f) > 0;
     // a forced strategy is honoured: the tile kernels that have the loader take it, every other strategy gets dense chunks
     if (f->strategy == TAHOE_STRATEGY_ROWTILE) return tile ? TAHOE_STRATEGY_ROWTILE : -1;
@@ -1242,6 +1242,19 @@ int csr_fused_strategy(const tahoe_forest *f, size_t rows, size_t nnz)
     if (f->strategy != TAHOE_STRATEGY_AUTO || f->knobs.csr_fused == 0) return -1;
     const int fused = top ? TAHOE_STRATEGY_TILEBLOCK : tile ? TAHOE_STRATEGY_ROWTILE : -1;
     if (f->knobs.csr_fused > 0) return fused;
+    if (f->ob || f->vl) {
+        // An oblivious or vector-leaf handle (TAHOE_CREATE_CSR), as measured (tools/native_csr_time.py,
+        // profiles/native_csr/native_csr_time.json).  AUTO runs the tile kernel on dense rows whenever the tile
+        // fits, so rule 1 alone would take the fused form at every density; it lost where rows store many entries: the one-wave
+        // loader scatters a row's entries 8 at a time behind two dependent loads, once per block of 8 classes, and a 64-row tile
+        // keeps ever fewer waves on a CU as it widens, while the densify pass costs the same per column at any density.  Both
+        // sides grow with num_cols, and the crossover sat near 100 stagings of an entry per row at 64 and at 512 columns (200 k
+        // rows, 100 trees: 64 columns, every entry stored, K = 8 fused / fallback 0.95, K = 10 -- two class blocks -- 1.02; 512
+        // columns, K = 8, oblivious 0.80 at 26 entries per row and 1.10 at 128, vector-leaf 0.77 at 26, 0.95 at 128 and 1.46
+        // at 512); a threshold of 96 keeps all of those on their faster side but the vector-leaf cell at 128, which it gives up 5 %.
+        const double class_blocks = (double)((f->num_classes + 7) / 8);  // (kObClasses = kVecClasses = 8)
+        return tile && (double)nnz * class_blocks <= 96.0 * (double)rows ? TAHOE_STRATEGY_ROWTILE : -1;
+    }
     // AUTO, as measured (tools/csr_time.py, profiles/csr/csr_time.json).  Where AUTO runs that tile kernel
     // on dense rows anyway, the same kernel fed from CSR saves writing the chunk and reading it back: faster at every density.
     if (resolve_strategy(f, rows) == fused) return fused;
@@ -1727,7 +1740,8 @@ const char *tahoe_kernel_form_name(int form)
                                         "qring_split", "qring_columns", "qring_wide", "qring_gx", "sparse_direct",
                                         "sparse_rowtile", "sparse_top", "sparse_qring", "qring_region8", "qring_region6",
                                         "csr_rowtile", "csr_sparse_rowtile", "csr_sparse_top", "?" /* 23: unassigned */, "oblivious_direct",
-                                        "oblivious_tile", "?" /* 26: unassigned */, "vector_direct", "vector_tile"};
+                                        "oblivious_tile", "?" /* 26: unassigned */, "vector_direct", "vector_tile", "?" /* 29: unassigned */,
+                                        "oblivious_csr_tile", "vector_csr_tile"};
     return form >= 0 && form < (int)(sizeof(names) / sizeof(names[0])) ? names[form] : "?";
 }
 

@@ -144,6 +144,9 @@ struct tahoe_forest {
     // An oblivious or vector-leaf handle created with TAHOE_CREATE_STAGED: the three staged calls are served (every other handle
     // kind serves them without a flag)
     bool staged = false;
+    // An oblivious or vector-leaf handle created with TAHOE_CREATE_CSR: the three CSR calls are served (every other handle kind
+    // serves them without a flag)
+    bool csr = false;
 };
 
 namespace tahoe {
@@ -305,6 +308,35 @@ __device__ __forceinline__ void csr_stage_tile(float *tile, int64_t *range, int 
     if (bad) atomicOr(csr.bad_column, 1);
 }
 
+// The one-wave form of csr_stage_tile, for the 64-thread tile kernels of oblivious and vector-leaf handles (lane = row): the same
+// fill, barrier and 8-lanes-per-row scatter, with no LDS scratch -- lane r keeps the clamped entry range of row row0 + r in
+// registers (the tile's 65 indptr values, read once per workgroup), and the kCsrLanes lanes that scatter row r get it by a wave
+// shuffle; the LDS need stays the tile's.  8 passes of 8 rows: a wave does not wait on the longest row of its tile as it would
+// with "lane owns its row", and each row's indices / values are read as 32-byte runs.  The scatter lands on words that other
+// lanes filled and the walk reads words that other lanes scattered: a barrier before it (here) and one after it (the caller's).
+__device__ __forceinline__ void csr_stage_tile_wave(float *tile, int cols, size_t row0, size_t rows, const CsrView &csr,
+                                                    float missing, int lane)
+{
+    float4 *tile4 = reinterpret_cast<float4 *>(tile);
+    const float4 m4 = make_float4(missing, missing, missing, missing);
+    for (int i = lane; i < cols * (kTileRows / 4); i += kTileRows) tile4[i] = m4;
+    const int64_t begin = csr_row_begin(csr, row0 + lane, rows);
+    const int64_t end = csr_row_begin(csr, row0 + lane + 1, rows);
+    __syncthreads();  // the fill lands before the scatter (s_waitcnt lgkmcnt(0); a one-wave workgroup needs no s_barrier beside it)
+    const int sub = lane % kCsrLanes;
+    bool bad = false;
+    for (int r = lane / kCsrLanes; r < kTileRows; r += kTileRows / kCsrLanes) {
+        const int64_t row_end = __shfl(end, r);  // (every lane is active here: the inner loop has reconverged)
+        for (int64_t k = __shfl(begin, r) + sub; k < row_end; k += kCsrLanes) {
+            const int32_t c = csr.indices[k];
+            const float v = csr.values[k];
+            if ((uint32_t)c < (uint32_t)cols) tile[c * kTileRows + r] = v;
+            else bad = true;
+        }
+    }
+    if (bad) atomicOr(csr.bad_column, 1);
+}
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is per function and process-wide, not per handle: always raise it to
 // the device limit (less the kernel's static LDS), so that handles of different shapes can coexist in one process.
 inline hipError_t allow_max_lds(const void *fn, int limit)
@@ -414,7 +446,7 @@ tahoe_status strategy_available(const tahoe_forest *f, int strategy);
 tahoe_status predict_rows(tahoe_forest *f, float *preds, const float *data, size_t rows, hipStream_t stream,
                           const CsrView *csr = nullptr, int csr_strategy = 0);
 // The strategy whose fused CSR kernel serves a batch of `rows` rows with nnz stored entries (ROWTILE, or TILEBLOCK on a sparse
-// handle), or -1: the batch is densified in chunks and takes the handle's own path (csr.hip)
+// handle; ROWTILE on an oblivious or vector-leaf handle of TAHOE_CREATE_CSR), or -1: the batch is densified in chunks and takes the handle's own path (csr.hip)
 int csr_fused_strategy(const tahoe_forest *f, size_t rows, size_t nnz);
 void csr_destroy(tahoe_forest *f);
 
@@ -561,8 +593,9 @@ tahoe_status contribs_build_sparse(tahoe_forest *f, const int32_t *trees, const 
 void contribs_destroy(tahoe_forest *f);
 // oblivious forests (oblivious.hip): strategy ROWTILE = oblivious_tile_kernel, DIRECT = oblivious_direct_kernel
 bool oblivious_tile_fits(const tahoe_forest *f);
+// csr (optional; a handle of TAHOE_CREATE_CSR, strategy ROWTILE, predictions only): the tile is staged from there, `data` is not read
 tahoe_status oblivious_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data, size_t rows, hipStream_t stream,
-                              int strategy, const float *sums_in);
+                              int strategy, const float *sums_in, const CsrView *csr = nullptr);
 // tahoe_forest_predict_staged on a handle created with TAHOE_CREATE_STAGED: the same walk (DIRECT or ROWTILE) with the stage stores
 // to out[rows][num_stages][K]; oblivious_allow_staged_lds lets its tile kernel take the device's LDS (set_stages calls it)
 tahoe_status oblivious_launch_staged(tahoe_forest *f, float *out, const float *data, size_t rows, hipStream_t stream, int strategy);
@@ -590,8 +623,9 @@ inline tahoe_status refuse_oblivious(const tahoe_forest *f, const char *fn)
 }
 // vector-leaf forests (vector.hip): strategy ROWTILE = vector_tile_kernel, DIRECT = vector_direct_kernel
 bool vector_tile_fits(const tahoe_forest *f);
+// (csr: as oblivious_launch's)
 tahoe_status vector_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data, size_t rows, hipStream_t stream,
-                           int strategy);
+                           int strategy, const CsrView *csr = nullptr);
 // ... and the same pair for a vector-leaf handle created with TAHOE_CREATE_STAGED
 tahoe_status vector_launch_staged(tahoe_forest *f, float *out, const float *data, size_t rows, hipStream_t stream, int strategy);
 tahoe_status vector_allow_staged_lds(const tahoe_forest *f);
@@ -624,6 +658,13 @@ inline tahoe_status refuse_vector(const tahoe_forest *f, const char *fn)
 inline tahoe_status refuse_unstaged(const tahoe_forest *f, const char *fn)
 {
     if (f->staged) return TAHOE_OK;
+    if (const tahoe_status s = refuse_oblivious(f, fn)) return s;
+    return refuse_vector(f, fn);
+}
+// ... of the three CSR entry points: both refusals give way on a handle created with TAHOE_CREATE_CSR
+inline tahoe_status refuse_no_csr(const tahoe_forest *f, const char *fn)
+{
+    if (f->csr) return TAHOE_OK;
     if (const tahoe_status s = refuse_oblivious(f, fn)) return s;
     return refuse_vector(f, fn);
 }

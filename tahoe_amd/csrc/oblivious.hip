@@ -137,7 +137,10 @@ __device__ __forceinline__ void oblivious_walk(const InnerNode *__restrict__ spl
 // rowtile_kernel; a level's feature is the row tile[fid][0..64): 64 consecutive floats, no bank conflict, no per-lane address
 // arithmetic.  A lane reads back only what it stored itself, so there is no barrier after staging, and nothing crosses waves.
 // Dynamic LDS: [cols][64] float.
-template <int KB, bool WRITE_LEAF, bool CAT, bool STAGED = false>
+// CSR (tahoe_forest_predict_csr on a handle of TAHOE_CREATE_CSR): the tile is staged from csr by
+// csr_stage_tile_wave (forest_internal.h) and `data` is not read.  There kCsrLanes lanes scatter one row, so a lane does read what
+// other lanes stored: a barrier stands between the staging and the walk.  Every class block stages the tile again.
+template <int KB, bool WRITE_LEAF, bool CAT, bool STAGED = false, bool CSR = false>
 __global__ void __launch_bounds__(kTileRows) oblivious_tile_kernel(const InnerNode *__restrict__ splits,
                                                                    const int32_t *__restrict__ split_off,
                                                                    const int64_t *__restrict__ leaf_off,
@@ -145,8 +148,10 @@ __global__ void __launch_bounds__(kTileRows) oblivious_tile_kernel(const InnerNo
                                                                    float *sums, uint32_t *__restrict__ leaf_out, const float *sums_in,
                                                                    size_t rows, int cols, int num_trees, int K, float missing,
                                                                    int vec4_ok, const uint32_t *__restrict__ cat_pool,
-                                                                   uint32_t cat_words, const int32_t *__restrict__ stages, int S)
+                                                                   uint32_t cat_words, const int32_t *__restrict__ stages, int S,
+                                                                   CsrView csr)
 {
+    static_assert(!CSR || (!WRITE_LEAF && !STAGED), "CSR rows: predictions only");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float *tile = reinterpret_cast<float *>(smem);
     const int lane = threadIdx.x;
@@ -156,18 +161,23 @@ __global__ void __launch_bounds__(kTileRows) oblivious_tile_kernel(const InnerNo
     const int first_end = STAGED ? stages[0] : 0;
 
     // ---- stage the row tile, transposed to feature-major ----
-    const float *src = data + (row_ok ? row : row0) * (size_t)cols;
-    if (vec4_ok) {
-        const float4 *src4 = reinterpret_cast<const float4 *>(src);
-        for (int f4 = 0; f4 < cols / 4; ++f4) {
-            float4 v = row_ok ? src4[f4] : make_float4(0.f, 0.f, 0.f, 0.f);
-            tile[(4 * f4 + 0) * kTileRows + lane] = v.x;
-            tile[(4 * f4 + 1) * kTileRows + lane] = v.y;
-            tile[(4 * f4 + 2) * kTileRows + lane] = v.z;
-            tile[(4 * f4 + 3) * kTileRows + lane] = v.w;
-        }
+    if constexpr (CSR) {
+        csr_stage_tile_wave(tile, cols, row0, rows, csr, missing, lane);
+        __syncthreads();  // the walk reads what other lanes scattered
     } else {
-        for (int f = 0; f < cols; ++f) tile[f * kTileRows + lane] = row_ok ? src[f] : 0.0f;
+        const float *src = data + (row_ok ? row : row0) * (size_t)cols;
+        if (vec4_ok) {
+            const float4 *src4 = reinterpret_cast<const float4 *>(src);
+            for (int f4 = 0; f4 < cols / 4; ++f4) {
+                float4 v = row_ok ? src4[f4] : make_float4(0.f, 0.f, 0.f, 0.f);
+                tile[(4 * f4 + 0) * kTileRows + lane] = v.x;
+                tile[(4 * f4 + 1) * kTileRows + lane] = v.y;
+                tile[(4 * f4 + 2) * kTileRows + lane] = v.z;
+                tile[(4 * f4 + 3) * kTileRows + lane] = v.w;
+            }
+        } else {
+            for (int f = 0; f < cols; ++f) tile[f * kTileRows + lane] = row_ok ? src[f] : 0.0f;
+        }
     }
 
     oblivious_walk<KB, WRITE_LEAF, CAT, STAGED>(splits, split_off, leaf_off, leaves, sums, leaf_out, sums_in, row, row_ok, num_trees,
@@ -198,11 +208,14 @@ static long long oblivious_tile_bytes(const tahoe_forest *f) { return (long long
 
 bool oblivious_tile_fits(const tahoe_forest *f) { return f->p.num_cols >= 1 && oblivious_tile_bytes(f) <= f->lds_limit; }
 
-// The launch of both forms.  STAGED: sums is out[rows][num_stages][K], leaf_out and sums_in are null
+// The launch of both forms.  STAGED: sums is out[rows][num_stages][K], leaf_out and sums_in are null.  csr (never with STAGED):
+// the tile kernel's CSR instantiation; strategy is ROWTILE (csr_fused_strategy), leaf_out null
 template <bool STAGED>
 static tahoe_status oblivious_launch_as(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data, size_t rows,
-                                        hipStream_t stream, int strategy, const float *sums_in)
+                                        hipStream_t stream, int strategy, const float *sums_in, const CsrView *csr = nullptr)
 {
+    if (csr && (STAGED || leaf_out || strategy != TAHOE_STRATEGY_ROWTILE))
+        return fail(TAHOE_ERR_UNSUPPORTED, "oblivious_launch: CSR rows are served by the tile kernel, predictions only");
     const tahoe_ostate *o = f->ob;
     const int32_t *stages = STAGED ? f->stages_dev : nullptr;
     const int S = STAGED ? (int)f->num_stages : 0;
@@ -213,11 +226,19 @@ static tahoe_status oblivious_launch_as(tahoe_forest *f, float *sums, uint32_t *
         constexpr int KB = decltype(kb)::value;
         constexpr bool WL = decltype(wl)::value && !STAGED;
         constexpr bool CAT = decltype(cat)::value;
-        if (strategy == TAHOE_STRATEGY_ROWTILE)
+        if (csr) {
+            if constexpr (!STAGED && !WL)
+                hipLaunchKernelGGL((oblivious_tile_kernel<KB, false, CAT, false, true>),
+                                   dim3((unsigned)((rows + kTileRows - 1) / kTileRows), blocks_y), dim3(kTileRows),
+                                   (size_t)oblivious_tile_bytes(f), stream, o->splits, o->split_off, o->leaf_off, o->leaves, data, sums,
+                                   leaf_out, sums_in, rows, cols, T, K, f->p.missing, vec4_ok, o->cat_pool, o->cat_words, stages, S,
+                                   *csr);
+        } else if (strategy == TAHOE_STRATEGY_ROWTILE)
             hipLaunchKernelGGL((oblivious_tile_kernel<KB, WL, CAT, STAGED>),
                                dim3((unsigned)((rows + kTileRows - 1) / kTileRows), blocks_y), dim3(kTileRows),
                                (size_t)oblivious_tile_bytes(f), stream, o->splits, o->split_off, o->leaf_off, o->leaves, data, sums,
-                               leaf_out, sums_in, rows, cols, T, K, f->p.missing, vec4_ok, o->cat_pool, o->cat_words, stages, S);
+                               leaf_out, sums_in, rows, cols, T, K, f->p.missing, vec4_ok, o->cat_pool, o->cat_words, stages, S,
+                               CsrView{});
         else
             hipLaunchKernelGGL((oblivious_direct_kernel<KB, WL, CAT, STAGED>), dim3((unsigned)((rows + kBlock - 1) / kBlock), blocks_y),
                                dim3(kBlock), 0, stream, o->splits, o->split_off, o->leaf_off, o->leaves, data, sums, leaf_out, sums_in,
@@ -236,9 +257,9 @@ static tahoe_status oblivious_launch_as(tahoe_forest *f, float *sums, uint32_t *
 }
 
 tahoe_status oblivious_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data, size_t rows, hipStream_t stream,
-                              int strategy, const float *sums_in)
+                              int strategy, const float *sums_in, const CsrView *csr)
 {
-    return oblivious_launch_as<false>(f, sums, leaf_out, data, rows, stream, strategy, sums_in);
+    return oblivious_launch_as<false>(f, sums, leaf_out, data, rows, stream, strategy, sums_in, csr);
 }
 
 tahoe_status oblivious_launch_staged(tahoe_forest *f, float *out, const float *data, size_t rows, hipStream_t stream, int strategy)
@@ -271,6 +292,14 @@ static tahoe_status oblivious_allow_lds(const tahoe_forest *f)
             : ((e = allow_max_lds_leaf([](auto wl) { return &oblivious_tile_kernel<1, decltype(wl)::value, false>; }, f->lds_limit)) != hipSuccess ||
                (e = allow_max_lds_leaf([](auto wl) { return &oblivious_tile_kernel<kObClasses, decltype(wl)::value, false>; }, f->lds_limit)) != hipSuccess))
         return hip_status(e, "hipFuncSetAttribute(oblivious_tile)");
+    if (f->csr) {  // the CSR-loader instantiations (tahoe_forest_predict_csr) of this handle's kind
+        const bool one = f->num_classes == 1;
+        const void *fn = f->ob->cats ? (one ? reinterpret_cast<const void *>(&oblivious_tile_kernel<1, false, true, false, true>)
+                                            : reinterpret_cast<const void *>(&oblivious_tile_kernel<kObClasses, false, true, false, true>))
+                                     : (one ? reinterpret_cast<const void *>(&oblivious_tile_kernel<1, false, false, false, true>)
+                                            : reinterpret_cast<const void *>(&oblivious_tile_kernel<kObClasses, false, false, false, true>));
+        return hip_status(allow_max_lds(fn, f->lds_limit), "hipFuncSetAttribute(oblivious_tile, csr)");
+    }
     return TAHOE_OK;
 }
 
@@ -335,9 +364,10 @@ extern "C" tahoe_status tahoe_oblivious_forest_create_cat(tahoe_forest **out, co
     }
 
     // ... and the checks of the explanation flags, after those every create makes
-    // (TAHOE_CREATE_STAGED opens tahoe_forest_set_stages / _predict_staged, reads no cover and builds no table)
-    const bool staged = (flags & TAHOE_CREATE_STAGED) != 0;
-    flags &= ~(unsigned)TAHOE_CREATE_STAGED;
+    // (TAHOE_CREATE_STAGED opens tahoe_forest_set_stages / _predict_staged, reads no cover and builds no table; TAHOE_CREATE_CSR
+    // opens tahoe_forest_predict_csr / _reserve_csr / _get_csr_plan in the same way)
+    const bool staged = (flags & TAHOE_CREATE_STAGED) != 0, csr_rows = (flags & TAHOE_CREATE_CSR) != 0;
+    flags &= ~(unsigned)(TAHOE_CREATE_STAGED | TAHOE_CREATE_CSR);
     if (flags & ~(unsigned)(TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS | TAHOE_CREATE_INTERACTIONS |
                             TAHOE_CREATE_OBLIVIOUS_INTERVENTIONAL))
         return fail(TAHOE_ERR_INVALID_ARG, "tahoe_oblivious_forest_create_ex: flags 0x%x: only TAHOE_CREATE_CONTRIBS, "
@@ -383,6 +413,7 @@ extern "C" tahoe_status tahoe_oblivious_forest_create_cat(tahoe_forest **out, co
     f->class_trees = T;  // AVG divides by (float)num_trees whatever K is
     f->p.depth = f->depth = max_depth;
     f->staged = staged;
+    f->csr = csr_rows;
     f->ob = new (std::nothrow) tahoe_ostate();
     if (!f->ob) return fail(TAHOE_ERR_NO_MEMORY, "tahoe_oblivious_forest_create");
     tahoe_ostate *o = f->ob;

@@ -131,13 +131,16 @@ __device__ __forceinline__ void vector_walk(const VNode *__restrict__ nodes, con
 // of oblivious_tile_kernel.  A node's feature is tile[fid * 64 + lane] with a per-lane fid: the bank is the lane's whatever fid
 // is, so the read is conflict-free.  A lane reads back only what it stored itself, so there is no barrier after staging, and
 // nothing crosses waves.  Dynamic LDS: [cols][64] float.
-template <int KB, bool WRITE_LEAF, bool STAGED = false>
+// CSR (tahoe_forest_predict_csr on a handle of TAHOE_CREATE_CSR): as oblivious_tile_kernel's -- the tile is
+// staged by csr_stage_tile_wave, whose lanes store other lanes' rows, so a barrier stands between the staging and the walk.
+template <int KB, bool WRITE_LEAF, bool STAGED = false, bool CSR = false>
 __global__ void __launch_bounds__(kTileRows) vector_tile_kernel(const VNode *__restrict__ nodes, const int32_t *__restrict__ roots,
                                                                 const float *__restrict__ leaves, const float *__restrict__ data,
                                                                 float *sums, uint32_t *__restrict__ leaf_out, size_t rows, int cols,
                                                                 int num_trees, int K, float missing, int vec4_ok,
-                                                                const int32_t *__restrict__ stages, int S)
+                                                                const int32_t *__restrict__ stages, int S, CsrView csr)
 {
+    static_assert(!CSR || (!WRITE_LEAF && !STAGED), "CSR rows: predictions only");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float *tile = reinterpret_cast<float *>(smem);
     const int lane = threadIdx.x;
@@ -146,19 +149,25 @@ __global__ void __launch_bounds__(kTileRows) vector_tile_kernel(const VNode *__r
     const bool row_ok = row < rows;
     const int first_end = STAGED ? stages[0] : 0;
 
-    // ---- stage the row tile, transposed to feature-major (a lane past the batch stages and walks a row of zeros) ----
-    const float *src = data + (row_ok ? row : row0) * (size_t)cols;
-    if (vec4_ok) {
-        const float4 *src4 = reinterpret_cast<const float4 *>(src);
-        for (int f4 = 0; f4 < cols / 4; ++f4) {
-            float4 v = row_ok ? src4[f4] : make_float4(0.f, 0.f, 0.f, 0.f);
-            tile[(4 * f4 + 0) * kTileRows + lane] = v.x;
-            tile[(4 * f4 + 1) * kTileRows + lane] = v.y;
-            tile[(4 * f4 + 2) * kTileRows + lane] = v.z;
-            tile[(4 * f4 + 3) * kTileRows + lane] = v.w;
-        }
+    // ---- stage the row tile, transposed to feature-major (a lane past the batch stages and walks a row of zeros; from CSR: an
+    // empty row, every feature missing) ----
+    if constexpr (CSR) {
+        csr_stage_tile_wave(tile, cols, row0, rows, csr, missing, lane);
+        __syncthreads();  // the walk reads what other lanes scattered
     } else {
-        for (int f = 0; f < cols; ++f) tile[f * kTileRows + lane] = row_ok ? src[f] : 0.0f;
+        const float *src = data + (row_ok ? row : row0) * (size_t)cols;
+        if (vec4_ok) {
+            const float4 *src4 = reinterpret_cast<const float4 *>(src);
+            for (int f4 = 0; f4 < cols / 4; ++f4) {
+                float4 v = row_ok ? src4[f4] : make_float4(0.f, 0.f, 0.f, 0.f);
+                tile[(4 * f4 + 0) * kTileRows + lane] = v.x;
+                tile[(4 * f4 + 1) * kTileRows + lane] = v.y;
+                tile[(4 * f4 + 2) * kTileRows + lane] = v.z;
+                tile[(4 * f4 + 3) * kTileRows + lane] = v.w;
+            }
+        } else {
+            for (int f = 0; f < cols; ++f) tile[f * kTileRows + lane] = row_ok ? src[f] : 0.0f;
+        }
     }
 
     vector_walk<KB, WRITE_LEAF, STAGED>(nodes, roots, leaves, sums, leaf_out, row, row_ok, num_trees, K, missing, stages, S,
@@ -184,11 +193,14 @@ static long long vector_tile_bytes(const tahoe_forest *f) { return (long long)f-
 
 bool vector_tile_fits(const tahoe_forest *f) { return f->p.num_cols >= 1 && vector_tile_bytes(f) <= f->lds_limit; }
 
-// The launch of both forms.  STAGED: sums is out[rows][num_stages][K] and leaf_out is null
+// The launch of both forms.  STAGED: sums is out[rows][num_stages][K] and leaf_out is null.  csr (never with STAGED): the tile
+// kernel's CSR instantiation; strategy is ROWTILE (csr_fused_strategy), leaf_out null
 template <bool STAGED>
 static tahoe_status vector_launch_as(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data, size_t rows,
-                                     hipStream_t stream, int strategy)
+                                     hipStream_t stream, int strategy, const CsrView *csr = nullptr)
 {
+    if (csr && (STAGED || leaf_out || strategy != TAHOE_STRATEGY_ROWTILE))
+        return fail(TAHOE_ERR_UNSUPPORTED, "vector_launch: CSR rows are served by the tile kernel, predictions only");
     const tahoe_vstate *v = f->vl;
     const int32_t *stages = STAGED ? f->stages_dev : nullptr;
     const int S = STAGED ? (int)f->num_stages : 0;
@@ -199,10 +211,16 @@ static tahoe_status vector_launch_as(tahoe_forest *f, float *sums, uint32_t *lea
     auto launch = [&](auto kb, auto wl) {
         constexpr int KB = decltype(kb)::value;
         constexpr bool WL = decltype(wl)::value && !STAGED;
-        if (strategy == TAHOE_STRATEGY_ROWTILE)
+        if (csr) {
+            if constexpr (!STAGED && !WL)
+                hipLaunchKernelGGL((vector_tile_kernel<KB, false, false, true>),
+                                   dim3((unsigned)((rows + kTileRows - 1) / kTileRows), blocks_y), dim3(kTileRows),
+                                   (size_t)vector_tile_bytes(f), stream, v->nodes, v->roots, v->leaves, data, sums, leaf_out, rows,
+                                   cols, T, K, f->p.missing, vec4_ok, stages, S, *csr);
+        } else if (strategy == TAHOE_STRATEGY_ROWTILE)
             hipLaunchKernelGGL((vector_tile_kernel<KB, WL, STAGED>), dim3((unsigned)((rows + kTileRows - 1) / kTileRows), blocks_y),
                                dim3(kTileRows), (size_t)vector_tile_bytes(f), stream, v->nodes, v->roots, v->leaves, data, sums,
-                               leaf_out, rows, cols, T, K, f->p.missing, vec4_ok, stages, S);
+                               leaf_out, rows, cols, T, K, f->p.missing, vec4_ok, stages, S, CsrView{});
         else
             hipLaunchKernelGGL((vector_direct_kernel<KB, WL, STAGED>), dim3((unsigned)((rows + kBlock - 1) / kBlock), blocks_y),
                                dim3(kBlock), 0, stream, v->nodes, v->roots, v->leaves, data, sums, leaf_out, rows, cols, T, K,
@@ -217,9 +235,9 @@ static tahoe_status vector_launch_as(tahoe_forest *f, float *sums, uint32_t *lea
 }
 
 tahoe_status vector_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data, size_t rows, hipStream_t stream,
-                           int strategy)
+                           int strategy, const CsrView *csr)
 {
-    return vector_launch_as<false>(f, sums, leaf_out, data, rows, stream, strategy);
+    return vector_launch_as<false>(f, sums, leaf_out, data, rows, stream, strategy, csr);
 }
 
 tahoe_status vector_launch_staged(tahoe_forest *f, float *out, const float *data, size_t rows, hipStream_t stream, int strategy)
@@ -249,6 +267,11 @@ static tahoe_status vector_allow_lds(const tahoe_forest *f)
         ((e = allow_max_lds_leaf([](auto wl) { return &vector_tile_kernel<1, decltype(wl)::value>; }, f->lds_limit)) != hipSuccess ||
          (e = allow_max_lds_leaf([](auto wl) { return &vector_tile_kernel<kVecClasses, decltype(wl)::value>; }, f->lds_limit)) != hipSuccess))
         return hip_status(e, "hipFuncSetAttribute(vector_tile)");
+    if (f->csr && vector_tile_fits(f)) {  // the CSR-loader instantiation (tahoe_forest_predict_csr) of this handle's K
+        const void *fn = f->num_classes == 1 ? reinterpret_cast<const void *>(&vector_tile_kernel<1, false, false, true>)
+                                             : reinterpret_cast<const void *>(&vector_tile_kernel<kVecClasses, false, false, true>);
+        return hip_status(allow_max_lds(fn, f->lds_limit), "hipFuncSetAttribute(vector_tile, csr)");
+    }
     return TAHOE_OK;
 }
 
@@ -320,9 +343,10 @@ extern "C" tahoe_status tahoe_vector_forest_create_ex(tahoe_forest **out, const 
     }
     // the checks of tahoe_sparse_forest_create_ex for the flags: covers (TAHOE_CREATE_CONTRIBS; TAHOE_CREATE_INTERVENTIONAL alone
     // reads none), and at most 31 distinct features on a leaf's path
-    // (TAHOE_CREATE_STAGED opens tahoe_forest_set_stages / _predict_staged, reads no cover and builds no table)
-    const bool staged = (flags & TAHOE_CREATE_STAGED) != 0;
-    flags &= ~(unsigned)TAHOE_CREATE_STAGED;
+    // (TAHOE_CREATE_STAGED opens tahoe_forest_set_stages / _predict_staged, reads no cover and builds no table; TAHOE_CREATE_CSR
+    // opens tahoe_forest_predict_csr / _reserve_csr / _get_csr_plan in the same way)
+    const bool staged = (flags & TAHOE_CREATE_STAGED) != 0, csr_rows = (flags & TAHOE_CREATE_CSR) != 0;
+    flags &= ~(unsigned)(TAHOE_CREATE_STAGED | TAHOE_CREATE_CSR);
     constexpr unsigned kShapFlags = TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_INTERVENTIONAL | TAHOE_CREATE_VECTOR_INTERACTIONS;
     if ((flags & ~(kShapFlags | TAHOE_CREATE_VECTOR_APPROX)) != 0)
         return fail(TAHOE_ERR_INVALID_ARG,
@@ -349,6 +373,7 @@ extern "C" tahoe_status tahoe_vector_forest_create_ex(tahoe_forest **out, const 
     f->p.depth = f->depth = max_depth;
     f->bits_bytes = 4;
     f->staged = staged;
+    f->csr = csr_rows;
     f->vl = new (std::nothrow) tahoe_vstate();
     if (!f->vl) return fail(TAHOE_ERR_NO_MEMORY, "tahoe_vector_forest_create");
     tahoe_vstate *v = f->vl;
