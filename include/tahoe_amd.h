@@ -774,7 +774,9 @@ tahoe_status tahoe_synth_sparse_forest(tahoe_sparse_node *nodes, int32_t *trees,
  * preds_dev[rows] <- per-row float32 sum of leaf values in tree order 0..T-1 (the order of
  * predict_on_cpu, BaseTahoeTest.h:462-466), then AVG / bias / sigmoid / threshold as
  * forest::predict + transform_k do (Struct.h:196-209, :263-268).  data_dev is row-major
- * rows x num_cols float32 (data_d of generate_data_from_file, BaseTahoeTest.h:378-392). */
+ * rows x num_cols float32 (data_d of generate_data_from_file, BaseTahoeTest.h:378-392); a batch held as columns (one buffer per
+ * column, or one buffer with a column stride) goes to tahoe_forest_predict_columns / tahoe_forest_predict_column_ptrs below, a
+ * batch held as CSR to tahoe_forest_predict_csr. */
 tahoe_status tahoe_forest_predict(tahoe_forest *f, float *preds_dev, const float *data_dev, size_t rows,
                                   void *stream);
 
@@ -810,6 +812,40 @@ tahoe_status tahoe_forest_reserve_csr(tahoe_forest *f, size_t rows, size_t nnz);
 /* How tahoe_forest_predict_csr runs a batch of `rows` rows with nnz entries: *chunk_rows = 0 and *form = the fused kernel
  * (TAHOE_FORM_CSR_*), or *chunk_rows = rows per densified chunk and *form = the kernel form that runs on a chunk. */
 tahoe_status tahoe_forest_get_csr_plan(const tahoe_forest *f, size_t rows, size_t nnz, int *form, size_t *chunk_rows);
+
+/* tahoe_forest_predict on a column-major batch -- a cuDF / Arrow table (one device buffer per column: _column_ptrs) or a
+ * Fortran-ordered array (one buffer with a column stride: _columns) -- without a row-major copy made by the caller.
+ *   _columns:      column c of the batch is data_dev[c * col_stride + r], r in [0, rows); col_stride >= rows, in floats
+ *   _column_ptrs:  column c of the batch is cols_dev[c][r]; cols_dev is a DEVICE array of num_cols device pointers
+ * preds_dev gets, bit for bit, what tahoe_forest_predict writes for the row-major matrix with the same values -- rows values,
+ * or rows x num_classes, output transform included -- under every strategy setting and on every handle kind: dense, multi-class,
+ * sparse, categorical, oblivious, vector-leaf.  No create flag is needed.
+ *   - Values are ordinary values: the sentinel is missing, NaN goes left, -0.0 stays -0.0.  Arrow validity bitmaps are not read:
+ *     a column with nulls must be filled with the sentinel by the caller (NaN is not missing here; it goes left).  float32 only.
+ *   - A column pointer needs float alignment only; col_stride is any value >= rows.  Columns may come from separate allocations
+ *     in any order, and two entries of the table may name the same buffer.
+ *   - No kernel reads outside [0, rows) of any column, nor outside [0, num_cols) of the table.
+ *   - NULL handle; NULL preds_dev / data_dev / cols_dev with rows > 0; col_stride < rows: TAHOE_ERR_INVALID_ARG, checked before
+ *     the handle or a device is touched.  rows == 0: TAHOE_OK, nothing launched.  A handle with num_cols == 0 or no trees
+ *     behaves as tahoe_forest_predict does (no value of the batch is read).
+ *   - Asynchronous on `stream`.  Where the handle's strategy for the batch is QRING, the quantise pass reads the columns and the
+ *     walk runs as ever (its ordinary kernel form); where it is ROWTILE, or TILEBLOCK on a sparse handle, the kernel stages its
+ *     64-row LDS tile from the columns (TAHOE_COLUMNS_FORM_*).  Every other kernel form, and every oblivious or vector-leaf
+ *     handle, gets the batch transposed chunk by chunk into the buffer tahoe_forest_predict_csr's fallback also uses -- at most
+ *     TAHOE_CSR_CHUNK_MB MiB, counted in device_bytes -- and runs on each chunk in turn.  TAHOE_COLUMNS_FUSED=0 (read at
+ *     create) sends AUTO to chunks always.  tahoe_forest_get_columns_plan tells.  The buffer and the kernels' workspace grow on
+ *     demand, which allocates and synchronises; after tahoe_forest_reserve_columns(rows) a call of at most that many rows
+ *     allocates nothing, leaves device_bytes unchanged and can be captured.
+ * Leaf indices, predict_accumulate, predict_host, staged output and the explanation calls keep taking row-major rows. */
+tahoe_status tahoe_forest_predict_columns(tahoe_forest *f, float *preds_dev, const float *data_dev, size_t rows, size_t col_stride,
+                                          void *stream);
+tahoe_status tahoe_forest_predict_column_ptrs(tahoe_forest *f, float *preds_dev, const float *const *cols_dev, size_t rows,
+                                              void *stream);
+tahoe_status tahoe_forest_reserve_columns(tahoe_forest *f, size_t rows);
+/* How the two calls above run a batch of `rows` rows: *chunk_rows = 0 when no row-major copy is made, and *form = the walk's
+ * ordinary form (TAHOE_FORM_QRING_*, TAHOE_FORM_SPARSE_QRING: the quantise pass reads the columns) or a TAHOE_COLUMNS_FORM_* (a
+ * tile kernel does); else *chunk_rows = rows per transposed chunk and *form = the kernel form that runs on a chunk. */
+tahoe_status tahoe_forest_get_columns_plan(const tahoe_forest *f, size_t rows, int *form, size_t *chunk_rows);
 
 /* Raw float32 per-row sums only (no output transform) -- the quantity tree shards exchange. */
 tahoe_status tahoe_forest_predict_raw(tahoe_forest *f, float *sums_dev, const float *data_dev, size_t rows,
@@ -985,6 +1021,13 @@ enum {
 enum {
     TAHOE_OBLIVIOUS_FORM_CSR_TILE = 30,   /* tahoe_forest_predict_csr only: oblivious_tile_kernel staging its tile from the CSR arrays */
     TAHOE_VECTOR_FORM_CSR_TILE = 31       /* ... vector_tile_kernel */
+};
+/* The tile kernels fed from column-major batches (tahoe_forest_get_columns_plan only).  32 stays unassigned for the same reason:
+ * the first value past TAHOE_VECTOR_FORM_CSR_TILE has no name (tahoe_kernel_form_name(32) == "?"). */
+enum {
+    TAHOE_COLUMNS_FORM_ROWTILE = 33,         /* rowtile_kernel staging its tile from the columns */
+    TAHOE_COLUMNS_FORM_SPARSE_ROWTILE = 34,  /* ... sparse_kernel with the tile */
+    TAHOE_COLUMNS_FORM_SPARSE_TOP = 35       /* ... sparse_top_kernel */
 };
 int tahoe_forest_get_kernel_form(const tahoe_forest *f, size_t rows);
 const char *tahoe_kernel_form_name(int form);

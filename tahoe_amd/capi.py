@@ -167,6 +167,10 @@ _PROTOS = {
     "tahoe_forest_predict_csr": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp]),
     "tahoe_forest_reserve_csr": (_i, [_vp, _sz, _sz]),
     "tahoe_forest_get_csr_plan": (_i, [_vp, _sz, _sz, C.POINTER(_i), C.POINTER(_sz)]),
+    "tahoe_forest_predict_columns": (_i, [_vp, _vp, _vp, _sz, _sz, _vp]),
+    "tahoe_forest_predict_column_ptrs": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "tahoe_forest_reserve_columns": (_i, [_vp, _sz]),
+    "tahoe_forest_get_columns_plan": (_i, [_vp, _sz, C.POINTER(_i), C.POINTER(_sz)]),
     "tahoe_forest_predict_raw": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "tahoe_forest_predict_accumulate": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "tahoe_forest_predict_leaf_idx": (_i, [_vp, _vp, _vp, _vp, _sz, _vp]),
@@ -510,6 +514,73 @@ class Forest:
         """(kernel form name, rows per densified chunk; 0 = the fused CSR kernel) of a predict_csr of that size."""
         form, chunk = _i(), _sz()
         _check(lib.tahoe_forest_get_csr_plan(self._h, rows, nnz, C.byref(form), C.byref(chunk)), "tahoe_forest_get_csr_plan")
+        return lib.tahoe_kernel_form_name(form.value).decode(), chunk.value
+
+    def predict_columns(self, x, out=None, stream=None):
+        """predict on a column-major batch, without a row-major copy.  x is a 2-D float32 CUDA tensor [rows, num_cols] with
+        x.stride(0) == 1 and x.stride(1) >= rows (a Fortran-ordered array, `rowmajor.t()` of a [num_cols, rows] tensor:
+        tahoe_forest_predict_columns), or a sequence of num_cols 1-D contiguous float32 CUDA tensors of one length (the columns
+        of a cuDF / Arrow table, in any allocation: tahoe_forest_predict_column_ptrs).  Bit for bit what predict returns for
+        the row-major matrix of the same values.  Anything else is a ValueError raised before the library is called."""
+        import torch
+
+        if isinstance(x, torch.Tensor):
+            if x.dim() != 2 or x.shape[1] != self.num_cols:
+                raise ValueError(f"x must be [rows, {self.num_cols}], got {tuple(x.shape)}")
+            if x.dtype != torch.float32:
+                raise ValueError(f"x must be float32, got {x.dtype}")
+            rows = x.shape[0]
+            if rows > 0 and self.num_cols > 0 and not ((rows == 1 or x.stride(0) == 1) and (self.num_cols == 1 or x.stride(1) >= rows)):
+                raise ValueError(f"x must be column-major (stride(0) == 1, stride(1) >= rows), got strides {tuple(x.stride())}; "
+                                 "a row-major tensor goes to predict")
+            if not x.is_cuda:
+                raise ValueError("x must be a CUDA tensor")
+            cols, device = None, x.device
+            stride = max(x.stride(1), rows) if self.num_cols > 1 else rows
+        else:
+            cols = list(x)
+            if len(cols) != self.num_cols:
+                raise ValueError(f"{len(cols)} columns given, the forest has {self.num_cols}")
+            for c in cols:
+                if not isinstance(c, torch.Tensor) or c.dim() != 1 or c.dtype != torch.float32:
+                    raise ValueError("every column must be a 1-D float32 tensor")
+            if len({c.numel() for c in cols}) > 1:
+                raise ValueError(f"columns of unequal lengths: {sorted({c.numel() for c in cols})}")
+            if any(not c.is_cuda or not c.is_contiguous() for c in cols):
+                raise ValueError("every column must be a contiguous CUDA tensor")
+            rows = cols[0].numel() if cols else 0
+            device = cols[0].device if cols else torch.device("cuda", torch.cuda.current_device())
+        if out is None:
+            out = torch.empty(self._out_shape(rows), dtype=torch.float32, device=device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == self._out_shape(rows)
+        if cols is None:
+            _check(lib.tahoe_forest_predict_columns(self._h, _ptr(out), _ptr(x), rows, stride, _stream(stream)),
+                   "tahoe_forest_predict_columns")
+            return out
+        # The int64 pointer table is built on the host and copied on the call's stream, so the kernels read it in stream order;
+        # table and columns stay referenced until the call has been enqueued (the caching allocator keeps the table's memory
+        # for that stream's work afterwards).  The copy reads host memory of this call: capture the strided form instead.
+        if stream is None:
+            s = torch.cuda.current_stream(device)
+        else:
+            s = torch.cuda.ExternalStream(stream, device=device) if isinstance(stream, int) else stream
+        with torch.cuda.stream(s):
+            table = torch.tensor([c.data_ptr() for c in cols], dtype=torch.int64).to(device)
+        keep = (cols, table)
+        _check(lib.tahoe_forest_predict_column_ptrs(self._h, _ptr(out), _ptr(table) if cols else None, rows, _stream(stream)),
+               "tahoe_forest_predict_column_ptrs")
+        del keep
+        return out
+
+    def reserve_columns(self, rows: int) -> None:
+        """Sizes the workspace of predict_columns for batches of up to `rows` rows (tahoe_forest_reserve_columns)."""
+        _check(lib.tahoe_forest_reserve_columns(self._h, rows), "tahoe_forest_reserve_columns")
+
+    def columns_plan(self, rows: int):
+        """(kernel form name, rows per transposed chunk; 0 = the kernel reads the columns itself) of a predict_columns of that
+        size."""
+        form, chunk = _i(), _sz()
+        _check(lib.tahoe_forest_get_columns_plan(self._h, rows, C.byref(form), C.byref(chunk)), "tahoe_forest_get_columns_plan")
         return lib.tahoe_kernel_form_name(form.value).decode(), chunk.value
 
     def predict_raw(self, data, sums=None, stream=None):

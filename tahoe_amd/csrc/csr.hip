@@ -49,7 +49,7 @@ __global__ void __launch_bounds__(kBlock) csr_densify_kernel(float *__restrict__
 
 // Rows per densify chunk: what TAHOE_CSR_CHUNK_MB holds, in whole tiles of every kernel form (384 = lcm of the 64-, 128-, 192-
 // and 384-row tiles) where that many fit, else in 64-row tiles; at least one of those
-static size_t csr_chunk_cap(const tahoe_forest *f)
+size_t csr_chunk_cap(const tahoe_forest *f)
 {
     const size_t row_bytes = std::max<size_t>((size_t)f->p.num_cols, 1) * sizeof(float);
     const size_t fit = ((size_t)std::max(f->knobs.csr_chunk_mb, 1) << 20) / row_bytes;
@@ -57,7 +57,7 @@ static size_t csr_chunk_cap(const tahoe_forest *f)
 }
 
 // The chunk buffer holds min(rows, cap) rows after this; grows only
-static tahoe_status csr_reserve_chunk(tahoe_forest *f, size_t rows)
+tahoe_status csr_reserve_chunk(tahoe_forest *f, size_t rows, const char *fn)
 {
     const size_t want = std::min(rows, csr_chunk_cap(f));
     if (want <= f->csr_chunk_rows) return TAHOE_OK;
@@ -72,7 +72,7 @@ static tahoe_status csr_reserve_chunk(tahoe_forest *f, size_t rows)
     }
     if (hipMalloc(reinterpret_cast<void **>(&f->csr_chunk), want * row_bytes) != hipSuccess) {
         f->csr_chunk = nullptr;
-        return fail(TAHOE_ERR_NO_MEMORY, "tahoe_forest_predict_csr: no room for a %zu-row chunk of %d columns", want, f->p.num_cols);
+        return fail(TAHOE_ERR_NO_MEMORY, "%s: no room for a %zu-row chunk of %d columns", fn, want, f->p.num_cols);
     }
     f->csr_chunk_rows = want;
     f->device_bytes += want * row_bytes;
@@ -92,14 +92,6 @@ static int csr_fused_form(const tahoe_forest *f, int strategy)
     if (!f->sp) return TAHOE_FORM_CSR_ROWTILE;
     return strategy == TAHOE_STRATEGY_TILEBLOCK ? TAHOE_FORM_CSR_SPARSE_TOP : TAHOE_FORM_CSR_SPARSE_ROWTILE;
 }
-
-// One event triple for the whole call (densify kernels included) instead of one per chunk: the inner launches are not timed
-struct ProfilingPause {
-    tahoe_forest *f;
-    bool was;
-    explicit ProfilingPause(tahoe_forest *f_) : f(f_), was(f_->profiling) { f->profiling = false; }
-    ~ProfilingPause() { f->profiling = was; }
-};
 
 }  // namespace tahoe
 
@@ -131,7 +123,7 @@ tahoe_status tahoe_forest_predict_csr(tahoe_forest *f, float *preds_dev, const i
         if (fused >= 0) {
             if (const tahoe_status s = predict_rows(f, preds_dev, nullptr, rows, stream, &csr, fused)) return s;
         } else {
-            if (const tahoe_status s = csr_reserve_chunk(f, rows)) return s;  // no-op unless this batch needs a larger chunk
+            if (const tahoe_status s = csr_reserve_chunk(f, rows, "tahoe_forest_predict_csr")) return s;  // no-op unless this batch needs a larger chunk
             const size_t chunk = f->csr_chunk_rows, out_cols = (size_t)f->num_classes;
             for (size_t r0 = 0; r0 < rows; r0 += chunk) {
                 const size_t n = std::min(chunk, rows - r0);
@@ -159,7 +151,7 @@ tahoe_status tahoe_forest_reserve_csr(tahoe_forest *f, size_t rows, size_t nnz)
     // chunk buffer, and what the handle's kernels need for a batch of one chunk.  The fused kernels need no workspace.
     (void)nnz;
     if (rows == 0) return TAHOE_OK;
-    if (const tahoe_status s = csr_reserve_chunk(f, rows)) return s;
+    if (const tahoe_status s = csr_reserve_chunk(f, rows, "tahoe_forest_reserve_csr")) return s;
     return tahoe_forest_reserve(f, f->csr_chunk_rows);
 }
 

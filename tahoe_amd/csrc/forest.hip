@@ -116,7 +116,8 @@ __global__ void __launch_bounds__(kBlock) direct_kernel(const InnerNode *__restr
 // MC: the owner lane stores its sum at the end of every class (direct_kernel).
 // CSR: the tile is staged from csr by csr_stage_tile (forest_internal.h) and `data` is not read.
 // STAGED: direct_kernel's stage cursor, kept by the owner lanes; a stage can end at any of a round's four trees.
-template <bool WRITE_LEAF, bool MC = false, bool CSR = false, bool STAGED = false>
+// COLS: the tile is staged from column-major buffers by cols_stage_tile (forest_internal.h) and `data` is not read.
+template <bool WRITE_LEAF, bool MC = false, bool CSR = false, bool STAGED = false, bool COLS = false>
 __global__ void __launch_bounds__(kBlock) rowtile_kernel(const InnerNode *__restrict__ inner,
                                                          const float *__restrict__ leaf_val,
                                                          const uint32_t *__restrict__ leaf_orig,
@@ -124,9 +125,10 @@ __global__ void __launch_bounds__(kBlock) rowtile_kernel(const InnerNode *__rest
                                                          uint32_t *__restrict__ leaf_out, const float *sums_in, size_t rows, int cols,
                                                          int num_trees, int depth, int lds_levels, float missing,
                                                          int vec4_ok, int num_classes, CsrView csr,
-                                                         const int32_t *__restrict__ stages, int S)
+                                                         const int32_t *__restrict__ stages, int S, ColsView cv)
 {
     static_assert(!STAGED || (!WRITE_LEAF && !CSR), "staged output: predictions from dense rows");
+    static_assert(!COLS || (!CSR && !WRITE_LEAF && !STAGED), "column-major rows: predictions only");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -144,6 +146,8 @@ __global__ void __launch_bounds__(kBlock) rowtile_kernel(const InnerNode *__rest
     // ---- stage the row tile, transposed to feature-major ----
     if constexpr (CSR) {
         csr_stage_tile<kBlock>(tile, reinterpret_cast<int64_t *>(vals), cols, row0, rows, csr, missing, threadIdx.x);
+    } else if constexpr (COLS) {
+        cols_stage_tile<kWaves>(tile, cols, row0, rows, cv, wave, lane);
     } else {
         const float *src = data + (row_ok ? row : row0) * (size_t)cols;
         if (vec4_ok) {
@@ -943,13 +947,19 @@ static void launch_tilering(tahoe_forest *f, float *sums, uint32_t *leaf_out, co
 // sums_in (optional, may be `sums` itself): running float32 sums of the trees BEFORE this forest -- every kernel then
 // continues that sum in tree order instead of starting from 0.0f (tahoe_forest_predict_accumulate).
 // csr (optional): the rows come from there through the fused loader of csr_strategy's tile kernel; `data` is not read.
+// cols (optional, never with csr, predictions only): the rows come from column-major buffers and `data` is not read;
+// csr_strategy is then what columns_fused_strategy returned -- QRING (the quantise pass reads the columns), ROWTILE, or
+// TILEBLOCK on a sparse handle (the tile loader does).
 static tahoe_status launch_traversal(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data,
                                      size_t rows, hipStream_t stream, const float *sums_in = nullptr, const CsrView *csr = nullptr,
-                                     int csr_strategy = 0)
+                                     int csr_strategy = 0, const ColsView *cols = nullptr)
 {
     if (rows == 0) return TAHOE_OK;
     DeviceGuard on_device(f->device);
-    const int strategy = csr ? csr_strategy : resolve_strategy(f, rows);
+    const int strategy = (csr || cols) ? csr_strategy : resolve_strategy(f, rows);
+    if (cols && (csr || leaf_out || sums_in || f->ob || f->vl ||
+                 !(strategy == TAHOE_STRATEGY_QRING || strategy == TAHOE_STRATEGY_ROWTILE || (strategy == TAHOE_STRATEGY_TILEBLOCK && f->sp))))
+        return fail(TAHOE_ERR_UNSUPPORTED, "launch_traversal: no kernel of strategy %d reads column-major rows", strategy);
     if ((rows + 63) / 64 > 0x7fffffffu) return fail(TAHOE_ERR_INVALID_ARG, "too many rows for one launch: %zu", rows);
     if (const tahoe_status s = strategy_available(f, strategy)) return s;  // (set_strategy has refused it already)
     const bool timed = f->profiling && f->prof_count < f->ev_start.size();
@@ -975,10 +985,10 @@ static tahoe_status launch_traversal(tahoe_forest *f, float *sums, uint32_t *lea
         const tahoe_status vs = vector_launch(f, sums, leaf_out, data, rows, stream, strategy, csr);
         if (vs != TAHOE_OK) return vs;
     } else if (f->sp) {
-        const tahoe_status ss = sparse_launch(f, sums, leaf_out, data, rows, stream, strategy, sums_in, csr);
+        const tahoe_status ss = sparse_launch(f, sums, leaf_out, data, rows, stream, strategy, sums_in, csr, cols);
         if (ss != TAHOE_OK) return ss;
     } else if (strategy == TAHOE_STRATEGY_QRING) {
-        const tahoe_status qs = qring_launch(f, sums, leaf_out, data, rows, stream, timed ? f->ev_mid[f->prof_count] : nullptr, sums_in);
+        const tahoe_status qs = qring_launch(f, sums, leaf_out, data, rows, stream, timed ? f->ev_mid[f->prof_count] : nullptr, sums_in, cols);
         mid_recorded = timed;
         if (qs != TAHOE_OK) return qs;
     } else if (strategy == TAHOE_STRATEGY_TILERING && tilering_rows(f) == 0 && widef_rows(f) > 0) {
@@ -1004,11 +1014,15 @@ static tahoe_status launch_traversal(tahoe_forest *f, float *sums, uint32_t *lea
             if (csr)  // (predictions only: no leaf-index form)
                 hipLaunchKernelGGL((rowtile_kernel<false, decltype(mc)::value, true>), dim3((unsigned)grid), dim3(kBlock), lds, stream,
                                    f->inner, f->leaf_val, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
-                                   f->p.num_trees, f->depth, f->lds_levels, f->p.missing, vec4_ok, nc, *csr, nullptr, 0);
+                                   f->p.num_trees, f->depth, f->lds_levels, f->p.missing, vec4_ok, nc, *csr, nullptr, 0, ColsView{});
+            else if (cols)
+                hipLaunchKernelGGL((rowtile_kernel<false, decltype(mc)::value, false, false, true>), dim3((unsigned)grid), dim3(kBlock), lds,
+                                   stream, f->inner, f->leaf_val, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
+                                   f->p.num_trees, f->depth, f->lds_levels, f->p.missing, 0, nc, CsrView{}, nullptr, 0, *cols);
             else
                 hipLaunchKernelGGL((rowtile_kernel<decltype(wl)::value, decltype(mc)::value>), dim3((unsigned)grid), dim3(kBlock), lds,
                                    stream, f->inner, f->leaf_val, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
-                                   f->p.num_trees, f->depth, f->lds_levels, f->p.missing, vec4_ok, nc, CsrView{}, nullptr, 0);
+                                   f->p.num_trees, f->depth, f->lds_levels, f->p.missing, vec4_ok, nc, CsrView{}, nullptr, 0, ColsView{});
         });
         TAHOE_HIP_TRY(hipGetLastError());
     } else if (strategy == TAHOE_STRATEGY_DIRECT) {
@@ -1116,6 +1130,7 @@ static tahoe_knobs read_knobs()
     k.approx_form = num("TAHOE_APPROX_FORM", k.approx_form);
     k.csr_chunk_mb = num("TAHOE_CSR_CHUNK_MB", k.csr_chunk_mb);
     k.csr_fused = num("TAHOE_CSR_FUSED", k.csr_fused);
+    k.columns_fused = num("TAHOE_COLUMNS_FUSED", k.columns_fused);
     k.oblivious_shap_inplace = num("TAHOE_OBLIVIOUS_SHAP_INPLACE", 0) != 0;
     k.vector_shap_kb = num("TAHOE_VECTOR_SHAP_KB", k.vector_shap_kb);
     k.vector_shap_grid = num("TAHOE_VECTOR_SHAP_GRID", k.vector_shap_grid);
@@ -1156,7 +1171,9 @@ static tahoe_status allow_float32_lds(const tahoe_forest *f)
         ((e = allow_max_lds_leaf([](auto wl) { return &rowtile_kernel<decltype(wl)::value>; }, lim)) != hipSuccess ||
          (f->num_classes > 1 && (e = allow_max_lds_leaf([](auto wl) { return &rowtile_kernel<decltype(wl)::value, true>; }, lim)) != hipSuccess) ||
          (e = allow_max_lds(reinterpret_cast<const void *>(&rowtile_kernel<false, false, true>), lim)) != hipSuccess ||
-         (e = allow_max_lds(reinterpret_cast<const void *>(&rowtile_kernel<false, true, true>), lim)) != hipSuccess))
+         (e = allow_max_lds(reinterpret_cast<const void *>(&rowtile_kernel<false, true, true>), lim)) != hipSuccess ||
+         (e = allow_max_lds(reinterpret_cast<const void *>(&rowtile_kernel<false, false, false, false, true>), lim)) != hipSuccess ||
+         (e = allow_max_lds(reinterpret_cast<const void *>(&rowtile_kernel<false, true, false, false, true>), lim)) != hipSuccess))
         return hip_status(e, "hipFuncSetAttribute(rowtile)");
     if (!f->has_blocks) return TAHOE_OK;
     if ((tileblock_lds_bytes(f, 128) <= lim &&
@@ -1173,10 +1190,10 @@ static tahoe_status allow_float32_lds(const tahoe_forest *f)
 }
 
 tahoe_status predict_rows(tahoe_forest *f, float *preds, const float *data, size_t rows, hipStream_t stream, const CsrView *csr,
-                          int csr_strategy)
+                          int csr_strategy, const ColsView *cols)
 {
     DeviceGuard on_device(f->device);
-    tahoe_status s = launch_traversal(f, preds, nullptr, data, rows, stream, nullptr, csr, csr_strategy);
+    tahoe_status s = launch_traversal(f, preds, nullptr, data, rows, stream, nullptr, csr, csr_strategy, cols);
     if (s != TAHOE_OK) return s;
     if (f->num_classes > 1) return launch_transform_mc(f, preds, rows, stream);
     return launch_transform(preds, rows, f->p.output, f->p.num_trees, f->p.threshold, f->p.global_bias, stream);
@@ -1217,7 +1234,7 @@ static tahoe_status launch_staged_dense(tahoe_forest *f, float *out, const float
         with_mc([&](auto mc) {
             hipLaunchKernelGGL((rowtile_kernel<false, decltype(mc)::value, false, true>), dim3((unsigned)grid), dim3(kBlock), lds, stream,
                                f->inner, f->leaf_val, f->leaf_orig, data, out, nullptr, nullptr, rows, f->p.num_cols, f->p.num_trees,
-                               f->depth, f->lds_levels, f->p.missing, vec4_ok, nc, CsrView{}, f->stages_dev, S);
+                               f->depth, f->lds_levels, f->p.missing, vec4_ok, nc, CsrView{}, f->stages_dev, S, ColsView{});
         });
     } else {
         const size_t grid = (rows + kBlock - 1) / kBlock;
@@ -1265,6 +1282,21 @@ int csr_fused_strategy(const tahoe_forest *f, size_t rows, size_t nnz)
     if (!f->sp && tile && (long long)f->p.num_trees * f->depth <= 8LL * f->p.num_cols &&
         4.0 * (double)nnz <= (double)rows * (double)f->p.num_cols)
         return TAHOE_STRATEGY_ROWTILE;
+    return -1;
+}
+
+// Which kernel reads a column-major batch in place.  The strategy is the one the same handle runs on
+// row-major rows -- a forced one, or AUTO's for this many rows -- whenever that strategy has a column loader: QRING (every form
+// walks codes; only the quantise pass reads floats), ROWTILE where the 64-row tile fits, TILEBLOCK on a sparse handle.  There
+// is no rule that swaps AUTO's form for another.  Everything else, and every oblivious or vector-leaf handle, gets chunks.
+int columns_fused_strategy(const tahoe_forest *f, size_t rows)
+{
+    if (f->p.num_trees == 0 || f->p.num_cols == 0 || f->ob || f->vl) return -1;
+    if (f->strategy == TAHOE_STRATEGY_AUTO && f->knobs.columns_fused == 0) return -1;
+    const int s = resolve_strategy(f, rows);  // (a forced strategy resolves to itself)
+    if (s == TAHOE_STRATEGY_QRING) return (f->sp ? sparse_q_available(f) : qring_walkers(f) > 0) ? s : -1;
+    if (s == TAHOE_STRATEGY_ROWTILE) return (f->sp ? sparse_tile_fits(f) : rowtile_fits(f)) ? s : -1;
+    if (s == TAHOE_STRATEGY_TILEBLOCK) return f->sp && sparse_top_waves(f) > 0 ? s : -1;
     return -1;
 }
 
@@ -1741,7 +1773,8 @@ const char *tahoe_kernel_form_name(int form)
                                         "sparse_rowtile", "sparse_top", "sparse_qring", "qring_region8", "qring_region6",
                                         "csr_rowtile", "csr_sparse_rowtile", "csr_sparse_top", "?" /* 23: unassigned */, "oblivious_direct",
                                         "oblivious_tile", "?" /* 26: unassigned */, "vector_direct", "vector_tile", "?" /* 29: unassigned */,
-                                        "oblivious_csr_tile", "vector_csr_tile"};
+                                        "oblivious_csr_tile", "vector_csr_tile", "?" /* 32: unassigned */, "columns_rowtile",
+                                        "columns_sparse_rowtile", "columns_sparse_top"};
     return form >= 0 && form < (int)(sizeof(names) / sizeof(names[0])) ? names[form] : "?";
 }
 

@@ -83,6 +83,7 @@ struct tahoe_knobs {
     int approx_form = 0;          // TAHOE_APPROX_FORM: 1 = the LDS slab wherever one wave's slab fits, 2 = in place
     int csr_chunk_mb = 64;        // TAHOE_CSR_CHUNK_MB: cap of tahoe_forest_predict_csr's densify chunk (at least one 64-row tile)
     int csr_fused = -1;           // TAHOE_CSR_FUSED: under AUTO, 0 = never the fused CSR tile kernels, 1 = wherever one exists, -1 = the rule
+    int columns_fused = -1;       // TAHOE_COLUMNS_FUSED: under AUTO, 0 = column batches always go through row-major chunks, else the rule
     bool oblivious_shap_inplace = false;  // TAHOE_OBLIVIOUS_SHAP_INPLACE = 1: an oblivious handle's explanations accumulate in phi_dev
     int vector_shap_kb = 0;       // TAHOE_VECTOR_SHAP_KB = 1 / 2 / 4 / 8: force the class block of a vector-leaf handle's TreeSHAP kernels
     int pd_chunk_rows = 0;        // TAHOE_PD_CHUNK_ROWS >= 1: grid points per chunk of tahoe_forest_predict_partial_dependence (rounded up to 64s)
@@ -109,7 +110,8 @@ struct tahoe_forest {
     uint4 *blocks = nullptr;       // [T][2^(De-2)][2]
     int *error_flag = nullptr;     // [0] set by TILERING if a bounded spin ever times out; [1] by a CSR loader that skipped an
                                    // entry whose column id is outside [0, num_cols) (tahoe_forest_check reports and clears it)
-    float *csr_chunk = nullptr;    // tahoe_forest_predict_csr's fallback: csr_chunk_rows x num_cols densified rows (csr.hip)
+    float *csr_chunk = nullptr;    // the row-major chunk of tahoe_forest_predict_csr's fallback (csr.hip) and of the column entry
+                                   // points' (columns.hip): csr_chunk_rows x num_cols floats, one buffer for both
     size_t csr_chunk_rows = 0;
     tahoe_qstate *q = nullptr;     // QRING: rank-quantised forest + row workspace (qring.hip)
     tahoe_sstate *sp = nullptr;    // non-null: this handle is a sparse forest (sparse.hip); the dense views are unused
@@ -337,6 +339,45 @@ __device__ __forceinline__ void csr_stage_tile_wave(float *tile, int cols, size_
     if (bad) atomicOr(csr.bad_column, 1);
 }
 
+// ---- column-major batches (tahoe_forest_predict_columns / _column_ptrs) ----
+// Column c of the batch is ptrs[c][r] (a device table of num_cols device pointers) or, with ptrs null, base[c * stride + r], for
+// r in [0, rows).  Passed to kernels by value; which of the two holds is uniform over a launch and every loader below asks for a
+// wave-uniform c, so the table read is a scalar load.
+struct ColsView {
+    const float *const *ptrs = nullptr;
+    const float *base = nullptr;
+    size_t stride = 0;  // floats, >= rows
+    __host__ __device__ __forceinline__ const float *col(int c) const { return ptrs ? ptrs[c] : base + (size_t)c * stride; }
+};
+
+// The fused column loader of the 64-row float32 tile kernels (NWAVES waves): wave w copies columns w, w + NWAVES, ...; lane r
+// loads col(c)[row0 + r] -- 64 consecutive floats, 256 bytes, per wave-load -- or takes 0.0f past the batch, as the row-major
+// loader does, and stores tile[c * 64 + r]: one ds_write_b32 per lane at a lane-linear address, no bank conflict.  Eight columns
+// are in flight per wave before the first store: with one, a wave waited out a table read and a global load per column, and the
+// loader lost to transposing the batch first (K5's forest on 480 features).  No scratch, no barrier of its
+// own: the caller's barrier after the staging completes the tile.  Nothing outside [0, rows) of a column or [0, cols) of the
+// table is read.
+template <int NWAVES>
+__device__ __forceinline__ void cols_stage_tile(float *tile, int cols, size_t row0, size_t rows, const ColsView &cv, int wave, int lane)
+{
+    constexpr int U = 8;
+    const bool row_ok = row0 + lane < rows;
+    for (int c0 = __builtin_amdgcn_readfirstlane(wave); c0 < cols; c0 += U * NWAVES) {  // (c in an SGPR: col(c) is a scalar load)
+        float v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int c = c0 + u * NWAVES;
+            v[u] = 0.0f;
+            if (c < cols && row_ok) v[u] = cv.col(c)[row0 + lane];
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int c = c0 + u * NWAVES;
+            if (c < cols) tile[c * kTileRows + lane] = v[u];
+        }
+    }
+}
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is per function and process-wide, not per handle: always raise it to
 // the device limit (less the kernel's static LDS), so that handles of different shapes can coexist in one process.
 inline hipError_t allow_max_lds(const void *fn, int limit)
@@ -443,12 +484,28 @@ inline tahoe_status finish_create(ForestPtr &f, unsigned flags, tahoe_forest **o
 tahoe_status strategy_available(const tahoe_forest *f, int strategy);
 // tahoe_forest_predict on device rows (forest.hip).  With csr the rows come from there through the fused loader of the tile
 // kernel of csr_strategy (a value csr_fused_strategy returned) and `data` is not read.
+// With cols the rows come from column-major buffers instead (`data` is not read) through the kernel of csr_strategy (a value
+// columns_fused_strategy returned): QRING's quantise pass or a tile kernel's column loader.
 tahoe_status predict_rows(tahoe_forest *f, float *preds, const float *data, size_t rows, hipStream_t stream,
-                          const CsrView *csr = nullptr, int csr_strategy = 0);
+                          const CsrView *csr = nullptr, int csr_strategy = 0, const ColsView *cols = nullptr);
 // The strategy whose fused CSR kernel serves a batch of `rows` rows with nnz stored entries (ROWTILE, or TILEBLOCK on a sparse
 // handle; ROWTILE on an oblivious or vector-leaf handle of TAHOE_CREATE_CSR), or -1: the batch is densified in chunks and takes the handle's own path (csr.hip)
 int csr_fused_strategy(const tahoe_forest *f, size_t rows, size_t nnz);
 void csr_destroy(tahoe_forest *f);
+// The row-major chunk buffer both fallbacks stage into (csr.hip): rows per chunk under TAHOE_CSR_CHUNK_MB, and the buffer grown to
+// hold min(rows, cap) rows (`fn` names the caller in a refusal)
+size_t csr_chunk_cap(const tahoe_forest *f);
+tahoe_status csr_reserve_chunk(tahoe_forest *f, size_t rows, const char *fn);
+// One event triple for a whole chunked call (staging kernels included) instead of one per chunk: the inner launches are not timed
+struct ProfilingPause {
+    tahoe_forest *f;
+    bool was;
+    explicit ProfilingPause(tahoe_forest *f_) : f(f_), was(f_->profiling) { f->profiling = false; }
+    ~ProfilingPause() { f->profiling = was; }
+};
+// The strategy whose kernel reads a batch of `rows` rows straight from columns (QRING: the quantise pass; ROWTILE, or TILEBLOCK
+// on a sparse handle: the tile loader), or -1: the batch is transposed in chunks and takes the handle's own path (columns.hip)
+int columns_fused_strategy(const tahoe_forest *f, size_t rows);
 
 // The branch rule of infer_one_tree, BaseTahoeTest.h:450-453: 1 = right child.
 __device__ __forceinline__ uint32_t go_right(float x, float thr, bool def_left, float missing)
@@ -534,7 +591,7 @@ int qring_walkers(const tahoe_forest *f);  // walker waves the kernel would use;
 long long qring_lds_bytes(const tahoe_forest *f);
 // mid_event (optional) is recorded between the quantise kernel and the walk kernel
 tahoe_status qring_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data, size_t rows,
-                          hipStream_t stream, hipEvent_t mid_event, const float *sums_in = nullptr);
+                          hipStream_t stream, hipEvent_t mid_event, const float *sums_in = nullptr, const ColsView *cols = nullptr);
 tahoe_status qring_reserve(tahoe_forest *f, size_t rows);
 int qwide_rows(const tahoe_forest *f);   // rows per tile of the wide-row form; 0 = not used
 int qwide_chains(const tahoe_forest *f); // ... and the trees a lane walks at once (1 or 3)
@@ -548,7 +605,8 @@ int qring_form(const tahoe_forest *f, size_t rows);  // TAHOE_FORM_* of the laun
 // sparse forests (sparse.hip)
 bool sparse_tile_fits(const tahoe_forest *f);
 tahoe_status sparse_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data, size_t rows,
-                           hipStream_t stream, int strategy, const float *sums_in = nullptr, const CsrView *csr = nullptr);
+                           hipStream_t stream, int strategy, const float *sums_in = nullptr, const CsrView *csr = nullptr,
+                           const ColsView *cols = nullptr);
 int sparse_top_waves(const tahoe_forest *f);
 // tahoe_forest_predict_staged on a sparse handle: the walk of `strategy` (DIRECT, ROWTILE or TILEBLOCK) with the stage stores to
 // out[rows][num_stages][num_classes]; sparse_allow_staged_lds lets those kernels take the device's LDS (set_stages calls it)

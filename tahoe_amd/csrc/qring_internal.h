@@ -287,9 +287,10 @@ tahoe_status quantize_build_tables(tahoe_forest *f, const std::vector<std::vecto
 void quantize_free_tables(tahoe_qgroup &g);
 hipError_t quantize_allow_lds(const tahoe_forest *f);  // kernels that need more than 64 KiB of dynamic LDS
 // Launches the quantise pass of group g for `rows` rows of `data` into f->q->xq (tiles of 2^trs rows) and the
-// per-chunk "missing seen" flags; *cshift_out = log2 of the rows per flag.
+// per-chunk "missing seen" flags; *cshift_out = log2 of the rows per flag.  cols (optional): the rows are read from column-major
+// buffers and `data` is not; the kernel form then depends on the group's tables alone (no float2 / float4 row load exists).
 tahoe_status quantize_launch(tahoe_forest *f, const tahoe_qgroup &g, const float *data, size_t rows, int trs, int perm,
-                             hipStream_t stream, int *cshift_out);
+                             hipStream_t stream, int *cshift_out, const ColsView *cols = nullptr);
 
 }  // namespace tahoe
 

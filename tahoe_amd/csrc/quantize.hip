@@ -29,8 +29,36 @@ __device__ __forceinline__ float qv_get(float v, int) { return v; }
 __device__ __forceinline__ float qv_get(float2 v, int j) { return j == 0 ? v.x : v.y; }
 __device__ __forceinline__ float qv_get(float4 v, int j) { return j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w; }
 
+// COLS (tahoe_forest_predict_columns): every kernel below is also instantiated on a column-major batch.
+// Its first argument is then the ColsView in place of the row pointer -- the row-major instantiations keep their argument list
+// and with it their instruction streams (an argument appended behind the others moves the hidden arguments that blockDim and
+// gridDim are read from) -- and the one or two places that form data + r * cols + f0 become F loads of col(f0 + j)[r].  Row-to-
+// thread mapping, search, missing test, code store and the per-chunk flag are the same code, so the codes are the same codes.
+// A lane takes one row per load: lanes that are adjacent in rows read adjacent floats of one column, so every 64-byte line a
+// wave touches is used whole -- what the row-major reads (F * 4 bytes of each line) never managed.
+template <bool COLS>
+struct QSrc { using T = const float *__restrict__; };
+template <>
+struct QSrc<true> { using T = ColsView; };
+// row r of F adjacent columns (cp[j] = col(f0 + j)) as the vector the row-major load returns
 template <int F>
-__global__ void __launch_bounds__(kQuantThreads) quantize_kernel(const float *__restrict__ data, const float *__restrict__ tables,
+__device__ __forceinline__ typename QVec<F>::T qv_cols(const float *const *cp, size_t r)
+{
+    if constexpr (F == 1) return cp[0][r];
+    else if constexpr (F == 2) return make_float2(cp[0][r], cp[1][r]);
+    else return make_float4(cp[0][r], cp[1][r], cp[2][r], cp[3][r]);
+}
+// fn(cols_c, src) with std::true_type and the view when the batch is column-major, else std::false_type and the row pointer:
+// src is the kernel's first argument
+template <class Fn>
+static void with_cols(const float *data, const ColsView *cols, Fn &&fn)
+{
+    if (cols) fn(std::true_type{}, *cols);
+    else fn(std::false_type{}, data);
+}
+
+template <int F, bool COLS = false>
+__global__ void __launch_bounds__(kQuantThreads) quantize_kernel(typename QSrc<COLS>::T data, const float *__restrict__ tables,
                                                                  const int *__restrict__ offsets, uint16_t *__restrict__ xq,
                                                                  uint32_t *__restrict__ chunk_flags, size_t rows, int cols,
                                                                  float missing, int tab_stride, int trs, int cshift, int perm)
@@ -64,13 +92,19 @@ __global__ void __launch_bounds__(kQuantThreads) quantize_kernel(const float *__
     const size_t r1 = min(rows, r0 + ((size_t)1 << cshift));
     constexpr int U = (F == 1) ? 4 : 2;  // rows per thread and iteration: U * F independent search chains
     using V = typename QVec<F>::T;
+    const float *cp[F];  // COLS: the F columns
+    if constexpr (COLS) {
+#pragma unroll
+        for (int j = 0; j < F; ++j) cp[j] = data.col(f0 + j);
+    }
     bool saw_missing = false;
     for (size_t rb = r0 + threadIdx.x; rb < r1; rb += (size_t)blockDim.x * U) {
         V xv[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const size_t r = min(rb + (size_t)u * blockDim.x, r1 - 1);  // clamped: in bounds, result unused
-            xv[u] = *reinterpret_cast<const V *>(data + r * (size_t)cols + f0);
+            if constexpr (COLS) xv[u] = qv_cols<F>(cp, r);
+            else xv[u] = *reinterpret_cast<const V *>(data + r * (size_t)cols + f0);
         }
 #pragma unroll
         for (int j = 0; j < F; ++j) {
@@ -107,8 +141,9 @@ __global__ void __launch_bounds__(kQuantThreads) quantize_kernel(const float *__
 // loads.  When both search trees fit the LDS budget they are resident together (one pass); a pair with an
 // oversized tree is done in two passes with one tree resident at a time, so a few large features do not
 // force the whole launch down to one feature per workgroup.
+template <bool COLS = false>
 __global__ void __launch_bounds__(kQuantPairThreads)
-    quantize_pair_kernel(const float *__restrict__ data, const float *__restrict__ tables, const int *__restrict__ offsets,
+    quantize_pair_kernel(typename QSrc<COLS>::T data, const float *__restrict__ tables, const int *__restrict__ offsets,
                          uint16_t *__restrict__ xq, uint32_t *__restrict__ chunk_flags, size_t rows, int cols, float missing,
                          int lds_floats, int trs, int cshift, int perm)
 {
@@ -125,6 +160,11 @@ __global__ void __launch_bounds__(kQuantPairThreads)
     const size_t r0 = chunk << cshift;
     const size_t r1 = min(rows, r0 + ((size_t)1 << cshift));
     constexpr int U = 4;  // rows per thread and iteration: 8 independent search chains hide the LDS latency
+    const float *cp[2];  // COLS: the pair's columns
+    if constexpr (COLS) {
+        cp[0] = data.col(f0);
+        cp[1] = data.col(f0 + 1);
+    }
     bool saw_missing = false;
     for (int pass = 0; pass < (together ? 1 : 2); ++pass) {
         if (pass) __syncthreads();  // everyone is done reading the first tree
@@ -139,7 +179,8 @@ __global__ void __launch_bounds__(kQuantPairThreads)
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const size_t r = min(r0 + threadIdx.x + (size_t)u * blockDim.x, r1 - 1);
-            nx[u] = *reinterpret_cast<const float2 *>(data + r * (size_t)cols + f0);
+            if constexpr (COLS) nx[u] = qv_cols<2>(cp, r);
+            else nx[u] = *reinterpret_cast<const float2 *>(data + r * (size_t)cols + f0);
         }
         for (size_t rb = r0 + threadIdx.x; rb < r1; rb += (size_t)blockDim.x * U) {
             float2 xv[U];
@@ -153,7 +194,8 @@ __global__ void __launch_bounds__(kQuantPairThreads)
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const size_t r = min(rb + (size_t)(U + u) * blockDim.x, r1 - 1);  // clamped: in bounds, result unused
-                nx[u] = *reinterpret_cast<const float2 *>(data + r * (size_t)cols + f0);
+                if constexpr (COLS) nx[u] = qv_cols<2>(cp, r);
+                else nx[u] = *reinterpret_cast<const float2 *>(data + r * (size_t)cols + f0);
             }
             // descend both trees: k <- 2k + (tab[k] <= x); k - 2^p = #{thresholds <= x} (NaN x -> 0)
             if (do0)
@@ -217,8 +259,9 @@ __global__ void bucket_index_kernel(const float *__restrict__ vals, const int *_
 // floats of a pair's image behind its two sorted runs: both start tables ((B + 2) u16 each), padded to 16 bytes
 __host__ __device__ __forceinline__ int q_bucket_tail_floats(int B) { return (B + 2 + 3) & ~3; }
 
+template <bool COLS = false>
 __global__ void __launch_bounds__(kQuantPairThreads)
-    quantize_bucket_pair_kernel(const float *__restrict__ data, const float *__restrict__ bimage, const int *__restrict__ boffsets,
+    quantize_bucket_pair_kernel(typename QSrc<COLS>::T data, const float *__restrict__ bimage, const int *__restrict__ boffsets,
                                 const float4 *__restrict__ bparams,
                                 uint16_t *__restrict__ xq, uint32_t *__restrict__ chunk_flags, size_t rows, int cols, float missing,
                                 int B, int trs, int cshift, int perm)
@@ -245,6 +288,11 @@ __global__ void __launch_bounds__(kQuantPairThreads)
     const size_t r0 = chunk << cshift;
     const size_t r1 = min(rows, r0 + ((size_t)1 << cshift));
     constexpr int U = 4;
+    const float *cp[2];  // COLS: the pair's columns
+    if constexpr (COLS) {
+        cp[0] = data.col(f0);
+        cp[1] = data.col(f0 + 1);
+    }
     bool saw_missing = false;
     // the rows of the next iterations are loaded before the current ones are converted: the loads (a new cache line
     // each, HBM latency) fly under the searching
@@ -252,7 +300,8 @@ __global__ void __launch_bounds__(kQuantPairThreads)
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const size_t r = min(r0 + threadIdx.x + (size_t)u * blockDim.x, r1 - 1);
-        nx[u] = *reinterpret_cast<const float2 *>(data + r * (size_t)cols + f0);
+        if constexpr (COLS) nx[u] = qv_cols<2>(cp, r);
+        else nx[u] = *reinterpret_cast<const float2 *>(data + r * (size_t)cols + f0);
     }
     for (size_t rb = r0 + threadIdx.x; rb < r1; rb += (size_t)blockDim.x * U) {
         float2 xv[U];
@@ -262,7 +311,8 @@ __global__ void __launch_bounds__(kQuantPairThreads)
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const size_t r = min(rb + (size_t)(U + u) * blockDim.x, r1 - 1);  // clamped: in bounds, result unused
-            nx[u] = *reinterpret_cast<const float2 *>(data + r * (size_t)cols + f0);
+            if constexpr (COLS) nx[u] = qv_cols<2>(cp, r);
+            else nx[u] = *reinterpret_cast<const float2 *>(data + r * (size_t)cols + f0);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {  // positions are kept in bytes: one add forms the probe address
@@ -317,9 +367,9 @@ __global__ void __launch_bounds__(kQuantPairThreads)
 // line per lane); with F = 4 * Q features per workgroup a row is read by Q adjacent lanes as float4, F = 16 uses
 // whole lines.  Tables: the Eytzinger search trees (a few hundred bytes each), descent as in quantize_kernel; the
 // trip count is per lane (adjacent lanes serve different features), a wave runs to its longest.
-template <int Q>
+template <int Q, bool COLS = false>
 __global__ void __launch_bounds__(kQuantPairThreads)
-    quantize_multi_kernel(const float *__restrict__ data, const float *__restrict__ tables, const int *__restrict__ offsets,
+    quantize_multi_kernel(typename QSrc<COLS>::T data, const float *__restrict__ tables, const int *__restrict__ offsets,
                           uint16_t *__restrict__ xq, uint32_t *__restrict__ chunk_flags, size_t rows, int cols, float missing,
                           int tab_stride, int trs, int cshift, int perm)
 {
@@ -347,12 +397,18 @@ __global__ void __launch_bounds__(kQuantPairThreads)
     __syncthreads();
     const size_t r0 = chunk << cshift;
     const size_t r1 = min(rows, r0 + ((size_t)1 << cshift));
+    const float *cp[4];  // COLS: this thread's four columns (Q adjacent lanes serve different features: a per-lane table read)
+    if constexpr (COLS) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) cp[j] = data.col(fq + j);
+    }
     bool saw_missing = false;
     float4 nx[U];  // next iteration's rows, loaded one iteration ahead (see quantize_bucket_pair_kernel)
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const size_t r = min(r0 + rsub + (size_t)u * RPI, r1 - 1);
-        nx[u] = *reinterpret_cast<const float4 *>(data + r * (size_t)cols + fq);
+        if constexpr (COLS) nx[u] = qv_cols<4>(cp, r);
+        else nx[u] = *reinterpret_cast<const float4 *>(data + r * (size_t)cols + fq);
     }
     for (size_t rb = r0 + rsub; rb < r1; rb += (size_t)RPI * U) {
         float4 xv[U];
@@ -361,7 +417,8 @@ __global__ void __launch_bounds__(kQuantPairThreads)
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const size_t r = min(rb + (size_t)(U + u) * RPI, r1 - 1);  // clamped: in bounds, result unused
-            nx[u] = *reinterpret_cast<const float4 *>(data + r * (size_t)cols + fq);
+            if constexpr (COLS) nx[u] = qv_cols<4>(cp, r);
+            else nx[u] = *reinterpret_cast<const float4 *>(data + r * (size_t)cols + fq);
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -592,8 +649,11 @@ void quantize_free_tables(tahoe_qgroup &g)
 hipError_t quantize_allow_lds(const tahoe_forest *f)
 {
     for (const void *k : {(const void *)&quantize_multi_kernel<8>, (const void *)&quantize_multi_kernel<4>, (const void *)&quantize_multi_kernel<2>,
-                          (const void *)&quantize_bucket_pair_kernel, (const void *)&quantize_pair_kernel,
-                          (const void *)&quantize_kernel<1>}) {
+                          (const void *)&quantize_bucket_pair_kernel<>, (const void *)&quantize_pair_kernel<>,
+                          (const void *)&quantize_kernel<1>,  // ... and the same six on a column-major batch
+                          (const void *)&quantize_multi_kernel<8, true>, (const void *)&quantize_multi_kernel<4, true>,
+                          (const void *)&quantize_multi_kernel<2, true>, (const void *)&quantize_bucket_pair_kernel<true>,
+                          (const void *)&quantize_pair_kernel<true>, (const void *)&quantize_kernel<1, true>}) {
         const hipError_t e = allow_max_lds(k, f->lds_limit);
         if (e != hipSuccess) return e;
     }
@@ -601,11 +661,12 @@ hipError_t quantize_allow_lds(const tahoe_forest *f)
 }
 
 tahoe_status quantize_launch(tahoe_forest *f, const tahoe_qgroup &g, const float *data, size_t rows, int trs, int perm,
-                             hipStream_t stream, int *cshift_out)
+                             hipStream_t stream, int *cshift_out, const ColsView *cols)
 {
     tahoe_qstate *q = f->q;
-    const bool pair_ok = g.pair_lds_floats > 0 && (reinterpret_cast<uintptr_t>(data) % 8) == 0;  // float2 loads
-    const bool multi_ok = g.multi_q > 0 && (reinterpret_cast<uintptr_t>(data) % 16) == 0;  // float4 loads
+    // (a column-major batch has no float2 / float4 row load: the form depends on the tables alone)
+    const bool pair_ok = g.pair_lds_floats > 0 && (cols || (reinterpret_cast<uintptr_t>(data) % 8) == 0);  // float2 loads
+    const bool multi_ok = g.multi_q > 0 && (cols || (reinterpret_cast<uintptr_t>(data) % 16) == 0);  // float4 loads
     // Rows per quantise workgroup (2^cshift): as many as 65536 so that staging the tables is amortised, fewer when
     // that would leave the chip short of workgroups (few columns or rows), never so few that the tables outweigh
     // the rows a workgroup converts.
@@ -621,30 +682,33 @@ tahoe_status quantize_launch(tahoe_forest *f, const tahoe_qgroup &g, const float
     const size_t chunks = (rows + ((size_t)1 << cshift) - 1) >> cshift;
     const size_t qgrid = chunks * fgroups;
     if (qgrid > 0x7fffffffu) return fail(TAHOE_ERR_INVALID_ARG, "too many rows x cols for one launch");
-    if (multi_ok && g.multi_q == 8)
-        hipLaunchKernelGGL(quantize_multi_kernel<8>, dim3((unsigned)qgrid), dim3(kQuantPairThreads),
-                           (size_t)32 * std::max(g.max_table, 1) * 4, stream, data, g.tables, g.offsets, q->xq, q->chunk_flags,
-                           rows, f->p.num_cols, f->p.missing, std::max(g.max_table, 1), trs, cshift, perm);
-    else if (multi_ok && g.multi_q == 4)
-        hipLaunchKernelGGL(quantize_multi_kernel<4>, dim3((unsigned)qgrid), dim3(kQuantPairThreads),
-                           (size_t)16 * std::max(g.max_table, 1) * 4, stream, data, g.tables, g.offsets, q->xq, q->chunk_flags,
-                           rows, f->p.num_cols, f->p.missing, std::max(g.max_table, 1), trs, cshift, perm);
-    else if (multi_ok)
-        hipLaunchKernelGGL(quantize_multi_kernel<2>, dim3((unsigned)qgrid), dim3(kQuantPairThreads),
-                           (size_t)8 * std::max(g.max_table, 1) * 4, stream, data, g.tables, g.offsets, q->xq, q->chunk_flags,
-                           rows, f->p.num_cols, f->p.missing, std::max(g.max_table, 1), trs, cshift, perm);
-    else if (pair_ok && g.buckets > 0)
-        hipLaunchKernelGGL(quantize_bucket_pair_kernel, dim3((unsigned)qgrid), dim3(kQuantPairThreads),
-                           (size_t)g.bucket_lds_bytes, stream, data, g.bimage, g.boffsets, g.bparams, q->xq,
-                           q->chunk_flags, rows, f->p.num_cols, f->p.missing, g.buckets, trs, cshift, perm);
-    else if (pair_ok)
-        hipLaunchKernelGGL(quantize_pair_kernel, dim3((unsigned)qgrid), dim3(kQuantPairThreads),
-                           (size_t)g.pair_lds_floats * 4, stream, data, g.tables, g.offsets, q->xq, q->chunk_flags, rows,
-                           f->p.num_cols, f->p.missing, g.pair_lds_floats, trs, cshift, perm);
-    else
-        hipLaunchKernelGGL(quantize_kernel<1>, dim3((unsigned)qgrid), dim3(kQuantThreads), (size_t)std::max(g.max_table, 1) * 4,
-                           stream, data, g.tables, g.offsets, q->xq, q->chunk_flags, rows, f->p.num_cols, f->p.missing,
-                           std::max(g.max_table, 1), trs, cshift, perm);
+    with_cols(data, cols, [&](auto cols_c, auto src) {  // (src: the kernels' first argument, the row pointer or the view)
+        constexpr bool COLS = decltype(cols_c)::value;
+        if (multi_ok && g.multi_q == 8)
+            hipLaunchKernelGGL((quantize_multi_kernel<8, COLS>), dim3((unsigned)qgrid), dim3(kQuantPairThreads),
+                               (size_t)32 * std::max(g.max_table, 1) * 4, stream, src, g.tables, g.offsets, q->xq, q->chunk_flags,
+                               rows, f->p.num_cols, f->p.missing, std::max(g.max_table, 1), trs, cshift, perm);
+        else if (multi_ok && g.multi_q == 4)
+            hipLaunchKernelGGL((quantize_multi_kernel<4, COLS>), dim3((unsigned)qgrid), dim3(kQuantPairThreads),
+                               (size_t)16 * std::max(g.max_table, 1) * 4, stream, src, g.tables, g.offsets, q->xq, q->chunk_flags,
+                               rows, f->p.num_cols, f->p.missing, std::max(g.max_table, 1), trs, cshift, perm);
+        else if (multi_ok)
+            hipLaunchKernelGGL((quantize_multi_kernel<2, COLS>), dim3((unsigned)qgrid), dim3(kQuantPairThreads),
+                               (size_t)8 * std::max(g.max_table, 1) * 4, stream, src, g.tables, g.offsets, q->xq, q->chunk_flags,
+                               rows, f->p.num_cols, f->p.missing, std::max(g.max_table, 1), trs, cshift, perm);
+        else if (pair_ok && g.buckets > 0)
+            hipLaunchKernelGGL(quantize_bucket_pair_kernel<COLS>, dim3((unsigned)qgrid), dim3(kQuantPairThreads),
+                               (size_t)g.bucket_lds_bytes, stream, src, g.bimage, g.boffsets, g.bparams, q->xq,
+                               q->chunk_flags, rows, f->p.num_cols, f->p.missing, g.buckets, trs, cshift, perm);
+        else if (pair_ok)
+            hipLaunchKernelGGL(quantize_pair_kernel<COLS>, dim3((unsigned)qgrid), dim3(kQuantPairThreads),
+                               (size_t)g.pair_lds_floats * 4, stream, src, g.tables, g.offsets, q->xq, q->chunk_flags, rows,
+                               f->p.num_cols, f->p.missing, g.pair_lds_floats, trs, cshift, perm);
+        else
+            hipLaunchKernelGGL((quantize_kernel<1, COLS>), dim3((unsigned)qgrid), dim3(kQuantThreads), (size_t)std::max(g.max_table, 1) * 4,
+                               stream, src, g.tables, g.offsets, q->xq, q->chunk_flags, rows, f->p.num_cols, f->p.missing,
+                               std::max(g.max_table, 1), trs, cshift, perm);
+    });
     TAHOE_HIP_TRY(hipGetLastError());
     *cshift_out = cshift;
     return TAHOE_OK;

@@ -79,15 +79,18 @@ constexpr long long kCatMaxWords = 1 << 19;  // categories < 2^24: exact in floa
 // STAGED (tahoe_forest_predict_staged): `sums` is out[rows][S][num_classes]; the owner lanes keep a stage cursor si and store the
 // running sum, without resetting it, to sums[(row * S + si) * num_classes + cls] after the tree that completes stages[si]
 // trees of the class; the cursor goes back to 0 at a class end and the final per-class / per-row store is not done.
-template <bool TILE, bool WRITE_LEAF, bool MC = false, bool CAT = false, bool CSR = false, bool STAGED = false>
+// COLS (with TILE): the tile is staged from column-major buffers by cols_stage_tile (forest_internal.h) and `data` is not read.
+template <bool TILE, bool WRITE_LEAF, bool MC = false, bool CAT = false, bool CSR = false, bool STAGED = false, bool COLS = false>
 __global__ void __launch_bounds__(kBlock) sparse_kernel(const tahoe_sparse_node *__restrict__ nodes,
                                                         const int32_t *__restrict__ trees, const float *__restrict__ data,
                                                         float *sums, uint32_t *__restrict__ leaf_out,
                                                         const float *sums_in, size_t rows, int cols, int num_trees, float missing,
                                                         int vec4_ok, int num_classes, const uint32_t *__restrict__ cat_pool,
-                                                        uint32_t cat_words, CsrView csr, const int32_t *__restrict__ stages, int S)
+                                                        uint32_t cat_words, CsrView csr, const int32_t *__restrict__ stages, int S,
+                                                        ColsView cv)
 {
     static_assert(TILE || !CSR, "the CSR loader fills a tile");
+    static_assert(!COLS || (TILE && !CSR && !WRITE_LEAF && !STAGED), "column-major rows: the tile kernel, predictions only");
     static_assert(!STAGED || (!WRITE_LEAF && !CSR), "staged output: predictions from dense rows");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
@@ -100,6 +103,9 @@ __global__ void __launch_bounds__(kBlock) sparse_kernel(const tahoe_sparse_node 
     const float *xrow = data + (row_ok ? row : row0) * (size_t)cols;
     if constexpr (CSR) {
         csr_stage_tile<kBlock>(tile, reinterpret_cast<int64_t *>(vals), cols, row0, rows, csr, missing, threadIdx.x);
+        __syncthreads();
+    } else if constexpr (COLS) {
+        cols_stage_tile<kWaves>(tile, cols, row0, rows, cv, wave, lane);
         __syncthreads();
     } else if (TILE) {
         if (vec4_ok) {
@@ -196,16 +202,18 @@ constexpr int kSBatch = 4;    // trees the consumer takes per poll (K5: 16 -> 5.
 // MC: as sparse_kernel's, in the consumer wave.  CAT: a node flagged kSCCat takes go_right_cat on the pool entry in its x word.
 // CSR: as sparse_kernel's.  STAGED: sparse_kernel's stage cursor, in a consumer loop of its own; the walkers and the ring
 // hand-over are the same code.
-template <int NW, bool WRITE_LEAF, bool MC = false, bool CAT = false, bool CSR = false, bool STAGED = false>
+// COLS: as sparse_kernel's.
+template <int NW, bool WRITE_LEAF, bool MC = false, bool CAT = false, bool CSR = false, bool STAGED = false, bool COLS = false>
 __global__ void __launch_bounds__(NW * 64) sparse_top_kernel(const uint2 *__restrict__ cnodes, const int32_t *__restrict__ ctrees,
                                                              const uint32_t *__restrict__ corig, const float *__restrict__ data,
                                                              float *sums, uint32_t *__restrict__ leaf_out,
                                                              const float *sums_in, size_t rows, int cols, int num_trees, float missing,
                                                              int vec4_ok, int *__restrict__ error_flag, int num_classes,
                                                              const uint32_t *__restrict__ cat_pool, uint32_t cat_words, CsrView csr,
-                                                             const int32_t *__restrict__ stages, int S)
+                                                             const int32_t *__restrict__ stages, int S, ColsView cv)
 {
     static_assert(!STAGED || (!WRITE_LEAF && !CSR), "staged output: predictions from dense rows");
+    static_assert(!COLS || (!CSR && !WRITE_LEAF && !STAGED), "column-major rows: predictions only");
     constexpr int NWALK = NW - 1;
     static_assert(kSRing >= 2 * kSBatch && kSRing > NWALK, "ring too small");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -222,6 +230,8 @@ __global__ void __launch_bounds__(NW * 64) sparse_top_kernel(const uint2 *__rest
     const float *xrow = data + (row_ok ? row : row0) * (size_t)cols;
     if constexpr (CSR) {
         csr_stage_tile<NW * 64>(tile, reinterpret_cast<int64_t *>(ring_vals), cols, row0, rows, csr, missing, threadIdx.x);
+    } else if constexpr (COLS) {
+        cols_stage_tile<NW>(tile, cols, row0, rows, cv, wave, lane);
     } else if (vec4_ok) {
         const float4 *src4 = reinterpret_cast<const float4 *>(xrow);
         for (int f4 = wave; f4 < cols / 4; f4 += NW) {
@@ -728,7 +738,7 @@ static void sparse_q_launch_form(tahoe_forest *f, const tahoe_qgroup &g, float *
 
 // quantise + walk per tree group, in stream order; the tile plan of the dense region form (qreg_plan)
 static tahoe_status sparse_q_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data, size_t rows,
-                                    hipStream_t stream, const float *sums_in0)
+                                    hipStream_t stream, const float *sums_in0, const ColsView *cols)
 {
     tahoe_qstate *q = f->q;
     const tahoe_status rs = qring_reserve(f, rows);  // no-op unless this batch is larger than any before
@@ -740,7 +750,7 @@ static tahoe_status sparse_q_launch(tahoe_forest *f, float *sums, uint32_t *leaf
     for (const tahoe_qgroup &g : q->groups) {
         TAHOE_HIP_TRY(hipMemsetAsync(q->chunk_flags, 0, q->n_chunk_flags * sizeof(uint32_t), stream));
         int cshift = 0;
-        const tahoe_status qs = quantize_launch(f, g, data, rows, 6, 1, stream, &cshift);
+        const tahoe_status qs = quantize_launch(f, g, data, rows, 6, 1, stream, &cshift, cols);
         if (qs != TAHOE_OK) return qs;
         const float *sums_in = first ? sums_in0 : sums;  // later groups continue the running float32 sums
         if (rows3 > 0) sparse_q_launch_form<kReg3Walkers, 3, kReg3Ring>(f, g, sums, sums_in, leaf_out, 0, rows3, stream, cshift);
@@ -776,12 +786,12 @@ static long long sparse_lds(const tahoe_forest *f, bool tile)
 bool sparse_tile_fits(const tahoe_forest *f) { return f->p.num_cols >= 1 && sparse_lds(f, true) <= f->lds_limit; }
 
 tahoe_status sparse_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data, size_t rows,
-                           hipStream_t stream, int strategy, const float *sums_in, const CsrView *csr)
+                           hipStream_t stream, int strategy, const float *sums_in, const CsrView *csr, const ColsView *cols)
 {
     const tahoe_sstate *sp = f->sp;
     const unsigned grid = (unsigned)((rows + kTileRows - 1) / kTileRows);
     const int vec4_ok = (f->p.num_cols % 4 == 0) && ((reinterpret_cast<uintptr_t>(data) & 15u) == 0);
-    if (strategy == TAHOE_STRATEGY_QRING) return sparse_q_launch(f, sums, leaf_out, data, rows, stream, sums_in);
+    if (strategy == TAHOE_STRATEGY_QRING) return sparse_q_launch(f, sums, leaf_out, data, rows, stream, sums_in, cols);
     if (strategy == TAHOE_STRATEGY_TILEBLOCK) {
         const int nw = sparse_top_waves(f);  // > 0: launch_traversal has checked strategy_available
         const int lds = (int)sparse_top_lds(f, nw);
@@ -793,12 +803,17 @@ tahoe_status sparse_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, con
                     hipLaunchKernelGGL((sparse_top_kernel<NW, false, decltype(mc)::value, decltype(cat)::value, true>), dim3(grid),
                                        dim3(NW * 64), lds, stream, sp->cnodes, sp->ctrees, sp->corig, data, sums, leaf_out, sums_in, rows,
                                        f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, f->error_flag, nc, sp->cat_pool,
-                                       sp->cat_words, *csr, nullptr, 0);
+                                       sp->cat_words, *csr, nullptr, 0, ColsView{});
+                else if (cols)
+                    hipLaunchKernelGGL((sparse_top_kernel<NW, false, decltype(mc)::value, decltype(cat)::value, false, false, true>),
+                                       dim3(grid), dim3(NW * 64), lds, stream, sp->cnodes, sp->ctrees, sp->corig, data, sums, leaf_out,
+                                       sums_in, rows, f->p.num_cols, f->p.num_trees, f->p.missing, 0, f->error_flag, nc, sp->cat_pool,
+                                       sp->cat_words, CsrView{}, nullptr, 0, *cols);
                 else
                     hipLaunchKernelGGL((sparse_top_kernel<NW, decltype(wl)::value, decltype(mc)::value, decltype(cat)::value>), dim3(grid),
                                        dim3(NW * 64), lds, stream, sp->cnodes, sp->ctrees, sp->corig, data, sums, leaf_out, sums_in, rows,
                                        f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, f->error_flag, nc, sp->cat_pool,
-                                       sp->cat_words, CsrView{}, nullptr, 0);
+                                       sp->cat_words, CsrView{}, nullptr, 0, ColsView{});
             };
             auto with_cat = [&](auto nw_c) {
                 if (sp->cat_pool) launch(nw_c, std::true_type{});
@@ -819,13 +834,22 @@ tahoe_status sparse_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, con
                 if (csr) {  // (predictions only: no leaf-index form)
                     hipLaunchKernelGGL((sparse_kernel<true, false, decltype(mc)::value, decltype(cat)::value, true>), dim3(grid),
                                        dim3(kBlock), lds, stream, sp->nodes, sp->trees, data, sums, leaf_out, sums_in, rows,
-                                       f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, nc, sp->cat_pool, sp->cat_words, *csr, nullptr, 0);
+                                       f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, nc, sp->cat_pool, sp->cat_words, *csr, nullptr, 0,
+                                       ColsView{});
+                    return;
+                }
+                if (cols) {
+                    hipLaunchKernelGGL((sparse_kernel<true, false, decltype(mc)::value, decltype(cat)::value, false, false, true>),
+                                       dim3(grid), dim3(kBlock), lds, stream, sp->nodes, sp->trees, data, sums, leaf_out, sums_in, rows,
+                                       f->p.num_cols, f->p.num_trees, f->p.missing, 0, nc, sp->cat_pool, sp->cat_words, CsrView{}, nullptr,
+                                       0, *cols);
                     return;
                 }
             }
             hipLaunchKernelGGL((sparse_kernel<decltype(tile_c)::value, decltype(wl)::value, decltype(mc)::value, decltype(cat)::value>),
                                dim3(grid), dim3(kBlock), lds, stream, sp->nodes, sp->trees, data, sums, leaf_out, sums_in, rows,
-                               f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, nc, sp->cat_pool, sp->cat_words, CsrView{}, nullptr, 0);
+                               f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, nc, sp->cat_pool, sp->cat_words, CsrView{}, nullptr, 0,
+                               ColsView{});
         };
         auto with_cat = [&](auto tile_c) {
             if (sp->cat_pool) launch(tile_c, std::true_type{});
@@ -869,7 +893,7 @@ tahoe_status sparse_launch_staged(tahoe_forest *f, float *out, const float *data
                 hipLaunchKernelGGL((sparse_top_kernel<NW, false, decltype(mc)::value, decltype(cat)::value, false, true>), dim3(grid),
                                    dim3(NW * 64), lds, stream, sp->cnodes, sp->ctrees, sp->corig, data, out, nullptr, nullptr, rows,
                                    f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, f->error_flag, nc, sp->cat_pool, sp->cat_words,
-                                   CsrView{}, f->stages_dev, S);
+                                   CsrView{}, f->stages_dev, S, ColsView{});
             };
             if (nw == 16) launch(std::integral_constant<int, 16>{});
             else launch(std::integral_constant<int, 8>{});
@@ -883,7 +907,7 @@ tahoe_status sparse_launch_staged(tahoe_forest *f, float *out, const float *data
                 hipLaunchKernelGGL((sparse_kernel<decltype(tile_c)::value, false, decltype(mc)::value, decltype(cat)::value, false, true>),
                                    dim3(grid), dim3(kBlock), lds, stream, sp->nodes, sp->trees, data, out, nullptr, nullptr, rows,
                                    f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, nc, sp->cat_pool, sp->cat_words, CsrView{},
-                                   f->stages_dev, S);
+                                   f->stages_dev, S, ColsView{});
             };
             if (tile) launch(std::true_type{});
             else launch(std::false_type{});
@@ -1209,8 +1233,12 @@ static tahoe_status sparse_top_build(tahoe_forest *f, const int32_t *trees, cons
     {  // the CSR-loader forms (tahoe_forest_predict_csr) of this handle's kind
         auto allow = [&](auto mc, auto ct_) {
             constexpr bool M = decltype(mc)::value, K = decltype(ct_)::value;
-            const hipError_t a = allow_max_lds(reinterpret_cast<const void *>(&sparse_top_kernel<16, false, M, K, true>), f->lds_limit);
-            return a != hipSuccess ? a : allow_max_lds(reinterpret_cast<const void *>(&sparse_top_kernel<8, false, M, K, true>), f->lds_limit);
+            hipError_t a = hipSuccess;  // (..., true>: the CSR loader; ..., false, false, true>: the column loader)
+            for (const void *k : {(const void *)&sparse_top_kernel<16, false, M, K, true>, (const void *)&sparse_top_kernel<8, false, M, K, true>,
+                                  (const void *)&sparse_top_kernel<16, false, M, K, false, false, true>,
+                                  (const void *)&sparse_top_kernel<8, false, M, K, false, false, true>})
+                if ((a = allow_max_lds(k, f->lds_limit)) != hipSuccess) break;
+            return a;
         };
         const bool mc = f->num_classes > 1;
         e = cat ? (mc ? allow(std::true_type{}, std::true_type{}) : allow(std::false_type{}, std::true_type{}))
@@ -1395,6 +1423,12 @@ static tahoe_status create_sparse(tahoe_forest **out, const int32_t *trees, cons
                              : (num_classes > 1 ? (const void *)&sparse_kernel<true, false, true, false, true>
                                                 : (const void *)&sparse_kernel<true, false, false, false, true>);
         if ((e = allow_max_lds(k, f->lds_limit)) != hipSuccess) return hip_status(e, "hipFuncSetAttribute(sparse, csr)");
+        // ... and its column-loader form (tahoe_forest_predict_columns)
+        const void *kc = cats ? (num_classes > 1 ? (const void *)&sparse_kernel<true, false, true, true, false, false, true>
+                                                 : (const void *)&sparse_kernel<true, false, false, true, false, false, true>)
+                              : (num_classes > 1 ? (const void *)&sparse_kernel<true, false, true, false, false, false, true>
+                                                 : (const void *)&sparse_kernel<true, false, false, false, false, false, true>);
+        if ((e = allow_max_lds(kc, f->lds_limit)) != hipSuccess) return hip_status(e, "hipFuncSetAttribute(sparse, columns)");
     }
     if (p->num_cols <= 32767 && p->num_trees > 0 && (s = sparse_top_build(f.get(), trees, nodes))) return s;
     if ((flags & TAHOE_CREATE_PARTIAL_DEPENDENCE) && (s = pd_build_sparse(f.get(), caller_trees, caller_nodes, covers))) return s;

@@ -26,7 +26,8 @@ FLAGGED = ("direct_kernel", "rowtile_kernel", "qring_kernel", "qwide_kernel",  #
            "interventional_kernel", "approx_kernel",
            "oblivious_tile_kernel", "oblivious_direct_kernel", "oblivious_shap_kernel", "oblivious_inter_kernel",
            "oblivious_iv_kernel",  # CAT
-           "vector_tile_kernel", "vector_direct_kernel")  # STAGED (the two oblivious walk kernels carry it too)
+           "vector_tile_kernel", "vector_direct_kernel",  # STAGED (the two oblivious walk kernels carry it too)
+           "quantize_kernel", "quantize_pair_kernel", "quantize_bucket_pair_kernel", "quantize_multi_kernel")  # COLS
 
 
 def functions(path):
