@@ -179,6 +179,26 @@ tahoe_status tahoe_forest_create_ex(tahoe_forest **out, const tahoe_dense_node *
                                     const tahoe_forest_params *params, unsigned flags);
 void tahoe_forest_destroy(tahoe_forest *f);
 
+/* NaN as a missing value (XGBoost, LightGBM, scikit-learn's histogram boosters, CatBoost's AsIs: the default-direction bit says
+ * where a NaN goes).  A create flag for tahoe_forest_create_ex, tahoe_forest_create_multiclass, tahoe_sparse_forest_create_ex and
+ * tahoe_sparse_forest_create_cat (tahoe_dense_to_sparse_ex converts node arrays and takes no flags: a converted forest gets the
+ * rule from the create it is passed to); it combines with TAHOE_CREATE_PROB_RELAYOUT.  On such a handle a feature value x is missing iff
+ *     isnan(x) || fabsf(x - params.missing) <= 1e-6f        (float32 arithmetic)
+ * and a missing value takes the node's default branch (right iff !def_left); at a categorical split the missing test, step 1 of
+ * the rule of tahoe_sparse_forest_create_cat, is this one, so a NaN takes the default branch instead of being a non-member.
+ * Nothing else in any rule changes.  The sentinel keeps working beside NaN (XGBoost's DMatrix(missing=m)); any NaN bit pattern
+ * counts (quiet, signalling, either sign, any payload); params.missing = NaN means "NaN only"; params.missing = +-inf stays what
+ * it is without the flag (inf - inf is NaN, the band never matches, and an infinite x is an ordinary value).  Without the flag
+ * every handle behaves as ever: a NaN goes left, and a NaN sentinel switches the missing branch off.
+ * Every call that walks rows to a leaf applies the rule: tahoe_forest_predict, _predict_raw, _predict_leaf_idx,
+ * _predict_accumulate, _predict_host, _predict_csr (a stored NaN is missing, as a stored sentinel and an absent entry are),
+ * _predict_columns / _predict_column_ptrs and _predict_staged.  Strategies served: AUTO, DIRECT, ROWTILE and QRING on a dense or
+ * multi-class handle -- TILEBLOCK and TILERING are TAHOE_ERR_UNSUPPORTED there, and AUTO plans only the served ones -- and every
+ * strategy of a sparse or categorical handle.  Refused with TAHOE_ERR_INVALID_ARG before a device is touched: the flag together
+ * with TAHOE_CREATE_CONTRIBS, _APPROX_CONTRIBS, _CAT_CONTRIBS or _PARTIAL_DEPENDENCE, and on the oblivious and vector-leaf
+ * creates.  tahoe_forest_create honours no environment variable for it. */
+#define TAHOE_CREATE_NAN_MISSING 0x1000u
+
 /* Multi-class forests (XGBoost multi:softprob / multi:softmax, LightGBM multiclass: one tree per class per boosting round);
  * sparse forests take the same contract through tahoe_sparse_forest_create_ex.
  * Tree t of the num_trees trees belongs to class t % num_classes; num_trees must be a multiple of num_classes, each class then
@@ -785,7 +805,8 @@ tahoe_status tahoe_forest_predict(tahoe_forest *f, float *preds_dev, const float
  * an entry that is not stored is missing and takes the node's default branch, as in XGBoost and LightGBM.  preds_dev gets, bit
  * for bit, what tahoe_forest_predict writes for that dense matrix -- rows values, or rows x num_classes on a multi-class
  * handle, output transform included -- under every strategy setting (every kernel adds a row's leaf values in tree order).
- *   - Stored values are ordinary values: a stored sentinel is missing, a stored NaN goes left, -0.0 stays -0.0.
+ *   - Stored values are ordinary values: a stored sentinel is missing, a stored NaN goes left (on a handle created with
+ *     TAHOE_CREATE_NAN_MISSING it is missing, by the rule stated there), -0.0 stays -0.0.
  *   - Column ids within a row need not be sorted; rows may be empty.  A row must not name a column twice: if it does, one of the
  *     two values is used, which one is unspecified, and nothing else is affected.
  *   - The kernels never read outside [0, nnz) of indices_dev / values_dev nor outside [0, rows] of indptr_dev, whatever
@@ -820,8 +841,9 @@ tahoe_status tahoe_forest_get_csr_plan(const tahoe_forest *f, size_t rows, size_
  * preds_dev gets, bit for bit, what tahoe_forest_predict writes for the row-major matrix with the same values -- rows values,
  * or rows x num_classes, output transform included -- under every strategy setting and on every handle kind: dense, multi-class,
  * sparse, categorical, oblivious, vector-leaf.  No create flag is needed.
- *   - Values are ordinary values: the sentinel is missing, NaN goes left, -0.0 stays -0.0.  Arrow validity bitmaps are not read:
- *     a column with nulls must be filled with the sentinel by the caller (NaN is not missing here; it goes left).  float32 only.
+ *   - Values are ordinary values: the sentinel is missing, NaN goes left, -0.0 stays -0.0.  On a handle created with
+ *     TAHOE_CREATE_NAN_MISSING a NaN is missing, by the rule stated there.  Arrow validity bitmaps are not read: a column with
+ *     nulls must be filled by the caller, with NaN on such a handle, else with the sentinel (NaN then goes left).  float32 only.
  *   - A column pointer needs float alignment only; col_stride is any value >= rows.  Columns may come from separate allocations
  *     in any order, and two entries of the table may name the same buffer.
  *   - No kernel reads outside [0, rows) of any column, nor outside [0, num_cols) of the table.

@@ -45,6 +45,7 @@ CREATE_OBLIVIOUS_INTERVENTIONAL = 0x200  # tahoe_oblivious_forest_create_ex: int
 CREATE_PARTIAL_DEPENDENCE = 0x800  # tahoe_sparse_forest_create_ex / _cat: partial dependence (tahoe_forest_predict_partial_dependence); needs covers
 CREATE_STAGED = 0x2000  # tahoe_oblivious_forest_create_ex / _cat, tahoe_vector_forest_create_ex: set_stages / predict_staged; no covers needed
 CREATE_CSR = 0x4000  # the same three creates: predict_csr / reserve_csr / csr_plan; no covers needed
+CREATE_NAN_MISSING = 0x1000  # dense, multi-class, sparse and categorical creates: a NaN feature value is missing, beside the sentinel
 CREATE_VECTOR_APPROX = 0x400  # tahoe_vector_forest_create_ex: Saabas contributions (tahoe_forest_predict_contribs_approx); needs covers
 STRATEGY_NAMES = {1: "direct", 2: "rowtile", 3: "tileblock", 4: "tilering", 5: "qring"}
 STATUS_NAMES = {
@@ -425,18 +426,29 @@ def _stream(stream) -> int:
     return stream if isinstance(stream, int) else stream.cuda_stream
 
 
+def _check_nan_missing(nan_missing: bool, **others) -> None:
+    """nan_missing=True beside an explanation or partial-dependence option: refused here as the C creates refuse the flags."""
+    bad = [k for k, v in others.items() if v]
+    if nan_missing and bad:
+        raise ValueError("nan_missing=True (TAHOE_CREATE_NAN_MISSING) does not combine with " + ", ".join(bad)
+                         + ": those kernels do not implement the rule")
+
+
 class Forest:
     """Handle on a device forest: tahoe_forest_create / predict / destroy.
 
     Mirrors the reference's init_dense* + predict_dense* pair (BaseTahoeTest.h:519-547, :599-611).
     Tensors are torch CUDA tensors (float32 data [rows, cols] contiguous, float32 preds [rows]).
     num_classes > 1 (tahoe_forest_create_multiclass): tree t belongs to class t % num_classes, predict / predict_raw
-    return [rows, num_classes] and predict_leaf_idx [rows, num_trees] leaves with [rows, num_classes] sums."""
+    return [rows, num_classes] and predict_leaf_idx [rows, num_trees] leaves with [rows, num_classes] sums.
+    nan_missing=True (TAHOE_CREATE_NAN_MISSING): a NaN is a missing value beside the sentinel and takes the node's default branch,
+    in every predict call; not together with contribs / approx_contribs.  TILEBLOCK and TILERING are then not served."""
 
     def __init__(self, nodes: np.ndarray, num_trees: int, depth: int, num_cols: int, missing: float = 0.0,
                  output: int = OUT_RAW, threshold: float = 0.0, global_bias: float = 0.0, algo: int = 0,
                  strategy: int = 0, relayout: bool = False, num_classes: int = 1, contribs: bool = False,
-                 approx_contribs: bool = False):
+                 approx_contribs: bool = False, nan_missing: bool = False):
+        _check_nan_missing(nan_missing, contribs=contribs, approx_contribs=approx_contribs)
         nodes = np.ascontiguousarray(nodes, dtype=NODE_DTYPE)
         if nodes.size != num_trees * tree_num_nodes(depth):
             raise ValueError("nodes.size != num_trees * tree_num_nodes(depth)")
@@ -444,7 +456,7 @@ class Forest:
                                    missing)
         self._h = _vp()
         flags = ((CREATE_PROB_RELAYOUT if relayout else 0) | (CREATE_CONTRIBS if contribs else 0)
-                 | (CREATE_APPROX_CONTRIBS if approx_contribs else 0))
+                 | (CREATE_APPROX_CONTRIBS if approx_contribs else 0) | (CREATE_NAN_MISSING if nan_missing else 0))
         if num_classes != 1:
             _check(lib.tahoe_forest_create_multiclass(C.byref(self._h), nodes.ctypes.data if nodes.size else None,
                                                       C.byref(self.params), num_classes, flags),
@@ -865,12 +877,16 @@ class SparseForest(Forest):
     deltas.  categories ({node index: category ids}) makes those nodes categorical splits, members going right unless the
     node is in members_left (tahoe_sparse_forest_create_cat; the node's val is then ignored).  categories together with
     contribs / approx_contribs sets TAHOE_CREATE_CAT_CONTRIBS: the four explanation calls then follow the category sets.
-    partial_dependence=True (TAHOE_CREATE_PARTIAL_DEPENDENCE; needs covers) serves Forest.partial_dependence."""
+    partial_dependence=True (TAHOE_CREATE_PARTIAL_DEPENDENCE; needs covers) serves Forest.partial_dependence.
+    nan_missing=True (TAHOE_CREATE_NAN_MISSING): as Forest's, under every strategy; at a categorical split a NaN then takes the
+    default branch; not together with contribs / approx_contribs / partial_dependence.  A forest from dense_to_sparse gets the
+    rule here."""
 
     def __init__(self, nodes: np.ndarray, trees: np.ndarray, num_cols: int, missing: float = 0.0, output: int = OUT_RAW,
                  threshold: float = 0.0, global_bias: float = 0.0, covers=None, num_classes: int = 1,
                  contribs: bool = False, approx_contribs: bool = False, categories=None, members_left=(),
-                 partial_dependence: bool = False):
+                 partial_dependence: bool = False, nan_missing: bool = False):
+        _check_nan_missing(nan_missing, contribs=contribs, approx_contribs=approx_contribs, partial_dependence=partial_dependence)
         nodes = np.ascontiguousarray(nodes, dtype=SPARSE_NODE_DTYPE)
         trees = np.ascontiguousarray(trees, dtype=np.int32)
         self.params = ForestParams(int(nodes.size), 0, int(trees.size), num_cols, 0, output, threshold, global_bias, 0,
@@ -878,7 +894,7 @@ class SparseForest(Forest):
         self._h = _vp()
         flags = (CREATE_CONTRIBS if contribs else 0) | (CREATE_APPROX_CONTRIBS if approx_contribs else 0)
         shap_flags = flags
-        flags |= CREATE_PARTIAL_DEPENDENCE if partial_dependence else 0
+        flags |= (CREATE_PARTIAL_DEPENDENCE if partial_dependence else 0) | (CREATE_NAN_MISSING if nan_missing else 0)
         if categories:
             cv = None if covers is None else np.ascontiguousarray(covers, dtype=np.float32)
             if cv is not None and cv.size != nodes.size:

@@ -40,9 +40,10 @@ namespace tahoe {
 
 // ------------------------------------------------------------------------------------------------
 // (go_right, the branch rule, lives in forest_internal.h)
+template <bool NANM = false>
 __device__ __forceinline__ uint32_t step(uint32_t idx, float thr, uint32_t meta, float x, float missing)
 {
-    return 2u * idx + 1u + go_right_meta(x, thr, meta, missing);
+    return 2u * idx + 1u + go_right_meta<NANM>(x, thr, meta, missing);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -53,7 +54,9 @@ __device__ __forceinline__ uint32_t step(uint32_t idx, float thr, uint32_t meta,
 // STAGED (tahoe_forest_predict_staged): `sums` is out[rows][S][num_classes] and stages[0..S) the strictly ascending counts of
 // trees per class after which the running sum is stored -- to sums[(row * S + si) * num_classes + cls], without resetting it
 // -- by a stage cursor si that goes back to 0 at a class end; the final per-class / per-row store is not done.
-template <bool WRITE_LEAF, bool MC = false, bool STAGED = false>
+// NANM (TAHOE_CREATE_NAN_MISSING): the branch rule counts a NaN as missing (is_missing_value<true>).  A template flag, here and
+// in rowtile_kernel, so that the instantiations without it stay the code they were.
+template <bool WRITE_LEAF, bool MC = false, bool STAGED = false, bool NANM = false>
 __global__ void __launch_bounds__(kBlock) direct_kernel(const InnerNode *__restrict__ inner,
                                                         const float *__restrict__ leaf_val,
                                                         const uint32_t *__restrict__ leaf_orig,
@@ -77,7 +80,7 @@ __global__ void __launch_bounds__(kBlock) direct_kernel(const InnerNode *__restr
         uint32_t idx = 0;
         for (int l = 0; l < depth; ++l) {
             const InnerNode n = tree[idx];
-            idx = step(idx, n.thr, n.meta, x[n.meta & kMetaFidMask], missing);
+            idx = step<NANM>(idx, n.thr, n.meta, x[n.meta & kMetaFidMask], missing);
         }
         const size_t b = (size_t)t * n_leaf + (idx - (uint32_t)n_inner);
         sum += leaf_val[b];
@@ -117,7 +120,7 @@ __global__ void __launch_bounds__(kBlock) direct_kernel(const InnerNode *__restr
 // CSR: the tile is staged from csr by csr_stage_tile (forest_internal.h) and `data` is not read.
 // STAGED: direct_kernel's stage cursor, kept by the owner lanes; a stage can end at any of a round's four trees.
 // COLS: the tile is staged from column-major buffers by cols_stage_tile (forest_internal.h) and `data` is not read.
-template <bool WRITE_LEAF, bool MC = false, bool CSR = false, bool STAGED = false, bool COLS = false>
+template <bool WRITE_LEAF, bool MC = false, bool CSR = false, bool STAGED = false, bool COLS = false, bool NANM = false>
 __global__ void __launch_bounds__(kBlock) rowtile_kernel(const InnerNode *__restrict__ inner,
                                                          const float *__restrict__ leaf_val,
                                                          const uint32_t *__restrict__ leaf_orig,
@@ -207,13 +210,13 @@ __global__ void __launch_bounds__(kBlock) rowtile_kernel(const InnerNode *__rest
             for (int l = 0; l < lds_levels; ++l) {
                 const InnerNode n = slot[idx];
                 const float x = tile[(n.meta & kMetaFidMask) * kTileRows + lane];
-                idx = step(idx, n.thr, n.meta, x, missing);
+                idx = step<NANM>(idx, n.thr, n.meta, x, missing);
             }
             const InnerNode *tree = inner + (size_t)t * n_inner;
             for (int l = lds_levels; l < depth; ++l) {
                 const InnerNode n = tree[idx];
                 const float x = tile[(n.meta & kMetaFidMask) * kTileRows + lane];
-                idx = step(idx, n.thr, n.meta, x, missing);
+                idx = step<NANM>(idx, n.thr, n.meta, x, missing);
             }
             const size_t b = (size_t)t * n_leaf + (idx - (uint32_t)n_inner);
             v = leaf_val[b];
@@ -899,6 +902,9 @@ tahoe_status strategy_available(const tahoe_forest *f, int strategy)
                         "trees of <= 65535 nodes, num_cols <= 32767) or QRING (quantised tile + tree tops; also num_cols <= 256)");
         return TAHOE_OK;
     }
+    if (f->nan_missing && (strategy == TAHOE_STRATEGY_TILEBLOCK || strategy == TAHOE_STRATEGY_TILERING))
+        return fail(TAHOE_ERR_UNSUPPORTED, "a dense handle created with TAHOE_CREATE_NAN_MISSING runs AUTO, DIRECT, ROWTILE or QRING: "
+                                           "the TILEBLOCK and TILERING kernels do not implement that rule");
     if (f->num_classes > 1 && (strategy == TAHOE_STRATEGY_TILEBLOCK || strategy == TAHOE_STRATEGY_TILERING))
         return fail(TAHOE_ERR_UNSUPPORTED, "a multi-class handle runs AUTO, DIRECT, ROWTILE or QRING (no float32 tile forms)");
     if (strategy == TAHOE_STRATEGY_ROWTILE && !rowtile_fits(f))
@@ -1010,17 +1016,18 @@ static tahoe_status launch_traversal(tahoe_forest *f, float *sums, uint32_t *lea
         const size_t grid = (rows + kTileRows - 1) / kTileRows;
         const int lds = rowtile_lds_bytes(f->p.num_cols, f->lds_levels);
         const int nc = f->num_classes;
-        with_leaf_mc(leaf_out != nullptr, nc > 1, [&](auto wl, auto mc) {
+        with_leaf_mc_nanm(leaf_out != nullptr, nc > 1, f->nan_missing, [&](auto wl, auto mc, auto nanm) {
+            constexpr bool NANM = decltype(nanm)::value;
             if (csr)  // (predictions only: no leaf-index form)
-                hipLaunchKernelGGL((rowtile_kernel<false, decltype(mc)::value, true>), dim3((unsigned)grid), dim3(kBlock), lds, stream,
+                hipLaunchKernelGGL((rowtile_kernel<false, decltype(mc)::value, true, false, false, NANM>), dim3((unsigned)grid), dim3(kBlock), lds, stream,
                                    f->inner, f->leaf_val, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
                                    f->p.num_trees, f->depth, f->lds_levels, f->p.missing, vec4_ok, nc, *csr, nullptr, 0, ColsView{});
             else if (cols)
-                hipLaunchKernelGGL((rowtile_kernel<false, decltype(mc)::value, false, false, true>), dim3((unsigned)grid), dim3(kBlock), lds,
+                hipLaunchKernelGGL((rowtile_kernel<false, decltype(mc)::value, false, false, true, NANM>), dim3((unsigned)grid), dim3(kBlock), lds,
                                    stream, f->inner, f->leaf_val, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
                                    f->p.num_trees, f->depth, f->lds_levels, f->p.missing, 0, nc, CsrView{}, nullptr, 0, *cols);
             else
-                hipLaunchKernelGGL((rowtile_kernel<decltype(wl)::value, decltype(mc)::value>), dim3((unsigned)grid), dim3(kBlock), lds,
+                hipLaunchKernelGGL((rowtile_kernel<decltype(wl)::value, decltype(mc)::value, false, false, false, NANM>), dim3((unsigned)grid), dim3(kBlock), lds,
                                    stream, f->inner, f->leaf_val, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
                                    f->p.num_trees, f->depth, f->lds_levels, f->p.missing, vec4_ok, nc, CsrView{}, nullptr, 0, ColsView{});
         });
@@ -1028,8 +1035,8 @@ static tahoe_status launch_traversal(tahoe_forest *f, float *sums, uint32_t *lea
     } else if (strategy == TAHOE_STRATEGY_DIRECT) {
         const size_t grid = (rows + kBlock - 1) / kBlock;
         const int nc = f->num_classes;
-        with_leaf_mc(leaf_out != nullptr, nc > 1, [&](auto wl, auto mc) {
-            hipLaunchKernelGGL((direct_kernel<decltype(wl)::value, decltype(mc)::value>), dim3((unsigned)grid), dim3(kBlock), 0,
+        with_leaf_mc_nanm(leaf_out != nullptr, nc > 1, f->nan_missing, [&](auto wl, auto mc, auto nanm) {
+            hipLaunchKernelGGL((direct_kernel<decltype(wl)::value, decltype(mc)::value, false, decltype(nanm)::value>), dim3((unsigned)grid), dim3(kBlock), 0,
                                stream, f->inner, f->leaf_val, f->leaf_orig, data, sums, leaf_out, sums_in, rows, f->p.num_cols,
                                f->p.num_trees, f->depth, f->p.missing, nc, nullptr, 0);
         });
@@ -1175,6 +1182,13 @@ static tahoe_status allow_float32_lds(const tahoe_forest *f)
          (e = allow_max_lds(reinterpret_cast<const void *>(&rowtile_kernel<false, false, false, false, true>), lim)) != hipSuccess ||
          (e = allow_max_lds(reinterpret_cast<const void *>(&rowtile_kernel<false, true, false, false, true>), lim)) != hipSuccess))
         return hip_status(e, "hipFuncSetAttribute(rowtile)");
+    if (rowtile_fits(f) && f->nan_missing)  // ... and the same forms under TAHOE_CREATE_NAN_MISSING, the staged ones included
+        for (const void *k : {(const void *)&rowtile_kernel<false, false, false, false, false, true>, (const void *)&rowtile_kernel<true, false, false, false, false, true>,
+                              (const void *)&rowtile_kernel<false, true, false, false, false, true>, (const void *)&rowtile_kernel<true, true, false, false, false, true>,
+                              (const void *)&rowtile_kernel<false, false, true, false, false, true>, (const void *)&rowtile_kernel<false, true, true, false, false, true>,
+                              (const void *)&rowtile_kernel<false, false, false, false, true, true>, (const void *)&rowtile_kernel<false, true, false, false, true, true>,
+                              (const void *)&rowtile_kernel<false, false, false, true, false, true>, (const void *)&rowtile_kernel<false, true, false, true, false, true>})
+            if ((e = allow_max_lds(k, lim)) != hipSuccess) return hip_status(e, "hipFuncSetAttribute(rowtile, NaN missing)");
     if (!f->has_blocks) return TAHOE_OK;
     if ((tileblock_lds_bytes(f, 128) <= lim &&
          (e = allow_max_lds_leaf([](auto wl) { return &tileblock_kernel<128, decltype(wl)::value>; }, lim)) != hipSuccess) ||
@@ -1224,22 +1238,21 @@ static tahoe_status launch_staged_dense(tahoe_forest *f, float *out, const float
 {
     const int nc = f->num_classes, S = (int)f->num_stages;
     const int vec4_ok = (f->p.num_cols % 4 == 0) && ((reinterpret_cast<uintptr_t>(data) & 15u) == 0);
-    auto with_mc = [&](auto &&fn) {
-        if (nc > 1) fn(std::true_type{});
-        else fn(std::false_type{});
+    auto with_mc = [&](auto &&fn) {  // fn(multi-class, NaN is missing)
+        with_leaf_mc(nc > 1, f->nan_missing, fn);
     };
     if (strategy == TAHOE_STRATEGY_ROWTILE) {
         const size_t grid = (rows + kTileRows - 1) / kTileRows;
         const int lds = rowtile_lds_bytes(f->p.num_cols, f->lds_levels);
-        with_mc([&](auto mc) {
-            hipLaunchKernelGGL((rowtile_kernel<false, decltype(mc)::value, false, true>), dim3((unsigned)grid), dim3(kBlock), lds, stream,
+        with_mc([&](auto mc, auto nanm) {
+            hipLaunchKernelGGL((rowtile_kernel<false, decltype(mc)::value, false, true, false, decltype(nanm)::value>), dim3((unsigned)grid), dim3(kBlock), lds, stream,
                                f->inner, f->leaf_val, f->leaf_orig, data, out, nullptr, nullptr, rows, f->p.num_cols, f->p.num_trees,
                                f->depth, f->lds_levels, f->p.missing, vec4_ok, nc, CsrView{}, f->stages_dev, S, ColsView{});
         });
     } else {
         const size_t grid = (rows + kBlock - 1) / kBlock;
-        with_mc([&](auto mc) {
-            hipLaunchKernelGGL((direct_kernel<false, decltype(mc)::value, true>), dim3((unsigned)grid), dim3(kBlock), 0, stream, f->inner,
+        with_mc([&](auto mc, auto nanm) {
+            hipLaunchKernelGGL((direct_kernel<false, decltype(mc)::value, true, decltype(nanm)::value>), dim3((unsigned)grid), dim3(kBlock), 0, stream, f->inner,
                                f->leaf_val, f->leaf_orig, data, out, nullptr, nullptr, rows, f->p.num_cols, f->p.num_trees, f->depth,
                                f->p.missing, nc, f->stages_dev, S);
         });
@@ -1319,8 +1332,9 @@ static tahoe_status create_dense(tahoe_forest **out, const tahoe_dense_node *nod
                                  int num_classes)
 {
     if (!out || !p) return fail(TAHOE_ERR_INVALID_ARG, "tahoe_forest_create: null argument");
-    if ((flags & ~(unsigned)(TAHOE_CREATE_PROB_RELAYOUT | TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS)) != 0)
+    if ((flags & ~(unsigned)(TAHOE_CREATE_PROB_RELAYOUT | TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS | TAHOE_CREATE_NAN_MISSING)) != 0)
         return fail(TAHOE_ERR_INVALID_ARG, "unknown create flags 0x%x", flags);
+    if (const tahoe_status s = check_nan_missing_flags(flags, nullptr)) return s;
     *out = nullptr;
     if (p->depth < 0 || p->depth > 30) return fail(TAHOE_ERR_INVALID_ARG, "depth must be in [0,30], got %d", p->depth);
     if (p->algo < TAHOE_ALGO_NAIVE || p->algo > TAHOE_ALGO_BATCH_TREE_REORG)
@@ -1342,8 +1356,10 @@ static tahoe_status create_dense(tahoe_forest **out, const tahoe_dense_node *nod
     f->lds_levels = std::max(0, std::min({De, kMaxLdsLevels, f->knobs.lds_levels}));
     f->top_levels = std::max(0, std::min({De - 2, kTopLevelsMax, f->knobs.lds_levels}));
     f->relayout = (flags & TAHOE_CREATE_PROB_RELAYOUT) != 0;
-    // the float32 top / block views pack fid and def_left into 10 / 16 bits: no room for the exchange bit
-    f->has_blocks = p->num_cols <= kBlockMaxCols && !f->relayout;
+    f->nan_missing = (flags & TAHOE_CREATE_NAN_MISSING) != 0;
+    // the float32 top / block views pack fid and def_left into 10 / 16 bits: no room for the exchange bit; and the kernels that
+    // walk them (TILEBLOCK, TILERING) do not implement TAHOE_CREATE_NAN_MISSING, so such a handle does not build them
+    f->has_blocks = p->num_cols <= kBlockMaxCols && !f->relayout && !f->nan_missing;
 
     // ---- normalise: heap records of the perfect depth-De tree ----
     const size_t T = (size_t)p->num_trees;
@@ -1521,7 +1537,9 @@ static tahoe_status create_dense(tahoe_forest **out, const tahoe_dense_node *nod
         return s;
     if ((s = allow_float32_lds(f.get())) || (s = qring_build(f.get(), h_inner, h_real, h_leaf))) return s;
     // no 64-row float32 tile kernel for this shape: the wide-row form
-    if (tilering_rows(f.get()) == 0 && tileblock_rows(f.get()) == 0 && (s = widef_build(f.get(), h_inner, h_real, h_leaf))) return s;
+    // (not under TAHOE_CREATE_NAN_MISSING: neither wide-row kernel implements it)
+    if (!f->nan_missing && tilering_rows(f.get()) == 0 && tileblock_rows(f.get()) == 0 && (s = widef_build(f.get(), h_inner, h_real, h_leaf)))
+        return s;
     // contributions from the caller's nodes, the Saabas records of the final (class-major, re-laid-out) layout
     return finish_create(f, flags, out, [&] { return contribs_build(f.get(), nodes); },
                          [&] { return approx_build(f.get(), nodes, h_inner, h_real); });

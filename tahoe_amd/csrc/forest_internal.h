@@ -135,6 +135,9 @@ struct tahoe_forest {
     // child is the left one, nodes carry an exchange bit.  Served by DIRECT, ROWTILE and the NARROW form of QRING.
     bool relayout = false;
     size_t relayout_swaps = 0;
+    // TAHOE_CREATE_NAN_MISSING: a NaN feature value is missing, beside the sentinel (is_missing_value<true>).  Served by DIRECT,
+    // ROWTILE and QRING on a dense handle, by every strategy of a sparse one.
+    bool nan_missing = false;
     // Profiling: one hipEvent pair per traversal launch, read back after the stream has drained.
     bool profiling = false;
     std::vector<hipEvent_t> ev_start, ev_mid, ev_stop;  // mid: between a pre-pass kernel and the walk kernel
@@ -403,6 +406,15 @@ inline void with_leaf_mc(bool leaf, bool mc, Fn &&fn)
         fn(std::false_type{}, std::false_type{});
     }
 }
+// ... x (NaN is missing: TAHOE_CREATE_NAN_MISSING): fn(wl, mc, nanm)
+template <class Fn>
+inline void with_leaf_mc_nanm(bool leaf, bool mc, bool nanm, Fn &&fn)
+{
+    with_leaf_mc(leaf, mc, [&](auto wl, auto mc_c) {
+        if (nanm) fn(wl, mc_c, std::true_type{});
+        else fn(wl, mc_c, std::false_type{});
+    });
+}
 template <class Fn>
 inline void with_leaf(bool leaf, Fn &&fn)
 {
@@ -479,6 +491,19 @@ inline tahoe_status finish_create(ForestPtr &f, unsigned flags, tahoe_forest **o
     if (s == TAHOE_OK) *out = f.release();
     return s;
 }
+// The refusals of TAHOE_CREATE_NAN_MISSING, for every create and before a device is touched.  unserved: the handle kind of a create
+// that does not take the flag at all, else null: the flag is then refused beside the explanation and partial-dependence flags,
+// whose kernels do not implement the rule
+inline tahoe_status check_nan_missing_flags(unsigned flags, const char *unserved)
+{
+    if (!(flags & TAHOE_CREATE_NAN_MISSING)) return TAHOE_OK;
+    if (unserved) return fail(TAHOE_ERR_INVALID_ARG, "TAHOE_CREATE_NAN_MISSING is not served on %s handle", unserved);
+    if (flags & (TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS | TAHOE_CREATE_CAT_CONTRIBS | TAHOE_CREATE_PARTIAL_DEPENDENCE))
+        return fail(TAHOE_ERR_INVALID_ARG, "TAHOE_CREATE_NAN_MISSING does not combine with TAHOE_CREATE_CONTRIBS, _APPROX_CONTRIBS, "
+                                           "_CAT_CONTRIBS or _PARTIAL_DEPENDENCE (flags 0x%x): those kernels do not implement the rule",
+                    flags);
+    return TAHOE_OK;
+}
 // TAHOE_OK when handle f can run `strategy` (a valid TAHOE_STRATEGY_*), else the refusal (TAHOE_ERR_UNSUPPORTED) saying why.
 // AUTO always resolves to an available strategy.
 tahoe_status strategy_available(const tahoe_forest *f, int strategy);
@@ -507,20 +532,33 @@ struct ProfilingPause {
 // on a sparse handle: the tile loader), or -1: the batch is transposed in chunks and takes the handle's own path (columns.hip)
 int columns_fused_strategy(const tahoe_forest *f, size_t rows);
 
+// Is feature value x a missing value?  The one definition, for the float32 walks and the quantise pass alike.  NANM: the handle
+// was created with TAHOE_CREATE_NAN_MISSING -- any NaN is missing beside the sentinel's band.  The two tests
+// stay two compares: !(fabsf(x - missing) > eps) would also call +inf missing under missing = +inf (inf - inf is NaN) and
+// everything missing under missing = NaN.  Without NANM this is the compare every kernel has always made.
+template <bool NANM = false>
+__device__ __forceinline__ bool is_missing_value(float x, float missing)
+{
+    const bool band = fabsf(x - missing) <= kMissingEps;
+    if constexpr (NANM) return band || x != x;
+    else return band;
+}
 // The branch rule of infer_one_tree, BaseTahoeTest.h:450-453: 1 = right child.
+template <bool NANM = false>
 __device__ __forceinline__ uint32_t go_right(float x, float thr, bool def_left, float missing)
 {
-    const bool is_missing = fabsf(x - missing) <= kMissingEps;
+    const bool is_missing = is_missing_value<NANM>(x, missing);
     const bool cond = is_missing ? !def_left : (x >= thr);
     return cond ? 1u : 0u;
 }
 // ... at a categorical split (tahoe_sparse_forest_create_cat).  pool[off] = members_left << 31 | nwords, the split's nwords
 // bitset words follow it; pool_words bounds the word read (an empty or short set may sit at the pool's end).  Below 2^24 a
 // float32 is exact and (uint32_t)x truncates, so x < 32 * nwords <=> (c >> 5) < nwords; NaN fails x >= 0.0f.
+template <bool NANM = false>
 __device__ __forceinline__ uint32_t go_right_cat(float x, const uint32_t *__restrict__ pool, uint32_t off, uint32_t pool_words,
                                                  bool def_left, float missing)
 {
-    const bool is_missing = fabsf(x - missing) <= kMissingEps;
+    const bool is_missing = is_missing_value<NANM>(x, missing);
     const bool in = x >= 0.0f && x < 16777216.0f;
     const uint32_t c = in ? (uint32_t)x : 0u;
     const uint32_t wi = off + 1u + (c >> 5);
@@ -535,9 +573,10 @@ __device__ __forceinline__ uint32_t go_right_cat(float x, const uint32_t *__rest
 constexpr int32_t kSCat = (int32_t)(1u << 29);
 constexpr int32_t kSCatFidMask = (int32_t)((1u << 29) - 1u);
 // ... on a heap record: the stored children are swapped where the exchange bit is set (Struct.h:1060-1063: cond = !cond)
+template <bool NANM = false>
 __device__ __forceinline__ uint32_t go_right_meta(float x, float thr, uint32_t meta, float missing)
 {
-    return go_right(x, thr, (meta >> 31) != 0, missing) ^ ((meta >> 30) & 1u);
+    return go_right<NANM>(x, thr, (meta >> 31) != 0, missing) ^ ((meta >> 30) & 1u);
 }
 // The argument checks of tahoe_categorical_splits, shared by the creates that take them (sparse.hip)
 tahoe_status check_cat_args(const tahoe_categorical_splits *c, int num_nodes);

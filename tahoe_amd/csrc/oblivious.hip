@@ -368,6 +368,7 @@ extern "C" tahoe_status tahoe_oblivious_forest_create_cat(tahoe_forest **out, co
     // opens tahoe_forest_predict_csr / _reserve_csr / _get_csr_plan in the same way)
     const bool staged = (flags & TAHOE_CREATE_STAGED) != 0, csr_rows = (flags & TAHOE_CREATE_CSR) != 0;
     flags &= ~(unsigned)(TAHOE_CREATE_STAGED | TAHOE_CREATE_CSR);
+    if (const tahoe_status s = check_nan_missing_flags(flags, "an oblivious")) return s;
     if (flags & ~(unsigned)(TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS | TAHOE_CREATE_INTERACTIONS |
                             TAHOE_CREATE_OBLIVIOUS_INTERVENTIONAL))
         return fail(TAHOE_ERR_INVALID_ARG, "tahoe_oblivious_forest_create_ex: flags 0x%x: only TAHOE_CREATE_CONTRIBS, "

@@ -36,6 +36,10 @@ __device__ __forceinline__ float qv_get(float4 v, int j) { return j == 0 ? v.x :
 // thread mapping, search, missing test, code store and the per-chunk flag are the same code, so the codes are the same codes.
 // A lane takes one row per load: lanes that are adjacent in rows read adjacent floats of one column, so every 64-byte line a
 // wave touches is used whole -- what the row-major reads (F * 4 bytes of each line) never managed.
+// NANM (TAHOE_CREATE_NAN_MISSING): a NaN gets the missing code and raises the chunk's "missing seen" flag,
+// as a value in the sentinel's band does (is_missing_value, forest_internal.h) -- the flag is what keeps the walk off its "no
+// missing value on this tile" forms.  A template flag behind COLS: the instantiations without it keep their argument lists and
+// instruction streams.
 template <bool COLS>
 struct QSrc { using T = const float *__restrict__; };
 template <>
@@ -57,7 +61,7 @@ static void with_cols(const float *data, const ColsView *cols, Fn &&fn)
     else fn(std::false_type{}, data);
 }
 
-template <int F, bool COLS = false>
+template <int F, bool COLS = false, bool NANM = false>
 __global__ void __launch_bounds__(kQuantThreads) quantize_kernel(typename QSrc<COLS>::T data, const float *__restrict__ tables,
                                                                  const int *__restrict__ offsets, uint16_t *__restrict__ xq,
                                                                  uint32_t *__restrict__ chunk_flags, size_t rows, int cols,
@@ -125,7 +129,7 @@ __global__ void __launch_bounds__(kQuantThreads) quantize_kernel(typename QSrc<C
             for (int u = 0; u < U; ++u) {
                 const size_t r = rb + (size_t)u * blockDim.x;
                 if (r < r1) {
-                    const bool ms = fabsf(x[u] - missing) <= kMissingEps;
+                    const bool ms = is_missing_value<NANM>(x[u], missing);
                     saw_missing |= ms;
                     const uint32_t code = ms ? kCodeMissing : (uint32_t)(cnt[u] - size[j]);
                     q_store_code(xq, r, f0 + j, cols, trs, perm, code);
@@ -141,7 +145,7 @@ __global__ void __launch_bounds__(kQuantThreads) quantize_kernel(typename QSrc<C
 // loads.  When both search trees fit the LDS budget they are resident together (one pass); a pair with an
 // oversized tree is done in two passes with one tree resident at a time, so a few large features do not
 // force the whole launch down to one feature per workgroup.
-template <bool COLS = false>
+template <bool COLS = false, bool NANM = false>
 __global__ void __launch_bounds__(kQuantPairThreads)
     quantize_pair_kernel(typename QSrc<COLS>::T data, const float *__restrict__ tables, const int *__restrict__ offsets,
                          uint16_t *__restrict__ xq, uint32_t *__restrict__ chunk_flags, size_t rows, int cols, float missing,
@@ -213,12 +217,12 @@ __global__ void __launch_bounds__(kQuantPairThreads)
                 const size_t r = rb + (size_t)u * blockDim.x;
                 if (r < r1) {
                     if (do0) {
-                        const bool ms = fabsf(xv[u].x - missing) <= kMissingEps;
+                        const bool ms = is_missing_value<NANM>(xv[u].x, missing);
                         saw_missing |= ms;
                         q_store_code(xq, r, f0, cols, trs, perm, ms ? kCodeMissing : (uint32_t)(c0[u] - size0));
                     }
                     if (do1) {
-                        const bool ms = fabsf(xv[u].y - missing) <= kMissingEps;
+                        const bool ms = is_missing_value<NANM>(xv[u].y, missing);
                         saw_missing |= ms;
                         q_store_code(xq, r, f0 + 1, cols, trs, perm, ms ? kCodeMissing : (uint32_t)(c1[u] - size1));
                     }
@@ -259,7 +263,7 @@ __global__ void bucket_index_kernel(const float *__restrict__ vals, const int *_
 // floats of a pair's image behind its two sorted runs: both start tables ((B + 2) u16 each), padded to 16 bytes
 __host__ __device__ __forceinline__ int q_bucket_tail_floats(int B) { return (B + 2 + 3) & ~3; }
 
-template <bool COLS = false>
+template <bool COLS = false, bool NANM = false>
 __global__ void __launch_bounds__(kQuantPairThreads)
     quantize_bucket_pair_kernel(typename QSrc<COLS>::T data, const float *__restrict__ bimage, const int *__restrict__ boffsets,
                                 const float4 *__restrict__ bparams,
@@ -351,7 +355,7 @@ __global__ void __launch_bounds__(kQuantPairThreads)
         for (int u = 0; u < U; ++u) {
             const size_t r = rb + (size_t)u * blockDim.x;
             if (r < r1) {
-                const bool ms0 = fabsf(xv[u].x - missing) <= kMissingEps, ms1 = fabsf(xv[u].y - missing) <= kMissingEps;
+                const bool ms0 = is_missing_value<NANM>(xv[u].x, missing), ms1 = is_missing_value<NANM>(xv[u].y, missing);
                 saw_missing |= ms0 | ms1;
                 q_store_code(xq, r, f0, cols, trs, perm, ms0 ? kCodeMissing : (uint32_t)c0[u]);
                 q_store_code(xq, r, f0 + 1, cols, trs, perm, ms1 ? kCodeMissing : (uint32_t)c1[u]);
@@ -367,7 +371,7 @@ __global__ void __launch_bounds__(kQuantPairThreads)
 // line per lane); with F = 4 * Q features per workgroup a row is read by Q adjacent lanes as float4, F = 16 uses
 // whole lines.  Tables: the Eytzinger search trees (a few hundred bytes each), descent as in quantize_kernel; the
 // trip count is per lane (adjacent lanes serve different features), a wave runs to its longest.
-template <int Q, bool COLS = false>
+template <int Q, bool COLS = false, bool NANM = false>
 __global__ void __launch_bounds__(kQuantPairThreads)
     quantize_multi_kernel(typename QSrc<COLS>::T data, const float *__restrict__ tables, const int *__restrict__ offsets,
                           uint16_t *__restrict__ xq, uint32_t *__restrict__ chunk_flags, size_t rows, int cols, float missing,
@@ -438,7 +442,7 @@ __global__ void __launch_bounds__(kQuantPairThreads)
             for (int u = 0; u < U; ++u) {
                 const size_t r = rb + (size_t)u * RPI;
                 if (r < r1) {
-                    const bool ms = fabsf(x[u] - missing) <= kMissingEps;
+                    const bool ms = is_missing_value<NANM>(x[u], missing);
                     saw_missing |= ms;
                     q_store_code(xq, r, fq + j, cols, trs, perm, ms ? kCodeMissing : (uint32_t)(cnt[u] - size[j]));
                 }
@@ -646,18 +650,26 @@ void quantize_free_tables(tahoe_qgroup &g)
     g.bparams = nullptr;
 }
 
-hipError_t quantize_allow_lds(const tahoe_forest *f)
+// the six kernels of one (COLS, NANM) pair
+template <bool COLS, bool NANM>
+static hipError_t quantize_allow_lds_of(int lds_limit)
 {
-    for (const void *k : {(const void *)&quantize_multi_kernel<8>, (const void *)&quantize_multi_kernel<4>, (const void *)&quantize_multi_kernel<2>,
-                          (const void *)&quantize_bucket_pair_kernel<>, (const void *)&quantize_pair_kernel<>,
-                          (const void *)&quantize_kernel<1>,  // ... and the same six on a column-major batch
-                          (const void *)&quantize_multi_kernel<8, true>, (const void *)&quantize_multi_kernel<4, true>,
-                          (const void *)&quantize_multi_kernel<2, true>, (const void *)&quantize_bucket_pair_kernel<true>,
-                          (const void *)&quantize_pair_kernel<true>, (const void *)&quantize_kernel<1, true>}) {
-        const hipError_t e = allow_max_lds(k, f->lds_limit);
+    for (const void *k : {(const void *)&quantize_multi_kernel<8, COLS, NANM>, (const void *)&quantize_multi_kernel<4, COLS, NANM>,
+                          (const void *)&quantize_multi_kernel<2, COLS, NANM>, (const void *)&quantize_bucket_pair_kernel<COLS, NANM>,
+                          (const void *)&quantize_pair_kernel<COLS, NANM>, (const void *)&quantize_kernel<1, COLS, NANM>}) {
+        const hipError_t e = allow_max_lds(k, lds_limit);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+hipError_t quantize_allow_lds(const tahoe_forest *f)
+{
+    hipError_t e = quantize_allow_lds_of<false, false>(f->lds_limit);
+    if (e == hipSuccess) e = quantize_allow_lds_of<true, false>(f->lds_limit);  // ... on a column-major batch
+    if (e == hipSuccess && f->nan_missing) e = quantize_allow_lds_of<false, true>(f->lds_limit);
+    if (e == hipSuccess && f->nan_missing) e = quantize_allow_lds_of<true, true>(f->lds_limit);
+    return e;
 }
 
 tahoe_status quantize_launch(tahoe_forest *f, const tahoe_qgroup &g, const float *data, size_t rows, int trs, int perm,
@@ -682,32 +694,37 @@ tahoe_status quantize_launch(tahoe_forest *f, const tahoe_qgroup &g, const float
     const size_t chunks = (rows + ((size_t)1 << cshift) - 1) >> cshift;
     const size_t qgrid = chunks * fgroups;
     if (qgrid > 0x7fffffffu) return fail(TAHOE_ERR_INVALID_ARG, "too many rows x cols for one launch");
-    with_cols(data, cols, [&](auto cols_c, auto src) {  // (src: the kernels' first argument, the row pointer or the view)
+    auto launch = [&](auto cols_c, auto nanm_c, auto src) {  // (src: the kernels' first argument, the row pointer or the view)
         constexpr bool COLS = decltype(cols_c)::value;
+        constexpr bool NANM = decltype(nanm_c)::value;
         if (multi_ok && g.multi_q == 8)
-            hipLaunchKernelGGL((quantize_multi_kernel<8, COLS>), dim3((unsigned)qgrid), dim3(kQuantPairThreads),
+            hipLaunchKernelGGL((quantize_multi_kernel<8, COLS, NANM>), dim3((unsigned)qgrid), dim3(kQuantPairThreads),
                                (size_t)32 * std::max(g.max_table, 1) * 4, stream, src, g.tables, g.offsets, q->xq, q->chunk_flags,
                                rows, f->p.num_cols, f->p.missing, std::max(g.max_table, 1), trs, cshift, perm);
         else if (multi_ok && g.multi_q == 4)
-            hipLaunchKernelGGL((quantize_multi_kernel<4, COLS>), dim3((unsigned)qgrid), dim3(kQuantPairThreads),
+            hipLaunchKernelGGL((quantize_multi_kernel<4, COLS, NANM>), dim3((unsigned)qgrid), dim3(kQuantPairThreads),
                                (size_t)16 * std::max(g.max_table, 1) * 4, stream, src, g.tables, g.offsets, q->xq, q->chunk_flags,
                                rows, f->p.num_cols, f->p.missing, std::max(g.max_table, 1), trs, cshift, perm);
         else if (multi_ok)
-            hipLaunchKernelGGL((quantize_multi_kernel<2, COLS>), dim3((unsigned)qgrid), dim3(kQuantPairThreads),
+            hipLaunchKernelGGL((quantize_multi_kernel<2, COLS, NANM>), dim3((unsigned)qgrid), dim3(kQuantPairThreads),
                                (size_t)8 * std::max(g.max_table, 1) * 4, stream, src, g.tables, g.offsets, q->xq, q->chunk_flags,
                                rows, f->p.num_cols, f->p.missing, std::max(g.max_table, 1), trs, cshift, perm);
         else if (pair_ok && g.buckets > 0)
-            hipLaunchKernelGGL(quantize_bucket_pair_kernel<COLS>, dim3((unsigned)qgrid), dim3(kQuantPairThreads),
+            hipLaunchKernelGGL((quantize_bucket_pair_kernel<COLS, NANM>), dim3((unsigned)qgrid), dim3(kQuantPairThreads),
                                (size_t)g.bucket_lds_bytes, stream, src, g.bimage, g.boffsets, g.bparams, q->xq,
                                q->chunk_flags, rows, f->p.num_cols, f->p.missing, g.buckets, trs, cshift, perm);
         else if (pair_ok)
-            hipLaunchKernelGGL(quantize_pair_kernel<COLS>, dim3((unsigned)qgrid), dim3(kQuantPairThreads),
+            hipLaunchKernelGGL((quantize_pair_kernel<COLS, NANM>), dim3((unsigned)qgrid), dim3(kQuantPairThreads),
                                (size_t)g.pair_lds_floats * 4, stream, src, g.tables, g.offsets, q->xq, q->chunk_flags, rows,
                                f->p.num_cols, f->p.missing, g.pair_lds_floats, trs, cshift, perm);
         else
-            hipLaunchKernelGGL((quantize_kernel<1, COLS>), dim3((unsigned)qgrid), dim3(kQuantThreads), (size_t)std::max(g.max_table, 1) * 4,
+            hipLaunchKernelGGL((quantize_kernel<1, COLS, NANM>), dim3((unsigned)qgrid), dim3(kQuantThreads), (size_t)std::max(g.max_table, 1) * 4,
                                stream, src, g.tables, g.offsets, q->xq, q->chunk_flags, rows, f->p.num_cols, f->p.missing,
                                std::max(g.max_table, 1), trs, cshift, perm);
+    };
+    with_cols(data, cols, [&](auto cols_c, auto src) {
+        if (f->nan_missing) launch(cols_c, std::true_type{}, src);
+        else launch(cols_c, std::false_type{}, src);
     });
     TAHOE_HIP_TRY(hipGetLastError());
     *cshift_out = cshift;

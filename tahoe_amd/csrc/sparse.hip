@@ -80,7 +80,10 @@ constexpr long long kCatMaxWords = 1 << 19;  // categories < 2^24: exact in floa
 // running sum, without resetting it, to sums[(row * S + si) * num_classes + cls] after the tree that completes stages[si]
 // trees of the class; the cursor goes back to 0 at a class end and the final per-class / per-row store is not done.
 // COLS (with TILE): the tile is staged from column-major buffers by cols_stage_tile (forest_internal.h) and `data` is not read.
-template <bool TILE, bool WRITE_LEAF, bool MC = false, bool CAT = false, bool CSR = false, bool STAGED = false, bool COLS = false>
+// NANM (TAHOE_CREATE_NAN_MISSING): both branch rules count a NaN as missing (is_missing_value<true>).  A
+// template flag, here and in sparse_top_kernel: the instantiations without it stay the code they were.
+template <bool TILE, bool WRITE_LEAF, bool MC = false, bool CAT = false, bool CSR = false, bool STAGED = false, bool COLS = false,
+          bool NANM = false>
 __global__ void __launch_bounds__(kBlock) sparse_kernel(const tahoe_sparse_node *__restrict__ nodes,
                                                         const int32_t *__restrict__ trees, const float *__restrict__ data,
                                                         float *sums, uint32_t *__restrict__ leaf_out,
@@ -143,9 +146,9 @@ __global__ void __launch_bounds__(kBlock) sparse_kernel(const tahoe_sparse_node 
                 const int fid = n.bits & (CAT ? kSCatFidMask : kSFidMask);
                 const float x = TILE ? tile[fid * kTileRows + lane] : xrow[fid];
                 if (CAT && (n.bits & kSCat))
-                    curr = (uint32_t)n.left_idx + go_right_cat(x, cat_pool, __float_as_uint(n.val), cat_words, (n.bits & kSDefLeft) != 0, missing);
+                    curr = (uint32_t)n.left_idx + go_right_cat<NANM>(x, cat_pool, __float_as_uint(n.val), cat_words, (n.bits & kSDefLeft) != 0, missing);
                 else
-                    curr = (uint32_t)n.left_idx + go_right(x, n.val, (n.bits & kSDefLeft) != 0, missing);
+                    curr = (uint32_t)n.left_idx + go_right<NANM>(x, n.val, (n.bits & kSDefLeft) != 0, missing);
             }
             if (WRITE_LEAF) {
                 if (row_ok) leaf_out[row * (size_t)num_trees + (MC ? mc_orig_tree(t, num_classes, class_trees) : t)] = curr;
@@ -203,7 +206,8 @@ constexpr int kSBatch = 4;    // trees the consumer takes per poll (K5: 16 -> 5.
 // CSR: as sparse_kernel's.  STAGED: sparse_kernel's stage cursor, in a consumer loop of its own; the walkers and the ring
 // hand-over are the same code.
 // COLS: as sparse_kernel's.
-template <int NW, bool WRITE_LEAF, bool MC = false, bool CAT = false, bool CSR = false, bool STAGED = false, bool COLS = false>
+template <int NW, bool WRITE_LEAF, bool MC = false, bool CAT = false, bool CSR = false, bool STAGED = false, bool COLS = false,
+          bool NANM = false>
 __global__ void __launch_bounds__(NW * 64) sparse_top_kernel(const uint2 *__restrict__ cnodes, const int32_t *__restrict__ ctrees,
                                                              const uint32_t *__restrict__ corig, const float *__restrict__ data,
                                                              float *sums, uint32_t *__restrict__ leaf_out,
@@ -374,8 +378,8 @@ __global__ void __launch_bounds__(NW * 64) sparse_top_kernel(const uint2 *__rest
                 pr = *reinterpret_cast<const uint4 *>(slot + left);
             else
                 pr = *reinterpret_cast<const uint4 *>(root + left);
-            const uint32_t r = (CAT && (n.y & kSCCat)) ? go_right_cat(x, cat_pool, n.x, cat_words, (n.y & 0x8000u) != 0u, missing)
-                                                       : go_right(x, __uint_as_float(n.x), (n.y & 0x8000u) != 0u, missing);
+            const uint32_t r = (CAT && (n.y & kSCCat)) ? go_right_cat<NANM>(x, cat_pool, n.x, cat_words, (n.y & 0x8000u) != 0u, missing)
+                                                       : go_right<NANM>(x, __uint_as_float(n.x), (n.y & 0x8000u) != 0u, missing);
             n = r ? make_uint2(pr.z, pr.w) : make_uint2(pr.x, pr.y);
             curr = left + r;
         }
@@ -796,21 +800,22 @@ tahoe_status sparse_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, con
         const int nw = sparse_top_waves(f);  // > 0: launch_traversal has checked strategy_available
         const int lds = (int)sparse_top_lds(f, nw);
         const int nc = f->num_classes;
-        with_leaf_mc(leaf_out != nullptr, nc > 1, [&](auto wl, auto mc) {
+        with_leaf_mc_nanm(leaf_out != nullptr, nc > 1, f->nan_missing, [&](auto wl, auto mc, auto nanm) {
+            constexpr bool NANM = decltype(nanm)::value;
             auto launch = [&](auto nw_c, auto cat) {
                 constexpr int NW = decltype(nw_c)::value;
                 if (csr)  // (predictions only: no leaf-index form)
-                    hipLaunchKernelGGL((sparse_top_kernel<NW, false, decltype(mc)::value, decltype(cat)::value, true>), dim3(grid),
+                    hipLaunchKernelGGL((sparse_top_kernel<NW, false, decltype(mc)::value, decltype(cat)::value, true, false, false, NANM>), dim3(grid),
                                        dim3(NW * 64), lds, stream, sp->cnodes, sp->ctrees, sp->corig, data, sums, leaf_out, sums_in, rows,
                                        f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, f->error_flag, nc, sp->cat_pool,
                                        sp->cat_words, *csr, nullptr, 0, ColsView{});
                 else if (cols)
-                    hipLaunchKernelGGL((sparse_top_kernel<NW, false, decltype(mc)::value, decltype(cat)::value, false, false, true>),
+                    hipLaunchKernelGGL((sparse_top_kernel<NW, false, decltype(mc)::value, decltype(cat)::value, false, false, true, NANM>),
                                        dim3(grid), dim3(NW * 64), lds, stream, sp->cnodes, sp->ctrees, sp->corig, data, sums, leaf_out,
                                        sums_in, rows, f->p.num_cols, f->p.num_trees, f->p.missing, 0, f->error_flag, nc, sp->cat_pool,
                                        sp->cat_words, CsrView{}, nullptr, 0, *cols);
                 else
-                    hipLaunchKernelGGL((sparse_top_kernel<NW, decltype(wl)::value, decltype(mc)::value, decltype(cat)::value>), dim3(grid),
+                    hipLaunchKernelGGL((sparse_top_kernel<NW, decltype(wl)::value, decltype(mc)::value, decltype(cat)::value, false, false, false, NANM>), dim3(grid),
                                        dim3(NW * 64), lds, stream, sp->cnodes, sp->ctrees, sp->corig, data, sums, leaf_out, sums_in, rows,
                                        f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, f->error_flag, nc, sp->cat_pool,
                                        sp->cat_words, CsrView{}, nullptr, 0, ColsView{});
@@ -828,25 +833,26 @@ tahoe_status sparse_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, con
     const bool tile = strategy == TAHOE_STRATEGY_ROWTILE;
     const int lds = (int)sparse_lds(f, tile);
     const int nc = f->num_classes;
-    with_leaf_mc(leaf_out != nullptr, nc > 1, [&](auto wl, auto mc) {
+    with_leaf_mc_nanm(leaf_out != nullptr, nc > 1, f->nan_missing, [&](auto wl, auto mc, auto nanm) {
+        constexpr bool NANM = decltype(nanm)::value;
         auto launch = [&](auto tile_c, auto cat) {
             if constexpr (decltype(tile_c)::value) {
                 if (csr) {  // (predictions only: no leaf-index form)
-                    hipLaunchKernelGGL((sparse_kernel<true, false, decltype(mc)::value, decltype(cat)::value, true>), dim3(grid),
+                    hipLaunchKernelGGL((sparse_kernel<true, false, decltype(mc)::value, decltype(cat)::value, true, false, false, NANM>), dim3(grid),
                                        dim3(kBlock), lds, stream, sp->nodes, sp->trees, data, sums, leaf_out, sums_in, rows,
                                        f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, nc, sp->cat_pool, sp->cat_words, *csr, nullptr, 0,
                                        ColsView{});
                     return;
                 }
                 if (cols) {
-                    hipLaunchKernelGGL((sparse_kernel<true, false, decltype(mc)::value, decltype(cat)::value, false, false, true>),
+                    hipLaunchKernelGGL((sparse_kernel<true, false, decltype(mc)::value, decltype(cat)::value, false, false, true, NANM>),
                                        dim3(grid), dim3(kBlock), lds, stream, sp->nodes, sp->trees, data, sums, leaf_out, sums_in, rows,
                                        f->p.num_cols, f->p.num_trees, f->p.missing, 0, nc, sp->cat_pool, sp->cat_words, CsrView{}, nullptr,
                                        0, *cols);
                     return;
                 }
             }
-            hipLaunchKernelGGL((sparse_kernel<decltype(tile_c)::value, decltype(wl)::value, decltype(mc)::value, decltype(cat)::value>),
+            hipLaunchKernelGGL((sparse_kernel<decltype(tile_c)::value, decltype(wl)::value, decltype(mc)::value, decltype(cat)::value, false, false, false, NANM>),
                                dim3(grid), dim3(kBlock), lds, stream, sp->nodes, sp->trees, data, sums, leaf_out, sums_in, rows,
                                f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, nc, sp->cat_pool, sp->cat_words, CsrView{}, nullptr, 0,
                                ColsView{});
@@ -862,19 +868,11 @@ tahoe_status sparse_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, con
     return TAHOE_OK;
 }
 
-// fn(mc, cat) with std::true_type / std::false_type for the handle's kind
+// fn(mc, cat, nanm) with std::true_type / std::false_type for the handle's kind
 template <class Fn>
 static void with_mc_cat(const tahoe_forest *f, Fn &&fn)
 {
-    const bool mc = f->num_classes > 1, cat = f->sp->cat_pool != nullptr;
-    if (mc) {
-        if (cat) fn(std::true_type{}, std::true_type{});
-        else fn(std::true_type{}, std::false_type{});
-    } else if (cat) {
-        fn(std::false_type{}, std::true_type{});
-    } else {
-        fn(std::false_type{}, std::false_type{});
-    }
+    with_leaf_mc_nanm(f->num_classes > 1, f->sp->cat_pool != nullptr, f->nan_missing, fn);
 }
 
 tahoe_status sparse_launch_staged(tahoe_forest *f, float *out, const float *data, size_t rows, hipStream_t stream, int strategy)
@@ -887,10 +885,11 @@ tahoe_status sparse_launch_staged(tahoe_forest *f, float *out, const float *data
         const int nw = sparse_top_waves(f);
         if (nw == 0) return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_staged: TILEBLOCK is not available on this sparse handle");
         const int lds = (int)sparse_top_lds(f, nw);
-        with_mc_cat(f, [&](auto mc, auto cat) {
+        with_mc_cat(f, [&](auto mc, auto cat, auto nanm) {
+            constexpr bool NANM = decltype(nanm)::value;
             auto launch = [&](auto nw_c) {
                 constexpr int NW = decltype(nw_c)::value;
-                hipLaunchKernelGGL((sparse_top_kernel<NW, false, decltype(mc)::value, decltype(cat)::value, false, true>), dim3(grid),
+                hipLaunchKernelGGL((sparse_top_kernel<NW, false, decltype(mc)::value, decltype(cat)::value, false, true, false, NANM>), dim3(grid),
                                    dim3(NW * 64), lds, stream, sp->cnodes, sp->ctrees, sp->corig, data, out, nullptr, nullptr, rows,
                                    f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, f->error_flag, nc, sp->cat_pool, sp->cat_words,
                                    CsrView{}, f->stages_dev, S, ColsView{});
@@ -902,9 +901,10 @@ tahoe_status sparse_launch_staged(tahoe_forest *f, float *out, const float *data
         const bool tile = strategy == TAHOE_STRATEGY_ROWTILE;
         if (tile && !sparse_tile_fits(f)) return fail(TAHOE_ERR_UNSUPPORTED, "tahoe_forest_predict_staged: no 64-row tile fits LDS");
         const int lds = (int)sparse_lds(f, tile);
-        with_mc_cat(f, [&](auto mc, auto cat) {
+        with_mc_cat(f, [&](auto mc, auto cat, auto nanm) {
+            constexpr bool NANM = decltype(nanm)::value;
             auto launch = [&](auto tile_c) {
-                hipLaunchKernelGGL((sparse_kernel<decltype(tile_c)::value, false, decltype(mc)::value, decltype(cat)::value, false, true>),
+                hipLaunchKernelGGL((sparse_kernel<decltype(tile_c)::value, false, decltype(mc)::value, decltype(cat)::value, false, true, false, NANM>),
                                    dim3(grid), dim3(kBlock), lds, stream, sp->nodes, sp->trees, data, out, nullptr, nullptr, rows,
                                    f->p.num_cols, f->p.num_trees, f->p.missing, vec4_ok, nc, sp->cat_pool, sp->cat_words, CsrView{},
                                    f->stages_dev, S, ColsView{});
@@ -920,14 +920,33 @@ tahoe_status sparse_launch_staged(tahoe_forest *f, float *out, const float *data
 tahoe_status sparse_allow_staged_lds(const tahoe_forest *f)
 {
     hipError_t e = hipSuccess;
-    with_mc_cat(f, [&](auto mc, auto cat) {
-        constexpr bool M = decltype(mc)::value, K = decltype(cat)::value;
-        if (sparse_tile_fits(f)) e = allow_max_lds(reinterpret_cast<const void *>(&sparse_kernel<true, false, M, K, false, true>), f->lds_limit);
+    with_mc_cat(f, [&](auto mc, auto cat, auto nanm) {
+        constexpr bool M = decltype(mc)::value, K = decltype(cat)::value, N = decltype(nanm)::value;
+        if (sparse_tile_fits(f))
+            e = allow_max_lds(reinterpret_cast<const void *>(&sparse_kernel<true, false, M, K, false, true, false, N>), f->lds_limit);
         if (e == hipSuccess && sparse_top_waves(f) > 0 &&
-            (e = allow_max_lds(reinterpret_cast<const void *>(&sparse_top_kernel<16, false, M, K, false, true>), f->lds_limit)) == hipSuccess)
-            e = allow_max_lds(reinterpret_cast<const void *>(&sparse_top_kernel<8, false, M, K, false, true>), f->lds_limit);
+            (e = allow_max_lds(reinterpret_cast<const void *>(&sparse_top_kernel<16, false, M, K, false, true, false, N>), f->lds_limit)) == hipSuccess)
+            e = allow_max_lds(reinterpret_cast<const void *>(&sparse_top_kernel<8, false, M, K, false, true, false, N>), f->lds_limit);
     });
     return hip_status(e, "hipFuncSetAttribute(sparse, staged)");
+}
+
+// The float32 kernels of a handle created with TAHOE_CREATE_NAN_MISSING, of its kind (classes, categorical splits): the tile
+// kernel and both tile + tops kernels, with leaf indices, from CSR and from columns (the staged ones: sparse_allow_staged_lds)
+static tahoe_status sparse_allow_nan_missing_lds(const tahoe_forest *f)
+{
+    hipError_t e = hipSuccess;
+    with_leaf_mc(f->num_classes > 1, f->sp->cat_pool != nullptr, [&](auto mc, auto cat) {
+        constexpr bool M = decltype(mc)::value, K = decltype(cat)::value;
+        for (const void *k : {(const void *)&sparse_kernel<true, false, M, K, false, false, false, true>, (const void *)&sparse_kernel<true, true, M, K, false, false, false, true>,
+                              (const void *)&sparse_kernel<true, false, M, K, true, false, false, true>, (const void *)&sparse_kernel<true, false, M, K, false, false, true, true>,
+                              (const void *)&sparse_top_kernel<16, false, M, K, false, false, false, true>, (const void *)&sparse_top_kernel<16, true, M, K, false, false, false, true>,
+                              (const void *)&sparse_top_kernel<16, false, M, K, true, false, false, true>, (const void *)&sparse_top_kernel<16, false, M, K, false, false, true, true>,
+                              (const void *)&sparse_top_kernel<8, false, M, K, false, false, false, true>, (const void *)&sparse_top_kernel<8, true, M, K, false, false, false, true>,
+                              (const void *)&sparse_top_kernel<8, false, M, K, true, false, false, true>, (const void *)&sparse_top_kernel<8, false, M, K, false, false, true, true>})
+            if (e == hipSuccess) e = allow_max_lds(k, f->lds_limit);
+    });
+    return hip_status(e, "hipFuncSetAttribute(sparse, NaN missing)");
 }
 
 void sparse_destroy(tahoe_forest *f)
@@ -1366,6 +1385,7 @@ static tahoe_status create_sparse(tahoe_forest **out, const int32_t *trees, cons
     tahoe_sstate *sp = new (std::nothrow) tahoe_sstate();
     if (!sp) return fail(TAHOE_ERR_NO_MEMORY, "tahoe_sparse_forest_create");
     f->sp = sp;
+    f->nan_missing = (flags & TAHOE_CREATE_NAN_MISSING) != 0;
     f->depth = 0;  // a placeholder value, as in sparse_forest::init (Struct.h:2332)
     f->bits_bytes = 4;
     sp->num_nodes = (size_t)p->num_nodes;
@@ -1431,6 +1451,7 @@ static tahoe_status create_sparse(tahoe_forest **out, const int32_t *trees, cons
         if ((e = allow_max_lds(kc, f->lds_limit)) != hipSuccess) return hip_status(e, "hipFuncSetAttribute(sparse, columns)");
     }
     if (p->num_cols <= 32767 && p->num_trees > 0 && (s = sparse_top_build(f.get(), trees, nodes))) return s;
+    if (f->nan_missing && (s = sparse_allow_nan_missing_lds(f.get()))) return s;
     if ((flags & TAHOE_CREATE_PARTIAL_DEPENDENCE) && (s = pd_build_sparse(f.get(), caller_trees, caller_nodes, covers))) return s;
     // contributions from the caller's trees, in the caller's numbering (contribs_build's order); Saabas deltas in the stored
     // (class-major) order
@@ -1462,9 +1483,10 @@ static tahoe_status create_sparse_checked(tahoe_forest **out, const int32_t *tre
     // tahoe_sparse_forest_create_ex comes here with cats == NULL and keeps its "any other bit" rule
     const unsigned known = TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_APPROX_CONTRIBS | TAHOE_CREATE_PARTIAL_DEPENDENCE |
                            (from_create_cat ? TAHOE_CREATE_CAT_CONTRIBS : 0u);
-    if ((flags & ~known) != 0)
+    if ((flags & ~(known | TAHOE_CREATE_NAN_MISSING)) != 0)
         return fail(TAHOE_ERR_INVALID_ARG, "unknown create flags 0x%x (a sparse handle takes TAHOE_CREATE_CONTRIBS, "
                                            "TAHOE_CREATE_APPROX_CONTRIBS and TAHOE_CREATE_PARTIAL_DEPENDENCE only)", flags);
+    if (const tahoe_status s = check_nan_missing_flags(flags, nullptr)) return s;
     if ((flags & TAHOE_CREATE_CONTRIBS) && !covers)
         return fail(TAHOE_ERR_INVALID_ARG, "TAHOE_CREATE_CONTRIBS needs covers (one per node)");
     if ((flags & TAHOE_CREATE_APPROX_CONTRIBS) && !covers)

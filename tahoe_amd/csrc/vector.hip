@@ -348,6 +348,7 @@ extern "C" tahoe_status tahoe_vector_forest_create_ex(tahoe_forest **out, const 
     const bool staged = (flags & TAHOE_CREATE_STAGED) != 0, csr_rows = (flags & TAHOE_CREATE_CSR) != 0;
     flags &= ~(unsigned)(TAHOE_CREATE_STAGED | TAHOE_CREATE_CSR);
     constexpr unsigned kShapFlags = TAHOE_CREATE_CONTRIBS | TAHOE_CREATE_INTERVENTIONAL | TAHOE_CREATE_VECTOR_INTERACTIONS;
+    if (const tahoe_status s = check_nan_missing_flags(flags, "a vector-leaf")) return s;
     if ((flags & ~(kShapFlags | TAHOE_CREATE_VECTOR_APPROX)) != 0)
         return fail(TAHOE_ERR_INVALID_ARG,
                     "unknown create flags 0x%x (a vector-leaf handle takes TAHOE_CREATE_CONTRIBS, TAHOE_CREATE_INTERVENTIONAL, "
