@@ -869,6 +869,61 @@ tahoe_status tahoe_forest_reserve_columns(tahoe_forest *f, size_t rows);
  * tile kernel does); else *chunk_rows = rows per transposed chunk and *form = the kernel form that runs on a chunk. */
 tahoe_status tahoe_forest_get_columns_plan(const tahoe_forest *f, size_t rows, int *form, size_t *chunk_rows);
 
+/* tahoe_forest_predict on a table of typed, nullable columns -- a cuDF / Arrow table as it is: no float32 copy of an integer or
+ * float64 column and no rewrite of a column with nulls is asked of the caller.
+ * A column is described in the layout of the Arrow C data interface: a data buffer, an optional validity bitmap, an offset. */
+enum {
+    TAHOE_COL_FLOAT32 = 0,
+    TAHOE_COL_FLOAT64 = 1,
+    TAHOE_COL_FLOAT16 = 2,
+    TAHOE_COL_INT8 = 3,
+    TAHOE_COL_INT16 = 4,
+    TAHOE_COL_INT32 = 5,
+    TAHOE_COL_INT64 = 6,
+    TAHOE_COL_UINT8 = 7,   /* cuDF's bool8 too; Arrow's bit-packed boolean is not served */
+    TAHOE_COL_UINT16 = 8,
+    TAHOE_COL_UINT32 = 9,
+    TAHOE_COL_UINT64 = 10
+};
+typedef struct tahoe_column {
+    const void    *data;      /* device; element i of the column is data[offset + i]; aligned to the element size */
+    const uint8_t *validity;  /* device or NULL (no nulls); bit (offset + i), LSB first, 1 = valid: Arrow's and cuDF's bitmap */
+    int64_t        offset;    /* >= 0, in elements; applies to data and to validity */
+    int32_t        type;      /* TAHOE_COL_* */
+    int32_t        reserved;  /* 0 */
+} tahoe_column;
+typedef struct tahoe_table tahoe_table;  /* opaque: num_cols descriptors on one device */
+
+/* Validates cols_host[0 .. num_cols) on the host -- an unknown type, a NULL data with rows > 0, a negative offset, a data pointer
+ * that is not aligned to its element size, a non-zero reserved field (each TAHOE_ERR_INVALID_ARG naming the column's index) and
+ * num_cols < 0 are refused before a device is touched -- then copies them to the current device with a synchronous copy and
+ * records that device.  The buffers the descriptors name stay the caller's: they must outlive the calls that read them and may be
+ * rewritten in place between calls (a captured call replays on the new contents).  tahoe_table_destroy(NULL) is a no-op. */
+tahoe_status tahoe_table_create(const tahoe_column *cols_host, int num_cols, size_t rows, tahoe_table **out);
+void         tahoe_table_destroy(tahoe_table *t);
+/* preds_dev gets, bit for bit, what tahoe_forest_predict writes for the row-major rows x num_cols matrix M, where
+ * M[r][c] = params.missing where column c has a validity buffer and bit offset + r is 0, else (float)data[offset + r] with C's
+ * conversion: round to nearest even for 64-bit integers and float64, float64 overflow to +-inf, NaN stays NaN, float32
+ * subnormal results kept (no flush), float16 and the narrow integers exact, float32 passed through bit for bit.  On every handle
+ * kind, under every strategy setting, without a create flag.  Everything else follows from the handle: with
+ * TAHOE_CREATE_NAN_MISSING a float64 / float16 NaN is missing, without it a NaN goes left.
+ *   - What lies under a null in data is never read.  No byte of validity outside [offset >> 3, (offset + rows - 1) >> 3] and no
+ *     element of data outside [offset, offset + rows) is read: no padding is assumed.
+ *   - NULL handle, table or preds_dev; a table whose num_cols differs from the handle's; a table on another device than the
+ *     handle's: TAHOE_ERR_INVALID_ARG before a device is touched.  A table of 0 rows: TAHOE_OK, nothing launched.
+ *   - Asynchronous on `stream`; uploads nothing.  Where the handle's strategy for the batch is QRING (dense, multi-class or
+ *     sparse handle), the quantise pass converts and tests the bitmap as it loads and the walk runs as ever (its ordinary kernel
+ *     form).  Every other kernel form, and every categorical, oblivious or vector-leaf handle, gets the batch converted chunk by
+ *     chunk into the row-major buffer tahoe_forest_predict_csr's fallback also uses -- at most TAHOE_CSR_CHUNK_MB MiB, counted in
+ *     device_bytes -- and runs on each chunk in turn.  TAHOE_TABLE_FUSED=0 (read at create) sends AUTO to chunks always.
+ *     tahoe_forest_get_table_plan tells, as tahoe_forest_get_columns_plan does: *chunk_rows = 0 and the walk's ordinary form, or
+ *     the rows per converted chunk and the form that runs on a chunk.  After tahoe_forest_reserve_table(rows) a call of at most
+ *     that many rows allocates nothing, leaves device_bytes unchanged and can be captured.
+ * Leaf indices, predict_accumulate, predict_host, staged output and the explanation calls keep taking row-major rows. */
+tahoe_status tahoe_forest_predict_table(tahoe_forest *f, float *preds_dev, const tahoe_table *t, void *stream);
+tahoe_status tahoe_forest_reserve_table(tahoe_forest *f, size_t rows);
+tahoe_status tahoe_forest_get_table_plan(const tahoe_forest *f, size_t rows, int *form, size_t *chunk_rows);
+
 /* Raw float32 per-row sums only (no output transform) -- the quantity tree shards exchange. */
 tahoe_status tahoe_forest_predict_raw(tahoe_forest *f, float *sums_dev, const float *data_dev, size_t rows,
                                       void *stream);

@@ -121,6 +121,27 @@ class CategoricalSplits(C.Structure):
     ]
 
 
+class Column(C.Structure):
+    """tahoe_column: one typed, nullable column in the layout of the Arrow C data interface (device buffers of the caller)."""
+
+    _fields_ = [
+        ("data", C.c_void_p),
+        ("validity", C.c_void_p),
+        ("offset", C.c_int64),
+        ("type", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+# TAHOE_COL_*, by __cuda_array_interface__ typestr (little-endian; "|" for the one-byte types) and element size
+(COL_FLOAT32, COL_FLOAT64, COL_FLOAT16, COL_INT8, COL_INT16, COL_INT32, COL_INT64, COL_UINT8, COL_UINT16, COL_UINT32,
+ COL_UINT64) = range(11)
+_COL_TYPESTR = {"<f4": COL_FLOAT32, "<f8": COL_FLOAT64, "<f2": COL_FLOAT16, "|i1": COL_INT8, "<i2": COL_INT16, "<i4": COL_INT32,
+                "<i8": COL_INT64, "|u1": COL_UINT8, "|b1": COL_UINT8, "<u2": COL_UINT16, "<u4": COL_UINT32, "<u8": COL_UINT64}
+_COL_SIZE = {COL_FLOAT32: 4, COL_FLOAT64: 8, COL_FLOAT16: 2, COL_INT8: 1, COL_INT16: 2, COL_INT32: 4, COL_INT64: 8, COL_UINT8: 1,
+             COL_UINT16: 2, COL_UINT32: 4, COL_UINT64: 8}
+
+
 class TahoeError(RuntimeError):
     def __init__(self, status: int, where: str):
         self.status = status
@@ -172,6 +193,11 @@ _PROTOS = {
     "tahoe_forest_predict_column_ptrs": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "tahoe_forest_reserve_columns": (_i, [_vp, _sz]),
     "tahoe_forest_get_columns_plan": (_i, [_vp, _sz, C.POINTER(_i), C.POINTER(_sz)]),
+    "tahoe_table_create": (_i, [_vp, _i, _sz, C.POINTER(_vp)]),
+    "tahoe_table_destroy": (None, [_vp]),
+    "tahoe_forest_predict_table": (_i, [_vp, _vp, _vp, _vp]),
+    "tahoe_forest_reserve_table": (_i, [_vp, _sz]),
+    "tahoe_forest_get_table_plan": (_i, [_vp, _sz, C.POINTER(_i), C.POINTER(_sz)]),
     "tahoe_forest_predict_raw": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "tahoe_forest_predict_accumulate": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "tahoe_forest_predict_leaf_idx": (_i, [_vp, _vp, _vp, _vp, _sz, _vp]),
@@ -434,6 +460,101 @@ def _check_nan_missing(nan_missing: bool, **others) -> None:
                          + ": those kernels do not implement the rule")
 
 
+def _torch_col_types():
+    import torch
+
+    types = {torch.float32: COL_FLOAT32, torch.float64: COL_FLOAT64, torch.float16: COL_FLOAT16, torch.int8: COL_INT8,
+             torch.int16: COL_INT16, torch.int32: COL_INT32, torch.int64: COL_INT64, torch.uint8: COL_UINT8, torch.bool: COL_UINT8}
+    for name, code in (("uint16", COL_UINT16), ("uint32", COL_UINT32), ("uint64", COL_UINT64)):
+        if hasattr(torch, name):
+            types[getattr(torch, name)] = code
+    return types
+
+
+def _column_buffer(col, what: str):
+    """(device pointer, elements, TAHOE_COL_* or None, device index or None, mask object or None) of a 1-D contiguous CUDA tensor
+    or of an object with __cuda_array_interface__; ValueError for anything else"""
+    import torch
+
+    if isinstance(col, torch.Tensor):
+        if col.dim() != 1:
+            raise ValueError(f"{what} must be 1-D, got shape {tuple(col.shape)}")
+        if not col.is_cuda or not col.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous CUDA tensor")
+        return col.data_ptr(), col.numel(), _torch_col_types().get(col.dtype), col.device.index, None
+    cai = getattr(col, "__cuda_array_interface__", None)
+    if not isinstance(cai, dict):
+        raise ValueError(f"{what} must be a CUDA tensor or have __cuda_array_interface__, got {type(col).__name__}")
+    shape = tuple(cai["shape"])
+    if len(shape) != 1:
+        raise ValueError(f"{what} must be 1-D, got shape {shape}")
+    code = _COL_TYPESTR.get(cai["typestr"])
+    strides = cai.get("strides")
+    if strides is not None and shape[0] > 1 and code is not None and tuple(strides) != (_COL_SIZE[code],):
+        raise ValueError(f"{what} must be contiguous, got strides {tuple(strides)}")
+    return int(cai["data"][0] or 0), int(shape[0]), code, None, cai.get("mask")
+
+
+class Table:
+    """A device table of typed, nullable columns (tahoe_table_create) for Forest.predict_table: a cuDF / Arrow table as it is.
+    columns: a sequence of 1-D contiguous CUDA tensors (float32 / float64 / float16, int8 .. int64, uint8, bool as uint8) or of
+    objects with __cuda_array_interface__, whose typestr gives the type (so the unsigned 16 / 32 / 64-bit types come in) and whose
+    optional `mask` entry the validity bitmap, as a cuDF Series publishes it.  validity: per column None (no nulls) or the bitmap's
+    bytes (uint8, bit offset + i of the buffer, LSB first, 1 = valid); it overrides a mask.  offsets: per column the element the
+    column starts at in its buffers (default 0); the column's rows are what follows it.  Everything malformed is a ValueError
+    raised before the library is called.  The table keeps the buffers referenced; they may be rewritten in place between
+    calls.  close() destroys it."""
+
+    def __init__(self, columns, validity=None, offsets=None):
+        import torch
+
+        columns = list(columns)
+        n = len(columns)
+        validity = [None] * n if validity is None else list(validity)
+        offsets = [0] * n if offsets is None else [int(o) for o in offsets]
+        if len(validity) != n or len(offsets) != n:
+            raise ValueError(f"{n} columns, {len(validity)} validity entries, {len(offsets)} offsets")
+        desc = (Column * max(n, 1))()
+        lengths, device = [], None
+        for c, (col, off) in enumerate(zip(columns, offsets)):
+            ptr, numel, code, dev, mask = _column_buffer(col, f"column {c}")
+            if code is None:
+                raise ValueError(f"column {c}: unsupported dtype {getattr(col, 'dtype', None) or col.__cuda_array_interface__['typestr']}")
+            if off < 0 or off > numel:
+                raise ValueError(f"column {c}: offset {off} outside its {numel} elements")
+            if dev is not None and device is not None and dev != device:
+                raise ValueError(f"column {c} is on device {dev}, earlier ones on device {device}")
+            device = dev if dev is not None else device
+            lengths.append(numel - off)
+            vptr = None
+            bitmap = validity[c] if validity[c] is not None else mask
+            if bitmap is not None:
+                vptr, vbytes, vcode, _, _ = _column_buffer(bitmap, f"validity of column {c}")
+                if vcode not in (COL_UINT8, COL_INT8):
+                    raise ValueError(f"validity of column {c} must be bytes (uint8)")
+                need = (off + lengths[-1] + 7) // 8
+                if vbytes < need:
+                    raise ValueError(f"validity of column {c}: mask of {vbytes} bytes is shorter than the {need} bytes of "
+                                     f"{off} + {lengths[-1]} bits")
+            desc[c] = Column(ptr or None, vptr, off, code, 0)
+        if len(set(lengths)) > 1:
+            raise ValueError(f"columns of unequal lengths: {sorted(set(lengths))}")
+        self.rows = lengths[0] if lengths else 0
+        self.num_cols = n
+        self.device = torch.device("cuda", device if device is not None else torch.cuda.current_device())
+        self._keep = (columns, validity)
+        self._h = _vp()
+        with torch.cuda.device(self.device):
+            _check(lib.tahoe_table_create(C.cast(desc, _vp), n, self.rows, C.byref(self._h)), "tahoe_table_create")
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h.value:
+            lib.tahoe_table_destroy(self._h)
+            self._h = _vp()
+
+    __del__ = close
+
+
 class Forest:
     """Handle on a device forest: tahoe_forest_create / predict / destroy.
 
@@ -593,6 +714,35 @@ class Forest:
         size."""
         form, chunk = _i(), _sz()
         _check(lib.tahoe_forest_get_columns_plan(self._h, rows, C.byref(form), C.byref(chunk)), "tahoe_forest_get_columns_plan")
+        return lib.tahoe_kernel_form_name(form.value).decode(), chunk.value
+
+    def predict_table(self, table, out=None, stream=None):
+        """predict on a Table of typed, nullable columns (tahoe_forest_predict_table): bit for bit what predict returns for the
+        row-major float32 matrix with `missing` at every null and (float)element elsewhere.  Uploads nothing: capturable after
+        reserve_table."""
+        import torch
+
+        if not isinstance(table, Table):
+            raise ValueError(f"table must be a tahoe_amd Table, got {type(table).__name__}")
+        if table.num_cols != self.num_cols:
+            raise ValueError(f"the table has {table.num_cols} columns, the forest {self.num_cols}")
+        if out is None:
+            out = torch.empty(self._out_shape(table.rows), dtype=torch.float32, device=table.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == self._out_shape(table.rows)
+        if table.rows == 0:
+            return out  # (an empty tensor has no address to hand on; the library launches nothing for such a table either)
+        _check(lib.tahoe_forest_predict_table(self._h, _ptr(out), table._h, _stream(stream)), "tahoe_forest_predict_table")
+        return out
+
+    def reserve_table(self, rows: int) -> None:
+        """Sizes the workspace of predict_table for tables of up to `rows` rows (tahoe_forest_reserve_table)."""
+        _check(lib.tahoe_forest_reserve_table(self._h, rows), "tahoe_forest_reserve_table")
+
+    def table_plan(self, rows: int):
+        """(kernel form name, rows per converted chunk; 0 = the quantise pass reads the table itself) of a predict_table of that
+        size."""
+        form, chunk = _i(), _sz()
+        _check(lib.tahoe_forest_get_table_plan(self._h, rows, C.byref(form), C.byref(chunk)), "tahoe_forest_get_table_plan")
         return lib.tahoe_kernel_form_name(form.value).decode(), chunk.value
 
     def predict_raw(self, data, sums=None, stream=None):

@@ -956,13 +956,17 @@ static void launch_tilering(tahoe_forest *f, float *sums, uint32_t *leaf_out, co
 // cols (optional, never with csr, predictions only): the rows come from column-major buffers and `data` is not read;
 // csr_strategy is then what columns_fused_strategy returned -- QRING (the quantise pass reads the columns), ROWTILE, or
 // TILEBLOCK on a sparse handle (the tile loader does).
+// table (optional, never with csr or cols, predictions only): the rows come from typed, nullable columns through QRING's
+// quantise pass; csr_strategy is what table_fused_strategy returned.
 static tahoe_status launch_traversal(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data,
                                      size_t rows, hipStream_t stream, const float *sums_in = nullptr, const CsrView *csr = nullptr,
-                                     int csr_strategy = 0, const ColsView *cols = nullptr)
+                                     int csr_strategy = 0, const ColsView *cols = nullptr, const TableView *table = nullptr)
 {
     if (rows == 0) return TAHOE_OK;
     DeviceGuard on_device(f->device);
-    const int strategy = (csr || cols) ? csr_strategy : resolve_strategy(f, rows);
+    const int strategy = (csr || cols || table) ? csr_strategy : resolve_strategy(f, rows);
+    if (table && (csr || cols || leaf_out || sums_in || f->ob || f->vl || strategy != TAHOE_STRATEGY_QRING))
+        return fail(TAHOE_ERR_UNSUPPORTED, "launch_traversal: no kernel of strategy %d reads a typed table", strategy);
     if (cols && (csr || leaf_out || sums_in || f->ob || f->vl ||
                  !(strategy == TAHOE_STRATEGY_QRING || strategy == TAHOE_STRATEGY_ROWTILE || (strategy == TAHOE_STRATEGY_TILEBLOCK && f->sp))))
         return fail(TAHOE_ERR_UNSUPPORTED, "launch_traversal: no kernel of strategy %d reads column-major rows", strategy);
@@ -991,10 +995,10 @@ static tahoe_status launch_traversal(tahoe_forest *f, float *sums, uint32_t *lea
         const tahoe_status vs = vector_launch(f, sums, leaf_out, data, rows, stream, strategy, csr);
         if (vs != TAHOE_OK) return vs;
     } else if (f->sp) {
-        const tahoe_status ss = sparse_launch(f, sums, leaf_out, data, rows, stream, strategy, sums_in, csr, cols);
+        const tahoe_status ss = sparse_launch(f, sums, leaf_out, data, rows, stream, strategy, sums_in, csr, cols, table);
         if (ss != TAHOE_OK) return ss;
     } else if (strategy == TAHOE_STRATEGY_QRING) {
-        const tahoe_status qs = qring_launch(f, sums, leaf_out, data, rows, stream, timed ? f->ev_mid[f->prof_count] : nullptr, sums_in, cols);
+        const tahoe_status qs = qring_launch(f, sums, leaf_out, data, rows, stream, timed ? f->ev_mid[f->prof_count] : nullptr, sums_in, cols, table);
         mid_recorded = timed;
         if (qs != TAHOE_OK) return qs;
     } else if (strategy == TAHOE_STRATEGY_TILERING && tilering_rows(f) == 0 && widef_rows(f) > 0) {
@@ -1138,6 +1142,7 @@ static tahoe_knobs read_knobs()
     k.csr_chunk_mb = num("TAHOE_CSR_CHUNK_MB", k.csr_chunk_mb);
     k.csr_fused = num("TAHOE_CSR_FUSED", k.csr_fused);
     k.columns_fused = num("TAHOE_COLUMNS_FUSED", k.columns_fused);
+    k.table_fused = num("TAHOE_TABLE_FUSED", k.table_fused);
     k.oblivious_shap_inplace = num("TAHOE_OBLIVIOUS_SHAP_INPLACE", 0) != 0;
     k.vector_shap_kb = num("TAHOE_VECTOR_SHAP_KB", k.vector_shap_kb);
     k.vector_shap_grid = num("TAHOE_VECTOR_SHAP_GRID", k.vector_shap_grid);
@@ -1204,10 +1209,10 @@ static tahoe_status allow_float32_lds(const tahoe_forest *f)
 }
 
 tahoe_status predict_rows(tahoe_forest *f, float *preds, const float *data, size_t rows, hipStream_t stream, const CsrView *csr,
-                          int csr_strategy, const ColsView *cols)
+                          int csr_strategy, const ColsView *cols, const TableView *table)
 {
     DeviceGuard on_device(f->device);
-    tahoe_status s = launch_traversal(f, preds, nullptr, data, rows, stream, nullptr, csr, csr_strategy, cols);
+    tahoe_status s = launch_traversal(f, preds, nullptr, data, rows, stream, nullptr, csr, csr_strategy, cols, table);
     if (s != TAHOE_OK) return s;
     if (f->num_classes > 1) return launch_transform_mc(f, preds, rows, stream);
     return launch_transform(preds, rows, f->p.output, f->p.num_trees, f->p.threshold, f->p.global_bias, stream);
@@ -1310,6 +1315,18 @@ int columns_fused_strategy(const tahoe_forest *f, size_t rows)
     if (s == TAHOE_STRATEGY_QRING) return (f->sp ? sparse_q_available(f) : qring_walkers(f) > 0) ? s : -1;
     if (s == TAHOE_STRATEGY_ROWTILE) return (f->sp ? sparse_tile_fits(f) : rowtile_fits(f)) ? s : -1;
     if (s == TAHOE_STRATEGY_TILEBLOCK) return f->sp && sparse_top_waves(f) > 0 ? s : -1;
+    return -1;
+}
+
+// Which kernel reads a typed table in place: QRING's quantise pass, where QRING is the strategy the same
+// handle runs on row-major rows -- forced, or AUTO's for this many rows.  No rule swaps AUTO's form.  Everything else -- the
+// float32 tile kernels too, which have no typed loader yet -- and every oblivious or vector-leaf handle gets chunks.
+int table_fused_strategy(const tahoe_forest *f, size_t rows)
+{
+    if (f->p.num_trees == 0 || f->p.num_cols == 0 || f->ob || f->vl) return -1;
+    if (f->strategy == TAHOE_STRATEGY_AUTO && f->knobs.table_fused == 0) return -1;
+    const int s = resolve_strategy(f, rows);  // (a forced strategy resolves to itself)
+    if (s == TAHOE_STRATEGY_QRING) return (f->sp ? sparse_q_available(f) : qring_walkers(f) > 0) ? s : -1;
     return -1;
 }
 

@@ -84,6 +84,7 @@ struct tahoe_knobs {
     int csr_chunk_mb = 64;        // TAHOE_CSR_CHUNK_MB: cap of tahoe_forest_predict_csr's densify chunk (at least one 64-row tile)
     int csr_fused = -1;           // TAHOE_CSR_FUSED: under AUTO, 0 = never the fused CSR tile kernels, 1 = wherever one exists, -1 = the rule
     int columns_fused = -1;       // TAHOE_COLUMNS_FUSED: under AUTO, 0 = column batches always go through row-major chunks, else the rule
+    int table_fused = -1;         // TAHOE_TABLE_FUSED: under AUTO, 0 = typed tables always go through row-major chunks, else the rule
     bool oblivious_shap_inplace = false;  // TAHOE_OBLIVIOUS_SHAP_INPLACE = 1: an oblivious handle's explanations accumulate in phi_dev
     int vector_shap_kb = 0;       // TAHOE_VECTOR_SHAP_KB = 1 / 2 / 4 / 8: force the class block of a vector-leaf handle's TreeSHAP kernels
     int pd_chunk_rows = 0;        // TAHOE_PD_CHUNK_ROWS >= 1: grid points per chunk of tahoe_forest_predict_partial_dependence (rounded up to 64s)
@@ -381,6 +382,65 @@ __device__ __forceinline__ void cols_stage_tile(float *tile, int cols, size_t ro
     }
 }
 
+// ---- typed, nullable columns (tahoe_forest_predict_table) ----
+// Column c of the batch is described by cols[c], a device copy of the caller's tahoe_column (tahoe_table_create has validated
+// every field on the host).  Passed to kernels by value.
+struct TableView {
+    const tahoe_column *cols = nullptr;
+};
+
+// Row r of column c as the float32 the walks compare: the one place that reads a validity bit or converts a column element.
+// A null is `missing` and the element under it is not read.  The bitmap is read by the byte that holds the row's bit and the data
+// by the element: nothing outside [offset >> 3, (offset + rows - 1) >> 3] of validity or [offset, offset + rows) of data is touched
+// for r in [0, rows).  The conversions are C's: round to nearest even from float64 and the 64-bit integers (a float32 subnormal
+// result is kept, the kernels run with denormals on), float64 overflow to +-inf, NaN stays NaN, everything narrower is exact.
+// Where c is wave-uniform the descriptor sits in SGPRs and the switch is a uniform branch.  N rows of one column at a time
+// (out[n] = row r[n]): one switch around N loads, not N switches -- the quantise kernels keep several rows in flight per column,
+// and a switch per load made quantize_pair_kernel spill.
+template <class T, int N>
+__device__ __forceinline__ void table_load_as(const tahoe_column &c, const size_t (&i)[N], const bool (&valid)[N], float missing,
+                                              float (&out)[N])
+{
+#pragma unroll
+    for (int n = 0; n < N; ++n) {
+        out[n] = missing;
+        if (valid[n]) out[n] = (float)static_cast<const T *>(c.data)[i[n]];
+    }
+}
+template <int N>
+__device__ __forceinline__ void table_load(const tahoe_column &c, const size_t (&r)[N], float missing, float (&out)[N])
+{
+    size_t i[N];
+    bool valid[N];
+#pragma unroll
+    for (int n = 0; n < N; ++n) {
+        i[n] = (size_t)c.offset + r[n];
+        valid[n] = true;
+        if (c.validity) valid[n] = ((c.validity[i[n] >> 3] >> (i[n] & 7u)) & 1u) != 0u;
+    }
+    switch (c.type) {
+    case TAHOE_COL_FLOAT32: table_load_as<float>(c, i, valid, missing, out); break;
+    case TAHOE_COL_FLOAT64: table_load_as<double>(c, i, valid, missing, out); break;
+    case TAHOE_COL_FLOAT16: table_load_as<_Float16>(c, i, valid, missing, out); break;
+    case TAHOE_COL_INT8: table_load_as<int8_t>(c, i, valid, missing, out); break;
+    case TAHOE_COL_INT16: table_load_as<int16_t>(c, i, valid, missing, out); break;
+    case TAHOE_COL_INT32: table_load_as<int32_t>(c, i, valid, missing, out); break;
+    case TAHOE_COL_INT64: table_load_as<int64_t>(c, i, valid, missing, out); break;
+    case TAHOE_COL_UINT8: table_load_as<uint8_t>(c, i, valid, missing, out); break;
+    case TAHOE_COL_UINT16: table_load_as<uint16_t>(c, i, valid, missing, out); break;
+    case TAHOE_COL_UINT32: table_load_as<uint32_t>(c, i, valid, missing, out); break;
+    default: table_load_as<uint64_t>(c, i, valid, missing, out); break;  // TAHOE_COL_UINT64 (create refuses every other code)
+    }
+}
+// ... one row
+__device__ __forceinline__ float table_load(const tahoe_column &c, size_t r, float missing)
+{
+    const size_t rr[1] = {r};
+    float out[1];
+    table_load<1>(c, rr, missing, out);
+    return out[0];
+}
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is per function and process-wide, not per handle: always raise it to
 // the device limit (less the kernel's static LDS), so that handles of different shapes can coexist in one process.
 inline hipError_t allow_max_lds(const void *fn, int limit)
@@ -511,8 +571,11 @@ tahoe_status strategy_available(const tahoe_forest *f, int strategy);
 // kernel of csr_strategy (a value csr_fused_strategy returned) and `data` is not read.
 // With cols the rows come from column-major buffers instead (`data` is not read) through the kernel of csr_strategy (a value
 // columns_fused_strategy returned): QRING's quantise pass or a tile kernel's column loader.
+// With table they come from typed, nullable columns through QRING's quantise pass (csr_strategy is what table_fused_strategy
+// returned: QRING).
 tahoe_status predict_rows(tahoe_forest *f, float *preds, const float *data, size_t rows, hipStream_t stream,
-                          const CsrView *csr = nullptr, int csr_strategy = 0, const ColsView *cols = nullptr);
+                          const CsrView *csr = nullptr, int csr_strategy = 0, const ColsView *cols = nullptr,
+                          const TableView *table = nullptr);
 // The strategy whose fused CSR kernel serves a batch of `rows` rows with nnz stored entries (ROWTILE, or TILEBLOCK on a sparse
 // handle; ROWTILE on an oblivious or vector-leaf handle of TAHOE_CREATE_CSR), or -1: the batch is densified in chunks and takes the handle's own path (csr.hip)
 int csr_fused_strategy(const tahoe_forest *f, size_t rows, size_t nnz);
@@ -531,6 +594,9 @@ struct ProfilingPause {
 // The strategy whose kernel reads a batch of `rows` rows straight from columns (QRING: the quantise pass; ROWTILE, or TILEBLOCK
 // on a sparse handle: the tile loader), or -1: the batch is transposed in chunks and takes the handle's own path (columns.hip)
 int columns_fused_strategy(const tahoe_forest *f, size_t rows);
+// ... straight from a typed table (tahoe_forest_predict_table): QRING where the handle runs QRING on a batch of this size (the
+// quantise pass converts as it loads), or -1: chunks (table.hip)
+int table_fused_strategy(const tahoe_forest *f, size_t rows);
 
 // Is feature value x a missing value?  The one definition, for the float32 walks and the quantise pass alike.  NANM: the handle
 // was created with TAHOE_CREATE_NAN_MISSING -- any NaN is missing beside the sentinel's band.  The two tests
@@ -630,7 +696,8 @@ int qring_walkers(const tahoe_forest *f);  // walker waves the kernel would use;
 long long qring_lds_bytes(const tahoe_forest *f);
 // mid_event (optional) is recorded between the quantise kernel and the walk kernel
 tahoe_status qring_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data, size_t rows,
-                          hipStream_t stream, hipEvent_t mid_event, const float *sums_in = nullptr, const ColsView *cols = nullptr);
+                          hipStream_t stream, hipEvent_t mid_event, const float *sums_in = nullptr, const ColsView *cols = nullptr,
+                          const TableView *table = nullptr);
 tahoe_status qring_reserve(tahoe_forest *f, size_t rows);
 int qwide_rows(const tahoe_forest *f);   // rows per tile of the wide-row form; 0 = not used
 int qwide_chains(const tahoe_forest *f); // ... and the trees a lane walks at once (1 or 3)
@@ -645,7 +712,7 @@ int qring_form(const tahoe_forest *f, size_t rows);  // TAHOE_FORM_* of the laun
 bool sparse_tile_fits(const tahoe_forest *f);
 tahoe_status sparse_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data, size_t rows,
                            hipStream_t stream, int strategy, const float *sums_in = nullptr, const CsrView *csr = nullptr,
-                           const ColsView *cols = nullptr);
+                           const ColsView *cols = nullptr, const TableView *table = nullptr);
 int sparse_top_waves(const tahoe_forest *f);
 // tahoe_forest_predict_staged on a sparse handle: the walk of `strategy` (DIRECT, ROWTILE or TILEBLOCK) with the stage stores to
 // out[rows][num_stages][num_classes]; sparse_allow_staged_lds lets those kernels take the device's LDS (set_stages calls it)

@@ -1387,7 +1387,7 @@ static void qreg_walk(const QPlan &p, tahoe_forest *f, const tahoe_qgroup &g, fl
 }
 
 tahoe_status qring_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data, size_t rows,
-                          hipStream_t stream, hipEvent_t mid_event, const float *sums_in0, const ColsView *cols)
+                          hipStream_t stream, hipEvent_t mid_event, const float *sums_in0, const ColsView *cols, const TableView *table)
 {
     tahoe_qstate *q = f->q;
     const int nwalk = qring_walkers(f);  // > 0: launch_traversal has checked strategy_available
@@ -1405,7 +1405,7 @@ tahoe_status qring_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, cons
         TAHOE_HIP_TRY(hipMemsetAsync(q->chunk_flags, 0, q->n_chunk_flags * sizeof(uint32_t), stream));
         int cshift = 0;  // rows per quantise workgroup = rows per "missing seen" flag, as a shift
         {
-            const tahoe_status qs = quantize_launch(f, g, data, rows, trs, q->code8 ? 2 : q->reg ? 1 : 0, stream, &cshift, cols);
+            const tahoe_status qs = quantize_launch(f, g, data, rows, trs, q->code8 ? 2 : q->reg ? 1 : 0, stream, &cshift, cols, table);
             if (qs != TAHOE_OK) return qs;
         }
         TAHOE_HIP_TRY(hipGetLastError());

@@ -290,7 +290,7 @@ hipError_t quantize_allow_lds(const tahoe_forest *f);  // kernels that need more
 // per-chunk "missing seen" flags; *cshift_out = log2 of the rows per flag.  cols (optional): the rows are read from column-major
 // buffers and `data` is not; the kernel form then depends on the group's tables alone (no float2 / float4 row load exists).
 tahoe_status quantize_launch(tahoe_forest *f, const tahoe_qgroup &g, const float *data, size_t rows, int trs, int perm,
-                             hipStream_t stream, int *cshift_out, const ColsView *cols = nullptr);
+                             hipStream_t stream, int *cshift_out, const ColsView *cols = nullptr, const TableView *table = nullptr);
 
 }  // namespace tahoe
 

@@ -40,10 +40,24 @@ __device__ __forceinline__ float qv_get(float4 v, int j) { return j == 0 ? v.x :
 // as a value in the sentinel's band does (is_missing_value, forest_internal.h) -- the flag is what keeps the walk off its "no
 // missing value on this tile" forms.  A template flag behind COLS: the instantiations without it keep their argument lists and
 // instruction streams.
-template <bool COLS>
+// TAB (tahoe_forest_predict_table): a third source, typed and nullable columns.  The first argument is the
+// TableView, a column is its descriptor instead of a float pointer, and a value is table_load(descriptor, r, missing): the
+// conversion and the null test sit in the load.  A null arrives as the float `missing`, so the code below it gives it the missing
+// code and raises the chunk's flag as for a sentinel in the batch.  In the one-feature, pair and bucketed-pair kernels f0 is
+// workgroup-uniform: the descriptor is a scalar load and the type switch a uniform branch; in quantize_multi_kernel adjacent lanes
+// serve different features, so descriptor and switch are per lane.  A trailing template flag: every other instantiation keeps
+// its argument list and instruction stream.
+template <bool COLS, bool TAB = false>
 struct QSrc { using T = const float *__restrict__; };
 template <>
-struct QSrc<true> { using T = ColsView; };
+struct QSrc<true, false> { using T = ColsView; };
+template <bool COLS>
+struct QSrc<COLS, true> { using T = TableView; };
+// what names one column of the source: its float pointer, or its descriptor
+template <bool TAB>
+struct QCol { using T = const float *; };
+template <>
+struct QCol<true> { using T = tahoe_column; };
 // row r of F adjacent columns (cp[j] = col(f0 + j)) as the vector the row-major load returns
 template <int F>
 __device__ __forceinline__ typename QVec<F>::T qv_cols(const float *const *cp, size_t r)
@@ -51,6 +65,25 @@ __device__ __forceinline__ typename QVec<F>::T qv_cols(const float *const *cp, s
     if constexpr (F == 1) return cp[0][r];
     else if constexpr (F == 2) return make_float2(cp[0][r], cp[1][r]);
     else return make_float4(cp[0][r], cp[1][r], cp[2][r], cp[3][r]);
+}
+// TAB: rows first, first + step, ... (clamped to last: in bounds, result unused) of F typed columns (cp[j] = the descriptor of
+// column f0 + j), the U rows of a column under one type switch (table_load, forest_internal.h)
+template <int F, int U>
+__device__ __forceinline__ void q_tab_rows(const tahoe_column *cp, size_t first, size_t step, size_t last, float missing,
+                                           typename QVec<F>::T (&dst)[U])
+{
+    size_t r[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) r[u] = min(first + (size_t)u * step, last);
+    float v[F][U];
+#pragma unroll
+    for (int j = 0; j < F; ++j) table_load<U>(cp[j], r, missing, v[j]);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        if constexpr (F == 1) dst[u] = v[0][u];
+        else if constexpr (F == 2) dst[u] = make_float2(v[0][u], v[1][u]);
+        else dst[u] = make_float4(v[0][u], v[1][u], v[2][u], v[3][u]);
+    }
 }
 // fn(cols_c, src) with std::true_type and the view when the batch is column-major, else std::false_type and the row pointer:
 // src is the kernel's first argument
@@ -61,8 +94,8 @@ static void with_cols(const float *data, const ColsView *cols, Fn &&fn)
     else fn(std::false_type{}, data);
 }
 
-template <int F, bool COLS = false, bool NANM = false>
-__global__ void __launch_bounds__(kQuantThreads) quantize_kernel(typename QSrc<COLS>::T data, const float *__restrict__ tables,
+template <int F, bool COLS = false, bool NANM = false, bool TAB = false>
+__global__ void __launch_bounds__(kQuantThreads) quantize_kernel(typename QSrc<COLS, TAB>::T data, const float *__restrict__ tables,
                                                                  const int *__restrict__ offsets, uint16_t *__restrict__ xq,
                                                                  uint32_t *__restrict__ chunk_flags, size_t rows, int cols,
                                                                  float missing, int tab_stride, int trs, int cshift, int perm)
@@ -96,19 +129,26 @@ __global__ void __launch_bounds__(kQuantThreads) quantize_kernel(typename QSrc<C
     const size_t r1 = min(rows, r0 + ((size_t)1 << cshift));
     constexpr int U = (F == 1) ? 4 : 2;  // rows per thread and iteration: U * F independent search chains
     using V = typename QVec<F>::T;
-    const float *cp[F];  // COLS: the F columns
-    if constexpr (COLS) {
+    typename QCol<TAB>::T cp[F];  // COLS / TAB: the F columns
+    if constexpr (TAB) {
+#pragma unroll
+        for (int j = 0; j < F; ++j) cp[j] = data.cols[f0 + j];
+    } else if constexpr (COLS) {
 #pragma unroll
         for (int j = 0; j < F; ++j) cp[j] = data.col(f0 + j);
     }
     bool saw_missing = false;
     for (size_t rb = r0 + threadIdx.x; rb < r1; rb += (size_t)blockDim.x * U) {
         V xv[U];
+        if constexpr (TAB) {
+            q_tab_rows<F, U>(cp, rb, blockDim.x, r1 - 1, missing, xv);
+        } else {
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const size_t r = min(rb + (size_t)u * blockDim.x, r1 - 1);  // clamped: in bounds, result unused
-            if constexpr (COLS) xv[u] = qv_cols<F>(cp, r);
-            else xv[u] = *reinterpret_cast<const V *>(data + r * (size_t)cols + f0);
+            for (int u = 0; u < U; ++u) {
+                const size_t r = min(rb + (size_t)u * blockDim.x, r1 - 1);  // clamped: in bounds, result unused
+                if constexpr (COLS) xv[u] = qv_cols<F>(cp, r);
+                else xv[u] = *reinterpret_cast<const V *>(data + r * (size_t)cols + f0);
+            }
         }
 #pragma unroll
         for (int j = 0; j < F; ++j) {
@@ -145,9 +185,9 @@ __global__ void __launch_bounds__(kQuantThreads) quantize_kernel(typename QSrc<C
 // loads.  When both search trees fit the LDS budget they are resident together (one pass); a pair with an
 // oversized tree is done in two passes with one tree resident at a time, so a few large features do not
 // force the whole launch down to one feature per workgroup.
-template <bool COLS = false, bool NANM = false>
+template <bool COLS = false, bool NANM = false, bool TAB = false>
 __global__ void __launch_bounds__(kQuantPairThreads)
-    quantize_pair_kernel(typename QSrc<COLS>::T data, const float *__restrict__ tables, const int *__restrict__ offsets,
+    quantize_pair_kernel(typename QSrc<COLS, TAB>::T data, const float *__restrict__ tables, const int *__restrict__ offsets,
                          uint16_t *__restrict__ xq, uint32_t *__restrict__ chunk_flags, size_t rows, int cols, float missing,
                          int lds_floats, int trs, int cshift, int perm)
 {
@@ -164,8 +204,11 @@ __global__ void __launch_bounds__(kQuantPairThreads)
     const size_t r0 = chunk << cshift;
     const size_t r1 = min(rows, r0 + ((size_t)1 << cshift));
     constexpr int U = 4;  // rows per thread and iteration: 8 independent search chains hide the LDS latency
-    const float *cp[2];  // COLS: the pair's columns
-    if constexpr (COLS) {
+    typename QCol<TAB>::T cp[2];  // COLS / TAB: the pair's columns
+    if constexpr (TAB) {
+        cp[0] = data.cols[f0];
+        cp[1] = data.cols[f0 + 1];
+    } else if constexpr (COLS) {
         cp[0] = data.col(f0);
         cp[1] = data.col(f0 + 1);
     }
@@ -179,27 +222,35 @@ __global__ void __launch_bounds__(kQuantPairThreads)
         stage_copy_once<kQuantPairThreads, 10>(tables + (pass ? base1 : base0), tab,
                                                (size_t)(together ? size0 + size1 : pass ? size1 : size0) * sizeof(float), (int)threadIdx.x);
         __syncthreads();
-        float2 nx[U];  // next iteration's rows, loaded one iteration ahead (see quantize_bucket_pair_kernel)
+        // next iteration's rows, loaded one iteration ahead (see quantize_bucket_pair_kernel).  Not with TAB: the second copy of
+        // both columns' type switches and the eight values held across the searches made this kernel, at 1024 threads and 128
+        // VGPRs, spill; a typed table loads an iteration's rows at its head (the bucketed form, which most forests take, prefetches).
+        float2 nx[U];
+        if constexpr (!TAB) {
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const size_t r = min(r0 + threadIdx.x + (size_t)u * blockDim.x, r1 - 1);
-            if constexpr (COLS) nx[u] = qv_cols<2>(cp, r);
-            else nx[u] = *reinterpret_cast<const float2 *>(data + r * (size_t)cols + f0);
+            for (int u = 0; u < U; ++u) {
+                const size_t r = min(r0 + threadIdx.x + (size_t)u * blockDim.x, r1 - 1);
+                if constexpr (COLS) nx[u] = qv_cols<2>(cp, r);
+                else nx[u] = *reinterpret_cast<const float2 *>(data + r * (size_t)cols + f0);
+            }
         }
         for (size_t rb = r0 + threadIdx.x; rb < r1; rb += (size_t)blockDim.x * U) {
             float2 xv[U];
             int c0[U], c1[U];
+            if constexpr (TAB) q_tab_rows<2, U>(cp, rb, blockDim.x, r1 - 1, missing, xv);
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                xv[u] = nx[u];
+                if constexpr (!TAB) xv[u] = nx[u];
                 c0[u] = 1;
                 c1[u] = 1;
             }
+            if constexpr (!TAB) {
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const size_t r = min(rb + (size_t)(U + u) * blockDim.x, r1 - 1);  // clamped: in bounds, result unused
-                if constexpr (COLS) nx[u] = qv_cols<2>(cp, r);
-                else nx[u] = *reinterpret_cast<const float2 *>(data + r * (size_t)cols + f0);
+                for (int u = 0; u < U; ++u) {
+                    const size_t r = min(rb + (size_t)(U + u) * blockDim.x, r1 - 1);  // clamped: in bounds, result unused
+                    if constexpr (COLS) nx[u] = qv_cols<2>(cp, r);
+                    else nx[u] = *reinterpret_cast<const float2 *>(data + r * (size_t)cols + f0);
+                }
             }
             // descend both trees: k <- 2k + (tab[k] <= x); k - 2^p = #{thresholds <= x} (NaN x -> 0)
             if (do0)
@@ -263,9 +314,9 @@ __global__ void bucket_index_kernel(const float *__restrict__ vals, const int *_
 // floats of a pair's image behind its two sorted runs: both start tables ((B + 2) u16 each), padded to 16 bytes
 __host__ __device__ __forceinline__ int q_bucket_tail_floats(int B) { return (B + 2 + 3) & ~3; }
 
-template <bool COLS = false, bool NANM = false>
+template <bool COLS = false, bool NANM = false, bool TAB = false>
 __global__ void __launch_bounds__(kQuantPairThreads)
-    quantize_bucket_pair_kernel(typename QSrc<COLS>::T data, const float *__restrict__ bimage, const int *__restrict__ boffsets,
+    quantize_bucket_pair_kernel(typename QSrc<COLS, TAB>::T data, const float *__restrict__ bimage, const int *__restrict__ boffsets,
                                 const float4 *__restrict__ bparams,
                                 uint16_t *__restrict__ xq, uint32_t *__restrict__ chunk_flags, size_t rows, int cols, float missing,
                                 int B, int trs, int cshift, int perm)
@@ -292,8 +343,11 @@ __global__ void __launch_bounds__(kQuantPairThreads)
     const size_t r0 = chunk << cshift;
     const size_t r1 = min(rows, r0 + ((size_t)1 << cshift));
     constexpr int U = 4;
-    const float *cp[2];  // COLS: the pair's columns
-    if constexpr (COLS) {
+    typename QCol<TAB>::T cp[2];  // COLS / TAB: the pair's columns
+    if constexpr (TAB) {
+        cp[0] = data.cols[f0];
+        cp[1] = data.cols[f0 + 1];
+    } else if constexpr (COLS) {
         cp[0] = data.col(f0);
         cp[1] = data.col(f0 + 1);
     }
@@ -301,22 +355,30 @@ __global__ void __launch_bounds__(kQuantPairThreads)
     // the rows of the next iterations are loaded before the current ones are converted: the loads (a new cache line
     // each, HBM latency) fly under the searching
     float2 nx[U];
+    if constexpr (TAB) {
+        q_tab_rows<2, U>(cp, r0 + threadIdx.x, blockDim.x, r1 - 1, missing, nx);
+    } else {
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const size_t r = min(r0 + threadIdx.x + (size_t)u * blockDim.x, r1 - 1);
-        if constexpr (COLS) nx[u] = qv_cols<2>(cp, r);
-        else nx[u] = *reinterpret_cast<const float2 *>(data + r * (size_t)cols + f0);
+        for (int u = 0; u < U; ++u) {
+            const size_t r = min(r0 + threadIdx.x + (size_t)u * blockDim.x, r1 - 1);
+            if constexpr (COLS) nx[u] = qv_cols<2>(cp, r);
+            else nx[u] = *reinterpret_cast<const float2 *>(data + r * (size_t)cols + f0);
+        }
     }
     for (size_t rb = r0 + threadIdx.x; rb < r1; rb += (size_t)blockDim.x * U) {
         float2 xv[U];
         int c0[U], c1[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) xv[u] = nx[u];
+        if constexpr (TAB) {
+            q_tab_rows<2, U>(cp, rb + (size_t)U * blockDim.x, blockDim.x, r1 - 1, missing, nx);
+        } else {
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const size_t r = min(rb + (size_t)(U + u) * blockDim.x, r1 - 1);  // clamped: in bounds, result unused
-            if constexpr (COLS) nx[u] = qv_cols<2>(cp, r);
-            else nx[u] = *reinterpret_cast<const float2 *>(data + r * (size_t)cols + f0);
+            for (int u = 0; u < U; ++u) {
+                const size_t r = min(rb + (size_t)(U + u) * blockDim.x, r1 - 1);  // clamped: in bounds, result unused
+                if constexpr (COLS) nx[u] = qv_cols<2>(cp, r);
+                else nx[u] = *reinterpret_cast<const float2 *>(data + r * (size_t)cols + f0);
+            }
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {  // positions are kept in bytes: one add forms the probe address
@@ -371,9 +433,9 @@ __global__ void __launch_bounds__(kQuantPairThreads)
 // line per lane); with F = 4 * Q features per workgroup a row is read by Q adjacent lanes as float4, F = 16 uses
 // whole lines.  Tables: the Eytzinger search trees (a few hundred bytes each), descent as in quantize_kernel; the
 // trip count is per lane (adjacent lanes serve different features), a wave runs to its longest.
-template <int Q, bool COLS = false, bool NANM = false>
+template <int Q, bool COLS = false, bool NANM = false, bool TAB = false>
 __global__ void __launch_bounds__(kQuantPairThreads)
-    quantize_multi_kernel(typename QSrc<COLS>::T data, const float *__restrict__ tables, const int *__restrict__ offsets,
+    quantize_multi_kernel(typename QSrc<COLS, TAB>::T data, const float *__restrict__ tables, const int *__restrict__ offsets,
                           uint16_t *__restrict__ xq, uint32_t *__restrict__ chunk_flags, size_t rows, int cols, float missing,
                           int tab_stride, int trs, int cshift, int perm)
 {
@@ -401,28 +463,40 @@ __global__ void __launch_bounds__(kQuantPairThreads)
     __syncthreads();
     const size_t r0 = chunk << cshift;
     const size_t r1 = min(rows, r0 + ((size_t)1 << cshift));
-    const float *cp[4];  // COLS: this thread's four columns (Q adjacent lanes serve different features: a per-lane table read)
-    if constexpr (COLS) {
+    typename QCol<TAB>::T cp[4];  // COLS / TAB: this thread's four columns (Q adjacent lanes serve different features: a per-lane
+                                  // table read, and with TAB a per-lane type switch)
+    if constexpr (TAB) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) cp[j] = data.cols[fq + j];
+    } else if constexpr (COLS) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) cp[j] = data.col(fq + j);
     }
     bool saw_missing = false;
     float4 nx[U];  // next iteration's rows, loaded one iteration ahead (see quantize_bucket_pair_kernel)
+    if constexpr (TAB) {
+        q_tab_rows<4, U>(cp, r0 + rsub, RPI, r1 - 1, missing, nx);
+    } else {
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const size_t r = min(r0 + rsub + (size_t)u * RPI, r1 - 1);
-        if constexpr (COLS) nx[u] = qv_cols<4>(cp, r);
-        else nx[u] = *reinterpret_cast<const float4 *>(data + r * (size_t)cols + fq);
+        for (int u = 0; u < U; ++u) {
+            const size_t r = min(r0 + rsub + (size_t)u * RPI, r1 - 1);
+            if constexpr (COLS) nx[u] = qv_cols<4>(cp, r);
+            else nx[u] = *reinterpret_cast<const float4 *>(data + r * (size_t)cols + fq);
+        }
     }
     for (size_t rb = r0 + rsub; rb < r1; rb += (size_t)RPI * U) {
         float4 xv[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) xv[u] = nx[u];
+        if constexpr (TAB) {
+            q_tab_rows<4, U>(cp, rb + (size_t)U * RPI, RPI, r1 - 1, missing, nx);
+        } else {
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const size_t r = min(rb + (size_t)(U + u) * RPI, r1 - 1);  // clamped: in bounds, result unused
-            if constexpr (COLS) nx[u] = qv_cols<4>(cp, r);
-            else nx[u] = *reinterpret_cast<const float4 *>(data + r * (size_t)cols + fq);
+            for (int u = 0; u < U; ++u) {
+                const size_t r = min(rb + (size_t)(U + u) * RPI, r1 - 1);  // clamped: in bounds, result unused
+                if constexpr (COLS) nx[u] = qv_cols<4>(cp, r);
+                else nx[u] = *reinterpret_cast<const float4 *>(data + r * (size_t)cols + fq);
+            }
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -650,13 +724,13 @@ void quantize_free_tables(tahoe_qgroup &g)
     g.bparams = nullptr;
 }
 
-// the six kernels of one (COLS, NANM) pair
-template <bool COLS, bool NANM>
+// the six kernels of one (COLS, NANM, TAB) triple
+template <bool COLS, bool NANM, bool TAB = false>
 static hipError_t quantize_allow_lds_of(int lds_limit)
 {
-    for (const void *k : {(const void *)&quantize_multi_kernel<8, COLS, NANM>, (const void *)&quantize_multi_kernel<4, COLS, NANM>,
-                          (const void *)&quantize_multi_kernel<2, COLS, NANM>, (const void *)&quantize_bucket_pair_kernel<COLS, NANM>,
-                          (const void *)&quantize_pair_kernel<COLS, NANM>, (const void *)&quantize_kernel<1, COLS, NANM>}) {
+    for (const void *k : {(const void *)&quantize_multi_kernel<8, COLS, NANM, TAB>, (const void *)&quantize_multi_kernel<4, COLS, NANM, TAB>,
+                          (const void *)&quantize_multi_kernel<2, COLS, NANM, TAB>, (const void *)&quantize_bucket_pair_kernel<COLS, NANM, TAB>,
+                          (const void *)&quantize_pair_kernel<COLS, NANM, TAB>, (const void *)&quantize_kernel<1, COLS, NANM, TAB>}) {
         const hipError_t e = allow_max_lds(k, lds_limit);
         if (e != hipSuccess) return e;
     }
@@ -669,16 +743,18 @@ hipError_t quantize_allow_lds(const tahoe_forest *f)
     if (e == hipSuccess) e = quantize_allow_lds_of<true, false>(f->lds_limit);  // ... on a column-major batch
     if (e == hipSuccess && f->nan_missing) e = quantize_allow_lds_of<false, true>(f->lds_limit);
     if (e == hipSuccess && f->nan_missing) e = quantize_allow_lds_of<true, true>(f->lds_limit);
+    if (e == hipSuccess) e = quantize_allow_lds_of<false, false, true>(f->lds_limit);  // ... on a typed table
+    if (e == hipSuccess && f->nan_missing) e = quantize_allow_lds_of<false, true, true>(f->lds_limit);
     return e;
 }
 
 tahoe_status quantize_launch(tahoe_forest *f, const tahoe_qgroup &g, const float *data, size_t rows, int trs, int perm,
-                             hipStream_t stream, int *cshift_out, const ColsView *cols)
+                             hipStream_t stream, int *cshift_out, const ColsView *cols, const TableView *table)
 {
     tahoe_qstate *q = f->q;
-    // (a column-major batch has no float2 / float4 row load: the form depends on the tables alone)
-    const bool pair_ok = g.pair_lds_floats > 0 && (cols || (reinterpret_cast<uintptr_t>(data) % 8) == 0);  // float2 loads
-    const bool multi_ok = g.multi_q > 0 && (cols || (reinterpret_cast<uintptr_t>(data) % 16) == 0);  // float4 loads
+    // (a column-major batch or a typed table has no float2 / float4 row load: the form depends on the tables alone)
+    const bool pair_ok = g.pair_lds_floats > 0 && (cols || table || (reinterpret_cast<uintptr_t>(data) % 8) == 0);  // float2 loads
+    const bool multi_ok = g.multi_q > 0 && (cols || table || (reinterpret_cast<uintptr_t>(data) % 16) == 0);  // float4 loads
     // Rows per quantise workgroup (2^cshift): as many as 65536 so that staging the tables is amortised, fewer when
     // that would leave the chip short of workgroups (few columns or rows), never so few that the tables outweigh
     // the rows a workgroup converts.
@@ -694,38 +770,44 @@ tahoe_status quantize_launch(tahoe_forest *f, const tahoe_qgroup &g, const float
     const size_t chunks = (rows + ((size_t)1 << cshift) - 1) >> cshift;
     const size_t qgrid = chunks * fgroups;
     if (qgrid > 0x7fffffffu) return fail(TAHOE_ERR_INVALID_ARG, "too many rows x cols for one launch");
-    auto launch = [&](auto cols_c, auto nanm_c, auto src) {  // (src: the kernels' first argument, the row pointer or the view)
+    auto launch = [&](auto cols_c, auto nanm_c, auto tab_c, auto src) {  // (src: the kernels' first argument, the row pointer or a view)
         constexpr bool COLS = decltype(cols_c)::value;
         constexpr bool NANM = decltype(nanm_c)::value;
+        constexpr bool TAB = decltype(tab_c)::value;
         if (multi_ok && g.multi_q == 8)
-            hipLaunchKernelGGL((quantize_multi_kernel<8, COLS, NANM>), dim3((unsigned)qgrid), dim3(kQuantPairThreads),
+            hipLaunchKernelGGL((quantize_multi_kernel<8, COLS, NANM, TAB>), dim3((unsigned)qgrid), dim3(kQuantPairThreads),
                                (size_t)32 * std::max(g.max_table, 1) * 4, stream, src, g.tables, g.offsets, q->xq, q->chunk_flags,
                                rows, f->p.num_cols, f->p.missing, std::max(g.max_table, 1), trs, cshift, perm);
         else if (multi_ok && g.multi_q == 4)
-            hipLaunchKernelGGL((quantize_multi_kernel<4, COLS, NANM>), dim3((unsigned)qgrid), dim3(kQuantPairThreads),
+            hipLaunchKernelGGL((quantize_multi_kernel<4, COLS, NANM, TAB>), dim3((unsigned)qgrid), dim3(kQuantPairThreads),
                                (size_t)16 * std::max(g.max_table, 1) * 4, stream, src, g.tables, g.offsets, q->xq, q->chunk_flags,
                                rows, f->p.num_cols, f->p.missing, std::max(g.max_table, 1), trs, cshift, perm);
         else if (multi_ok)
-            hipLaunchKernelGGL((quantize_multi_kernel<2, COLS, NANM>), dim3((unsigned)qgrid), dim3(kQuantPairThreads),
+            hipLaunchKernelGGL((quantize_multi_kernel<2, COLS, NANM, TAB>), dim3((unsigned)qgrid), dim3(kQuantPairThreads),
                                (size_t)8 * std::max(g.max_table, 1) * 4, stream, src, g.tables, g.offsets, q->xq, q->chunk_flags,
                                rows, f->p.num_cols, f->p.missing, std::max(g.max_table, 1), trs, cshift, perm);
         else if (pair_ok && g.buckets > 0)
-            hipLaunchKernelGGL((quantize_bucket_pair_kernel<COLS, NANM>), dim3((unsigned)qgrid), dim3(kQuantPairThreads),
+            hipLaunchKernelGGL((quantize_bucket_pair_kernel<COLS, NANM, TAB>), dim3((unsigned)qgrid), dim3(kQuantPairThreads),
                                (size_t)g.bucket_lds_bytes, stream, src, g.bimage, g.boffsets, g.bparams, q->xq,
                                q->chunk_flags, rows, f->p.num_cols, f->p.missing, g.buckets, trs, cshift, perm);
         else if (pair_ok)
-            hipLaunchKernelGGL((quantize_pair_kernel<COLS, NANM>), dim3((unsigned)qgrid), dim3(kQuantPairThreads),
+            hipLaunchKernelGGL((quantize_pair_kernel<COLS, NANM, TAB>), dim3((unsigned)qgrid), dim3(kQuantPairThreads),
                                (size_t)g.pair_lds_floats * 4, stream, src, g.tables, g.offsets, q->xq, q->chunk_flags, rows,
                                f->p.num_cols, f->p.missing, g.pair_lds_floats, trs, cshift, perm);
         else
-            hipLaunchKernelGGL((quantize_kernel<1, COLS, NANM>), dim3((unsigned)qgrid), dim3(kQuantThreads), (size_t)std::max(g.max_table, 1) * 4,
+            hipLaunchKernelGGL((quantize_kernel<1, COLS, NANM, TAB>), dim3((unsigned)qgrid), dim3(kQuantThreads), (size_t)std::max(g.max_table, 1) * 4,
                                stream, src, g.tables, g.offsets, q->xq, q->chunk_flags, rows, f->p.num_cols, f->p.missing,
                                std::max(g.max_table, 1), trs, cshift, perm);
     };
-    with_cols(data, cols, [&](auto cols_c, auto src) {
-        if (f->nan_missing) launch(cols_c, std::true_type{}, src);
-        else launch(cols_c, std::false_type{}, src);
-    });
+    if (table) {
+        if (f->nan_missing) launch(std::false_type{}, std::true_type{}, std::true_type{}, *table);
+        else launch(std::false_type{}, std::false_type{}, std::true_type{}, *table);
+    } else {
+        with_cols(data, cols, [&](auto cols_c, auto src) {
+            if (f->nan_missing) launch(cols_c, std::true_type{}, std::false_type{}, src);
+            else launch(cols_c, std::false_type{}, std::false_type{}, src);
+        });
+    }
     TAHOE_HIP_TRY(hipGetLastError());
     *cshift_out = cshift;
     return TAHOE_OK;

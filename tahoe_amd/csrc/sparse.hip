@@ -742,7 +742,7 @@ static void sparse_q_launch_form(tahoe_forest *f, const tahoe_qgroup &g, float *
 
 // quantise + walk per tree group, in stream order; the tile plan of the dense region form (qreg_plan)
 static tahoe_status sparse_q_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data, size_t rows,
-                                    hipStream_t stream, const float *sums_in0, const ColsView *cols)
+                                    hipStream_t stream, const float *sums_in0, const ColsView *cols, const TableView *table)
 {
     tahoe_qstate *q = f->q;
     const tahoe_status rs = qring_reserve(f, rows);  // no-op unless this batch is larger than any before
@@ -754,7 +754,7 @@ static tahoe_status sparse_q_launch(tahoe_forest *f, float *sums, uint32_t *leaf
     for (const tahoe_qgroup &g : q->groups) {
         TAHOE_HIP_TRY(hipMemsetAsync(q->chunk_flags, 0, q->n_chunk_flags * sizeof(uint32_t), stream));
         int cshift = 0;
-        const tahoe_status qs = quantize_launch(f, g, data, rows, 6, 1, stream, &cshift, cols);
+        const tahoe_status qs = quantize_launch(f, g, data, rows, 6, 1, stream, &cshift, cols, table);
         if (qs != TAHOE_OK) return qs;
         const float *sums_in = first ? sums_in0 : sums;  // later groups continue the running float32 sums
         if (rows3 > 0) sparse_q_launch_form<kReg3Walkers, 3, kReg3Ring>(f, g, sums, sums_in, leaf_out, 0, rows3, stream, cshift);
@@ -790,12 +790,13 @@ static long long sparse_lds(const tahoe_forest *f, bool tile)
 bool sparse_tile_fits(const tahoe_forest *f) { return f->p.num_cols >= 1 && sparse_lds(f, true) <= f->lds_limit; }
 
 tahoe_status sparse_launch(tahoe_forest *f, float *sums, uint32_t *leaf_out, const float *data, size_t rows,
-                           hipStream_t stream, int strategy, const float *sums_in, const CsrView *csr, const ColsView *cols)
+                           hipStream_t stream, int strategy, const float *sums_in, const CsrView *csr, const ColsView *cols,
+                           const TableView *table)
 {
     const tahoe_sstate *sp = f->sp;
     const unsigned grid = (unsigned)((rows + kTileRows - 1) / kTileRows);
     const int vec4_ok = (f->p.num_cols % 4 == 0) && ((reinterpret_cast<uintptr_t>(data) & 15u) == 0);
-    if (strategy == TAHOE_STRATEGY_QRING) return sparse_q_launch(f, sums, leaf_out, data, rows, stream, sums_in, cols);
+    if (strategy == TAHOE_STRATEGY_QRING) return sparse_q_launch(f, sums, leaf_out, data, rows, stream, sums_in, cols, table);
     if (strategy == TAHOE_STRATEGY_TILEBLOCK) {
         const int nw = sparse_top_waves(f);  // > 0: launch_traversal has checked strategy_available
         const int lds = (int)sparse_top_lds(f, nw);
